@@ -1,7 +1,13 @@
 """bench.py -- EnCodec codec-tokens/sec of the 100-step D3PM sampler on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `whole_step_tflops`).
+--full adds everything else this script measures, as before: HIP-event brackets around the GEMM launches of the timed region
+(`roofline`, `kernel_classes`, `launches_per_iteration`), the single-utterance latencies, the NAR stage, the n_q = 8
+extension, the fp8 fast path, the VCTK config and the CPU baseline (each still switched off by its --no-* / --cpu-steps 0).
+--dump-outputs DIR writes the ids of the last timed step (what generate_audio returns) to DIR/ids.npy as float32.
 
 With --gpus N > 1 and no torchrun environment (no WORLD_SIZE) the script starts the N ranks itself: a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` of this same command line, launched
@@ -62,7 +68,20 @@ def parse():
     ap.add_argument("--profile-iters", type=int, default=0,
                     help="PROFILING ONLY: run this many diffusion iterations instead of all 99 (the JSON line is then "
                          "marked invalid_for_headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take every measurement beside the headline: kernel-class events in the timed region, latency, "
+                         "NAR, n_q = 8, fp8, VCTK and the CPU baseline (the --no-* flags and --cpu-steps apply only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the ids of the last one to DIR/ids.npy (float32, [global batch, canvas])")
     return ap.parse_args()
+
+
+def dump_outputs(directory, ids):
+    """What the timed path hands its caller in the last timed step: the int64 id grid, stored as float32 (ids < 2^24 are
+    exact) so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "ids.npy"), ids.detach().cpu().numpy().astype(np.float32))
 
 
 def algorithmic_flops_per_step(cfg, batch):
@@ -400,6 +419,8 @@ def stand_in_main(args, rank, world):
     assert out.shape == (batch * world, cfg.canvas)
     single = StandInModel(cfg).generate_audio(texts, proms, seed=123 + args.warmup + args.steps - 1).reshape(batch * world, -1)
     assert torch.equal(out, single.long()), "gathered grid differs from the one-rank grid"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     if rank == 0:
         print(json.dumps({"metric": "EnCodec codec-tokens/sec (whole node), 100-step D3PM", "value": batch * world * cfg.n_frames * args.steps / elapsed,
                           "unit": "codec_tokens/s", "n_gpus": world, "n_ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup,
@@ -531,16 +552,17 @@ def main():
         note(f"warmup {i + 1}/{args.warmup} done")
     fence()
     iters = args.profile_iters or (cfg.timesteps - 1)
-    if not args.no_kernel_events:     # every kernel class, launches inside the diffusion loop only, each 16th iteration
+    if args.full and not args.no_kernel_events:     # every kernel class, launches inside the diffusion loop only, each 16th iteration
         _hip.prof_enable(_hip.K_ALL, args.steps * (iters // 16 + 2) * (cfg.n_layers * 14 + 4) + 64)
     t0 = time.perf_counter()
     for i in range(args.steps):
         out = step(args.warmup + i)
     fence()
     elapsed = time.perf_counter() - t0
-    per_class = {name: _hip.prof_read_class(k) for name, k in CLASSES}
-    launches, gemm_ms, gemm_flops, gemm_bytes = per_class["gemm"]
-    _hip.prof_disable()
+    if args.full:
+        per_class = {name: _hip.prof_read_class(k) for name, k in CLASSES}
+        launches, gemm_ms, gemm_flops, gemm_bytes = per_class["gemm"]
+        _hip.prof_disable()
     elapsed, ranks_seen = reduce_over_ranks(elapsed, world, dev if args.backend == "nccl" else torch.device("cpu"))
     assert out.shape == (batch * world, cfg.canvas)
 
@@ -563,60 +585,63 @@ def main():
     if args.profile_iters:
         result["invalid_for_headline"] = result.get("invalid_for_headline", "") + f" profiling run: {iters} of {cfg.timesteps - 1} diffusion iterations"
     if rank == 0:
-        key = args.dtype
-        achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-        traffic, traffic_src = pmc_traffic("gemm") if args.config == "libritts" and batch == 32 else (None, "PMC passes cover the headline workload only")
-        result["roofline"] = {"bound": "mfma", "kernel": "gemm_mfma_* (every projection / MLP / final GEMM launch inside the diffusion loop -- the "
-                              "largest class; with the LayerNorms folded into the projections (d3pm_tuning.ln_fold, the default) that is 37 launches "
-                              "per iteration and there is no stand-alone LayerNorm or row-panel launch left: the `layernorm` row of kernel_classes is "
-                              "the token-embedding gather and the per-iteration fc1 FiLM fold)",
-                              "achieved": achieved, "peak": MFMA_PEAK_TFLOPS[key], "unit": "TFLOP/s",
-                              "frac": achieved / MFMA_PEAK_TFLOPS[key], "traffic": traffic,
-                              "traffic_unit": "bytes/launch (L2 fabric-side, rocprofv3 PMC)", "traffic_source": traffic_src,
-                              "build_id": build_id(),
-                              "algorithmic_bytes_per_launch": gemm_bytes / max(launches, 1),
-                              "algorithmic_flops_per_launch": gemm_flops / max(launches, 1),
-                              "launches_timed": launches, "avg_launch_us": gemm_ms * 1e3 / max(launches, 1),
-                              "timing": "HIP event pairs on the launch stream around every launch of each 16th diffusion "
-                                        "iteration of the timed region (bracketing all launches costs ~6 % of the step)"}
-        result["kernel_classes"] = class_table(per_class, key)
-        result["launches_per_iteration"] = {name: round(v[0] / max(args.steps * len([t for t in range(iters, 0, -1) if t % 16 == 0]), 1), 2)
-                                            for name, v in per_class.items() if v[0]}
         whole = algorithmic_flops_per_step(cfg, batch) * iters / (cfg.timesteps - 1) / (ms_per_step * 1e-3) / 1e12
         result["whole_step_tflops"] = whole
-        if not args.no_latency:
-            note(f"timed region {elapsed:.2f}s; measuring single-utterance latency")
-            # third form: one utterance run as a shard of a 32-utterance logical batch (global_batch = 32: it takes the 32 x 32 x 16
-            # attention kernels of the big batch, so that its ids are those of the unsplit batch) -- what rank-count independence costs
-            for key, use_graph, gb in (("p50_utterance_latency_ms", False, None), ("p50_utterance_latency_graph_replay_ms", True, None),
-                                       ("p50_utterance_latency_as_shard_of_32_ms", False, 32)):
-                lat = []
-                for i in range(6):       # the first two calls of the graph mode warm up and capture
-                    torch.cuda.synchronize()
-                    t1 = time.perf_counter()
-                    model.generate_audio(texts[:1], proms[:1], seed=i, graph=use_graph, global_batch=gb)
-                    torch.cuda.synchronize()
-                    lat.append((time.perf_counter() - t1) * 1e3)
-                result[key] = statistics.median(lat[2:])
-        if not args.no_nar and args.config == "libritts":
-            result["nar_levels_1to7"] = nar_stage(dev, dtype, batch, cfg, out[:batch])
-            d3pm_s = ms_per_step * 1e-3
-            result["nar_levels_1to7"]["all_8_levels_codec_tokens_per_s"] = (
-                8 * batch * cfg.n_frames / (d3pm_s + result["nar_levels_1to7"]["seconds_per_batch"]))
-        if world == 1 and not args.no_nq8 and args.config == "libritts" and dtype != torch.float32:
-            note("measuring the n_q = 8 extension")
-            result["n_q8_extension"] = n_q8_extension(dev, dtype, batch, texts, proms)
-        if world == 1 and not args.no_fp8 and args.config == "libritts" and dtype != torch.float32:
-            note("measuring the fp8 / 50-step fast path")
-            result["fp8_fast_path"] = fp8_fast_path(dev, dtype, batch, cfg, sd32, texts, proms)
-        if world == 1 and not args.no_vctk and args.config == "libritts" and dtype != torch.float32:
-            note("measuring the VCTK long-prompt config")
-            result["vctk_long_prompt"] = vctk_long_prompt(dev, dtype, batch, args.dtype)
-        if world == 1 and args.cpu_steps > 0:
-            note("timing the CPU port of the reference sampler")
-            cpu_texts, cpu_proms = synth.make_inputs(cfg, 1, 1)
-            result["cpu_baseline"] = cpu_baseline(cfg, sd32, cpu_texts, cpu_proms, args.cpu_steps)
-            result["speedup_vs_cpu_baseline"] = result["value"] / result["cpu_baseline"]["value"]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out)
+        if args.full:
+            key = args.dtype
+            achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+            traffic, traffic_src = pmc_traffic("gemm") if args.config == "libritts" and batch == 32 else (None, "PMC passes cover the headline workload only")
+            result["roofline"] = {"bound": "mfma", "kernel": "gemm_mfma_* (every projection / MLP / final GEMM launch inside the diffusion loop -- the "
+                                  "largest class; with the LayerNorms folded into the projections (d3pm_tuning.ln_fold, the default) that is 37 launches "
+                                  "per iteration and there is no stand-alone LayerNorm or row-panel launch left: the `layernorm` row of kernel_classes is "
+                                  "the token-embedding gather and the per-iteration fc1 FiLM fold)",
+                                  "achieved": achieved, "peak": MFMA_PEAK_TFLOPS[key], "unit": "TFLOP/s",
+                                  "frac": achieved / MFMA_PEAK_TFLOPS[key], "traffic": traffic,
+                                  "traffic_unit": "bytes/launch (L2 fabric-side, rocprofv3 PMC)", "traffic_source": traffic_src,
+                                  "build_id": build_id(),
+                                  "algorithmic_bytes_per_launch": gemm_bytes / max(launches, 1),
+                                  "algorithmic_flops_per_launch": gemm_flops / max(launches, 1),
+                                  "launches_timed": launches, "avg_launch_us": gemm_ms * 1e3 / max(launches, 1),
+                                  "timing": "HIP event pairs on the launch stream around every launch of each 16th diffusion "
+                                            "iteration of the timed region (bracketing all launches costs ~6 % of the step)"}
+            result["kernel_classes"] = class_table(per_class, key)
+            result["launches_per_iteration"] = {name: round(v[0] / max(args.steps * len([t for t in range(iters, 0, -1) if t % 16 == 0]), 1), 2)
+                                                for name, v in per_class.items() if v[0]}
+            if not args.no_latency:
+                note(f"timed region {elapsed:.2f}s; measuring single-utterance latency")
+                # third form: one utterance run as a shard of a 32-utterance logical batch (global_batch = 32: it takes the 32 x 32 x 16
+                # attention kernels of the big batch, so that its ids are those of the unsplit batch) -- what rank-count independence costs
+                for key, use_graph, gb in (("p50_utterance_latency_ms", False, None), ("p50_utterance_latency_graph_replay_ms", True, None),
+                                           ("p50_utterance_latency_as_shard_of_32_ms", False, 32)):
+                    lat = []
+                    for i in range(6):       # the first two calls of the graph mode warm up and capture
+                        torch.cuda.synchronize()
+                        t1 = time.perf_counter()
+                        model.generate_audio(texts[:1], proms[:1], seed=i, graph=use_graph, global_batch=gb)
+                        torch.cuda.synchronize()
+                        lat.append((time.perf_counter() - t1) * 1e3)
+                    result[key] = statistics.median(lat[2:])
+            if not args.no_nar and args.config == "libritts":
+                result["nar_levels_1to7"] = nar_stage(dev, dtype, batch, cfg, out[:batch])
+                d3pm_s = ms_per_step * 1e-3
+                result["nar_levels_1to7"]["all_8_levels_codec_tokens_per_s"] = (
+                    8 * batch * cfg.n_frames / (d3pm_s + result["nar_levels_1to7"]["seconds_per_batch"]))
+            if world == 1 and not args.no_nq8 and args.config == "libritts" and dtype != torch.float32:
+                note("measuring the n_q = 8 extension")
+                result["n_q8_extension"] = n_q8_extension(dev, dtype, batch, texts, proms)
+            if world == 1 and not args.no_fp8 and args.config == "libritts" and dtype != torch.float32:
+                note("measuring the fp8 / 50-step fast path")
+                result["fp8_fast_path"] = fp8_fast_path(dev, dtype, batch, cfg, sd32, texts, proms)
+            if world == 1 and not args.no_vctk and args.config == "libritts" and dtype != torch.float32:
+                note("measuring the VCTK long-prompt config")
+                result["vctk_long_prompt"] = vctk_long_prompt(dev, dtype, batch, args.dtype)
+            if world == 1 and args.cpu_steps > 0:
+                note("timing the CPU port of the reference sampler")
+                cpu_texts, cpu_proms = synth.make_inputs(cfg, 1, 1)
+                result["cpu_baseline"] = cpu_baseline(cfg, sd32, cpu_texts, cpu_proms, args.cpu_steps)
+                result["speedup_vs_cpu_baseline"] = result["value"] / result["cpu_baseline"]["value"]
         print(json.dumps(result), flush=True)
     if world > 1:
         torch.distributed.barrier()          # rank 0 may still be timing its extras: leave together

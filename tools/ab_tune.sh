@@ -1,9 +1,9 @@
 # A/B of d3pm_tuning fields on the headline workload: bash tools/ab_tune.sh "row_panel=0" "row_panel=3" ...   (one bench line per arm)
-: "${GRAFT_REPO_ROOT:=$(cd "$(dirname "$0")/.." && pwd)}"; cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
+cd "$(dirname "$0")/.."; mkdir -p "${OUT:=out}"     # OUT: where the per-arm JSON lines go
 for arm in "$@"; do
   tag=$(echo "$arm" | tr ',=' '__')
-  timeout -k 10 250 python bench.py --steps 3 --warmup 1 --cpu-steps 0 --no-latency --no-nar --no-fp8 --tune "$arm" > gpurun_out/ab_$tag.json 2> gpurun_out/ab_$tag.err || exit 1
-  python - "$arm" gpurun_out/ab_$tag.json <<'PY'
+  timeout -k 10 250 python bench.py --full --steps 3 --warmup 1 --cpu-steps 0 --no-latency --no-nar --no-fp8 --tune "$arm" > $OUT/ab_$tag.json 2> $OUT/ab_$tag.err || exit 1
+  python - "$arm" $OUT/ab_$tag.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))
 kc = d.get("kernel_classes", {})
