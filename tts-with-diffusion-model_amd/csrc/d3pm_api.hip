@@ -94,6 +94,9 @@ static int run_linear(const Ctx& cx, int dtype, LinearArgs a, uint32_t flags, hi
               es * (static_cast<double>(a.M) * a.K + static_cast<double>(a.N) * a.K +
                     static_cast<double>(a.M) * a.N * (1 + (a.R1 ? 1 : 0) + (a.R2 ? 1 : 0))));
   if (!(flags & D3PM_FLAG_FORCE_GENERIC) && mfma_linear_supported(dtype, a)) return mfma_linear(dtype, a, s);
+  // the generic family has no folded-LayerNorm epilogues: it would ignore the moments (read stale ones, or leave them unwritten)
+  D3PM_REQUIRE(!a.fold_s && !a.stats_out && !a.moment_quads, D3PM_E_SHAPE, "folded-LayerNorm projection %d x %d x %d needs the MFMA family",
+               a.M, a.N, a.K);
   return generic_linear(dtype, a, s);
 }
 #ifdef D3PM_ABLATIONS
@@ -224,7 +227,7 @@ static char* at(void* p, size_t elems, size_t es) { return static_cast<char*>(p)
 //   fc1 + GELU <- x [norm3 + FiLM(t) folded], fc2 + x, frame mask (+ moments) }: ten launches per block, none of them a LayerNorm.
 static int denoiser_blocks_folded(const d3pm_shape& sh, const d3pm_weights& w, int batch, const int32_t* x_t, const uint8_t* frame_mask,
                                   int t, const void* film, const void* kv_text, const void* kv_prompt, const Workspace& ws, int layers,
-                                  hipStream_t s, bool prepared) {
+                                  hipStream_t s, bool prepared, bool quads) {
   const int dt = sh.dtype, d = sh.d_model, H = sh.n_heads, hd = d / H, T = sh.canvas, n = batch * T;
   const Ctx cx(sh.tuning);
   const size_t es = dtype_size(dt);
@@ -235,7 +238,7 @@ static int denoiser_blocks_folded(const d3pm_shape& sh, const d3pm_weights& w, i
   if (!prepared) {      // (inside the loop the previous iteration's sampler launch has done both: posterior_sample_prep)
     {
       ProfScope p(cx, D3PM_K_LN, s, 0.0, es * static_cast<double>(n) * d * 2.0);
-      D3PM_TRY(embed_tokens_stats(dt, e, ws.stats, s));
+      D3PM_TRY(embed_tokens_stats(dt, e, ws.stats, quads, s));
     }
     {   // fc1 of every block under norm3 + FiLM(t): the weights this evaluation's fc1 launches read
       ProfScope p(cx, D3PM_K_LN, s, 0.0, es * 2.0 * layers * 4.0 * d * d);
@@ -246,7 +249,7 @@ static int denoiser_blocks_folded(const d3pm_shape& sh, const d3pm_weights& w, i
   auto folded = [&](const void* Wf, const float* fs, const float* fb, void* Y, int N, int act) -> int {
     LinearArgs g;
     g.X = ws.x; g.ldx = d; g.W = Wf; g.Y = Y; g.ldy = N; g.M = n; g.N = N; g.K = d; g.act = act;
-    g.fold_s = fs; g.fold_b = fb; g.stats_in = ws.stats; g.fold_eps = 1e-6f;
+    g.fold_s = fs; g.fold_b = fb; g.stats_in = ws.stats; g.fold_eps = 1e-6f; g.moment_quads = quads;
     D3PM_REQUIRE(mfma_linear_supported(dt, g), D3PM_E_SHAPE, "folded LayerNorm projection %d x %d x %d not supported", n, N, d);
     return run_linear(cx, dt, g, 0, s);
   };
@@ -261,7 +264,7 @@ static int denoiser_blocks_folded(const d3pm_shape& sh, const d3pm_weights& w, i
     D3PM_TRY(run_attention(cx, dt, a, 0, s));
     LinearArgs g;
     g.X = ws.att; g.ldx = d; g.W = b.attn_out_w; g.bias = b.attn_out_b; g.Y = ws.x; g.ldy = d;
-    g.R1 = ws.x; g.ldr = d; g.M = n; g.N = d; g.K = d; g.stats_out = ws.stats;
+    g.R1 = ws.x; g.ldr = d; g.M = n; g.N = d; g.K = d; g.stats_out = ws.stats; g.moment_quads = quads;
     D3PM_TRY(run_linear(cx, dt, g, 0, s));
     // ---- cross-attention: q_text | q_prompt are the two halves of ONE [n][2d] projection of x (the same q rows under norm2 / norm22)
     D3PM_TRY(folded(f.q2_w, f.q2_s, f.q2_b, ws.qkv, 2 * d, ACT_NONE));
@@ -277,7 +280,7 @@ static int denoiser_blocks_folded(const d3pm_shape& sh, const d3pm_weights& w, i
     // ---- x = (x + o_text) + o_prompt, rounded at each add like the eager sum ----
     g = LinearArgs();
     g.X = ws.att; g.ldx = d; g.W = b.cross_out_w; g.bias = b.cross_out_b; g.Y = ws.x; g.ldy = d; g.R1 = ws.x; g.ldr = d;
-    g.M = n; g.N = d; g.K = d; g.stats_out = ws.stats;
+    g.M = n; g.N = d; g.K = d; g.stats_out = ws.stats; g.moment_quads = quads;
     if ((tune_of(sh.tuning).row_panel & 8) && tune_of(sh.tuning).gemm_variant == 0 && panel64_dual_supported(dt, g, ws.att2)) {
       g.tune = cx.tune;      // one or two utterances: both products through one resident weight panel (same bits as the two launches)
       ProfScope p(cx, D3PM_K_GEMM, s, 2.0 * 2.0 * g.M * g.N * g.K, es * (2.0 * g.M * g.K + static_cast<double>(g.N) * g.K + 2.0 * g.M * g.N));
@@ -287,11 +290,11 @@ static int denoiser_blocks_folded(const d3pm_shape& sh, const d3pm_weights& w, i
       ProfScope p(cx, D3PM_K_GEMM, s, 2.0 * 2.0 * g.M * g.N * g.K, es * (2.0 * g.M * g.K + static_cast<double>(g.N) * g.K + 2.0 * g.M * g.N));
       D3PM_TRY(big_dual(dt, g, ws.att2, s));
     } else {
-      g.Y = ws.h; g.R1 = nullptr; g.stats_out = nullptr;          // o_text -> h (free: no LayerNorm output lives there any more)
+      g.Y = ws.h; g.R1 = nullptr; g.stats_out = nullptr; g.moment_quads = false;   // o_text -> h (free: no LayerNorm output lives there any more)
       D3PM_TRY(run_linear(cx, dt, g, 0, s));
       g = LinearArgs();
       g.X = ws.att2; g.ldx = d; g.W = b.cross_out_w; g.bias = b.cross_out_b; g.Y = ws.x; g.ldy = d;
-      g.R1 = ws.x; g.R2 = ws.h; g.ldr = d; g.M = n; g.N = d; g.K = d; g.stats_out = ws.stats;
+      g.R1 = ws.x; g.R2 = ws.h; g.ldr = d; g.M = n; g.N = d; g.K = d; g.stats_out = ws.stats; g.moment_quads = quads;
       D3PM_TRY(run_linear(cx, dt, g, 0, s));
     }
     // ---- FiLM-modulated MLP: the (layer, t) copy of fc1 carries norm3 and the modulation ----
@@ -299,16 +302,62 @@ static int denoiser_blocks_folded(const d3pm_shape& sh, const d3pm_weights& w, i
     D3PM_TRY(folded(at(ws.fc1f, ln * d, es), ws.fc1f_s + ln, ws.fc1f_b + ln, ws.mlp, 4 * d, ACT_GELU));
     g = LinearArgs();
     g.X = ws.mlp; g.ldx = 4 * d; g.W = b.fc2_w; g.bias = b.fc2_b; g.Y = ws.x; g.ldy = d; g.R1 = ws.x; g.ldr = d;
-    g.row_mask = frame_mask; g.mask_period = T; g.M = n; g.N = d; g.K = 4 * d; g.stats_out = ws.stats;
+    g.row_mask = frame_mask; g.mask_period = T; g.M = n; g.N = d; g.K = 4 * d; g.stats_out = ws.stats; g.moment_quads = quads;
     D3PM_TRY(run_linear(cx, dt, g, 0, s));
   }
   return D3PM_OK;
 }
 
 // hidden state after `layers` blocks is left in ws.x
-// is this evaluation taking the folded-LayerNorm launch sequence (denoiser_blocks_folded)?
-static bool fold_active(const d3pm_shape& sh, const d3pm_weights& w, uint32_t flags, const d3pm_fp8_block_weights* f8) {
-  return !f8 && w.fold && tune_of(sh.tuning).ln_fold && !(flags & D3PM_FLAG_FORCE_GENERIC) && fold_shape_ok(sh.dtype, sh.d_model);
+// Is this evaluation taking the folded-LayerNorm launch sequence (denoiser_blocks_folded), and in which format do its row moments
+// travel?  FOLD_NONE: the LayerNorm launches (the fold is off, or a projection of the sequence would not run on the MFMA family, whose
+// epilogues alone read and write moments).  FOLD_QUADS: every projection that reads or writes moments runs on big tiles (128-column
+// aligned, d = 512), so the producers can leave one quad per 128 columns (d3pm_mfma_tile.h EpiFold).  FOLD_PARTS: 32-column parts,
+// which the 128 x 128 and 64 x 64 (panel64, one or two utterances) families need.  One decision for the whole sequence: every
+// producer and consumer of ws.stats, the sampler's embedding rows included, must use the same format.
+enum { FOLD_NONE = 0, FOLD_PARTS = 1, FOLD_QUADS = 2 };
+static int fold_plan(const d3pm_shape& sh, const d3pm_weights& w, uint32_t flags, const d3pm_fp8_block_weights* f8, int batch,
+                     const Workspace& ws) {
+  if (f8 || !w.fold || !tune_of(sh.tuning).ln_fold || (flags & D3PM_FLAG_FORCE_GENERIC) || !fold_shape_ok(sh.dtype, sh.d_model)) return FOLD_NONE;
+  const int dt = sh.dtype, d = sh.d_model, n = batch * sh.canvas;
+  const size_t es = dtype_size(dt);
+  const Ctx cx(sh.tuning);
+  bool big = d == 512;
+  // the launches of denoiser_blocks_folded that read or write ws.stats, with the same arguments
+  auto check = [&](const LinearArgs& g) {
+    if (!mfma_linear_supported(dt, g)) return false;
+    big = big && mfma_linear_takes_big_tiles(dt, g);
+    return true;
+  };
+  for (int l = 0; l < sh.n_layers; ++l) {
+    const d3pm_block_weights& b = w.blocks[l];
+    const d3pm_fold_block& f = w.fold[l];
+    auto consumer = [&](const void* Wf, const float* fs, const float* fb, void* Y, int N, int act) {
+      LinearArgs g;
+      g.X = ws.x; g.ldx = d; g.W = Wf; g.Y = Y; g.ldy = N; g.M = n; g.N = N; g.K = d; g.act = act;
+      g.fold_s = fs; g.fold_b = fb; g.stats_in = ws.stats; g.tune = cx.tune;
+      return check(g);
+    };
+    auto producer = [&](const void* X, int K, const void* W, const void* bias, const void* R2, const uint8_t* mask) {
+      LinearArgs g;
+      g.X = X; g.ldx = K; g.W = W; g.bias = bias; g.Y = ws.x; g.ldy = d; g.R1 = ws.x; g.R2 = R2; g.ldr = d;
+      g.row_mask = mask; g.mask_period = sh.canvas; g.M = n; g.N = d; g.K = K; g.stats_out = ws.stats; g.tune = cx.tune;
+      return g;
+    };
+    const size_t ln = static_cast<size_t>(l) * 4 * d;
+    if (!consumer(f.qkv_w, f.qkv_s, f.qkv_b, ws.qkv, 3 * d, ACT_NONE) || !consumer(f.q2_w, f.q2_s, f.q2_b, ws.qkv, 2 * d, ACT_NONE) ||
+        !consumer(at(ws.fc1f, ln * d, es), ws.fc1f_s + ln, ws.fc1f_b + ln, ws.mlp, 4 * d, ACT_GELU))
+      return FOLD_NONE;
+    static const uint8_t one = 1;      // a frame mask stand-in: the kernel choice does not depend on its address
+    if (!check(producer(ws.att, d, b.attn_out_w, b.attn_out_b, nullptr, nullptr)) ||
+        !check(producer(ws.mlp, 4 * d, b.fc2_w, b.fc2_b, nullptr, &one)))
+      return FOLD_NONE;
+    const LinearArgs g = producer(ws.att, d, b.cross_out_w, b.cross_out_b, nullptr, nullptr);
+    if ((tune_of(sh.tuning).row_panel & 8) && tune_of(sh.tuning).gemm_variant == 0 && panel64_dual_supported(dt, g, ws.att2)) big = false;
+    else if ((tune_of(sh.tuning).row_panel & 2) && big_dual_supported(dt, g, ws.att2)) {}
+    else if (!check(producer(ws.att2, d, b.cross_out_w, b.cross_out_b, ws.h, nullptr))) return FOLD_NONE;
+  }
+  return big ? FOLD_QUADS : FOLD_PARTS;
 }
 
 static int denoiser_blocks(const d3pm_shape& sh, const d3pm_weights& w, int batch, const int32_t* x_t,
@@ -350,8 +399,8 @@ static int denoiser_blocks(const d3pm_shape& sh, const d3pm_weights& w, int batc
 
   // LayerNorm folded into the projections (d3pm_tuning.ln_fold, d3pm_fold_block): every LayerNorm-fed projection reads the raw
   // residual stream and normalises in its epilogue; every projection that lands on the residual stream leaves the row moments
-  if (fold_active(sh, w, flags, f8))
-    return denoiser_blocks_folded(sh, w, batch, x_t, frame_mask, t, film, kv_text, kv_prompt, ws, layers, s, prepared);
+  if (const int plan = fold_plan(sh, w, flags, f8, batch, ws))
+    return denoiser_blocks_folded(sh, w, batch, x_t, frame_mask, t, film, kv_text, kv_prompt, ws, layers, s, prepared, plan == FOLD_QUADS);
 
   EmbedArgs e;
   e.tokens = x_t; e.frame_mask = frame_mask; e.canvas = T; e.table = w.resps_emb; e.Y = ws.x;
@@ -913,9 +962,11 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
       ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0,
                   static_cast<double>(rows) * levels(*sh) * (sh->n_classes * dtype_size(sh->dtype) + 8.0));
       NextIterPrep nx;
-      if (t - 1 > t_stop && fold_active(*sh, *w, flags, f8)) {
+      const int plan = t - 1 > t_stop ? fold_plan(*sh, *w, flags, f8, batch, ws) : FOLD_NONE;
+      if (plan != FOLD_NONE) {
         const size_t es = dtype_size(sh->dtype);
         nx.dtype = sh->dtype; nx.table = w->resps_emb; nx.x = ws.x; nx.stats = ws.stats; nx.frame_mask = frame_mask; nx.d = sh->d_model;
+        nx.quads = plan == FOLD_QUADS;
         nx.blocks = w->blocks; nx.n_layers = sh->n_layers;
         nx.film_t = at(film, static_cast<size_t>(t - 1) * sh->n_layers * 2 * sh->d_model, es);
         nx.Wf = ws.fc1f; nx.s_out = ws.fc1f_s; nx.b_out = ws.fc1f_b;

@@ -72,17 +72,15 @@ __global__ __launch_bounds__(256) void fold_rows_layers(FoldStepPtrs p, const T*
 // lane L of pass j owns the 16-byte chunk 64 j + L; the four lanes of a quad own one part.  Used where the residual rows do not
 // come out of a GEMM epilogue: the token embedding in front of the first block (ar_discrete.py:753), and as a stand-alone op.
 template <typename T>
-__global__ __launch_bounds__(256) void row_stats(const T* __restrict__ x, int ldx, int M, int d, float* __restrict__ stats) {
+__global__ __launch_bounds__(256) void row_stats(const T* __restrict__ x, int ldx, int M, int d, float* __restrict__ stats, bool quads) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + wave;
   if (row >= M) return;
-  typedef float float2v __attribute__((ext_vector_type(2)));
-  const int parts = d >> 5;
   for (int c = lane; c < (d >> 3); c += kWave) {
     const Vec8<T> raw = *reinterpret_cast<const Vec8<T>*>(x + static_cast<size_t>(row) * ldx + c * 8);
     float a, q;
     part_moments(raw, a, q);
-    if ((lane & 3) == 0) *reinterpret_cast<float2v*>(stats + stats_index_dev(static_cast<size_t>(row), c >> 2, parts)) = float2v{a, q};
+    store_row_moments(a, q, stats, row, c, d, quads, lane);
   }
 }
 
@@ -90,11 +88,11 @@ __global__ __launch_bounds__(256) void row_stats(const T* __restrict__ x, int ld
 template <typename T>
 __global__ __launch_bounds__(256) void embed_rows_stats(const int32_t* __restrict__ tok, const uint8_t* __restrict__ frame_mask,
                                                         int canvas, const T* __restrict__ table, T* __restrict__ y, int M, int d,
-                                                        int n_classes, float* __restrict__ stats) {
+                                                        int n_classes, float* __restrict__ stats, bool quads) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + wave;
   if (row >= M) return;
-  embed_row_stats<T>(table, tok[row], frame_mask[row % canvas] != 0, y, row, d, n_classes, stats, lane);
+  embed_row_stats<T>(table, tok[row], frame_mask[row % canvas] != 0, y, row, d, n_classes, stats, quads, lane);
 }
 
 }  // namespace
@@ -142,26 +140,28 @@ int fold_fc1_step_launch(int dtype, const d3pm_block_weights* blocks, int n_laye
   return D3PM_OK;
 }
 
-int row_stats_launch(int dtype, const void* x, int ldx, int M, int d, float* stats, hipStream_t s) {
+int row_stats_launch(int dtype, const void* x, int ldx, int M, int d, float* stats, hipStream_t s, bool quads) {
+  if (quads && d != 512) return D3PM_E_SHAPE;        // a quad pass is one 512-column row (store_row_moments)
   const dim3 grid(static_cast<unsigned>((M + 3) / 4)), block(256);
-  if (dtype == D3PM_F16) row_stats<f16><<<grid, block, 0, s>>>(static_cast<const f16*>(x), ldx, M, d, stats);
-  else row_stats<bf16><<<grid, block, 0, s>>>(static_cast<const bf16*>(x), ldx, M, d, stats);
+  if (dtype == D3PM_F16) row_stats<f16><<<grid, block, 0, s>>>(static_cast<const f16*>(x), ldx, M, d, stats, quads);
+  else row_stats<bf16><<<grid, block, 0, s>>>(static_cast<const bf16*>(x), ldx, M, d, stats, quads);
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }
 
-int embed_tokens_stats(int dtype, const EmbedArgs& a, float* stats, hipStream_t s) {
+int embed_tokens_stats(int dtype, const EmbedArgs& a, float* stats, bool quads, hipStream_t s) {
+  if (quads && a.d != 512) return D3PM_E_SHAPE;
   if (a.n_q > 1) {                 // level-summed rows (extension): the generic gather, then the moments of the rows it wrote
     int rc = embed_tokens(dtype, a, s);
-    return rc != D3PM_OK ? rc : row_stats_launch(dtype, a.Y, a.d, a.M, a.d, stats, s);
+    return rc != D3PM_OK ? rc : row_stats_launch(dtype, a.Y, a.d, a.M, a.d, stats, s, quads);
   }
   const dim3 grid(static_cast<unsigned>((a.M + 3) / 4)), block(256);
   if (dtype == D3PM_F16)
     embed_rows_stats<f16><<<grid, block, 0, s>>>(a.tokens, a.frame_mask, a.canvas, static_cast<const f16*>(a.table), static_cast<f16*>(a.Y),
-                                                 a.M, a.d, a.n_classes, stats);
+                                                 a.M, a.d, a.n_classes, stats, quads);
   else
     embed_rows_stats<bf16><<<grid, block, 0, s>>>(a.tokens, a.frame_mask, a.canvas, static_cast<const bf16*>(a.table),
-                                                  static_cast<bf16*>(a.Y), a.M, a.d, a.n_classes, stats);
+                                                  static_cast<bf16*>(a.Y), a.M, a.d, a.n_classes, stats, quads);
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

@@ -68,22 +68,36 @@ __device__ __forceinline__ void part_moments(const Vec8<T>& raw, float& a, float
   a = add_dpp<0xB1>(a); q = add_dpp<0xB1>(q);     // lane ^ 1
 }
 
+// store the moments of chunk c's part (every lane of its quad holds them after part_moments).  quads (d = 512: one pass of all 64
+// lanes, d3pm_mfma_tile.h EpiFold): lane 16 j stores quad j of the row, (((0 + p_4j) + p_4j+1) + p_4j+2) + p_4j+3 -- the order of the
+// big-tile GEMM producers and of every consumer's lane group j
+__device__ __forceinline__ void store_row_moments(float a, float q, float* __restrict__ stats, int row, int c, int d, bool quads, int lane) {
+  typedef float float2v __attribute__((ext_vector_type(2)));
+  if (quads) {
+    float qa = 0.f, qq = 0.f;
+    const int base = lane & ~15;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { qa += __shfl(a, base + 4 * i); qq += __shfl(q, base + 4 * i); }
+    if ((lane & 15) == 0) *reinterpret_cast<float2v*>(stats + stats_index_dev(static_cast<size_t>(row), c >> 4, d >> 7)) = float2v{qa, qq};
+  } else if ((lane & 3) == 0) {
+    *reinterpret_cast<float2v*>(stats + stats_index_dev(static_cast<size_t>(row), c >> 2, d >> 5)) = float2v{a, q};
+  }
+}
+
 // one wave, one canvas row: x[row] = table[id] (zeros on a padded frame), and the row's moments (embed_rows_vec + row_stats)
 template <typename T>
 __device__ __forceinline__ void embed_row_stats(const T* __restrict__ table, int id, bool live, T* __restrict__ y, int row, int d, int n_classes,
-                                                float* __restrict__ stats, int lane) {
-  typedef float float2v __attribute__((ext_vector_type(2)));
+                                                float* __restrict__ stats, bool quads, int lane) {
   id = id < 0 ? 0 : (id >= n_classes ? n_classes - 1 : id);
   const Vec8<T>* src = reinterpret_cast<const Vec8<T>*>(table + static_cast<size_t>(id) * d);
   Vec8<T>* dst = reinterpret_cast<Vec8<T>*>(y + static_cast<size_t>(row) * d);
-  const int parts = d >> 5;
   for (int c = lane; c < (d >> 3); c += kWave) {
     Vec8<T> raw = src[c];
     if (!live) raw = Vec8<T>{};
     dst[c] = raw;
     float a, q;
     part_moments(raw, a, q);
-    if ((lane & 3) == 0) *reinterpret_cast<float2v*>(stats + stats_index_dev(static_cast<size_t>(row), c >> 2, parts)) = float2v{a, q};
+    store_row_moments(a, q, stats, row, c, d, quads, lane);
   }
 }
 

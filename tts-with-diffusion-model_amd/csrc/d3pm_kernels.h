@@ -45,6 +45,9 @@ struct LinearArgs {
   const float* fold_s = nullptr; const float* fold_b = nullptr; const float* stats_in = nullptr; float fold_eps = 1e-6f;
   // moments of the rows this launch stores (N = d_model, after residual / mask): stats_out [M][N / 32][2] partial (sum, sum of squares)
   float* stats_out = nullptr;
+  // stats_in / stats_out in the quad format [M / 16][d / 128][16][2] (d3pm_mfma_tile.h EpiFold) instead of 32-column parts: d_model = 512,
+  // big-tile GEMM only (mfma_linear fails with D3PM_E_SHAPE on any other family); one host decision per folded sequence (d3pm_api.hip)
+  bool moment_quads = false;
 };
 // which LayerNorm-fold combinations the MFMA epilogues instantiate: LNF [+ GELU] without residual / mask; STATS with R1, R1 + R2, R1 + mask
 inline bool fold_args_ok(const LinearArgs& a) {
@@ -57,6 +60,10 @@ inline bool fold_args_ok(const LinearArgs& a) {
   }
   if (a.stats_out) {
     if (!a.R1 || a.act != ACT_NONE || a.N % 32 != 0 || (reinterpret_cast<uintptr_t>(a.stats_out) % 8) != 0) return false;
+  }
+  if (a.moment_quads) {
+    if (!a.fold_s && !a.stats_out) return false;
+    if ((a.fold_s && a.K != 512) || (a.stats_out && a.N != 512)) return false;
   }
   return true;
 }
@@ -157,6 +164,7 @@ int posterior_sample(const SampleArgs& a, hipStream_t s);
 struct NextIterPrep {
   int dtype = D3PM_BF16;
   const void* table = nullptr; void* x = nullptr; float* stats = nullptr; const uint8_t* frame_mask = nullptr; int d = 0;
+  bool quads = false;                                                                               // stats in the quad format
   const d3pm_block_weights* blocks = nullptr; int n_layers = 0; const void* film_t = nullptr;      // film_t: row t - 1 of the FiLM table
   void* Wf = nullptr; float* s_out = nullptr; float* b_out = nullptr;
 };
@@ -209,6 +217,7 @@ bool panel64_dual_supported(int dtype, const LinearArgs& a, const void* X2);
 int panel64_dual(int dtype, const LinearArgs& a, const void* X2, hipStream_t s);
 // big-tile GEMM, the same two products at throughput batch sizes (d3pm_mfma_gemm_big.hip); stats_out optional
 bool big_dual_supported(int dtype, const LinearArgs& a, const void* X2);
+bool mfma_linear_takes_big_tiles(int dtype, const LinearArgs& a);     // would mfma_linear run `a` on the big-tile GEMM?
 int big_dual(int dtype, const LinearArgs& a, const void* X2, hipStream_t s);
 bool row_panel_supported(int dtype, const LinearArgs& a, const RowPanelFuse& f);
 int row_panel_linear(int dtype, const LinearArgs& a, const RowPanelFuse& f, hipStream_t s);
@@ -223,8 +232,9 @@ int fold_rows_launch(int dtype, const void* W, const void* bias, const void* gam
                      int n_rows, int n_t, int K, void* Wf, float* s_out, float* b_out, hipStream_t s);
 int fold_fc1_step_launch(int dtype, const d3pm_block_weights* blocks, int n_layers, const void* film_t, int d, void* Wf, float* s_out,
                          float* b_out, hipStream_t s);
-int row_stats_launch(int dtype, const void* x, int ldx, int M, int d, float* stats, hipStream_t s);
-int embed_tokens_stats(int dtype, const EmbedArgs& a, float* stats, hipStream_t s);
+// quads: the moments in the quad format of d3pm_mfma_tile.h (EpiFold; d = 512) instead of 32-column parts
+int row_stats_launch(int dtype, const void* x, int ldx, int M, int d, float* stats, hipStream_t s, bool quads = false);
+int embed_tokens_stats(int dtype, const EmbedArgs& a, float* stats, bool quads, hipStream_t s);
 
 // ---- stock NAR model (levels 1..7): input assembly, AdaLN, temperature sampling (d3pm_nar.hip) ----
 struct NarEmbedArgs {

@@ -399,18 +399,31 @@ bool ln_prologue_linear_applies(int dtype, const LinearArgs& a, const LnPrologue
 int ln_prologue_linear(int dtype, const LinearArgs& a, const LnPrologue& ln, hipStream_t s) { return panel64_linear(dtype, a, s, &ln); }
 #endif
 
+// the big-tile geometry mfma_linear takes for `a` (d3pm_mfma_gemm_big.hip), 0 = another family
+static int mfma_linear_big_id(int dtype, const LinearArgs& a) {
+#ifdef D3PM_ABLATIONS
+  if (ab_knobs().ring && ring_linear_supported(dtype, a)) return 0;
+#endif
+  const int v = tune_of(a.tune).gemm_variant;
+  if (!(v == 0 || (v >= 6 && v <= 8))) return 0;
+  return big_linear_tile(dtype, a, v == 6 ? 2 : v == 7 ? 1 : v == 8 ? 3 : 0);
+}
+
+bool mfma_linear_takes_big_tiles(int dtype, const LinearArgs& a) { return mfma_linear_supported(dtype, a) && mfma_linear_big_id(dtype, a) != 0; }
+
 int mfma_linear(int dtype, const LinearArgs& a, hipStream_t s) {
   // All schedules accumulate in the same order, so the choice never changes a bit of the result.
   const bool ffn_act = a.act == ACT_RELU || a.act == ACT_SILU;
   const d3pm_tuning& tn = tune_of(a.tune);
   const int g_gemm_variant = tn.gemm_variant, g_persist_slots = tn.gemm_persist_slots >= 8 ? (tn.gemm_persist_slots & ~7) : 1024;
 #ifdef D3PM_ABLATIONS
-  if (ab_knobs().ring && ring_linear_supported(dtype, a)) return ring_linear(dtype, a, s);   // experimental ring schedule
+  if (ab_knobs().ring && ring_linear_supported(dtype, a) && !a.moment_quads) return ring_linear(dtype, a, s);   // experimental ring schedule
 #endif
   const bool autosel = g_gemm_variant == 0 || (g_gemm_variant >= 6 && g_gemm_variant <= 8);
-  if (autosel) {
-    const int id = big_linear_tile(dtype, a, g_gemm_variant == 6 ? 2 : g_gemm_variant == 7 ? 1 : g_gemm_variant == 8 ? 3 : 0);
-    if (id) return big_linear(dtype, a, id, s);
+  if (const int id = mfma_linear_big_id(dtype, a)) return big_linear(dtype, a, id, s);
+  if (a.moment_quads) {            // the quad format of the row moments exists in the big-tile epilogues only
+    set_error("row-moment quads: %d x %d x %d does not run on big tiles", a.M, a.N, a.K);
+    return D3PM_E_SHAPE;
   }
   // one or two utterances: 64 x 64 tiles with whole-K panels in flight (d3pm_mfma_gemm_lat.hip); 4 forces it for any M
   if ((g_gemm_variant == 4 || (autosel && a.M <= 1536)) && panel64_linear_supported(dtype, a)) return panel64_linear(dtype, a, s);

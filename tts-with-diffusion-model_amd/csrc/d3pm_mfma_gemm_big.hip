@@ -105,16 +105,21 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
   // residual read runs under the k-loop instead of after it.  NPRE = the vector-memory operations this certainly adds behind
   // the previous tile's stores (a LOWER bound keeps the counted waits safe: they may only wait for more): 12 residual + 6 mask loads
   constexpr bool kPreEpi = (MODE & 32768) != 0 && FUSE == 0 && (EPI & EPI_R2) == 0;
-  // EPI_LNF (K = 512: the launcher): the row moments a lane needs for its six row blocks are 12 x 16 bytes per tile -- 48 KB per
-  // workgroup tile beside its 320 KB of operands, through the same CU <-> L2 path -- and a round trip the epilogue would start
-  // with.  Loaded where the epilogue needs them they cost qkv 36.7 -> 45.1 us and fc1 69.7 -> 84.8 us in the loop; requested at
+  // EPI_LNF (K = 512: the launcher): the row moments a lane needs for its six row blocks are 24 x 8 bytes per tile -- 48 KB per
+  // workgroup tile beside its 320 KB of operands, through the same CU <-> L2 path (EPI_QUADS: 6 x 8 bytes, 12 KB) -- and a round trip
+  // the epilogue would start with.  Loaded where the epilogue needs them they cost qkv 36.7 -> 45.1 us and fc1 69.7 -> 84.8 us in the loop; requested at
   // the top of the tile they stalled the second k-step instead (every k-step waits with vmcnt(0), vector-memory operations
   // retire in order).  The one place such a load can hide is ACROSS an epilogue: the moments of the NEXT row panel are requested
-  // at the start of the epilogue of the last tile of this one, from inline asm (exactly 12 loads) behind the tile's own
-  // per-column vectors (8 asm loads), the epilogue waits with vmcnt(24) -- its vectors have landed, the moments may stay in
+  // at the start of the epilogue of the last tile of this one, from inline asm (NMOM = 24 loads, 6 with quads) behind the tile's own
+  // per-column vectors (8 asm loads), the epilogue waits with vmcnt(NMOM) -- its vectors have landed, the moments may stay in
   // flight -- and the next tile's first k-step, which waits for everything older than the 12 output stores anyway, finds them
   // landed; they are reduced to the two scalars per row right behind that k-step.
   constexpr bool kLnfPre = (EPI & EPI_LNF) != 0;
+  constexpr bool kQuads = (EPI & EPI_QUADS) != 0;
+  static_assert(!kQuads || ((EPI & (EPI_LNF | EPI_STATS)) != 0 && WN % 2 == 0), "a quad = the 128 columns of two neighbouring waves");
+  constexpr int MPR = kQuads ? 1 : 4;                   // moment loads per row block and lane: one quad, or parts 4 g .. 4 g + 3
+  constexpr int NMOM = 6 * MPR;                         // the moment loads of a tile: what the epilogue's counted wait leaves in flight
+  static_assert(NMOM == (kQuads ? 6 : 24) && NMOM < 64, "vmcnt operand");
   constexpr int NPRE = !kPreEpi ? 0 : ((EPI & EPI_R1) ? 12 : 0) + ((EPI & EPI_MASK) ? 6 : 0);
   static_assert((MODE & 32768) == 0 || (!kDrip && (MODE & 1)), "epilogue prefetch rides in the hand-placed schedule");
   constexpr bool kDual = (FUSE & FUSE_DUAL) != 0, kLn = (FUSE & FUSE_LN) != 0, kLn2 = (FUSE & FUSE_LN2) != 0, kFilm = (FUSE & FUSE_FILM) != 0;
@@ -199,16 +204,20 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
 #pragma unroll
   for (int p = 0; p < NDMA; ++p) dma(p, sx, sw, lds_base);          // first k-step of the first tile
   typedef float float2v __attribute__((ext_vector_type(2)));
-  [[maybe_unused]] float2v lst[6][4];                                // EPI_LNF: the moments of the tile about to start, in flight
+  [[maybe_unused]] float2v lst[6][MPR];                              // EPI_LNF: the moments of the tile about to start, in flight
   auto moments_request = [&](int mrow0) __attribute__((always_inline)) {
-    // parts 4 g .. 4 g + 3 of row (lane & 15) of each of the six 16-row blocks: [row block][part][row][2] (stats_index), 24 loads
-    const float* sp = ef.stats_in + stats_index(static_cast<size_t>(mrow0 + wm * 96 + (lane & 15)), (lane >> 4) * 4, 16);
+    // entries MPR g .. MPR g + MPR - 1 of row (lane & 15) of each of the six 16-row blocks: [row block][entry][row][2] (stats_index,
+    // 16 parts or 4 quads per row; one entry of a row block = one 128-byte line), NMOM loads
+    constexpr int P = 4 * MPR;
+    const float* sp = ef.stats_in + stats_index(static_cast<size_t>(mrow0 + wm * 96 + (lane & 15)), (lane >> 4) * MPR, P);
 #pragma unroll
     for (int mt = 0; mt < 6; ++mt) {
-      asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(lst[mt][0]) : "v"(sp + mt * 512) : "memory");
-      asm volatile("global_load_dwordx2 %0, %1, off offset:128" : "=v"(lst[mt][1]) : "v"(sp + mt * 512) : "memory");
-      asm volatile("global_load_dwordx2 %0, %1, off offset:256" : "=v"(lst[mt][2]) : "v"(sp + mt * 512) : "memory");
-      asm volatile("global_load_dwordx2 %0, %1, off offset:384" : "=v"(lst[mt][3]) : "v"(sp + mt * 512) : "memory");
+      asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(lst[mt][0]) : "v"(sp + mt * P * 32) : "memory");
+      if constexpr (MPR == 4) {
+        asm volatile("global_load_dwordx2 %0, %1, off offset:128" : "=v"(lst[mt][MPR - 3]) : "v"(sp + mt * P * 32) : "memory");
+        asm volatile("global_load_dwordx2 %0, %1, off offset:256" : "=v"(lst[mt][MPR - 2]) : "v"(sp + mt * P * 32) : "memory");
+        asm volatile("global_load_dwordx2 %0, %1, off offset:384" : "=v"(lst[mt][MPR - 1]) : "v"(sp + mt * P * 32) : "memory");
+      }
     }
   };
   if constexpr (kLnfPre) moments_request((tile / n_tiles) * TM);     // the first tile's: covered by the wait below
@@ -222,6 +231,28 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
   for (int j = 0; j < 12; ++j) pend[j] = uintx4{0u, 0u, 0u, 0u};
   T* pend_y = Y;
   bool pending = false;
+  // EPI_STATS | EPI_QUADS: the quads of the tile's rows from the part moments z[mt * 2 + np] (part_stats_reduce) of this wave's 64
+  // columns.  Waves 2 j and 2 j + 1 own the 128 columns of quad j: the even one adds its two parts from 0.f, hands that over through
+  // stage 1 (its last reads were the k-step that has just ended; the next DMA into it is issued behind the next tile's first barrier,
+  // after the odd wave has consumed the hand-over), the odd one adds its own two parts and stores the quad
+  [[maybe_unused]] auto quads_out = [&](const float (&z)[12], int m0, int n0) __attribute__((always_inline)) {
+    float* xch = reinterpret_cast<float*>(smem + STAGE) + (wm * (WN / 2) + (wn >> 1)) * 6 * 64 + lane;
+    static_assert(WM * (WN / 2) * 6 * 64 * 4 <= STAGE, "hand-over fits in one stage");
+    asm volatile("s_barrier" ::: "memory");             // every wave has retired its fragment reads of stage 1
+    if ((wn & 1) == 0) {
+#pragma unroll
+      for (int mt = 0; mt < 6; ++mt) xch[mt * 64] = (0.f + z[mt * 2]) + z[mt * 2 + 1];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the hand-over is in LDS
+    if ((wn & 1) != 0) {
+      const int g = lane >> 4;
+#pragma unroll
+      for (int mt = 0; mt < 6; ++mt) {
+        const float qv = (xch[mt * 64] + z[mt * 2]) + z[mt * 2 + 1];
+        if (g < 2) ef.stats_out[stats_index(static_cast<size_t>(m0 + wm * 96 + mt * 16 + (lane & 15)), (n0 + wn * 64) >> 7, N >> 7) + g] = qv;
+      }
+    }
+  };
   for (;;) {
     floatx4 acc[4][6];
 #pragma unroll
@@ -359,10 +390,11 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
         if (fresh)
 #pragma unroll
         for (int mt = 0; mt < 6; ++mt) {
-          asm volatile("" : "+v"(lst[mt][0]), "+v"(lst[mt][1]), "+v"(lst[mt][2]), "+v"(lst[mt][3]));
-          float a = 0.f, q = 0.f;
 #pragma unroll
-          for (int i = 0; i < 4; ++i) { a += lst[mt][i][0]; q += lst[mt][i][1]; }
+          for (int i = 0; i < MPR; ++i) asm volatile("" : "+v"(lst[mt][i]));
+          float a = 0.f, q = 0.f;                        // fold_row_moments' order: a quad is these four adds done by the producer
+#pragma unroll
+          for (int i = 0; i < MPR; ++i) { a += lst[mt][i][0]; q += lst[mt][i][1]; }
           a = add_xor16(a); q = add_xor16(q);
           fold_row_scalars(add_xor32(a), add_xor32(q), 512, ef.eps, rows.ra[mt], rows.rc[mt]);
         }
@@ -441,14 +473,17 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
         else *reinterpret_cast<uintx4*>(yp) = xp[j];
       }
       if constexpr ((EPI & EPI_STATS) != 0) {        // the row moments of the new rows for the folded LayerNorm that reads them next
+        [[maybe_unused]] float z[12];
 #pragma unroll
         for (int j = 0; j < 12; ++j) {
           const Pack8<T> p = __builtin_bit_cast(Pack8<T>, xp[j]);
           float v[8];
 #pragma unroll
           for (int i = 0; i < 8; ++i) v[i] = static_cast<float>(p.v[i]);
-          part_stats_store(v, ef.stats_out, static_cast<size_t>(m0 + wm * 96 + (j / 2) * 16 + (lane & 15)), N, n0 + wn * 64 + (j % 2) * 32, g, true);
+          if constexpr (kQuads) z[j] = part_stats_reduce(v);
+          else part_stats_store(v, ef.stats_out, static_cast<size_t>(m0 + wm * 96 + (j / 2) * 16 + (lane & 15)), N, n0 + wn * 64 + (j % 2) * 32, g, true);
         }
+        if constexpr (kQuads) quads_out(z, m0, n0);
       }
       if constexpr (kLn && (FUSE & FUSE_ABL_NOLN) != 0) {      // timing-only: the stores of the LayerNorm outputs without their arithmetic
 #pragma unroll
@@ -614,7 +649,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
         fresh = more && (tile_next / n_tiles) != (tile / n_tiles);      // the next tile reads other rows
         if (fresh) {
           moments_request((tile_next / n_tiles) * TM);
-          asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NMOM) : "memory");
         } else {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -626,12 +661,15 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
         }
         epilogue_store<T, EPI, 4, 6, true, false, true, true>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 96,
                                                               n0 + wn * 64, lane, nullptr, gelu_tab, &pre, &ef, &rows);
-      } else if (!kept)
+      } else if (!kept) {
         // output rows leave as `sc1` stores (kNts): they are not read again by this launch, and left in the XCD's L2 they displace the
         // operand panels the other tiles of the launch still stream (in the loop: 103.8 k -> 106.2 k tokens/s with the stand-alone
         // LayerNorms, 104.5 k -> 110.5 k with them folded; MODE bit 9 of the A/B library used to try `nt`, which keeps the line in L2)
+        [[maybe_unused]] float z[12];
         epilogue_store<T, EPI, 4, 6, true, false, true, kPreEpi>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 96,
-                                                                 n0 + wn * 64, lane, nullptr, gelu_tab, &pre, &ef);
+                                                                 n0 + wn * 64, lane, nullptr, gelu_tab, &pre, &ef, nullptr, z);
+        if constexpr (kQuads && (EPI & EPI_STATS) != 0) quads_out(z, m0, n0);
+      }
     }
     if (!more) break;
     t = t_next;
@@ -842,6 +880,9 @@ int big_dual(int dtype, const LinearArgs& a, const void* X2, hipStream_t s) {
   const size_t lds = 2 * static_cast<size_t>(tm + tn) * ROW_BYTES;
   auto go = [&](auto* tag) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
+    if (a.stats_out && a.moment_quads)
+      return id == 2 ? big_dual_launch<U, EPI_R2 | EPI_STATS | EPI_QUADS, 2, 4>(a, X2, n_tiles, tiles_total, grid, lds, s)
+                     : big_dual_launch<U, EPI_R2 | EPI_STATS | EPI_QUADS, 2, 2>(a, X2, n_tiles, tiles_total, grid, lds, s);
     if (a.stats_out)
       return id == 2 ? big_dual_launch<U, EPI_R2 | EPI_STATS, 2, 4>(a, X2, n_tiles, tiles_total, grid, lds, s)
                      : big_dual_launch<U, EPI_R2 | EPI_STATS, 2, 2>(a, X2, n_tiles, tiles_total, grid, lds, s);
@@ -859,7 +900,7 @@ int big_linear(int dtype, const LinearArgs& a, int id, hipStream_t s) {
   const dim3 grid(static_cast<unsigned>(want < slots ? want : slots));
   const size_t lds = 2 * static_cast<size_t>(tm + tn) * ROW_BYTES;
   const int epi = (a.act == ACT_GELU ? EPI_GELU : 0) | (a.R1 ? (a.R2 ? EPI_R2 : EPI_R1) : 0) | (a.row_mask ? EPI_MASK : 0) |
-                  (a.fold_s ? EPI_LNF : 0) | (a.stats_out ? EPI_STATS : 0);
+                  (a.fold_s ? EPI_LNF : 0) | (a.stats_out ? EPI_STATS : 0) | (a.moment_quads ? EPI_QUADS : 0);
   auto go = [&](auto* tag) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
     switch (epi) {
@@ -868,6 +909,12 @@ int big_linear(int dtype, const LinearArgs& a, int id, hipStream_t s) {
       case EPI_R1 | EPI_STATS: return big_launch_fold<U, EPI_R1 | EPI_STATS>(id, a, n_tiles, tiles_total, grid, lds, s);
       case EPI_R2 | EPI_STATS: return big_launch_fold<U, EPI_R2 | EPI_STATS>(id, a, n_tiles, tiles_total, grid, lds, s);
       case EPI_R1 | EPI_MASK | EPI_STATS: return big_launch_fold<U, EPI_R1 | EPI_MASK | EPI_STATS>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_LNF | EPI_QUADS: return big_launch_fold<U, EPI_LNF | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_LNF | EPI_GELU | EPI_QUADS: return big_launch_fold<U, EPI_LNF | EPI_GELU | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_R1 | EPI_STATS | EPI_QUADS: return big_launch_fold<U, EPI_R1 | EPI_STATS | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_R2 | EPI_STATS | EPI_QUADS: return big_launch_fold<U, EPI_R2 | EPI_STATS | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_R1 | EPI_MASK | EPI_STATS | EPI_QUADS:
+        return big_launch_fold<U, EPI_R1 | EPI_MASK | EPI_STATS | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
       case 0: return big_launch_geometry<U, 0>(id, a, n_tiles, tiles_total, grid, lds, s);
       case EPI_GELU: return big_launch_geometry<U, EPI_GELU>(id, a, n_tiles, tiles_total, grid, lds, s);
       case EPI_R1: return big_launch_geometry<U, EPI_R1>(id, a, n_tiles, tiles_total, grid, lds, s);

@@ -88,7 +88,9 @@ __device__ __forceinline__ void gelu_table_to_lds(const uint16_t* __restrict__ g
 // Residual loads are branch-free (clamped addresses) and batched per row; only the stores are predicated.
 // EPI bits: 1 = exact-erf GELU, 2 = one residual (R1), 4 = two residuals (R1, R2), 8 = frame mask, 16 = ReLU, 32 = SiLU
 //           64 = LayerNorm folded into this projection (EPI_LNF), 128 = row moments of the output rows (EPI_STATS): below
+//           256 = the moments in and out of this launch are in the quad format (EPI_QUADS, big-tile GEMM only: below)
 constexpr int EPI_GELU = 1, EPI_R1 = 2, EPI_R2 = 4, EPI_MASK = 8, EPI_RELU = 16, EPI_SILU = 32, EPI_LNF = 64, EPI_STATS = 128;
+constexpr int EPI_QUADS = 256;
 
 // LayerNorm taken out of the launch list algebraically (ar_discrete.py:131-132, 136-142, 153-159: LayerNorm -> Linear).  With
 // W' = W o gamma (rounded to the storage type once, at weight-preparation time), s_n = sum_k W'[n][k] and
@@ -105,13 +107,18 @@ constexpr int EPI_GELU = 1, EPI_R1 = 2, EPI_R2 = 4, EPI_MASK = 8, EPI_RELU = 16,
 // parts each, then two butterfly steps).  var = E[y^2] - mean^2 in fp32: with |mean| <~ 10 sigma the relative error of rstd stays
 // below 1e-5, two orders under the 16-bit storage quantum.  This skips the 16-bit rounding of the LayerNorm output (closer to the
 // fp32 model than the eager chain); the F32 / generic family keeps the stand-alone LayerNorm.
+// Quad format (EPI_QUADS, LinearArgs::moment_quads; d_model = 512 only): the same layout with one "quad" per 128 columns instead of one
+// part per 32, [M / 16][N / 128][16][2].  Quad g of a row is (((0 + p_4g) + p_4g+1) + p_4g+2) + p_4g+3 -- exactly the partial sum that
+// lane group g of every consumer forms from the 16 parts (fold_row_moments) -- so a consumer reading 4 quads per row instead of 16 parts
+// computes the same bits, from a quarter of the bytes.  The producers sum it in that order (big-tile epilogue: the two waves that own
+// a 128-column quad hand the first half over through LDS, gemm_mfma_big; the embedding rows: store_row_moments, d3pm_fold_rows.h).
 struct EpiFold {
   const float* s = nullptr;          // [N]  sum_k W'[n][k]
   const float* b = nullptr;          // [N]  folded bias b'
   const float* stats_in = nullptr;   // [M][parts_in][2]  moments of the operand rows (the residual stream, K columns)
-  float* stats_out = nullptr;        // [M][N / 32][2]    moments of the rows this launch stores (N = d_model)
+  float* stats_out = nullptr;        // [M][N / 32][2]    moments of the rows this launch stores (N = d_model); N / 128 quads
   float eps = 1e-6f;
-  int parts_in = 0;                  // K / 32, a multiple of 8
+  int parts_in = 0;                  // K / 32 (a multiple of 8), or K / 128 = 4 quads
 };
 
 // float index of (row, part) in a moments buffer of `parts` parts per row: [row / 16][part][row % 16][2]
@@ -121,7 +128,8 @@ __host__ __device__ __forceinline__ size_t stats_index(size_t row, int part, int
 
 inline EpiFold epi_fold_of(const LinearArgs& a) {
   EpiFold e;
-  e.s = a.fold_s; e.b = a.fold_b; e.stats_in = a.stats_in; e.stats_out = a.stats_out; e.eps = a.fold_eps; e.parts_in = a.K / 32;
+  e.s = a.fold_s; e.b = a.fold_b; e.stats_in = a.stats_in; e.stats_out = a.stats_out; e.eps = a.fold_eps;
+  e.parts_in = a.moment_quads ? a.K / 128 : a.K / 32;
   return e;
 }
 
@@ -149,7 +157,8 @@ __device__ __forceinline__ void part_moments8(const float (&v)[8], float& a, flo
 // EPI_STATS: (sum, sum of squares) of the 32 stored values of row m in the 32-column part starting at column `col0` -- eight in this
 // lane, the other 24 in the lanes 16 / 32 / 48 away.  The order below is the definition of a part's moments for every kernel
 // (and of d3pm_op_row_stats, d3pm_fold.hip).  Executed by the whole wave (lane permutes); `ok` only predicates the store.
-__device__ __forceinline__ void part_stats_store(const float (&v)[8], float* __restrict__ stats_out, size_t m, int N, int col0, int g, bool ok) {
+// part_stats_reduce leaves the sum in lane group 0 and the sum of squares in lane group 1 (groups 2 and 3 hold copies).
+__device__ __forceinline__ float part_stats_reduce(const float (&v)[8]) {
   float a, q;
   part_moments8(v, a, q);
   // one butterfly for both moments: after the 16-lane swap the even lane rows hold sums of `a`, the odd ones sums of `q`
@@ -158,7 +167,10 @@ __device__ __forceinline__ void part_stats_store(const float (&v)[8], float* __r
   asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(q));
   float z = a + q, z2 = z;
   asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(z), "+v"(z2));
-  z += z2;
+  return z + z2;
+}
+__device__ __forceinline__ void part_stats_store(const float (&v)[8], float* __restrict__ stats_out, size_t m, int N, int col0, int g, bool ok) {
+  const float z = part_stats_reduce(v);
   if (g < 2 && ok) stats_out[stats_index(m, col0 >> 5, N >> 5) + g] = z;
 }
 
@@ -287,8 +299,10 @@ __device__ __forceinline__ void epilogue_store(floatx4 (&acc)[NT][MT], const T* 
                                                uintx4* packed = nullptr, const uint16_t* gelu_tab = nullptr,
                                                const EpiPre<T, NT, MT>* pre = nullptr,      // pre: read only when kPre
                                                const EpiFold* ef = nullptr,                 // ef: read only under EPI_LNF / EPI_STATS
-                                               const RowScalars<MT>* rows = nullptr) {      // EPI_LNF: the row scalars, when the caller has them
+                                               const RowScalars<MT>* rows = nullptr,        // EPI_LNF: the row scalars, when the caller has them
+                                               float* zq = nullptr) {     // EPI_STATS | EPI_QUADS: part moments [MT][NT / 2] (part_stats_reduce)
   static_assert(!kPack || kInteriorOnly, "packing to registers is for whole tiles");
+  static_assert((EPI & EPI_QUADS) == 0 || kInteriorOnly, "quads: the big-tile GEMM, whole tiles");
   static_assert(NT % 2 == 0, "column blocks are regrouped in pairs");
   constexpr bool kGelu = EPI & EPI_GELU, kR1 = (EPI & (EPI_R1 | EPI_R2)) != 0, kR2 = (EPI & EPI_R2) != 0, kMask = (EPI & EPI_MASK) != 0;
   constexpr bool kLnf = (EPI & EPI_LNF) != 0, kStats = (EPI & EPI_STATS) != 0;
@@ -317,7 +331,7 @@ __device__ __forceinline__ void epilogue_store(floatx4 (&acc)[NT][MT], const T* 
         for (int r = 0; r < 4; ++r) { bv[nt][r] = b4[r]; sv[nt][r] = s4[r]; }
       }
     }
-    const int d_in = ef->parts_in * 32;
+    const int d_in = ef->parts_in * ((EPI & EPI_QUADS) != 0 ? 128 : 32);
     if (rows != nullptr) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) { ra[mt] = rows->ra[mt]; rc[mt] = rows->rc[mt]; }
@@ -433,7 +447,8 @@ __device__ __forceinline__ void epilogue_store(floatx4 (&acc)[NT][MT], const T* 
           }
           if (kMask) v[r] *= mk;
         }
-        if constexpr (kStats) emit_stats(v, m + mt * 16, np, true);
+        if constexpr (kStats && (EPI & EPI_QUADS) != 0) zq[mt * NP + np] = part_stats_reduce(v);   // the caller forms the quads
+        else if constexpr (kStats) emit_stats(v, m + mt * 16, np, true);
         const uintx4 grp = uintx4{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7])};
         if constexpr (kPack) packed[mt * NP + np] = grp;
         else if constexpr (kNts) {

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void posterior_sample_prep_rows(
     const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next, int32_t* x_next2, int rows, int K, int mask_id,
     uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int canvas, int sample_blocks,
     const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
-    FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out) {
+    bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (static_cast<int>(blockIdx.x) >= sample_blocks) {
     const int r = (blockIdx.x - sample_blocks) * 4 + wave;
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void posterior_sample_prep_rows(
     x_next[row] = best_j;
     if (x_next2) x_next2[row] = best_j;
   }
-  embed_row_stats<T>(table, best_j, frame_mask[row % canvas] != 0, xres, row, d, K, stats, lane);
+  embed_row_stats<T>(table, best_j, frame_mask[row % canvas] != 0, xres, row, d, K, stats, quads, lane);
 }
 
 // forward noising: logits are log16(rn16(row_of_Qbar_t + eps)) with at most three distinct values
@@ -152,7 +152,7 @@ int posterior_sample(const SampleArgs& a, hipStream_t s) {
 
 bool posterior_sample_prep_supported(const SampleArgs& a, const NextIterPrep& n) {
   return a.n_q == 1 && !a.posterior_out && a.logits_dtype == n.dtype && (n.dtype == D3PM_F16 || n.dtype == D3PM_BF16) && n.n_layers <= 16 &&
-         n.d % 256 == 0 && a.n_classes <= kWave * kMaxGroupsPerLane * 4 && n.table && n.x && n.stats && n.blocks && n.film_t && n.Wf;
+         n.d % 256 == 0 && (!n.quads || n.d == 512) && a.n_classes <= kWave * kMaxGroupsPerLane * 4 && n.table && n.x && n.stats && n.blocks && n.film_t && n.Wf;
 }
 
 int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_t s) {
@@ -165,7 +165,7 @@ int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_
 #define D3PM_PSP(T)                                                                                                                 \
   posterior_sample_prep_rows<T><<<grid, block, 0, s>>>(static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next, a.x_next2, a.rows, a.n_classes, \
       a.mask_id, a.seed, a.seed_hbm, a.row0, a.greedy, a.pc, a.canvas, sample_blocks, static_cast<const T*>(n.table), static_cast<T*>(n.x),    \
-      n.stats, n.frame_mask, n.d, p, static_cast<const T*>(n.film_t), n.n_layers, static_cast<T*>(n.Wf), n.s_out, n.b_out)
+      n.stats, n.frame_mask, n.d, n.quads, p, static_cast<const T*>(n.film_t), n.n_layers, static_cast<T*>(n.Wf), n.s_out, n.b_out)
   if (n.dtype == D3PM_F16) D3PM_PSP(f16); else D3PM_PSP(bf16);
 #undef D3PM_PSP
   D3PM_LAUNCH_CHECK();
