@@ -49,7 +49,9 @@ extern "C" {
  *    4 / 5); layouts unchanged */
 /* 6: LayerNorm folded into the projections (d3pm_fold_block, d3pm_weights.fold, d3pm_fold_bytes / d3pm_fold_build,
  *    d3pm_op_linear_fold / d3pm_op_linear_stats / d3pm_op_row_stats); d3pm_tuning gained regime_batch and ln_fold (layout change);
- *    d3pm_workspace_bytes grew by the row-moment buffer and the fp8 path's scale slot */
+ *    d3pm_workspace_bytes grew by the row-moment buffer and the fp8 path's scale slot;
+ *    later additions only: the condition encoders' training-step dropout (d3pm_op_dropout_f32, d3pm_op_attention_dropout_f32,
+ *    d3pm_op_attention_bwd_dropout_f32) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -509,7 +511,22 @@ int d3pm_prof_destroy(struct d3pm_prof *prof);
  * d3pm_op_attention_bwd_f32  softmax(scale q k^T) v backward (nn.MultiheadAttention core, :132,138,142): dQ overwritten,
  *                         dK / dV = beta_kv * old + new; stats = 2 B H Tq floats of scratch
  * d3pm_op_ce_bwd_f32      dlogits = mask (softmax(logits mask) - onehot(target)) gscale    (:683-690)
- * d3pm_op_embed_f32 / d3pm_op_embed_bwd_f32  nn.Embedding gather with the row mask, and its scatter-add (padding_idx row skipped) */
+ * d3pm_op_embed_f32 / d3pm_op_embed_bwd_f32  nn.Embedding gather with the row mask, and its scatter-add (padding_idx row skipped)
+ *
+ * Dropout of the two condition encoders in train mode (ar_discrete.py:216-230: nn.TransformerEncoderLayer dropout 0.1 at four
+ * sites per layer, timm Mlp drop 0.01 at two), from a counter-based mask that the backward pass regenerates (nothing stored):
+ *   Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter (idx >> 2, utt, site, 3), word idx & 3,
+ *   u = (word >> 8) 2^-24, keep <=> u >= p, kept value x s with s = 1.0f / (1.0f - p) in fp32, dropped value 0;
+ *   site = (which << 8) | (layer << 4) | kind  (which 0 text encoder, 1 prompt encoder; layer 0 .. cond_layers - 1 with kind
+ *   0 attention probabilities, 1 after self-attn out_proj, 2 FFN hidden after ReLU, 3 after linear2; layer 15 = the Mlp with
+ *   kind 0 after SiLU, 1 after fc2);  idx = r cols + c of an [rows][cols] activation (logical, independent of the row stride),
+ *   (h Tq + i) S + j of the attention probabilities.  0 <= p < 1 (else D3PM_E_ARG); an extent whose idx would not fit in 32 bits
+ *   is refused (D3PM_E_SHAPE).
+ * d3pm_op_dropout_f32     Y = (R ? R + X z : X z), z = keep ? s : 0, over [M][N] (row strides ldx / ldr / ldy >= N; Y may be X with
+ *                         ldy = ldx).  The backward pass of a site is the same call on the gradient.
+ * d3pm_op_attention_dropout_f32  d3pm_op_attention (generic family, fp32) with every normalised probability multiplied by
+ *                         z(h, i, j) before P V; utterance b draws with utt = utt0 + b
+ * d3pm_op_attention_bwd_dropout_f32  d3pm_op_attention_bwd_f32 of that forward (O = (P o Z) V); Tq, S <= 4096 */
 /* The condition-side embeddings as a single op (ar_discrete.py:736-741): which = 0 text rows W[tok] + pe0 (`tables` [n_classes][d],
  * `pe` [d]); which = 1 prompt rows sum_l W[l][tok_l] + pe[s] (`tokens` [rows][n_levels], -1 = level absent; `tables`
  * [n_levels][n_classes][d]; `pe` [s_prompt][d]).  Used by the training step, which needs the encoder inputs it stashes. */
@@ -531,6 +548,14 @@ int d3pm_op_embed_f32(const int32_t *tok, const uint8_t *mask, int period, const
                       void *stream);
 int d3pm_op_embed_bwd_f32(const int32_t *tok, const uint8_t *mask, int period, const float *dY, float *dTable, int rows, int d,
                           int n_classes, int padding_idx, void *stream);
+int d3pm_op_dropout_f32(const float *X, int ldx, const float *R, int ldr, float *Y, int ldy, int M, int N, float p, uint64_t seed,
+                        uint32_t utt, uint32_t site, void *stream);
+int d3pm_op_attention_dropout_f32(const float *Q, int ldq, const float *K, const float *V, int ldkv, float *O, int ldo, int B, int Tq,
+                                  int S, int H, int hd, float scale, float p, uint64_t seed, uint32_t utt0, uint32_t site, void *stream);
+int d3pm_op_attention_bwd_dropout_f32(const float *Q, int ldq, const float *K, const float *V, int ldkv, const float *dO, int ldo,
+                                      float *dQ, int lddq, float *dK, float *dV, int lddkv, float *stats, int B, int Tq, int S, int H,
+                                      int hd, float scale, float beta_kv, float p, uint64_t seed, uint32_t utt0, uint32_t site,
+                                      void *stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

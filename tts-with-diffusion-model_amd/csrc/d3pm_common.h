@@ -104,6 +104,18 @@ __host__ __device__ inline void noise4(uint64_t seed, uint32_t group, uint32_t r
 #pragma unroll
   for (int i = 0; i < 4; ++i) u[i] = static_cast<float>(c[i] >> 8) * 5.9604644775390625e-08f;  // 2^-24
 }
+// Dropout masks of the training step's condition encoders (DESIGN.md "Dropout mask stream"): stream 3,
+//   counter = (idx >> 2, utt, site, 3), word = idx & 3, keep <=> u >= p, kept value x * s (s = 1 / (1 - p) in fp32), dropped 0;
+//   site = (which << 8) | (layer << 4) | kind, idx = the logical element index (r * cols + c; attention (h * Tq + i) * S + j).
+constexpr uint32_t kStreamDropout = 3;
+// the factor z of one element (one Philox call per element: for the gathers of the attention kernels, whose indices are not
+// four consecutive ones; the elementwise op draws four elements per call)
+__device__ __forceinline__ float dropout_z(uint64_t seed, uint32_t utt, uint32_t site, uint32_t idx, float p, float s) {
+  float u[4];
+  noise4(seed, idx >> 2, utt, site, kStreamDropout, u);
+  const float w = (idx & 2) ? ((idx & 1) ? u[3] : u[2]) : ((idx & 1) ? u[1] : u[0]);    // selects, no dynamic register index
+  return w >= p ? s : 0.f;
+}
 // -log(-log(clamp(u, FLT_MIN, 1)))  (ar_discrete.py:416-417)
 __device__ __forceinline__ float gumbel(float u) {
   u = fminf(fmaxf(u, 1.17549435e-38f), 1.0f);

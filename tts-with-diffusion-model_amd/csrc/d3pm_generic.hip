@@ -171,13 +171,16 @@ __global__ __launch_bounds__(256) void linear_tiled(const T* __restrict__ X, int
 // dtype like the eager bmm/softmax/bmm chain.  LDS: per wave [S] floats + [hd] floats.
 template <typename T> struct alignas(16) Vec16 { T v[16 / sizeof(T)]; };
 
-template <typename T>
+// DROP (fp32 training step only): every normalised probability is multiplied by its dropout factor z(h, i, j) before P.V;
+// DROP = false is the kernel the denoiser has always run (the arm compiles away).
+template <typename T, bool DROP = false>
 __global__ __launch_bounds__(256) void attention_rows(const T* __restrict__ Q, int ldq,
                                                       const T* __restrict__ Kp,
                                                       const T* __restrict__ Vp, int ldkv,
                                                       T* __restrict__ O, int ldo, int Tq, int S_pad,
                                                       int hd, float scale, int q_per_wave,
-                                                      const int32_t* __restrict__ key_len) {
+                                                      const int32_t* __restrict__ key_len,
+                                                      DropoutArgs dr = DropoutArgs{}) {
   extern __shared__ float smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   float* sc = smem + static_cast<size_t>(wave) * (S_pad + hd);
@@ -224,6 +227,10 @@ __global__ __launch_bounds__(256) void attention_rows(const T* __restrict__ Q, i
       }
       sum = wave_sum(sum);
       for (int j = lane; j < S; j += kWave) sc[j] = rn<T>(sc[j] / sum);
+      if constexpr (DROP) {
+        const uint32_t row = (static_cast<uint32_t>(h) * Tq + i) * static_cast<uint32_t>(S), utt = dr.utt0 + b;
+        for (int j = lane; j < S; j += kWave) sc[j] *= dropout_z(dr.seed, utt, dr.site, row + j, dr.p, dr.s);
+      }
     }
     __syncthreads();
     if (active) {
@@ -357,22 +364,40 @@ int generic_linear(int dtype, const LinearArgs& a, hipStream_t s) {
   });
 }
 
-int generic_attention(int dtype, const AttnArgs& a, hipStream_t s) {
+static int generic_attention_shape(const AttnArgs& a) {
   bool pow2 = (a.hd & (a.hd - 1)) == 0;
   D3PM_REQUIRE((a.hd <= kWave && pow2) || a.hd % kWave == 0, D3PM_E_SHAPE,
                "generic attention needs head_dim a power of two <= 64 or a multiple of 64 (got %d)", a.hd);
+  D3PM_REQUIRE(static_cast<size_t>(4) * (a.S + a.hd) * sizeof(float) <= 64 * 1024, D3PM_E_SHAPE,
+               "generic attention: %d keys exceed the LDS budget", a.S);
+  return D3PM_OK;
+}
+
+int generic_attention(int dtype, const AttnArgs& a, hipStream_t s) {
+  if (int rc = generic_attention_shape(a)) return rc;
   return dispatch(dtype, [&](auto* tag) {
     using T = std::remove_pointer_t<decltype(tag)>;
     const int nw = 4, qpw = 4;
     dim3 grid((a.Tq + nw * qpw - 1) / (nw * qpw), a.H, a.B);
     size_t lds = static_cast<size_t>(nw) * (a.S + a.hd) * sizeof(float);
-    D3PM_REQUIRE(lds <= 64 * 1024, D3PM_E_SHAPE, "generic attention: %d keys exceed the LDS budget", a.S);
     attention_rows<T><<<grid, nw * kWave, lds, s>>>(static_cast<const T*>(a.Q), a.ldq, static_cast<const T*>(a.K),
                                                    static_cast<const T*>(a.V), a.ldkv, static_cast<T*>(a.O),
                                                    a.ldo, a.Tq, a.S, a.hd, a.scale, qpw, a.key_len);
     D3PM_LAUNCH_CHECK();
     return D3PM_OK;
   });
+}
+
+int generic_attention_dropout_f32(const AttnArgs& a, const DropoutArgs& dr, hipStream_t s) {
+  if (int rc = generic_attention_shape(a)) return rc;
+  const int nw = 4, qpw = 4;
+  dim3 grid((a.Tq + nw * qpw - 1) / (nw * qpw), a.H, a.B);
+  size_t lds = static_cast<size_t>(nw) * (a.S + a.hd) * sizeof(float);
+  attention_rows<float, true><<<grid, nw * kWave, lds, s>>>(static_cast<const float*>(a.Q), a.ldq, static_cast<const float*>(a.K),
+                                                            static_cast<const float*>(a.V), a.ldkv, static_cast<float*>(a.O), a.ldo,
+                                                            a.Tq, a.S, a.hd, a.scale, qpw, nullptr, dr);
+  D3PM_LAUNCH_CHECK();
+  return D3PM_OK;
 }
 
 }  // namespace d3pm

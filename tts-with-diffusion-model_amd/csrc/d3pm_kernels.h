@@ -147,6 +147,14 @@ struct SampleArgs {
 
 int generic_linear(int dtype, const LinearArgs& a, hipStream_t s);
 int generic_attention(int dtype, const AttnArgs& a, hipStream_t s);
+// probability dropout of a training-step attention (d3pm_common.h dropout_z): utterance b draws with utt = utt0 + b, s = 1 / (1 - p)
+struct DropoutArgs {
+  float p = 0.f, s = 1.f;
+  uint64_t seed = 0;
+  uint32_t utt0 = 0, site = 0;
+};
+// the fp32 generic attention with sc = rn(e / sum) * z(h, i, j) before P.V (training step; key_len / Q2 unsupported)
+int generic_attention_dropout_f32(const AttnArgs& a, const DropoutArgs& dr, hipStream_t s);
 int generic_layernorm(int dtype, const LayerNormArgs& a, hipStream_t s);
 int embed_tokens(int dtype, const EmbedArgs& a, hipStream_t s);
 // condition-side embeddings: text rows = rn(W[tok] + pe0); prompt rows = rn(rn(sum_l W[l][tok_l]) + pe[s])

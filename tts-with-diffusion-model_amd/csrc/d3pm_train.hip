@@ -214,10 +214,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows(const float* __restric
 // Attention backward, pass 1: one wave per (utterance, head, query).  P = softmax(scale * q . k^T) recomputed;
 // stats[.][0] = logsumexp of the scaled scores, stats[.][1] = D = dO . O = sum_j P_j (dO . v_j);
 // dQ = scale * sum_j P_j ((dO . v_j) - D) k_j
+// DROP (O = (P o Z) V, Z the probability-dropout factors of the forward, d3pm_common.h dropout_z): D = sum_j P_j Z_j (dO . v_j),
+// dQ = scale * sum_j P_j (Z_j (dO . v_j) - D) k_j.  The mask is drawn once per (query, key) into a bit set -- bit n of a lane is
+// key lane + 64 n, S <= 4096 -- so the column loop below only reads bits.  DROP = false is the kernel as it always was.
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_q_rows(const float* __restrict__ Q, int ldq, const float* __restrict__ Kp,
                                                        const float* __restrict__ Vp, int ldkv, const float* __restrict__ dO, int ldo,
                                                        float* __restrict__ dQ, int lddq, float* __restrict__ stats, int B, int Tq,
-                                                       int S, int H, int hd, float scale) {
+                                                       int S, int H, int hd, float scale, DropoutArgs dr = DropoutArgs{}) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const long idx = static_cast<long>(blockIdx.x) * 4 + wave;
   if (idx >= static_cast<long>(B) * H * Tq) return;
@@ -233,6 +237,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_rows(const float* __restrict__
     mx = fmaxf(mx, sc);
   }
   mx = wave_max(mx);
+  uint64_t keep = 0;
   float l = 0.f, dsum = 0.f;
   for (int j = lane; j < S; j += kWave) {
     float sc = 0.f, dp = 0.f;
@@ -242,6 +247,11 @@ __global__ __launch_bounds__(256) void attn_bwd_q_rows(const float* __restrict__
     }
     const float e = expf(sc - mx);
     l += e;
+    if constexpr (DROP) {
+      const float z = dropout_z(dr.seed, dr.utt0 + b, dr.site, (static_cast<uint32_t>(h) * Tq + i) * static_cast<uint32_t>(S) + j, dr.p, dr.s);
+      if (z != 0.f) keep |= 1ull << (j >> 6);
+      dp *= z;
+    }
     dsum += e * dp;
   }
   l = wave_sum(l);
@@ -256,6 +266,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_rows(const float* __restrict__
         sc = fmaf(q[c] * scale, kb[static_cast<size_t>(j) * ldkv + c], sc);
         dp = fmaf(go[c], vb[static_cast<size_t>(j) * ldkv + c], dp);
       }
+      if constexpr (DROP) dp *= ((keep >> (j >> 6)) & 1) ? dr.s : 0.f;
       const float p = expf(sc - lse);
       part = fmaf(p * (dp - D), kb[static_cast<size_t>(j) * ldkv + c0], part);
     }
@@ -265,11 +276,14 @@ __global__ __launch_bounds__(256) void attn_bwd_q_rows(const float* __restrict__
 }
 
 // pass 2: one wave per (utterance, head, key):  dV_j = sum_i P_ij dO_i,  dK_j = scale * sum_i P_ij ((dO_i . v_j) - D_i) q_i
+// DROP: dV_j = sum_i P_ij Z_ij dO_i,  dK_j = scale * sum_i P_ij (Z_ij (dO_i . v_j) - D_i) q_i  (bit n of a lane: query lane + 64 n,
+// Tq <= 4096)
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_kv_rows(const float* __restrict__ Q, int ldq, const float* __restrict__ Kp,
                                                         const float* __restrict__ Vp, int ldkv, const float* __restrict__ dO, int ldo,
                                                         float* __restrict__ dK, float* __restrict__ dV, int lddkv,
                                                         const float* __restrict__ stats, int B, int Tq, int S, int H, int hd,
-                                                        float scale, float beta) {
+                                                        float scale, float beta, DropoutArgs dr = DropoutArgs{}) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const long idx = static_cast<long>(blockIdx.x) * 4 + wave;
   if (idx >= static_cast<long>(B) * H * S) return;
@@ -281,6 +295,11 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_rows(const float* __restrict_
   const float* st = stats + (static_cast<size_t>(b) * H + h) * Tq * 2;
   float* dk = dK + (static_cast<size_t>(b) * S + j) * lddkv + h * hd;
   float* dv = dV + (static_cast<size_t>(b) * S + j) * lddkv + h * hd;
+  uint64_t keep = 0;
+  if constexpr (DROP)
+    for (int i = lane; i < Tq; i += kWave)
+      if (dropout_z(dr.seed, dr.utt0 + b, dr.site, (static_cast<uint32_t>(h) * Tq + i) * static_cast<uint32_t>(S) + j, dr.p, dr.s) != 0.f)
+        keep |= 1ull << (i >> 6);
   for (int c0 = 0; c0 < hd; ++c0) {
     float pk = 0.f, pv = 0.f;
     for (int i = lane; i < Tq; i += kWave) {
@@ -290,7 +309,13 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_rows(const float* __restrict_
         dp = fmaf(gb[static_cast<size_t>(i) * ldo + c], v[c], dp);
       }
       const float p = expf(sc - st[i * 2]);
-      pv = fmaf(p, gb[static_cast<size_t>(i) * ldo + c0], pv);
+      float pz = p;
+      if constexpr (DROP) {
+        const float z = ((keep >> (i >> 6)) & 1) ? dr.s : 0.f;
+        pz = p * z;
+        dp *= z;
+      }
+      pv = fmaf(pz, gb[static_cast<size_t>(i) * ldo + c0], pv);
       pk = fmaf(p * (dp - st[i * 2 + 1]), qb[static_cast<size_t>(i) * ldq + c0], pk);
     }
     pk = wave_sum(pk);
@@ -299,6 +324,27 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_rows(const float* __restrict_
       dk[c0] = beta == 0.f ? pk * scale : fmaf(beta, dk[c0], pk * scale);
       dv[c0] = beta == 0.f ? pv : fmaf(beta, dv[c0], pv);
     }
+  }
+}
+
+// Elementwise dropout with an optional residual: Y = (R ? R + X z : X z), z = keep ? s : 0 (d3pm_common.h dropout_z), over the
+// logical [M][N] index r * N + c whatever the row strides.  One thread = four consecutive logical elements = one Philox call
+// (the four may straddle a row end).  Y may be X (in place): each element is read and written by the same thread.
+__global__ __launch_bounds__(256) void dropout_rows(const float* X, int ldx, const float* R, int ldr, float* Y, int ldy, int M, int N,
+                                                    DropoutArgs dr) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t n = static_cast<uint64_t>(M) * N;        // <= 2^32 (host check)
+  if (g >= (n + 3) / 4) return;
+  float u[4];
+  noise4(dr.seed, g, dr.utt0, dr.site, kStreamDropout, u);
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const uint64_t e = 4ull * g + w;
+    if (e >= n) break;
+    const uint32_t r = static_cast<uint32_t>(e / N), c = static_cast<uint32_t>(e % N);
+    const float z = u[w] >= dr.p ? dr.s : 0.f;
+    const float x = X[static_cast<size_t>(r) * ldx + c] * z;
+    Y[static_cast<size_t>(r) * ldy + c] = R ? R[static_cast<size_t>(r) * ldr + c] + x : x;
   }
 }
 
@@ -408,8 +454,8 @@ int d3pm_op_attention_bwd_f32(const float* Q, int ldq, const float* K, const flo
                "d3pm_op_attention_bwd_f32: bad arguments");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const long nq = static_cast<long>(B) * H * Tq, nk = static_cast<long>(B) * H * S;
-  attn_bwd_q_rows<<<static_cast<unsigned>((nq + 3) / 4), 256, 0, s>>>(Q, ldq, K, V, ldkv, dO, ldo, dQ, lddq, stats, B, Tq, S, H, hd, scale);
-  attn_bwd_kv_rows<<<static_cast<unsigned>((nk + 3) / 4), 256, 0, s>>>(Q, ldq, K, V, ldkv, dO, ldo, dK, dV, lddkv, stats, B, Tq, S, H, hd,
+  attn_bwd_q_rows<><<<static_cast<unsigned>((nq + 3) / 4), 256, 0, s>>>(Q, ldq, K, V, ldkv, dO, ldo, dQ, lddq, stats, B, Tq, S, H, hd, scale);
+  attn_bwd_kv_rows<><<<static_cast<unsigned>((nk + 3) / 4), 256, 0, s>>>(Q, ldq, K, V, ldkv, dO, ldo, dK, dV, lddkv, stats, B, Tq, S, H, hd,
                                                                       scale, beta_kv);
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
@@ -440,6 +486,67 @@ int d3pm_op_embed_bwd_f32(const int32_t* tok, const uint8_t* mask, int period, c
   const size_t n = static_cast<size_t>(rows) * d;
   embed_bwd_rows<<<static_cast<unsigned>((n + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(tok, mask, period > 0 ? period : 1, dY,
                                                                                                       dTable, rows, d, n_classes, padding_idx);
+  D3PM_LAUNCH_CHECK();
+  return D3PM_OK;
+}
+
+// ---- dropout of the condition encoders' training step (d3pm_common.h dropout_z; DESIGN.md "Dropout mask stream") ----------------
+static int dropout_args(float p, uint64_t seed, uint32_t utt0, uint32_t site, DropoutArgs& dr) {
+  D3PM_REQUIRE(p >= 0.f && p < 1.f, D3PM_E_ARG, "dropout: p = %g is outside [0, 1)", p);
+  dr.p = p;
+  dr.s = 1.0f / (1.0f - p);
+  dr.seed = seed;
+  dr.utt0 = utt0;
+  dr.site = site;
+  return D3PM_OK;
+}
+constexpr uint64_t kMaxIdx = 1ull << 32;     // the mask's element index is 32 bits wide
+
+int d3pm_op_dropout_f32(const float* X, int ldx, const float* R, int ldr, float* Y, int ldy, int M, int N, float p, uint64_t seed,
+                        uint32_t utt, uint32_t site, void* stream) {
+  D3PM_REQUIRE(X && Y && M > 0 && N > 0 && ldx >= N && ldy >= N && (!R || ldr >= N) && (Y != X || ldy == ldx), D3PM_E_ARG,
+               "d3pm_op_dropout_f32: bad arguments");
+  D3PM_REQUIRE(static_cast<uint64_t>(M) * N <= kMaxIdx, D3PM_E_SHAPE, "d3pm_op_dropout_f32: %d x %d elements exceed the 32-bit mask index", M,
+               N);
+  DropoutArgs dr;
+  if (int rc = dropout_args(p, seed, utt, site, dr)) return rc;
+  const uint64_t groups = (static_cast<uint64_t>(M) * N + 3) / 4;
+  dropout_rows<<<static_cast<unsigned>((groups + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(X, ldx, R, ldr, Y, ldy, M, N, dr);
+  D3PM_LAUNCH_CHECK();
+  return D3PM_OK;
+}
+
+int d3pm_op_attention_dropout_f32(const float* Q, int ldq, const float* K, const float* V, int ldkv, float* O, int ldo, int B, int Tq, int S,
+                                  int H, int hd, float scale, float p, uint64_t seed, uint32_t utt0, uint32_t site, void* stream) {
+  D3PM_REQUIRE(Q && K && V && O && B > 0 && Tq > 0 && S > 0 && H > 0 && hd > 0, D3PM_E_ARG, "d3pm_op_attention_dropout_f32: bad arguments");
+  D3PM_REQUIRE(static_cast<uint64_t>(H) * Tq * S <= kMaxIdx, D3PM_E_SHAPE,
+               "d3pm_op_attention_dropout_f32: %d x %d x %d probabilities exceed the 32-bit mask index", H, Tq, S);
+  DropoutArgs dr;
+  if (int rc = dropout_args(p, seed, utt0, site, dr)) return rc;
+  AttnArgs a;
+  a.Q = Q; a.ldq = ldq; a.K = K; a.V = V; a.ldkv = ldkv; a.O = O; a.ldo = ldo; a.B = B; a.Tq = Tq; a.S = S; a.H = H;
+  a.hd = hd; a.scale = scale;
+  return generic_attention_dropout_f32(a, dr, static_cast<hipStream_t>(stream));
+}
+
+int d3pm_op_attention_bwd_dropout_f32(const float* Q, int ldq, const float* K, const float* V, int ldkv, const float* dO, int ldo,
+                                      float* dQ, int lddq, float* dK, float* dV, int lddkv, float* stats, int B, int Tq, int S, int H,
+                                      int hd, float scale, float beta_kv, float p, uint64_t seed, uint32_t utt0, uint32_t site,
+                                      void* stream) {
+  D3PM_REQUIRE(Q && K && V && dO && dQ && dK && dV && stats && B > 0 && Tq > 0 && S > 0 && H > 0 && hd > 0, D3PM_E_ARG,
+               "d3pm_op_attention_bwd_dropout_f32: bad arguments");
+  D3PM_REQUIRE(static_cast<uint64_t>(H) * Tq * S <= kMaxIdx, D3PM_E_SHAPE,
+               "d3pm_op_attention_bwd_dropout_f32: %d x %d x %d probabilities exceed the 32-bit mask index", H, Tq, S);
+  D3PM_REQUIRE(Tq <= 64 * kWave && S <= 64 * kWave, D3PM_E_SHAPE,
+               "d3pm_op_attention_bwd_dropout_f32: the per-lane mask bits hold at most 4096 queries and keys (got %d, %d)", Tq, S);
+  DropoutArgs dr;
+  if (int rc = dropout_args(p, seed, utt0, site, dr)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long nq = static_cast<long>(B) * H * Tq, nk = static_cast<long>(B) * H * S;
+  attn_bwd_q_rows<true><<<static_cast<unsigned>((nq + 3) / 4), 256, 0, s>>>(Q, ldq, K, V, ldkv, dO, ldo, dQ, lddq, stats, B, Tq, S, H, hd,
+                                                                             scale, dr);
+  attn_bwd_kv_rows<true><<<static_cast<unsigned>((nk + 3) / 4), 256, 0, s>>>(Q, ldq, K, V, ldkv, dO, ldo, dK, dV, lddkv, stats, B, Tq, S,
+                                                                              H, hd, scale, beta_kv, dr);
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

@@ -346,17 +346,22 @@ class AR(SymmapState, nn.Module):
         fm = mask.to(torch.uint8).contiguous()
         return smp.q_sample(x_start.to(torch.int32).contiguous(), fm, int(t.reshape(-1)[0]), seed, utt0).long()
 
-    def forward_backward(self, text_list, proms_list, resps_list, *, seed: Optional[int] = None, timesteps: Optional[int] = None):
+    def forward_backward(self, text_list, proms_list, resps_list, *, seed: Optional[int] = None, timesteps: Optional[int] = None,
+                         dropout=False, utt0: int = 0):
         """The training step's compute (reference: `engine.backward(engine(...))`, utils/engines.py:144-147 over
         ar_discrete.py:588-694): the loss of `forward` AND its gradient for every parameter the forward reads, accumulated
         into `param.grad` by the HIP backward kernels (vall_e/vall_e/train.py; fp32 model).  Follow it with
         `train.all_reduce_gradients(self)` under torch.distributed and any torch.optim step.  Returns the loss.
-        Eval-mode arithmetic: the dropout the reference applies inside its condition encoders in train mode (p = 0.1 /
-        0.01, ar_discrete.py:216-230) is omitted (vall_e/vall_e/train.py)."""
+        dropout=True applies the dropout the reference's condition encoders apply in train mode (p = 0.1 / 0.01,
+        ar_discrete.py:216-230) from a Philox mask keyed by (seed, utterance, site); a (p_layer, p_mlp) pair sets other
+        probabilities; the default False is eval-mode arithmetic (`self.training` is not consulted).  Upstream's masks come
+        from torch's global generator, a stream that is not reproduced.  utt0: global index of the first utterance (a
+        data-parallel rank passes its shard offset), which keys the q_sample noise and the masks."""
         from .train import D3PMTrainer
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        loss, _ = D3PMTrainer(self).forward_backward(text_list, proms_list, resps_list, seed=seed, timesteps=timesteps)
+        loss, _ = D3PMTrainer(self).forward_backward(text_list, proms_list, resps_list, seed=seed, timesteps=timesteps, dropout=dropout,
+                                                     utt0=utt0)
         return loss
 
     @torch.no_grad()

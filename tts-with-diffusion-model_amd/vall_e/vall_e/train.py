@@ -17,15 +17,21 @@ via `timestep_fc` -- and, through the cached cross-attention K / V, into the two
 two post-norm TransformerEncoder layers + a SiLU Mlp each) and their embeddings `text_emb` (padding row 0 excluded, as
 nn.Embedding(padding_idx=0) does) and `proms_emb`.
 
-Dropout is NOT applied: the step is the eval-mode forward (`model.eval()`), and the gradient fixtures were generated that
-way (tests/golden/make_golden.py gen_grads).  The reference trains with dropout active -- p = 0.1 inside both condition
-encoders' TransformerEncoderLayers and drop = 0.01 in their Mlp (ar_discrete.py:216-230) -- drawn from torch's global
-generator, a stream this build cannot reproduce; the DiT blocks themselves have dropout 0 (:109,123).  A training run
-that needs the regulariser has to add it outside this step.
+Dropout: by default the step is the eval-mode forward (`model.eval()`), which is how the gradient fixtures were generated
+(tests/golden/make_golden.py gen_grads).  The reference trains with dropout active inside both condition encoders
+(ar_discrete.py:216-230): p = 0.1 at the four sites of each TransformerEncoderLayer (attention probabilities, after the
+self-attention out_proj, the FFN hidden after the ReLU, after linear2) and drop = 0.01 at the two of its Mlp (after the SiLU,
+after fc2); the DiT blocks have dropout 0 (:109,123).  `forward_backward(dropout=True)` applies those six sites, and
+`dropout=(p_layer, p_mlp)` other probabilities.  The masks come from a counter-based Philox stream keyed by (seed, utterance,
+site) (include/d3pm_hip.h, DESIGN.md "Dropout mask stream"), drawn once per utterance per call as upstream's encoders run once
+per forward, and regenerated in the backward pass rather than stored.  Upstream draws them from torch's global generator; that
+stream itself is not reproduced.  The argument is explicit on purpose: `model.training` is not consulted (a freshly built
+nn.Module is in train mode, and honouring the flag would change what every existing caller computes).
 """
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 from typing import Optional, Sequence
 
 import torch
@@ -96,16 +102,82 @@ def layernorm_bwd(x, dout, w, b, dx, dw, db, film=None, dfilm=None, eps=1e-6, ac
                                                     _hip.stream_ptr()), "d3pm_op_layernorm_bwd_f32")
 
 
-def attention_bwd(q, k, v, do, dq, dk, dv, n_heads, scale, beta_kv=0.0):
-    """q [B,Tq,d], k / v [B,S,d] views (row strides free), do [B,Tq,d]; dq / dk / dv views of the same shapes."""
+def attention_bwd(q, k, v, do, dq, dk, dv, n_heads, scale, beta_kv=0.0, drop=None):
+    """q [B,Tq,d], k / v [B,S,d] views (row strides free), do [B,Tq,d]; dq / dk / dv views of the same shapes.  drop = (p, seed,
+    utt0, site): the backward pass of attention_dropout with those arguments."""
     B, Tq, d = q.shape
     S = k.shape[1]
     hd = d // n_heads
     stats = torch.empty(B * n_heads * Tq * 2, dtype=torch.float32, device=q.device)
     assert k.stride(1) == v.stride(1) and dk.stride(1) == dv.stride(1)
+    if drop is not None:
+        p, seed, utt0, site = drop
+        _hip.check(_hip.lib().d3pm_op_attention_bwd_dropout_f32(
+            _ptr(_f32(q, "q")), q.stride(1), _ptr(_f32(k, "k")), _ptr(_f32(v, "v")), k.stride(1), _ptr(_f32(do, "do")), do.stride(1), _ptr(dq),
+            dq.stride(1), _ptr(dk), _ptr(dv), dk.stride(1), _ptr(stats), B, Tq, S, n_heads, hd, float(scale), float(beta_kv), float(p),
+            _seed(seed), utt0, site, _hip.stream_ptr()), "d3pm_op_attention_bwd_dropout_f32")
+        return
     _hip.check(_hip.lib().d3pm_op_attention_bwd_f32(_ptr(q), q.stride(1), _ptr(k), _ptr(v), k.stride(1), _ptr(do), do.stride(1), _ptr(dq),
                                                     dq.stride(1), _ptr(dk), _ptr(dv), dk.stride(1), _ptr(stats), B, Tq, S, n_heads, hd,
                                                     float(scale), float(beta_kv), _hip.stream_ptr()), "d3pm_op_attention_bwd_f32")
+
+
+def attention_dropout(q, k, v, n_heads, scale, p, seed, utt0, site):
+    """softmax(scale q k^T) with probability dropout, times v (d3pm_op_attention_dropout_f32): q [B,Tq,d], k / v [B,S,d] views
+    (row strides free); utterance b draws its mask with utt0 + b.  -> [B,Tq,d]."""
+    B, Tq, d = q.shape
+    S = k.shape[1]
+    assert k.stride(1) == v.stride(1) and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    assert q.stride(0) == Tq * q.stride(1) and k.stride(0) == S * k.stride(1) and v.stride(0) == S * v.stride(1)
+    o = torch.empty((B, Tq, d), dtype=torch.float32, device=q.device)
+    _hip.check(_hip.lib().d3pm_op_attention_dropout_f32(_ptr(_f32(q, "q")), q.stride(1), _ptr(_f32(k, "k")), _ptr(_f32(v, "v")), k.stride(1),
+                                                        _ptr(o), d, B, Tq, S, n_heads, d // n_heads, float(scale), float(p), _seed(seed),
+                                                        utt0, site, _hip.stream_ptr()), "d3pm_op_attention_dropout_f32")
+    return o
+
+
+def dropout(x, p, seed, utt, site, *, residual=None, out=None):
+    """out = (residual +) x * z over the 2-D view x (d3pm_op_dropout_f32; row strides free, `out=x` works in place), z the
+    mask factor of (seed, utt, site) at each logical index r * cols + c.  Also the backward pass of the site, on the gradient."""
+    M, N = x.shape
+    y = torch.empty((M, N), dtype=torch.float32, device=x.device) if out is None else out
+    for t_ in (x, y) + (() if residual is None else (residual,)):
+        assert t_.stride(1) == 1 and tuple(t_.shape) == (M, N)
+    _hip.check(_hip.lib().d3pm_op_dropout_f32(_ptr(_f32(x, "x")), x.stride(0), _ptr(residual), 0 if residual is None else residual.stride(0),
+                                              _ptr(_f32(y, "out")), y.stride(0), M, N, float(p), _seed(seed), utt, site, _hip.stream_ptr()),
+               "d3pm_op_dropout_f32")
+    return y
+
+
+def _seed(seed: int) -> int:
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+DROPOUT_TRAIN = (0.1, 0.01)      # (p_layer, p_mlp): nn.TransformerEncoderLayer's default and the Mlp's drop (ar_discrete.py:216-230)
+MLP_LAYER = 15                   # the `layer` field of the Mlp's two sites
+
+
+def dropout_probs(dropout) -> tuple:
+    """The `dropout` argument of forward_backward -> (p_layer, p_mlp): False / None -> (0, 0), True -> the reference's
+    (0.1, 0.01), a pair of numbers -> itself.  Each p must lie in [0, 1); anything else raises ValueError."""
+    if dropout is None or dropout is False:
+        return 0.0, 0.0
+    if dropout is True:
+        return DROPOUT_TRAIN
+    if not isinstance(dropout, (tuple, list)) or len(dropout) != 2 or \
+            not all(isinstance(p, numbers.Real) and not isinstance(p, bool) for p in dropout):
+        raise ValueError(f"dropout: expected True / False or a (p_layer, p_mlp) pair of numbers, got {dropout!r}")
+    p_layer, p_mlp = float(dropout[0]), float(dropout[1])
+    for p in (p_layer, p_mlp):
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"dropout: every probability must lie in [0, 1), got {dropout!r}")
+    return p_layer, p_mlp
+
+
+def dropout_site(which: int, layer: int, kind: int) -> int:
+    """Site number of the mask stream: which 0 text / 1 prompt encoder; layer 0 .. cond_layers - 1 with kind 0 attention
+    probabilities, 1 after out_proj, 2 FFN hidden, 3 after linear2; layer MLP_LAYER with kind 0 after SiLU, 1 after fc2."""
+    return (which << 8) | (layer << 4) | kind
 
 
 def ce_bwd(logits, targets, frame_mask, gscale):
@@ -146,8 +218,11 @@ class D3PMTrainer:
         self.model = model
 
     # ---- condition encoders (once per utterance) with a stash ------------------------------------------------
-    def _encode(self, which, tokens):
-        """which 0: text int32 [S_t]; 1: prompt int32 [S_p, n_levels] -> (cond [S, d], stash)."""
+    def _encode(self, which, tokens, drop=(0.0, 0.0, 0, 0)):
+        """which 0: text int32 [S_t]; 1: prompt int32 [S_p, n_levels] -> (cond [S, d], stash).  drop = (p_layer, p_mlp, seed,
+        utt): the six dropout sites (module docstring); a site with p = 0 is the eval-mode op.  The stash keeps the dropped
+        tensors that the weight gradients read (linear2's and fc2's inputs)."""
+        p_layer, p_mlp, seed, utt = drop
         m, cfg = self.model, self.model.cfg
         d = cfg.d_model
         G = _hip.FAMILY_GENERIC
@@ -163,21 +238,36 @@ class D3PMTrainer:
         H = cfg.cond_heads
         scale = (1.0 / (d // H)) ** 0.5
         layers = []
-        for layer in enc[0].layers:
+        for l, layer in enumerate(enc[0].layers):
             s = {"x": x}
             s["qkv"] = lin(x, layer.self_attn.in_proj_weight, layer.self_attn.in_proj_bias)
             qkv = s["qkv"].view(1, rows, 3 * d)
-            s["att"] = _hip.op_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale, family=G).view(rows, d)
-            s["t1"] = lin(s["att"], layer.self_attn.out_proj.weight, layer.self_attn.out_proj.bias, r1=x)
+            q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
+            if p_layer > 0:                 # t1 = x + dropout1(out_proj(attention with dropped probabilities))
+                s["att"] = attention_dropout(q, k, v, H, scale, p_layer, seed, utt, dropout_site(which, l, 0)).view(rows, d)
+                s["t1"] = dropout(lin(s["att"], layer.self_attn.out_proj.weight, layer.self_attn.out_proj.bias), p_layer, seed, utt,
+                                  dropout_site(which, l, 1), residual=x)
+            else:
+                s["att"] = _hip.op_attention(q, k, v, H, scale, family=G).view(rows, d)
+                s["t1"] = lin(s["att"], layer.self_attn.out_proj.weight, layer.self_attn.out_proj.bias, r1=x)
             s["x1"] = _hip.op_layernorm(s["t1"], layer.norm1.weight, layer.norm1.bias, eps=1e-5)
             s["ff"] = lin(s["x1"], layer.linear1.weight, layer.linear1.bias, act=RELU)
-            s["t2"] = lin(s["ff"], layer.linear2.weight, layer.linear2.bias, r1=s["x1"])
+            if p_layer > 0:                 # t2 = x1 + dropout2(linear2(dropout(relu(linear1(x1)))))
+                dropout(s["ff"], p_layer, seed, utt, dropout_site(which, l, 2), out=s["ff"])
+                s["t2"] = dropout(lin(s["ff"], layer.linear2.weight, layer.linear2.bias), p_layer, seed, utt, dropout_site(which, l, 3),
+                                  residual=s["x1"])
+            else:
+                s["t2"] = lin(s["ff"], layer.linear2.weight, layer.linear2.bias, r1=s["x1"])
             x = _hip.op_layernorm(s["t2"], layer.norm2.weight, layer.norm2.bias, eps=1e-5)
             layers.append(s)
         mlp = enc[1]
         top = {"x": x, "u": lin(x, mlp.fc1.weight, mlp.fc1.bias), "h": lin(x, mlp.fc1.weight, mlp.fc1.bias, act=SILU)}
+        if p_mlp > 0:                       # drop1 after the SiLU
+            dropout(top["h"], p_mlp, seed, utt, dropout_site(which, MLP_LAYER, 0), out=top["h"])
         cond = lin(top["h"], mlp.fc2.weight, mlp.fc2.bias)
-        return cond, {"which": which, "tokens": tokens, "layers": layers, "top": top}
+        if p_mlp > 0:                       # drop2 after fc2
+            dropout(cond, p_mlp, seed, utt, dropout_site(which, MLP_LAYER, 1), out=cond)
+        return cond, {"which": which, "tokens": tokens, "layers": layers, "top": top, "drop": drop}
 
     def _encode_backward(self, stash, dcond):
         m, cfg = self.model, self.model.cfg
@@ -188,29 +278,41 @@ class D3PMTrainer:
         rows = tokens.shape[0]
         dev = dcond.device
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        p_layer, p_mlp, seed, utt = stash["drop"]
         mlp = enc[1]
+        if p_mlp > 0:                                            # drop2 (a copy: the caller keeps dcond)
+            dcond = dropout(dcond, p_mlp, seed, utt, dropout_site(which, MLP_LAYER, 1))
         dh = new(rows, top["h"].shape[1])
         linear_bwd(top["h"], mlp.fc2.weight, dcond, _grad(mlp.fc2.weight), _grad(mlp.fc2.bias), dh)
+        if p_mlp > 0:                                            # drop1
+            dropout(dh, p_mlp, seed, utt, dropout_site(which, MLP_LAYER, 0), out=dh)
         du = act_bwd(top["u"], dh, SILU)
         dx = new(rows, d)
         linear_bwd(top["x"], mlp.fc1.weight, du, _grad(mlp.fc1.weight), _grad(mlp.fc1.bias), dx)
-        for layer, s in reversed(list(zip(enc[0].layers, stash["layers"]))):
+        for l, layer, s in reversed([(l, layer, s) for l, (layer, s) in enumerate(zip(enc[0].layers, stash["layers"]))]):
             dt2 = new(rows, d)                                   # x = LN(t2; norm2), t2 = x1 + linear2(relu(linear1(x1)))
             layernorm_bwd(s["t2"], dx, layer.norm2.weight, layer.norm2.bias, dt2, _grad(layer.norm2.weight), _grad(layer.norm2.bias),
                           eps=1e-5, accumulate=False)
+            # dropout2 (a copy: dt2 goes on to collect the residual branch's gradient)
+            dl2 = dropout(dt2, p_layer, seed, utt, dropout_site(which, l, 3)) if p_layer > 0 else dt2
             dff = new(rows, s["ff"].shape[1])
-            linear_bwd(s["ff"], layer.linear2.weight, dt2, _grad(layer.linear2.weight), _grad(layer.linear2.bias), dff)
-            dpre = act_bwd(s["ff"], dff, RELU)                    # relu'(u) = [u > 0] = [relu(u) > 0]
+            linear_bwd(s["ff"], layer.linear2.weight, dl2, _grad(layer.linear2.weight), _grad(layer.linear2.bias), dff)
+            if p_layer > 0:                                      # dropout on the FFN hidden
+                dropout(dff, p_layer, seed, utt, dropout_site(which, l, 2), out=dff)
+            # relu'(u) = [u > 0] = [relu(u) > 0]; with dropout s["ff"] is the dropped hidden, which keeps the sign where kept,
+            # and dff is already 0 where dropped
+            dpre = act_bwd(s["ff"], dff, RELU)
             linear_bwd(s["x1"], layer.linear1.weight, dpre, _grad(layer.linear1.weight), _grad(layer.linear1.bias), dt2, dx_beta=1.0)
             dt1 = new(rows, d)                                   # x1 = LN(t1; norm1), t1 = x + out_proj(attention)
             layernorm_bwd(s["t1"], dt2, layer.norm1.weight, layer.norm1.bias, dt1, _grad(layer.norm1.weight), _grad(layer.norm1.bias),
                           eps=1e-5, accumulate=False)
+            do = dropout(dt1, p_layer, seed, utt, dropout_site(which, l, 1)) if p_layer > 0 else dt1     # dropout1 (a copy)
             datt = new(rows, d)
-            linear_bwd(s["att"], layer.self_attn.out_proj.weight, dt1, _grad(layer.self_attn.out_proj.weight),
+            linear_bwd(s["att"], layer.self_attn.out_proj.weight, do, _grad(layer.self_attn.out_proj.weight),
                        _grad(layer.self_attn.out_proj.bias), datt)
             qkv, dqkv = s["qkv"].view(1, rows, 3 * d), new(1, rows, 3 * d)
             attention_bwd(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], datt.view(1, rows, d), dqkv[..., :d], dqkv[..., d:2 * d],
-                          dqkv[..., 2 * d:], H, scale)
+                          dqkv[..., 2 * d:], H, scale, drop=(p_layer, seed, utt, dropout_site(which, l, 0)) if p_layer > 0 else None)
             dx = dt1                                             # residual branch; the in-projection adds its part
             linear_bwd(s["x"], layer.self_attn.in_proj_weight, dqkv.view(rows, 3 * d), _grad(layer.self_attn.in_proj_weight),
                        _grad(layer.self_attn.in_proj_bias), dx, dx_beta=1.0)
@@ -314,10 +416,14 @@ class D3PMTrainer:
 
     @torch.no_grad()
     def forward_backward(self, text_list: Sequence[torch.Tensor], proms_list: Sequence[torch.Tensor], resps_list: Sequence[torch.Tensor],
-                         *, seed: int = 0, timesteps: Optional[int] = None):
-        """The loss of AR.forward (mean over the utterances) and its gradient, accumulated into `param.grad`; eval-mode
-        arithmetic (no dropout in the condition encoders: module docstring).
+                         *, seed: int = 0, timesteps: Optional[int] = None, dropout=False, utt0: int = 0):
+        """The loss of AR.forward (mean over the utterances) and its gradient, accumulated into `param.grad`.
+        dropout: False (default) = eval-mode arithmetic; True = the reference's train-mode condition encoders (p 0.1 in the
+        encoder layers, 0.01 in the Mlp); a (p_layer, p_mlp) pair = those probabilities (dropout_probs; module docstring).
+        utt0: global index of this call's first utterance -- utterance b keys its q_sample noise and its dropout masks with
+        utt0 + b, so data-parallel ranks that pass their shard offset draw what one process over the whole batch would.
         Returns (loss fp32 scalar tensor, [(dcond_text, dcond_prompt)] per utterance)."""
+        p_layer, p_mlp = dropout_probs(dropout)
         m, cfg = self.model, self.model.cfg
         smp = m.sampler()
         T = m.timesteps if timesteps is None else int(timesteps)
@@ -334,14 +440,15 @@ class D3PMTrainer:
                 prom_p = prom_p[0].to(torch.int32)
                 if prom_p.shape[-1] < cfg.n_levels:
                     prom_p = F.pad(prom_p, (0, cfg.n_levels - prom_p.shape[-1]), value=-1)
-                cond_t2, st_t = self._encode(0, text_p[0].to(torch.int32).contiguous())
-                cond_p2, st_p = self._encode(1, prom_p.contiguous())
+                drop = (p_layer, p_mlp, seed, utt0 + b)
+                cond_t2, st_t = self._encode(0, text_p[0].to(torch.int32).contiguous(), drop)
+                cond_p2, st_p = self._encode(1, prom_p.contiguous(), drop)
                 kv_t, kv_p = smp.cond_kv(cond_t2[None], cond_p2[None])
                 dcond_t, dcond_p = torch.zeros_like(cond_t2), torch.zeros_like(cond_p2)
                 gscale = 1.0 / (cfg.canvas * max(n_live, 1) * B)
                 total = torch.zeros((), dtype=torch.float32, device=m.device)
                 for t in range(1, T):
-                    x_t = smp.q_sample(x0, fm, t, seed, b)
+                    x_t = smp.q_sample(x0, fm, t, seed, utt0 + b)
                     x_last, logits, stash = self._forward(x_t, fm, t, kv_t, kv_p, smp.film)
                     total += smp.ce_loss_rows(logits.view(1, cfg.canvas, cfg.n_classes), targets.view(1, -1), fm).mean()
                     self._backward(x_t, fm, t, kv_t, kv_p, cond_t2, cond_p2, dcond_t, dcond_p, x_last, logits, stash, targets, gscale)
