@@ -155,8 +155,10 @@ __global__ void act_bwd_k(const float* __restrict__ U, const float* __restrict__
   } else if (act == ACT_RELU) {
     g = u > 0.f ? 1.f : 0.f;
   } else {
-    const float sg = 1.0f / (1.0f + expf(-u));
-    g = sg * (1.0f + u * (1.0f - sg));
+    // 1 - sigmoid(u) as sigmoid(-u), not by subtraction: near u = 17, 1 + e^-u rounds by up to 2^-24, and u times that
+    // cancellation error reached 1.5e-6 of dM
+    const float sg = 1.0f / (1.0f + expf(-u)), sn = 1.0f / (1.0f + expf(u));
+    g = sg * (1.0f + u * sn);
   }
   dU[i] = dM[i] * g;
 }
