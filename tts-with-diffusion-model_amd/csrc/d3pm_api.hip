@@ -221,154 +221,211 @@ static int check_shape(const d3pm_shape* sh, int batch) {
 static const char* at(const void* p, size_t elems, size_t es) { return static_cast<const char*>(p) + elems * es; }
 static char* at(void* p, size_t elems, size_t es) { return static_cast<char*>(p) + elems * es; }
 
-// The block sequence with the LayerNorms folded into the projections (ar_discrete.py:126-161; d3pm_mfma_tile.h EPI_LNF / EPI_STATS):
+// ---- argument builders: the shapes the launch sequences below repeat -----------------------------------------------------
+// Y[M][N] = X[M][K] . W[N][K]^T + bias over packed rows (ldx = K, ldy = N); a caller with a wider output row sets ldy afterwards
+static LinearArgs projection(const void* X, const void* W, const void* bias, void* Y, int M, int N, int K, int act = ACT_NONE) {
+  LinearArgs g;
+  g.X = X; g.ldx = K; g.W = W; g.bias = bias; g.Y = Y; g.ldy = N; g.M = M; g.N = N; g.K = K; g.act = act;
+  return g;
+}
+// ... + R1 (+ R2): rows of the output's width
+static LinearArgs with_residual(LinearArgs g, const void* R1, const void* R2 = nullptr) {
+  g.R1 = R1; g.R2 = R2; g.ldr = g.N;
+  return g;
+}
+// ... * row_mask[row % period]
+static LinearArgs with_row_mask(LinearArgs g, const uint8_t* mask, int period) {
+  g.row_mask = mask; g.mask_period = period;
+  return g;
+}
+// ... leaving the moments of the rows it stores (a producer of the folded LayerNorm, d3pm_mfma_tile.h EPI_STATS)
+static LinearArgs with_moments_out(LinearArgs g, float* stats, bool quads) {
+  g.stats_out = stats; g.moment_quads = quads;
+  return g;
+}
+// a LayerNorm-fed projection of the raw residual rows X [M][K] (a consumer, EPI_LNF): Wf = W o gamma, no bias operand
+static LinearArgs folded_projection(const void* X, const void* Wf, const float* fold_s, const float* fold_b, const float* stats, bool quads,
+                                    void* Y, int M, int N, int K, int act) {
+  LinearArgs g = projection(X, Wf, nullptr, Y, M, N, K, act);
+  g.fold_s = fold_s; g.fold_b = fold_b; g.stats_in = stats; g.moment_quads = quads;
+  return g;
+}
+static float attn_scale(int hd) { return static_cast<float>(std::sqrt(1.0 / static_cast<double>(hd))); }
+// self-attention over a packed [B * T][3 H hd] buffer of q | k | v rows
+static AttnArgs self_attention(const void* qkv, void* O, int B, int T, int H, int hd, size_t es) {
+  const int d = H * hd;
+  AttnArgs a;
+  a.Q = qkv; a.ldq = 3 * d; a.K = at(qkv, d, es); a.V = at(qkv, 2 * d, es); a.ldkv = 3 * d; a.O = O; a.ldo = d;
+  a.B = B; a.Tq = T; a.S = T; a.H = H; a.hd = hd; a.scale = attn_scale(hd);
+  return a;
+}
+// the text | prompt cross-attentions of one block in one launch: queries with row stride ldq, keys and values packed [B * S][2 H hd]
+static AttnArgs cross_attention_pair(const void* q_text, const void* q_prompt, int ldq, const void* kv_text, int s_text, const void* kv_prompt,
+                                     int s_prompt, void* o_text, void* o_prompt, int B, int T, int H, int hd, size_t es) {
+  const int d = H * hd;
+  AttnArgs a;
+  a.Q = q_text; a.ldq = ldq; a.K = kv_text; a.V = at(kv_text, d, es); a.ldkv = 2 * d; a.O = o_text; a.ldo = d;
+  a.B = B; a.Tq = T; a.S = s_text; a.H = H; a.hd = hd; a.scale = attn_scale(hd);
+  a.Q2 = q_prompt; a.K2 = kv_prompt; a.V2 = at(kv_prompt, d, es); a.O2 = o_prompt; a.S2 = s_prompt;
+  return a;
+}
+static EmbedArgs embed_args(const d3pm_shape& sh, const d3pm_weights& w, int batch, const int32_t* x_t, const uint8_t* frame_mask, void* Y) {
+  EmbedArgs e;
+  e.tokens = x_t; e.frame_mask = frame_mask; e.canvas = sh.canvas; e.table = w.resps_emb; e.Y = Y;
+  e.M = batch * sh.canvas; e.d = sh.d_model; e.n_classes = sh.n_classes; e.n_q = levels(sh);
+  return e;
+}
+
+// ---- the cross-attention out-projection pair: x = (x + o_text) + o_prompt through the same weights --------------------------------
+// Three forms with the same bits.  `g` is the o_text projection onto the residual stream (R1 = Y = x, tune set), X2 the o_prompt rows.
+enum { CROSS_OUT_TWO_LAUNCHES = 0, CROSS_OUT_PANEL64_DUAL, CROSS_OUT_BIG_DUAL };
+static int cross_out_form(int dt, const LinearArgs& g, const void* X2, uint32_t flags, bool big_dual_allowed) {
+  const d3pm_tuning& tn = tune_of(g.tune);
+  if (flags & D3PM_FLAG_FORCE_GENERIC) return CROSS_OUT_TWO_LAUNCHES;
+  // one or two utterances: both products through one resident weight panel of the latency GEMM (o_text stays in registers)
+  if ((tn.row_panel & 8) && tn.gemm_variant == 0 && panel64_dual_supported(dt, g, X2)) return CROSS_OUT_PANEL64_DUAL;
+  // throughput batches: the same two products through one tile of the ordinary big-tile launch
+  if (big_dual_allowed && (tn.row_panel & 2) && big_dual_supported(dt, g, X2)) return CROSS_OUT_BIG_DUAL;
+  return CROSS_OUT_TWO_LAUNCHES;      // o_text -> ws.h, then o_prompt with R1 = x, R2 = h
+}
+static int run_cross_out_dual(const Ctx& cx, int dt, int form, const LinearArgs& g, const void* X2, hipStream_t s) {
+  ProfScope p(cx, D3PM_K_GEMM, s, 2.0 * 2.0 * g.M * g.N * g.K,
+              dtype_size(dt) * (2.0 * g.M * g.K + static_cast<double>(g.N) * g.K + 2.0 * g.M * g.N));
+  return form == CROSS_OUT_PANEL64_DUAL ? panel64_dual(dt, g, X2, s) : big_dual(dt, g, X2, s);
+}
+
+struct DenoiserArgs {      // what every block of one evaluation sees
+  const d3pm_shape& sh; const d3pm_weights& w; int batch; const uint8_t* frame_mask; const void* kv_text; const void* kv_prompt;
+  const Workspace& ws;
+};
+
+// ---- the block sequence with the LayerNorms folded into the projections (ar_discrete.py:126-161; d3pm_mfma_tile.h EPI_LNF / EPI_STATS)
 //   embed (+ moments) -> n_layers x { QKV <- x [norm1 folded], self-attention, out-projection + x (+ moments),
 //   merged query projection <- x [norm2 | norm22 folded, N = 2d], paired cross-attention, both out-projections + x (+ moments),
 //   fc1 + GELU <- x [norm3 + FiLM(t) folded], fc2 + x, frame mask (+ moments) }: ten launches per block, none of them a LayerNorm.
-static int denoiser_blocks_folded(const d3pm_shape& sh, const d3pm_weights& w, int batch, const int32_t* x_t, const uint8_t* frame_mask,
-                                  int t, const void* film, const void* kv_text, const void* kv_prompt, const Workspace& ws, int layers,
-                                  hipStream_t s, bool prepared, bool quads) {
-  const int dt = sh.dtype, d = sh.d_model, H = sh.n_heads, hd = d / H, T = sh.canvas, n = batch * T;
+// The launches of block l, written ONCE and handed to a visitor in order: FoldPlanner asks whether and on which tiles they would run,
+// FoldLauncher enqueues them.  Every LinearArgs that reads or writes ws.stats is constructed here and nowhere else.
+template <class Visitor>
+static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v) {
+  const d3pm_shape& sh = q.sh;
+  const Workspace& ws = q.ws;
+  const int dt = sh.dtype, d = sh.d_model, H = sh.n_heads, hd = d / H, T = sh.canvas, n = q.batch * T;
+  const size_t es = dtype_size(dt);
+  const d3pm_block_weights& b = q.w.blocks[l];
+  const d3pm_fold_block& f = q.w.fold[l];
+  auto consumer = [&](const void* Wf, const float* fs, const float* fb, void* Y, int N, int act) {
+    return v.linear(folded_projection(ws.x, Wf, fs, fb, ws.stats, quads, Y, n, N, d, act));
+  };
+  // a projection onto the residual stream: x += X . W^T + bias (+ R2), then the moments of the new rows
+  auto producer = [&](const void* X, int K, const void* W, const void* bias, const void* R2 = nullptr) {
+    return with_moments_out(with_residual(projection(X, W, bias, ws.x, n, d, K), ws.x, R2), ws.stats, quads);
+  };
+  // ---- self-attention ----
+  D3PM_TRY(consumer(f.qkv_w, f.qkv_s, f.qkv_b, ws.qkv, 3 * d, ACT_NONE));
+  D3PM_TRY(v.attention(self_attention(ws.qkv, ws.att, q.batch, T, H, hd, es)));
+  D3PM_TRY(v.linear(producer(ws.att, d, b.attn_out_w, b.attn_out_b)));
+  // ---- cross-attention: q_text | q_prompt are the two halves of ONE [n][2d] projection of x (the same q rows under norm2 / norm22)
+  D3PM_TRY(consumer(f.q2_w, f.q2_s, f.q2_b, ws.qkv, 2 * d, ACT_NONE));
+  const void* kvt = at(q.kv_text, static_cast<size_t>(l) * q.batch * sh.s_text * 2 * d, es);
+  const void* kvp = at(q.kv_prompt, static_cast<size_t>(l) * q.batch * sh.s_prompt * 2 * d, es);
+  D3PM_TRY(v.attention(cross_attention_pair(ws.qkv, at(ws.qkv, d, es), 2 * d, kvt, sh.s_text, kvp, sh.s_prompt, ws.att, ws.att2, q.batch, T, H, hd, es)));
+  // ---- x = (x + o_text) + o_prompt, rounded at each add like the eager sum ----
+  LinearArgs g = producer(ws.att, d, b.cross_out_w, b.cross_out_b);
+  g.tune = sh.tuning;      // big_dual_supported reads it
+  const int form = cross_out_form(dt, g, ws.att2, 0, true);
+  if (form != CROSS_OUT_TWO_LAUNCHES) {
+    D3PM_TRY(v.dual(form, g, ws.att2));
+  } else {
+    g.Y = ws.h; g.R1 = nullptr; g.stats_out = nullptr; g.moment_quads = false;   // o_text -> h (free: no LayerNorm output lives there any more)
+    D3PM_TRY(v.linear(g));
+    D3PM_TRY(v.linear(producer(ws.att2, d, b.cross_out_w, b.cross_out_b, ws.h)));
+  }
+  // ---- FiLM-modulated MLP: the (layer, t) copy of fc1 carries norm3 and the modulation ----
+  const size_t ln = static_cast<size_t>(l) * 4 * d;
+  D3PM_TRY(consumer(at(ws.fc1f, ln * d, es), ws.fc1f_s + ln, ws.fc1f_b + ln, ws.mlp, 4 * d, ACT_GELU));
+  return v.linear(with_row_mask(producer(ws.mlp, 4 * d, b.fc2_w, b.fc2_b), q.frame_mask, T));
+}
+
+// asks: would every launch that touches the moments run on the MFMA family (D3PM_E_SHAPE if not), and all of them on big tiles?
+struct FoldPlanner {
+  int dt; const d3pm_tuning* tune; bool big;
+  int linear(LinearArgs g) {
+    if (!g.fold_s && !g.stats_out) return D3PM_OK;      // no moments: any family will do
+    g.tune = tune;
+    if (!mfma_linear_supported(dt, g)) return D3PM_E_SHAPE;
+    big = big && mfma_linear_takes_big_tiles(dt, g);
+    return D3PM_OK;
+  }
+  int attention(const AttnArgs&) { return D3PM_OK; }
+  int dual(int form, const LinearArgs&, const void*) {
+    if (form == CROSS_OUT_PANEL64_DUAL) big = false;      // the 64 x 64 family keeps the 32-column parts
+    return D3PM_OK;
+  }
+};
+struct FoldLauncher {
+  const Ctx& cx; int dt; hipStream_t s;
+  int linear(const LinearArgs& g) { return run_linear(cx, dt, g, 0, s); }      // (fails rather than take the generic family with moments)
+  int attention(const AttnArgs& a) { return run_attention(cx, dt, a, 0, s); }
+  int dual(int form, const LinearArgs& g, const void* X2) { return run_cross_out_dual(cx, dt, form, g, X2, s); }
+};
+
+// Is this evaluation taking the folded-LayerNorm launch sequence, and in which format do its row moments travel?  FOLD_NONE: the
+// LayerNorm launches (the fold is off, or a projection of the sequence would not run on the MFMA family, whose epilogues alone read
+// and write moments).  FOLD_QUADS: every projection that reads or writes moments runs on big tiles (128-column aligned, d = 512), so
+// the producers can leave one quad per 128 columns (d3pm_mfma_tile.h EpiFold).  FOLD_PARTS: 32-column parts, which the 128 x 128 and
+// 64 x 64 (panel64, one or two utterances) families need.  One decision for the whole sequence -- every producer and consumer of
+// ws.stats, the sampler's embedding rows included, must use the same format -- taken once per call by denoise_step_impl /
+// sample_loop_impl over ALL layers (only_layers never changes the format).  The walk asks with the parts format and the sequence
+// launches with the answer; at d = 512, the only width that gets quads, fold_args_ok accepts both formats for these arguments.
+enum { FOLD_NONE = 0, FOLD_PARTS = 1, FOLD_QUADS = 2 };
+static int fold_plan(const DenoiserArgs& q, uint32_t flags, const d3pm_fp8_block_weights* f8) {
+  const d3pm_shape& sh = q.sh;
+  if (f8 || !q.w.fold || !tune_of(sh.tuning).ln_fold || (flags & D3PM_FLAG_FORCE_GENERIC) || !fold_shape_ok(sh.dtype, sh.d_model)) return FOLD_NONE;
+  FoldPlanner plan{sh.dtype, sh.tuning, sh.d_model == 512};
+  for (int l = 0; l < sh.n_layers; ++l)
+    if (folded_block(q, l, false, plan) != D3PM_OK) return FOLD_NONE;
+  return plan.big ? FOLD_QUADS : FOLD_PARTS;
+}
+
+static int denoiser_blocks_folded(const DenoiserArgs& q, const int32_t* x_t, int t, const void* film, int layers, hipStream_t s, bool prepared,
+                                  bool quads) {
+  const d3pm_shape& sh = q.sh;
+  const int dt = sh.dtype, d = sh.d_model, n = q.batch * sh.canvas;
   const Ctx cx(sh.tuning);
   const size_t es = dtype_size(dt);
-  const float scale = static_cast<float>(std::sqrt(1.0 / static_cast<double>(hd)));
-  EmbedArgs e;
-  e.tokens = x_t; e.frame_mask = frame_mask; e.canvas = T; e.table = w.resps_emb; e.Y = ws.x;
-  e.M = n; e.d = d; e.n_classes = sh.n_classes; e.n_q = levels(sh);
   if (!prepared) {      // (inside the loop the previous iteration's sampler launch has done both: posterior_sample_prep)
     {
       ProfScope p(cx, D3PM_K_LN, s, 0.0, es * static_cast<double>(n) * d * 2.0);
-      D3PM_TRY(embed_tokens_stats(dt, e, ws.stats, quads, s));
+      D3PM_TRY(embed_tokens_stats(dt, embed_args(sh, q.w, q.batch, x_t, q.frame_mask, q.ws.x), q.ws.stats, quads, s));
     }
     {   // fc1 of every block under norm3 + FiLM(t): the weights this evaluation's fc1 launches read
       ProfScope p(cx, D3PM_K_LN, s, 0.0, es * 2.0 * layers * 4.0 * d * d);
-      D3PM_TRY(fold_fc1_step_launch(dt, w.blocks, layers, at(film, static_cast<size_t>(t) * sh.n_layers * 2 * d, es), d, ws.fc1f, ws.fc1f_s,
-                                    ws.fc1f_b, s));
+      D3PM_TRY(fold_fc1_step_launch(dt, q.w.blocks, layers, at(film, static_cast<size_t>(t) * sh.n_layers * 2 * d, es), d, q.ws.fc1f, q.ws.fc1f_s,
+                                    q.ws.fc1f_b, s));
     }
   }
-  auto folded = [&](const void* Wf, const float* fs, const float* fb, void* Y, int N, int act) -> int {
-    LinearArgs g;
-    g.X = ws.x; g.ldx = d; g.W = Wf; g.Y = Y; g.ldy = N; g.M = n; g.N = N; g.K = d; g.act = act;
-    g.fold_s = fs; g.fold_b = fb; g.stats_in = ws.stats; g.fold_eps = 1e-6f; g.moment_quads = quads;
-    D3PM_REQUIRE(mfma_linear_supported(dt, g), D3PM_E_SHAPE, "folded LayerNorm projection %d x %d x %d not supported", n, N, d);
-    return run_linear(cx, dt, g, 0, s);
-  };
-  for (int l = 0; l < layers; ++l) {
-    const d3pm_block_weights& b = w.blocks[l];
-    const d3pm_fold_block& f = w.fold[l];
-    // ---- self-attention ----
-    D3PM_TRY(folded(f.qkv_w, f.qkv_s, f.qkv_b, ws.qkv, 3 * d, ACT_NONE));
-    AttnArgs a;
-    a.Q = ws.qkv; a.ldq = 3 * d; a.K = at(ws.qkv, d, es); a.V = at(ws.qkv, 2 * d, es); a.ldkv = 3 * d;
-    a.O = ws.att; a.ldo = d; a.B = batch; a.Tq = T; a.S = T; a.H = H; a.hd = hd; a.scale = scale;
-    D3PM_TRY(run_attention(cx, dt, a, 0, s));
-    LinearArgs g;
-    g.X = ws.att; g.ldx = d; g.W = b.attn_out_w; g.bias = b.attn_out_b; g.Y = ws.x; g.ldy = d;
-    g.R1 = ws.x; g.ldr = d; g.M = n; g.N = d; g.K = d; g.stats_out = ws.stats; g.moment_quads = quads;
-    D3PM_TRY(run_linear(cx, dt, g, 0, s));
-    // ---- cross-attention: q_text | q_prompt are the two halves of ONE [n][2d] projection of x (the same q rows under norm2 / norm22)
-    D3PM_TRY(folded(f.q2_w, f.q2_s, f.q2_b, ws.qkv, 2 * d, ACT_NONE));
-    {
-      const void* kvt = at(kv_text, static_cast<size_t>(l) * batch * sh.s_text * 2 * d, es);
-      const void* kvp = at(kv_prompt, static_cast<size_t>(l) * batch * sh.s_prompt * 2 * d, es);
-      a = AttnArgs();
-      a.Q = ws.qkv; a.ldq = 2 * d; a.K = kvt; a.V = at(kvt, d, es); a.ldkv = 2 * d; a.O = ws.att; a.ldo = d;
-      a.B = batch; a.Tq = T; a.S = sh.s_text; a.H = H; a.hd = hd; a.scale = scale;
-      a.Q2 = at(ws.qkv, d, es); a.K2 = kvp; a.V2 = at(kvp, d, es); a.O2 = ws.att2; a.S2 = sh.s_prompt;
-      D3PM_TRY(run_attention(cx, dt, a, 0, s));
-    }
-    // ---- x = (x + o_text) + o_prompt, rounded at each add like the eager sum ----
-    g = LinearArgs();
-    g.X = ws.att; g.ldx = d; g.W = b.cross_out_w; g.bias = b.cross_out_b; g.Y = ws.x; g.ldy = d; g.R1 = ws.x; g.ldr = d;
-    g.M = n; g.N = d; g.K = d; g.stats_out = ws.stats; g.moment_quads = quads;
-    if ((tune_of(sh.tuning).row_panel & 8) && tune_of(sh.tuning).gemm_variant == 0 && panel64_dual_supported(dt, g, ws.att2)) {
-      g.tune = cx.tune;      // one or two utterances: both products through one resident weight panel (same bits as the two launches)
-      ProfScope p(cx, D3PM_K_GEMM, s, 2.0 * 2.0 * g.M * g.N * g.K, es * (2.0 * g.M * g.K + static_cast<double>(g.N) * g.K + 2.0 * g.M * g.N));
-      D3PM_TRY(panel64_dual(dt, g, ws.att2, s));
-    } else if ((tune_of(sh.tuning).row_panel & 2) && (g.tune = cx.tune, big_dual_supported(dt, g, ws.att2))) {
-      // throughput batches: the same two products through one tile of the ordinary big-tile launch (same bits again)
-      ProfScope p(cx, D3PM_K_GEMM, s, 2.0 * 2.0 * g.M * g.N * g.K, es * (2.0 * g.M * g.K + static_cast<double>(g.N) * g.K + 2.0 * g.M * g.N));
-      D3PM_TRY(big_dual(dt, g, ws.att2, s));
-    } else {
-      g.Y = ws.h; g.R1 = nullptr; g.stats_out = nullptr; g.moment_quads = false;   // o_text -> h (free: no LayerNorm output lives there any more)
-      D3PM_TRY(run_linear(cx, dt, g, 0, s));
-      g = LinearArgs();
-      g.X = ws.att2; g.ldx = d; g.W = b.cross_out_w; g.bias = b.cross_out_b; g.Y = ws.x; g.ldy = d;
-      g.R1 = ws.x; g.R2 = ws.h; g.ldr = d; g.M = n; g.N = d; g.K = d; g.stats_out = ws.stats; g.moment_quads = quads;
-      D3PM_TRY(run_linear(cx, dt, g, 0, s));
-    }
-    // ---- FiLM-modulated MLP: the (layer, t) copy of fc1 carries norm3 and the modulation ----
-    const size_t ln = static_cast<size_t>(l) * 4 * d;
-    D3PM_TRY(folded(at(ws.fc1f, ln * d, es), ws.fc1f_s + ln, ws.fc1f_b + ln, ws.mlp, 4 * d, ACT_GELU));
-    g = LinearArgs();
-    g.X = ws.mlp; g.ldx = 4 * d; g.W = b.fc2_w; g.bias = b.fc2_b; g.Y = ws.x; g.ldy = d; g.R1 = ws.x; g.ldr = d;
-    g.row_mask = frame_mask; g.mask_period = T; g.M = n; g.N = d; g.K = 4 * d; g.stats_out = ws.stats; g.moment_quads = quads;
-    D3PM_TRY(run_linear(cx, dt, g, 0, s));
-  }
+  FoldLauncher launch{cx, dt, s};
+  for (int l = 0; l < layers; ++l) D3PM_TRY(folded_block(q, l, quads, launch));
   return D3PM_OK;
 }
 
-// hidden state after `layers` blocks is left in ws.x
-// Is this evaluation taking the folded-LayerNorm launch sequence (denoiser_blocks_folded), and in which format do its row moments
-// travel?  FOLD_NONE: the LayerNorm launches (the fold is off, or a projection of the sequence would not run on the MFMA family, whose
-// epilogues alone read and write moments).  FOLD_QUADS: every projection that reads or writes moments runs on big tiles (128-column
-// aligned, d = 512), so the producers can leave one quad per 128 columns (d3pm_mfma_tile.h EpiFold).  FOLD_PARTS: 32-column parts,
-// which the 128 x 128 and 64 x 64 (panel64, one or two utterances) families need.  One decision for the whole sequence: every
-// producer and consumer of ws.stats, the sampler's embedding rows included, must use the same format.
-enum { FOLD_NONE = 0, FOLD_PARTS = 1, FOLD_QUADS = 2 };
-static int fold_plan(const d3pm_shape& sh, const d3pm_weights& w, uint32_t flags, const d3pm_fp8_block_weights* f8, int batch,
-                     const Workspace& ws) {
-  if (f8 || !w.fold || !tune_of(sh.tuning).ln_fold || (flags & D3PM_FLAG_FORCE_GENERIC) || !fold_shape_ok(sh.dtype, sh.d_model)) return FOLD_NONE;
-  const int dt = sh.dtype, d = sh.d_model, n = batch * sh.canvas;
-  const size_t es = dtype_size(dt);
-  const Ctx cx(sh.tuning);
-  bool big = d == 512;
-  // the launches of denoiser_blocks_folded that read or write ws.stats, with the same arguments
-  auto check = [&](const LinearArgs& g) {
-    if (!mfma_linear_supported(dt, g)) return false;
-    big = big && mfma_linear_takes_big_tiles(dt, g);
-    return true;
-  };
-  for (int l = 0; l < sh.n_layers; ++l) {
-    const d3pm_block_weights& b = w.blocks[l];
-    const d3pm_fold_block& f = w.fold[l];
-    auto consumer = [&](const void* Wf, const float* fs, const float* fb, void* Y, int N, int act) {
-      LinearArgs g;
-      g.X = ws.x; g.ldx = d; g.W = Wf; g.Y = Y; g.ldy = N; g.M = n; g.N = N; g.K = d; g.act = act;
-      g.fold_s = fs; g.fold_b = fb; g.stats_in = ws.stats; g.tune = cx.tune;
-      return check(g);
-    };
-    auto producer = [&](const void* X, int K, const void* W, const void* bias, const void* R2, const uint8_t* mask) {
-      LinearArgs g;
-      g.X = X; g.ldx = K; g.W = W; g.bias = bias; g.Y = ws.x; g.ldy = d; g.R1 = ws.x; g.R2 = R2; g.ldr = d;
-      g.row_mask = mask; g.mask_period = sh.canvas; g.M = n; g.N = d; g.K = K; g.stats_out = ws.stats; g.tune = cx.tune;
-      return g;
-    };
-    const size_t ln = static_cast<size_t>(l) * 4 * d;
-    if (!consumer(f.qkv_w, f.qkv_s, f.qkv_b, ws.qkv, 3 * d, ACT_NONE) || !consumer(f.q2_w, f.q2_s, f.q2_b, ws.qkv, 2 * d, ACT_NONE) ||
-        !consumer(at(ws.fc1f, ln * d, es), ws.fc1f_s + ln, ws.fc1f_b + ln, ws.mlp, 4 * d, ACT_GELU))
-      return FOLD_NONE;
-    static const uint8_t one = 1;      // a frame mask stand-in: the kernel choice does not depend on its address
-    if (!check(producer(ws.att, d, b.attn_out_w, b.attn_out_b, nullptr, nullptr)) ||
-        !check(producer(ws.mlp, 4 * d, b.fc2_w, b.fc2_b, nullptr, &one)))
-      return FOLD_NONE;
-    const LinearArgs g = producer(ws.att, d, b.cross_out_w, b.cross_out_b, nullptr, nullptr);
-    if ((tune_of(sh.tuning).row_panel & 8) && tune_of(sh.tuning).gemm_variant == 0 && panel64_dual_supported(dt, g, ws.att2)) big = false;
-    else if ((tune_of(sh.tuning).row_panel & 2) && big_dual_supported(dt, g, ws.att2)) {}
-    else if (!check(producer(ws.att2, d, b.cross_out_w, b.cross_out_b, ws.h, nullptr))) return FOLD_NONE;
-  }
-  return big ? FOLD_QUADS : FOLD_PARTS;
-}
+// One denoiser evaluation up to the final projection: the hidden state after `layers` blocks is left in ws.x.  `plan` is the caller's
+// fold_plan(): FOLD_NONE runs the LayerNorm / row-panel launches below (and the fp8 fast path, BASELINE.json configs[4]).
+static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, const void* film, int layers, uint32_t flags, hipStream_t s,
+                           const d3pm_fp8_block_weights* f8, int plan, bool prepared = false) {
+  // LayerNorm folded into the projections (d3pm_tuning.ln_fold, d3pm_fold_block): every LayerNorm-fed projection reads the raw
+  // residual stream and normalises in its epilogue; every projection that lands on the residual stream leaves the row moments
+  if (plan != FOLD_NONE) return denoiser_blocks_folded(q, x_t, t, film, layers, s, prepared, plan == FOLD_QUADS);
 
-static int denoiser_blocks(const d3pm_shape& sh, const d3pm_weights& w, int batch, const int32_t* x_t,
-                           const uint8_t* frame_mask, int t, const void* film, const void* kv_text,
-                           const void* kv_prompt, const Workspace& ws, int layers, uint32_t flags, hipStream_t s,
-                           const d3pm_fp8_block_weights* f8 = nullptr, bool prepared = false) {
-  const int dt = sh.dtype, d = sh.d_model, H = sh.n_heads, hd = d / H, T = sh.canvas;
+  const d3pm_shape& sh = q.sh;
+  const d3pm_weights& w = q.w;
+  const Workspace& ws = q.ws;
+  const uint8_t* frame_mask = q.frame_mask;
+  const int dt = sh.dtype, d = sh.d_model, H = sh.n_heads, hd = d / H, T = sh.canvas, batch = q.batch;
   const int n = batch * T;
   const Ctx cx(sh.tuning);
   const size_t es = dtype_size(dt);
-  // fp8 fast path (BASELINE.json configs[4]): the three LayerNorm-fed K = d projections take e4m3 operands; the e4m3 rows
+  // fp8 fast path: the three LayerNorm-fed K = d projections take e4m3 operands; the e4m3 rows
   // and their scales live where the 16-bit LayerNorm outputs would (ws.h | ws.h2 are adjacent: 2 n d 2 bytes)
   const bool use8 = f8 != nullptr;
   if (use8) {   // the *_fp8 entry points never fall back to the 16-bit kernels silently: a number labelled fp8 is fp8
@@ -395,22 +452,18 @@ static int denoiser_blocks(const d3pm_shape& sh, const d3pm_weights& w, int batc
                 1.03125 * (static_cast<double>(M) * K + static_cast<double>(N) * K) + static_cast<double>(M) * N * (Y8 ? 1.03125 : (R1 ? 2.0 : 1.0) * es));
     return mx_linear(dt, m, s);
   };
-  const float scale = static_cast<float>(std::sqrt(1.0 / static_cast<double>(hd)));
+  auto layernorm = [&](const void* lw, const void* lb) {      // x -> h, eps 1e-6
+    LayerNormArgs ln;
+    ln.X = ws.x; ln.Y = ws.h; ln.w = lw; ln.b = lb; ln.M = n; ln.d = d; ln.eps = 1e-6f;
+    return ln;
+  };
 
-  // LayerNorm folded into the projections (d3pm_tuning.ln_fold, d3pm_fold_block): every LayerNorm-fed projection reads the raw
-  // residual stream and normalises in its epilogue; every projection that lands on the residual stream leaves the row moments
-  if (const int plan = fold_plan(sh, w, flags, f8, batch, ws))
-    return denoiser_blocks_folded(sh, w, batch, x_t, frame_mask, t, film, kv_text, kv_prompt, ws, layers, s, prepared, plan == FOLD_QUADS);
-
-  EmbedArgs e;
-  e.tokens = x_t; e.frame_mask = frame_mask; e.canvas = T; e.table = w.resps_emb; e.Y = ws.x;
-  e.M = n; e.d = d; e.n_classes = sh.n_classes; e.n_q = levels(sh);
   // the first block's norm1 reads the embedding rows straight from the table and writes x beside its own output: one launch and
   // one pass over x less per iteration (same bits: the gather is a copy)
   bool embed_fused = false;
   if (!use8 && !(flags & D3PM_FLAG_FORCE_GENERIC) && layers > 0 && levels(sh) == 1) {
-    LayerNormArgs ln0;
-    ln0.X = w.resps_emb; ln0.Y = ws.h; ln0.w = w.blocks[0].norm1_w; ln0.b = w.blocks[0].norm1_b; ln0.M = n; ln0.d = d; ln0.eps = 1e-6f;
+    LayerNormArgs ln0 = layernorm(w.blocks[0].norm1_w, w.blocks[0].norm1_b);
+    ln0.X = w.resps_emb;
     ln0.tokens = x_t; ln0.frame_mask = frame_mask; ln0.canvas = T; ln0.n_classes = sh.n_classes; ln0.Xout = ws.x;
     if (fast_layernorm_supported(dt, ln0)) {
       ProfScope p(cx, D3PM_K_LN, s, 0.0, dtype_size(dt) * static_cast<double>(n) * d * 3.0);
@@ -418,7 +471,7 @@ static int denoiser_blocks(const d3pm_shape& sh, const d3pm_weights& w, int batc
       embed_fused = true;
     }
   }
-  if (!embed_fused) D3PM_TRY(embed_tokens(dt, e, s));
+  if (!embed_fused) D3PM_TRY(embed_tokens(dt, embed_args(sh, w, batch, x_t, frame_mask, ws.x), s));
 
   // row-panel launches (D3PM_TUNE_ROW_PANEL): a projection that lands on the residual stream also writes the LayerNorm(s) the
   // block applies to the new rows next -- same bits, one launch and one pass over x less each
@@ -435,15 +488,20 @@ static int denoiser_blocks(const d3pm_shape& sh, const d3pm_weights& w, int batc
   const bool lnpro_on = false;
 #endif
   const bool lnpro = lnpro_on && !use8 && !(flags & D3PM_FLAG_FORCE_GENERIC) && d == 512 && (dt == D3PM_F16 || dt == D3PM_BF16);
+  // a LayerNorm-fed projection g (g.X = the LayerNorm output): LayerNorm launch + projection, unless an earlier launch has written
+  // the LayerNorm rows already (ablation build only: or the latency GEMM normalises the rows of x itself)
+  auto ln_linear = [&](bool ln_done, const LayerNormArgs& ln, const LnPrologue& lp, const LinearArgs& g) -> int {
+    LinearArgs gx = g;
+    gx.X = ws.x;
+    if (!ln_done && lnpro && ln_prologue_applies(cx, dt, gx, lp)) return run_ln_linear(cx, dt, gx, lp, s);
+    if (!ln_done) D3PM_TRY(run_layernorm(cx, dt, ln, flags, s));
+    return run_linear(cx, dt, g, flags, s);
+  };
 
   for (int l = 0; l < layers; ++l) {
     const d3pm_block_weights& b = w.blocks[l];
     // ---- self-attention ----
-    LayerNormArgs ln;
-    ln.X = ws.x; ln.Y = ws.h; ln.w = b.norm1_w; ln.b = b.norm1_b; ln.M = n; ln.d = d; ln.eps = 1e-6f;
-    LinearArgs g;
-    g.X = ws.h; g.ldx = d; g.W = b.attn_in_w; g.bias = b.attn_in_b; g.Y = ws.qkv; g.ldy = 3 * d;
-    g.M = n; g.N = 3 * d; g.K = d;
+    LayerNormArgs ln = layernorm(b.norm1_w, b.norm1_b);
     if (use8) {
       {
         ProfScope p(cx, D3PM_K_LN, s, 0.0, static_cast<double>(n) * d * (es + 1.03125));
@@ -454,27 +512,14 @@ static int denoiser_blocks(const d3pm_shape& sh, const d3pm_weights& w, int batc
     } else {
       LnPrologue lp;
       lp.w = ln.w; lp.b = ln.b; lp.eps = ln.eps;
-      LinearArgs gx = g;
-      gx.X = ws.x;
-      if (!norm1_done && lnpro && ln_prologue_applies(cx, dt, gx, lp)) {
-        D3PM_TRY(run_ln_linear(cx, dt, gx, lp, s));
-      } else {
-        if (!norm1_done) D3PM_TRY(run_layernorm(cx, dt, ln, flags, s));
-        D3PM_TRY(run_linear(cx, dt, g, flags, s));
-      }
+      D3PM_TRY(ln_linear(norm1_done, ln, lp, projection(ws.h, b.attn_in_w, b.attn_in_b, ws.qkv, n, 3 * d, d)));
     }
     norm1_done = false;
-    AttnArgs a;
-    a.Q = ws.qkv; a.ldq = 3 * d; a.K = at(ws.qkv, d, es); a.V = at(ws.qkv, 2 * d, es); a.ldkv = 3 * d;
-    a.O = ws.att; a.ldo = d; a.B = batch; a.Tq = T; a.S = T; a.H = H; a.hd = hd; a.scale = scale;
-    D3PM_TRY(run_attention(cx, dt, a, flags, s));
-    g = LinearArgs();
-    g.X = ws.att; g.ldx = d; g.W = b.attn_out_w; g.bias = b.attn_out_b; g.Y = ws.x; g.ldy = d;
-    g.R1 = ws.x; g.ldr = d; g.M = n; g.N = d; g.K = d;
+    D3PM_TRY(run_attention(cx, dt, self_attention(ws.qkv, ws.att, batch, T, H, hd, es), flags, s));
+    LinearArgs g = with_residual(projection(ws.att, b.attn_out_w, b.attn_out_b, ws.x, n, d, d), ws.x);
     // ---- cross-attention: text keys with LN2 queries, prompt keys with LN22 queries, SAME weights ----
-    ln = LayerNormArgs();
-    ln.X = ws.x; ln.Y = ws.h; ln.w = b.norm2_w; ln.b = b.norm2_b; ln.Y2 = ws.h2; ln.w2 = b.norm22_w; ln.b2 = b.norm22_b;
-    ln.M = n; ln.d = d; ln.eps = 1e-6f;
+    ln = layernorm(b.norm2_w, b.norm2_b);
+    ln.Y2 = ws.h2; ln.w2 = b.norm22_w; ln.b2 = b.norm22_b;
     RowPanelFuse rp;
     rp.lnw = ln.w; rp.lnb = ln.b; rp.lny = ln.Y; rp.lnw2 = ln.w2; rp.lnb2 = ln.b2; rp.lny2 = ln.Y2; rp.eps = ln.eps;
     if (use8) {      // the LayerNorm rows leave the row-panel launch as MX codes + block scales: the query projection's operand
@@ -497,69 +542,40 @@ static int denoiser_blocks(const d3pm_shape& sh, const d3pm_weights& w, int batc
     } else if (ws.h2 == at(ws.h, static_cast<size_t>(n) * d, es)) {
       // both query projections share cross_attn's q rows: LN2|LN22 outputs and q_text|q_prompt are adjacent in
       // the workspace, so the pair is ONE [2n, d] x [d, d] GEMM (twice the workgroups of either alone)
-      g = LinearArgs();
-      g.X = ws.h; g.ldx = d; g.W = b.cross_in_w; g.bias = b.cross_in_b; g.Y = q_text; g.ldy = d; g.M = 2 * n; g.N = d; g.K = d;
       LnPrologue lp;
       lp.w = ln.w; lp.b = ln.b; lp.w2 = ln.w2; lp.b2 = ln.b2; lp.eps = ln.eps; lp.period = n;
-      LinearArgs gx = g;
-      gx.X = ws.x;
-      if (!norm2_fused && lnpro && ln_prologue_applies(cx, dt, gx, lp)) {
-        D3PM_TRY(run_ln_linear(cx, dt, gx, lp, s));
-      } else {
-        if (!norm2_fused) D3PM_TRY(run_layernorm(cx, dt, ln, flags, s));
-        D3PM_TRY(run_linear(cx, dt, g, flags, s));
-      }
+      D3PM_TRY(ln_linear(norm2_fused, ln, lp, projection(ws.h, b.cross_in_w, b.cross_in_b, q_text, 2 * n, d, d)));
     } else {
       if (!norm2_fused) D3PM_TRY(run_layernorm(cx, dt, ln, flags, s));
-      for (int which = 0; which < 2; ++which) {
-        g = LinearArgs();
-        g.X = which ? ws.h2 : ws.h; g.ldx = d; g.W = b.cross_in_w; g.bias = b.cross_in_b;
-        g.Y = which ? q_prom : q_text; g.ldy = d; g.M = n; g.N = d; g.K = d;
-        D3PM_TRY(run_linear(cx, dt, g, flags, s));
-      }
+      D3PM_TRY(run_linear(cx, dt, projection(ws.h, b.cross_in_w, b.cross_in_b, q_text, n, d, d), flags, s));
+      D3PM_TRY(run_linear(cx, dt, projection(ws.h2, b.cross_in_w, b.cross_in_b, q_prom, n, d, d), flags, s));
     }
     {   // text and prompt cross-attention are independent: one paired launch
-      const void* kvt = at(kv_text, static_cast<size_t>(l) * batch * sh.s_text * 2 * d, es);
-      const void* kvp = at(kv_prompt, static_cast<size_t>(l) * batch * sh.s_prompt * 2 * d, es);
-      a = AttnArgs();
-      a.Q = q_text; a.ldq = d; a.K = kvt; a.V = at(kvt, d, es); a.ldkv = 2 * d; a.O = ws.att; a.ldo = d;
-      a.B = batch; a.Tq = T; a.S = sh.s_text; a.H = H; a.hd = hd; a.scale = scale;
-      a.Q2 = q_prom; a.K2 = kvp; a.V2 = at(kvp, d, es); a.O2 = ws.att2; a.S2 = sh.s_prompt;
-      D3PM_TRY(run_attention(cx, dt, a, flags, s));
+      const void* kvt = at(q.kv_text, static_cast<size_t>(l) * batch * sh.s_text * 2 * d, es);
+      const void* kvp = at(q.kv_prompt, static_cast<size_t>(l) * batch * sh.s_prompt * 2 * d, es);
+      D3PM_TRY(run_attention(cx, dt, cross_attention_pair(q_text, q_prom, d, kvt, sh.s_text, kvp, sh.s_prompt, ws.att, ws.att2, batch, T, H, hd, es),
+                             flags, s));
     }
     // ---- both out-projections, then the FiLM-modulated MLP ----
-    ln = LayerNormArgs();
-    ln.X = ws.x; ln.Y = ws.h; ln.w = b.norm3_w; ln.b = b.norm3_b; ln.M = n; ln.d = d; ln.eps = 1e-6f;
+    ln = layernorm(b.norm3_w, b.norm3_b);
     ln.film = at(film, (static_cast<size_t>(t) * sh.n_layers + l) * 2 * d, es);
-    g = LinearArgs();
-    g.X = ws.att; g.ldx = d; g.W = b.cross_out_w; g.bias = b.cross_out_b; g.Y = ws.x; g.ldy = d; g.R1 = ws.x; g.ldr = d;
-    g.M = n; g.N = d; g.K = d;
+    g = with_residual(projection(ws.att, b.cross_out_w, b.cross_out_b, ws.x, n, d, d), ws.x);
     rp = RowPanelFuse();
     rp.X2 = ws.att2; rp.lnw = ln.w; rp.lnb = ln.b; rp.lny = ln.Y; rp.film = ln.film; rp.eps = ln.eps;
     if (use8) { rp.lny = x8; rp.sx = sx8; }
     const bool norm3_fused = (panel & 2) && row_panel_supported(dt, g, rp);
     if (norm3_fused) {
       D3PM_TRY(run_row_panel(cx, dt, g, rp, s));
-    } else if ((tune_of(sh.tuning).row_panel & 8) && !(flags & D3PM_FLAG_FORCE_GENERIC) && tune_of(sh.tuning).gemm_variant == 0 &&
-               panel64_dual_supported(dt, g, ws.att2)) {
-      // one or two utterances: both out-projections in ONE launch of the latency GEMM (the weight panel is resident in LDS; o_text
-      // stays in registers): x = (x + o_text) + o_prompt with the roundings of the two-launch form below
-      g.tune = cx.tune;
-      ProfScope p(cx, D3PM_K_GEMM, s, 2.0 * 2.0 * g.M * g.N * g.K, es * (2.0 * g.M * g.K + static_cast<double>(g.N) * g.K + 2.0 * g.M * g.N));
-      D3PM_TRY(panel64_dual(dt, g, ws.att2, s));
     } else {
-      // o_text -> h (free now); x = (x + o_text) + o_prompt, rounded at each add like the eager sum
-      g = LinearArgs();
-      g.X = ws.att; g.ldx = d; g.W = b.cross_out_w; g.bias = b.cross_out_b; g.Y = ws.h; g.ldy = d; g.M = n; g.N = d; g.K = d;
-      D3PM_TRY(run_linear(cx, dt, g, flags, s));
-      g = LinearArgs();
-      g.X = ws.att2; g.ldx = d; g.W = b.cross_out_w; g.bias = b.cross_out_b; g.Y = ws.x; g.ldy = d;
-      g.R1 = ws.x; g.R2 = ws.h; g.ldr = d; g.M = n; g.N = d; g.K = d;
-      D3PM_TRY(run_linear(cx, dt, g, flags, s));
+      g.tune = cx.tune;
+      const int form = cross_out_form(dt, g, ws.att2, flags, false);      // (throughput batches have the row-panel launch above: no big_dual here)
+      if (form != CROSS_OUT_TWO_LAUNCHES) {
+        D3PM_TRY(run_cross_out_dual(cx, dt, form, g, ws.att2, s));
+      } else {
+        D3PM_TRY(run_linear(cx, dt, projection(ws.att, b.cross_out_w, b.cross_out_b, ws.h, n, d, d), flags, s));
+        D3PM_TRY(run_linear(cx, dt, with_residual(projection(ws.att2, b.cross_out_w, b.cross_out_b, ws.x, n, d, d), ws.x, ws.h), flags, s));
+      }
     }
-    g = LinearArgs();
-    g.X = ws.h; g.ldx = d; g.W = b.fc1_w; g.bias = b.fc1_b; g.Y = ws.mlp; g.ldy = 4 * d; g.M = n; g.N = 4 * d; g.K = d;
-    g.act = ACT_GELU;
     const bool fc2_mx = use8 && f8[l].fc2_w8 && f8[l].fc2_scale;
     if (use8) {
       if (!norm3_fused) {
@@ -572,18 +588,9 @@ static int denoiser_blocks(const d3pm_shape& sh, const d3pm_weights& w, int batc
     } else {
       LnPrologue lp;
       lp.w = ln.w; lp.b = ln.b; lp.film = ln.film; lp.eps = ln.eps;
-      LinearArgs gx = g;
-      gx.X = ws.x;
-      if (!norm3_fused && lnpro && ln_prologue_applies(cx, dt, gx, lp)) {
-        D3PM_TRY(run_ln_linear(cx, dt, gx, lp, s));
-      } else {
-        if (!norm3_fused) D3PM_TRY(run_layernorm(cx, dt, ln, flags, s));
-        D3PM_TRY(run_linear(cx, dt, g, flags, s));
-      }
+      D3PM_TRY(ln_linear(norm3_fused, ln, lp, projection(ws.h, b.fc1_w, b.fc1_b, ws.mlp, n, 4 * d, d, ACT_GELU)));
     }
-    g = LinearArgs();
-    g.X = ws.mlp; g.ldx = 4 * d; g.W = b.fc2_w; g.bias = b.fc2_b; g.Y = ws.x; g.ldy = d; g.R1 = ws.x; g.ldr = d;
-    g.row_mask = frame_mask; g.mask_period = T; g.M = n; g.N = d; g.K = 4 * d;
+    g = with_row_mask(with_residual(projection(ws.mlp, b.fc2_w, b.fc2_b, ws.x, n, d, 4 * d), ws.x), frame_mask, T);
     rp = RowPanelFuse();
     if (l + 1 < layers) { rp.lnw = w.blocks[l + 1].norm1_w; rp.lnb = w.blocks[l + 1].norm1_b; rp.lny = ws.h; rp.eps = 1e-6f; }
     if (fc2_mx) {
@@ -616,10 +623,10 @@ static int final_logits(const d3pm_shape& sh, const d3pm_weights& w, int batch, 
   const Ctx cx(sh.tuning);
   const size_t es = dtype_size(sh.dtype);
   for (int l = 0; l < levels(sh); ++l) {
-    LinearArgs g;
-    g.X = ws.x; g.ldx = sh.d_model; g.W = at(w.final_w, static_cast<size_t>(l) * sh.n_classes * sh.d_model, es);
-    g.bias = at(w.final_b, static_cast<size_t>(l) * sh.n_classes, es); g.Y = at(logits, static_cast<size_t>(l) * ldl, es);
-    g.ldy = levels(sh) * ldl; g.M = batch * sh.canvas; g.N = sh.n_classes; g.K = sh.d_model;
+    LinearArgs g = projection(ws.x, at(w.final_w, static_cast<size_t>(l) * sh.n_classes * sh.d_model, es),
+                              at(w.final_b, static_cast<size_t>(l) * sh.n_classes, es), at(logits, static_cast<size_t>(l) * ldl, es),
+                              batch * sh.canvas, sh.n_classes, sh.d_model);
+    g.ldy = levels(sh) * ldl;
     D3PM_TRY(run_linear(cx, sh.dtype, g, flags, s));
   }
   return D3PM_OK;
@@ -644,10 +651,9 @@ int d3pm_film_table(const d3pm_shape* sh, const d3pm_weights* w, void* film, voi
   D3PM_REQUIRE(w && w->blocks && w->time_emb && film, D3PM_E_ARG, "d3pm_film_table: null pointer");
   const int d = sh->d_model;
   for (int l = 0; l < sh->n_layers; ++l) {
-    LinearArgs g;
-    g.X = w->time_emb; g.ldx = d; g.W = w->blocks[l].tfc_w; g.bias = w->blocks[l].tfc_b;
-    g.Y = at(film, static_cast<size_t>(l) * 2 * d, dtype_size(sh->dtype)); g.ldy = sh->n_layers * 2 * d;
-    g.M = sh->timesteps + 1; g.N = 2 * d; g.K = d;
+    LinearArgs g = projection(w->time_emb, w->blocks[l].tfc_w, w->blocks[l].tfc_b, at(film, static_cast<size_t>(l) * 2 * d, dtype_size(sh->dtype)),
+                              sh->timesteps + 1, 2 * d, d);
+    g.ldy = sh->n_layers * 2 * d;
     D3PM_TRY(generic_linear(sh->dtype, g, static_cast<hipStream_t>(stream)));
   }
   return D3PM_OK;
@@ -745,12 +751,10 @@ int d3pm_cond_kv(const d3pm_shape* sh, const d3pm_weights* w, int batch, const v
   for (int l = 0; l < sh->n_layers; ++l)
     for (int which = 0; which < 2; ++which) {
       const int S = which ? sh->s_prompt : sh->s_text;
-      LinearArgs g;
-      g.X = which ? cond_prompt : cond_text; g.ldx = d;
-      g.W = at(w->blocks[l].cross_in_w, static_cast<size_t>(d) * d, es);   // k|v rows of the packed in-projection
-      g.bias = at(w->blocks[l].cross_in_b, d, es);
-      g.Y = at(which ? kv_prompt : kv_text, static_cast<size_t>(l) * batch * S * 2 * d, es); g.ldy = 2 * d;
-      g.M = batch * S; g.N = 2 * d; g.K = d;
+      // the k | v rows of the packed in-projection
+      const LinearArgs g = projection(which ? cond_prompt : cond_text, at(w->blocks[l].cross_in_w, static_cast<size_t>(d) * d, es),
+                                      at(w->blocks[l].cross_in_b, d, es), at(which ? kv_prompt : kv_text, static_cast<size_t>(l) * batch * S * 2 * d, es),
+                                      batch * S, 2 * d, d);
       D3PM_TRY(run_linear(cx, sh->dtype, g, 0, static_cast<hipStream_t>(stream)));
     }
   return D3PM_OK;
@@ -794,12 +798,8 @@ static int run_encoder(const d3pm_shape& sh, const d3pm_encoder_weights& e, int 
   const Ctx cx(sh.tuning);
   for (int l = 0; l < e.n_layers; ++l) {
     const d3pm_encoder_layer_weights& w = e.layers[l];
-    LinearArgs g;
-    g.X = ws.x; g.ldx = d; g.W = w.in_w; g.bias = w.in_b; g.Y = ws.qkv; g.ldy = 3 * d; g.M = n; g.N = 3 * d; g.K = d;
-    D3PM_TRY(run_linear(cx, dt, g, 0, s));
-    AttnArgs a;
-    a.Q = ws.qkv; a.ldq = 3 * d; a.K = at(ws.qkv, d, es); a.V = at(ws.qkv, 2 * d, es); a.ldkv = 3 * d; a.O = ws.att; a.ldo = d;
-    a.B = batch; a.Tq = seq; a.S = seq; a.H = e.n_heads; a.hd = hd; a.scale = static_cast<float>(std::sqrt(1.0 / hd));
+    D3PM_TRY(run_linear(cx, dt, projection(ws.x, w.in_w, w.in_b, ws.qkv, n, 3 * d, d), 0, s));
+    const AttnArgs a = self_attention(ws.qkv, ws.att, batch, seq, e.n_heads, hd, es);
     if (encoder_pads_heads(sh, e) && ws.qkv_pad) {
       D3PM_TRY(pad_heads(ws.qkv, ws.qkv_pad, n, 3 * e.n_heads, hd, s));
       AttnArgs p = a;
@@ -810,28 +810,20 @@ static int run_encoder(const d3pm_shape& sh, const d3pm_encoder_weights& e, int 
     } else {
       D3PM_TRY(run_attention(cx, dt, a, 0, s));
     }
-    g = LinearArgs();   // x + self_attn(x), then post-norm
-    g.X = ws.att; g.ldx = d; g.W = w.out_w; g.bias = w.out_b; g.Y = ws.tmp; g.ldy = d; g.R1 = ws.x; g.ldr = d; g.M = n; g.N = d; g.K = d;
-    D3PM_TRY(run_linear(cx, dt, g, 0, s));
+    // x + self_attn(x), then post-norm
+    D3PM_TRY(run_linear(cx, dt, with_residual(projection(ws.att, w.out_w, w.out_b, ws.tmp, n, d, d), ws.x), 0, s));
     LayerNormArgs ln;
     ln.X = ws.tmp; ln.Y = ws.x; ln.w = w.norm1_w; ln.b = w.norm1_b; ln.M = n; ln.d = d; ln.eps = 1e-5f;
     D3PM_TRY(run_layernorm(cx, dt, ln, 0, s));
-    g = LinearArgs();   // FFN: linear2(relu(linear1(x)))
-    g.X = ws.x; g.ldx = d; g.W = w.lin1_w; g.bias = w.lin1_b; g.Y = ws.ff; g.ldy = e.d_ff; g.M = n; g.N = e.d_ff; g.K = d; g.act = ACT_RELU;
-    D3PM_TRY(run_linear(cx, dt, g, 0, s));
-    g = LinearArgs();
-    g.X = ws.ff; g.ldx = e.d_ff; g.W = w.lin2_w; g.bias = w.lin2_b; g.Y = ws.tmp; g.ldy = d; g.R1 = ws.x; g.ldr = d; g.M = n; g.N = d; g.K = e.d_ff;
-    D3PM_TRY(run_linear(cx, dt, g, 0, s));
-    ln = LayerNormArgs();
-    ln.X = ws.tmp; ln.Y = ws.x; ln.w = w.norm2_w; ln.b = w.norm2_b; ln.M = n; ln.d = d; ln.eps = 1e-5f;
+    // FFN: linear2(relu(linear1(x)))
+    D3PM_TRY(run_linear(cx, dt, projection(ws.x, w.lin1_w, w.lin1_b, ws.ff, n, e.d_ff, d, ACT_RELU), 0, s));
+    D3PM_TRY(run_linear(cx, dt, with_residual(projection(ws.ff, w.lin2_w, w.lin2_b, ws.tmp, n, d, e.d_ff), ws.x), 0, s));
+    ln.w = w.norm2_w; ln.b = w.norm2_b;
     D3PM_TRY(run_layernorm(cx, dt, ln, 0, s));
   }
-  LinearArgs g;   // timm Mlp: fc2(silu(fc1(x)))
-  g.X = ws.x; g.ldx = d; g.W = e.fc1_w; g.bias = e.fc1_b; g.Y = ws.ff; g.ldy = e.mlp_hidden; g.M = n; g.N = e.mlp_hidden; g.K = d; g.act = ACT_SILU;
-  D3PM_TRY(run_linear(cx, dt, g, 0, s));
-  g = LinearArgs();
-  g.X = ws.ff; g.ldx = e.mlp_hidden; g.W = e.fc2_w; g.bias = e.fc2_b; g.Y = out; g.ldy = d; g.M = n; g.N = d; g.K = e.mlp_hidden;
-  return run_linear(cx, dt, g, 0, s);
+  // timm Mlp: fc2(silu(fc1(x)))
+  D3PM_TRY(run_linear(cx, dt, projection(ws.x, e.fc1_w, e.fc1_b, ws.ff, n, e.mlp_hidden, d, ACT_SILU), 0, s));
+  return run_linear(cx, dt, projection(ws.ff, e.fc2_w, e.fc2_b, out, n, d, e.mlp_hidden), 0, s);
 }
 
 static bool encoder_ok(const d3pm_encoder_weights& e, int d) {
@@ -875,7 +867,8 @@ static int denoise_step_impl(const d3pm_shape* sh, const d3pm_weights* w, int ba
   D3PM_REQUIRE(workspace_bytes >= ws.total, D3PM_E_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, ws.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int layers = (only_layers >= 0 && only_layers < sh->n_layers) ? only_layers : sh->n_layers;
-  D3PM_TRY(denoiser_blocks(*sh, *w, batch, x_t, frame_mask, t, film, kv_text, kv_prompt, ws, layers, flags, s, f8));
+  const DenoiserArgs q{*sh, *w, batch, frame_mask, kv_text, kv_prompt, ws};
+  D3PM_TRY(denoiser_blocks(q, x_t, t, film, layers, flags, s, f8, fold_plan(q, flags, f8)));
   if (hidden_out)
     D3PM_CHECK_HIP(hipMemcpyAsync(hidden_out, ws.x, static_cast<size_t>(batch) * sh->canvas * sh->d_model * dtype_size(sh->dtype),
                                   hipMemcpyDeviceToDevice, s));
@@ -935,10 +928,12 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rows = batch * sh->canvas;
   const Ctx cx(sh->tuning);
+  const DenoiserArgs q{*sh, *w, batch, frame_mask, kv_text, kv_prompt, ws};
+  const int plan = fold_plan(q, flags, f8);      // the same for every iteration: the blocks and the sampler's prep share it
   bool prepared = false;      // the previous iteration's sampler launch has already embedded x_t and folded fc1 for this t
   for (int t = t_start; t > t_stop; --t) {
     if (cx.prof) cx.prof->sample_now = (t % cx.prof->stride) == 0;
-    D3PM_TRY(denoiser_blocks(*sh, *w, batch, x, frame_mask, t, film, kv_text, kv_prompt, ws, sh->n_layers, flags, s, f8, prepared));
+    D3PM_TRY(denoiser_blocks(q, x, t, film, sh->n_layers, flags, s, f8, plan, prepared));
     prepared = false;
     SampleArgs a;
     a.logits = ws.logits; a.logits_dtype = sh->dtype; a.ldl = logits_ld(*sh); a.x_t = x; a.x_next = x;
@@ -947,12 +942,10 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     if (flags & D3PM_FLAG_SEED_IN_HBM) a.seed_hbm = reinterpret_cast<const uint64_t*>(static_cast<uintptr_t>(seed));
     a.row0 = utt0 * static_cast<uint32_t>(sh->canvas); a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0;
     a.pc = make_posterior_consts(sched, t);
-    const double fin_flops = 2.0 * rows * sh->n_classes * sh->d_model;
-    (void)fin_flops;
 #ifdef D3PM_ABLATIONS
     if (fused_final_sample_applies(*sh, *w, ws, flags)) {
       // final projection + posterior + draw in one kernel: the logits stay on chip (d3pm_final_sample.hip)
-      ProfScope p(cx, D3PM_K_SAMPLE, s, fin_flops,
+      ProfScope p(cx, D3PM_K_SAMPLE, s, 2.0 * rows * sh->n_classes * sh->d_model,
                   dtype_size(sh->dtype) * (static_cast<double>(rows) * sh->d_model + static_cast<double>(sh->n_classes) * sh->d_model) + 8.0 * rows);
       D3PM_TRY(final_sample(sh->dtype, ws.x, sh->d_model, w->final_w, w->final_b, sh->d_model, a, s));
     } else
@@ -962,8 +955,7 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
       ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0,
                   static_cast<double>(rows) * levels(*sh) * (sh->n_classes * dtype_size(sh->dtype) + 8.0));
       NextIterPrep nx;
-      const int plan = t - 1 > t_stop ? fold_plan(*sh, *w, flags, f8, batch, ws) : FOLD_NONE;
-      if (plan != FOLD_NONE) {
+      if (t - 1 > t_stop && plan != FOLD_NONE) {
         const size_t es = dtype_size(sh->dtype);
         nx.dtype = sh->dtype; nx.table = w->resps_emb; nx.x = ws.x; nx.stats = ws.stats; nx.frame_mask = frame_mask; nx.d = sh->d_model;
         nx.quads = plan == FOLD_QUADS;
@@ -1083,32 +1075,18 @@ int d3pm_nar_level(const d3pm_nar_shape* sh, const d3pm_nar_weights* w, int batc
     const d3pm_nar_block_weights& b = w->blocks[l];
     // x = (x + to_out(attention(AdaLN(x) * m)) * m) * m
     D3PM_TRY(adaln(dt, ws.x, ws.h, at(b.attn_norm_emb, static_cast<size_t>(level) * 2 * d, es), ws.mask, n, d, s));
-    LinearArgs g;
-    g.X = ws.h; g.ldx = d; g.W = b.to_qkv_w; g.Y = ws.qkv; g.ldy = 3 * d; g.M = n; g.N = 3 * d; g.K = d;
-    D3PM_TRY(run_linear(cx, dt, g, flags, s));
-    AttnArgs a;
-    a.Q = ws.qkv; a.ldq = 3 * d; a.K = at(ws.qkv, d, es); a.V = at(ws.qkv, 2 * d, es); a.ldkv = 3 * d; a.O = ws.att; a.ldo = d;
-    a.B = batch; a.Tq = t_max; a.S = t_max; a.H = sh->n_heads; a.hd = hd; a.scale = 1.0f / std::sqrt(static_cast<float>(hd));
+    D3PM_TRY(run_linear(cx, dt, projection(ws.h, b.to_qkv_w, nullptr, ws.qkv, n, 3 * d, d), flags, s));
+    AttnArgs a = self_attention(ws.qkv, ws.att, batch, t_max, sh->n_heads, hd, es);
+    a.scale = 1.0f / std::sqrt(static_cast<float>(hd));      // rounded as the stock model rounds it
     a.key_len = ws.key_len;
     D3PM_TRY(run_attention(cx, dt, a, flags, s));
-    g = LinearArgs();
-    g.X = ws.att; g.ldx = d; g.W = b.to_out_w; g.bias = b.to_out_b; g.Y = ws.x; g.ldy = d; g.R1 = ws.x; g.ldr = d;
-    g.row_mask = ws.mask; g.mask_period = n; g.M = n; g.N = d; g.K = d;
-    D3PM_TRY(run_linear(cx, dt, g, flags, s));
+    D3PM_TRY(run_linear(cx, dt, with_row_mask(with_residual(projection(ws.att, b.to_out_w, b.to_out_b, ws.x, n, d, d), ws.x), ws.mask, n), flags, s));
     // x = (x + ffn(AdaLN(x) * m)) * m
     D3PM_TRY(adaln(dt, ws.x, ws.h, at(b.ffn_norm_emb, static_cast<size_t>(level) * 2 * d, es), ws.mask, n, d, s));
-    g = LinearArgs();
-    g.X = ws.h; g.ldx = d; g.W = b.ffn0_w; g.bias = b.ffn0_b; g.Y = ws.ffn; g.ldy = 4 * d; g.M = n; g.N = 4 * d; g.K = d; g.act = ACT_GELU;
-    D3PM_TRY(run_linear(cx, dt, g, flags, s));
-    g = LinearArgs();
-    g.X = ws.ffn; g.ldx = 4 * d; g.W = b.ffn3_w; g.bias = b.ffn3_b; g.Y = ws.x; g.ldy = d; g.R1 = ws.x; g.ldr = d;
-    g.row_mask = ws.mask; g.mask_period = n; g.M = n; g.N = d; g.K = 4 * d;
-    D3PM_TRY(run_linear(cx, dt, g, flags, s));
+    D3PM_TRY(run_linear(cx, dt, projection(ws.h, b.ffn0_w, b.ffn0_b, ws.ffn, n, 4 * d, d, ACT_GELU), flags, s));
+    D3PM_TRY(run_linear(cx, dt, with_row_mask(with_residual(projection(ws.ffn, b.ffn3_w, b.ffn3_b, ws.x, n, d, 4 * d), ws.x), ws.mask, n), flags, s));
   }
-  LinearArgs g;
-  g.X = ws.x; g.ldx = d; g.W = w->classifier_w; g.bias = w->classifier_b; g.Y = ws.logits; g.ldy = sh->n_tokens; g.M = n;
-  g.N = sh->n_tokens; g.K = d;
-  D3PM_TRY(run_linear(cx, dt, g, flags, s));
+  D3PM_TRY(run_linear(cx, dt, projection(ws.x, w->classifier_w, w->classifier_b, ws.logits, n, sh->n_tokens, d), flags, s));
   if (logits_out)
     D3PM_CHECK_HIP(hipMemcpyAsync(logits_out, ws.logits, static_cast<size_t>(n) * sh->n_tokens * es, hipMemcpyDeviceToDevice, s));
   return nar_sample(dt, ws.logits, sh->n_tokens, lens, resp, tr_max, stride, t_max, sh->n_tokens, level, temperature, seed, utt0,
