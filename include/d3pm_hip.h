@@ -38,13 +38,13 @@ extern "C" {
 /* 2: + d3pm_ce_loss_rows, the fp8 entry points (d3pm_*_fp8), D3PM_FLAG_SEED_IN_HBM, tuning knobs 2..3, GEMM variant 5
  *    (additions only) */
 /* 3: + d3pm_op_final_sample, d3pm_op_cond_embed, the fp32 training ops (d3pm_op_*_f32), d3pm_op_linear_rowpanel / _lnpro,
- *    d3pm_prof_read_class, d3pm_debug_gemm_clock, tuning knobs 4..11, GEMM variants 6..8; the kernel class D3PM_K_GEMM_LN took
+ *    d3pm_prof_read_class, d3pm_debug_gemm_clock [since removed], tuning knobs 4..11, GEMM variants 6..8; the kernel class D3PM_K_GEMM_LN took
  *    the value 4, so "every class" (D3PM_K_COUNT) is now 5 */
 /* 4: the tuning knobs moved from process-wide state (d3pm_set_tuning) into `d3pm_tuning`, reached through the shape structs
  *    (and a trailing argument of d3pm_op_linear / d3pm_op_attention); the profiling hooks became a handle (d3pm_prof);
  *    the library keeps no mutable global state besides the thread-local error string.  The experiment-only entry points
  *    (d3pm_set_tuning's ablation arms, d3pm_op_final_sample, d3pm_op_linear_lnpro, d3pm_debug_gemm_clock) left the product:
- *    they live in libd3pm_hip_ab.so, include/d3pm_hip_ab.h. */
+ *    they live in libd3pm_hip_ab.so, include/d3pm_hip_ab.h (d3pm_debug_gemm_clock has since been removed there too). */
 /* 5: + d3pm_op_attention_pair; new VALUES of existing tuning fields (row_panel bit 3, attn_query_groups 4, attn_cross_resident
  *    4 / 5); layouts unchanged */
 /* 6: LayerNorm folded into the projections (d3pm_fold_block, d3pm_weights.fold, d3pm_fold_bytes / d3pm_fold_build,

@@ -3,8 +3,8 @@
  * NOT part of the product.  libd3pm_hip_ab.so is the same sources compiled with -DD3PM_ABLATIONS
  * (python -c "import __graft_entry__ as g; g.build_ab()"); it exports everything include/d3pm_hip.h declares PLUS the
  * entry points below, and is loaded only by the interleaved A/B scripts tests/ab_*.py and tests/ab_bit_identity.py.  It holds
- * the schedules and fusions that were built, measured and NOT shipped (DESIGN.md section 3 records each measurement), and
- * timing-only ablation builds of the shipped kernels.  Its knobs are process-wide state on purpose (an experiment toggles
+ * the schedules and fusions that were built, measured and NOT shipped (DESIGN.md section 3 records each measurement); every
+ * one of them computes the results of the product.  Its knobs are process-wide state on purpose (an experiment toggles
  * them between interleaved arms); nothing in libd3pm_hip.so can reach any of this.
  */
 #ifndef D3PM_HIP_AB_H
@@ -21,17 +21,14 @@ extern "C" {
 #endif
 
 /* D3PM_AB_GEMM_BIG_MODE  schedule of the big-tile GEMM: 1 (shipped) / 0 = hand-placed / compiler-placed fragment reads, 9 = the
- *                        output stores of a tile issued inside the next tile's k-steps, 513 = non-temporal output stores,
- *                        2049 = every DMA piece of a k-step issued at its top (all: same results, none faster); 32769 = the
- *                        epilogue's operands (bias, residual rows, frame mask) requested at the top of the tile (same results).
- *                        TIMING-ONLY builds whose results are wrong by construction (parts of the kernel removed; bits:
- *                        16 no DMA, 32 no MFMA, 64 no barriers, 128 no LDS reads, 256 clock stamp for d3pm_debug_gemm_clock,
- *                        4096 with 32 = the operand stream through registers; 1025 = row panels without their LayerNorm
- *                        arithmetic): 17 32 33 81 145 209 257 465 1025 4129.
- * D3PM_AB_ATTN_ARM       0 = shipped; 3 = three 16-query groups per wave (bf16 self-attention; same results); 164 =
- *                        hand-placed fragment reads, 228 = K / V tiles by direct-to-LDS DMA (same results); 201 / 202 = the shipped
- *                        kernel held to two / one workgroup per CU; 100 + bits 1..32 = TIMING-ONLY builds with parts of the
- *                        kernel removed (results wrong by construction).
+ *                        output stores of a tile issued inside the next tile's k-steps, 2049 = every DMA piece of a k-step
+ *                        issued at its top (all: same results, none faster); 513 = accepted, runs the shipped schedule (its
+ *                        non-temporal output stores became the product's).
+ * D3PM_AB_ATTN_ARM       0 = shipped; 3 = three 16-query groups per wave (bf16 self-attention); 164 = hand-placed fragment
+ *                        reads, 228 = K / V tiles by direct-to-LDS DMA; 300 = the cross-attention walk software-pipelined (all:
+ *                        same results); 301 = accepted (tests/ab_attn_loop.py), runs the shipped kernels.
+ * Any other value is D3PM_E_ARG.  The probe builds that removed parts of a kernel to time the rest (and the clock / stamp
+ * read-outs that went with them) existed up to commit 4442690 and can be recovered from there; their figures are in profiles/.
  * D3PM_AB_GEMM_RING      1 = the five-slab ring schedule (csrc/d3pm_mfma_gemm_ring.hip; same results, measured slower) where it applies.
  * D3PM_AB_GELU_TABLE     1 = the bf16 GELU epilogue of the 192 x 256 big-tile and the latency GEMM reads rn_bf16(gelu(v)) from an
  *                        8.5 KiB LDS table (same results; 86 vs 73 us on fc1).
@@ -58,17 +55,6 @@ int d3pm_op_linear_lnpro(int dtype, const void *X, const void *W, const void *bi
 int d3pm_op_final_sample(const d3pm_shape *shape, const d3pm_weights *w, int batch, const void *hidden, const int32_t *x_t,
                          int32_t *x_next, int t, const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags,
                          void *stream);
-
-/* After a big-tile GEMM launched with D3PM_AB_GEMM_BIG_MODE bit 8 set (and a device synchronisation): {shader clocks, 100 MHz
- * reference ticks} that workgroup 0 spent in the kernel: clocks / ticks * 100 MHz = the clock the chip held under that load
- * (MI355X_MICROARCH.md "DVFS give-back" item 6).  No output of the kernel depends on it. */
-int d3pm_debug_gemm_clock(unsigned long long *clocks_and_ticks);
-
-/* Shader-clock stamps of the 32 x 32 x 16 self-attention kernel launched under D3PM_AB_ATTN_ARM = 320 with attn_query_groups = 32
- * (d3pm_mfma_attn32.hip): out[(slot * 12 + tile) * 8 + point], slot 0 = the first workgroup, 1 = one in the middle of the grid,
- * wave 0 of each; points: 0 top of the tile, 1 next tile's global loads issued, 2 scores available, 3 softmax done,
- * 4 P.V issued, 5 global loads returned, 6 LDS stores issued, 7 barrier passed. */
-int d3pm_debug_attn32_stamps(unsigned long long *out, int n);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

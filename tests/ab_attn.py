@@ -1,5 +1,7 @@
-"""Timing-only ablations of the MFMA self-attention kernel (not a test): python tests/ab_attn.py
-Runs on libd3pm_hip_ab.so (include/d3pm_hip_ab.h).  Arms: the shipped kernel and builds with parts removed (results wrong by construction) -- what each part costs in place."""
+"""Interleaved timing of the schedules of the MFMA self-attention kernel (not a test): python tests/ab_attn.py [arm ...]
+Runs on libd3pm_hip_ab.so (include/d3pm_hip_ab.h).  Arms: the shipped kernel (QG 2), QG 1 / 3, hand-placed fragment reads (164) and
+K / V by direct-to-LDS DMA (228); all give the same bits, which is asserted.  The builds with parts of the kernel removed (101 .. 160)
+and the occupancy probes (201 / 202) existed up to commit 4442690 and can be recovered from there; their figures are in profiles/."""
 import os
 import sys
 
@@ -9,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "tts-with-diffusion-model_amd"), ROOT]
 import __graft_entry__ as g  # noqa: E402
 
-g.build_ab()                       # libd3pm_hip_ab.so: the ablation arms are not in the product
+g.build_ab()                       # libd3pm_hip_ab.so: the experiment arms are not in the product
 from vall_e.vall_e import _hip  # noqa: E402
 _hip.use_ab_library()
 
@@ -33,11 +35,12 @@ def timeit(fn, reps=30):
     return e0.elapsed_time(e1) * 1e3 / reps
 
 
-ARMS = [(2, "shipped (QG 2)"), (228, "K/V tiles by direct-to-LDS DMA (same results)"), (164, "all fragment reads of a tile issued at its top (same results)"), (3, "QG 3 (48 queries per wave)"), (201, "shipped, two workgroups per CU"), (202, "shipped, one workgroup per CU"), (1, "QG 1"), (101, "no v_exp"), (102, "no max / rescale"), (103, "no exp, no max"), (104, "no staging"),
-        (112, "no staging, no barriers"), (116, "no P.V"), (132, "no Q.K"), (148, "no MFMA products"), (115, "only the MFMA products"),
-        (160, "only softmax VALU")]
+ARMS = [(2, "shipped (QG 2)"), (228, "K/V tiles by direct-to-LDS DMA (same results)"), (164, "all fragment reads of a tile issued at its top (same results)"), (3, "QG 3 (48 queries per wave)"), (1, "QG 1")]
 arms = [int(a) for a in sys.argv[1:]] or [a for a, _ in ARMS]
 names = dict(ARMS)
+for arm in arms:
+    if arm not in names:
+        sys.exit(f"arm {arm} is not built any more ({', '.join(str(a) for a in names)} are; see the docstring)")
 flops = 4.0 * B * H * T * T * 64
 ref = None
 for arm in arms:
@@ -45,10 +48,9 @@ for arm in arms:
         _hip.set_attn_arm(0); _hip.set_attn_query_groups(arm)
     else:
         _hip.set_attn_query_groups(0); _hip.set_attn_arm(arm)
-    if arm in (1, 2, 3, 164, 228, 201, 202):                  # the arms that must give the shipped kernel's bits
-        o = _hip.op_attention(q, k, v, H, 0.125, family=_hip.FAMILY_MFMA)
-        ref = o.clone() if ref is None else ref
-        assert torch.equal(o, ref), f"arm {arm}: output differs from the first arm"
+    o = _hip.op_attention(q, k, v, H, 0.125, family=_hip.FAMILY_MFMA)      # every arm must give the shipped kernel's bits
+    ref = o.clone() if ref is None else ref
+    assert torch.equal(o, ref), f"arm {arm}: output differs from the first arm"
     t = timeit(lambda: _hip.op_attention(q, k, v, H, 0.125, family=_hip.FAMILY_MFMA))
     print("%-28s %7.1f us  %6.0f TFLOP/s-equivalent" % (names.get(arm, str(arm)), t, flops / t / 1e6), flush=True)
 _hip.set_attn_query_groups(0)

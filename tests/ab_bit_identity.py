@@ -8,7 +8,8 @@ It builds the A/B library on demand (`__graft_entry__.build_ab()`, -DD3PM_ABLATI
 it for this process.  Every arm here was measured slower than the shipped path and is therefore not
 in libd3pm_hip.so; the tests keep the claim "same results" checkable: the fused final + sampler kernel, the bf16 GELU
 table, the LayerNorm-prologue GEMM, the compiler-placed / deferred-store / non-temporal big-tile schedules and the
-five-slab ring GEMM.
+five-slab ring GEMM.  These are all the arms the library still builds; the probe builds that removed parts of a kernel to time the
+rest existed up to commit 4442690 and can be recovered from there.
 """
 import math
 

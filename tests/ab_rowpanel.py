@@ -1,10 +1,12 @@
-"""Timing of the row-panel launches against the launches they replace (not a test): python tests/ab_rowpanel.py"""
+"""Timing of the row-panel launches against the launches they replace (not a test): python tests/ab_rowpanel.py
+(--abl, the build without the LayerNorm arithmetic, existed up to commit 4442690 and can be recovered from there)"""
 import math, statistics, sys, torch
 sys.path[:0] = ["tts-with-diffusion-model_amd", "."]
 import __graft_entry__ as g
-g.build_ab()                       # libd3pm_hip_ab.so: the no-LayerNorm timing build is not in the product
+if "--abl" in sys.argv:
+    sys.exit("--abl: the row-panel build without its LayerNorm arithmetic is not built any more (see the docstring)")
+g.build()
 from vall_e.vall_e import _hip
-_hip.use_ab_library()
 DEV, dtype = "cuda", torch.bfloat16
 M, K = 24576, 512
 g = torch.Generator(device="cpu").manual_seed(0)
@@ -31,10 +33,6 @@ def sep_self():
 arms = {"self_out fused": lambda: _hip.op_linear_rowpanel(x, w, b, r1, lw, lb, ln2_w=lw2, ln2_b=lb2),
         "self_out GEMM only (192x256)": lambda: _hip.op_linear(x, w, b, r1=r1, family=_hip.FAMILY_MFMA),
         "cross_out fused": lambda: _hip.op_linear_rowpanel(x, w, b, r1, lw, lb, x2=x2, film=film)}
-modes = [(1, "")] + ([(1025, " [no LN arithmetic]")] if "--abl" in sys.argv else [])
-for mode, tag in modes:
-    _hip.set_gemm_big_mode(mode)
-    for name, f in arms.items():
-        t = statistics.median(timeit(f) for _ in range(5))
-        print(f"{name + tag:48s} {t:6.1f} us", flush=True)
-_hip.set_gemm_big_mode(1)
+for name, f in arms.items():
+    t = statistics.median(timeit(f) for _ in range(5))
+    print(f"{name:48s} {t:6.1f} us", flush=True)

@@ -32,7 +32,6 @@ int ce_loss_launch(int, const void*, int, const int32_t*, const uint8_t*, int, i
 #ifdef D3PM_ABLATIONS
 bool final_sample_supported(int dtype, int n_classes, int d, const void* X, int ldx, const void* W);
 int final_sample(int dtype, const void* X, int ldx, const void* W, const void* bias, int d, const SampleArgs& a, hipStream_t s);
-int read_big_gemm_stamp(unsigned long long* out);
 // libd3pm_hip_ab.so only: the knobs of the experiments (include/d3pm_hip_ab.h).  Process-wide on purpose -- an A/B script toggles
 // them between interleaved arms; the product library does not contain this object.
 AbKnobs& ab_knobs() {
@@ -1245,28 +1244,18 @@ void d3pm_tuning_default(d3pm_tuning* t) {
 #ifdef D3PM_ABLATIONS
 int d3pm_ab_set(int knob, int value) {
   AbKnobs& k = ab_knobs();
-  static const int big_modes[] = {0, 1, 3, 5, 9, 17, 32, 33, 81, 145, 209, 257, 465, 513, 1025, 2049, 4129, 8193, 16385, 24577, 32769};
+  static const int big_modes[] = {0, 1, 9, 513, 2049};
   if (knob == D3PM_AB_GEMM_BIG_MODE) {
     for (int m : big_modes)
       if (m == value) { k.big_mode = value; return D3PM_OK; }
   }
-  if (knob == D3PM_AB_ATTN_ARM && (value == 0 || value == 3 || (value >= 100 && value <= 164) || value == 228 || value == 201 || value == 202 || value == 300 || value == 301 || (value >= 320 && value <= 324))) { k.attn_arm = value; return D3PM_OK; }
+  if (knob == D3PM_AB_ATTN_ARM && (value == 0 || value == 3 || value == 164 || value == 228 || value == 300 || value == 301)) { k.attn_arm = value; return D3PM_OK; }
   if (knob == D3PM_AB_GEMM_RING && (value == 0 || value == 1)) { k.ring = value; return D3PM_OK; }
   if (knob == D3PM_AB_GELU_TABLE && (value == 0 || value == 1)) { k.gelu_table = value; return D3PM_OK; }
   if (knob == D3PM_AB_LN_PROLOGUE && (value == 0 || value == 1)) { k.ln_prologue = value; return D3PM_OK; }
   if (knob == D3PM_AB_FUSED_FINAL_SAMPLE && (value == 0 || value == 1)) { k.fused_final_sample = value; return D3PM_OK; }
   set_error("d3pm_ab_set: unknown knob %d / value %d", knob, value);
   return D3PM_E_ARG;
-}
-
-int d3pm_debug_gemm_clock(unsigned long long* clocks_and_ticks) {
-  D3PM_REQUIRE(clocks_and_ticks, D3PM_E_ARG, "d3pm_debug_gemm_clock: null pointer");
-  return read_big_gemm_stamp(clocks_and_ticks);
-}
-
-int d3pm_debug_attn32_stamps(unsigned long long* out, int n) {
-  D3PM_REQUIRE(out && n > 0, D3PM_E_ARG, "d3pm_debug_attn32_stamps: bad arguments");
-  return read_attn32_stamps(out, n);
 }
 #endif
 

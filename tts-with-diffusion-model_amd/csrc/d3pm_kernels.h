@@ -213,9 +213,6 @@ int mfma_attention32_cross(int dtype, const AttnArgs& a, int n_qsplit, hipStream
 bool mfma_attention_split_supported(int dtype, const AttnArgs& a);
 int mfma_attention_split(int dtype, const AttnArgs& a, hipStream_t s);
 #ifdef D3PM_ABLATIONS
-int read_attn32_stamps(unsigned long long* out, int n);
-#endif
-#ifdef D3PM_ABLATIONS
 bool panel64_ln_supported(int dtype, const LinearArgs& a, const LnPrologue& ln);
 bool ln_prologue_linear_applies(int dtype, const LinearArgs& a, const LnPrologue& ln);   // would mfma_linear pick the latency GEMM?
 int ln_prologue_linear(int dtype, const LinearArgs& a, const LnPrologue& ln, hipStream_t s);

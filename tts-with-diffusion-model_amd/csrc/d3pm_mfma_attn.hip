@@ -94,8 +94,7 @@ __device__ __forceinline__ void store_rows16(T* row_base /* O + row * ldo + h * 
   }
 }
 
-// ABL != 0 is instantiated in the A/B library only (-DD3PM_ABLATIONS): timing-only ablation builds (results wrong by construction; tests/ab_attn.py): 1 no v_exp, 2 no maximum / rescale logic, 4 no K/V
-// staging after the first tile, 8 no barriers, 16 no P.V product, 32 no Q.K product
+// ABL != 0 is instantiated in the A/B library only (-DD3PM_ABLATIONS; same results; tests/ab_attn.py): bits 6 and 7.
 // fragment reads whose completion is waited for by hand (ABL bit 6: every K and V fragment of a tile issued at the top of
 // the tile, counted lgkmcnt before each consumer) -- hipcc sinks a plain LDS load to the instruction before its first use
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -278,7 +277,7 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
     if constexpr (kDma) {
       if (more) dma_tile(tile + 1, BUF ^ 1);           // BUF ^ 1 was last read in the previous tile, behind its barrier
     } else {
-      if (more && !(ABL & 4)) st = load_tile(tile + 1);
+      if (more) st = load_tile(tile + 1);
     }
 
     // ---- S^T tile: 64 keys x (16 QG) queries per wave; each K fragment feeds QG MFMAs ----
@@ -289,10 +288,7 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        if constexpr (ABL & 32) {
-#pragma unroll
-          for (int qg = 0; qg < QG; ++qg) s[qg][kt] = negm[qg] + floatx4{0.1f * kt, 0.2f, 0.3f * tile, 0.4f};
-        } else if constexpr ((ABL & 64) == 0) {
+        if constexpr ((ABL & 64) == 0) {
         uint4 kf = *reinterpret_cast<const uint4*>(kb + ok[ks] + kt * 16 * ROWB);
 #pragma unroll
         for (int qg = 0; qg < QG; ++qg) s[qg][kt] = mma<T>(kf, qf[qg][ks], ks == 0 ? negm[qg] : s[qg][kt]);
@@ -347,7 +343,7 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
       // Deferred maximum: m_ref only moves when some score of the wave exceeds it by more than 2^kDefer (or on the
       // first tile), so the common tile does neither the cross-lane maximum nor the rescale of O; probabilities are
       // then at most 2^kDefer instead of 1, which neither fp32 sums nor 16-bit P notice (normalised by the same sum).
-      if (!(ABL & 2) && (tile == 0 || __any(mx > kDefer))) {               // wave-uniform
+      if (tile == 0 || __any(mx > kDefer)) {               // wave-uniform
         mx = max_over_query_lanes(mx);                     // lanes l, l^16, l^32, l^48 share a query
         const float delta = tile == 0 ? mx : fmaxf(mx, 0.f);
 #pragma unroll
@@ -369,7 +365,7 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) s[qg][kt][r] = (ABL & 1) ? s[qg][kt][r] : __builtin_amdgcn_exp2f(s[qg][kt][r]);
+        for (int r = 0; r < 4; ++r) s[qg][kt][r] = __builtin_amdgcn_exp2f(s[qg][kt][r]);
       // contraction index j<4 -> key tile 2kb, j>=4 -> key tile 2kb+1 (same permutation as the V reads)
 #pragma unroll
       for (int kb2 = 0; kb2 < 2; ++kb2) {
@@ -379,16 +375,6 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
     }
 
     // ---- O^T += V^T . P^T ; each transposed V fragment feeds QG MFMAs ----
-    if constexpr (ABL & 16) {
-#pragma unroll
-      for (int qg = 0; qg < QG; ++qg)
-#pragma unroll
-        for (int kb2 = 0; kb2 < 2; ++kb2) {
-          acc_o[qg][kb2][0] += __builtin_bit_cast(float, pf[qg][kb2].x); acc_o[qg][kb2][1] += __builtin_bit_cast(float, pf[qg][kb2].y);
-          acc_o[qg][kb2][2] += __builtin_bit_cast(float, pf[qg][kb2].z); acc_o[qg][kb2][3] += __builtin_bit_cast(float, pf[qg][kb2].w);
-          acc_l[qg][0] += 1.0f;
-        }
-    } else {
     if constexpr ((ABL & 64) != 0) lds_wait_v<0>(vfr);
 #pragma unroll
     for (int kb2 = 0; kb2 < 2; ++kb2)
@@ -414,13 +400,12 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
     for (int kb2 = 0; kb2 < 2; ++kb2)
 #pragma unroll
       for (int qg = 0; qg < QG; ++qg) acc_l[qg] = mma<T>(ones, pf[qg][kb2], acc_l[qg]);
-    }
     if constexpr (kDma) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the next tile have landed
     } else {
-      if (more && !(ABL & 4)) store_tile(smem + (BUF ^ 1) * 2 * TILE, st);
+      if (more) store_tile(smem + (BUF ^ 1) * 2 * TILE, st);
     }
-    if constexpr (!(ABL & 8)) __syncthreads();
+    __syncthreads();
   };
   for (int tile = 0; tile < n_tiles; tile += 2) {
     do_tile(tile, std::integral_constant<int, 0>{});
@@ -768,19 +753,10 @@ int mfma_attention(int dtype, const AttnArgs& a, hipStream_t s) {
 #ifdef D3PM_ABLATIONS
   if (g_attn_qg == 3 && dtype == D3PM_BF16 && !a.Q2) {        // three query groups per wave (A/B: fewer LDS reads per MFMA, two waves per SIMD)
     D3PM_ATTN(bf16, 3, false);
-  } else if (g_attn_qg >= 200 && dtype == D3PM_BF16 && !a.Q2) {      // occupancy probe: the shipped QG = 2 kernel with idle dynamic LDS
-    const size_t pad = g_attn_qg == 201 ? 32 * 1024 : 96 * 1024;   // 201: two workgroups per CU, 202: one (three without)
-    D3PM_LDS_ATTR((&attn_mfma_hd64<bf16, 2, false, 0>), 96 * 1024);
-    attn_mfma_hd64<bf16, 2, false, 0><<<grid, block, pad, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K),
-        static_cast<const bf16*>(a.V), a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, nullptr, nullptr, nullptr,
-        nullptr, 0, n_first, a.key_len);
-  } else if (g_attn_qg >= 100 && dtype == D3PM_BF16 && !a.Q2) {      // timing-only ablations of the QG = 2 kernel
-#define D3PM_ABL(A) case A: attn_mfma_hd64<bf16, 2, false, A><<<grid, block, 0, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), \
-      static_cast<const bf16*>(a.V), a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, nullptr, nullptr, nullptr, nullptr, 0, n_first, a.key_len); break
-    switch (g_attn_qg - 100) {
-      D3PM_ABL(64); D3PM_ABL(128); D3PM_ABL(1); D3PM_ABL(2); D3PM_ABL(3); D3PM_ABL(4); D3PM_ABL(12); D3PM_ABL(16); D3PM_ABL(32); D3PM_ABL(48); D3PM_ABL(15); D3PM_ABL(60);
-      default: D3PM_ATTN(bf16, 2, false);
-    }
+  } else if ((g_attn_qg == 164 || g_attn_qg == 228) && dtype == D3PM_BF16 && !a.Q2) {      // the QG = 2 kernel with ABL bit 6 / bit 7
+#define D3PM_ABL(A) attn_mfma_hd64<bf16, 2, false, A><<<grid, block, 0, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), \
+      static_cast<const bf16*>(a.V), a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, nullptr, nullptr, nullptr, nullptr, 0, n_first, a.key_len)
+    if (g_attn_qg == 164) D3PM_ABL(64); else D3PM_ABL(128);
 #undef D3PM_ABL
   } else
 #endif

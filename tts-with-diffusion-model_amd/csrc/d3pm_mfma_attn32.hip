@@ -83,19 +83,12 @@ __device__ __forceinline__ void store_rows32(T* row_base /* O + row * ldo + h * 
   }
 }
 
-// STAMP (A/B library only): wave 0 of the first workgroup and of one in the middle of the grid records the shader clock at eight
-// points of every key tile (d3pm_debug_attn32_stamps); see the stamp() calls for the points
-constexpr int kStampTiles = 12, kStampPoints = 8;
-__device__ unsigned long long g_attn32_stamp[2 * kStampTiles * kStampPoints];
-
-template <typename T, int STAMP = 0>   // 1: coarse (start / end of every 32nd workgroup: shader clocks + 100 MHz ticks), 2: per tile
+template <typename T>
 __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, int ldq, const T* __restrict__ Kp,
                                                       const T* __restrict__ Vp, int ldkv, T* __restrict__ O, int ldo, int Tq,
                                                       int S, float scale, int H, int n_qblocks) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE];   // [buffer][K tile | V tile]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned long long stamp_c = 0, stamp_r = 0;
-  if constexpr (STAMP == 1) { stamp_c = __builtin_amdgcn_s_memtime(); stamp_r = __builtin_amdgcn_s_memrealtime(); }
   // XCD-aware order: each XCD gets a contiguous range of (utterance, head, query-block) ids, so the query blocks that share
   // one K / V share one L2
   int bid;
@@ -173,23 +166,12 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
     }
   }
 
-  const int stamp_slot = blockIdx.x == 0 ? 0 : (blockIdx.x == (gridDim.x / 16) * 8 + 3 ? 1 : -1);
-  auto stamp = [&](int tile, int point) __attribute__((always_inline)) {
-    if constexpr (STAMP == 2) {
-      __builtin_amdgcn_sched_barrier(0);
-      if (stamp_slot >= 0 && tid == 0 && tile < kStampTiles)
-        g_attn32_stamp[(stamp_slot * kStampTiles + tile) * kStampPoints + point] = __builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
   auto do_tile = [&](int tile, auto BUF_) __attribute__((always_inline)) {
     constexpr int BUF = decltype(BUF_)::value;
-    stamp(tile, 0);                                     // top of the tile (behind the previous tile's barrier)
     const char* kb_ = smem + BUF * 2 * TILE;
     const char* vb_ = kb_ + TILE;
     const bool more = tile + 1 < n_tiles;
     if (more) st = load_tile(tile + 1);
-    stamp(tile, 1);                                     // the next tile's global loads are issued
 
     // ---- S^T tile: 64 keys x 32 queries; the accumulator starts at -m_ref, so the scores leave the matrix pipe relative to
     // the running reference
@@ -222,7 +204,6 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
 #pragma unroll
       for (int i = 0; i < 16; ++i) negm[i] = -m_ref;
     }
-    stamp(tile, 2);                                     // scores available: K reads, 8 MFMAs, the maximum (+ a rare rescale)
     uint4 pf[4];
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
@@ -238,7 +219,6 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
                                pack2<T>(s[kb][8 * u + 4], s[kb][8 * u + 5]), pack2<T>(s[kb][8 * u + 6], s[kb][8 * u + 7])};
     }
 
-    stamp(tile, 3);                                     // exponentials, row sum, packing
     // ---- O^T += V^T . P ----
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -250,13 +230,8 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
         const uint2 lo = __builtin_bit_cast(uint2, va), hi = __builtin_bit_cast(uint2, vc);
         acc_o[db] = mma32<T>(uint4{lo.x, lo.y, hi.x, hi.y}, pf[t], acc_o[db]);
       }
-    stamp(tile, 4);                                     // V reads and the 8 P.V MFMAs issued
-    if constexpr (STAMP == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp(tile, 5);                                     // the next tile's global loads have returned
     if (more) store_tile(smem + (BUF ^ 1) * 2 * TILE, st);
-    stamp(tile, 6);                                     // its LDS stores issued
     __syncthreads();
-    stamp(tile, 7);                                     // barrier passed
   };
   for (int tile = 0; tile < n_tiles; tile += 2) {
     do_tile(tile, std::integral_constant<int, 0>{});
@@ -267,12 +242,6 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
   halves(lsum, la, lc);
   const float inv = 1.0f / (la + lc);
   store_rows32<T>(O + (static_cast<size_t>(b) * Tq + q0 + qn) * ldo + h * HD, acc_o, inv, hh, true);
-  if constexpr (STAMP == 1) {
-    if (tid == 0 && (blockIdx.x & 31) == 0 && (blockIdx.x >> 5) < 48) {
-      unsigned long long* o = g_attn32_stamp + (blockIdx.x >> 5) * 4;
-      o[0] = stamp_c; o[1] = __builtin_amdgcn_s_memtime(); o[2] = stamp_r; o[3] = __builtin_amdgcn_s_memrealtime();
-    }
-  }
 }
 
 // ---- the software-pipelined form ---------------------------------------------------------------------------------------
@@ -287,20 +256,15 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
 // The groups are pinned with sched_barrier(0) (hipcc otherwise hoists the exponentials in front of the products).  K(j + 1)
 // of the next tile is read half a tile before that tile's turn: three LDS buffers, tiles staged two ahead, still one barrier
 // per tile.
-// ABL != 0: timing-only ablations for tools/probe_attn32.hip (WRONG results): 1 no exponentials, 2 no S products, 4 no P.V
-// products, 8 no V fragment reads, 16 no K fragment reads, 32 no staging / barrier after the prologue, 64 no maximum / test,
-// 128 no packing, 256 no row sum
 // NW = waves (32-query groups) per workgroup: 4 = 128 queries, three workgroups per CU; 6 = 192 queries, two workgroups per CU --
 // the same twelve waves per CU, but every staged K / V tile serves half as many queries again (a third fewer bytes L2 -> LDS and
 // staging instructions per query; waves 4 and 5 do not stage).  A query's arithmetic does not depend on NW: bit-identical.
-template <typename T, int STAMP = 0, int ABL = 0, int NW = 4>
+template <typename T, int NW = 4>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T* __restrict__ Q, int ldq, const T* __restrict__ Kp,
                                                        const T* __restrict__ Vp, int ldkv, T* __restrict__ O, int ldo, int Tq,
                                                        int S, float scale, int H, int n_qblocks) {
   __shared__ __attribute__((aligned(16))) char smem[3 * 2 * TILE];   // [buffer][K tile | V tile]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned long long stamp_c = 0, stamp_r = 0;
-  if constexpr (STAMP == 1) { stamp_c = __builtin_amdgcn_s_memtime(); stamp_r = __builtin_amdgcn_s_memrealtime(); }
   int bid;
   {
     const int nblocks = gridDim.x, q = nblocks >> 3, r = nblocks & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
@@ -406,7 +370,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
   }
 
 #define SB() __builtin_amdgcn_sched_barrier(0)
-#define EXP2(x) ((ABL & 1) ? (x) + 1.0f : __builtin_amdgcn_exp2f(x))
+#define EXP2(x) __builtin_amdgcn_exp2f(x)
   // one block: sc = S(j) relative to m_ref; NEXT: sn <- S(j + 1), kf holds K(j + 1) on entry and K(j + 2) (from knext) on exit;
   // vblock = the 32 V rows of block j
   // STG: which half of the tile staged two ahead this block carries through registers (0 none, 1 the K rows, 2 the V rows): a
@@ -414,37 +378,29 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
   auto block = [&](floatx16& sc, floatx16& sn, const char* vblock, const char* knext, auto NEXT_, auto STG_, int stile, char* sdst)
       __attribute__((always_inline)) {
     constexpr bool NEXT = decltype(NEXT_)::value;
-    constexpr int STG = (ABL & 32) ? 0 : decltype(STG_)::value;
+    constexpr int STG = decltype(STG_)::value;
     typedef short4v __attribute__((address_space(3))) * lds_ptr;
     uint4 vf[2], pf, h0, h1;
     auto read_v = [&](int t, int db) __attribute__((always_inline)) {
-      if constexpr (ABL & 8) {
-        vf[db] = uint4{0x3c003c00u + t, 0x3c003800u + db, 0x38003c00u, 0x3c003c00u ^ static_cast<uint32_t>(lane)};
-      } else {
-        const uint2 lo = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(vblock + ov[db] + (16 * t) * ROWB)));
-        const uint2 hi = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(vblock + ov[db] + (16 * t + 8) * ROWB)));
-        vf[db] = uint4{lo.x, lo.y, hi.x, hi.y};
-      }
+      const uint2 lo = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(vblock + ov[db] + (16 * t) * ROWB)));
+      const uint2 hi = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(vblock + ov[db] + (16 * t + 8) * ROWB)));
+      vf[db] = uint4{lo.x, lo.y, hi.x, hi.y};
     };
     // Vector work per MFMA gap is sized from tools/probe_issue2.hip: beside one v_mfma_f32_32x32x16 (32 cycles) fit three v_exp_f32
     // or v_cvt_pk (8 - 10 cycles each) or six plain adds; v_pk_add_f32 / v_pk_mul_f32 do NOT overlap with the matrix pipe (three
     // per gap: 62 cycles per gap), so the row sum is four chains of plain v_add_f32 from asm (hipcc would pair them)
     auto e4 = [&](int i) __attribute__((always_inline)) {
       sc[i] = EXP2(sc[i]); sc[i + 1] = EXP2(sc[i + 1]); sc[i + 2] = EXP2(sc[i + 2]); sc[i + 3] = EXP2(sc[i + 3]);
-      if constexpr (!(ABL & 256)) {
-        asm volatile("v_add_f32 %0, %0, %1" : "+v"(ls[0]) : "v"(sc[i]));
-        asm volatile("v_add_f32 %0, %0, %1" : "+v"(ls[1]) : "v"(sc[i + 1]));
-        asm volatile("v_add_f32 %0, %0, %1" : "+v"(ls[2]) : "v"(sc[i + 2]));
-        asm volatile("v_add_f32 %0, %0, %1" : "+v"(ls[3]) : "v"(sc[i + 3]));
-      }
+      asm volatile("v_add_f32 %0, %0, %1" : "+v"(ls[0]) : "v"(sc[i]));
+      asm volatile("v_add_f32 %0, %0, %1" : "+v"(ls[1]) : "v"(sc[i + 1]));
+      asm volatile("v_add_f32 %0, %0, %1" : "+v"(ls[2]) : "v"(sc[i + 2]));
+      asm volatile("v_add_f32 %0, %0, %1" : "+v"(ls[3]) : "v"(sc[i + 3]));
     };
     auto pack8 = [&](int i) __attribute__((always_inline)) {
-      if constexpr (ABL & 128) pf = uint4{__builtin_bit_cast(uint32_t, sc[i]), __builtin_bit_cast(uint32_t, sc[i + 2]), __builtin_bit_cast(uint32_t, sc[i + 4]), __builtin_bit_cast(uint32_t, sc[i + 6])};
-      else pf = uint4{pack2<T>(sc[i], sc[i + 1]), pack2<T>(sc[i + 2], sc[i + 3]), pack2<T>(sc[i + 4], sc[i + 5]), pack2<T>(sc[i + 6], sc[i + 7])};
+      pf = uint4{pack2<T>(sc[i], sc[i + 1]), pack2<T>(sc[i + 2], sc[i + 3]), pack2<T>(sc[i + 4], sc[i + 5]), pack2<T>(sc[i + 6], sc[i + 7])};
     };
-    auto pv = [&](int db, int slot) __attribute__((always_inline)) {
-      if constexpr (ABL & 4) acc_o[db][slot] += __builtin_bit_cast(float, pf.x) + __builtin_bit_cast(float, vf[db].y);
-      else acc_o[db] = mma32<T>(vf[db], pf, acc_o[db]);
+    auto pv = [&](int db) __attribute__((always_inline)) {
+      acc_o[db] = mma32<T>(vf[db], pf, acc_o[db]);
     };
     SB();
     if constexpr (STG != 0) {      // unconditional in the tile index (a branch on it splits the block and hipcc sinks the vector work
@@ -459,33 +415,33 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
     read_v(0, 1);
     SB();
     // ---- phase 1
-    if constexpr (NEXT) { if constexpr (ABL & 2) sn = negm; else sn = mma32<T>(kf[0], qf[0], negm); }
+    if constexpr (NEXT) sn = mma32<T>(kf[0], qf[0], negm);
     e4(0);
     SB();
-    if constexpr (NEXT && !(ABL & 2)) sn = mma32<T>(kf[1], qf[1], sn);
+    if constexpr (NEXT) sn = mma32<T>(kf[1], qf[1], sn);
     e4(4);
     SB();
-    if constexpr (NEXT && !(ABL & 2)) sn = mma32<T>(kf[2], qf[2], sn);
+    if constexpr (NEXT) sn = mma32<T>(kf[2], qf[2], sn);
     pack8(0);
     SB();
-    if constexpr (NEXT && !(ABL & 2)) sn = mma32<T>(kf[3], qf[3], sn);
+    if constexpr (NEXT) sn = mma32<T>(kf[3], qf[3], sn);
     e4(8);
     SB();
     // ---- phase 2
-    pv(0, 0);
+    pv(0);
     read_v(1, 0);                                          // the fragment register is free once the product is issued
     e4(12);
     SB();
-    pv(1, 0);
+    pv(1);
     read_v(1, 1);
-    if constexpr (NEXT && !(ABL & 16)) read_k(knext);
+    if constexpr (NEXT) read_k(knext);
     pack8(8);
     SB();
-    pv(0, 1);
+    pv(0);
     float mx = 0.f;
-    if constexpr (NEXT && !(ABL & 64)) mx = row_max(sn);
+    if constexpr (NEXT) mx = row_max(sn);
     SB();
-    pv(1, 1);
+    pv(1);
     if constexpr (STG != 0) {
       if (NW == 4 || stager) {
         *reinterpret_cast<uint4*>(sdst + (STG == 1 ? ko0 : TILE + vo0)) = h0;
@@ -493,7 +449,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
       }
     }
     SB();
-    if constexpr (NEXT && !(ABL & 64)) {
+    if constexpr (NEXT) {
       if (__builtin_expect(__any(mx > kDefer), 0)) {       // wave-uniform, rare
         float a, c;
         halves(mx, a, c);                                  // lanes l and l ^ 32 share a query
@@ -529,7 +485,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
     const char* vb = smem + cur + TILE;
     block(sA, sB, vb, smem + nx1, Yes{}, StK{}, i + 2, smem + nx2);                     // keys 0..31 of tile i; then K(tile i + 1, first half)
     block(sB, sA, vb + 32 * ROWB, smem + nx1 + 32 * ROWB, Yes{}, StV{}, i + 2, smem + nx2);
-    if constexpr (!(ABL & 32)) __syncthreads();
+    __syncthreads();
     const int t = cur;
     cur = nx1; nx1 = nx2; nx2 = t;
   }
@@ -545,12 +501,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
   halves((ls[0] + ls[1]) + (ls[2] + ls[3]), la, lc);
   const float inv = 1.0f / (la + lc);
   store_rows32<T>(O + (static_cast<size_t>(b) * Tq + q0 + qn) * ldo + h * HD, acc_o, inv, hh, true);
-  if constexpr (STAMP == 1) {
-    if (tid == 0 && (blockIdx.x & 31) == 0 && (blockIdx.x >> 5) < 48) {
-      unsigned long long* o = g_attn32_stamp + (blockIdx.x >> 5) * 4;
-      o[0] = stamp_c; o[1] = __builtin_amdgcn_s_memtime(); o[2] = stamp_r; o[3] = __builtin_amdgcn_s_memrealtime();
-    }
-  }
 }
 
 // ---- the cross-attention pair of a block on the same instruction: attn32_cross_hd64 ------------------------------------------
@@ -811,15 +761,6 @@ bool mfma_attention32_supported(int dtype, const AttnArgs& a) {
   return aligned(a.Q, 16) && aligned(a.K, 16) && aligned(a.V, 16) && aligned(a.O, 16);
 }
 
-#ifdef D3PM_ABLATIONS
-int read_attn32_stamps(unsigned long long* out, int n) {
-  const int total = 2 * kStampTiles * kStampPoints;
-  D3PM_CHECK_HIP(hipDeviceSynchronize());
-  D3PM_CHECK_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_attn32_stamp), sizeof(unsigned long long) * (n < total ? n : total)));
-  return D3PM_OK;
-}
-#endif
-
 // the cross-attention pair of a block with both K / V images resident (<= 64 text keys, <= 256 prompt keys), no key lengths
 bool mfma_attention32_cross_supported(int dtype, const AttnArgs& a) {
   if (dtype != D3PM_F16 && dtype != D3PM_BF16) return false;
@@ -850,28 +791,6 @@ int mfma_attention32_cross(int dtype, const AttnArgs& a, int n_qsplit, hipStream
 int mfma_attention32(int dtype, const AttnArgs& a, hipStream_t s) {
   const int n_qblocks = a.Tq / 128;
   const dim3 grid(static_cast<unsigned>(n_qblocks * a.H * a.B)), block(256);
-#ifdef D3PM_ABLATIONS
-  if (ab_knobs().attn_arm >= 321 && ab_knobs().attn_arm <= 324 && dtype == D3PM_BF16) {      // coarse stamps: 321 the plain walk, 322 the pipelined one; 323 / 324: the same at ONE workgroup per CU (idle dynamic LDS)
-    const int arm = ab_knobs().attn_arm;
-    const size_t pad = arm >= 323 ? 72 * 1024 : 0;
-    D3PM_LDS_ATTR((&attn32_hd64<bf16, 1>), 96 * 1024);
-    D3PM_LDS_ATTR((&attn32p_hd64<bf16, 1>), 96 * 1024);
-    if (arm == 321 || arm == 323)
-      attn32_hd64<bf16, 1><<<grid, block, pad, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), static_cast<const bf16*>(a.V),
-                                                  a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks);
-    else
-      attn32p_hd64<bf16, 1><<<grid, block, pad, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), static_cast<const bf16*>(a.V),
-                                                   a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks);
-    D3PM_LAUNCH_CHECK();
-    return D3PM_OK;
-  }
-  if (ab_knobs().attn_arm == 320 && dtype == D3PM_BF16) {      // the stamped build (timing probe)
-    attn32_hd64<bf16, 2><<<grid, block, 0, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), static_cast<const bf16*>(a.V),
-                                                   a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks);
-    D3PM_LAUNCH_CHECK();
-    return D3PM_OK;
-  }
-#endif
   if (tune_of(a.tune).attn_query_groups != 33) {           // 33: the plain walk (A/B against the pipelined one)
 #ifdef D3PM_ABLATIONS
     // A/B library only (attn_query_groups = 35): 192-query workgroups of six waves, two per CU -- a third fewer K / V bytes staged
@@ -880,11 +799,11 @@ int mfma_attention32(int dtype, const AttnArgs& a, hipStream_t s) {
     if (tune_of(a.tune).attn_query_groups == 35 && a.Tq % 192 == 0) {
       const dim3 grid6(static_cast<unsigned>(a.Tq / 192 * a.H * a.B)), block6(384);
       if (dtype == D3PM_F16)
-        attn32p_hd64<f16, 0, 0, 6><<<grid6, block6, 0, s>>>(static_cast<const f16*>(a.Q), a.ldq, static_cast<const f16*>(a.K), static_cast<const f16*>(a.V),
-                                                            a.ldkv, static_cast<f16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, a.Tq / 192);
+        attn32p_hd64<f16, 6><<<grid6, block6, 0, s>>>(static_cast<const f16*>(a.Q), a.ldq, static_cast<const f16*>(a.K), static_cast<const f16*>(a.V),
+                                                      a.ldkv, static_cast<f16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, a.Tq / 192);
       else
-        attn32p_hd64<bf16, 0, 0, 6><<<grid6, block6, 0, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), static_cast<const bf16*>(a.V),
-                                                             a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, a.Tq / 192);
+        attn32p_hd64<bf16, 6><<<grid6, block6, 0, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), static_cast<const bf16*>(a.V),
+                                                       a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, a.Tq / 192);
       D3PM_LAUNCH_CHECK();
       return D3PM_OK;
     }

@@ -60,10 +60,8 @@ __device__ __forceinline__ void glds16_m0(const void* sbase, uint32_t voff, uint
 // bit 0 = hand-scheduled fragment reads (asm, counted lgkmcnt); bit 3 (8) = deferred stores: a tile's 12 output stores
 // per wave are issued a few per k-step inside the NEXT tile's main loop (all CUs finish their tiles together, so stores
 // issued in the epilogue arrive as one chip-wide burst that the HBM write path drains at ~5.5 TB/s while every MFMA pipe
-// idles: 4.5 us per 25 MB round; needs K >= 512); the other bits are timing-only ablations (WRONG
-// results): 16 = no DMA pieces in the k-loop, 32 = no fragment reads / MFMAs, 64 = no waits / barriers, 128 = the MFMAs
-// take their operands from registers (no LDS reads)
-__device__ unsigned long long g_big_stamp[4];   // MODE bit 8: {shader clocks, 100 MHz ticks} of block 0 (clock under load)
+// idles: 4.5 us per 25 MB round; needs K >= 512); bit 11 (2048) = every DMA piece of the next k-step issued in front of the
+// first MFMA group instead of one per group.  Instantiated: 1, 0, 9 and 2049.
 
 // Row-panel fusion (FUSE != 0; 96 x 512 tiles, d_model = 512 only: a workgroup then owns whole rows of the residual stream):
 //   bit 0  a SECOND product with the same weights runs through the same tile before the epilogue -- the text and prompt
@@ -80,7 +78,7 @@ template <typename T> struct RowPanelArgs {
   const T* X2; const T* lnw; const T* lnb; const T* lnw2; const T* lnb2; const T* film; T* lny; T* lny2; float eps;
   uint8_t* sx; uint8_t* sx2;
 };
-constexpr int FUSE_DUAL = 1, FUSE_LN = 2, FUSE_LN2 = 4, FUSE_FILM = 8, FUSE_ABL_NOLN = 16, FUSE_MX = 32;   // 16: timing-only (LayerNorm arithmetic skipped)
+constexpr int FUSE_DUAL = 1, FUSE_LN = 2, FUSE_LN2 = 4, FUSE_FILM = 8, FUSE_MX = 32;
 
 template <typename T, int EPI, int WM, int WN, int MODE, int FUSE = 0>
 __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __restrict__ X, int ldx, const T* __restrict__ W,
@@ -97,14 +95,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
   constexpr int X_BYTES = TM * ROW_BYTES, STAGE = (TM + TN) * ROW_BYTES;
   static_assert(NDMA <= 12, "one DMA piece per group of four MFMAs");
   constexpr bool kHand = (MODE & 1) != 0;
-  constexpr int ABL = (MODE >> 4) & 3;
-  constexpr bool kNoSync = (MODE & 64) != 0, kNoReads = (MODE & 128) != 0, kStamp = (MODE & 256) != 0;
-  constexpr bool kPrioYoung = (MODE & 2) != 0, kPrioMfma = (MODE & 4) != 0, kDrip = (MODE & 8) != 0;
-  // MODE bit 15: the epilogue's operands (bias, residual rows, frame mask) of a tile are requested at the top of the tile instead
-  // of behind its last MFMA -- one exposed round trip less per tile, and for one-round launches (fc2: one tile per CU) the 25 MB
-  // residual read runs under the k-loop instead of after it.  NPRE = the vector-memory operations this certainly adds behind
-  // the previous tile's stores (a LOWER bound keeps the counted waits safe: they may only wait for more): 12 residual + 6 mask loads
-  constexpr bool kPreEpi = (MODE & 32768) != 0 && FUSE == 0 && (EPI & EPI_R2) == 0;
+  constexpr bool kDrip = (MODE & 8) != 0;
   // EPI_LNF (K = 512: the launcher): the row moments a lane needs for its six row blocks are 24 x 8 bytes per tile -- 48 KB per
   // workgroup tile beside its 320 KB of operands, through the same CU <-> L2 path (EPI_QUADS: 6 x 8 bytes, 12 KB) -- and a round trip
   // the epilogue would start with.  Loaded where the epilogue needs them they cost qkv 36.7 -> 45.1 us and fc1 69.7 -> 84.8 us in the loop; requested at
@@ -120,22 +111,18 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
   constexpr int MPR = kQuads ? 1 : 4;                   // moment loads per row block and lane: one quad, or parts 4 g .. 4 g + 3
   constexpr int NMOM = 6 * MPR;                         // the moment loads of a tile: what the epilogue's counted wait leaves in flight
   static_assert(NMOM == (kQuads ? 6 : 24) && NMOM < 64, "vmcnt operand");
-  constexpr int NPRE = !kPreEpi ? 0 : ((EPI & EPI_R1) ? 12 : 0) + ((EPI & EPI_MASK) ? 6 : 0);
-  static_assert((MODE & 32768) == 0 || (!kDrip && (MODE & 1)), "epilogue prefetch rides in the hand-placed schedule");
   constexpr bool kDual = (FUSE & FUSE_DUAL) != 0, kLn = (FUSE & FUSE_LN) != 0, kLn2 = (FUSE & FUSE_LN2) != 0, kFilm = (FUSE & FUSE_FILM) != 0;
   constexpr bool kMx = (FUSE & FUSE_MX) != 0;
   static_assert(!kMx || kLn, "the MX output is the LayerNorm output");
   static_assert(FUSE == 0 || !kDrip, "fusions ride in the hand-placed schedule without deferred stores");
   static_assert(FUSE == 0 || FUSE == FUSE_DUAL || (WM == 1 && WN == 8 && (MODE & 1)), "row-panel fusion: 96 x 512 tiles, hand-placed schedule");
-  static_assert((EPI & (EPI_LNF | EPI_STATS)) == 0 || ((FUSE == 0 || (FUSE == FUSE_DUAL && (EPI & EPI_LNF) == 0)) && !kDrip && !kPreEpi),
+  static_assert((EPI & (EPI_LNF | EPI_STATS)) == 0 || ((FUSE == 0 || (FUSE == FUSE_DUAL && (EPI & EPI_LNF) == 0)) && !kDrip),
                 "the folded-LayerNorm epilogues ride in the plain launches (and the row moments in the dual out-projection)");
   static_assert(!kLn2 || kLn, "the second LayerNorm shares the moments of the first");
   static_assert(!kDrip || kHand, "deferred stores ride in the hand-placed schedule");
   constexpr int SPS = 12 - NDMA;                        // deferred stores per k-step: the MFMA groups behind the last DMA piece
   constexpr int DRIP_STEPS = kDrip ? (12 + SPS - 1) / SPS : 0;          // 3 (192 x 256) or 6
   constexpr int PEEL = kDrip ? ((DRIP_STEPS + 1 + 1) & ~1) : 2;           // k-steps written out per tile (even)
-  unsigned long long stamp_c = 0, stamp_r = 0;
-  if constexpr (kStamp) { stamp_c = __builtin_amdgcn_s_memtime(); stamp_r = __builtin_amdgcn_s_memrealtime(); }
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -152,15 +139,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
   // re-fetched each panel 2-3 times from the fabric (PMC 93.6 MB per launch against 49 / 30 algorithmic), so it is not kept.
   const int t_end = cnt, t_step = per_xcd;
   if (t >= t_end) return;                                            // block-uniform
-  if constexpr ((MODE & (8192 | 16384)) != 0) {
-    // A/B: de-synchronise the chip-wide output burst -- the workgroups of every second XCD start later by a fraction of a tile
-    // (bits 13 / 14 / both: ~2 / 4 / 6 us; one s_sleep 127 measured ~3.1 us), so that one group's stores drain while the other
-    // group streams operands
-    if (xcd & 1) {
-      constexpr int units = ((MODE >> 13) & 3) * 2;
-      for (int i = 0; i < units; ++i) __builtin_amdgcn_s_sleep(40);          // ~1 us each
-    }
-  }
   const uint32_t lds_base = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem));
   // DMA piece j of an operand tile = rows 8j .. 8j+7; a wave takes pieces j = wave + NW p, so the swizzle key
   // (row >> 1) & 7 = (4 (j & 1) + (lane >> 4)) & 7 is the same for all of its pieces: one per-lane offset per operand
@@ -193,9 +171,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
       gelu_table_to_lds(gelu_tab_g, smem + 2 * STAGE, tid, NW * 64);
       gelu_tab = reinterpret_cast<const uint16_t*>(smem + 2 * STAGE);     // the first k-step's barrier publishes it
     }
-  }
-  if constexpr (kPrioYoung) {      // the later-dispatched half of an 8-wave workgroup loses issue arbitration on its SIMD
-    if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
   }
   const int nk = K / BK;                                             // even (checked by the launcher)
   int tile = lo + t;
@@ -261,7 +236,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
       for (int b = 0; b < 6; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
     const int m0 = (tile / n_tiles) * TM, n0 = (tile % n_tiles) * TN;
     [[maybe_unused]] EpiPre<T, 4, 6> pre;
-    if constexpr (kPreEpi) epilogue_prefetch<T, EPI, 4, 6>(pre, bias, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 96, n0 + wn * 64, lane);
     // what follows this tile (block-uniform); the last tile re-reads its own first k-step: valid memory, never used
     const int t_next = t + t_step;
     const bool more = t_next < t_end;
@@ -278,79 +252,40 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
       const char* bw = fw_base + S * STAGE;
       const uint32_t nxt = lds_base + (S ^ 1) * STAGE;
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (!kNoSync) {
-        if constexpr (WAITN > 0) {
-          if (!kDrip || pending) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAITN) : "memory");
-          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();      // every wave's pieces of this k-step have landed; stage S ^ 1 is no longer read
+      if constexpr (WAITN > 0) {
+        if (!kDrip || pending) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAITN) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
+      __builtin_amdgcn_s_barrier();      // every wave's pieces of this k-step have landed; stage S ^ 1 is no longer read
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (ABL == 2 && (MODE & 4096) != 0) {
-        // timing probe: the same pieces through registers (global_load_dwordx4 -> ds_write_b128) instead of LDS-DMA
-        uintx4 stg[NDMA];
-#pragma unroll
-        for (int p = 0; p < NDMA; ++p) {
-          if (p < XPW) {
-            int j = wave + NW * p;
-            if constexpr (XD % NW != 0) { if (j >= XD) j = (XD / NW) * NW + wave % (XD % NW); }
-            stg[p] = *reinterpret_cast<const uintx4*>(reinterpret_cast<const char*>(px + static_cast<size_t>(8 * j) * ldx) + ox);
-          } else {
-            const int j = wave + NW * (p - XPW);
-            stg[p] = *reinterpret_cast<const uintx4*>(reinterpret_cast<const char*>(pw + static_cast<size_t>(8 * j) * K) + ow);
-          }
-        }
-#pragma unroll
-        for (int p = 0; p < NDMA; ++p) {
-          int j = p < XPW ? wave + NW * p : wave + NW * (p - XPW);
-          if constexpr (XD % NW != 0) { if (p < XPW && j >= XD) j = (XD / NW) * NW + wave % (XD % NW); }
-          *reinterpret_cast<uintx4*>(smem + (S ^ 1) * STAGE + (p < XPW ? 0 : X_BYTES) + j * 1024 + lane * 16) = stg[p];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      } else if constexpr (ABL == 2) {
-#pragma unroll
-        for (int g = 0; g < NDMA; ++g) dma(g, px, pw, nxt);
-      } else if constexpr (kHand) {
+      if constexpr (kHand) {
         // issue order of the 20 fragment reads of a k-step: W0..3 X0 X1 | g0: X2 | g1: X3 | g2: X4 W'0 | g3: X5 W'1 | g4: X6 W'2 |
         // g5: X7 W'3 | g6: X8 | g7: X9 | g8: X10 | g9: X11 (X six row blocks per k-half, W' = the second k-half's W fragments);
         // group g consumes X_g (and W at g = 0, W' at g = 6): the counts below are the reads younger than what it needs
         const uint32_t ax0 = lds_base + S * STAGE + wm * 96 * ROW_BYTES + fo0, ax1 = ax0 - fo0 + fo1;
         const uint32_t aw0 = lds_base + S * STAGE + X_BYTES + wn * 64 * ROW_BYTES + fo0, aw1 = aw0 - fo0 + fo1;
         uintx4 fw0[4], fw1[4], fx[3];
-        if constexpr (kNoReads) {
-          const uintx4 junk = {0x3f803f80u + lane * 0x10001u, 0x3f003e80u ^ (lane << 7), 0xbf80bf00u + S, 0x3e803f00u ^ lane};
-          for (int q = 0; q < 4; ++q) { fw0[q] = junk + q; fw1[q] = junk * (q + 3); }
-          fx[0] = junk + 7; fx[1] = junk * 5; fx[2] = junk + 11;
-          for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(fw0[q]), "+v"(fw1[q]));
-          asm volatile("" : "+v"(fx[0]), "+v"(fx[1]), "+v"(fx[2]));
-        } else {
-          static_for<4>([&](auto NT) { lds_read16(fw0[NT.value], aw0, NT.value * 16 * ROW_BYTES); });
-          lds_read16(fx[0], ax0, 0);
-          lds_read16(fx[1], ax0, 16 * ROW_BYTES);
-        }
+        static_for<4>([&](auto NT) { lds_read16(fw0[NT.value], aw0, NT.value * 16 * ROW_BYTES); });
+        lds_read16(fx[0], ax0, 0);
+        lds_read16(fx[1], ax0, 16 * ROW_BYTES);
         static_for<12>([&](auto G) {
           constexpr int g = G.value, ks = g / 6, mt = g % 6;
-          if constexpr (!kNoReads) {
-            if constexpr (g + 2 < 12) lds_read16(fx[(g + 2) % 3], (g + 2) / 6 ? ax1 : ax0, ((g + 2) % 6) * 16 * ROW_BYTES);
-            if constexpr (ks == 0 && mt >= 2) lds_read16(fw1[mt - 2], aw1, (mt - 2) * 16 * ROW_BYTES);
-          }
+          if constexpr (g + 2 < 12) lds_read16(fx[(g + 2) % 3], (g + 2) / 6 ? ax1 : ax0, ((g + 2) % 6) * 16 * ROW_BYTES);
+          if constexpr (ks == 0 && mt >= 2) lds_read16(fw1[mt - 2], aw1, (mt - 2) * 16 * ROW_BYTES);
           if constexpr ((MODE & 2048) != 0) {                // A/B: every piece of the next k-step issued in front of the first MFMA group
-            if constexpr (g == 0 && ABL != 1) {
+            if constexpr (g == 0) {
 #pragma unroll
               for (int p = 0; p < NDMA; ++p) dma(p, px, pw, nxt);
             }
-          } else if constexpr (g < NDMA && ABL != 1) dma(g, px, pw, nxt);
+          } else if constexpr (g < NDMA) dma(g, px, pw, nxt);
           constexpr int kWait[12] = {2, 2, 3, 4, 5, 5, 1, 2, 2, 2, 1, 0};
-          if constexpr (kNoReads) {}
-          else if constexpr (g == 0) lds_wait<kWait[g]>(fw0[0], fw0[1], fw0[2], fw0[3], fx[0]);
+          if constexpr (g == 0) lds_wait<kWait[g]>(fw0[0], fw0[1], fw0[2], fw0[3], fx[0]);
           else if constexpr (g == 6) lds_wait<kWait[g]>(fw1[0], fw1[1], fw1[2], fw1[3], fx[g % 3]);
           else lds_wait<kWait[g]>(fx[g % 3]);
-          if constexpr (kPrioMfma) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) acc[nt][mt] = mma<T>(__builtin_bit_cast(uint4, ks ? fw1[nt] : fw0[nt]), __builtin_bit_cast(uint4, fx[g % 3]), acc[nt][mt]);
-          if constexpr (kPrioMfma) __builtin_amdgcn_s_setprio(0);
           if constexpr (kDrip && g >= NDMA && g - NDMA < STN) {
             constexpr int j = ST0 + g - NDMA;          // store j = (row block j / 2, column pair j % 2) of the previous tile
             if (pending) *reinterpret_cast<uintx4*>(pend_y + static_cast<size_t>((j / 2) * 16) * ldy + (j % 2) * 32) = pend[j];
@@ -370,7 +305,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
           fx[g2 % 3] = *reinterpret_cast<const uint4*>(bx + (g2 % 6) * 16 * ROW_BYTES + (g2 / 6 ? fo1 : fo0));
         }
         if (ks == 0 && mt >= 2) fw[1][mt - 2] = *reinterpret_cast<const uint4*>(bw + (mt - 2) * 16 * ROW_BYTES + fo1);
-        if (g < NDMA && ABL != 1) dma(g, px, pw, nxt);
+        if (g < NDMA) dma(g, px, pw, nxt);
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) acc[nt][mt] = mma<T>(fw[ks][nt], fx[g % 3], acc[nt][mt]);
       }
@@ -440,7 +375,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
         }
       }
     } else {
-      run_k(sx, sx_next, sw_next, std::integral_constant<int, 12 + NPRE>{});
+      run_k(sx, sx_next, sw_next, std::integral_constant<int, 12>{});
     }
     if constexpr (FUSE != 0) {
       uintx4 xp[12];
@@ -485,16 +420,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
         }
         if constexpr (kQuads) quads_out(z, m0, n0);
       }
-      if constexpr (kLn && (FUSE & FUSE_ABL_NOLN) != 0) {      // timing-only: the stores of the LayerNorm outputs without their arithmetic
-#pragma unroll
-        for (int np = 0; np < 2; ++np)
-#pragma unroll
-          for (int mt = 0; mt < 6; ++mt) {
-            const size_t off = static_cast<size_t>(m0 + mt * 16 + (lane & 15)) * 512 + n0 + wn * 64 + np * 32 + nq;
-            *reinterpret_cast<uintx4*>(rp.lny + off) = xp[mt * 2 + np];
-            if constexpr (kLn2) *reinterpret_cast<uintx4*>(rp.lny2 + off) = xp[mt * 2 + np];
-          }
-      } else if constexpr (kLn) {
+      if constexpr (kLn) {
         float* red = reinterpret_cast<float*>(smem + 2 * STAGE);              // [2][96 rows][8 waves] partial sums
         auto unpack = [&](int j, float (&v)[8]) __attribute__((always_inline)) {
           const Pack8<T> p = __builtin_bit_cast(Pack8<T>, xp[j]);
@@ -666,8 +592,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
         // operand panels the other tiles of the launch still stream (in the loop: 103.8 k -> 106.2 k tokens/s with the stand-alone
         // LayerNorms, 104.5 k -> 110.5 k with them folded; MODE bit 9 of the A/B library used to try `nt`, which keeps the line in L2)
         [[maybe_unused]] float z[12];
-        epilogue_store<T, EPI, 4, 6, true, false, true, kPreEpi>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 96,
-                                                                 n0 + wn * 64, lane, nullptr, gelu_tab, &pre, &ef, nullptr, z);
+        epilogue_store<T, EPI, 4, 6, true, false, true>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 96,
+                                                          n0 + wn * 64, lane, nullptr, gelu_tab, &pre, &ef, nullptr, z);
         if constexpr (kQuads && (EPI & EPI_STATS) != 0) quads_out(z, m0, n0);
       }
     }
@@ -678,12 +604,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
     sw = sw_next;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the unused look-ahead pieces must not outlive the workgroup's LDS
-  if constexpr (kStamp) {
-    if (blockIdx.x == 0 && tid == 0) {
-      g_big_stamp[0] = __builtin_amdgcn_s_memtime() - stamp_c;
-      g_big_stamp[1] = __builtin_amdgcn_s_memrealtime() - stamp_r;
-    }
-  }
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; }
@@ -757,10 +677,6 @@ int big_linear_tile(int dtype, const LinearArgs& a, int want) {
 // exists in libd3pm_hip_ab.so only (include/d3pm_hip_ab.h, D3PM_AB_GEMM_BIG_MODE)
 #ifdef D3PM_ABLATIONS
 int big_gemm_mode() { return ab_knobs().big_mode; }
-int read_big_gemm_stamp(unsigned long long* out) {
-  D3PM_CHECK_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_big_stamp), 2 * sizeof(unsigned long long)));
-  return D3PM_OK;
-}
 #endif
 
 template <typename U, int E, int WM, int WN, int MD>
@@ -781,70 +697,27 @@ static int big_launch(const LinearArgs& a, int n_tiles, int tiles_total, dim3 gr
   return D3PM_OK;
 }
 
+// The folded-LayerNorm epilogues (EPI_LNF / EPI_STATS, d3pm_mfma_tile.h) run on the shipped schedule of each geometry only; for the
+// others the A/B library picks among MODE 0 / 1 / 9 / 2049 (2049: plain epilogue, 192 x 256 only; tests/ab_gemm.py)
 template <typename U, int E>
 static int big_launch_geometry(int id, const LinearArgs& a, int n_tiles, int tiles_total, dim3 grid, size_t lds, hipStream_t s) {
-#ifndef D3PM_ABLATIONS
-  if (id == 1) return big_launch<U, E, 1, 8, 1>(a, n_tiles, tiles_total, grid, lds, s);
-  if (id == 2) return big_launch<U, E, 2, 4, 1>(a, n_tiles, tiles_total, grid, lds, s);
-  return big_launch<U, E, 2, 2, 1>(a, n_tiles, tiles_total, grid, lds, s);
-#else
-  const int md = big_gemm_mode();
-  if (E == 0 && id == 3 && md >= 16) {
-    switch (md) {
-      case 17: return big_launch<U, 0, 2, 2, 17>(a, n_tiles, tiles_total, grid, lds, s);
-      case 33: return big_launch<U, 0, 2, 2, 33>(a, n_tiles, tiles_total, grid, lds, s);
-      case 209: return big_launch<U, 0, 2, 2, 209>(a, n_tiles, tiles_total, grid, lds, s);
-      default: break;
+#ifdef D3PM_ABLATIONS
+  if constexpr ((E & (EPI_LNF | EPI_STATS)) == 0) {
+    const int md = big_gemm_mode();
+    if (md == 2049 && E == 0 && id == 2) return big_launch<U, 0, 2, 4, 2049>(a, n_tiles, tiles_total, grid, lds, s);
+    // deferred stores need a next tile to hide in (more tiles than persistent workgroups) and K >= 8 k-steps
+    if (md == 9 && a.K >= 8 * BK && tiles_total > static_cast<int>(grid.x)) {
+      if (id == 1) return big_launch<U, E, 1, 8, 9>(a, n_tiles, tiles_total, grid, lds, s);
+      if (id == 2) return big_launch<U, E, 2, 4, 9>(a, n_tiles, tiles_total, grid, lds, s);
+      return big_launch<U, E, 2, 2, 9>(a, n_tiles, tiles_total, grid, lds, s);
+    }
+    if ((md & 1) == 0) {
+      if (id == 1) return big_launch<U, E, 1, 8, 0>(a, n_tiles, tiles_total, grid, lds, s);
+      if (id == 2) return big_launch<U, E, 2, 4, 0>(a, n_tiles, tiles_total, grid, lds, s);
+      return big_launch<U, E, 2, 2, 0>(a, n_tiles, tiles_total, grid, lds, s);
     }
   }
-  if (E == 0 && id == 2 && (md == 3 || md == 5)) {
-    if (md == 3) return big_launch<U, 0, 2, 4, 3>(a, n_tiles, tiles_total, grid, lds, s);
-    return big_launch<U, 0, 2, 4, 5>(a, n_tiles, tiles_total, grid, lds, s);
-  }
-  if (E == 0 && id == 2 && md >= 16) {      // timing-only ablation builds (tests/ab_gemm.py): plain epilogue, 192 x 256 only
-    switch (md) {
-      case 17: return big_launch<U, 0, 2, 4, 17>(a, n_tiles, tiles_total, grid, lds, s);
-      case 32: return big_launch<U, 0, 2, 4, 32>(a, n_tiles, tiles_total, grid, lds, s);
-      case 81: return big_launch<U, 0, 2, 4, 81>(a, n_tiles, tiles_total, grid, lds, s);
-      case 145: return big_launch<U, 0, 2, 4, 145>(a, n_tiles, tiles_total, grid, lds, s);
-      case 209: return big_launch<U, 0, 2, 4, 209>(a, n_tiles, tiles_total, grid, lds, s);
-      case 257: return big_launch<U, 0, 2, 4, 257>(a, n_tiles, tiles_total, grid, lds, s);
-      case 465: return big_launch<U, 0, 2, 4, 465>(a, n_tiles, tiles_total, grid, lds, s);
-      default: break;
-    }
-  }
-  if (md == 4129 && E == 0 && id == 2) return big_launch<U, 0, 2, 4, 4129>(a, n_tiles, tiles_total, grid, lds, s);   // timing probe
-  if (md == 33 && E == 0 && id == 2) return big_launch<U, 0, 2, 4, 33>(a, n_tiles, tiles_total, grid, lds, s);       // its LDS-DMA twin
-  if (md == 2049 && E == 0) {      // A/B: all DMA pieces of a k-step issued at its top (tests/ab_gemm.py), plain epilogue only
-    if (id == 2) return big_launch<U, 0, 2, 4, 2049>(a, n_tiles, tiles_total, grid, lds, s);
-  }
-  if (md == 8193 || md == 16385 || md == 24577) {      // staggered XCD groups (A/B: tests/ab_gemm.py), 192 x 256 and plain / R1 epilogues only
-    if (id == 2 && md == 8193) return big_launch<U, E, 2, 4, 8193>(a, n_tiles, tiles_total, grid, lds, s);
-    if (id == 2 && md == 16385) return big_launch<U, E, 2, 4, 16385>(a, n_tiles, tiles_total, grid, lds, s);
-    if (id == 2 && md == 24577) return big_launch<U, E, 2, 4, 24577>(a, n_tiles, tiles_total, grid, lds, s);
-  }
-  if (md == 32769) {    // A/B: epilogue operands prefetched at the top of the tile (tests/ab_gemm.py)
-    if (id == 1) return big_launch<U, E, 1, 8, 32769>(a, n_tiles, tiles_total, grid, lds, s);
-    if (id == 2) return big_launch<U, E, 2, 4, 32769>(a, n_tiles, tiles_total, grid, lds, s);
-    return big_launch<U, E, 2, 2, 32769>(a, n_tiles, tiles_total, grid, lds, s);
-  }
-  if (md == 513) {      // hand-placed schedule with non-temporal output stores (A/B: tests/ab_gemm.py)
-    if (id == 1) return big_launch<U, E, 1, 8, 513>(a, n_tiles, tiles_total, grid, lds, s);
-    if (id == 2) return big_launch<U, E, 2, 4, 513>(a, n_tiles, tiles_total, grid, lds, s);
-    return big_launch<U, E, 2, 2, 513>(a, n_tiles, tiles_total, grid, lds, s);
-  }
-  const bool hand = (md & 1) != 0;
-  // deferred stores need a next tile to hide in (more tiles than persistent workgroups) and K >= 8 k-steps
-  const bool drip = md == 9 && a.K >= 8 * BK && tiles_total > static_cast<int>(grid.x);
-  if (id == 1) return drip ? big_launch<U, E, 1, 8, 9>(a, n_tiles, tiles_total, grid, lds, s) : hand ? big_launch<U, E, 1, 8, 1>(a, n_tiles, tiles_total, grid, lds, s) : big_launch<U, E, 1, 8, 0>(a, n_tiles, tiles_total, grid, lds, s);
-  if (id == 2) return drip ? big_launch<U, E, 2, 4, 9>(a, n_tiles, tiles_total, grid, lds, s) : hand ? big_launch<U, E, 2, 4, 1>(a, n_tiles, tiles_total, grid, lds, s) : big_launch<U, E, 2, 4, 0>(a, n_tiles, tiles_total, grid, lds, s);
-  return drip ? big_launch<U, E, 2, 2, 9>(a, n_tiles, tiles_total, grid, lds, s) : hand ? big_launch<U, E, 2, 2, 1>(a, n_tiles, tiles_total, grid, lds, s) : big_launch<U, E, 2, 2, 0>(a, n_tiles, tiles_total, grid, lds, s);
 #endif
-}
-
-// the folded-LayerNorm epilogues (EPI_LNF / EPI_STATS, d3pm_mfma_tile.h) run on the shipped schedule of each geometry only
-template <typename U, int E>
-static int big_launch_fold(int id, const LinearArgs& a, int n_tiles, int tiles_total, dim3 grid, size_t lds, hipStream_t s) {
   if (id == 1) return big_launch<U, E, 1, 8, 1>(a, n_tiles, tiles_total, grid, lds, s);
   if (id == 2) return big_launch<U, E, 2, 4, 1>(a, n_tiles, tiles_total, grid, lds, s);
   return big_launch<U, E, 2, 2, 1>(a, n_tiles, tiles_total, grid, lds, s);
@@ -904,17 +777,17 @@ int big_linear(int dtype, const LinearArgs& a, int id, hipStream_t s) {
   auto go = [&](auto* tag) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
     switch (epi) {
-      case EPI_LNF: return big_launch_fold<U, EPI_LNF>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_LNF | EPI_GELU: return big_launch_fold<U, EPI_LNF | EPI_GELU>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R1 | EPI_STATS: return big_launch_fold<U, EPI_R1 | EPI_STATS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R2 | EPI_STATS: return big_launch_fold<U, EPI_R2 | EPI_STATS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R1 | EPI_MASK | EPI_STATS: return big_launch_fold<U, EPI_R1 | EPI_MASK | EPI_STATS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_LNF | EPI_QUADS: return big_launch_fold<U, EPI_LNF | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_LNF | EPI_GELU | EPI_QUADS: return big_launch_fold<U, EPI_LNF | EPI_GELU | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R1 | EPI_STATS | EPI_QUADS: return big_launch_fold<U, EPI_R1 | EPI_STATS | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R2 | EPI_STATS | EPI_QUADS: return big_launch_fold<U, EPI_R2 | EPI_STATS | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_LNF: return big_launch_geometry<U, EPI_LNF>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_LNF | EPI_GELU: return big_launch_geometry<U, EPI_LNF | EPI_GELU>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_R1 | EPI_STATS: return big_launch_geometry<U, EPI_R1 | EPI_STATS>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_R2 | EPI_STATS: return big_launch_geometry<U, EPI_R2 | EPI_STATS>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_R1 | EPI_MASK | EPI_STATS: return big_launch_geometry<U, EPI_R1 | EPI_MASK | EPI_STATS>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_LNF | EPI_QUADS: return big_launch_geometry<U, EPI_LNF | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_LNF | EPI_GELU | EPI_QUADS: return big_launch_geometry<U, EPI_LNF | EPI_GELU | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_R1 | EPI_STATS | EPI_QUADS: return big_launch_geometry<U, EPI_R1 | EPI_STATS | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
+      case EPI_R2 | EPI_STATS | EPI_QUADS: return big_launch_geometry<U, EPI_R2 | EPI_STATS | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
       case EPI_R1 | EPI_MASK | EPI_STATS | EPI_QUADS:
-        return big_launch_fold<U, EPI_R1 | EPI_MASK | EPI_STATS | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
+        return big_launch_geometry<U, EPI_R1 | EPI_MASK | EPI_STATS | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
       case 0: return big_launch_geometry<U, 0>(id, a, n_tiles, tiles_total, grid, lds, s);
       case EPI_GELU: return big_launch_geometry<U, EPI_GELU>(id, a, n_tiles, tiles_total, grid, lds, s);
       case EPI_R1: return big_launch_geometry<U, EPI_R1>(id, a, n_tiles, tiles_total, grid, lds, s);
@@ -976,9 +849,6 @@ int row_panel_linear(int dtype, const LinearArgs& a, const RowPanelFuse& f, hipS
     switch (kind) {
       case 1:
         if (f.sx) return row_panel_launch<U, EPI_R1, FUSE_LN | FUSE_LN2 | FUSE_MX>(a, f, s);
-#ifdef D3PM_ABLATIONS
-        if (big_gemm_mode() == 1025) return row_panel_launch<U, EPI_R1, FUSE_LN | FUSE_LN2 | FUSE_ABL_NOLN>(a, f, s);
-#endif
         return row_panel_launch<U, EPI_R1, FUSE_LN | FUSE_LN2>(a, f, s);
       case 2: return f.sx ? row_panel_launch<U, EPI_R2, FUSE_DUAL | FUSE_LN | FUSE_FILM | FUSE_MX>(a, f, s)
                           : row_panel_launch<U, EPI_R2, FUSE_DUAL | FUSE_LN | FUSE_FILM>(a, f, s);

@@ -30,7 +30,7 @@ constexpr int XH = RTM * HROW, SLOT = (RTM + RTN) * HROW;  // 12288, 28672
 constexpr int NSLOT = 5;
 constexpr int XPC = RTM / 16, WPC = RTN / 16, HPC = XPC + WPC;   // 1-KiB pieces per slab: 12 + 16 = 28
 
-template <typename T, int EPI, bool kProbe = false>   // kProbe: timing only, the operand stream without fragment reads / MFMAs
+template <typename T, int EPI>
 __global__ __launch_bounds__(RNW * 64, 2) void gemm_mfma_ring(const T* __restrict__ X, int ldx, const T* __restrict__ W,
                                                               const T* __restrict__ bias, T* Y, int ldy, const T* R1, const T* R2,
                                                               int ldr, const uint8_t* __restrict__ row_mask, int mask_period, int M,
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(RNW * 64, 2) void gemm_mfma_ring(const T* __restric
       __builtin_amdgcn_s_barrier();                        // every wave's pieces have landed; the previous k-step's slots are free
       issue_pair();
 #pragma unroll
-      for (int ks = 0; ks < (kProbe ? 0 : 2); ++ks) {
+      for (int ks = 0; ks < 2; ++ks) {
         int slot = cslot + ks;
         slot = slot >= NSLOT ? slot - NSLOT : slot;
         const char* bx = smem + slot * SLOT + (wm * 96) * HROW + fo;
@@ -156,8 +156,6 @@ bool ring_linear_supported(int dtype, const LinearArgs& a) {
   return true;
 }
 
-int big_gemm_mode();
-
 int ring_linear(int dtype, const LinearArgs& a, hipStream_t s) {
   const int n_tiles = a.N / RTN, tiles_total = (a.M / RTM) * n_tiles, want = (tiles_total + 7) & ~7;
   const dim3 grid(static_cast<unsigned>(want < 256 ? want : 256)), block(RNW * 64);
@@ -173,17 +171,6 @@ int ring_linear(int dtype, const LinearArgs& a, hipStream_t s) {
   } while (0)
   auto go = [&](auto* tag) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
-    if (epi == 0 && big_gemm_mode() == 33) {               // timing probe (tests/ab_gemm.py 9m33)
-      static bool attr_probe = false;
-      if (!attr_probe) {
-        D3PM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mfma_ring<U, 0, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, NSLOT * SLOT));
-        attr_probe = true;
-      }
-      gemm_mfma_ring<U, 0, true><<<grid, block, lds, s>>>(static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W),
-          static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy, nullptr, nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, n_tiles, tiles_total);
-      return D3PM_OK;
-    }
     switch (epi) {
       case 0: D3PM_RING(0);
       case EPI_R1: D3PM_RING(EPI_R1);

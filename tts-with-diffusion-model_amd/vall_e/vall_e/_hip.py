@@ -209,8 +209,6 @@ AB_SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "d3pm_op_final_sample": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]),
-    "d3pm_debug_gemm_clock": (C.c_int, [C.POINTER(C.c_uint64)]),
-    "d3pm_debug_attn32_stamps": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
 }
 AB_GEMM_BIG_MODE, AB_ATTN_ARM, AB_GEMM_RING, AB_GELU_TABLE, AB_LN_PROLOGUE, AB_FUSED_FINAL_SAMPLE = range(6)
 _is_ab = False
@@ -1018,25 +1016,6 @@ def set_attn_arm(v: int):
 
 def set_gemm_ring(v: bool):
     _ab_set(AB_GEMM_RING, 1 if v else 0)
-
-
-def gemm_clock_ghz() -> float:
-    """Shader clock (GHz) held during the last big-tile GEMM launched with big mode bit 8 set; synchronises."""
-    if not _is_ab:
-        raise D3PMError("d3pm_debug_gemm_clock lives in libd3pm_hip_ab.so (use_ab_library())")
-    torch.cuda.synchronize()
-    buf = (C.c_uint64 * 2)()
-    check(lib().d3pm_debug_gemm_clock(buf), "d3pm_debug_gemm_clock")
-    return buf[0] / max(buf[1], 1) * 0.1
-
-
-def attn32_stamps():
-    """[2][12][8] shader-clock stamps of the last attn32 launch under set_attn_arm(320) (include/d3pm_hip_ab.h); synchronises."""
-    if not _is_ab:
-        raise D3PMError("d3pm_debug_attn32_stamps lives in libd3pm_hip_ab.so (use_ab_library())")
-    buf = (C.c_uint64 * 192)()
-    check(lib().d3pm_debug_attn32_stamps(buf, 192), "d3pm_debug_attn32_stamps")
-    return [[[int(buf[(s * 12 + t) * 8 + p]) for p in range(8)] for t in range(12)] for s in range(2)]
 
 
 # ---- timing hooks: a d3pm_prof handle attached to the default Tuning ------------------------------------------------------
