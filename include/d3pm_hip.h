@@ -51,7 +51,8 @@ extern "C" {
  *    d3pm_op_linear_fold / d3pm_op_linear_stats / d3pm_op_row_stats); d3pm_tuning gained regime_batch and ln_fold (layout change);
  *    d3pm_workspace_bytes grew by the row-moment buffer and the fp8 path's scale slot;
  *    later additions only: the condition encoders' training-step dropout (d3pm_op_dropout_f32, d3pm_op_attention_dropout_f32,
- *    d3pm_op_attention_bwd_dropout_f32) */
+ *    d3pm_op_attention_bwd_dropout_f32); per-utterance canvases (d3pm_canvas, d3pm_denoise_step_canvas,
+ *    d3pm_posterior_sample_known, d3pm_sample_loop_canvas, d3pm_sample_loop_fp8_canvas) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -346,6 +347,54 @@ int d3pm_sample_loop_fp8(const d3pm_shape *shape, const d3pm_weights *weights,
                          const uint8_t *frame_mask, int t_start, int t_stop, const void *film, const void *kv_text,
                          const void *kv_prompt, const d3pm_schedule *sched, uint64_t seed, uint32_t utt0,
                          uint32_t flags, void *workspace, size_t workspace_bytes, int32_t *trace, void *stream);
+
+/* Per-utterance canvases ---------------------------------------------------------------------------
+ * The entries above share ONE frame mask [canvas] between the utterances of a batch: every utterance has the same number of live
+ * frames.  The *_canvas entries take one mask per utterance and, for the sampler, a map of the frames the caller already knows:
+ *   frame_mask  device uint8 [batch][canvas]: utterance b's live frames (upstream builds it once from x_T != 0, :705-709, and keeps
+ *               it for the whole loop).  Utterance b with L_b live frames is exactly the one-utterance run with that mask: padded
+ *               rows are still keys of the self-attention and are still sampled from final.bias, no work is skipped for them.
+ *   known       device uint8 [batch][canvas] or NULL: known[b][i] != 0 marks a frame whose id the caller gives.  `x` carries x_T
+ *               with the given ids already in place (the mask id on every other live frame); after every reverse step
+ *               x_{t-1}[b][i] = x_T[b][i] on the marked frames (replacement conditioning -- for an absorbing process the same as
+ *               never resampling the row), so the denoiser sees them as revealed context from the first iteration on.  A marked
+ *               row draws nothing; the Philox stream of every other row is keyed by its own (global row, t) and does not move.
+ *               With n_q > 1 the map is per frame: all levels of a marked frame are kept.  Ids are taken verbatim from 0 .. 1023;
+ *               512 is upstream's mask id (1025 // 2) and doubles as a codec id there, so a known 512 is legal and stays 512.
+ *               Nothing is checked on the device: marking only live frames is the caller's contract (the Python layer raises).
+ * With every row of frame_mask equal and known NULL or all zero, each entry is bit-identical to the one it generalises; utterance b
+ * of a batch never depends on the lengths or maps of the others, nor on how the batch is split (utt0, regime_batch). */
+typedef struct d3pm_canvas {
+  const uint8_t *frame_mask;   /* device [batch][canvas]         */
+  const uint8_t *known;        /* device [batch][canvas] or NULL */
+} d3pm_canvas;
+
+/* d3pm_denoise_step with a per-utterance frame mask (canvas->known is not read: the denoiser only reads ids). */
+int d3pm_denoise_step_canvas(const d3pm_shape *shape, const d3pm_weights *w, int batch, const int32_t *x_t,
+                             const d3pm_canvas *canvas, int t, const void *film, const void *kv_text,
+                             const void *kv_prompt, void *workspace, size_t workspace_bytes, void *logits_out,
+                             void *hidden_out, int only_layers, uint32_t flags, void *stream);
+
+/* d3pm_posterior_sample with a known-frame map (device uint8 [batch][canvas] or NULL): x_next = x_t on the marked frames, the
+ * posterior draw everywhere else (posterior_out rows of marked frames are left unwritten).  One step of what
+ * d3pm_sample_loop_canvas does between two denoiser evaluations. */
+int d3pm_posterior_sample_known(const d3pm_shape *shape, int batch, const void *logits, int logits_dtype,
+                                const int32_t *x_t, int32_t *x_next, const uint8_t *known, int t,
+                                const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags,
+                                uint16_t *posterior_out, void *stream);
+
+/* d3pm_sample_loop / d3pm_sample_loop_fp8 over per-utterance canvases; every other argument as there. */
+int d3pm_sample_loop_canvas(const d3pm_shape *shape, const d3pm_weights *w, int batch, int32_t *x,
+                            const d3pm_canvas *canvas, int t_start, int t_stop, const void *film,
+                            const void *kv_text, const void *kv_prompt, const d3pm_schedule *sched,
+                            uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
+                            size_t workspace_bytes, int32_t *trace, void *stream);
+int d3pm_sample_loop_fp8_canvas(const d3pm_shape *shape, const d3pm_weights *weights,
+                                const d3pm_fp8_block_weights *fp8_blocks, int batch, int32_t *x,
+                                const d3pm_canvas *canvas, int t_start, int t_stop, const void *film,
+                                const void *kv_text, const void *kv_prompt, const d3pm_schedule *sched,
+                                uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
+                                size_t workspace_bytes, int32_t *trace, void *stream);
 
 /* Replaces AR.q_sample / q_probs (ar_discrete.py:467-502): forward noising of x0 at step t with
  * Philox stream 1.  x0, x_out device int32 [batch][canvas]. */

@@ -268,9 +268,10 @@ static AttnArgs cross_attention_pair(const void* q_text, const void* q_prompt, i
   a.Q2 = q_prompt; a.K2 = kv_prompt; a.V2 = at(kv_prompt, d, es); a.O2 = o_prompt; a.S2 = s_prompt;
   return a;
 }
-static EmbedArgs embed_args(const d3pm_shape& sh, const d3pm_weights& w, int batch, const int32_t* x_t, const uint8_t* frame_mask, void* Y) {
+static EmbedArgs embed_args(const d3pm_shape& sh, const d3pm_weights& w, int batch, const int32_t* x_t, const uint8_t* frame_mask, int mask_period,
+                            void* Y) {
   EmbedArgs e;
-  e.tokens = x_t; e.frame_mask = frame_mask; e.canvas = sh.canvas; e.table = w.resps_emb; e.Y = Y;
+  e.tokens = x_t; e.frame_mask = frame_mask; e.mask_period = mask_period; e.table = w.resps_emb; e.Y = Y;
   e.M = batch * sh.canvas; e.d = sh.d_model; e.n_classes = sh.n_classes; e.n_q = levels(sh);
   return e;
 }
@@ -293,8 +294,20 @@ static int run_cross_out_dual(const Ctx& cx, int dt, int form, const LinearArgs&
   return form == CROSS_OUT_PANEL64_DUAL ? panel64_dual(dt, g, X2, s) : big_dual(dt, g, X2, s);
 }
 
+// The frame mask of a call and the period it repeats with over the packed [batch * canvas] rows: one mask [canvas] shared by every
+// utterance (period canvas: d3pm_denoise_step, d3pm_sample_loop) or one per utterance [batch][canvas] (period batch * canvas: the
+// *_canvas entries).  `known` is the known-frame map of d3pm_canvas ([batch][canvas] or null), read by the sampler only.
+struct CanvasMask {
+  const uint8_t* frame_mask; int period; const uint8_t* known;
+};
+static CanvasMask shared_mask(const d3pm_shape* sh, const uint8_t* frame_mask) { return CanvasMask{frame_mask, sh ? sh->canvas : 0, nullptr}; }
+static CanvasMask per_utterance_mask(const d3pm_shape* sh, int batch, const d3pm_canvas* cv, bool with_known) {
+  if (!cv || !sh) return CanvasMask{nullptr, 0, nullptr};
+  return CanvasMask{cv->frame_mask, batch * sh->canvas, with_known ? cv->known : nullptr};
+}
+
 struct DenoiserArgs {      // what every block of one evaluation sees
-  const d3pm_shape& sh; const d3pm_weights& w; int batch; const uint8_t* frame_mask; const void* kv_text; const void* kv_prompt;
+  const d3pm_shape& sh; const d3pm_weights& w; int batch; const uint8_t* frame_mask; int mask_period; const void* kv_text; const void* kv_prompt;
   const Workspace& ws;
 };
 
@@ -342,7 +355,7 @@ static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v) {
   // ---- FiLM-modulated MLP: the (layer, t) copy of fc1 carries norm3 and the modulation ----
   const size_t ln = static_cast<size_t>(l) * 4 * d;
   D3PM_TRY(consumer(at(ws.fc1f, ln * d, es), ws.fc1f_s + ln, ws.fc1f_b + ln, ws.mlp, 4 * d, ACT_GELU));
-  return v.linear(with_row_mask(producer(ws.mlp, 4 * d, b.fc2_w, b.fc2_b), q.frame_mask, T));
+  return v.linear(with_row_mask(producer(ws.mlp, 4 * d, b.fc2_w, b.fc2_b), q.frame_mask, q.mask_period));
 }
 
 // asks: would every launch that touches the moments run on the MFMA family (D3PM_E_SHAPE if not), and all of them on big tiles?
@@ -395,7 +408,7 @@ static int denoiser_blocks_folded(const DenoiserArgs& q, const int32_t* x_t, int
   if (!prepared) {      // (inside the loop the previous iteration's sampler launch has done both: posterior_sample_prep)
     {
       ProfScope p(cx, D3PM_K_LN, s, 0.0, es * static_cast<double>(n) * d * 2.0);
-      D3PM_TRY(embed_tokens_stats(dt, embed_args(sh, q.w, q.batch, x_t, q.frame_mask, q.ws.x), q.ws.stats, quads, s));
+      D3PM_TRY(embed_tokens_stats(dt, embed_args(sh, q.w, q.batch, x_t, q.frame_mask, q.mask_period, q.ws.x), q.ws.stats, quads, s));
     }
     {   // fc1 of every block under norm3 + FiLM(t): the weights this evaluation's fc1 launches read
       ProfScope p(cx, D3PM_K_LN, s, 0.0, es * 2.0 * layers * 4.0 * d * d);
@@ -421,7 +434,7 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
   const Workspace& ws = q.ws;
   const uint8_t* frame_mask = q.frame_mask;
   const int dt = sh.dtype, d = sh.d_model, H = sh.n_heads, hd = d / H, T = sh.canvas, batch = q.batch;
-  const int n = batch * T;
+  const int n = batch * T, mask_period = q.mask_period;
   const Ctx cx(sh.tuning);
   const size_t es = dtype_size(dt);
   // fp8 fast path: the three LayerNorm-fed K = d projections take e4m3 operands; the e4m3 rows
@@ -463,14 +476,14 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
   if (!use8 && !(flags & D3PM_FLAG_FORCE_GENERIC) && layers > 0 && levels(sh) == 1) {
     LayerNormArgs ln0 = layernorm(w.blocks[0].norm1_w, w.blocks[0].norm1_b);
     ln0.X = w.resps_emb;
-    ln0.tokens = x_t; ln0.frame_mask = frame_mask; ln0.canvas = T; ln0.n_classes = sh.n_classes; ln0.Xout = ws.x;
+    ln0.tokens = x_t; ln0.frame_mask = frame_mask; ln0.mask_period = mask_period; ln0.n_classes = sh.n_classes; ln0.Xout = ws.x;
     if (fast_layernorm_supported(dt, ln0)) {
       ProfScope p(cx, D3PM_K_LN, s, 0.0, dtype_size(dt) * static_cast<double>(n) * d * 3.0);
       D3PM_TRY(fast_layernorm(dt, ln0, s));
       embed_fused = true;
     }
   }
-  if (!embed_fused) D3PM_TRY(embed_tokens(dt, embed_args(sh, w, batch, x_t, frame_mask, ws.x), s));
+  if (!embed_fused) D3PM_TRY(embed_tokens(dt, embed_args(sh, w, batch, x_t, frame_mask, mask_period, ws.x), s));
 
   // row-panel launches (D3PM_TUNE_ROW_PANEL): a projection that lands on the residual stream also writes the LayerNorm(s) the
   // block applies to the new rows next -- same bits, one launch and one pass over x less each
@@ -589,11 +602,11 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
       lp.w = ln.w; lp.b = ln.b; lp.film = ln.film; lp.eps = ln.eps;
       D3PM_TRY(ln_linear(norm3_fused, ln, lp, projection(ws.h, b.fc1_w, b.fc1_b, ws.mlp, n, 4 * d, d, ACT_GELU)));
     }
-    g = with_row_mask(with_residual(projection(ws.mlp, b.fc2_w, b.fc2_b, ws.x, n, d, 4 * d), ws.x), frame_mask, T);
+    g = with_row_mask(with_residual(projection(ws.mlp, b.fc2_w, b.fc2_b, ws.x, n, d, 4 * d), ws.x), frame_mask, mask_period);
     rp = RowPanelFuse();
     if (l + 1 < layers) { rp.lnw = w.blocks[l + 1].norm1_w; rp.lnb = w.blocks[l + 1].norm1_b; rp.lny = ws.h; rp.eps = 1e-6f; }
     if (fc2_mx) {
-      D3PM_TRY(mx_gemm(h8, 4 * d, sh8, f8[l].fc2_w8, f8[l].fc2_scale, b.fc2_b, ws.x, d, ws.x, frame_mask, T, nullptr, nullptr, n, d, 4 * d,
+      D3PM_TRY(mx_gemm(h8, 4 * d, sh8, f8[l].fc2_w8, f8[l].fc2_scale, b.fc2_b, ws.x, d, ws.x, frame_mask, mask_period, nullptr, nullptr, n, d, 4 * d,
                        ACT_NONE));
     } else if ((panel & 4) && l + 1 < layers && row_panel_supported(dt, g, rp)) {
       D3PM_TRY(run_row_panel(cx, dt, g, rp, s));
@@ -855,18 +868,18 @@ int d3pm_encode_conditions(const d3pm_shape* sh, const d3pm_cond_weights* cw, in
 }
 
 static int denoise_step_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, const int32_t* x_t,
-                             const uint8_t* frame_mask, int t, const void* film, const void* kv_text, const void* kv_prompt,
+                             const CanvasMask& cm, int t, const void* film, const void* kv_text, const void* kv_prompt,
                              void* workspace, size_t workspace_bytes, void* logits_out, void* hidden_out, int only_layers,
                              uint32_t flags, void* stream, const d3pm_fp8_block_weights* f8) {
   D3PM_TRY(check_shape(sh, batch));
-  D3PM_REQUIRE(w && w->blocks && x_t && frame_mask && film && kv_text && kv_prompt && workspace, D3PM_E_ARG,
+  D3PM_REQUIRE(w && w->blocks && x_t && cm.frame_mask && film && kv_text && kv_prompt && workspace, D3PM_E_ARG,
                "d3pm_denoise_step: null pointer");
   D3PM_REQUIRE(t >= 0 && t <= sh->timesteps, D3PM_E_ARG, "t=%d outside [0,%d]", t, sh->timesteps);
   Workspace ws = carve(*sh, batch, static_cast<char*>(workspace));
   D3PM_REQUIRE(workspace_bytes >= ws.total, D3PM_E_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, ws.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int layers = (only_layers >= 0 && only_layers < sh->n_layers) ? only_layers : sh->n_layers;
-  const DenoiserArgs q{*sh, *w, batch, frame_mask, kv_text, kv_prompt, ws};
+  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws};
   D3PM_TRY(denoiser_blocks(q, x_t, t, film, layers, flags, s, f8, fold_plan(q, flags, f8)));
   if (hidden_out)
     D3PM_CHECK_HIP(hipMemcpyAsync(hidden_out, ws.x, static_cast<size_t>(batch) * sh->canvas * sh->d_model * dtype_size(sh->dtype),
@@ -884,8 +897,16 @@ int d3pm_denoise_step(const d3pm_shape* sh, const d3pm_weights* w, int batch, co
                       const uint8_t* frame_mask, int t, const void* film, const void* kv_text, const void* kv_prompt,
                       void* workspace, size_t workspace_bytes, void* logits_out, void* hidden_out, int only_layers,
                       uint32_t flags, void* stream) {
-  return denoise_step_impl(sh, w, batch, x_t, frame_mask, t, film, kv_text, kv_prompt, workspace, workspace_bytes, logits_out,
+  return denoise_step_impl(sh, w, batch, x_t, shared_mask(sh, frame_mask), t, film, kv_text, kv_prompt, workspace, workspace_bytes, logits_out,
                            hidden_out, only_layers, flags, stream, nullptr);
+}
+
+int d3pm_denoise_step_canvas(const d3pm_shape* sh, const d3pm_weights* w, int batch, const int32_t* x_t, const d3pm_canvas* canvas, int t,
+                             const void* film, const void* kv_text, const void* kv_prompt, void* workspace, size_t workspace_bytes,
+                             void* logits_out, void* hidden_out, int only_layers, uint32_t flags, void* stream) {
+  D3PM_REQUIRE(canvas, D3PM_E_ARG, "d3pm_denoise_step_canvas: null canvas");
+  return denoise_step_impl(sh, w, batch, x_t, per_utterance_mask(sh, batch, canvas, false), t, film, kv_text, kv_prompt, workspace, workspace_bytes,
+                           logits_out, hidden_out, only_layers, flags, stream, nullptr);
 }
 
 int d3pm_denoise_step_fp8(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch,
@@ -893,13 +914,13 @@ int d3pm_denoise_step_fp8(const d3pm_shape* sh, const d3pm_weights* w, const d3p
                           const void* kv_prompt, void* workspace, size_t workspace_bytes, void* logits_out, void* hidden_out,
                           int only_layers, uint32_t flags, void* stream) {
   D3PM_REQUIRE(fp8_blocks, D3PM_E_ARG, "d3pm_denoise_step_fp8: null fp8 weights");
-  return denoise_step_impl(sh, w, batch, x_t, frame_mask, t, film, kv_text, kv_prompt, workspace, workspace_bytes, logits_out,
+  return denoise_step_impl(sh, w, batch, x_t, shared_mask(sh, frame_mask), t, film, kv_text, kv_prompt, workspace, workspace_bytes, logits_out,
                            hidden_out, only_layers, flags, stream, fp8_blocks);
 }
 
-int d3pm_posterior_sample(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
-                          int32_t* x_next, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
-                          uint32_t flags, uint16_t* posterior_out, void* stream) {
+static int posterior_sample_impl(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
+                                 int32_t* x_next, const uint8_t* known, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                                 uint32_t flags, uint16_t* posterior_out, void* stream) {
   D3PM_TRY(check_shape(sh, batch));
   D3PM_REQUIRE(logits && x_t && x_next && sched && sched->d && sched->c && sched->dbar && sched->cbar, D3PM_E_ARG,
                "d3pm_posterior_sample: null pointer");
@@ -910,15 +931,28 @@ int d3pm_posterior_sample(const d3pm_shape* sh, int batch, const void* logits, i
   a.n_q = levels(*sh);
   a.canvas = sh->canvas; a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas);
   a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0; a.pc = make_posterior_consts(sched, t);
+  a.known = known;
   return posterior_sample(a, static_cast<hipStream_t>(stream));
 }
 
-static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask,
+int d3pm_posterior_sample(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
+                          int32_t* x_next, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                          uint32_t flags, uint16_t* posterior_out, void* stream) {
+  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, nullptr, t, sched, seed, utt0, flags, posterior_out, stream);
+}
+
+int d3pm_posterior_sample_known(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
+                                int32_t* x_next, const uint8_t* known, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                                uint32_t flags, uint16_t* posterior_out, void* stream) {
+  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, known, t, sched, seed, utt0, flags, posterior_out, stream);
+}
+
+static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const CanvasMask& cm,
                             int t_start, int t_stop, const void* film, const void* kv_text, const void* kv_prompt,
                             const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace,
                             size_t workspace_bytes, int32_t* trace, void* stream, const d3pm_fp8_block_weights* f8) {
   D3PM_TRY(check_shape(sh, batch));
-  D3PM_REQUIRE(w && w->blocks && x && frame_mask && film && kv_text && kv_prompt && sched && workspace, D3PM_E_ARG,
+  D3PM_REQUIRE(w && w->blocks && x && cm.frame_mask && film && kv_text && kv_prompt && sched && workspace, D3PM_E_ARG,
                "d3pm_sample_loop: null pointer");
   D3PM_REQUIRE(t_start < sched->timesteps && t_start <= sh->timesteps && t_stop >= 0 && t_stop <= t_start, D3PM_E_ARG,
                "bad step range %d..%d", t_start, t_stop);
@@ -927,7 +961,7 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rows = batch * sh->canvas;
   const Ctx cx(sh->tuning);
-  const DenoiserArgs q{*sh, *w, batch, frame_mask, kv_text, kv_prompt, ws};
+  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws};
   const int plan = fold_plan(q, flags, f8);      // the same for every iteration: the blocks and the sampler's prep share it
   bool prepared = false;      // the previous iteration's sampler launch has already embedded x_t and folded fc1 for this t
   for (int t = t_start; t > t_stop; --t) {
@@ -941,8 +975,9 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     if (flags & D3PM_FLAG_SEED_IN_HBM) a.seed_hbm = reinterpret_cast<const uint64_t*>(static_cast<uintptr_t>(seed));
     a.row0 = utt0 * static_cast<uint32_t>(sh->canvas); a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0;
     a.pc = make_posterior_consts(sched, t);
+    a.known = cm.known;
 #ifdef D3PM_ABLATIONS
-    if (fused_final_sample_applies(*sh, *w, ws, flags)) {
+    if (!cm.known && fused_final_sample_applies(*sh, *w, ws, flags)) {
       // final projection + posterior + draw in one kernel: the logits stay on chip (d3pm_final_sample.hip)
       ProfScope p(cx, D3PM_K_SAMPLE, s, 2.0 * rows * sh->n_classes * sh->d_model,
                   dtype_size(sh->dtype) * (static_cast<double>(rows) * sh->d_model + static_cast<double>(sh->n_classes) * sh->d_model) + 8.0 * rows);
@@ -956,7 +991,7 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
       NextIterPrep nx;
       if (t - 1 > t_stop && plan != FOLD_NONE) {
         const size_t es = dtype_size(sh->dtype);
-        nx.dtype = sh->dtype; nx.table = w->resps_emb; nx.x = ws.x; nx.stats = ws.stats; nx.frame_mask = frame_mask; nx.d = sh->d_model;
+        nx.dtype = sh->dtype; nx.table = w->resps_emb; nx.x = ws.x; nx.stats = ws.stats; nx.frame_mask = cm.frame_mask; nx.mask_period = cm.period; nx.d = sh->d_model;
         nx.quads = plan == FOLD_QUADS;
         nx.blocks = w->blocks; nx.n_layers = sh->n_layers;
         nx.film_t = at(film, static_cast<size_t>(t - 1) * sh->n_layers * 2 * sh->d_model, es);
@@ -978,8 +1013,17 @@ int d3pm_sample_loop(const d3pm_shape* sh, const d3pm_weights* w, int batch, int
                      int t_start, int t_stop, const void* film, const void* kv_text, const void* kv_prompt,
                      const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace,
                      size_t workspace_bytes, int32_t* trace, void* stream) {
-  return sample_loop_impl(sh, w, batch, x, frame_mask, t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags,
+  return sample_loop_impl(sh, w, batch, x, shared_mask(sh, frame_mask), t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags,
                           workspace, workspace_bytes, trace, stream, nullptr);
+}
+
+int d3pm_sample_loop_canvas(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const d3pm_canvas* canvas,
+                            int t_start, int t_stop, const void* film, const void* kv_text, const void* kv_prompt,
+                            const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace,
+                            size_t workspace_bytes, int32_t* trace, void* stream) {
+  D3PM_REQUIRE(canvas, D3PM_E_ARG, "d3pm_sample_loop_canvas: null canvas");
+  return sample_loop_impl(sh, w, batch, x, per_utterance_mask(sh, batch, canvas, true), t_start, t_stop, film, kv_text, kv_prompt, sched, seed,
+                          utt0, flags, workspace, workspace_bytes, trace, stream, nullptr);
 }
 
 int d3pm_sample_loop_fp8(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch,
@@ -987,8 +1031,17 @@ int d3pm_sample_loop_fp8(const d3pm_shape* sh, const d3pm_weights* w, const d3pm
                          const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
                          uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, void* stream) {
   D3PM_REQUIRE(fp8_blocks, D3PM_E_ARG, "d3pm_sample_loop_fp8: null fp8 weights");
-  return sample_loop_impl(sh, w, batch, x, frame_mask, t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags,
+  return sample_loop_impl(sh, w, batch, x, shared_mask(sh, frame_mask), t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags,
                           workspace, workspace_bytes, trace, stream, fp8_blocks);
+}
+
+int d3pm_sample_loop_fp8_canvas(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch,
+                                int32_t* x, const d3pm_canvas* canvas, int t_start, int t_stop, const void* film,
+                                const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                                uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, void* stream) {
+  D3PM_REQUIRE(fp8_blocks && canvas, D3PM_E_ARG, "d3pm_sample_loop_fp8_canvas: null fp8 weights or canvas");
+  return sample_loop_impl(sh, w, batch, x, per_utterance_mask(sh, batch, canvas, true), t_start, t_stop, film, kv_text, kv_prompt, sched, seed,
+                          utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks);
 }
 
 int d3pm_q_sample(const d3pm_shape* sh, int batch, const int32_t* x0, int32_t* x_out, const uint8_t* frame_mask, int t,

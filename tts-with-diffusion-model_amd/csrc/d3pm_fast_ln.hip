@@ -17,7 +17,7 @@ __global__ __launch_bounds__(256) void layernorm_vec(const T* __restrict__ x, T*
                                                      const T* __restrict__ w2, const T* __restrict__ b2,
                                                      T* __restrict__ y2, const T* __restrict__ film, int M, float eps,
                                                      const int32_t* __restrict__ tok, const uint8_t* __restrict__ frame_mask,
-                                                     int canvas, int n_classes, T* __restrict__ xout) {
+                                                     int mask_period, int n_classes, T* __restrict__ xout) {
   constexpr int d = CH * 512;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // XCD-aware order: workgroups are dealt round-robin over the 8 XCDs, so give each XCD a contiguous range of rows -- the ranges
@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void layernorm_vec(const T* __restrict__ x, T*
   if (tok) {                                  // x is the embedding table: this row = table[token] * frame mask (embed_rows_vec)
     int id = tok[row];
     id = id < 0 ? 0 : (id >= n_classes ? n_classes - 1 : id);
-    live = frame_mask[row % canvas] != 0;
+    live = frame_mask[row % mask_period] != 0;
     xr = x + static_cast<size_t>(id) * d;
   }
   // d = 512: the per-column parameters are fetched beside the row, not behind the two reductions (at one utterance a launch is a
@@ -106,7 +106,7 @@ template <typename T> int launch(const LayerNormArgs& a, hipStream_t s) {
                                               static_cast<const T*>(a.w), static_cast<const T*>(a.b),        \
                                               static_cast<const T*>(a.w2), static_cast<const T*>(a.b2),      \
                                               static_cast<T*>(a.Y2), static_cast<const T*>(a.film), a.M, a.eps,  \
-                                              a.tokens, a.frame_mask, a.canvas, a.n_classes, static_cast<T*>(a.Xout))
+                                              a.tokens, a.frame_mask, a.mask_period, a.n_classes, static_cast<T*>(a.Xout))
   switch (a.d / 512) {
     case 1: D3PM_LN(1); break;
     case 2: D3PM_LN(2); break;
@@ -124,7 +124,7 @@ bool fast_layernorm_supported(int dtype, const LayerNormArgs& a) {
   if (dtype != D3PM_F16 && dtype != D3PM_BF16) return false;
   if (a.d != 512 && a.d != 1024 && a.d != 2048) return false;
   auto al = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % 16) == 0; };
-  if (a.tokens && !(a.frame_mask && a.canvas > 0 && a.n_classes > 0 && a.Xout && al(a.Xout))) return false;
+  if (a.tokens && !(a.frame_mask && a.mask_period > 0 && a.n_classes > 0 && a.Xout && al(a.Xout))) return false;
   return al(a.X) && al(a.Y) && al(a.w) && al(a.b) && al(a.w2) && al(a.b2) && al(a.Y2) && al(a.film);
 }
 

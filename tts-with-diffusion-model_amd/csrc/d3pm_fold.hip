@@ -87,12 +87,12 @@ __global__ __launch_bounds__(256) void row_stats(const T* __restrict__ x, int ld
 // embed_rows_vec (d3pm_generic.hip) + the moments of the gathered rows in the same pass
 template <typename T>
 __global__ __launch_bounds__(256) void embed_rows_stats(const int32_t* __restrict__ tok, const uint8_t* __restrict__ frame_mask,
-                                                        int canvas, const T* __restrict__ table, T* __restrict__ y, int M, int d,
+                                                        int mask_period, const T* __restrict__ table, T* __restrict__ y, int M, int d,
                                                         int n_classes, float* __restrict__ stats, bool quads) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + wave;
   if (row >= M) return;
-  embed_row_stats<T>(table, tok[row], frame_mask[row % canvas] != 0, y, row, d, n_classes, stats, quads, lane);
+  embed_row_stats<T>(table, tok[row], frame_mask[row % mask_period] != 0, y, row, d, n_classes, stats, quads, lane);
 }
 
 }  // namespace
@@ -157,10 +157,10 @@ int embed_tokens_stats(int dtype, const EmbedArgs& a, float* stats, bool quads, 
   }
   const dim3 grid(static_cast<unsigned>((a.M + 3) / 4)), block(256);
   if (dtype == D3PM_F16)
-    embed_rows_stats<f16><<<grid, block, 0, s>>>(a.tokens, a.frame_mask, a.canvas, static_cast<const f16*>(a.table), static_cast<f16*>(a.Y),
+    embed_rows_stats<f16><<<grid, block, 0, s>>>(a.tokens, a.frame_mask, a.mask_period, static_cast<const f16*>(a.table), static_cast<f16*>(a.Y),
                                                  a.M, a.d, a.n_classes, stats, quads);
   else
-    embed_rows_stats<bf16><<<grid, block, 0, s>>>(a.tokens, a.frame_mask, a.canvas, static_cast<const bf16*>(a.table),
+    embed_rows_stats<bf16><<<grid, block, 0, s>>>(a.tokens, a.frame_mask, a.mask_period, static_cast<const bf16*>(a.table),
                                                   static_cast<bf16*>(a.Y), a.M, a.d, a.n_classes, stats, quads);
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;

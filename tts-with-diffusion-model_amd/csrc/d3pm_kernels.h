@@ -94,8 +94,9 @@ struct LayerNormArgs {
   const void* film = nullptr;
   int M = 0, d = 0; float eps = 1e-6f;
   // optional gather in front (the first block's norm1 directly on the token embedding, ar_discrete.py:753,127,131): row m of the
-  // input is table[tokens[m]] (zeros where frame_mask[m % canvas] == 0) with X = the table; the gathered rows also go to Xout
-  const int32_t* tokens = nullptr; const uint8_t* frame_mask = nullptr; int canvas = 0, n_classes = 0; void* Xout = nullptr;
+  // input is table[tokens[m]] (zeros where frame_mask[m % mask_period] == 0) with X = the table; the gathered rows also go to Xout.
+  // mask_period: canvas for a mask the utterances share, batch * canvas for a per-utterance one (d3pm_canvas)
+  const int32_t* tokens = nullptr; const uint8_t* frame_mask = nullptr; int mask_period = 0, n_classes = 0; void* Xout = nullptr;
 };
 
 // what the row-panel projection (d3pm_mfma_gemm_big.hip) does to the rows it has just finished: N = d_model = 512
@@ -118,7 +119,7 @@ struct LnPrologue {
 };
 
 struct EmbedArgs {
-  const int32_t* tokens = nullptr; const uint8_t* frame_mask = nullptr; int canvas = 0;
+  const int32_t* tokens = nullptr; const uint8_t* frame_mask = nullptr; int mask_period = 0;      // frame_mask[row % mask_period]
   const void* table = nullptr; void* Y = nullptr; int M = 0, d = 0, n_classes = 0;
   int n_q = 1;      // > 1: tokens [M][n_q], table [n_q][n_classes][d], row = rn(sum over the levels) (d3pm_shape.n_q)
 };
@@ -142,6 +143,8 @@ struct SampleArgs {
   uint64_t seed = 0; uint32_t row0 = 0; int greedy = 0;
   const uint64_t* seed_hbm = nullptr;   // when set, the kernel reads the seed from HBM (lets a captured HIP graph be replayed with a new seed)
   int n_q = 1;      // > 1: row r = (frame row r / n_q, level r % n_q); Philox row = row0 + frame row, stream = level ? 16 + level : 0
+  // known frames (d3pm_canvas.known, uint8 [frame rows]) or nullptr: a marked frame keeps x_t (all its levels) and draws nothing
+  const uint8_t* known = nullptr;
   PosteriorConsts pc{};
 };
 
@@ -172,6 +175,7 @@ int posterior_sample(const SampleArgs& a, hipStream_t s);
 struct NextIterPrep {
   int dtype = D3PM_BF16;
   const void* table = nullptr; void* x = nullptr; float* stats = nullptr; const uint8_t* frame_mask = nullptr; int d = 0;
+  int mask_period = 0;                                                                              // frame_mask[row % mask_period]
   bool quads = false;                                                                               // stats in the quad format
   const d3pm_block_weights* blocks = nullptr; int n_layers = 0; const void* film_t = nullptr;      // film_t: row t - 1 of the FiLM table
   void* Wf = nullptr; float* s_out = nullptr; float* b_out = nullptr;

@@ -26,14 +26,34 @@
 namespace d3pm {
 namespace {
 
-template <typename T>
+// Is this wave's frame row given by the caller (the known-frame map of d3pm_canvas, uint8 [batch][canvas])?  One byte load per wave,
+// broadcast through readfirstlane so that the branch on it is a scalar one: a known row skips the whole draw.
+__device__ __forceinline__ bool row_is_known(const uint8_t* __restrict__ known, int frow) {
+  return __builtin_amdgcn_readfirstlane(static_cast<int>(known[frow])) != 0;
+}
+
+// kKnown (replacement conditioning): a row whose frame is marked in `known` keeps x_t[row] -- no logits read, no
+// Philox draw (the noise of every other row is keyed by its own global row and does not move) -- and takes the same stores.
+// kKnown = false is the kernel without the map: `known` is never read.
+template <typename T, bool kKnown>
 __global__ __launch_bounds__(256) void posterior_sample_rows(
     const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next,
     int32_t* x_next2, uint16_t* __restrict__ post_out, int rows, int K, int mask_id,
-    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int n_q) {
+    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int n_q,
+    const uint8_t* __restrict__ known) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x >> 6) + wave;
   if (row >= rows) return;
+  if constexpr (kKnown) {
+    if (row_is_known(known, n_q > 1 ? row / n_q : row)) {      // wave-uniform: one wave per row
+      if (lane == 0) {
+        const int keep = x_t[row];
+        x_next[row] = keep;
+        if (x_next2) x_next2[row] = keep;
+      }
+      return;
+    }
+  }
   if (seed_hbm) seed = *seed_hbm;
   // n_q > 1 (d3pm_shape.n_q): row = frame row * n_q + level; the level-0 token of a frame draws the noise the level-0-only
   // path draws, level l > 0 draws from Philox stream 16 + l at the same (frame row, t)
@@ -56,12 +76,15 @@ __global__ __launch_bounds__(256) void posterior_sample_rows(
 // their moments (the id is in every lane after the wave argmax); the workgroups behind them rebuild fc1 o norm3 o FiLM(t - 1) of
 // every block.  The two halves are independent (one VALU-bound, one a 24-MB stream), so the launch costs the longer of them: at one
 // utterance 12.4 + 8.7 + 5.0 us of launches become ~13, at 32 utterances 94 + 10.8 + 10.5 become ~97.
-template <typename T>
+// kKnown as in posterior_sample_rows: a known row takes best_j = x_t[row] and goes through the same stores and the same gather, so
+// the next iteration's residual row and moments are written exactly as for a drawn id.
+template <typename T, bool kKnown>
 __global__ __launch_bounds__(256) void posterior_sample_prep_rows(
     const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next, int32_t* x_next2, int rows, int K, int mask_id,
-    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int canvas, int sample_blocks,
+    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int mask_period, int sample_blocks,
     const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
-    bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out) {
+    bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
+    const uint8_t* __restrict__ known) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (static_cast<int>(blockIdx.x) >= sample_blocks) {
     const int r = (blockIdx.x - sample_blocks) * 4 + wave;
@@ -71,19 +94,25 @@ __global__ __launch_bounds__(256) void posterior_sample_prep_rows(
   const int row = blockIdx.x * 4 + wave;
   if (row >= rows) return;
   if (seed_hbm) seed = *seed_hbm;
-  const int best_j = (K == 1025 && mask_id < 1024)
-      ? sample_row_1025<T>(logits + static_cast<size_t>(row) * ldl, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, lane, 0u)
-      : sample_row<T>(logits + static_cast<size_t>(row) * ldl, K, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, nullptr, lane, 0u);
+  int best_j;
+  bool keep = false;
+  if constexpr (kKnown) keep = row_is_known(known, row);      // wave-uniform: one wave per row
+  if (keep)
+    best_j = x_t[row];
+  else
+    best_j = (K == 1025 && mask_id < 1024)
+        ? sample_row_1025<T>(logits + static_cast<size_t>(row) * ldl, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, lane, 0u)
+        : sample_row<T>(logits + static_cast<size_t>(row) * ldl, K, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, nullptr, lane, 0u);
   if (lane == 0) {
     x_next[row] = best_j;
     if (x_next2) x_next2[row] = best_j;
   }
-  embed_row_stats<T>(table, best_j, frame_mask[row % canvas] != 0, xres, row, d, K, stats, quads, lane);
+  embed_row_stats<T>(table, best_j, frame_mask[row % mask_period] != 0, xres, row, d, K, stats, quads, lane);
 }
 
 // forward noising: logits are log16(rn16(row_of_Qbar_t + eps)) with at most three distinct values
 __global__ __launch_bounds__(256) void q_sample_rows(const int32_t* __restrict__ x0, int32_t* __restrict__ out,
-                                                     const uint8_t* __restrict__ frame_mask, int canvas,
+                                                     const uint8_t* __restrict__ frame_mask, int mask_period,
                                                      int rows, int K, int mask_id, uint64_t seed,
                                                      uint32_t row0, int t, float log_dbar, float log_cbar,
                                                      float log_zero, float log_one) {
@@ -109,7 +138,7 @@ __global__ __launch_bounds__(256) void q_sample_rows(const int32_t* __restrict__
     }
   }
   wave_argmax(best_v, best_j);
-  if (lane == 0) out[row] = frame_mask[row % canvas] ? best_j : 0;
+  if (lane == 0) out[row] = frame_mask[row % mask_period] ? best_j : 0;
 }
 
 __global__ void uniform_rows(uint64_t seed, int t, uint32_t row0, int rows, int K, int stream_id,
@@ -135,10 +164,16 @@ int posterior_sample(const SampleArgs& a, hipStream_t s) {
                "posterior_sample supports up to %d classes", kWave * kMaxGroupsPerLane * 4);
   const int rpb = 4;
   dim3 grid((a.rows + rpb - 1) / rpb), block(rpb * kWave);
-#define D3PM_PS(T)                                                                                      \
-  posterior_sample_rows<T><<<grid, block, 0, s>>>(static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next, \
-                                                  a.x_next2, a.posterior_out, a.rows, a.n_classes,        \
-                                                  a.mask_id, a.seed, a.seed_hbm, a.row0, a.greedy, a.pc, a.n_q)
+  // no map: the kernel without the known-row arm
+#define D3PM_PS_ARM(T, kKnown)                                                                                           \
+  posterior_sample_rows<T, kKnown><<<grid, block, 0, s>>>(static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next,        \
+                                                          a.x_next2, a.posterior_out, a.rows, a.n_classes, a.mask_id,   \
+                                                          a.seed, a.seed_hbm, a.row0, a.greedy, a.pc, a.n_q, a.known)
+#define D3PM_PS(T)                    \
+  do {                                \
+    if (a.known) D3PM_PS_ARM(T, true); \
+    else D3PM_PS_ARM(T, false);       \
+  } while (0)
   switch (a.logits_dtype) {
     case D3PM_F32: D3PM_PS(float); break;
     case D3PM_F16: D3PM_PS(f16); break;
@@ -146,13 +181,14 @@ int posterior_sample(const SampleArgs& a, hipStream_t s) {
     default: set_error("unknown logits dtype %d", a.logits_dtype); return D3PM_E_ARG;
   }
 #undef D3PM_PS
+#undef D3PM_PS_ARM
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }
 
 bool posterior_sample_prep_supported(const SampleArgs& a, const NextIterPrep& n) {
   return a.n_q == 1 && !a.posterior_out && a.logits_dtype == n.dtype && (n.dtype == D3PM_F16 || n.dtype == D3PM_BF16) && n.n_layers <= 16 &&
-         n.d % 256 == 0 && (!n.quads || n.d == 512) && a.n_classes <= kWave * kMaxGroupsPerLane * 4 && n.table && n.x && n.stats && n.blocks && n.film_t && n.Wf;
+         n.d % 256 == 0 && (!n.quads || n.d == 512) && a.n_classes <= kWave * kMaxGroupsPerLane * 4 && n.table && n.x && n.stats && n.frame_mask && n.mask_period > 0 && n.blocks && n.film_t && n.Wf;
 }
 
 int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_t s) {
@@ -162,12 +198,18 @@ int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_
   }
   const int sample_blocks = (a.rows + 3) / 4, fold_blocks = (4 * n.d * n.n_layers + 3) / 4;
   const dim3 grid(static_cast<unsigned>(sample_blocks + fold_blocks)), block(256);
-#define D3PM_PSP(T)                                                                                                                 \
-  posterior_sample_prep_rows<T><<<grid, block, 0, s>>>(static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next, a.x_next2, a.rows, a.n_classes, \
-      a.mask_id, a.seed, a.seed_hbm, a.row0, a.greedy, a.pc, a.canvas, sample_blocks, static_cast<const T*>(n.table), static_cast<T*>(n.x),    \
-      n.stats, n.frame_mask, n.d, n.quads, p, static_cast<const T*>(n.film_t), n.n_layers, static_cast<T*>(n.Wf), n.s_out, n.b_out)
+#define D3PM_PSP_ARM(T, kKnown)                                                                                                                     \
+  posterior_sample_prep_rows<T, kKnown><<<grid, block, 0, s>>>(static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next, a.x_next2, a.rows, a.n_classes, \
+      a.mask_id, a.seed, a.seed_hbm, a.row0, a.greedy, a.pc, n.mask_period, sample_blocks, static_cast<const T*>(n.table), static_cast<T*>(n.x),       \
+      n.stats, n.frame_mask, n.d, n.quads, p, static_cast<const T*>(n.film_t), n.n_layers, static_cast<T*>(n.Wf), n.s_out, n.b_out, a.known)
+#define D3PM_PSP(T)                     \
+  do {                                  \
+    if (a.known) D3PM_PSP_ARM(T, true);  \
+    else D3PM_PSP_ARM(T, false);        \
+  } while (0)
   if (n.dtype == D3PM_F16) D3PM_PSP(f16); else D3PM_PSP(bf16);
 #undef D3PM_PSP
+#undef D3PM_PSP_ARM
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }
@@ -188,12 +230,12 @@ int q_sample_launch(const d3pm_shape* sh, int batch, const int32_t* x0, int32_t*
 // canvas.  One wave per row, fp32 arithmetic on the logits as stored.
 template <typename T>
 __global__ __launch_bounds__(256) void ce_loss_rows(const T* __restrict__ logits, int ldl, const int32_t* __restrict__ targets,
-                                                    const uint8_t* __restrict__ frame_mask, int canvas, int rows, int K,
+                                                    const uint8_t* __restrict__ frame_mask, int mask_period, int rows, int K,
                                                     float* __restrict__ row_loss) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x >> 6) + wave;
   if (row >= rows) return;
-  if (!frame_mask[row % canvas]) {
+  if (!frame_mask[row % mask_period]) {
     if (lane == 0) row_loss[row] = logf(static_cast<float>(K));
     return;
   }
@@ -209,13 +251,13 @@ __global__ __launch_bounds__(256) void ce_loss_rows(const T* __restrict__ logits
   if (lane == 0) row_loss[row] = mx + logf(sum) - static_cast<float>(lr[tg]);
 }
 
-int ce_loss_launch(int dtype, const void* logits, int ldl, const int32_t* targets, const uint8_t* frame_mask, int canvas,
+int ce_loss_launch(int dtype, const void* logits, int ldl, const int32_t* targets, const uint8_t* frame_mask, int mask_period,
                    int rows, int K, float* row_loss, hipStream_t s) {
   const dim3 grid((rows + 3) / 4), block(256);
   switch (dtype) {
-    case D3PM_F32: ce_loss_rows<float><<<grid, block, 0, s>>>(static_cast<const float*>(logits), ldl, targets, frame_mask, canvas, rows, K, row_loss); break;
-    case D3PM_F16: ce_loss_rows<f16><<<grid, block, 0, s>>>(static_cast<const f16*>(logits), ldl, targets, frame_mask, canvas, rows, K, row_loss); break;
-    case D3PM_BF16: ce_loss_rows<bf16><<<grid, block, 0, s>>>(static_cast<const bf16*>(logits), ldl, targets, frame_mask, canvas, rows, K, row_loss); break;
+    case D3PM_F32: ce_loss_rows<float><<<grid, block, 0, s>>>(static_cast<const float*>(logits), ldl, targets, frame_mask, mask_period, rows, K, row_loss); break;
+    case D3PM_F16: ce_loss_rows<f16><<<grid, block, 0, s>>>(static_cast<const f16*>(logits), ldl, targets, frame_mask, mask_period, rows, K, row_loss); break;
+    case D3PM_BF16: ce_loss_rows<bf16><<<grid, block, 0, s>>>(static_cast<const bf16*>(logits), ldl, targets, frame_mask, mask_period, rows, K, row_loss); break;
     default: set_error("unknown logits dtype %d", dtype); return D3PM_E_ARG;
   }
   D3PM_LAUNCH_CHECK();

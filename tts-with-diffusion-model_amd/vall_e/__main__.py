@@ -19,6 +19,10 @@ The second form takes what those front-ends write (formats.py) and writes what E
   --prompt-qnt  a `.qnt.pt` file as written by the reference's emb/qnt.py:68,93 (int64 [1, 8, t])
   --nar-ckpt    state_dict of the stock NAR model: levels 1..7 are filled in and `out` is a `.qnt.pt` [1, 8, t];
                 without it `out` holds the level-0 codes only ([1, 1, t])
+  --frames N    frames to generate (default: the model's n_frames); the `.qnt.pt` that is written holds N frames
+  --continue-from FILE.qnt.pt
+                level 0 of that file is a known prefix of the utterance: its frames are revealed to the sampler from the
+                first iteration on and come back unchanged, the remaining N - prefix frames are generated
 """
 import argparse
 from pathlib import Path
@@ -40,6 +44,8 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--dtype", default="float16", choices=["float16", "bfloat16", "float32"])
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--frames", type=int, default=None, help="frames to generate (default: the model's n_frames)")
+    ap.add_argument("--continue-from", type=Path, default=None, help=".qnt.pt whose level 0 is the known prefix of the utterance")
     ap.add_argument("--native", action="store_true", help="the shape upstream's class really builds (d=32, 16 heads, 8 blocks)")
     args = ap.parse_args(argv)
 
@@ -52,6 +58,8 @@ def main(argv=None):
     if upstream_form:
         if args.phonemes is not None or args.phn_file is not None or args.prompt_qnt is not None:
             ap.error("TEXT REFERENCE OUT takes its phonemes and prompt from TEXT and REFERENCE")
+        if args.frames is not None or args.continue_from is not None:
+            ap.error("--frames / --continue-from belong to the pre-tokenised form")
         if args.ar_ckpt is None and args.symmap is None:
             ap.error("TEXT needs a phone symmap: an --ar-ckpt that carries ar.phone_symmap, or --symmap")
         from . import frontends
@@ -85,8 +93,13 @@ def main(argv=None):
         phns = formats.phones_to_ids(phones, symmap)                                # symmap = ar.phone_symmap, __main__.py:56,61
     else:
         phns = torch.tensor([int(p) for p in args.phonemes.split()], dtype=torch.long)
-    codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed)
-    resps = codes[: model.cfg.n_frames].unsqueeze(-1)                              # __main__.py:64 of the reference
+    n_frames = model.cfg.n_frames if args.frames is None else args.frames
+    if args.frames is None and args.continue_from is None:
+        codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed)
+    else:
+        prefix = None if args.continue_from is None else [formats.load_quants(args.continue_from)[:, 0]]
+        codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed, n_frames=[n_frames], known=prefix)
+    resps = codes[:n_frames].unsqueeze(-1)                                         # __main__.py:64 of the reference
     if args.nar_ckpt is not None:
         nar = get_model(args.nar_model)
         nar.load_state_dict(torch.load(args.nar_ckpt, map_location="cpu"))

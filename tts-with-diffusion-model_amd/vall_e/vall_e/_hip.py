@@ -96,6 +96,11 @@ class NarWeights(C.Structure):
                 ("blocks", C.POINTER(NarBlockWeights))]
 
 
+class Canvas(C.Structure):
+    """d3pm_canvas: per-utterance frame masks and the optional known-frame map, both device uint8 [batch][canvas]."""
+    _fields_ = [("frame_mask", C.c_void_p), ("known", C.c_void_p)]
+
+
 class ScheduleC(C.Structure):
     _fields_ = [("timesteps", C.c_int32), ("d", C.POINTER(C.c_uint16)), ("c", C.POINTER(C.c_uint16)),
                 ("dbar", C.POINTER(C.c_uint16)), ("cbar", C.POINTER(C.c_uint16))]
@@ -132,6 +137,19 @@ SIGNATURES = {
     "d3pm_sample_loop": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ScheduleC), C.c_uint64,
                                    C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "d3pm_denoise_step_canvas": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.POINTER(Canvas), C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                           C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]),
+    "d3pm_posterior_sample_known": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32,
+                                              C.c_void_p, C.c_void_p]),
+    "d3pm_sample_loop_canvas": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.POINTER(Canvas), C.c_int,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ScheduleC), C.c_uint64,
+                                          C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "d3pm_sample_loop_fp8_canvas": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_int, C.c_void_p,
+                                              C.POINTER(Canvas), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_void_p]),
     "d3pm_q_sample": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                 C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_void_p]),
     "d3pm_denoise_step_fp8": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -504,6 +522,20 @@ class Sampler:
             _require(frame_mask, "frame_mask", (cfg.canvas,), (torch.uint8,), self.device)
         return x.shape[0]
 
+    def _check_canvas(self, B, frame_mask, known=None):
+        """The per-utterance calls: frame_mask uint8 [B, canvas] (a shared [canvas] mask is repeated per utterance) and the
+        known-frame map, uint8 [B, canvas] or None -> the d3pm_canvas struct (keeps its tensors alive)."""
+        cfg = self.cfg
+        if isinstance(frame_mask, torch.Tensor) and frame_mask.dim() == 1:
+            _require(frame_mask, "frame_mask", (cfg.canvas,), (torch.uint8,), self.device)
+            frame_mask = frame_mask[None].expand(B, cfg.canvas).contiguous()
+        _require(frame_mask, "frame_mask", (B, cfg.canvas), (torch.uint8,), self.device)
+        if known is not None:
+            _require(known, "known", (B, cfg.canvas), (torch.uint8,), self.device)
+        cv = Canvas(frame_mask.data_ptr(), None if known is None else known.data_ptr())
+        cv._keep = (frame_mask, known)
+        return cv
+
     def _check_kv(self, kv_t, kv_p, B):
         cfg = self.cfg
         _require(kv_t, "kv_text", (cfg.n_layers, B, cfg.s_text, 2 * cfg.d_model), (self.dtype,), self.device)
@@ -528,16 +560,38 @@ class Sampler:
                                       _p(hidden), only_layers, flags, stream_ptr()), "d3pm_denoise_step")
         return logits, hidden
 
+    def denoise_canvas(self, x_t, frame_mask, t, kv_t, kv_p, *, want_logits=True, want_hidden=False, only_layers=-1, flags=0):
+        """`denoise` with one frame mask per utterance, uint8 [B, canvas] (d3pm_denoise_step_canvas)."""
+        cfg = self.cfg
+        B = self._check_grid(x_t)
+        cv = self._check_canvas(B, frame_mask)
+        self._check_kv(kv_t, kv_p, B)
+        ws = self.workspace(B)
+        logits = torch.empty((B, cfg.canvas) + self._lvl() + (cfg.n_classes,), dtype=self.dtype, device=self.device) if want_logits else None
+        hidden = torch.empty((B, cfg.canvas, cfg.d_model), dtype=self.dtype, device=self.device) if want_hidden else None
+        check(lib().d3pm_denoise_step_canvas(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x_t), C.byref(cv),
+                                             int(t), _p(self.film), _p(kv_t), _p(kv_p), _p(ws), ws.numel(), _p(logits),
+                                             _p(hidden), only_layers, flags, stream_ptr()), "d3pm_denoise_step_canvas")
+        return logits, hidden
+
     def _lvl(self):
         return () if self.n_q == 1 else (self.n_q,)
 
-    def posterior_sample(self, logits, x_t, t, seed, utt0=0, flags=0, want_posterior=False):
+    def posterior_sample(self, logits, x_t, t, seed, utt0=0, flags=0, want_posterior=False, known=None):
+        """known: uint8 [B, canvas] or None -- frames that keep x_t instead of being drawn (d3pm_posterior_sample_known)."""
         cfg = self.cfg
         B = self._check_grid(x_t)
+        if known is not None:
+            _require(known, "known", (B, cfg.canvas), (torch.uint8,), self.device)
         logits = logits.contiguous() if isinstance(logits, torch.Tensor) else logits
         _require(logits, "logits", (B, cfg.canvas) + self._lvl() + (cfg.n_classes,), tuple(_DTYPES), self.device)
         x_next = torch.empty_like(x_t)
         post = torch.empty((B, cfg.canvas) + self._lvl() + (cfg.n_classes,), dtype=torch.int16, device=self.device) if want_posterior else None
+        if known is not None:
+            check(lib().d3pm_posterior_sample_known(C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), _p(x_t),
+                                                    _p(x_next), _p(known), int(t), C.byref(self.schedule.c_struct), seed, utt0,
+                                                    flags, _p(post), stream_ptr()), "d3pm_posterior_sample_known")
+            return x_next, post
         check(lib().d3pm_posterior_sample(C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), _p(x_t),
                                           _p(x_next), int(t), C.byref(self.schedule.c_struct), seed, utt0, flags,
                                           _p(post), stream_ptr()), "d3pm_posterior_sample")
@@ -557,12 +611,29 @@ class Sampler:
         return x_next
 
     def sample_loop(self, x, frame_mask, t_start, t_stop, kv_t, kv_p, seed, utt0=0, flags=0, trace=False, slot=0,
-                    fp8=False):
+                    fp8=False, known=None):
+        """frame_mask uint8 [canvas] (shared by the batch) runs d3pm_sample_loop(_fp8); a per-utterance mask [B, canvas] and / or a
+        known-frame map `known` (uint8 [B, canvas]; `x` already carries the given ids) run the *_canvas entries."""
         cfg = self.cfg
-        B = self._check_grid(x, frame_mask, "x")
+        per_utt = known is not None or (isinstance(frame_mask, torch.Tensor) and frame_mask.dim() == 2)
+        B = self._check_grid(x, None if per_utt else frame_mask, "x")
+        cv = self._check_canvas(B, frame_mask, known) if per_utt else None
         self._check_kv(kv_t, kv_p, B)
         ws = self.workspace(B, slot)
         tr = torch.empty((t_start - t_stop, B, cfg.canvas) + self._lvl(), dtype=torch.int32, device=self.device) if trace else None
+        if per_utt and fp8:
+            check(lib().d3pm_sample_loop_fp8_canvas(C.byref(self.shape), C.byref(self.weights.c_struct),
+                                                    C.cast(self.fp8_weights().blocks, C.c_void_p), B, _p(x), C.byref(cv),
+                                                    int(t_start), int(t_stop), _p(self.film), _p(kv_t), _p(kv_p),
+                                                    C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
+                                                    stream_ptr()), "d3pm_sample_loop_fp8_canvas")
+            return tr
+        if per_utt:
+            check(lib().d3pm_sample_loop_canvas(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), C.byref(cv),
+                                                int(t_start), int(t_stop), _p(self.film), _p(kv_t), _p(kv_p),
+                                                C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
+                                                stream_ptr()), "d3pm_sample_loop_canvas")
+            return tr
         if fp8:
             check(lib().d3pm_sample_loop_fp8(C.byref(self.shape), C.byref(self.weights.c_struct),
                                              C.cast(self.fp8_weights().blocks, C.c_void_p), B, _p(x), _p(frame_mask),

@@ -18,7 +18,8 @@ Differences from upstream, all opt-in or strictly more general:
 from __future__ import annotations
 
 import math
-from typing import Optional, Sequence
+from numbers import Integral
+from typing import Optional, Sequence, Union
 
 import torch
 import torch.nn.functional as F
@@ -249,10 +250,15 @@ class AR(SymmapState, nn.Module):
         cp = self.encoder2(cp.transpose(0, 1)).transpose(0, 1)
         return ct.contiguous(), cp.contiguous()
 
-    def canvas_init(self, batch: int, n_frames: Optional[int] = None):
-        """x_T: `n_frames` mask ids then zeros; the frame mask is fixed for the whole loop (:699-709)."""
+    def canvas_init(self, batch: int, n_frames: Union[int, Sequence[int], None] = None):
+        """x_T: `n_frames` mask ids then zeros; the frame mask is fixed for the whole loop (:699-709).  An int (or None: the
+        constructor's n_frames) gives the mask every utterance shares, uint8 [canvas]; a sequence of `batch` ints gives utterance
+        b its own `n_frames[b]` live frames and a mask uint8 [batch, canvas]."""
         cfg = self.cfg
-        n_frames = cfg.n_frames if n_frames is None else n_frames
+        if n_frames is not None and not isinstance(n_frames, Integral):
+            x, frame_mask, _ = self.canvas_init_known(batch, n_frames)
+            return x, frame_mask
+        n_frames = cfg.n_frames if n_frames is None else int(n_frames)
         if not 0 < n_frames <= cfg.canvas:
             raise ValueError(f"n_frames must be in 1..{cfg.canvas}")
         shape = (batch, cfg.canvas) if cfg.n_q == 1 else (batch, cfg.canvas, cfg.n_q)
@@ -261,16 +267,85 @@ class AR(SymmapState, nn.Module):
         frame_mask = (x[0].reshape(cfg.canvas, -1)[:, 0] != 0).to(torch.uint8)
         return x, frame_mask
 
+    def canvas_init_known(self, batch: int, n_frames: Union[int, Sequence[int], None] = None, known=None, known_mask=None):
+        """Per-utterance canvases (include/d3pm_hip.h: d3pm_canvas) -> (x_T int32 [batch, canvas(, n_q)], frame mask uint8
+        [batch, canvas], known-frame map uint8 [batch, canvas] or None when no frame is given).
+        Utterance b has L_b = n_frames[b] live frames (an int or None: the same for all).  known[b] (or None) is an int tensor
+        [n] -- [n, n_q] for a model built with n_q > 1 -- of codec ids 0 .. 1023 for frames 0 .. n - 1, and known_mask[b] (or None) a
+        bool [n] that marks which of them are given; without a mask all n are, i.e. a known[b] shorter than L_b is a prefix to
+        continue.  x_T carries the given ids, the mask id on the other live frames and zeros on the padding.  Ids are taken
+        verbatim: 512 is upstream's mask id (1025 // 2) and doubles as a codec id there, so a known 512 is legal and stays 512.
+        Everything is validated here, on the host (ValueError); the kernels check nothing."""
+        cfg = self.cfg
+        if n_frames is None or isinstance(n_frames, Integral):
+            lens = [cfg.n_frames if n_frames is None else int(n_frames)] * batch
+        else:
+            lens = [int(v) for v in n_frames]
+        if len(lens) != batch:
+            raise ValueError(f"n_frames has {len(lens)} entries for {batch} utterances")
+        for L in lens:
+            if not 0 < L <= cfg.canvas:
+                raise ValueError(f"n_frames must be in 1..{cfg.canvas}, got {L}")
+        if known is None and known_mask is not None:
+            raise ValueError("known_mask without known")
+        for name, lst in (("known", known), ("known_mask", known_mask)):
+            if lst is not None and len(lst) != batch:
+                raise ValueError(f"{name} has {len(lst)} entries for {batch} utterances")
+        x = torch.zeros((batch, cfg.canvas, cfg.n_q), dtype=torch.int32)
+        frame_mask = torch.zeros((batch, cfg.canvas), dtype=torch.uint8)
+        kmap = torch.zeros((batch, cfg.canvas), dtype=torch.uint8)
+        for b, L in enumerate(lens):
+            x[b, :L] = MASK_ID
+            frame_mask[b, :L] = 1
+            ids = None if known is None else known[b]
+            if ids is None:
+                if known_mask is not None and known_mask[b] is not None:
+                    raise ValueError(f"known_mask[{b}] without known[{b}]")
+                continue
+            ids = torch.as_tensor(ids).detach().cpu()
+            if ids.is_floating_point() or ids.dtype == torch.bool or ids.dim() not in (1, 2):
+                raise ValueError(f"known[{b}] must be an integer tensor [n] or [n, n_q]")
+            ids = ids.long().reshape(ids.shape[0], -1)
+            if ids.shape[1] != cfg.n_q:
+                raise ValueError(f"known[{b}] must give all {cfg.n_q} level(s) of a frame, got {ids.shape[1]}")
+            given = torch.ones(ids.shape[0], dtype=torch.bool)
+            if known_mask is not None and known_mask[b] is not None:
+                given = torch.as_tensor(known_mask[b]).detach().cpu().reshape(-1).bool()
+                if given.shape[0] != ids.shape[0]:
+                    raise ValueError(f"known_mask[{b}] has {given.shape[0]} entries for {ids.shape[0]} known frames")
+            at = given.nonzero().reshape(-1)
+            if at.numel() == 0:
+                continue
+            if int(at.max()) >= L:
+                raise ValueError(f"known[{b}] gives frame {int(at.max())}, at or beyond the utterance's {L} live frames")
+            vals = ids[at]
+            if int(vals.min()) < 0 or int(vals.max()) > N_CLASSES - 2:
+                raise ValueError(f"known[{b}] holds an id outside 0..{N_CLASSES - 2}")
+            x[b, at] = vals.to(torch.int32)
+            kmap[b, at] = 1
+        if cfg.n_q == 1:
+            x = x[:, :, 0]
+        dev = self.device
+        return x.contiguous().to(dev), frame_mask.to(dev), (kmap.to(dev) if bool(kmap.any()) else None)
+
     # ------------------------------------------------------------------ the hot path
     @torch.no_grad()
     def generate_audio(self, text_list, proms_list, resps_list=None, *, steps: Optional[int] = None,
-                       n_frames: Optional[int] = None, seed: Optional[int] = None, greedy: bool = False,
+                       n_frames: Union[int, Sequence[int], None] = None, seed: Optional[int] = None, greedy: bool = False,
                        utt0: int = 0, return_trace: bool = False, flags: int = 0, streams: Optional[int] = None,
-                       graph: Optional[bool] = None, fp8: bool = False, global_batch: Optional[int] = None):
+                       graph: Optional[bool] = None, fp8: bool = False, global_batch: Optional[int] = None,
+                       known: Optional[Sequence[Optional[Tensor]]] = None,
+                       known_mask: Optional[Sequence[Optional[Tensor]]] = None):
         """Reverse diffusion for len(text_list) utterances.  Positional behaviour as upstream:
         one utterance -> int64 [canvas] (squeezed, untrimmed; rows >= n_frames are sampled from
         final.bias and meaningless); with n_q > 1 (constructor) [canvas, n_q] / [B, canvas, n_q].  `resps_list` is ignored, as
         upstream ignores it (:699).
+        `n_frames` may be a sequence of B ints: utterance b then has n_frames[b] live frames and is exactly the one-utterance run
+        `generate_audio([text_b], [prom_b], n_frames=n_frames[b], utt0=utt0 + b, global_batch=...)`, bit for bit.  `known` /
+        `known_mask` give frames the caller already has (canvas_init_known: ids, and which of them are given; a known[b] shorter
+        than the utterance with no mask is a prefix to continue): they are revealed context from the first iteration on and
+        come back unchanged; every other frame draws the noise it would have drawn without them.  The result stays [B, canvas],
+        untrimmed: the caller trims with its own lengths.
         `fp8=True` is the fast configuration of BASELINE.json configs[4]: the QKV, cross-attention query, fc1 and fc2
         projections run on the block-scaled fp8 matrix instruction (e4m3 codes, one power-of-two scale per 32 elements;
         d_model = 512, 16-bit model, batch * canvas a multiple of 192); the reference has no such mode.
@@ -284,6 +359,12 @@ class AR(SymmapState, nn.Module):
         if len(text_list) != len(proms_list) or len(text_list) == 0:
             raise ValueError("text_list and proms_list must be non-empty and of equal length")
         B = len(text_list)
+        per_utt = known is not None or known_mask is not None or not (n_frames is None or isinstance(n_frames, Integral))
+        if per_utt:
+            if graph:
+                raise ValueError("graph=True replays static buffers captured per (batch, step range): per-utterance n_frames / "
+                                 "known frames run on the eager loop only")
+            x, frame_mask, kmap = self.canvas_init_known(B, n_frames, known, known_mask)      # host validation before any GPU work
         smp = self.sampler()
         t_start = (self.timesteps - 1) if steps is None else steps
         if not 0 < t_start < smp.schedule.timesteps:
@@ -294,7 +375,8 @@ class AR(SymmapState, nn.Module):
         regime = max(int(global_batch), B) if global_batch else (B if n_streams > 1 else 0)
         with torch.cuda.device(self.device), _hip.tuning(regime_batch=regime):
             cond_text, cond_prompt = self.encode_conditions(text_list, proms_list)
-            x, frame_mask = self.canvas_init(B, n_frames)
+            if not per_utt:
+                x, frame_mask, kmap = self.canvas_init(B, n_frames) + (None,)
             fl = flags | (_hip.FLAG_GREEDY if greedy else 0)
             use_graph = bool(graph)
             if fp8 and (use_graph or (n_streams > 1 and not return_trace)):
@@ -306,7 +388,7 @@ class AR(SymmapState, nn.Module):
                 smp.sample_loop_graphed(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl)
             elif n_streams == 1 or return_trace:
                 kv_t, kv_p = smp.cond_kv(cond_text, cond_prompt)
-                trace = smp.sample_loop(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl, trace=return_trace, fp8=fp8)
+                trace = smp.sample_loop(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl, trace=return_trace, fp8=fp8, known=kmap)
             else:
                 # utterances are independent: chunks of the batch run the whole loop on their own stream so that
                 # the short kernels of one chunk fill the ramp-up / epilogue bubbles of the others
@@ -321,7 +403,8 @@ class AR(SymmapState, nn.Module):
                     st.wait_stream(cur)
                     with torch.cuda.stream(st):
                         kv_t, kv_p = smp.cond_kv(cond_text[lo:hi], cond_prompt[lo:hi])
-                        smp.sample_loop(x[lo:hi], frame_mask, t_start, 0, kv_t, kv_p, seed, utt0 + lo, fl, slot=i)
+                        smp.sample_loop(x[lo:hi], frame_mask[lo:hi] if per_utt else frame_mask, t_start, 0, kv_t, kv_p, seed, utt0 + lo, fl,
+                                        slot=i, known=None if kmap is None else kmap[lo:hi])
                         for t_ in (kv_t, kv_p, cond_text, cond_prompt, x):
                             t_.record_stream(st)
                 for i in range(n_streams):

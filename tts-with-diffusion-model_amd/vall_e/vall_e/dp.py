@@ -12,6 +12,7 @@ The reference has no multi-GPU inference (its only distributed code is DeepSpeed
 """
 from __future__ import annotations
 
+from numbers import Integral
 from typing import Callable, Optional, Sequence
 
 import torch
@@ -23,6 +24,19 @@ def shard_bounds(n_items: int, world: int, rank: int) -> tuple[int, int]:
     base, extra = divmod(n_items, world)
     lo = rank * base + min(rank, extra)
     return lo, lo + base + (1 if rank < extra else 0)
+
+
+_PER_UTTERANCE = ("n_frames", "known", "known_mask")
+
+
+def _shard_kwargs(kw: dict, lo: int, hi: int) -> dict:
+    """Per-utterance keyword arguments of AR.generate_audio (a sequence n_frames, known, known_mask) cut to the shard."""
+    out = dict(kw)
+    for name in _PER_UTTERANCE:
+        v = out.get(name)
+        if v is not None and not isinstance(v, Integral):
+            out[name] = list(v[lo:hi])
+    return out
 
 
 def generate_audio_dp(model, text_list: Sequence[torch.Tensor], proms_list: Sequence[torch.Tensor], *, seed: int,
@@ -37,7 +51,7 @@ def generate_audio_dp(model, text_list: Sequence[torch.Tensor], proms_list: Sequ
     if generate_fn is None:
         kw = dict(kw, global_batch=B)          # a shard takes the attention kernels of the unsplit batch: same ids at any rank count
     if hi > lo:
-        local = fn(list(text_list[lo:hi]), list(proms_list[lo:hi]), seed=seed, utt0=lo, **kw)
+        local = fn(list(text_list[lo:hi]), list(proms_list[lo:hi]), seed=seed, utt0=lo, **_shard_kwargs(kw, lo, hi))
         local = local.reshape(hi - lo, -1).to(torch.int32)
     else:
         local = None
@@ -66,12 +80,19 @@ def generate_codes_dp(ar, nar, text_list: Sequence[torch.Tensor], proms_list: Se
     """Both stages of the reference's inference script (/root/reference/vall_e/__main__.py:60-71) sharded the same way:
     every rank runs the D3PM stage and then the NAR stage (levels 1..7) for its contiguous slice of the utterances --
     noise keyed by the global utterance index in both -- and ONE all-gather returns the int64 [B, n_frames, 8] codes
-    to every rank.  No collective sits between the stages: a rank's NAR input is its own D3PM output."""
+    to every rank.  No collective sits between the stages: a rank's NAR input is its own D3PM output.
+    With a sequence `n_frames` (one length per utterance) the NAR stage sees utterance b's own L_b frames and the result is
+    [B, max L, 8], zero beyond L_b."""
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank(group) if world > 1 else 0
     B = len(text_list)
     lo, hi = shard_bounds(B, world, rank)
-    n_frames, levels = ar.cfg.n_frames, nar.n_resp_levels + 1
+    levels = nar.n_resp_levels + 1
+    nf = kw.get("n_frames")
+    lens = [int(ar.cfg.n_frames if nf is None else nf)] * B if nf is None or isinstance(nf, Integral) else [int(v) for v in nf]
+    if len(lens) != B:
+        raise ValueError(f"n_frames has {len(lens)} entries for {B} utterances")
+    n_frames = max(lens)
     gen = ar_fn or ar.generate_audio
     fill = nar_fn or nar
     if ar_fn is None:
@@ -79,10 +100,12 @@ def generate_codes_dp(ar, nar, text_list: Sequence[torch.Tensor], proms_list: Se
     local = None
     if hi > lo:
         texts, proms = list(text_list[lo:hi]), list(proms_list[lo:hi])
-        lvl0 = gen(texts, proms, seed=seed, utt0=lo, **kw).reshape(hi - lo, -1)[:, :n_frames]
-        resps = [lvl0[b].clamp(max=nar.n_tokens - 1).reshape(-1, 1) for b in range(hi - lo)]
+        lvl0 = gen(texts, proms, seed=seed, utt0=lo, **_shard_kwargs(kw, lo, hi)).reshape(hi - lo, -1)
+        resps = [lvl0[b][: lens[lo + b]].clamp(max=nar.n_tokens - 1).reshape(-1, 1) for b in range(hi - lo)]
         full = fill(texts, proms, resps, seed=seed, utt0=lo)
-        local = torch.stack([f.reshape(n_frames, levels) for f in full]).to(torch.int32)
+        local = torch.zeros((hi - lo, n_frames, levels), dtype=torch.int32, device=full[0].device)
+        for b, f in enumerate(full):
+            local[b, : lens[lo + b]] = f.reshape(lens[lo + b], levels).to(torch.int32)
     if world == 1:
         return local.long()
     dev = local.device if local is not None else ar.device
