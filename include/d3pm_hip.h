@@ -52,7 +52,8 @@ extern "C" {
  *    d3pm_workspace_bytes grew by the row-moment buffer and the fp8 path's scale slot;
  *    later additions only: the condition encoders' training-step dropout (d3pm_op_dropout_f32, d3pm_op_attention_dropout_f32,
  *    d3pm_op_attention_bwd_dropout_f32); per-utterance canvases (d3pm_canvas, d3pm_denoise_step_canvas,
- *    d3pm_posterior_sample_known, d3pm_sample_loop_canvas, d3pm_sample_loop_fp8_canvas) */
+ *    d3pm_posterior_sample_known, d3pm_sample_loop_canvas, d3pm_sample_loop_fp8_canvas); temperature / top-k on the x0-logits
+ *    (d3pm_sampling, d3pm_posterior_sample_sampling, d3pm_sample_loop_sampling) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -395,6 +396,42 @@ int d3pm_sample_loop_fp8_canvas(const d3pm_shape *shape, const d3pm_weights *wei
                                 const void *kv_text, const void *kv_prompt, const d3pm_schedule *sched,
                                 uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
                                 size_t workspace_bytes, int32_t *trace, void *stream);
+
+/* Temperature and top-k on the x0-logits ----------------------------------------------------------------
+ * How sharply the reverse step draws (the reference has neither; the NAR stage's own temperature is d3pm_nar_level's).  Two numbers
+ * per call, applied to every row's logits l_j right after the sampler has loaded them, exactly (no tolerance anywhere):
+ *     z_j   = rn16(float(l_j))                           what the sampler reads today
+ *     z'_j  = rn16(z_j / temperature)                    fp32 division, one rounding (temperature 1: z' = z bit for bit)
+ *     theta = the top_k-th largest of z'_0 .. z'_{K-1}, counted with multiplicity      (top_k 0: -inf)
+ *     z''_j = z'_j >= theta ? z'_j : -inf                ties at theta are all kept, so >= top_k classes survive
+ *     x_{t-1} = the unfiltered routine on z'' (softmax, fact1 / fact2, logs, Gumbel add, first-index argmax: unchanged)
+ * i.e. a filtered call equals the unfiltered entry fed with host-filtered logits, id for id.  All n_classes take part alike (no
+ * special case for the mask id); with n_q > 1 each level's n_classes logits are filtered on their own.  The noise does not move:
+ * every class keeps the uniform it had, a class that was cut carries p = 0 into the same arithmetic.  D3PM_FLAG_GREEDY, t = 0,
+ * known frames, per-utterance masks, utt0 / regime_batch compose with it as they compose with each other.
+ *   temperature  finite and > 0; 1 = off        top_k  0 = off, else 1 .. n_classes        (anything else: D3PM_E_ARG, nothing launched)
+ * A NULL d3pm_sampling, or {1.0f, 0}, is bit-identical to the entry that is generalised and launches the very same kernels; any
+ * other pair ({1.0f, n_classes} included) takes the kernels' filter arm. */
+typedef struct d3pm_sampling {
+  float temperature;
+  int32_t top_k;
+} d3pm_sampling;
+
+/* d3pm_posterior_sample_known (known may be NULL: d3pm_posterior_sample) with sampling options. */
+int d3pm_posterior_sample_sampling(const d3pm_shape *shape, int batch, const void *logits, int logits_dtype,
+                                   const int32_t *x_t, int32_t *x_next, const uint8_t *known, int t,
+                                   const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags,
+                                   uint16_t *posterior_out, const d3pm_sampling *sampling, void *stream);
+
+/* The four loops above in one entry, with sampling options: exactly one of `frame_mask` (device uint8 [canvas], shared by the
+ * batch: d3pm_sample_loop) and `canvas` (d3pm_sample_loop_canvas) is given, the other is NULL; `fp8_blocks` NULL = the 16-bit
+ * loop, else the fp8 fast path (d3pm_sample_loop_fp8 / _fp8_canvas, same shape requirements).  Every other argument as there. */
+int d3pm_sample_loop_sampling(const d3pm_shape *shape, const d3pm_weights *weights,
+                              const d3pm_fp8_block_weights *fp8_blocks, int batch, int32_t *x, const uint8_t *frame_mask,
+                              const d3pm_canvas *canvas, int t_start, int t_stop, const void *film, const void *kv_text,
+                              const void *kv_prompt, const d3pm_schedule *sched, uint64_t seed, uint32_t utt0,
+                              uint32_t flags, void *workspace, size_t workspace_bytes, int32_t *trace,
+                              const d3pm_sampling *sampling, void *stream);
 
 /* Replaces AR.q_sample / q_probs (ar_discrete.py:467-502): forward noising of x0 at step t with
  * Philox stream 1.  x0, x_out device int32 [batch][canvas]. */

@@ -18,7 +18,7 @@ for line in sys.stdin:
 names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True, text=True).stdout.splitlines()
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
 for r, n in zip(rows, names):
-    n = re.sub(r"\(.*", "", n).replace("d3pm::(anonymous namespace)::", "").replace("void ", "")
+    n = re.sub(r"\(.*", "", n.replace("d3pm::(anonymous namespace)::", "")).replace("void ", "")
     if flt and not re.search(flt, n): continue
     print("%-70s VGPR %4s AGPR %4s scratch %4s occ %s" % (n[:70], r.get("VGPRs", "?"), r.get("AGPRs", "?"), r.get("ScratchSize [bytes/lane]", "?"), r.get("Occupancy [waves/SIMD]", "?")))
 ' "$2"

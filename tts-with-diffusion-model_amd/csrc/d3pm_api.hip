@@ -5,6 +5,7 @@
 //   2 x cross-attention against the cached condition K/V, 2 x out GEMM(+res), LN3+FiLM,
 //   fc1 GEMM(+GELU), fc2 GEMM(+res, *mask) } -> final GEMM -> posterior/sample.
 // Nothing here allocates or synchronises; everything is enqueued on the caller's stream.
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <new>
@@ -918,10 +919,21 @@ int d3pm_denoise_step_fp8(const d3pm_shape* sh, const d3pm_weights* w, const d3p
                            hidden_out, only_layers, flags, stream, fp8_blocks);
 }
 
+// d3pm_sampling of the *_sampling entries: NULL = the neutral pair.  Refused before anything is launched.
+static int check_sampling(const d3pm_shape* sh, const d3pm_sampling* sm, const char* who) {
+  if (!sm) return D3PM_OK;
+  D3PM_REQUIRE(std::isfinite(sm->temperature) && sm->temperature > 0.f, D3PM_E_ARG, "%s: temperature %g is not a finite number > 0", who,
+               static_cast<double>(sm->temperature));
+  D3PM_REQUIRE(sm->top_k >= 0 && sm->top_k <= sh->n_classes, D3PM_E_ARG, "%s: top_k %d outside 0 (off) .. %d (n_classes)", who, sm->top_k,
+               sh->n_classes);
+  return D3PM_OK;
+}
+
 static int posterior_sample_impl(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
                                  int32_t* x_next, const uint8_t* known, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
-                                 uint32_t flags, uint16_t* posterior_out, void* stream) {
+                                 uint32_t flags, uint16_t* posterior_out, void* stream, const d3pm_sampling* sm = nullptr) {
   D3PM_TRY(check_shape(sh, batch));
+  D3PM_TRY(check_sampling(sh, sm, "d3pm_posterior_sample_sampling"));
   D3PM_REQUIRE(logits && x_t && x_next && sched && sched->d && sched->c && sched->dbar && sched->cbar, D3PM_E_ARG,
                "d3pm_posterior_sample: null pointer");
   D3PM_REQUIRE(t >= 0 && t < sched->timesteps, D3PM_E_ARG, "t=%d outside the schedule", t);
@@ -932,6 +944,7 @@ static int posterior_sample_impl(const d3pm_shape* sh, int batch, const void* lo
   a.canvas = sh->canvas; a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas);
   a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0; a.pc = make_posterior_consts(sched, t);
   a.known = known;
+  if (sm) { a.temperature = sm->temperature; a.top_k = sm->top_k; }
   return posterior_sample(a, static_cast<hipStream_t>(stream));
 }
 
@@ -947,11 +960,19 @@ int d3pm_posterior_sample_known(const d3pm_shape* sh, int batch, const void* log
   return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, known, t, sched, seed, utt0, flags, posterior_out, stream);
 }
 
+int d3pm_posterior_sample_sampling(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
+                                   int32_t* x_next, const uint8_t* known, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                                   uint32_t flags, uint16_t* posterior_out, const d3pm_sampling* sampling, void* stream) {
+  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, known, t, sched, seed, utt0, flags, posterior_out, stream, sampling);
+}
+
 static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const CanvasMask& cm,
                             int t_start, int t_stop, const void* film, const void* kv_text, const void* kv_prompt,
                             const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace,
-                            size_t workspace_bytes, int32_t* trace, void* stream, const d3pm_fp8_block_weights* f8) {
+                            size_t workspace_bytes, int32_t* trace, void* stream, const d3pm_fp8_block_weights* f8,
+                            const d3pm_sampling* sm = nullptr) {
   D3PM_TRY(check_shape(sh, batch));
+  D3PM_TRY(check_sampling(sh, sm, "d3pm_sample_loop_sampling"));
   D3PM_REQUIRE(w && w->blocks && x && cm.frame_mask && film && kv_text && kv_prompt && sched && workspace, D3PM_E_ARG,
                "d3pm_sample_loop: null pointer");
   D3PM_REQUIRE(t_start < sched->timesteps && t_start <= sh->timesteps && t_stop >= 0 && t_stop <= t_start, D3PM_E_ARG,
@@ -976,8 +997,9 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     a.row0 = utt0 * static_cast<uint32_t>(sh->canvas); a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0;
     a.pc = make_posterior_consts(sched, t);
     a.known = cm.known;
+    if (sm) { a.temperature = sm->temperature; a.top_k = sm->top_k; }
 #ifdef D3PM_ABLATIONS
-    if (!cm.known && fused_final_sample_applies(*sh, *w, ws, flags)) {
+    if (!cm.known && !a.filtered() && fused_final_sample_applies(*sh, *w, ws, flags)) {
       // final projection + posterior + draw in one kernel: the logits stay on chip (d3pm_final_sample.hip)
       ProfScope p(cx, D3PM_K_SAMPLE, s, 2.0 * rows * sh->n_classes * sh->d_model,
                   dtype_size(sh->dtype) * (static_cast<double>(rows) * sh->d_model + static_cast<double>(sh->n_classes) * sh->d_model) + 8.0 * rows);
@@ -1042,6 +1064,17 @@ int d3pm_sample_loop_fp8_canvas(const d3pm_shape* sh, const d3pm_weights* w, con
   D3PM_REQUIRE(fp8_blocks && canvas, D3PM_E_ARG, "d3pm_sample_loop_fp8_canvas: null fp8 weights or canvas");
   return sample_loop_impl(sh, w, batch, x, per_utterance_mask(sh, batch, canvas, true), t_start, t_stop, film, kv_text, kv_prompt, sched, seed,
                           utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks);
+}
+
+int d3pm_sample_loop_sampling(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch, int32_t* x,
+                              const uint8_t* frame_mask, const d3pm_canvas* canvas, int t_start, int t_stop, const void* film,
+                              const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                              uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_sampling* sampling,
+                              void* stream) {
+  D3PM_REQUIRE(sh && (frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
+               "d3pm_sample_loop_sampling: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)");
+  return sample_loop_impl(sh, w, batch, x, canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask), t_start, t_stop,
+                          film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks, sampling);
 }
 
 int d3pm_q_sample(const d3pm_shape* sh, int batch, const int32_t* x0, int32_t* x_out, const uint8_t* frame_mask, int t,

@@ -145,6 +145,10 @@ struct SampleArgs {
   int n_q = 1;      // > 1: row r = (frame row r / n_q, level r % n_q); Philox row = row0 + frame row, stream = level ? 16 + level : 0
   // known frames (d3pm_canvas.known, uint8 [frame rows]) or nullptr: a marked frame keeps x_t (all its levels) and draws nothing
   const uint8_t* known = nullptr;
+  // d3pm_sampling, validated by the entry point: z' = rn16(z / temperature), then everything below the top_k-th largest z' becomes
+  // -inf (0 = no cut).  The neutral pair launches the kernels without the filter arm.
+  float temperature = 1.0f; int top_k = 0;
+  bool filtered() const { return temperature != 1.0f || top_k != 0; }
   PosteriorConsts pc{};
 };
 

@@ -35,12 +35,14 @@ __device__ __forceinline__ bool row_is_known(const uint8_t* __restrict__ known, 
 // kKnown (replacement conditioning): a row whose frame is marked in `known` keeps x_t[row] -- no logits read, no
 // Philox draw (the noise of every other row is keyed by its own global row and does not move) -- and takes the same stores.
 // kKnown = false is the kernel without the map: `known` is never read.
-template <typename T, bool kKnown>
-__global__ __launch_bounds__(256) void posterior_sample_rows(
+// kFilter (temperature / top-k, d3pm_sample_row.h): a compile-time arm like kKnown.  The kernels without it keep their names, their
+// arguments and their code; the *_filtered kernels below carry the two numbers as one more argument.
+template <typename T, bool kKnown, bool kFilter>
+__device__ __forceinline__ void posterior_sample_rows_body(
     const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next,
     int32_t* x_next2, uint16_t* __restrict__ post_out, int rows, int K, int mask_id,
-    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int n_q,
-    const uint8_t* __restrict__ known) {
+    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, const PosteriorConsts& pc, int n_q,
+    const uint8_t* __restrict__ known, const RowFilter& flt) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x >> 6) + wave;
   if (row >= rows) return;
@@ -61,14 +63,35 @@ __global__ __launch_bounds__(256) void posterior_sample_rows(
   const uint32_t strm = level ? 16u + static_cast<uint32_t>(level) : 0u;
   int best_j;
   if (K == 1025 && mask_id < 1024 && !post_out)        // kernel-uniform: the predicate-free routine for the reference's class count (same bits)
-    best_j = sample_row_1025<T>(logits + static_cast<size_t>(row) * ldl, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(frow), greedy, pc, lane, strm);
+    best_j = sample_row_1025<T, kFilter>(logits + static_cast<size_t>(row) * ldl, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(frow), greedy, pc, lane, strm,
+                                         D3PM_SAMPLER_EARLY_OUT != 0, flt);
   else
-    best_j = sample_row<T>(logits + static_cast<size_t>(row) * ldl, K, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(frow), greedy, pc,
-                           post_out ? post_out + static_cast<size_t>(row) * K : nullptr, lane, strm);
+    best_j = sample_row<T, kFilter>(logits + static_cast<size_t>(row) * ldl, K, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(frow), greedy, pc,
+                                    post_out ? post_out + static_cast<size_t>(row) * K : nullptr, lane, strm, flt);
   if (lane == 0) {
     x_next[row] = best_j;
     if (x_next2) x_next2[row] = best_j;
   }
+}
+
+template <typename T, bool kKnown>
+__global__ __launch_bounds__(256) void posterior_sample_rows(
+    const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next,
+    int32_t* x_next2, uint16_t* __restrict__ post_out, int rows, int K, int mask_id,
+    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int n_q,
+    const uint8_t* __restrict__ known) {
+  posterior_sample_rows_body<T, kKnown, false>(logits, ldl, x_t, x_next, x_next2, post_out, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, n_q,
+                                               known, RowFilter{});
+}
+
+template <typename T, bool kKnown>
+__global__ __launch_bounds__(256) void posterior_sample_rows_filtered(
+    const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next,
+    int32_t* x_next2, uint16_t* __restrict__ post_out, int rows, int K, int mask_id,
+    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int n_q,
+    const uint8_t* __restrict__ known, RowFilter flt) {
+  posterior_sample_rows_body<T, kKnown, true>(logits, ldl, x_t, x_next, x_next2, post_out, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, n_q,
+                                              known, flt);
 }
 
 // The sampler of iteration t and the preparation of iteration t - 1 in one launch (NextIterPrep, d3pm_kernels.h): workgroups
@@ -78,13 +101,13 @@ __global__ __launch_bounds__(256) void posterior_sample_rows(
 // utterance 12.4 + 8.7 + 5.0 us of launches become ~13, at 32 utterances 94 + 10.8 + 10.5 become ~97.
 // kKnown as in posterior_sample_rows: a known row takes best_j = x_t[row] and goes through the same stores and the same gather, so
 // the next iteration's residual row and moments are written exactly as for a drawn id.
-template <typename T, bool kKnown>
-__global__ __launch_bounds__(256) void posterior_sample_prep_rows(
+template <typename T, bool kKnown, bool kFilter>
+__device__ __forceinline__ void posterior_sample_prep_rows_body(
     const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next, int32_t* x_next2, int rows, int K, int mask_id,
-    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int mask_period, int sample_blocks,
+    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, const PosteriorConsts& pc, int mask_period, int sample_blocks,
     const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
-    bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
-    const uint8_t* __restrict__ known) {
+    bool quads, const FoldStepPtrs& fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
+    const uint8_t* __restrict__ known, const RowFilter& flt) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (static_cast<int>(blockIdx.x) >= sample_blocks) {
     const int r = (blockIdx.x - sample_blocks) * 4 + wave;
@@ -101,13 +124,38 @@ __global__ __launch_bounds__(256) void posterior_sample_prep_rows(
     best_j = x_t[row];
   else
     best_j = (K == 1025 && mask_id < 1024)
-        ? sample_row_1025<T>(logits + static_cast<size_t>(row) * ldl, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, lane, 0u)
-        : sample_row<T>(logits + static_cast<size_t>(row) * ldl, K, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, nullptr, lane, 0u);
+        ? sample_row_1025<T, kFilter>(logits + static_cast<size_t>(row) * ldl, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, lane, 0u,
+                                      D3PM_SAMPLER_EARLY_OUT != 0, flt)
+        : sample_row<T, kFilter>(logits + static_cast<size_t>(row) * ldl, K, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, nullptr, lane, 0u, flt);
   if (lane == 0) {
     x_next[row] = best_j;
     if (x_next2) x_next2[row] = best_j;
   }
   embed_row_stats<T>(table, best_j, frame_mask[row % mask_period] != 0, xres, row, d, K, stats, quads, lane);
+}
+
+template <typename T, bool kKnown>
+__global__ __launch_bounds__(256) void posterior_sample_prep_rows(
+    const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next, int32_t* x_next2, int rows, int K, int mask_id,
+    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int mask_period, int sample_blocks,
+    const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
+    bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
+    const uint8_t* __restrict__ known) {
+  posterior_sample_prep_rows_body<T, kKnown, false>(logits, ldl, x_t, x_next, x_next2, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, mask_period,
+                                                    sample_blocks, table, xres, stats, frame_mask, d, quads, fp, film_t, n_layers, Wf, s_out, b_out, known,
+                                                    RowFilter{});
+}
+
+template <typename T, bool kKnown>
+__global__ __launch_bounds__(256) void posterior_sample_prep_rows_filtered(
+    const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next, int32_t* x_next2, int rows, int K, int mask_id,
+    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int mask_period, int sample_blocks,
+    const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
+    bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
+    const uint8_t* __restrict__ known, RowFilter flt) {
+  posterior_sample_prep_rows_body<T, kKnown, true>(logits, ldl, x_t, x_next, x_next2, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, mask_period,
+                                                   sample_blocks, table, xres, stats, frame_mask, d, quads, fp, film_t, n_layers, Wf, s_out, b_out, known,
+                                                   flt);
 }
 
 // forward noising: logits are log16(rn16(row_of_Qbar_t + eps)) with at most three distinct values
@@ -164,11 +212,16 @@ int posterior_sample(const SampleArgs& a, hipStream_t s) {
                "posterior_sample supports up to %d classes", kWave * kMaxGroupsPerLane * 4);
   const int rpb = 4;
   dim3 grid((a.rows + rpb - 1) / rpb), block(rpb * kWave);
-  // no map: the kernel without the known-row arm
-#define D3PM_PS_ARM(T, kKnown)                                                                                           \
-  posterior_sample_rows<T, kKnown><<<grid, block, 0, s>>>(static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next,        \
-                                                          a.x_next2, a.posterior_out, a.rows, a.n_classes, a.mask_id,   \
-                                                          a.seed, a.seed_hbm, a.row0, a.greedy, a.pc, a.n_q, a.known)
+  const RowFilter flt{a.temperature, a.top_k};
+  // no map: the kernel without the known-row arm; neutral sampling options: the kernel without the filter arm
+#define D3PM_PS_ARGS(T)                                                                                                          \
+  static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next, a.x_next2, a.posterior_out, a.rows, a.n_classes, a.mask_id, a.seed, \
+      a.seed_hbm, a.row0, a.greedy, a.pc, a.n_q, a.known
+#define D3PM_PS_ARM(T, kKnown)                                                                            \
+  do {                                                                                                    \
+    if (a.filtered()) posterior_sample_rows_filtered<T, kKnown><<<grid, block, 0, s>>>(D3PM_PS_ARGS(T), flt); \
+    else posterior_sample_rows<T, kKnown><<<grid, block, 0, s>>>(D3PM_PS_ARGS(T));                           \
+  } while (0)
 #define D3PM_PS(T)                    \
   do {                                \
     if (a.known) D3PM_PS_ARM(T, true); \
@@ -182,6 +235,7 @@ int posterior_sample(const SampleArgs& a, hipStream_t s) {
   }
 #undef D3PM_PS
 #undef D3PM_PS_ARM
+#undef D3PM_PS_ARGS
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }
@@ -198,10 +252,16 @@ int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_
   }
   const int sample_blocks = (a.rows + 3) / 4, fold_blocks = (4 * n.d * n.n_layers + 3) / 4;
   const dim3 grid(static_cast<unsigned>(sample_blocks + fold_blocks)), block(256);
-#define D3PM_PSP_ARM(T, kKnown)                                                                                                                     \
-  posterior_sample_prep_rows<T, kKnown><<<grid, block, 0, s>>>(static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next, a.x_next2, a.rows, a.n_classes, \
-      a.mask_id, a.seed, a.seed_hbm, a.row0, a.greedy, a.pc, n.mask_period, sample_blocks, static_cast<const T*>(n.table), static_cast<T*>(n.x),       \
-      n.stats, n.frame_mask, n.d, n.quads, p, static_cast<const T*>(n.film_t), n.n_layers, static_cast<T*>(n.Wf), n.s_out, n.b_out, a.known)
+  const RowFilter flt{a.temperature, a.top_k};
+#define D3PM_PSP_ARGS(T)                                                                                                                            \
+  static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next, a.x_next2, a.rows, a.n_classes, a.mask_id, a.seed, a.seed_hbm, a.row0, a.greedy, a.pc, \
+      n.mask_period, sample_blocks, static_cast<const T*>(n.table), static_cast<T*>(n.x), n.stats, n.frame_mask, n.d, n.quads, p,                 \
+      static_cast<const T*>(n.film_t), n.n_layers, static_cast<T*>(n.Wf), n.s_out, n.b_out, a.known
+#define D3PM_PSP_ARM(T, kKnown)                                                                                  \
+  do {                                                                                                           \
+    if (a.filtered()) posterior_sample_prep_rows_filtered<T, kKnown><<<grid, block, 0, s>>>(D3PM_PSP_ARGS(T), flt); \
+    else posterior_sample_prep_rows<T, kKnown><<<grid, block, 0, s>>>(D3PM_PSP_ARGS(T));                            \
+  } while (0)
 #define D3PM_PSP(T)                     \
   do {                                  \
     if (a.known) D3PM_PSP_ARM(T, true);  \
@@ -210,6 +270,7 @@ int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_
   if (n.dtype == D3PM_F16) D3PM_PSP(f16); else D3PM_PSP(bf16);
 #undef D3PM_PSP
 #undef D3PM_PSP_ARM
+#undef D3PM_PSP_ARGS
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

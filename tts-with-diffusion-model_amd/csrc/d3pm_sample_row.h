@@ -12,11 +12,75 @@ namespace {
 constexpr int kMaxGroupsPerLane = 5;   // supports n_classes <= 64*5*4 = 1280
 constexpr float kEps = 1.0e-6f;        // self.eps (ar_discrete.py:276), added in fp32 opmath then rounded
 
+// ---- temperature / top-k on the x0-logits (d3pm_sampling) ----------------------------------------------
+// kFilter arm of the two routines below: right after the load, the row's z = rn16(logit) become
+//     z'  = rn16(z / temperature)                         (fp32 division, one rounding)
+//     z'' = z' >= theta ? z' : -inf,  theta = the top_k-th largest z' counted with multiplicity (top_k = 0: no cut)
+// and everything behind the load runs on z'' as it is.  theta is found without LDS and without a sort: every fp16 value maps to a
+// 16-bit key whose unsigned order is the order of the values, and the key of theta is the largest c with
+// #{key >= c} >= top_k, built bit by bit from the top.  One round counts each of the lane's values with one vector compare
+// whose wave-wide mask is popcounted on the scalar unit, so the count is wave-uniform by construction: no shuffle, no barrier,
+// no divergence.  The final cut compares VALUES (z' >= theta), so that -0 and +0 (two keys, one value) are kept or cut together.
+struct RowFilter {
+  float temperature = 1.0f;
+  int top_k = 0;
+};
+
+// fp16-exact float -> key: negative values reverse (all bits flipped), the others move above them (sign bit set)
+__device__ __forceinline__ uint32_t f16_order_key(float v) {
+  const uint32_t u = __builtin_bit_cast(uint16_t, static_cast<f16>(v));
+  return (u & 0x8000u) ? (~u & 0xFFFFu) : (u | 0x8000u);
+}
+__device__ __forceinline__ float f16_order_value(uint32_t key) {
+  const uint16_t u = static_cast<uint16_t>((key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu));
+  return static_cast<float>(__builtin_bit_cast(f16, u));
+}
+
+// z[R][4]: the lane's classes (valid(i, w) says which slots hold a class of the row; the others hold -inf and stay -inf);
+// zt: one more class in the lanes where has_tail is set (sample_row_1025's class 1024), -inf elsewhere.
+template <int R, typename V>
+__device__ __forceinline__ void filter_row(float (&z)[R][4], float& zt, bool has_tail, V valid, const RowFilter& f) {
+  if (f.temperature != 1.0f) {      // kernel-uniform
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+      for (int w = 0; w < 4; ++w) z[i][w] = rn16(z[i][w] / f.temperature);      // -inf stays -inf
+    zt = rn16(zt / f.temperature);
+  }
+  if (f.top_k > 0) {                // kernel-uniform
+    uint32_t key[R][4];             // 0 for a slot without a class: below every candidate (>= 1), never counted
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+      for (int w = 0; w < 4; ++w) key[i][w] = valid(i, w) ? f16_order_key(z[i][w]) : 0u;
+    const uint32_t kt = has_tail ? f16_order_key(zt) : 0u;
+    uint32_t c = 0u;
+#pragma unroll
+    for (uint32_t bit = 0x8000u; bit; bit >>= 1) {
+      const uint32_t cand = c | bit;
+      int n = __popcll(__ballot(kt >= cand));
+#pragma unroll
+      for (int i = 0; i < R; ++i)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) n += __popcll(__ballot(key[i][w] >= cand));
+      c = n >= f.top_k ? cand : c;
+    }
+    const float theta = f16_order_value(c);
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+      for (int w = 0; w < 4; ++w) z[i][w] = z[i][w] >= theta ? z[i][w] : -INFINITY;
+    zt = zt >= theta ? zt : -INFINITY;
+  }
+}
+
 // One wave draws x_{t-1} of one row.  `lr[j]` are the row's K logits in the model dtype (any address space);
 // returns the sampled id in every lane.  `post_row` (optional) receives the fp16 posterior logits of the row.
-template <typename T, typename P>
+// kFilter: the row's logits pass through filter_row first (`flt`); false = the routine without it, `flt` is never read.
+template <typename T, bool kFilter = false, typename P>
 __device__ __forceinline__ int sample_row(P lr, int K, int mask_id, int x, uint64_t seed, uint32_t grow, int greedy,
-                                          const PosteriorConsts& pc, uint16_t* post_row, int lane, uint32_t stream = 0u) {
+                                          const PosteriorConsts& pc, uint16_t* post_row, int lane, uint32_t stream = 0u,
+                                          const RowFilter& flt = RowFilter{}) {
   const int groups = (K + 3) >> 2;
   float z[kMaxGroupsPerLane][4];
   float mx = -INFINITY;
@@ -30,6 +94,15 @@ __device__ __forceinline__ int sample_row(P lr, int K, int mask_id, int x, uint6
       z[i][w] = v;
       mx = fmaxf(mx, v);
     }
+  }
+  if constexpr (kFilter) {
+    float none = -INFINITY;
+    filter_row(z, none, false, [&](int i, int w) { const int g = lane + i * kWave; return g < groups && g * 4 + w < K; }, flt);
+    mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < kMaxGroupsPerLane; ++i)
+#pragma unroll
+      for (int w = 0; w < 4; ++w) mx = fmaxf(mx, z[i][w]);
   }
   int best_j = 0;
   float best_v = -INFINITY;
@@ -102,9 +175,13 @@ __device__ __forceinline__ int sample_row(P lr, int K, int mask_id, int x, uint6
 #ifndef D3PM_SAMPLER_EARLY_OUT
 #define D3PM_SAMPLER_EARLY_OUT 1      // A/B builds (tools/build_variant.py NAME -DD3PM_SAMPLER_EARLY_OUT=0): the full routine for every row
 #endif
-template <typename T, typename P>
+// kFilter as in sample_row.  The revealed-row early-out below stays exact under it: its bounds are statements about the routine's
+// inputs, and the routine's inputs are then z'' -- `sum` is the sum over the kept classes, the kept token's score is computed from
+// its own z'' (probability 0 when the filter cut it: the test then fails or holds exactly as the full routine decides).
+template <typename T, bool kFilter = false, typename P>
 __device__ __forceinline__ int sample_row_1025(P lr, int mask_id, int x, uint64_t seed, uint32_t grow, int greedy,
-                                               const PosteriorConsts& pc, int lane, uint32_t stream = 0u, bool early_out = D3PM_SAMPLER_EARLY_OUT != 0) {
+                                               const PosteriorConsts& pc, int lane, uint32_t stream = 0u, bool early_out = D3PM_SAMPLER_EARLY_OUT != 0,
+                                               const RowFilter& flt = RowFilter{}) {
   constexpr int K = 1025;
   float z[4][4], zt;
   float mx = -INFINITY;
@@ -117,6 +194,14 @@ __device__ __forceinline__ int sample_row_1025(P lr, int mask_id, int x, uint64_
     }
   zt = lane == 0 ? rn16(static_cast<float>(lr[K - 1])) : -INFINITY;
   mx = fmaxf(mx, zt);
+  if constexpr (kFilter) {
+    filter_row(z, zt, lane == 0, [](int, int) { return true; }, flt);
+    mx = zt;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int w = 0; w < 4; ++w) mx = fmaxf(mx, z[i][w]);
+  }
   int best_j = 0;
   float best_v = -INFINITY;
   if (pc.t == 0) {

@@ -23,6 +23,10 @@ The second form takes what those front-ends write (formats.py) and writes what E
   --continue-from FILE.qnt.pt
                 level 0 of that file is a known prefix of the utterance: its frames are revealed to the sampler from the
                 first iteration on and come back unchanged, the remaining N - prefix frames are generated
+  --temperature F, --top-k N
+                how sharply the D3PM stage draws: the x0-logits of every reverse step are divided by F (> 0, default 1) and cut
+                to their N largest (0 = off, the default; ties kept) before the posterior draw (AR.generate_audio); the NAR stage
+                keeps its own sampling_temperature
 """
 import argparse
 from pathlib import Path
@@ -46,11 +50,17 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--frames", type=int, default=None, help="frames to generate (default: the model's n_frames)")
     ap.add_argument("--continue-from", type=Path, default=None, help=".qnt.pt whose level 0 is the known prefix of the utterance")
+    ap.add_argument("--temperature", type=float, default=1.0, help="D3PM stage: divide the x0-logits by this (> 0) before every draw")
+    ap.add_argument("--top-k", type=int, default=0, help="D3PM stage: draw from the N largest x0-logits only (0 = off)")
     ap.add_argument("--native", action="store_true", help="the shape upstream's class really builds (d=32, 16 heads, 8 blocks)")
     args = ap.parse_args(argv)
 
     from . import formats
-    from .vall_e import AR, get_model
+    from .vall_e import AR, _hip, get_model
+    try:
+        _hip.sampling_options(args.temperature, args.top_k, 1025)
+    except ValueError as e:
+        ap.error(str(e))
     if len(args.paths) not in (1, 3):
         ap.error("give OUT, or TEXT REFERENCE OUT")
     upstream_form = len(args.paths) == 3
@@ -94,11 +104,13 @@ def main(argv=None):
     else:
         phns = torch.tensor([int(p) for p in args.phonemes.split()], dtype=torch.long)
     n_frames = model.cfg.n_frames if args.frames is None else args.frames
+    sampling = dict(temperature=args.temperature, top_k=args.top_k)
     if args.frames is None and args.continue_from is None:
-        codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed)
+        codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed, **sampling)
     else:
         prefix = None if args.continue_from is None else [formats.load_quants(args.continue_from)[:, 0]]
-        codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed, n_frames=[n_frames], known=prefix)
+        codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed, n_frames=[n_frames], known=prefix,
+                                     **sampling)
     resps = codes[:n_frames].unsqueeze(-1)                                         # __main__.py:64 of the reference
     if args.nar_ckpt is not None:
         nar = get_model(args.nar_model)

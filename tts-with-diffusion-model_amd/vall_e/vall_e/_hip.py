@@ -8,7 +8,9 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
+from numbers import Integral
 
 import numpy as np
 import torch
@@ -101,6 +103,30 @@ class Canvas(C.Structure):
     _fields_ = [("frame_mask", C.c_void_p), ("known", C.c_void_p)]
 
 
+class Sampling(C.Structure):
+    """d3pm_sampling: temperature and top-k on the x0-logits of the D3PM sampler (include/d3pm_hip.h)."""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32)]
+
+
+def sampling_options(temperature=1.0, top_k=0, n_classes=None):
+    """Host validation of the two sampling options (ValueError, before any GPU work) -> a Sampling struct, or None for the neutral
+    pair (temperature 1, top_k 0), which runs the entries and the kernels that know nothing of the filter."""
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)):
+        raise ValueError(f"temperature must be a number, got {temperature!r}")
+    tau = float(temperature)
+    if not (math.isfinite(tau) and tau > 0.0) or not math.isfinite(C.c_float(tau).value) or C.c_float(tau).value <= 0.0:
+        raise ValueError(f"temperature must be finite and > 0, got {temperature!r}")
+    if isinstance(top_k, bool) or not isinstance(top_k, Integral):
+        raise ValueError(f"top_k must be an int, got {top_k!r}")
+    k = int(top_k)
+    if k < 0 or (n_classes is not None and k > n_classes):
+        raise ValueError(f"top_k must be 0 (off) or 1..{n_classes}, got {k}")
+    tau = C.c_float(tau).value
+    if tau == 1.0 and k == 0:
+        return None
+    return Sampling(tau, k)
+
+
 class ScheduleC(C.Structure):
     _fields_ = [("timesteps", C.c_int32), ("d", C.POINTER(C.c_uint16)), ("c", C.POINTER(C.c_uint16)),
                 ("dbar", C.POINTER(C.c_uint16)), ("cbar", C.POINTER(C.c_uint16))]
@@ -150,6 +176,13 @@ SIGNATURES = {
                                               C.POINTER(Canvas), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                               C.c_void_p, C.c_void_p]),
+    "d3pm_posterior_sample_sampling": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32,
+                                                 C.c_void_p, C.POINTER(Sampling), C.c_void_p]),
+    "d3pm_sample_loop_sampling": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.POINTER(Canvas), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                            C.c_void_p, C.POINTER(Sampling), C.c_void_p]),
     "d3pm_q_sample": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                 C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_void_p]),
     "d3pm_denoise_step_fp8": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -577,9 +610,11 @@ class Sampler:
     def _lvl(self):
         return () if self.n_q == 1 else (self.n_q,)
 
-    def posterior_sample(self, logits, x_t, t, seed, utt0=0, flags=0, want_posterior=False, known=None):
-        """known: uint8 [B, canvas] or None -- frames that keep x_t instead of being drawn (d3pm_posterior_sample_known)."""
+    def posterior_sample(self, logits, x_t, t, seed, utt0=0, flags=0, want_posterior=False, known=None, temperature=1.0, top_k=0):
+        """known: uint8 [B, canvas] or None -- frames that keep x_t instead of being drawn (d3pm_posterior_sample_known).
+        temperature / top_k: d3pm_sampling (d3pm_posterior_sample_sampling); the neutral pair takes the entries without them."""
         cfg = self.cfg
+        smp = sampling_options(temperature, top_k, cfg.n_classes)
         B = self._check_grid(x_t)
         if known is not None:
             _require(known, "known", (B, cfg.canvas), (torch.uint8,), self.device)
@@ -587,6 +622,11 @@ class Sampler:
         _require(logits, "logits", (B, cfg.canvas) + self._lvl() + (cfg.n_classes,), tuple(_DTYPES), self.device)
         x_next = torch.empty_like(x_t)
         post = torch.empty((B, cfg.canvas) + self._lvl() + (cfg.n_classes,), dtype=torch.int16, device=self.device) if want_posterior else None
+        if smp is not None:
+            check(lib().d3pm_posterior_sample_sampling(C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), _p(x_t),
+                                                       _p(x_next), _p(known), int(t), C.byref(self.schedule.c_struct), seed, utt0,
+                                                       flags, _p(post), C.byref(smp), stream_ptr()), "d3pm_posterior_sample_sampling")
+            return x_next, post
         if known is not None:
             check(lib().d3pm_posterior_sample_known(C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), _p(x_t),
                                                     _p(x_next), _p(known), int(t), C.byref(self.schedule.c_struct), seed, utt0,
@@ -611,16 +651,26 @@ class Sampler:
         return x_next
 
     def sample_loop(self, x, frame_mask, t_start, t_stop, kv_t, kv_p, seed, utt0=0, flags=0, trace=False, slot=0,
-                    fp8=False, known=None):
+                    fp8=False, known=None, temperature=1.0, top_k=0):
         """frame_mask uint8 [canvas] (shared by the batch) runs d3pm_sample_loop(_fp8); a per-utterance mask [B, canvas] and / or a
-        known-frame map `known` (uint8 [B, canvas]; `x` already carries the given ids) run the *_canvas entries."""
+        known-frame map `known` (uint8 [B, canvas]; `x` already carries the given ids) run the *_canvas entries.  temperature /
+        top_k other than the neutral (1, 0) run d3pm_sample_loop_sampling, which covers the four of them."""
         cfg = self.cfg
+        smp = sampling_options(temperature, top_k, cfg.n_classes)
         per_utt = known is not None or (isinstance(frame_mask, torch.Tensor) and frame_mask.dim() == 2)
         B = self._check_grid(x, None if per_utt else frame_mask, "x")
         cv = self._check_canvas(B, frame_mask, known) if per_utt else None
         self._check_kv(kv_t, kv_p, B)
         ws = self.workspace(B, slot)
         tr = torch.empty((t_start - t_stop, B, cfg.canvas) + self._lvl(), dtype=torch.int32, device=self.device) if trace else None
+        if smp is not None:
+            check(lib().d3pm_sample_loop_sampling(C.byref(self.shape), C.byref(self.weights.c_struct),
+                                                  C.cast(self.fp8_weights().blocks, C.c_void_p) if fp8 else None, B, _p(x),
+                                                  None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None,
+                                                  int(t_start), int(t_stop), _p(self.film), _p(kv_t), _p(kv_p),
+                                                  C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
+                                                  C.byref(smp), stream_ptr()), "d3pm_sample_loop_sampling")
+            return tr
         if per_utt and fp8:
             check(lib().d3pm_sample_loop_fp8_canvas(C.byref(self.shape), C.byref(self.weights.c_struct),
                                                     C.cast(self.fp8_weights().blocks, C.c_void_p), B, _p(x), C.byref(cv),

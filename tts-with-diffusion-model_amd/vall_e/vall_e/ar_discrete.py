@@ -335,7 +335,7 @@ class AR(SymmapState, nn.Module):
                        utt0: int = 0, return_trace: bool = False, flags: int = 0, streams: Optional[int] = None,
                        graph: Optional[bool] = None, fp8: bool = False, global_batch: Optional[int] = None,
                        known: Optional[Sequence[Optional[Tensor]]] = None,
-                       known_mask: Optional[Sequence[Optional[Tensor]]] = None):
+                       known_mask: Optional[Sequence[Optional[Tensor]]] = None, temperature: float = 1.0, top_k: int = 0):
         """Reverse diffusion for len(text_list) utterances.  Positional behaviour as upstream:
         one utterance -> int64 [canvas] (squeezed, untrimmed; rows >= n_frames are sampled from
         final.bias and meaningless); with n_q > 1 (constructor) [canvas, n_q] / [B, canvas, n_q].  `resps_list` is ignored, as
@@ -353,12 +353,25 @@ class AR(SymmapState, nn.Module):
         chunks below do too).  The attention kernels come in two instruction shapes that are picked by batch size and accumulate
         in different orders; with the global batch given, a shard takes the kernels of the unsplit batch, so the ids of an
         utterance do not depend on how the batch was split (d3pm_tuning.regime_batch).
+        `temperature` (finite, > 0) and `top_k` (0 = off, else 1 .. 1025) shape how sharply every reverse step draws
+        (include/d3pm_hip.h: d3pm_sampling): each row's x0-logits become rn16(rn16(l) / temperature), everything below the top_k-th
+        largest of them (ties kept) becomes -inf, and the posterior draw runs on that -- inside the sampler launch, with the noise
+        every class would have had anyway; the same ids as filtering the logits on the host between d3pm_denoise_step and
+        d3pm_posterior_sample.  All 1025 classes take part alike; with n_q > 1 every level's logits are filtered on their own.  They
+        compose with greedy, n_frames, known frames, fp8, utt0 / global_batch and stream chunks; the defaults (1, 0) run the loop
+        that knows nothing of them.  Bad values are a ValueError before any GPU work.  The NAR stage keeps its own
+        `sampling_temperature`.
         `graph=True` replays the loop from a captured HIP graph (seed read from HBM, identical results).  Off by
         default: measured on MI355X one utterance takes 66.6 ms replayed and 66.3 ms launched eagerly -- the ~5000
-        kernels of a reverse process are bound by their own ~10 us latency at M = 768 rows, not by launch overhead."""
+        kernels of a reverse process are bound by their own ~10 us latency at M = 768 rows, not by launch overhead.  The graph cache is keyed on batch, step range, utt0 and flags, not on sampling options:
+        `graph=True` with a temperature / top_k other than (1, 0) raises ValueError, like the per-utterance arguments."""
         if len(text_list) != len(proms_list) or len(text_list) == 0:
             raise ValueError("text_list and proms_list must be non-empty and of equal length")
         B = len(text_list)
+        filtered = _hip.sampling_options(temperature, top_k, N_CLASSES) is not None      # host validation before any GPU work
+        if filtered and graph:
+            raise ValueError("graph=True replays a loop captured per (batch, step range, utt0, flags): temperature / top_k run on the "
+                             "eager loop only")
         per_utt = known is not None or known_mask is not None or not (n_frames is None or isinstance(n_frames, Integral))
         if per_utt:
             if graph:
@@ -388,7 +401,8 @@ class AR(SymmapState, nn.Module):
                 smp.sample_loop_graphed(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl)
             elif n_streams == 1 or return_trace:
                 kv_t, kv_p = smp.cond_kv(cond_text, cond_prompt)
-                trace = smp.sample_loop(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl, trace=return_trace, fp8=fp8, known=kmap)
+                trace = smp.sample_loop(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl, trace=return_trace, fp8=fp8, known=kmap,
+                                        temperature=temperature, top_k=top_k)
             else:
                 # utterances are independent: chunks of the batch run the whole loop on their own stream so that
                 # the short kernels of one chunk fill the ramp-up / epilogue bubbles of the others
@@ -404,7 +418,7 @@ class AR(SymmapState, nn.Module):
                     with torch.cuda.stream(st):
                         kv_t, kv_p = smp.cond_kv(cond_text[lo:hi], cond_prompt[lo:hi])
                         smp.sample_loop(x[lo:hi], frame_mask[lo:hi] if per_utt else frame_mask, t_start, 0, kv_t, kv_p, seed, utt0 + lo, fl,
-                                        slot=i, known=None if kmap is None else kmap[lo:hi])
+                                        slot=i, known=None if kmap is None else kmap[lo:hi], temperature=temperature, top_k=top_k)
                         for t_ in (kv_t, kv_p, cond_text, cond_prompt, x):
                             t_.record_stream(st)
                 for i in range(n_streams):
@@ -415,11 +429,15 @@ class AR(SymmapState, nn.Module):
 
     # ------------------------------------------------------------------ upstream method names
     @torch.no_grad()
-    def p_sample(self, model_logits: Tensor, t: Tensor, x: Tensor, *, seed: int = 0, utt0: int = 0):
+    def p_sample(self, model_logits: Tensor, t: Tensor, x: Tensor, *, seed: int = 0, utt0: int = 0, temperature: float = 1.0,
+                 top_k: int = 0):
         """One reverse transition from x0-logits [B,T,K] at step t[0] (ar_discrete.py:401-420).
-        Returns (sample int64 [B,T], softmax(logits)) like upstream."""
+        Returns (sample int64 [B,T], softmax(logits)) like upstream (the softmax of the logits as given: `temperature` / `top_k`,
+        as in generate_audio, act on the draw only).  Bad values are a ValueError before any GPU work."""
+        _hip.sampling_options(temperature, top_k, N_CLASSES)
         smp = self.sampler()
-        x_next, _ = smp.posterior_sample(model_logits, x.to(torch.int32).contiguous(), int(t.reshape(-1)[0]), seed, utt0)
+        x_next, _ = smp.posterior_sample(model_logits, x.to(torch.int32).contiguous(), int(t.reshape(-1)[0]), seed, utt0,
+                                         temperature=temperature, top_k=top_k)
         return x_next.long(), F.softmax(model_logits, dim=-1)
 
     @torch.no_grad()
