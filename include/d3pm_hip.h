@@ -53,7 +53,8 @@ extern "C" {
  *    later additions only: the condition encoders' training-step dropout (d3pm_op_dropout_f32, d3pm_op_attention_dropout_f32,
  *    d3pm_op_attention_bwd_dropout_f32); per-utterance canvases (d3pm_canvas, d3pm_denoise_step_canvas,
  *    d3pm_posterior_sample_known, d3pm_sample_loop_canvas, d3pm_sample_loop_fp8_canvas); temperature / top-k on the x0-logits
- *    (d3pm_sampling, d3pm_posterior_sample_sampling, d3pm_sample_loop_sampling) */
+ *    (d3pm_sampling, d3pm_posterior_sample_sampling, d3pm_sample_loop_sampling); the nucleus (top-p) cut behind them
+ *    (d3pm_nucleus, d3pm_posterior_sample_nucleus, d3pm_sample_loop_nucleus) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -432,6 +433,57 @@ int d3pm_sample_loop_sampling(const d3pm_shape *shape, const d3pm_weights *weigh
                               const void *kv_prompt, const d3pm_schedule *sched, uint64_t seed, uint32_t utt0,
                               uint32_t flags, void *workspace, size_t workspace_bytes, int32_t *trace,
                               const d3pm_sampling *sampling, void *stream);
+
+/* Nucleus (top-p) cut on the x0-logits ------------------------------------------------------------------
+ * One more number per call, `top_p`: "draw from the smallest set of classes that carries this share of the mass", per row and per
+ * step (the reference has no such option).  It acts on a row's z'' -- the logits after temperature and top-k as defined above --
+ * and, with n_q > 1, on each level's n_classes logits on their own:
+ *     m       = max_j z''_j
+ *     e_j     = expf(z''_j - m)                  the value the sampler computes for its softmax anyway (-inf -> 0)
+ *     q_j     = (uint32) (e_j * 1048576.0f)      truncated; q of the maximum is 2^20; the sum over <= 1280 classes is < 2^31
+ *     Q       = sum_j q_j                        an integer: the same whatever order lanes and waves add in
+ *     mass(c) = sum_{key(z''_j) >= c} q_j        key = the 16-bit order key of the fp16 value (unsigned order = order of the values)
+ *     theta   = value of the LARGEST key c with (double) mass(c) >= (double) top_p * (double) Q
+ *     z'''_j  = z''_j >= theta ? z''_j : -inf    ties at theta are all kept; compared on VALUES, so -0 / +0 stand or fall together
+ *     x_{t-1} = the unfiltered routine on z'''
+ * i.e. a call equals the unfiltered entry fed with the host-filtered z'' cut at theta, id for id.  What follows from it:
+ *   - mass is monotone in c, so the key of theta is built bit by bit from the top (16 rounds), exactly like the top-k one;
+ *   - the largest such key is the key of a class of the row with q > 0: theta is one of the row's values;
+ *   - the maximum is always kept; m and the e_j of the kept classes are unchanged, so the ids do not depend on whether the routine
+ *     computes them again or reuses them;
+ *   - Q <= n_classes * 2^20 and n_classes <= 1280: any top_p <= 1/1280 keeps exactly the classes tied at the maximum, which gives
+ *     the ids of top_k = 1;
+ *   - for every set S of classes |sum_S q / Q - sum_S softmax(z'')| <= n_classes / 2^20 + 2^-20 (<= 1.0e-3 at 1025 classes:
+ *     truncation of less than one unit per class, Q >= 2^20, expf to within a few ulp).  This is the only slack in the contract: it
+ *     bounds how far the kept mass may sit from top_p.  It bounds no id;
+ *   - noise, D3PM_FLAG_GREEDY, t = 0, known frames, per-utterance masks, utt0 / regime_batch, the fp8 loop compose with top_p exactly
+ *     as they do with top_k: a class that is cut carries p = 0 into the same arithmetic, and its uniform is still drawn;
+ *   - a row whose logits are all -inf is outside the contract, as it is for the entries above.
+ *   temperature, top_k  as in d3pm_sampling        top_p  finite, 0 < top_p <= 1; 1 = off      (anything else: D3PM_E_ARG, nothing launched)
+ * A NULL d3pm_nucleus, or {1.0f, 0, 1.0f}, is bit-identical to the entry that is generalised and launches the very same kernels;
+ * {temperature, top_k, 1.0f} is d3pm_sampling{temperature, top_k} and launches what that launches; top_p < 1 takes the kernels'
+ * nucleus arm (kernels of their own: a call without top_p runs none of its code). */
+typedef struct d3pm_nucleus {
+  float temperature;
+  int32_t top_k;
+  float top_p;
+} d3pm_nucleus;
+
+/* d3pm_posterior_sample_sampling with the triple.  theta_out: optional device float [batch][canvas] ([batch][canvas][n_q] with
+ * n_q > 1), NULL = not wanted: the wave that filtered a row writes the row's theta there (top_p = 1: -inf, nothing is cut); a known
+ * row writes NaN.  A non-NULL theta_out takes the nucleus arm whatever top_p is; the ids are those of the same call without it. */
+int d3pm_posterior_sample_nucleus(const d3pm_shape *shape, int batch, const void *logits, int logits_dtype,
+                                  const int32_t *x_t, int32_t *x_next, const uint8_t *known, int t,
+                                  const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags,
+                                  uint16_t *posterior_out, const d3pm_nucleus *nucleus, float *theta_out, void *stream);
+
+/* d3pm_sample_loop_sampling with the triple; every other argument as there. */
+int d3pm_sample_loop_nucleus(const d3pm_shape *shape, const d3pm_weights *weights,
+                             const d3pm_fp8_block_weights *fp8_blocks, int batch, int32_t *x, const uint8_t *frame_mask,
+                             const d3pm_canvas *canvas, int t_start, int t_stop, const void *film, const void *kv_text,
+                             const void *kv_prompt, const d3pm_schedule *sched, uint64_t seed, uint32_t utt0,
+                             uint32_t flags, void *workspace, size_t workspace_bytes, int32_t *trace,
+                             const d3pm_nucleus *nucleus, void *stream);
 
 /* Replaces AR.q_sample / q_probs (ar_discrete.py:467-502): forward noising of x0 at step t with
  * Philox stream 1.  x0, x_out device int32 [batch][canvas]. */

@@ -919,21 +919,31 @@ int d3pm_denoise_step_fp8(const d3pm_shape* sh, const d3pm_weights* w, const d3p
                            hidden_out, only_layers, flags, stream, fp8_blocks);
 }
 
-// d3pm_sampling of the *_sampling entries: NULL = the neutral pair.  Refused before anything is launched.
-static int check_sampling(const d3pm_shape* sh, const d3pm_sampling* sm, const char* who) {
+// d3pm_nucleus of the *_nucleus entries (the *_sampling entries forward their pair with top_p = 1): NULL = the neutral triple.
+// Refused before anything is launched.
+static int check_sampling(const d3pm_shape* sh, const d3pm_nucleus* sm, const char* who) {
   if (!sm) return D3PM_OK;
   D3PM_REQUIRE(std::isfinite(sm->temperature) && sm->temperature > 0.f, D3PM_E_ARG, "%s: temperature %g is not a finite number > 0", who,
                static_cast<double>(sm->temperature));
   D3PM_REQUIRE(sm->top_k >= 0 && sm->top_k <= sh->n_classes, D3PM_E_ARG, "%s: top_k %d outside 0 (off) .. %d (n_classes)", who, sm->top_k,
                sh->n_classes);
+  D3PM_REQUIRE(std::isfinite(sm->top_p) && sm->top_p > 0.f && sm->top_p <= 1.f, D3PM_E_ARG, "%s: top_p %g outside (0, 1] (1 = off)", who,
+               static_cast<double>(sm->top_p));
   return D3PM_OK;
+}
+// the pair of a *_sampling entry as a triple (`out` lives in the caller)
+static const d3pm_nucleus* with_top_p_off(const d3pm_sampling* sm, d3pm_nucleus* out) {
+  if (!sm) return nullptr;
+  *out = d3pm_nucleus{sm->temperature, sm->top_k, 1.0f};
+  return out;
 }
 
 static int posterior_sample_impl(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
                                  int32_t* x_next, const uint8_t* known, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
-                                 uint32_t flags, uint16_t* posterior_out, void* stream, const d3pm_sampling* sm = nullptr) {
+                                 uint32_t flags, uint16_t* posterior_out, void* stream, const d3pm_nucleus* sm = nullptr,
+                                 float* theta_out = nullptr, const char* who = "d3pm_posterior_sample_sampling") {
   D3PM_TRY(check_shape(sh, batch));
-  D3PM_TRY(check_sampling(sh, sm, "d3pm_posterior_sample_sampling"));
+  D3PM_TRY(check_sampling(sh, sm, who));
   D3PM_REQUIRE(logits && x_t && x_next && sched && sched->d && sched->c && sched->dbar && sched->cbar, D3PM_E_ARG,
                "d3pm_posterior_sample: null pointer");
   D3PM_REQUIRE(t >= 0 && t < sched->timesteps, D3PM_E_ARG, "t=%d outside the schedule", t);
@@ -944,7 +954,8 @@ static int posterior_sample_impl(const d3pm_shape* sh, int batch, const void* lo
   a.canvas = sh->canvas; a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas);
   a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0; a.pc = make_posterior_consts(sched, t);
   a.known = known;
-  if (sm) { a.temperature = sm->temperature; a.top_k = sm->top_k; }
+  if (sm) { a.temperature = sm->temperature; a.top_k = sm->top_k; a.top_p = sm->top_p; }
+  a.theta_out = theta_out;
   return posterior_sample(a, static_cast<hipStream_t>(stream));
 }
 
@@ -963,16 +974,25 @@ int d3pm_posterior_sample_known(const d3pm_shape* sh, int batch, const void* log
 int d3pm_posterior_sample_sampling(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
                                    int32_t* x_next, const uint8_t* known, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
                                    uint32_t flags, uint16_t* posterior_out, const d3pm_sampling* sampling, void* stream) {
-  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, known, t, sched, seed, utt0, flags, posterior_out, stream, sampling);
+  d3pm_nucleus nu;
+  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, known, t, sched, seed, utt0, flags, posterior_out, stream,
+                               with_top_p_off(sampling, &nu));
+}
+
+int d3pm_posterior_sample_nucleus(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
+                                  int32_t* x_next, const uint8_t* known, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                                  uint32_t flags, uint16_t* posterior_out, const d3pm_nucleus* nucleus, float* theta_out, void* stream) {
+  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, known, t, sched, seed, utt0, flags, posterior_out, stream, nucleus,
+                               theta_out, "d3pm_posterior_sample_nucleus");
 }
 
 static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const CanvasMask& cm,
                             int t_start, int t_stop, const void* film, const void* kv_text, const void* kv_prompt,
                             const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace,
                             size_t workspace_bytes, int32_t* trace, void* stream, const d3pm_fp8_block_weights* f8,
-                            const d3pm_sampling* sm = nullptr) {
+                            const d3pm_nucleus* sm = nullptr, const char* who = "d3pm_sample_loop_sampling") {
   D3PM_TRY(check_shape(sh, batch));
-  D3PM_TRY(check_sampling(sh, sm, "d3pm_sample_loop_sampling"));
+  D3PM_TRY(check_sampling(sh, sm, who));
   D3PM_REQUIRE(w && w->blocks && x && cm.frame_mask && film && kv_text && kv_prompt && sched && workspace, D3PM_E_ARG,
                "d3pm_sample_loop: null pointer");
   D3PM_REQUIRE(t_start < sched->timesteps && t_start <= sh->timesteps && t_stop >= 0 && t_stop <= t_start, D3PM_E_ARG,
@@ -997,9 +1017,9 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     a.row0 = utt0 * static_cast<uint32_t>(sh->canvas); a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0;
     a.pc = make_posterior_consts(sched, t);
     a.known = cm.known;
-    if (sm) { a.temperature = sm->temperature; a.top_k = sm->top_k; }
+    if (sm) { a.temperature = sm->temperature; a.top_k = sm->top_k; a.top_p = sm->top_p; }
 #ifdef D3PM_ABLATIONS
-    if (!cm.known && !a.filtered() && fused_final_sample_applies(*sh, *w, ws, flags)) {
+    if (!cm.known && !a.filtered() && !a.nucleus() && fused_final_sample_applies(*sh, *w, ws, flags)) {
       // final projection + posterior + draw in one kernel: the logits stay on chip (d3pm_final_sample.hip)
       ProfScope p(cx, D3PM_K_SAMPLE, s, 2.0 * rows * sh->n_classes * sh->d_model,
                   dtype_size(sh->dtype) * (static_cast<double>(rows) * sh->d_model + static_cast<double>(sh->n_classes) * sh->d_model) + 8.0 * rows);
@@ -1073,8 +1093,22 @@ int d3pm_sample_loop_sampling(const d3pm_shape* sh, const d3pm_weights* w, const
                               void* stream) {
   D3PM_REQUIRE(sh && (frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
                "d3pm_sample_loop_sampling: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)");
+  d3pm_nucleus nu;
   return sample_loop_impl(sh, w, batch, x, canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask), t_start, t_stop,
-                          film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks, sampling);
+                          film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks,
+                          with_top_p_off(sampling, &nu));
+}
+
+int d3pm_sample_loop_nucleus(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch, int32_t* x,
+                             const uint8_t* frame_mask, const d3pm_canvas* canvas, int t_start, int t_stop, const void* film,
+                             const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                             uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus,
+                             void* stream) {
+  D3PM_REQUIRE(sh && (frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
+               "d3pm_sample_loop_nucleus: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)");
+  return sample_loop_impl(sh, w, batch, x, canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask), t_start, t_stop,
+                          film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks, nucleus,
+                          "d3pm_sample_loop_nucleus");
 }
 
 int d3pm_q_sample(const d3pm_shape* sh, int batch, const int32_t* x0, int32_t* x_out, const uint8_t* frame_mask, int t,

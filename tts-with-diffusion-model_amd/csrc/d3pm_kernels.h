@@ -149,6 +149,10 @@ struct SampleArgs {
   // -inf (0 = no cut).  The neutral pair launches the kernels without the filter arm.
   float temperature = 1.0f; int top_k = 0;
   bool filtered() const { return temperature != 1.0f || top_k != 0; }
+  // d3pm_nucleus: behind them, everything below the nucleus threshold theta of z'' becomes -inf (top_p 1 = no cut); theta_out is the
+  // step entry's optional device float [rows] (theta per row, NaN for a known row).  Either one takes the kernels' nucleus arm.
+  float top_p = 1.0f; float* theta_out = nullptr;
+  bool nucleus() const { return top_p < 1.0f || theta_out != nullptr; }
   PosteriorConsts pc{};
 };
 

@@ -36,13 +36,15 @@ __device__ __forceinline__ bool row_is_known(const uint8_t* __restrict__ known, 
 // Philox draw (the noise of every other row is keyed by its own global row and does not move) -- and takes the same stores.
 // kKnown = false is the kernel without the map: `known` is never read.
 // kFilter (temperature / top-k, d3pm_sample_row.h): a compile-time arm like kKnown.  The kernels without it keep their names, their
-// arguments and their code; the *_filtered kernels below carry the two numbers as one more argument.
-template <typename T, bool kKnown, bool kFilter>
+// arguments and their code; the *_filtered kernels below carry the two numbers as one more argument.  kFilter == kNucleusArm
+// (top-p behind them, d3pm_nucleus) is a third arm with kernels of its own (nucleus_sample_*), so that a call without top_p launches
+// the kernels it launched before there was one; `theta_out` [rows] is that arm's optional output (a known row: NaN).
+template <typename T, bool kKnown, int kFilter>
 __device__ __forceinline__ void posterior_sample_rows_body(
     const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next,
     int32_t* x_next2, uint16_t* __restrict__ post_out, int rows, int K, int mask_id,
     uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, const PosteriorConsts& pc, int n_q,
-    const uint8_t* __restrict__ known, const RowFilter& flt) {
+    const uint8_t* __restrict__ known, const RowFilter& flt, const RowNucleus& nuc = RowNucleus{}) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x >> 6) + wave;
   if (row >= rows) return;
@@ -52,10 +54,13 @@ __device__ __forceinline__ void posterior_sample_rows_body(
         const int keep = x_t[row];
         x_next[row] = keep;
         if (x_next2) x_next2[row] = keep;
+        if constexpr (kFilter == kNucleusArm)
+          if (nuc.theta_out) nuc.theta_out[row] = __builtin_nanf("");
       }
       return;
     }
   }
+  const RowNucleus row_nuc{nuc.top_p, nuc.theta_out ? nuc.theta_out + row : nullptr};      // (never read outside the nucleus arm)
   if (seed_hbm) seed = *seed_hbm;
   // n_q > 1 (d3pm_shape.n_q): row = frame row * n_q + level; the level-0 token of a frame draws the noise the level-0-only
   // path draws, level l > 0 draws from Philox stream 16 + l at the same (frame row, t)
@@ -64,10 +69,10 @@ __device__ __forceinline__ void posterior_sample_rows_body(
   int best_j;
   if (K == 1025 && mask_id < 1024 && !post_out)        // kernel-uniform: the predicate-free routine for the reference's class count (same bits)
     best_j = sample_row_1025<T, kFilter>(logits + static_cast<size_t>(row) * ldl, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(frow), greedy, pc, lane, strm,
-                                         D3PM_SAMPLER_EARLY_OUT != 0, flt);
+                                         D3PM_SAMPLER_EARLY_OUT != 0, flt, row_nuc);
   else
     best_j = sample_row<T, kFilter>(logits + static_cast<size_t>(row) * ldl, K, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(frow), greedy, pc,
-                                    post_out ? post_out + static_cast<size_t>(row) * K : nullptr, lane, strm, flt);
+                                    post_out ? post_out + static_cast<size_t>(row) * K : nullptr, lane, strm, flt, row_nuc);
   if (lane == 0) {
     x_next[row] = best_j;
     if (x_next2) x_next2[row] = best_j;
@@ -80,7 +85,7 @@ __global__ __launch_bounds__(256) void posterior_sample_rows(
     int32_t* x_next2, uint16_t* __restrict__ post_out, int rows, int K, int mask_id,
     uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int n_q,
     const uint8_t* __restrict__ known) {
-  posterior_sample_rows_body<T, kKnown, false>(logits, ldl, x_t, x_next, x_next2, post_out, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, n_q,
+  posterior_sample_rows_body<T, kKnown, 0>(logits, ldl, x_t, x_next, x_next2, post_out, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, n_q,
                                                known, RowFilter{});
 }
 
@@ -90,8 +95,18 @@ __global__ __launch_bounds__(256) void posterior_sample_rows_filtered(
     int32_t* x_next2, uint16_t* __restrict__ post_out, int rows, int K, int mask_id,
     uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int n_q,
     const uint8_t* __restrict__ known, RowFilter flt) {
-  posterior_sample_rows_body<T, kKnown, true>(logits, ldl, x_t, x_next, x_next2, post_out, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, n_q,
-                                              known, flt);
+  posterior_sample_rows_body<T, kKnown, kFilterArm>(logits, ldl, x_t, x_next, x_next2, post_out, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc,
+                                                    n_q, known, flt);
+}
+
+template <typename T, bool kKnown>
+__global__ __launch_bounds__(256) void nucleus_sample_rows(
+    const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next,
+    int32_t* x_next2, uint16_t* __restrict__ post_out, int rows, int K, int mask_id,
+    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int n_q,
+    const uint8_t* __restrict__ known, RowFilter flt, RowNucleus nuc) {
+  posterior_sample_rows_body<T, kKnown, kNucleusArm>(logits, ldl, x_t, x_next, x_next2, post_out, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc,
+                                                     n_q, known, flt, nuc);
 }
 
 // The sampler of iteration t and the preparation of iteration t - 1 in one launch (NextIterPrep, d3pm_kernels.h): workgroups
@@ -101,13 +116,13 @@ __global__ __launch_bounds__(256) void posterior_sample_rows_filtered(
 // utterance 12.4 + 8.7 + 5.0 us of launches become ~13, at 32 utterances 94 + 10.8 + 10.5 become ~97.
 // kKnown as in posterior_sample_rows: a known row takes best_j = x_t[row] and goes through the same stores and the same gather, so
 // the next iteration's residual row and moments are written exactly as for a drawn id.
-template <typename T, bool kKnown, bool kFilter>
+template <typename T, bool kKnown, int kFilter>
 __device__ __forceinline__ void posterior_sample_prep_rows_body(
     const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next, int32_t* x_next2, int rows, int K, int mask_id,
     uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, const PosteriorConsts& pc, int mask_period, int sample_blocks,
     const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
     bool quads, const FoldStepPtrs& fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
-    const uint8_t* __restrict__ known, const RowFilter& flt) {
+    const uint8_t* __restrict__ known, const RowFilter& flt, const RowNucleus& nuc = RowNucleus{}) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (static_cast<int>(blockIdx.x) >= sample_blocks) {
     const int r = (blockIdx.x - sample_blocks) * 4 + wave;
@@ -125,8 +140,9 @@ __device__ __forceinline__ void posterior_sample_prep_rows_body(
   else
     best_j = (K == 1025 && mask_id < 1024)
         ? sample_row_1025<T, kFilter>(logits + static_cast<size_t>(row) * ldl, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, lane, 0u,
-                                      D3PM_SAMPLER_EARLY_OUT != 0, flt)
-        : sample_row<T, kFilter>(logits + static_cast<size_t>(row) * ldl, K, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, nullptr, lane, 0u, flt);
+                                      D3PM_SAMPLER_EARLY_OUT != 0, flt, nuc)
+        : sample_row<T, kFilter>(logits + static_cast<size_t>(row) * ldl, K, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, nullptr, lane, 0u, flt,
+                                 nuc);
   if (lane == 0) {
     x_next[row] = best_j;
     if (x_next2) x_next2[row] = best_j;
@@ -141,7 +157,7 @@ __global__ __launch_bounds__(256) void posterior_sample_prep_rows(
     const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
     bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
     const uint8_t* __restrict__ known) {
-  posterior_sample_prep_rows_body<T, kKnown, false>(logits, ldl, x_t, x_next, x_next2, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, mask_period,
+  posterior_sample_prep_rows_body<T, kKnown, 0>(logits, ldl, x_t, x_next, x_next2, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, mask_period,
                                                     sample_blocks, table, xres, stats, frame_mask, d, quads, fp, film_t, n_layers, Wf, s_out, b_out, known,
                                                     RowFilter{});
 }
@@ -153,9 +169,22 @@ __global__ __launch_bounds__(256) void posterior_sample_prep_rows_filtered(
     const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
     bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
     const uint8_t* __restrict__ known, RowFilter flt) {
-  posterior_sample_prep_rows_body<T, kKnown, true>(logits, ldl, x_t, x_next, x_next2, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, mask_period,
-                                                   sample_blocks, table, xres, stats, frame_mask, d, quads, fp, film_t, n_layers, Wf, s_out, b_out, known,
-                                                   flt);
+  posterior_sample_prep_rows_body<T, kKnown, kFilterArm>(logits, ldl, x_t, x_next, x_next2, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, mask_period,
+                                                         sample_blocks, table, xres, stats, frame_mask, d, quads, fp, film_t, n_layers, Wf, s_out, b_out,
+                                                         known, flt);
+}
+
+// the loop's launch with top_p: no theta output (the loop has none), so `top_p` travels alone
+template <typename T, bool kKnown>
+__global__ __launch_bounds__(256) void nucleus_sample_prep_rows(
+    const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next, int32_t* x_next2, int rows, int K, int mask_id,
+    uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int mask_period, int sample_blocks,
+    const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
+    bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
+    const uint8_t* __restrict__ known, RowFilter flt, float top_p) {
+  posterior_sample_prep_rows_body<T, kKnown, kNucleusArm>(logits, ldl, x_t, x_next, x_next2, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, mask_period,
+                                                          sample_blocks, table, xres, stats, frame_mask, d, quads, fp, film_t, n_layers, Wf, s_out, b_out,
+                                                          known, flt, RowNucleus{top_p, nullptr});
 }
 
 // forward noising: logits are log16(rn16(row_of_Qbar_t + eps)) with at most three distinct values
@@ -213,13 +242,16 @@ int posterior_sample(const SampleArgs& a, hipStream_t s) {
   const int rpb = 4;
   dim3 grid((a.rows + rpb - 1) / rpb), block(rpb * kWave);
   const RowFilter flt{a.temperature, a.top_k};
-  // no map: the kernel without the known-row arm; neutral sampling options: the kernel without the filter arm
+  const RowNucleus nuc{a.top_p, a.theta_out};
+  // no map: the kernel without the known-row arm; neutral sampling options: the kernel without the filter arm; top_p (or a theta
+  // output): the nucleus arm
 #define D3PM_PS_ARGS(T)                                                                                                          \
   static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next, a.x_next2, a.posterior_out, a.rows, a.n_classes, a.mask_id, a.seed, \
       a.seed_hbm, a.row0, a.greedy, a.pc, a.n_q, a.known
 #define D3PM_PS_ARM(T, kKnown)                                                                            \
   do {                                                                                                    \
-    if (a.filtered()) posterior_sample_rows_filtered<T, kKnown><<<grid, block, 0, s>>>(D3PM_PS_ARGS(T), flt); \
+    if (a.nucleus()) nucleus_sample_rows<T, kKnown><<<grid, block, 0, s>>>(D3PM_PS_ARGS(T), flt, nuc);         \
+    else if (a.filtered()) posterior_sample_rows_filtered<T, kKnown><<<grid, block, 0, s>>>(D3PM_PS_ARGS(T), flt); \
     else posterior_sample_rows<T, kKnown><<<grid, block, 0, s>>>(D3PM_PS_ARGS(T));                           \
   } while (0)
 #define D3PM_PS(T)                    \
@@ -241,7 +273,7 @@ int posterior_sample(const SampleArgs& a, hipStream_t s) {
 }
 
 bool posterior_sample_prep_supported(const SampleArgs& a, const NextIterPrep& n) {
-  return a.n_q == 1 && !a.posterior_out && a.logits_dtype == n.dtype && (n.dtype == D3PM_F16 || n.dtype == D3PM_BF16) && n.n_layers <= 16 &&
+  return a.n_q == 1 && !a.posterior_out && !a.theta_out && a.logits_dtype == n.dtype && (n.dtype == D3PM_F16 || n.dtype == D3PM_BF16) && n.n_layers <= 16 &&
          n.d % 256 == 0 && (!n.quads || n.d == 512) && a.n_classes <= kWave * kMaxGroupsPerLane * 4 && n.table && n.x && n.stats && n.frame_mask && n.mask_period > 0 && n.blocks && n.film_t && n.Wf;
 }
 
@@ -259,7 +291,8 @@ int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_
       static_cast<const T*>(n.film_t), n.n_layers, static_cast<T*>(n.Wf), n.s_out, n.b_out, a.known
 #define D3PM_PSP_ARM(T, kKnown)                                                                                  \
   do {                                                                                                           \
-    if (a.filtered()) posterior_sample_prep_rows_filtered<T, kKnown><<<grid, block, 0, s>>>(D3PM_PSP_ARGS(T), flt); \
+    if (a.nucleus()) nucleus_sample_prep_rows<T, kKnown><<<grid, block, 0, s>>>(D3PM_PSP_ARGS(T), flt, a.top_p);    \
+    else if (a.filtered()) posterior_sample_prep_rows_filtered<T, kKnown><<<grid, block, 0, s>>>(D3PM_PSP_ARGS(T), flt); \
     else posterior_sample_prep_rows<T, kKnown><<<grid, block, 0, s>>>(D3PM_PSP_ARGS(T));                            \
   } while (0)
 #define D3PM_PSP(T)                     \

@@ -74,13 +74,92 @@ __device__ __forceinline__ void filter_row(float (&z)[R][4], float& zt, bool has
   }
 }
 
+// ---- nucleus (top-p) on z'' (d3pm_nucleus) ---------------------------------------------------------------
+// kFilter == kNucleusArm of the two routines below: behind filter_row, the row's z'' lose everything below the nucleus threshold,
+//     e_j = expf(z''_j - max z''),  q_j = (uint32)(e_j * 2^20) truncated,  Q = sum_j q_j,  mass(c) = sum_{key_j >= c} q_j,
+//     theta = value of the LARGEST key c with (double) mass(c) >= (double) top_p * (double) Q,   z'''_j = z''_j >= theta ? z''_j : -inf.
+// The selection is the top-k one with weights instead of counts: mass is monotone in c, so the key is built bit by bit from the
+// top; one round adds, per lane, the q of the lane's keys that are >= the candidate and sums the 64 integers over the wave (DPP and
+// permlane-swap adds: no LDS, no barrier, no atomics).  Integers: Q and every mass are the same whatever order lanes add in, so theta
+// is a function of the q_j alone.  A mass is an integer and the right-hand side one rounded fp64 product <= Q < 2^31, so
+// mass >= rhs <=> mass >= ceil(rhs): the fp64 comparison is made once per row, as an integer target.  The maximum has q = 2^20 and
+// is always kept: max z''' = max z'', and the exponentials of the kept classes are those the routine computes again behind this.
+constexpr int kFilterArm = 1, kNucleusArm = 2;      // values of the routines' kFilter (0: no filter)
+struct RowNucleus {
+  float top_p = 1.0f;            // 1 = no cut (theta = -inf)
+  float* theta_out = nullptr;    // optional: where lane 0 of the wave that filtered this row writes the row's theta
+};
+
+// wave_sum_up (d3pm_common.h) on integers: every step is v[l] + v[l ^ off], here exact in any order
+template <int CTRL> __device__ __forceinline__ uint32_t add_dpp_u32(uint32_t v) {
+  return v + static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+  v = add_dpp_u32<0xB1>(v);    // quad_perm [1, 0, 3, 2]: l ^ 1
+  v = add_dpp_u32<0x4E>(v);    // quad_perm [2, 3, 0, 1]: l ^ 2
+  v = add_dpp_u32<0x141>(v);   // row_half_mirror
+  v = add_dpp_u32<0x140>(v);   // row_mirror
+  uint32_t a = v, b = v;
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  v = a + b;
+  a = v; b = v;
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  return a + b;
+}
+
+// z, zt, has_tail, valid: as for filter_row (which has run).  Returns theta in every lane.
+template <int R, typename V>
+__device__ __forceinline__ float nucleus_row(float (&z)[R][4], float& zt, bool has_tail, V valid, float top_p) {
+  if (!(top_p < 1.0f)) return -INFINITY;      // kernel-uniform
+  float mx = zt;
+#pragma unroll
+  for (int i = 0; i < R; ++i)
+#pragma unroll
+    for (int w = 0; w < 4; ++w) mx = fmaxf(mx, z[i][w]);
+  mx = wave_max(mx);
+  uint32_t key[R][4], q[R][4];      // 0 / 0 for a slot without a class (its z is -inf: expf gives 0)
+  uint32_t part = 0u;
+#pragma unroll
+  for (int i = 0; i < R; ++i)
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      key[i][w] = valid(i, w) ? f16_order_key(z[i][w]) : 0u;
+      q[i][w] = static_cast<uint32_t>(expf(z[i][w] - mx) * 1048576.0f);
+      part += q[i][w];
+    }
+  const uint32_t kt = has_tail ? f16_order_key(zt) : 0u;
+  const uint32_t qt = static_cast<uint32_t>(expf(zt - mx) * 1048576.0f);
+  const uint32_t Q = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(wave_sum_u32(part + qt))));
+  const uint32_t target = static_cast<uint32_t>(ceil(static_cast<double>(top_p) * static_cast<double>(Q)));
+  uint32_t c = 0u;
+#pragma unroll
+  for (uint32_t bit = 0x8000u; bit; bit >>= 1) {
+    const uint32_t cand = c | bit;
+    uint32_t m = kt >= cand ? qt : 0u;
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+      for (int w = 0; w < 4; ++w) m += key[i][w] >= cand ? q[i][w] : 0u;
+    m = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(wave_sum_u32(m))));      // every lane holds the sum
+    c = m >= target ? cand : c;
+  }
+  const float theta = f16_order_value(c);
+#pragma unroll
+  for (int i = 0; i < R; ++i)
+#pragma unroll
+    for (int w = 0; w < 4; ++w) z[i][w] = z[i][w] >= theta ? z[i][w] : -INFINITY;
+  zt = zt >= theta ? zt : -INFINITY;
+  return theta;
+}
+
 // One wave draws x_{t-1} of one row.  `lr[j]` are the row's K logits in the model dtype (any address space);
 // returns the sampled id in every lane.  `post_row` (optional) receives the fp16 posterior logits of the row.
-// kFilter: the row's logits pass through filter_row first (`flt`); false = the routine without it, `flt` is never read.
-template <typename T, bool kFilter = false, typename P>
+// kFilter: kFilterArm = the row's logits pass through filter_row first (`flt`), kNucleusArm = through nucleus_row behind it as well
+// (`nuc`); 0 = the routine without either, `flt` and `nuc` are never read.
+template <typename T, int kFilter = 0, typename P>
 __device__ __forceinline__ int sample_row(P lr, int K, int mask_id, int x, uint64_t seed, uint32_t grow, int greedy,
                                           const PosteriorConsts& pc, uint16_t* post_row, int lane, uint32_t stream = 0u,
-                                          const RowFilter& flt = RowFilter{}) {
+                                          const RowFilter& flt = RowFilter{}, const RowNucleus& nuc = RowNucleus{}) {
   const int groups = (K + 3) >> 2;
   float z[kMaxGroupsPerLane][4];
   float mx = -INFINITY;
@@ -95,9 +174,14 @@ __device__ __forceinline__ int sample_row(P lr, int K, int mask_id, int x, uint6
       mx = fmaxf(mx, v);
     }
   }
-  if constexpr (kFilter) {
+  if constexpr (kFilter != 0) {
     float none = -INFINITY;
-    filter_row(z, none, false, [&](int i, int w) { const int g = lane + i * kWave; return g < groups && g * 4 + w < K; }, flt);
+    auto valid = [&](int i, int w) { const int g = lane + i * kWave; return g < groups && g * 4 + w < K; };
+    filter_row(z, none, false, valid, flt);
+    if constexpr (kFilter == kNucleusArm) {
+      const float theta = nucleus_row(z, none, false, valid, nuc.top_p);
+      if (nuc.theta_out && lane == 0) *nuc.theta_out = theta;
+    }
     mx = -INFINITY;
 #pragma unroll
     for (int i = 0; i < kMaxGroupsPerLane; ++i)
@@ -178,10 +262,10 @@ __device__ __forceinline__ int sample_row(P lr, int K, int mask_id, int x, uint6
 // kFilter as in sample_row.  The revealed-row early-out below stays exact under it: its bounds are statements about the routine's
 // inputs, and the routine's inputs are then z'' -- `sum` is the sum over the kept classes, the kept token's score is computed from
 // its own z'' (probability 0 when the filter cut it: the test then fails or holds exactly as the full routine decides).
-template <typename T, bool kFilter = false, typename P>
+template <typename T, int kFilter = 0, typename P>
 __device__ __forceinline__ int sample_row_1025(P lr, int mask_id, int x, uint64_t seed, uint32_t grow, int greedy,
                                                const PosteriorConsts& pc, int lane, uint32_t stream = 0u, bool early_out = D3PM_SAMPLER_EARLY_OUT != 0,
-                                               const RowFilter& flt = RowFilter{}) {
+                                               const RowFilter& flt = RowFilter{}, const RowNucleus& nuc = RowNucleus{}) {
   constexpr int K = 1025;
   float z[4][4], zt;
   float mx = -INFINITY;
@@ -194,8 +278,12 @@ __device__ __forceinline__ int sample_row_1025(P lr, int mask_id, int x, uint64_
     }
   zt = lane == 0 ? rn16(static_cast<float>(lr[K - 1])) : -INFINITY;
   mx = fmaxf(mx, zt);
-  if constexpr (kFilter) {
+  if constexpr (kFilter != 0) {
     filter_row(z, zt, lane == 0, [](int, int) { return true; }, flt);
+    if constexpr (kFilter == kNucleusArm) {      // paid before the early-out test below, whose `sum` is then the sum over z'''
+      const float theta = nucleus_row(z, zt, lane == 0, [](int, int) { return true; }, nuc.top_p);
+      if (nuc.theta_out && lane == 0) *nuc.theta_out = theta;
+    }
     mx = zt;
 #pragma unroll
     for (int i = 0; i < 4; ++i)

@@ -27,6 +27,8 @@ The second form takes what those front-ends write (formats.py) and writes what E
                 how sharply the D3PM stage draws: the x0-logits of every reverse step are divided by F (> 0, default 1) and cut
                 to their N largest (0 = off, the default; ties kept) before the posterior draw (AR.generate_audio); the NAR stage
                 keeps its own sampling_temperature
+  --top-p P     nucleus cut behind them (0 < P <= 1, default 1 = off): every draw keeps the smallest set of the largest x0-logits
+                that carries the share P of the softmax mass, per row and per step (include/d3pm_hip.h: d3pm_nucleus)
 """
 import argparse
 from pathlib import Path
@@ -52,13 +54,14 @@ def main(argv=None):
     ap.add_argument("--continue-from", type=Path, default=None, help=".qnt.pt whose level 0 is the known prefix of the utterance")
     ap.add_argument("--temperature", type=float, default=1.0, help="D3PM stage: divide the x0-logits by this (> 0) before every draw")
     ap.add_argument("--top-k", type=int, default=0, help="D3PM stage: draw from the N largest x0-logits only (0 = off)")
+    ap.add_argument("--top-p", type=float, default=1.0, help="D3PM stage: draw from the smallest set of classes that carries this share of the mass (1 = off)")
     ap.add_argument("--native", action="store_true", help="the shape upstream's class really builds (d=32, 16 heads, 8 blocks)")
     args = ap.parse_args(argv)
 
     from . import formats
     from .vall_e import AR, _hip, get_model
     try:
-        _hip.sampling_options(args.temperature, args.top_k, 1025)
+        _hip.nucleus_options(args.temperature, args.top_k, args.top_p, 1025)
     except ValueError as e:
         ap.error(str(e))
     if len(args.paths) not in (1, 3):
@@ -104,7 +107,7 @@ def main(argv=None):
     else:
         phns = torch.tensor([int(p) for p in args.phonemes.split()], dtype=torch.long)
     n_frames = model.cfg.n_frames if args.frames is None else args.frames
-    sampling = dict(temperature=args.temperature, top_k=args.top_k)
+    sampling = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
     if args.frames is None and args.continue_from is None:
         codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed, **sampling)
     else:

@@ -127,6 +127,26 @@ def sampling_options(temperature=1.0, top_k=0, n_classes=None):
     return Sampling(tau, k)
 
 
+class Nucleus(C.Structure):
+    """d3pm_nucleus: d3pm_sampling plus the nucleus (top-p) cut behind it (include/d3pm_hip.h)."""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float)]
+
+
+def nucleus_options(temperature=1.0, top_k=0, top_p=1.0, n_classes=None):
+    """Host validation of the three sampling options (ValueError, before any GPU work) -> None for the neutral triple (1, 0, 1), what
+    sampling_options returns when top_p == 1 (the entries and kernels that know nothing of the nucleus), a Nucleus struct otherwise."""
+    smp = sampling_options(temperature, top_k, n_classes)
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)):
+        raise ValueError(f"top_p must be a number, got {top_p!r}")
+    p = float(top_p)
+    if not (math.isfinite(p) and 0.0 < p <= 1.0) or not 0.0 < C.c_float(p).value <= 1.0:
+        raise ValueError(f"top_p must be finite, > 0 and <= 1 (1 = off), got {top_p!r}")
+    p = C.c_float(p).value
+    if p == 1.0:
+        return smp
+    return Nucleus(1.0, 0, p) if smp is None else Nucleus(smp.temperature, smp.top_k, p)
+
+
 class ScheduleC(C.Structure):
     _fields_ = [("timesteps", C.c_int32), ("d", C.POINTER(C.c_uint16)), ("c", C.POINTER(C.c_uint16)),
                 ("dbar", C.POINTER(C.c_uint16)), ("cbar", C.POINTER(C.c_uint16))]
@@ -183,6 +203,13 @@ SIGNATURES = {
                                             C.POINTER(Canvas), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                             C.c_void_p, C.POINTER(Sampling), C.c_void_p]),
+    "d3pm_posterior_sample_nucleus": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_int, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32,
+                                                C.c_void_p, C.POINTER(Nucleus), C.c_void_p, C.c_void_p]),
+    "d3pm_sample_loop_nucleus": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.POINTER(Canvas), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.POINTER(Nucleus), C.c_void_p]),
     "d3pm_q_sample": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                 C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_void_p]),
     "d3pm_denoise_step_fp8": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -610,11 +637,14 @@ class Sampler:
     def _lvl(self):
         return () if self.n_q == 1 else (self.n_q,)
 
-    def posterior_sample(self, logits, x_t, t, seed, utt0=0, flags=0, want_posterior=False, known=None, temperature=1.0, top_k=0):
+    def posterior_sample(self, logits, x_t, t, seed, utt0=0, flags=0, want_posterior=False, known=None, temperature=1.0, top_k=0,
+                         top_p=1.0, want_theta=False):
         """known: uint8 [B, canvas] or None -- frames that keep x_t instead of being drawn (d3pm_posterior_sample_known).
-        temperature / top_k: d3pm_sampling (d3pm_posterior_sample_sampling); the neutral pair takes the entries without them."""
+        temperature / top_k: d3pm_sampling (d3pm_posterior_sample_sampling); the neutral pair takes the entries without them.
+        top_p: d3pm_nucleus (d3pm_posterior_sample_nucleus); 1 takes the entries without it.  want_theta: a third result, the nucleus
+        threshold of every row as float32 in the shape of x_t (-inf where top_p is 1, NaN for a known frame)."""
         cfg = self.cfg
-        smp = sampling_options(temperature, top_k, cfg.n_classes)
+        smp = nucleus_options(temperature, top_k, top_p, cfg.n_classes)
         B = self._check_grid(x_t)
         if known is not None:
             _require(known, "known", (B, cfg.canvas), (torch.uint8,), self.device)
@@ -622,6 +652,14 @@ class Sampler:
         _require(logits, "logits", (B, cfg.canvas) + self._lvl() + (cfg.n_classes,), tuple(_DTYPES), self.device)
         x_next = torch.empty_like(x_t)
         post = torch.empty((B, cfg.canvas) + self._lvl() + (cfg.n_classes,), dtype=torch.int16, device=self.device) if want_posterior else None
+        if want_theta or isinstance(smp, Nucleus):
+            theta = torch.empty(x_t.shape, dtype=torch.float32, device=self.device) if want_theta else None
+            nuc = smp if isinstance(smp, Nucleus) else None if smp is None else Nucleus(smp.temperature, smp.top_k, 1.0)
+            check(lib().d3pm_posterior_sample_nucleus(C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), _p(x_t),
+                                                      _p(x_next), _p(known), int(t), C.byref(self.schedule.c_struct), seed, utt0,
+                                                      flags, _p(post), None if nuc is None else C.byref(nuc), _p(theta), stream_ptr()),
+                  "d3pm_posterior_sample_nucleus")
+            return (x_next, post, theta) if want_theta else (x_next, post)
         if smp is not None:
             check(lib().d3pm_posterior_sample_sampling(C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), _p(x_t),
                                                        _p(x_next), _p(known), int(t), C.byref(self.schedule.c_struct), seed, utt0,
@@ -651,12 +689,13 @@ class Sampler:
         return x_next
 
     def sample_loop(self, x, frame_mask, t_start, t_stop, kv_t, kv_p, seed, utt0=0, flags=0, trace=False, slot=0,
-                    fp8=False, known=None, temperature=1.0, top_k=0):
+                    fp8=False, known=None, temperature=1.0, top_k=0, top_p=1.0):
         """frame_mask uint8 [canvas] (shared by the batch) runs d3pm_sample_loop(_fp8); a per-utterance mask [B, canvas] and / or a
         known-frame map `known` (uint8 [B, canvas]; `x` already carries the given ids) run the *_canvas entries.  temperature /
-        top_k other than the neutral (1, 0) run d3pm_sample_loop_sampling, which covers the four of them."""
+        top_k other than the neutral (1, 0) run d3pm_sample_loop_sampling, which covers the four of them; top_p other than 1 runs
+        d3pm_sample_loop_nucleus, which takes the same arguments."""
         cfg = self.cfg
-        smp = sampling_options(temperature, top_k, cfg.n_classes)
+        smp = nucleus_options(temperature, top_k, top_p, cfg.n_classes)
         per_utt = known is not None or (isinstance(frame_mask, torch.Tensor) and frame_mask.dim() == 2)
         B = self._check_grid(x, None if per_utt else frame_mask, "x")
         cv = self._check_canvas(B, frame_mask, known) if per_utt else None
@@ -664,12 +703,13 @@ class Sampler:
         ws = self.workspace(B, slot)
         tr = torch.empty((t_start - t_stop, B, cfg.canvas) + self._lvl(), dtype=torch.int32, device=self.device) if trace else None
         if smp is not None:
-            check(lib().d3pm_sample_loop_sampling(C.byref(self.shape), C.byref(self.weights.c_struct),
-                                                  C.cast(self.fp8_weights().blocks, C.c_void_p) if fp8 else None, B, _p(x),
-                                                  None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None,
-                                                  int(t_start), int(t_stop), _p(self.film), _p(kv_t), _p(kv_p),
-                                                  C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
-                                                  C.byref(smp), stream_ptr()), "d3pm_sample_loop_sampling")
+            name = "d3pm_sample_loop_nucleus" if isinstance(smp, Nucleus) else "d3pm_sample_loop_sampling"
+            check(getattr(lib(), name)(C.byref(self.shape), C.byref(self.weights.c_struct),
+                                       C.cast(self.fp8_weights().blocks, C.c_void_p) if fp8 else None, B, _p(x),
+                                       None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None,
+                                       int(t_start), int(t_stop), _p(self.film), _p(kv_t), _p(kv_p),
+                                       C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
+                                       C.byref(smp), stream_ptr()), name)
             return tr
         if per_utt and fp8:
             check(lib().d3pm_sample_loop_fp8_canvas(C.byref(self.shape), C.byref(self.weights.c_struct),

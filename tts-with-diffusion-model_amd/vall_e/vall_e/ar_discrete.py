@@ -335,7 +335,8 @@ class AR(SymmapState, nn.Module):
                        utt0: int = 0, return_trace: bool = False, flags: int = 0, streams: Optional[int] = None,
                        graph: Optional[bool] = None, fp8: bool = False, global_batch: Optional[int] = None,
                        known: Optional[Sequence[Optional[Tensor]]] = None,
-                       known_mask: Optional[Sequence[Optional[Tensor]]] = None, temperature: float = 1.0, top_k: int = 0):
+                       known_mask: Optional[Sequence[Optional[Tensor]]] = None, temperature: float = 1.0, top_k: int = 0,
+                       top_p: float = 1.0):
         """Reverse diffusion for len(text_list) utterances.  Positional behaviour as upstream:
         one utterance -> int64 [canvas] (squeezed, untrimmed; rows >= n_frames are sampled from
         final.bias and meaningless); with n_q > 1 (constructor) [canvas, n_q] / [B, canvas, n_q].  `resps_list` is ignored, as
@@ -361,17 +362,23 @@ class AR(SymmapState, nn.Module):
         compose with greedy, n_frames, known frames, fp8, utt0 / global_batch and stream chunks; the defaults (1, 0) run the loop
         that knows nothing of them.  Bad values are a ValueError before any GPU work.  The NAR stage keeps its own
         `sampling_temperature`.
+        `top_p` (finite, 0 < top_p <= 1; 1 = off) is the nucleus cut behind them (include/d3pm_hip.h: d3pm_nucleus): of a row's
+        logits after temperature and top_k, the draw keeps the smallest set of the largest ones that carries the share top_p of the
+        softmax mass (measured in units of 2^-20 of the largest class's weight, ties at the threshold all kept) and sends the rest to
+        -inf, per row and per step, inside the same launch.  The kept mass sits within 1.0e-3 of what the definition in exact
+        arithmetic keeps; the ids are exactly those of the unfiltered sampler on logits cut at the kernel's threshold.  It composes
+        with everything top_k composes with; `top_p <= 1/1280` draws what `top_k = 1` draws.
         `graph=True` replays the loop from a captured HIP graph (seed read from HBM, identical results).  Off by
         default: measured on MI355X one utterance takes 66.6 ms replayed and 66.3 ms launched eagerly -- the ~5000
         kernels of a reverse process are bound by their own ~10 us latency at M = 768 rows, not by launch overhead.  The graph cache is keyed on batch, step range, utt0 and flags, not on sampling options:
-        `graph=True` with a temperature / top_k other than (1, 0) raises ValueError, like the per-utterance arguments."""
+        `graph=True` with a temperature / top_k / top_p other than (1, 0, 1) raises ValueError, like the per-utterance arguments."""
         if len(text_list) != len(proms_list) or len(text_list) == 0:
             raise ValueError("text_list and proms_list must be non-empty and of equal length")
         B = len(text_list)
-        filtered = _hip.sampling_options(temperature, top_k, N_CLASSES) is not None      # host validation before any GPU work
+        filtered = _hip.nucleus_options(temperature, top_k, top_p, N_CLASSES) is not None      # host validation before any GPU work
         if filtered and graph:
-            raise ValueError("graph=True replays a loop captured per (batch, step range, utt0, flags): temperature / top_k run on the "
-                             "eager loop only")
+            raise ValueError("graph=True replays a loop captured per (batch, step range, utt0, flags): temperature / top_k / top_p run "
+                             "on the eager loop only")
         per_utt = known is not None or known_mask is not None or not (n_frames is None or isinstance(n_frames, Integral))
         if per_utt:
             if graph:
@@ -402,7 +409,7 @@ class AR(SymmapState, nn.Module):
             elif n_streams == 1 or return_trace:
                 kv_t, kv_p = smp.cond_kv(cond_text, cond_prompt)
                 trace = smp.sample_loop(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl, trace=return_trace, fp8=fp8, known=kmap,
-                                        temperature=temperature, top_k=top_k)
+                                        temperature=temperature, top_k=top_k, top_p=top_p)
             else:
                 # utterances are independent: chunks of the batch run the whole loop on their own stream so that
                 # the short kernels of one chunk fill the ramp-up / epilogue bubbles of the others
@@ -418,7 +425,8 @@ class AR(SymmapState, nn.Module):
                     with torch.cuda.stream(st):
                         kv_t, kv_p = smp.cond_kv(cond_text[lo:hi], cond_prompt[lo:hi])
                         smp.sample_loop(x[lo:hi], frame_mask[lo:hi] if per_utt else frame_mask, t_start, 0, kv_t, kv_p, seed, utt0 + lo, fl,
-                                        slot=i, known=None if kmap is None else kmap[lo:hi], temperature=temperature, top_k=top_k)
+                                        slot=i, known=None if kmap is None else kmap[lo:hi], temperature=temperature, top_k=top_k,
+                                        top_p=top_p)
                         for t_ in (kv_t, kv_p, cond_text, cond_prompt, x):
                             t_.record_stream(st)
                 for i in range(n_streams):
@@ -430,14 +438,14 @@ class AR(SymmapState, nn.Module):
     # ------------------------------------------------------------------ upstream method names
     @torch.no_grad()
     def p_sample(self, model_logits: Tensor, t: Tensor, x: Tensor, *, seed: int = 0, utt0: int = 0, temperature: float = 1.0,
-                 top_k: int = 0):
+                 top_k: int = 0, top_p: float = 1.0):
         """One reverse transition from x0-logits [B,T,K] at step t[0] (ar_discrete.py:401-420).
-        Returns (sample int64 [B,T], softmax(logits)) like upstream (the softmax of the logits as given: `temperature` / `top_k`,
-        as in generate_audio, act on the draw only).  Bad values are a ValueError before any GPU work."""
-        _hip.sampling_options(temperature, top_k, N_CLASSES)
+        Returns (sample int64 [B,T], softmax(logits)) like upstream (the softmax of the logits as given: `temperature` / `top_k` /
+        `top_p`, as in generate_audio, act on the draw only).  Bad values are a ValueError before any GPU work."""
+        _hip.nucleus_options(temperature, top_k, top_p, N_CLASSES)
         smp = self.sampler()
         x_next, _ = smp.posterior_sample(model_logits, x.to(torch.int32).contiguous(), int(t.reshape(-1)[0]), seed, utt0,
-                                         temperature=temperature, top_k=top_k)
+                                         temperature=temperature, top_k=top_k, top_p=top_p)
         return x_next.long(), F.softmax(model_logits, dim=-1)
 
     @torch.no_grad()
