@@ -54,7 +54,8 @@ extern "C" {
  *    d3pm_op_attention_bwd_dropout_f32); per-utterance canvases (d3pm_canvas, d3pm_denoise_step_canvas,
  *    d3pm_posterior_sample_known, d3pm_sample_loop_canvas, d3pm_sample_loop_fp8_canvas); temperature / top-k on the x0-logits
  *    (d3pm_sampling, d3pm_posterior_sample_sampling, d3pm_sample_loop_sampling); the nucleus (top-p) cut behind them
- *    (d3pm_nucleus, d3pm_posterior_sample_nucleus, d3pm_sample_loop_nucleus) */
+ *    (d3pm_nucleus, d3pm_posterior_sample_nucleus, d3pm_sample_loop_nucleus); the confidence-ordered reveal schedule
+ *    (d3pm_reveal, d3pm_reveal_plan, d3pm_reveal_step, d3pm_reveal_loop) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -484,6 +485,70 @@ int d3pm_sample_loop_nucleus(const d3pm_shape *shape, const d3pm_weights *weight
                              const void *kv_prompt, const d3pm_schedule *sched, uint64_t seed, uint32_t utt0,
                              uint32_t flags, void *workspace, size_t workspace_bytes, int32_t *trace,
                              const d3pm_nucleus *nucleus, void *stream);
+
+/* Confidence-ordered reveal in N denoiser evaluations ----------------------------------------------------
+ * A second reverse schedule on the same canvas (MaskGIT / SoundStorm decoding; the reference has none): instead of revealing every
+ * masked row at random with the schedule's probability over timesteps - 1 evaluations, each of N steps reveals the rows the model is
+ * most sure of, under a quota that follows cbar -- the share of masked frames the denoiser was trained on at that timestep.  No
+ * statement about audio quality is made; what follows is an exact definition.  n_q = 1 only; a batch is B independent one-utterance
+ * runs.  T = sched->timesteps, 1 <= N <= T - 1.
+ *   timesteps  t_i = (T-1) - floor(i (T-1) / N), i = 0 .. N-1, and t_N = 0: strictly decreasing, t_0 = T-1, t_{N-1} >= 1; N = T-1 gives
+ *              T-1, T-2, .. 1 (d3pm_reveal_plan).  Evaluation i runs the denoiser at t_i.
+ *   rows       a row of utterance b is FREE when it is live (frame_mask) and not known; F_b = number of free rows; a free row is
+ *              MASKED when x == mask_id.  The canvas starts as for the D3PM loop (known ids in place, the mask id on the other
+ *              live frames, 0 on the padding).
+ *   quota      after step i utterance b keeps  keep = min(masked_now, floor((double) F_b * (double) float(cbar[t_{i+1}])))  rows
+ *              masked (after the last step: 0) and reveals masked_now - keep.  An fp16 significand times a count < 2^20 is exact in
+ *              fp64, so host and device agree on the count with no tolerance.  The kernel counts F_b and masked_now itself from
+ *              frame_mask, known and x_t: no plan is uploaded, shards and stream chunks need nothing extra.
+ *   candidate  of a masked row at step i:  z_j = rn16(float(l_j)) as the sampler reads the logits; z_{mask_id} = -inf (the mask is not
+ *              a token to reveal); then temperature, top_k, top_p exactly as d3pm_sampling / d3pm_nucleus define them -> z''' (the
+ *              neutral triple leaves only the -inf);  m = max z''',  e_j = expf(z'''_j - m),  S = sum_j e_j in fp32;
+ *              cand = first-index argmax of z'''_j + gumbel(u_j) in fp32, u_j the uniform the posterior draw of that row would take:
+ *              Philox key (seed; class group, global row, t_i, stream 0).  D3PM_FLAG_GREEDY: cand = first-index argmax of z'''_j, no
+ *              draw.  A row whose z''' are all -inf is outside the contract.
+ *   score      conf = z'''_cand - m - logf(S) in fp32;  score = conf + lambda_i * gumbel(v),  lambda_i = choice_temperature *
+ *              float(cbar[t_{i+1}]) (fp32), lambda_{N-1} = 0;  v = word 0 of Philox key (seed; 0, global row, t_i, stream 4).
+ *              choice_temperature = 0 and D3PM_FLAG_GREEDY draw no v and give score = conf bit for bit.  The score sits within
+ *              1.0e-4 of the definition in exact arithmetic (1033 * 2^-24 on S, three fp32 roundings at magnitude <= 32); the bound
+ *              limits how far a score may sit from the definition.  It bounds no id:
+ *   selection  the order key is the monotone uint32 image of the score's fp32 bits; the rows revealed are the masked_now - keep
+ *              masked rows that come first in the order (key descending, frame index ascending) -- given the scores the device
+ *              reports, the revealed set is exact.  A revealed row takes cand (never mask_id) and is never drawn again; every other
+ *              row keeps x_t.  Known rows and padded rows are never given a new id: padded rows stay 0 -- they are NOT "sampled from
+ *              final.bias" as on the D3PM path.  After step N-1 no free row holds the mask id.
+ * Refused with nothing launched: n_steps outside 1 .. T-1, choice_temperature negative or not finite (D3PM_E_ARG); n_q > 1,
+ * canvas > 1024 (D3PM_E_SHAPE).  There is no fp8 entry. */
+typedef struct d3pm_reveal {
+  int32_t n_steps;
+  float choice_temperature;     /* >= 0, finite; 0 = rows are revealed in the order of their confidence alone */
+} d3pm_reveal;
+
+/* t_out[i] = t_i for i = 0 .. n_steps - 1 (HOST array).  Host arithmetic only. */
+int d3pm_reveal_plan(const d3pm_schedule *sched, int n_steps, int32_t *t_out /* host [n_steps] */);
+
+/* One step between two denoiser evaluations: the evaluation ran at t (= t_i) and the next one runs at t_next (= t_{i+1}; 0 marks the
+ * last step: keep = 0, lambda = 0), sched->timesteps > t > t_next >= 0.  Exactly one of frame_mask (device uint8 [canvas], shared by
+ * the batch) and canvas (per utterance, with the optional known map) is given.  logits device [batch*canvas][n_classes] of
+ * logits_dtype; x_next may be x_t (in place: only revealed rows are stored) or another grid (every row is stored).  cand_out (int32)
+ * and score_out (fp32), device [batch][canvas], receive cand and score of every row that was masked at x_t, written by the wave that
+ * scored the row; rows that were not masked are left unwritten.  They are also what the step's second launch reads, so both are
+ * required.  nucleus NULL = the neutral triple. */
+int d3pm_reveal_step(const d3pm_shape *shape, int batch, const void *logits, int logits_dtype, const int32_t *x_t,
+                     int32_t *x_next, const uint8_t *frame_mask, const d3pm_canvas *canvas, int t, int t_next,
+                     const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags, const d3pm_nucleus *nucleus,
+                     float choice_temperature, int32_t *cand_out, float *score_out, void *stream);
+
+/* The whole schedule: for i = 0 .. n_steps-1: denoiser evaluation at t_i + d3pm_reveal_step(t_i, t_{i+1}).  x device int32
+ * [batch][canvas], in: the initial canvas, out: the result.  trace optional device int32 [n_steps][batch][canvas] receiving x after
+ * every step, or NULL.  Workspace as for d3pm_sample_loop.  Two launches per step behind the final projection; with the folded
+ * LayerNorms the second one also gathers the embedding rows of the next evaluation with their moments and rebuilds fc1 for t_{i+1}
+ * (same ids as the step entry, step by step). */
+int d3pm_reveal_loop(const d3pm_shape *shape, const d3pm_weights *weights, int batch, int32_t *x, const uint8_t *frame_mask,
+                     const d3pm_canvas *canvas, const void *film, const void *kv_text, const void *kv_prompt,
+                     const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
+                     size_t workspace_bytes, int32_t *trace, const d3pm_nucleus *nucleus, const d3pm_reveal *reveal,
+                     void *stream);
 
 /* Replaces AR.q_sample / q_probs (ar_discrete.py:467-502): forward noising of x0 at step t with
  * Philox stream 1.  x0, x_out device int32 [batch][canvas]. */

@@ -30,6 +30,7 @@ int q_sample_launch(const d3pm_shape*, int, const int32_t*, int32_t*, const uint
                     uint64_t, uint32_t, hipStream_t);
 int uniform_launch(uint64_t, int, uint32_t, int, int, int, float*, hipStream_t);
 int ce_loss_launch(int, const void*, int, const int32_t*, const uint8_t*, int, int, int, float*, hipStream_t);
+float host_h2f(uint16_t h);
 #ifdef D3PM_ABLATIONS
 bool final_sample_supported(int dtype, int n_classes, int d, const void* X, int ldx, const void* W);
 int final_sample(int dtype, const void* X, int ldx, const void* W, const void* bias, int d, const SampleArgs& a, hipStream_t s);
@@ -1109,6 +1110,126 @@ int d3pm_sample_loop_nucleus(const d3pm_shape* sh, const d3pm_weights* w, const 
   return sample_loop_impl(sh, w, batch, x, canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask), t_start, t_stop,
                           film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks, nucleus,
                           "d3pm_sample_loop_nucleus");
+}
+
+// ---- confidence-ordered reveal (d3pm_reveal) ------------------------------------------------------------------------------------------
+int d3pm_reveal_plan(const d3pm_schedule* sched, int n_steps, int32_t* t_out) {
+  D3PM_REQUIRE(sched && t_out, D3PM_E_ARG, "d3pm_reveal_plan: null pointer");
+  const int T = sched->timesteps;
+  D3PM_REQUIRE(T >= 2 && n_steps >= 1 && n_steps <= T - 1, D3PM_E_ARG, "d3pm_reveal_plan: n_steps %d outside 1 .. %d (timesteps - 1)", n_steps, T - 1);
+  for (int i = 0; i < n_steps; ++i) t_out[i] = (T - 1) - static_cast<int>((static_cast<long long>(i) * (T - 1)) / n_steps);
+  return D3PM_OK;
+}
+
+// what the reveal entries refuse before anything is launched
+static int check_reveal(const d3pm_shape* sh, int batch, const d3pm_schedule* sched, float choice_temperature, uint32_t flags, const char* who) {
+  D3PM_TRY(check_shape(sh, batch));
+  D3PM_REQUIRE(sched && sched->cbar, D3PM_E_ARG, "%s: null schedule", who);
+  D3PM_REQUIRE(std::isfinite(choice_temperature) && choice_temperature >= 0.f, D3PM_E_ARG, "%s: choice_temperature %g is not a finite number >= 0", who,
+               static_cast<double>(choice_temperature));
+  D3PM_REQUIRE(!(flags & D3PM_FLAG_SEED_IN_HBM), D3PM_E_ARG, "%s: D3PM_FLAG_SEED_IN_HBM belongs to the captured D3PM loop", who);
+  D3PM_REQUIRE(levels(*sh) == 1, D3PM_E_SHAPE, "%s: n_q = %d; the reveal schedule is defined for n_q = 1", who, sh->n_q);
+  D3PM_REQUIRE(sh->canvas <= 1024, D3PM_E_SHAPE, "%s: canvas %d; the selection supports up to 1024 frames", who, sh->canvas);
+  return D3PM_OK;
+}
+
+// the scalars of the step that evaluates at t and is followed by t_next (0: the last step, which keeps nothing and draws no v)
+static void reveal_step_scalars(RevealArgs& a, const d3pm_schedule* sched, int t, int t_next, float choice_temperature) {
+  a.t = t;
+  a.keep_frac = t_next > 0 ? host_h2f(sched->cbar[t_next]) : 0.f;
+  a.lambda = t_next > 0 ? choice_temperature * a.keep_frac : 0.f;
+}
+
+int d3pm_reveal_step(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t, int32_t* x_next,
+                     const uint8_t* frame_mask, const d3pm_canvas* canvas, int t, int t_next, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                     uint32_t flags, const d3pm_nucleus* nucleus, float choice_temperature, int32_t* cand_out, float* score_out, void* stream) {
+  D3PM_TRY(check_reveal(sh, batch, sched, choice_temperature, flags, "d3pm_reveal_step"));
+  D3PM_TRY(check_sampling(sh, nucleus, "d3pm_reveal_step"));
+  D3PM_REQUIRE((frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
+               "d3pm_reveal_step: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)");
+  D3PM_REQUIRE(logits && x_t && x_next && cand_out && score_out && (!canvas || canvas->frame_mask), D3PM_E_ARG, "d3pm_reveal_step: null pointer");
+  D3PM_REQUIRE(t >= 1 && t < sched->timesteps && t_next >= 0 && t_next < t, D3PM_E_ARG, "d3pm_reveal_step: t = %d, t_next = %d outside %d > t > t_next >= 0", t,
+               t_next, sched->timesteps);
+  const CanvasMask cm = canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask);
+  RevealArgs a;
+  a.logits = logits; a.logits_dtype = logits_dtype; a.ldl = sh->n_classes; a.x_t = x_t; a.x_next = x_next;
+  a.frame_mask = cm.frame_mask; a.mask_period = cm.period; a.known = cm.known; a.cand = cand_out; a.score = score_out;
+  a.rows = batch * sh->canvas; a.canvas = sh->canvas; a.n_classes = sh->n_classes; a.mask_id = sh->mask_id;
+  a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas); a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0;
+  if (nucleus) { a.temperature = nucleus->temperature; a.top_k = nucleus->top_k; a.top_p = nucleus->top_p; }
+  reveal_step_scalars(a, sched, t, t_next, choice_temperature);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  D3PM_TRY(reveal_candidates(a, s));
+  return reveal_commit(a, s);
+}
+
+int d3pm_reveal_loop(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
+                     const void* film, const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags,
+                     void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus, const d3pm_reveal* reveal, void* stream) {
+  D3PM_REQUIRE(reveal, D3PM_E_ARG, "d3pm_reveal_loop: null d3pm_reveal");
+  D3PM_TRY(check_reveal(sh, batch, sched, reveal->choice_temperature, flags, "d3pm_reveal_loop"));
+  D3PM_TRY(check_sampling(sh, nucleus, "d3pm_reveal_loop"));
+  const int T = sched->timesteps, N = reveal->n_steps;
+  D3PM_REQUIRE(N >= 1 && N <= T - 1 && T - 1 <= sh->timesteps, D3PM_E_ARG, "d3pm_reveal_loop: n_steps %d outside 1 .. %d (timesteps - 1)", N, T - 1);
+  D3PM_REQUIRE((frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
+               "d3pm_reveal_loop: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)");
+  D3PM_REQUIRE(w && w->blocks && x && film && kv_text && kv_prompt && workspace && (!canvas || canvas->frame_mask), D3PM_E_ARG, "d3pm_reveal_loop: null pointer");
+  Workspace ws = carve(*sh, batch, static_cast<char*>(workspace));
+  D3PM_REQUIRE(workspace_bytes >= ws.total, D3PM_E_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, ws.total);
+  const int rows = batch * sh->canvas;
+  const size_t es = dtype_size(sh->dtype);
+  // candidates and scores live in the attention-output region, dead behind the last block.  The second id grid of the fused launch has
+  // to survive the next evaluation: it takes the fp8 path's scale slot, which a 16-bit evaluation never touches (2 d / 32 >= 16 bytes
+  // per row wherever the fused launch applies, d a multiple of 256).
+  D3PM_REQUIRE(static_cast<size_t>(sh->d_model) * es >= 2 * sizeof(int32_t), D3PM_E_SHAPE, "d3pm_reveal_loop: d_model %d too small", sh->d_model);
+  int32_t* cand = reinterpret_cast<int32_t*>(ws.att);
+  float* score = reinterpret_cast<float*>(ws.att) + rows;
+  int32_t* x_alt = reinterpret_cast<int32_t*>(ws.mxs);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const CanvasMask cm = canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask);
+  const Ctx cx(sh->tuning);
+  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws};
+  const int plan = fold_plan(q, flags, nullptr);
+  bool prepared = false;
+  int32_t* cur = x;      // where x_t of the step lives: the fused launch cannot store in place, so it alternates between x and x_alt
+  for (int i = 0; i < N; ++i) {
+    const int t = (T - 1) - static_cast<int>((static_cast<long long>(i) * (T - 1)) / N);
+    const int t_next = i + 1 < N ? (T - 1) - static_cast<int>((static_cast<long long>(i + 1) * (T - 1)) / N) : 0;
+    if (cx.prof) cx.prof->sample_now = (t % cx.prof->stride) == 0;
+    D3PM_TRY(denoiser_blocks(q, cur, t, film, sh->n_layers, flags, s, nullptr, plan, prepared));
+    prepared = false;
+    D3PM_TRY(final_logits(*sh, *w, batch, ws, ws.logits, logits_ld(*sh), flags, s));
+    RevealArgs a;
+    a.logits = ws.logits; a.logits_dtype = sh->dtype; a.ldl = logits_ld(*sh); a.x_t = cur;
+    a.x_next2 = trace ? trace + static_cast<size_t>(i) * rows : nullptr;
+    a.frame_mask = cm.frame_mask; a.mask_period = cm.period; a.known = cm.known; a.cand = cand; a.score = score;
+    a.rows = rows; a.canvas = sh->canvas; a.n_classes = sh->n_classes; a.mask_id = sh->mask_id;
+    a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas); a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0;
+    if (nucleus) { a.temperature = nucleus->temperature; a.top_k = nucleus->top_k; a.top_p = nucleus->top_p; }
+    reveal_step_scalars(a, sched, t, t_next, reveal->choice_temperature);
+    ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0, static_cast<double>(rows) * (sh->n_classes * es + 16.0));
+    D3PM_TRY(reveal_candidates(a, s));
+    NextIterPrep nx;
+    if (t_next > 0 && plan != FOLD_NONE) {
+      nx.dtype = sh->dtype; nx.table = w->resps_emb; nx.x = ws.x; nx.stats = ws.stats; nx.frame_mask = cm.frame_mask; nx.mask_period = cm.period; nx.d = sh->d_model;
+      nx.quads = plan == FOLD_QUADS;
+      nx.blocks = w->blocks; nx.n_layers = sh->n_layers;
+      nx.film_t = at(film, static_cast<size_t>(t_next) * sh->n_layers * 2 * sh->d_model, es);
+      nx.Wf = ws.fc1f; nx.s_out = ws.fc1f_s; nx.b_out = ws.fc1f_b;
+    }
+    a.x_next = cur == x ? x_alt : x;
+    if (nx.table && reveal_commit_prep_supported(a, nx)) {
+      D3PM_TRY(reveal_commit_prep(a, nx, s));      // + the embedding rows, their moments and the fc1 fold of t_next
+      prepared = true;
+      cur = a.x_next;
+    } else {
+      a.x_next = x;      // one wave per utterance: in place when cur is x, else back into x
+      D3PM_TRY(reveal_commit(a, s));
+      cur = x;
+    }
+  }
+  if (cx.prof) cx.prof->sample_now = false;
+  return D3PM_OK;      // the last step is never fused (no next evaluation): the result is in x
 }
 
 int d3pm_q_sample(const d3pm_shape* sh, int batch, const int32_t* x0, int32_t* x_out, const uint8_t* frame_mask, int t,

@@ -185,11 +185,33 @@ struct NextIterPrep {
   const void* table = nullptr; void* x = nullptr; float* stats = nullptr; const uint8_t* frame_mask = nullptr; int d = 0;
   int mask_period = 0;                                                                              // frame_mask[row % mask_period]
   bool quads = false;                                                                               // stats in the quad format
-  const d3pm_block_weights* blocks = nullptr; int n_layers = 0; const void* film_t = nullptr;      // film_t: row t - 1 of the FiLM table
+  const d3pm_block_weights* blocks = nullptr; int n_layers = 0; const void* film_t = nullptr;      // film_t: the FiLM table's row of the next evaluation's timestep (t - 1; the reveal loop: t_{i+1})
   void* Wf = nullptr; float* s_out = nullptr; float* b_out = nullptr;
 };
 bool posterior_sample_prep_supported(const SampleArgs& a, const NextIterPrep& n);
 int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_t s);
+
+// One step of the confidence-ordered reveal (d3pm_reveal, d3pm_reveal.hip; n_q = 1): reveal_candidates scores the masked free rows at
+// timestep t into cand / score, then reveal_commit (one wave per utterance) or reveal_commit_prep (one wave per row + NextIterPrep
+// with film_t = the row of the NEXT timestep of the plan; x_next != x_t) picks the step's rows and stores x_next.
+struct RevealArgs {
+  const void* logits = nullptr; int logits_dtype = D3PM_F16; int ldl = 0;
+  const int32_t* x_t = nullptr; int32_t* x_next = nullptr; int32_t* x_next2 = nullptr;
+  const uint8_t* frame_mask = nullptr; int mask_period = 0;      // frame_mask[row % mask_period]
+  const uint8_t* known = nullptr;                                // [rows] or nullptr
+  int32_t* cand = nullptr; float* score = nullptr;               // [rows]: written for masked free rows only
+  int rows = 0, canvas = 0, n_classes = 0, mask_id = 0;
+  uint64_t seed = 0; uint32_t row0 = 0; int greedy = 0;
+  int t = 0;                  // timestep of the evaluation: keys the uniforms
+  float lambda = 0.f;         // choice_temperature * float(cbar[t_next]); 0 on the last step
+  float keep_frac = 0.f;      // float(cbar[t_next]); 0 on the last step
+  float temperature = 1.0f; int top_k = 0; float top_p = 1.0f;
+  bool filtered() const { return temperature != 1.0f || top_k != 0 || top_p < 1.0f; }
+};
+int reveal_candidates(const RevealArgs& a, hipStream_t s);
+int reveal_commit(const RevealArgs& a, hipStream_t s);
+bool reveal_commit_prep_supported(const RevealArgs& a, const NextIterPrep& n);
+int reveal_commit_prep(const RevealArgs& a, const NextIterPrep& n, hipStream_t s);
 
 // fp8 fast path on the block-scaled MFMA (d3pm_mx.hip): e4m3 codes [rows][K] + e8m0 block scales [rows][4][K / 128]
 //   Y[M][N] = epilogue(sum_k X8 2^sx . W8 2^sw + bias), epilogue as LinearArgs (plain, GELU, R1, R1 + mask); with Y8 / SY set the

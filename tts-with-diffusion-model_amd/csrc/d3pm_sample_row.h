@@ -407,5 +407,107 @@ __device__ __forceinline__ int sample_row_1025(P lr, int mask_id, int x, uint64_
   return best_j;
 }
 
+// ---- confidence-ordered reveal (d3pm_reveal): candidate and score of one masked row ------------------------
+// One wave, one row.  z, zt, has_tail, valid as for filter_row; kTail says whether the routine carries a tail class at all (class
+// tail_j, held by the lanes with has_tail).  The row's z lose the mask class (-inf: the mask is not a token to reveal), pass through
+// filter_row / nucleus_row as they are (kFilter != 0), and then
+//     m = max z''',  S = sum_j expf(z'''_j - m),  cand = first-index argmax of z'''_j + gumbel(u_j)   (greedy: of z'''_j)
+//     conf = z'''_cand - m - logf(S),  score = conf + lambda * gumbel(v)                              (lambda 0 or greedy: conf)
+// u_j is the uniform the posterior draw of this row would take at this t (stream 0), v word 0 of (0, row, t, stream 4).
+constexpr uint32_t kStreamRevealChoice = 4;
+struct RevealRow { int cand; float score; };
+
+template <int R, bool kTail, int kFilter, typename V>
+__device__ __forceinline__ RevealRow reveal_from_z(float (&z)[R][4], float zt, bool has_tail, int tail_j, V valid, int mask_id, uint64_t seed,
+                                                   uint32_t grow, uint32_t t, int greedy, float lambda, int lane, const RowFilter& flt, float top_p) {
+#pragma unroll
+  for (int i = 0; i < R; ++i)
+#pragma unroll
+    for (int w = 0; w < 4; ++w) z[i][w] = (lane + i * kWave) * 4 + w == mask_id ? -INFINITY : z[i][w];
+  if (kTail && tail_j == mask_id) zt = -INFINITY;
+  if constexpr (kFilter != 0) {
+    filter_row(z, zt, has_tail, valid, flt);
+    (void)nucleus_row(z, zt, has_tail, valid, top_p);
+  }
+  float mx = zt;
+#pragma unroll
+  for (int i = 0; i < R; ++i)
+#pragma unroll
+    for (int w = 0; w < 4; ++w) mx = fmaxf(mx, z[i][w]);
+  mx = wave_max(mx);
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < R; ++i)
+#pragma unroll
+    for (int w = 0; w < 4; ++w) sum += expf(z[i][w] - mx);      // exp(-inf) = 0: cut classes, the mask class, slots without a class
+  if constexpr (kTail) sum += expf(zt - mx);
+  sum = wave_sum(sum);
+  int best_j = 0;
+  float best_v = -INFINITY, best_z = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const int g = lane + i * kWave;
+    float u[4] = {0.5f, 0.5f, 0.5f, 0.5f};
+    if (!greedy) noise4(seed, static_cast<uint32_t>(g), grow, t, 0u, u);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float v = greedy ? z[i][w] : z[i][w] + gumbel(u[w]);      // -inf stays -inf and never wins
+      if (v > best_v) { best_v = v; best_j = g * 4 + w; best_z = z[i][w]; }      // ascending j per lane keeps the first maximum
+    }
+  }
+  if constexpr (kTail) {
+    float ut[4] = {0.5f, 0.5f, 0.5f, 0.5f};
+    if (!greedy) noise4(seed, static_cast<uint32_t>(tail_j >> 2), grow, t, 0u, ut);
+    const float uw = (tail_j & 2) ? ((tail_j & 1) ? ut[3] : ut[2]) : ((tail_j & 1) ? ut[1] : ut[0]);
+    const float v = greedy ? zt : zt + gumbel(uw);
+    if (has_tail && v > best_v) { best_v = v; best_j = tail_j; best_z = zt; }
+  }
+  wave_argmax(best_v, best_j);
+  // the lane that owns class best_j holds it as its own best (it carries the wave's maximum, first index): its z is z'''_cand
+  const float zc = __shfl(best_z, (best_j >> 2) & (kWave - 1), kWave);
+  RevealRow r;
+  r.cand = best_j;
+  r.score = zc - mx - logf(sum);
+  if (lambda != 0.f && !greedy) {      // kernel-uniform
+    float v[4];
+    noise4(seed, 0u, grow, t, kStreamRevealChoice, v);
+    r.score = r.score + lambda * gumbel(v[0]);
+  }
+  return r;
+}
+
+// the K = 1025 layout of sample_row_1025 (17 values per lane, no predicate) and the general one (K <= 1280) of sample_row
+template <typename T, int kFilter, typename P>
+__device__ __forceinline__ RevealRow reveal_row_1025(P lr, int mask_id, uint64_t seed, uint32_t grow, uint32_t t, int greedy, float lambda, int lane,
+                                                     const RowFilter& flt, float top_p) {
+  constexpr int K = 1025;
+  float z[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int w = 0; w < 4; ++w) z[i][w] = rn16(static_cast<float>(lr[(lane + i * kWave) * 4 + w]));
+  const float zt = lane == 0 ? rn16(static_cast<float>(lr[K - 1])) : -INFINITY;
+  return reveal_from_z<4, true, kFilter>(z, zt, lane == 0, K - 1, [](int, int) { return true; }, mask_id, seed, grow, t, greedy, lambda, lane, flt,
+                                         top_p);
+}
+
+template <typename T, int kFilter, typename P>
+__device__ __forceinline__ RevealRow reveal_row(P lr, int K, int mask_id, uint64_t seed, uint32_t grow, uint32_t t, int greedy, float lambda, int lane,
+                                                const RowFilter& flt, float top_p) {
+  const int groups = (K + 3) >> 2;
+  float z[kMaxGroupsPerLane][4];
+#pragma unroll
+  for (int i = 0; i < kMaxGroupsPerLane; ++i) {
+    const int g = lane + i * kWave;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int j = g * 4 + w;
+      z[i][w] = (g < groups && j < K) ? rn16(static_cast<float>(lr[j])) : -INFINITY;
+    }
+  }
+  auto valid = [&](int i, int w) { const int g = lane + i * kWave; return g < groups && g * 4 + w < K; };
+  return reveal_from_z<kMaxGroupsPerLane, false, kFilter>(z, -INFINITY, false, 0, valid, mask_id, seed, grow, t, greedy, lambda, lane, flt, top_p);
+}
+
 }  // namespace
 }  // namespace d3pm

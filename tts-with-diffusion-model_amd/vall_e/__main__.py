@@ -29,6 +29,10 @@ The second form takes what those front-ends write (formats.py) and writes what E
                 keeps its own sampling_temperature
   --top-p P     nucleus cut behind them (0 < P <= 1, default 1 = off): every draw keeps the smallest set of the largest x0-logits
                 that carries the share P of the softmax mass, per row and per step (include/d3pm_hip.h: d3pm_nucleus)
+  --reveal-steps N, --choice-temperature F
+                run the D3PM stage as a confidence-ordered reveal in N denoiser evaluations (1 .. timesteps - 1; default: the
+                timesteps - 1 evaluations of the D3PM loop): every step reveals the frames the model is most sure of; F (>= 0,
+                default 0) adds annealed Gumbel noise to that order (include/d3pm_hip.h: d3pm_reveal)
 """
 import argparse
 from pathlib import Path
@@ -55,6 +59,8 @@ def main(argv=None):
     ap.add_argument("--temperature", type=float, default=1.0, help="D3PM stage: divide the x0-logits by this (> 0) before every draw")
     ap.add_argument("--top-k", type=int, default=0, help="D3PM stage: draw from the N largest x0-logits only (0 = off)")
     ap.add_argument("--top-p", type=float, default=1.0, help="D3PM stage: draw from the smallest set of classes that carries this share of the mass (1 = off)")
+    ap.add_argument("--reveal-steps", type=int, default=None, help="D3PM stage: confidence-ordered reveal in this many denoiser evaluations")
+    ap.add_argument("--choice-temperature", type=float, default=0.0, help="D3PM stage, with --reveal-steps: Gumbel noise on the reveal order (>= 0)")
     ap.add_argument("--native", action="store_true", help="the shape upstream's class really builds (d=32, 16 heads, 8 blocks)")
     args = ap.parse_args(argv)
 
@@ -62,6 +68,7 @@ def main(argv=None):
     from .vall_e import AR, _hip, get_model
     try:
         _hip.nucleus_options(args.temperature, args.top_k, args.top_p, 1025)
+        _hip.reveal_options(args.reveal_steps, args.choice_temperature)
     except ValueError as e:
         ap.error(str(e))
     if len(args.paths) not in (1, 3):
@@ -107,7 +114,8 @@ def main(argv=None):
     else:
         phns = torch.tensor([int(p) for p in args.phonemes.split()], dtype=torch.long)
     n_frames = model.cfg.n_frames if args.frames is None else args.frames
-    sampling = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
+    sampling = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, reveal_steps=args.reveal_steps,
+                    choice_temperature=args.choice_temperature)
     if args.frames is None and args.continue_from is None:
         codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed, **sampling)
     else:

@@ -147,6 +147,31 @@ def nucleus_options(temperature=1.0, top_k=0, top_p=1.0, n_classes=None):
     return Nucleus(1.0, 0, p) if smp is None else Nucleus(smp.temperature, smp.top_k, p)
 
 
+class Reveal(C.Structure):
+    """d3pm_reveal: the confidence-ordered reveal schedule, N denoiser evaluations (include/d3pm_hip.h)."""
+    _fields_ = [("n_steps", C.c_int32), ("choice_temperature", C.c_float)]
+
+
+def reveal_options(reveal_steps, choice_temperature=0.0, timesteps=None):
+    """Host validation of the reveal schedule's two numbers (ValueError, before any GPU work) -> a Reveal struct, or None when
+    reveal_steps is None (the D3PM loop; a choice_temperature other than 0 then has nothing to act on and is refused)."""
+    if isinstance(choice_temperature, bool) or not isinstance(choice_temperature, (int, float)):
+        raise ValueError(f"choice_temperature must be a number, got {choice_temperature!r}")
+    ct = float(choice_temperature)
+    if not (math.isfinite(ct) and ct >= 0.0) or not math.isfinite(C.c_float(ct).value):
+        raise ValueError(f"choice_temperature must be finite and >= 0, got {choice_temperature!r}")
+    if reveal_steps is None:
+        if ct != 0.0:
+            raise ValueError("choice_temperature without reveal_steps")
+        return None
+    if isinstance(reveal_steps, bool) or not isinstance(reveal_steps, Integral):
+        raise ValueError(f"reveal_steps must be an int, got {reveal_steps!r}")
+    n = int(reveal_steps)
+    if n < 1 or (timesteps is not None and n > timesteps - 1):
+        raise ValueError(f"reveal_steps must be in 1..{None if timesteps is None else timesteps - 1}, got {n}")
+    return Reveal(n, C.c_float(ct).value)
+
+
 class ScheduleC(C.Structure):
     _fields_ = [("timesteps", C.c_int32), ("d", C.POINTER(C.c_uint16)), ("c", C.POINTER(C.c_uint16)),
                 ("dbar", C.POINTER(C.c_uint16)), ("cbar", C.POINTER(C.c_uint16))]
@@ -210,6 +235,13 @@ SIGNATURES = {
                                            C.POINTER(Canvas), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.POINTER(Nucleus), C.c_void_p]),
+    "d3pm_reveal_plan": (C.c_int, [C.POINTER(ScheduleC), C.c_int, C.POINTER(C.c_int32)]),
+    "d3pm_reveal_step": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(Canvas), C.c_int, C.c_int, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32,
+                                   C.POINTER(Nucleus), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "d3pm_reveal_loop": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Canvas),
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32,
+                                   C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(Nucleus), C.POINTER(Reveal), C.c_void_p]),
     "d3pm_q_sample": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                 C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_void_p]),
     "d3pm_denoise_step_fp8": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -735,6 +767,66 @@ class Sampler:
                                      int(t_start), int(t_stop), _p(self.film), _p(kv_t), _p(kv_p),
                                      C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
                                      stream_ptr()), "d3pm_sample_loop")
+        return tr
+
+    def reveal_plan(self, n_steps):
+        """The timesteps t_0 .. t_{N-1} of the reveal schedule (d3pm_reveal_plan) as a list of ints."""
+        rv = reveal_options(n_steps, 0.0, self.schedule.timesteps)
+        out = (C.c_int32 * rv.n_steps)()
+        check(lib().d3pm_reveal_plan(C.byref(self.schedule.c_struct), rv.n_steps, out), "d3pm_reveal_plan")
+        return list(out)
+
+    @staticmethod
+    def _as_nucleus(smp):
+        return smp if smp is None or isinstance(smp, Nucleus) else Nucleus(smp.temperature, smp.top_k, 1.0)
+
+    def reveal_step(self, logits, x_t, frame_mask, t, t_next, seed, utt0=0, flags=0, known=None, temperature=1.0, top_k=0, top_p=1.0,
+                    choice_temperature=0.0, x_next=None):
+        """One step of the reveal schedule (d3pm_reveal_step) on the logits of the evaluation at `t`, followed by `t_next` (0 = the
+        last step) -> (x_next, cand, score): cand int32 / score float32 [B, canvas] hold a value only where x_t was a masked free
+        row (the other entries are 0).  frame_mask uint8 [canvas] or [B, canvas]; known uint8 [B, canvas] or None.  x_next: the grid
+        to store into (x_t itself for an in-place step), default a new one."""
+        cfg = self.cfg
+        smp = self._as_nucleus(nucleus_options(temperature, top_k, top_p, cfg.n_classes))
+        reveal_options(1, choice_temperature)
+        per_utt = known is not None or (isinstance(frame_mask, torch.Tensor) and frame_mask.dim() == 2)
+        B = self._check_grid(x_t, None if per_utt else frame_mask)
+        cv = self._check_canvas(B, frame_mask, known) if per_utt else None
+        logits = logits.contiguous() if isinstance(logits, torch.Tensor) else logits
+        _require(logits, "logits", (B, cfg.canvas, cfg.n_classes), tuple(_DTYPES), self.device)
+        if x_next is None:
+            x_next = torch.empty_like(x_t)
+        else:
+            _require(x_next, "x_next", tuple(x_t.shape), (torch.int32,), self.device)
+        cand = torch.zeros((B, cfg.canvas), dtype=torch.int32, device=self.device)
+        score = torch.zeros((B, cfg.canvas), dtype=torch.float32, device=self.device)
+        check(lib().d3pm_reveal_step(C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), _p(x_t), _p(x_next),
+                                     None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None, int(t), int(t_next),
+                                     C.byref(self.schedule.c_struct), seed, utt0, flags, None if smp is None else C.byref(smp),
+                                     float(choice_temperature), _p(cand), _p(score), stream_ptr()), "d3pm_reveal_step")
+        return x_next, cand, score
+
+    def reveal_loop(self, x, frame_mask, n_steps, kv_t, kv_p, seed, utt0=0, flags=0, trace=False, slot=0, known=None, temperature=1.0,
+                    top_k=0, top_p=1.0, choice_temperature=0.0):
+        """The reveal schedule in n_steps denoiser evaluations (d3pm_reveal_loop), in place on x; masks and known frames as for
+        sample_loop.  -> the trace int32 [n_steps, B, canvas] (x after every step) or None."""
+        cfg = self.cfg
+        smp = self._as_nucleus(nucleus_options(temperature, top_k, top_p, cfg.n_classes))
+        rv = reveal_options(n_steps, choice_temperature, self.schedule.timesteps)
+        if rv is None:
+            raise ValueError("reveal_loop needs n_steps")
+        if self.n_q != 1:
+            raise ValueError("the reveal schedule is defined for n_q = 1")
+        per_utt = known is not None or (isinstance(frame_mask, torch.Tensor) and frame_mask.dim() == 2)
+        B = self._check_grid(x, None if per_utt else frame_mask, "x")
+        cv = self._check_canvas(B, frame_mask, known) if per_utt else None
+        self._check_kv(kv_t, kv_p, B)
+        ws = self.workspace(B, slot)
+        tr = torch.empty((rv.n_steps, B, cfg.canvas), dtype=torch.int32, device=self.device) if trace else None
+        check(lib().d3pm_reveal_loop(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), None if per_utt else _p(frame_mask),
+                                     C.byref(cv) if per_utt else None, _p(self.film), _p(kv_t), _p(kv_p),
+                                     C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
+                                     None if smp is None else C.byref(smp), C.byref(rv), stream_ptr()), "d3pm_reveal_loop")
         return tr
 
     def ce_loss_rows(self, logits, targets, frame_mask):

@@ -336,7 +336,7 @@ class AR(SymmapState, nn.Module):
                        graph: Optional[bool] = None, fp8: bool = False, global_batch: Optional[int] = None,
                        known: Optional[Sequence[Optional[Tensor]]] = None,
                        known_mask: Optional[Sequence[Optional[Tensor]]] = None, temperature: float = 1.0, top_k: int = 0,
-                       top_p: float = 1.0):
+                       top_p: float = 1.0, reveal_steps: Optional[int] = None, choice_temperature: float = 0.0):
         """Reverse diffusion for len(text_list) utterances.  Positional behaviour as upstream:
         one utterance -> int64 [canvas] (squeezed, untrimmed; rows >= n_frames are sampled from
         final.bias and meaningless); with n_q > 1 (constructor) [canvas, n_q] / [B, canvas, n_q].  `resps_list` is ignored, as
@@ -371,7 +371,17 @@ class AR(SymmapState, nn.Module):
         `graph=True` replays the loop from a captured HIP graph (seed read from HBM, identical results).  Off by
         default: measured on MI355X one utterance takes 66.6 ms replayed and 66.3 ms launched eagerly -- the ~5000
         kernels of a reverse process are bound by their own ~10 us latency at M = 768 rows, not by launch overhead.  The graph cache is keyed on batch, step range, utt0 and flags, not on sampling options:
-        `graph=True` with a temperature / top_k / top_p other than (1, 0, 1) raises ValueError, like the per-utterance arguments."""
+        `graph=True` with a temperature / top_k / top_p other than (1, 0, 1) raises ValueError, like the per-utterance arguments.
+        `reveal_steps=N` (1 .. timesteps - 1; None = the loop above, untouched) runs the confidence-ordered reveal schedule instead
+        (include/d3pm_hip.h: d3pm_reveal): N denoiser evaluations at timesteps spread over timesteps - 1 .. 1, each followed by a step
+        that reveals the masked frames the model is most sure of -- as many as leave the share cbar[next timestep] of the utterance's
+        free frames masked -- with the candidate id drawn by Gumbel-max from the x0-logits (mask class excluded; temperature / top_k /
+        top_p apply to them as above; greedy takes the argmax).  `choice_temperature` (>= 0, default 0) adds Gumbel noise, annealed
+        with cbar, to the confidence that orders the frames.  Known frames come back unchanged and frames beyond n_frames stay 0:
+        they are NOT sampled from final.bias as on the default path.  It composes with n_frames sequences, known / known_mask,
+        temperature / top_k / top_p, greedy, utt0 / global_batch, streams and return_trace (the trace then has N entries);
+        with `steps`, graph=True, fp8=True or an n_q > 1 model it raises ValueError before any GPU work.  No statement about audio
+        quality is made for it."""
         if len(text_list) != len(proms_list) or len(text_list) == 0:
             raise ValueError("text_list and proms_list must be non-empty and of equal length")
         B = len(text_list)
@@ -379,6 +389,11 @@ class AR(SymmapState, nn.Module):
         if filtered and graph:
             raise ValueError("graph=True replays a loop captured per (batch, step range, utt0, flags): temperature / top_k / top_p run "
                              "on the eager loop only")
+        rv = _hip.reveal_options(reveal_steps, choice_temperature, self.timesteps)
+        if rv is not None:
+            for name, bad in (("steps", steps is not None), ("graph=True", bool(graph)), ("fp8=True", bool(fp8)), ("an n_q > 1 model", self.cfg.n_q > 1)):
+                if bad:
+                    raise ValueError(f"reveal_steps does not combine with {name}")
         per_utt = known is not None or known_mask is not None or not (n_frames is None or isinstance(n_frames, Integral))
         if per_utt:
             if graph:
@@ -408,8 +423,12 @@ class AR(SymmapState, nn.Module):
                 smp.sample_loop_graphed(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl)
             elif n_streams == 1 or return_trace:
                 kv_t, kv_p = smp.cond_kv(cond_text, cond_prompt)
-                trace = smp.sample_loop(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl, trace=return_trace, fp8=fp8, known=kmap,
-                                        temperature=temperature, top_k=top_k, top_p=top_p)
+                if rv is not None:
+                    trace = smp.reveal_loop(x, frame_mask, rv.n_steps, kv_t, kv_p, seed, utt0, fl, trace=return_trace, known=kmap,
+                                            temperature=temperature, top_k=top_k, top_p=top_p, choice_temperature=rv.choice_temperature)
+                else:
+                    trace = smp.sample_loop(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl, trace=return_trace, fp8=fp8, known=kmap,
+                                            temperature=temperature, top_k=top_k, top_p=top_p)
             else:
                 # utterances are independent: chunks of the batch run the whole loop on their own stream so that
                 # the short kernels of one chunk fill the ramp-up / epilogue bubbles of the others
@@ -424,9 +443,14 @@ class AR(SymmapState, nn.Module):
                     st.wait_stream(cur)
                     with torch.cuda.stream(st):
                         kv_t, kv_p = smp.cond_kv(cond_text[lo:hi], cond_prompt[lo:hi])
-                        smp.sample_loop(x[lo:hi], frame_mask[lo:hi] if per_utt else frame_mask, t_start, 0, kv_t, kv_p, seed, utt0 + lo, fl,
-                                        slot=i, known=None if kmap is None else kmap[lo:hi], temperature=temperature, top_k=top_k,
-                                        top_p=top_p)
+                        if rv is not None:
+                            smp.reveal_loop(x[lo:hi], frame_mask[lo:hi] if per_utt else frame_mask, rv.n_steps, kv_t, kv_p, seed, utt0 + lo, fl,
+                                            slot=i, known=None if kmap is None else kmap[lo:hi], temperature=temperature, top_k=top_k,
+                                            top_p=top_p, choice_temperature=rv.choice_temperature)
+                        else:
+                            smp.sample_loop(x[lo:hi], frame_mask[lo:hi] if per_utt else frame_mask, t_start, 0, kv_t, kv_p, seed, utt0 + lo, fl,
+                                            slot=i, known=None if kmap is None else kmap[lo:hi], temperature=temperature, top_k=top_k,
+                                            top_p=top_p)
                         for t_ in (kv_t, kv_p, cond_text, cond_prompt, x):
                             t_.record_stream(st)
                 for i in range(n_streams):
