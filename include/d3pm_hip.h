@@ -55,7 +55,8 @@ extern "C" {
  *    d3pm_posterior_sample_known, d3pm_sample_loop_canvas, d3pm_sample_loop_fp8_canvas); temperature / top-k on the x0-logits
  *    (d3pm_sampling, d3pm_posterior_sample_sampling, d3pm_sample_loop_sampling); the nucleus (top-p) cut behind them
  *    (d3pm_nucleus, d3pm_posterior_sample_nucleus, d3pm_sample_loop_nucleus); the confidence-ordered reveal schedule
- *    (d3pm_reveal, d3pm_reveal_plan, d3pm_reveal_step, d3pm_reveal_loop) */
+ *    (d3pm_reveal, d3pm_reveal_plan, d3pm_reveal_step, d3pm_reveal_loop); the per-utterance key mask at kernel level
+ *    (d3pm_op_attention_keylen) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -658,6 +659,14 @@ int d3pm_op_fold_weights(int dtype, const void *W, const void *bias, const void 
 int d3pm_op_attention(int dtype, int family, const void *Q, int ldq, const void *K, const void *V, int ldkv,
                       void *O, int ldo, int B, int Tq, int S, int H, int hd, float scale, const d3pm_tuning *tuning,
                       void *stream);
+/* d3pm_op_attention with the per-utterance key mask of the stock NAR attention: key_len (device int32 [B]) = the number of valid
+ * keys of each utterance, keys >= key_len[b] are masked out and S is the padded key count (the row stride of the K / V batches);
+ * NULL = d3pm_op_attention.  1 <= key_len[b] <= S is the caller's contract: the values live on the device and are read by the
+ * kernels only, so nothing here can refuse them.  Family 2 runs the schedules that take a mask (attn_query_groups 1 / 2; a request
+ * for 4 / 32 / 33 falls back to the automatic choice between those two). */
+int d3pm_op_attention_keylen(int dtype, int family, const void *Q, int ldq, const void *K, const void *V, int ldkv, void *O, int ldo,
+                             int B, int Tq, int S, int H, int hd, float scale, const int32_t *key_len, const d3pm_tuning *tuning,
+                             void *stream);
 /* The text and prompt cross-attentions of a DiT block (ar_discrete.py:138,142) as the block launches them: two independent
  * problems with the same B / Tq / H / hd -- queries Q1 / Q2 [B][Tq][ldq], keys and values K / V [B][S][ldkv] with S1 / S2 keys,
  * outputs O1 / O2 [B][Tq][ldo] -- in ONE launch (tuning->attn_cross_resident / attn_pair_sequential pick the schedule). */

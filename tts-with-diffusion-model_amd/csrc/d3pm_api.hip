@@ -1377,21 +1377,35 @@ int d3pm_op_linear_mx(int out_dtype, const void* X8, int ldx, const void* SX, co
   return mx_linear(out_dtype, m, static_cast<hipStream_t>(stream));
 }
 
-int d3pm_op_attention(int dtype, int family, const void* Q, int ldq, const void* K, const void* V, int ldkv, void* O,
-                      int ldo, int B, int Tq, int S, int H, int hd, float scale, const d3pm_tuning* tuning, void* stream) {
-  D3PM_REQUIRE(Q && K && V && O && B > 0 && Tq > 0 && S > 0 && H > 0 && hd > 0, D3PM_E_ARG, "d3pm_op_attention: bad arguments");
+static int op_attention_impl(const char* who, int dtype, int family, const void* Q, int ldq, const void* K, const void* V, int ldkv, void* O,
+                             int ldo, int B, int Tq, int S, int H, int hd, float scale, const int32_t* key_len, const d3pm_tuning* tuning,
+                             void* stream) {
+  D3PM_REQUIRE(Q && K && V && O && B > 0 && Tq > 0 && S > 0 && H > 0 && hd > 0, D3PM_E_ARG, "%s: bad arguments", who);
   const Ctx cx(tuning);
   AttnArgs a;
   a.tune = tuning;
   a.Q = Q; a.ldq = ldq; a.K = K; a.V = V; a.ldkv = ldkv; a.O = O; a.ldo = ldo; a.B = B; a.Tq = Tq; a.S = S; a.H = H;
-  a.hd = hd; a.scale = scale;
+  a.hd = hd; a.scale = scale; a.key_len = key_len;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (family == 1) return generic_attention(dtype, a, s);
   if (family == 2) {
-    D3PM_REQUIRE(mfma_attention_supported(dtype, a), D3PM_E_SHAPE, "d3pm_op_attention: shape not supported by the MFMA kernel");
+    D3PM_REQUIRE(mfma_attention_supported(dtype, a), D3PM_E_SHAPE, "%s: shape not supported by the MFMA kernel", who);
     return mfma_attention(dtype, a, s);
   }
   return run_attention(cx, dtype, a, 0, s);
+}
+
+int d3pm_op_attention(int dtype, int family, const void* Q, int ldq, const void* K, const void* V, int ldkv, void* O,
+                      int ldo, int B, int Tq, int S, int H, int hd, float scale, const d3pm_tuning* tuning, void* stream) {
+  return op_attention_impl("d3pm_op_attention", dtype, family, Q, ldq, K, V, ldkv, O, ldo, B, Tq, S, H, hd, scale, nullptr, tuning, stream);
+}
+
+// key_len (device, [B]) is read by the kernels only: a value outside 1 .. S cannot be refused here without a copy to the host
+int d3pm_op_attention_keylen(int dtype, int family, const void* Q, int ldq, const void* K, const void* V, int ldkv, void* O,
+                             int ldo, int B, int Tq, int S, int H, int hd, float scale, const int32_t* key_len,
+                             const d3pm_tuning* tuning, void* stream) {
+  return op_attention_impl("d3pm_op_attention_keylen", dtype, family, Q, ldq, K, V, ldkv, O, ldo, B, Tq, S, H, hd, scale, key_len, tuning,
+                           stream);
 }
 
 int d3pm_op_attention_pair(int dtype, const void* Q1, const void* K1, const void* V1, void* O1, int S1, const void* Q2, const void* K2,

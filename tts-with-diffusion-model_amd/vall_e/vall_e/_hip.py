@@ -269,6 +269,9 @@ SIGNATURES = {
     "d3pm_op_attention": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                     C.POINTER(Tuning), C.c_void_p]),
+    "d3pm_op_attention_keylen": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                           C.c_void_p, C.POINTER(Tuning), C.c_void_p]),
     "d3pm_op_attention_pair": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_float, C.POINTER(Tuning), C.c_void_p]),
@@ -977,16 +980,24 @@ def op_linear_mx(x8, sx, w8, sw, bias, out_dtype, *, act=0, r1=None, row_mask=No
     return (y8, sy) if mx_out else y
 
 
-def op_attention(q, k, v, n_heads, scale, *, family=0):
-    """q [B,Tq,d], k/v [B,S,d] (views with arbitrary row stride allowed) -> [B,Tq,d]."""
+def op_attention(q, k, v, n_heads, scale, *, family=0, key_len=None):
+    """q [B,Tq,d], k/v [B,S,d] (views with arbitrary row stride allowed) -> [B,Tq,d].  key_len: int32 [B] on the device, the valid
+    keys of each utterance (1 .. S, the caller's contract: the library cannot check device values); keys behind them are masked."""
     B, Tq, d = q.shape
     S = k.shape[1]
     assert k.stride(1) == v.stride(1) and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
     assert q.stride(0) == Tq * q.stride(1) and k.stride(0) == S * k.stride(1) and v.stride(0) == S * v.stride(1)
     o = torch.empty((B, Tq, d), dtype=q.dtype, device=q.device)
-    check(lib().d3pm_op_attention(dtype_code(q.dtype), family, _p(q), q.stride(1), _p(k), _p(v), k.stride(1), _p(o), d,
-                                  B, Tq, S, n_heads, d // n_heads, float(scale), C.byref(TUNING), stream_ptr()),
-          "d3pm_op_attention")
+    if key_len is None:
+        check(lib().d3pm_op_attention(dtype_code(q.dtype), family, _p(q), q.stride(1), _p(k), _p(v), k.stride(1), _p(o), d,
+                                      B, Tq, S, n_heads, d // n_heads, float(scale), C.byref(TUNING), stream_ptr()),
+              "d3pm_op_attention")
+        return o
+    if key_len.dtype != torch.int32 or key_len.shape != (B,) or key_len.device != q.device or not key_len.is_contiguous():
+        raise D3PMError(f"key_len must be a contiguous int32 [{B}] tensor on {q.device}")
+    check(lib().d3pm_op_attention_keylen(dtype_code(q.dtype), family, _p(q), q.stride(1), _p(k), _p(v), k.stride(1), _p(o), d,
+                                         B, Tq, S, n_heads, d // n_heads, float(scale), _p(key_len), C.byref(TUNING), stream_ptr()),
+          "d3pm_op_attention_keylen")
     return o
 
 
