@@ -56,7 +56,8 @@ extern "C" {
  *    (d3pm_sampling, d3pm_posterior_sample_sampling, d3pm_sample_loop_sampling); the nucleus (top-p) cut behind them
  *    (d3pm_nucleus, d3pm_posterior_sample_nucleus, d3pm_sample_loop_nucleus); the confidence-ordered reveal schedule
  *    (d3pm_reveal, d3pm_reveal_plan, d3pm_reveal_step, d3pm_reveal_loop); the per-utterance key mask at kernel level
- *    (d3pm_op_attention_keylen) */
+ *    (d3pm_op_attention_keylen); key-padding masks through the denoiser (d3pm_keys, d3pm_encode_conditions_keys,
+ *    d3pm_denoise_step_keys, d3pm_sample_loop_keys, d3pm_reveal_loop_keys, d3pm_op_attention_pair_keylen) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -551,6 +552,56 @@ int d3pm_reveal_loop(const d3pm_shape *shape, const d3pm_weights *weights, int b
                      size_t workspace_bytes, int32_t *trace, const d3pm_nucleus *nucleus, const d3pm_reveal *reveal,
                      void *stream);
 
+/* ---- key-padding masks (additions; ABI version unchanged) -------------------------------------------------------------------------
+ * Upstream lets every utterance attend to its own padding: the canvas - L_b padded frames are keys of every self-attention, the
+ * zero-padded phonemes and prompt frames are keys of both cross-attentions and of the two condition encoders.  With d3pm_keys
+ * utterance b has three key counts, device int32 [batch] each:
+ *   frames[b]   its live frames L_b            -> the keys of every DiT self-attention
+ *   text[b]     its phonemes, <= s_text        -> the keys of the text cross-attention and of the text encoder's self-attention
+ *   prompt[b]   its prompt frames, <= s_prompt -> the keys of the prompt cross-attention and of the prompt encoder's self-attention
+ * A masked key carries probability exactly 0; its K / V rows need not be read and never influence a result (large finite garbage
+ * there changes nothing; NaN is outside the contract).  Padded rows stay queries: no row of work is skipped and their outputs are
+ * masked or trimmed as without d3pm_keys; the frame-mask multiply, the sampling of padded rows, the Philox keys, known frames,
+ * sampling options and the reveal quota are unchanged.  The live rows of utterance b therefore compute what the model computes at
+ * canvas = L_b, s_text = text[b], s_prompt = prompt[b] -- within accumulation order, not bit for bit: the MFMA kernels tile the keys
+ * by the padded counts' grid, and padded rows, being queries, share a wave with live rows, where the flash kernels decide per wave
+ * whether the running maximum moves.  Bit for bit it holds on the generic family (D3PM_FLAG_FORCE_GENERIC, fp32).
+ * Contract (the values live on the device and are read by the kernels only, so nothing here can refuse them):
+ *   1 <= frames[b] <= canvas, 1 <= text[b] <= s_text, 1 <= prompt[b] <= s_prompt, and frames[b] = the number of leading ones of
+ *   frame_mask[b] (the live frames are a prefix of the canvas).
+ * A shard or a stream chunk that starts at utterance u passes the three pointers offset by u.  Any of the three may be NULL (that
+ * attention is not masked); a NULL d3pm_keys is the entry that is generalised and launches the very same kernels.  A masked
+ * evaluation takes the schedules of the unmasked one (same regime rule): the mask does not switch the instruction shape.  There are
+ * no fp8 entries: d3pm_sample_loop_keys refuses keys together with fp8_blocks (D3PM_E_ARG).  The training step takes no mask. */
+typedef struct d3pm_keys {
+  const int32_t *frames, *text, *prompt;      /* device int32 [batch] each */
+} d3pm_keys;
+
+/* d3pm_encode_conditions with keys->text / keys->prompt on the two encoders' self-attentions (keys->frames is not read).  The ids
+ * behind a length are not read: those rows are embedded as padding (text: id 0; prompt: every level absent), so nothing that
+ * `text` / `prompt` hold there reaches a result, in any bit.  (The rows stay queries of their encoder, and a query row can move the
+ * last bit of a live row it shares a wave with; that is why the padding is made here and not left to the caller.) */
+int d3pm_encode_conditions_keys(const d3pm_shape *shape, const d3pm_cond_weights *cw, int batch, const int32_t *text,
+                                const int32_t *prompt, void *cond_text, void *cond_prompt, void *workspace,
+                                size_t workspace_bytes, const d3pm_keys *keys, void *stream);
+/* d3pm_denoise_step_canvas + keys */
+int d3pm_denoise_step_keys(const d3pm_shape *shape, const d3pm_weights *w, int batch, const int32_t *x_t,
+                           const d3pm_canvas *canvas, int t, const void *film, const void *kv_text, const void *kv_prompt,
+                           void *workspace, size_t workspace_bytes, void *logits_out, void *hidden_out, int only_layers,
+                           uint32_t flags, const d3pm_keys *keys, void *stream);
+/* d3pm_sample_loop_nucleus + keys */
+int d3pm_sample_loop_keys(const d3pm_shape *shape, const d3pm_weights *weights, const d3pm_fp8_block_weights *fp8_blocks, int batch,
+                          int32_t *x, const uint8_t *frame_mask, const d3pm_canvas *canvas, int t_start, int t_stop,
+                          const void *film, const void *kv_text, const void *kv_prompt, const d3pm_schedule *sched, uint64_t seed,
+                          uint32_t utt0, uint32_t flags, void *workspace, size_t workspace_bytes, int32_t *trace,
+                          const d3pm_nucleus *nucleus, const d3pm_keys *keys, void *stream);
+/* d3pm_reveal_loop + keys */
+int d3pm_reveal_loop_keys(const d3pm_shape *shape, const d3pm_weights *weights, int batch, int32_t *x, const uint8_t *frame_mask,
+                          const d3pm_canvas *canvas, const void *film, const void *kv_text, const void *kv_prompt,
+                          const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
+                          size_t workspace_bytes, int32_t *trace, const d3pm_nucleus *nucleus, const d3pm_reveal *reveal,
+                          const d3pm_keys *keys, void *stream);
+
 /* Replaces AR.q_sample / q_probs (ar_discrete.py:467-502): forward noising of x0 at step t with
  * Philox stream 1.  x0, x_out device int32 [batch][canvas]. */
 int d3pm_q_sample(const d3pm_shape *shape, int batch, const int32_t *x0, int32_t *x_out,
@@ -662,8 +713,10 @@ int d3pm_op_attention(int dtype, int family, const void *Q, int ldq, const void 
 /* d3pm_op_attention with the per-utterance key mask of the stock NAR attention: key_len (device int32 [B]) = the number of valid
  * keys of each utterance, keys >= key_len[b] are masked out and S is the padded key count (the row stride of the K / V batches);
  * NULL = d3pm_op_attention.  1 <= key_len[b] <= S is the caller's contract: the values live on the device and are read by the
- * kernels only, so nothing here can refuse them.  Family 2 runs the schedules that take a mask (attn_query_groups 1 / 2; a request
- * for 4 / 32 / 33 falls back to the automatic choice between those two). */
+ * kernels only, so nothing here can refuse them.  Family 2: attn_query_groups 0 keeps the automatic choice between one and two
+ * query groups of the 16 x 16 x 32 kernel (a masked call never moves to the 32 x 32 x 16 kernel by itself); 1 / 2 name them; 32 / 33
+ * take the masked 32 x 32 x 16 kernels (pipelined / plain walk) where the shape is eligible -- Tq a multiple of 128 and S of 64 --
+ * and fall back to the automatic choice elsewhere; 4 (the key-split kernel) refuses a mask and falls back likewise. */
 int d3pm_op_attention_keylen(int dtype, int family, const void *Q, int ldq, const void *K, const void *V, int ldkv, void *O, int ldo,
                              int B, int Tq, int S, int H, int hd, float scale, const int32_t *key_len, const d3pm_tuning *tuning,
                              void *stream);
@@ -673,6 +726,13 @@ int d3pm_op_attention_keylen(int dtype, int family, const void *Q, int ldq, cons
 int d3pm_op_attention_pair(int dtype, const void *Q1, const void *K1, const void *V1, void *O1, int S1, const void *Q2,
                            const void *K2, const void *V2, void *O2, int S2, int ldq, int ldkv, int ldo, int B, int Tq, int H,
                            int hd, float scale, const d3pm_tuning *tuning, void *stream);
+/* d3pm_op_attention_pair with a key mask per problem: key_len1 / key_len2 (device int32 [B], either may be NULL) = the valid keys
+ * among the S1 / S2 padded ones, which stay the row strides of the K / V batches.  Contract as d3pm_op_attention_keylen.  Every
+ * pair schedule takes the masks except the key-split kernel (attn_query_groups = 4), which falls back to the tile-by-tile pair. */
+int d3pm_op_attention_pair_keylen(int dtype, const void *Q1, const void *K1, const void *V1, void *O1, int S1, const void *Q2,
+                                  const void *K2, const void *V2, void *O2, int S2, int ldq, int ldkv, int ldo, int B, int Tq,
+                                  int H, int hd, float scale, const int32_t *key_len1, const int32_t *key_len2,
+                                  const d3pm_tuning *tuning, void *stream);
 int d3pm_op_layernorm(int dtype, const void *X, void *Y, const void *w, const void *b, const void *film,
                       int M, int d, float eps, void *stream);
 /* Row-panel projection (d_model = 512): a Linear whose output is added to the residual stream, together with the LayerNorm(s)

@@ -136,9 +136,9 @@ static int run_attention(const Ctx& cx, int dtype, AttnArgs a, uint32_t flags, h
   if (!(flags & D3PM_FLAG_FORCE_GENERIC) && mfma_attention_supported(dtype, a)) return mfma_attention(dtype, a, s);
   if (a.Q2) {   // the generic kernel takes one problem per launch
     AttnArgs first = a, second = a;
-    first.Q2 = first.K2 = first.V2 = nullptr; first.O2 = nullptr; first.S2 = 0;
+    first.Q2 = first.K2 = first.V2 = nullptr; first.O2 = nullptr; first.S2 = 0; first.key_len2 = nullptr;
     second = first;
-    second.Q = a.Q2; second.K = a.K2; second.V = a.V2; second.O = a.O2; second.S = a.S2;
+    second.Q = a.Q2; second.K = a.K2; second.V = a.V2; second.O = a.O2; second.S = a.S2; second.key_len = a.key_len2;
     int rc = generic_attention(dtype, first, s);
     return rc != D3PM_OK ? rc : generic_attention(dtype, second, s);
   }
@@ -308,9 +308,25 @@ static CanvasMask per_utterance_mask(const d3pm_shape* sh, int batch, const d3pm
   return CanvasMask{cv->frame_mask, batch * sh->canvas, with_known ? cv->known : nullptr};
 }
 
+// d3pm_keys of a call (all null without one): the key counts of the self-attention and of the two cross-attentions
+struct KeyCounts {
+  const int32_t *frames = nullptr, *text = nullptr, *prompt = nullptr;
+};
+static KeyCounts key_counts(const d3pm_keys* k) { return k ? KeyCounts{k->frames, k->text, k->prompt} : KeyCounts{}; }
+// a masked self-attention of the denoiser: the schedule of the unmasked one
+static AttnArgs with_frame_keys(AttnArgs a, const KeyCounts& kc) {
+  a.key_len = kc.frames; a.masked_keeps_schedule = kc.frames != nullptr;
+  return a;
+}
+static AttnArgs with_cond_keys(AttnArgs a, const KeyCounts& kc) {
+  a.key_len = kc.text; a.key_len2 = kc.prompt;
+  return a;
+}
+
 struct DenoiserArgs {      // what every block of one evaluation sees
   const d3pm_shape& sh; const d3pm_weights& w; int batch; const uint8_t* frame_mask; int mask_period; const void* kv_text; const void* kv_prompt;
   const Workspace& ws;
+  KeyCounts keys = {};
 };
 
 // ---- the block sequence with the LayerNorms folded into the projections (ar_discrete.py:126-161; d3pm_mfma_tile.h EPI_LNF / EPI_STATS)
@@ -336,13 +352,14 @@ static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v) {
   };
   // ---- self-attention ----
   D3PM_TRY(consumer(f.qkv_w, f.qkv_s, f.qkv_b, ws.qkv, 3 * d, ACT_NONE));
-  D3PM_TRY(v.attention(self_attention(ws.qkv, ws.att, q.batch, T, H, hd, es)));
+  D3PM_TRY(v.attention(with_frame_keys(self_attention(ws.qkv, ws.att, q.batch, T, H, hd, es), q.keys)));
   D3PM_TRY(v.linear(producer(ws.att, d, b.attn_out_w, b.attn_out_b)));
   // ---- cross-attention: q_text | q_prompt are the two halves of ONE [n][2d] projection of x (the same q rows under norm2 / norm22)
   D3PM_TRY(consumer(f.q2_w, f.q2_s, f.q2_b, ws.qkv, 2 * d, ACT_NONE));
   const void* kvt = at(q.kv_text, static_cast<size_t>(l) * q.batch * sh.s_text * 2 * d, es);
   const void* kvp = at(q.kv_prompt, static_cast<size_t>(l) * q.batch * sh.s_prompt * 2 * d, es);
-  D3PM_TRY(v.attention(cross_attention_pair(ws.qkv, at(ws.qkv, d, es), 2 * d, kvt, sh.s_text, kvp, sh.s_prompt, ws.att, ws.att2, q.batch, T, H, hd, es)));
+  D3PM_TRY(v.attention(with_cond_keys(cross_attention_pair(ws.qkv, at(ws.qkv, d, es), 2 * d, kvt, sh.s_text, kvp, sh.s_prompt, ws.att, ws.att2, q.batch, T, H, hd, es),
+                                      q.keys)));
   // ---- x = (x + o_text) + o_prompt, rounded at each add like the eager sum ----
   LinearArgs g = producer(ws.att, d, b.cross_out_w, b.cross_out_b);
   g.tune = sh.tuning;      // big_dual_supported reads it
@@ -529,7 +546,7 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
       D3PM_TRY(ln_linear(norm1_done, ln, lp, projection(ws.h, b.attn_in_w, b.attn_in_b, ws.qkv, n, 3 * d, d)));
     }
     norm1_done = false;
-    D3PM_TRY(run_attention(cx, dt, self_attention(ws.qkv, ws.att, batch, T, H, hd, es), flags, s));
+    D3PM_TRY(run_attention(cx, dt, with_frame_keys(self_attention(ws.qkv, ws.att, batch, T, H, hd, es), q.keys), flags, s));
     LinearArgs g = with_residual(projection(ws.att, b.attn_out_w, b.attn_out_b, ws.x, n, d, d), ws.x);
     // ---- cross-attention: text keys with LN2 queries, prompt keys with LN22 queries, SAME weights ----
     ln = layernorm(b.norm2_w, b.norm2_b);
@@ -567,7 +584,7 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
     {   // text and prompt cross-attention are independent: one paired launch
       const void* kvt = at(q.kv_text, static_cast<size_t>(l) * batch * sh.s_text * 2 * d, es);
       const void* kvp = at(q.kv_prompt, static_cast<size_t>(l) * batch * sh.s_prompt * 2 * d, es);
-      D3PM_TRY(run_attention(cx, dt, cross_attention_pair(q_text, q_prom, d, kvt, sh.s_text, kvp, sh.s_prompt, ws.att, ws.att2, batch, T, H, hd, es),
+      D3PM_TRY(run_attention(cx, dt, with_cond_keys(cross_attention_pair(q_text, q_prom, d, kvt, sh.s_text, kvp, sh.s_prompt, ws.att, ws.att2, batch, T, H, hd, es), q.keys),
                              flags, s));
     }
     // ---- both out-projections, then the FiLM-modulated MLP ----
@@ -805,15 +822,17 @@ static CondWs carve_cond(const d3pm_shape& sh, const d3pm_cond_weights& cw, int 
 }
 
 // x (ws.x, [rows][d]) -> out ([rows][d]); `seq` rows per utterance
+// key_len: the valid rows of each utterance (d3pm_keys.text / .prompt) or null: the keys of the encoder's self-attention
 static int run_encoder(const d3pm_shape& sh, const d3pm_encoder_weights& e, int batch, int seq, const CondWs& ws, void* out,
-                       hipStream_t s) {
+                       const int32_t* key_len, hipStream_t s) {
   const int dt = sh.dtype, d = sh.d_model, n = batch * seq, hd = d / e.n_heads;
   const size_t es = dtype_size(dt);
   const Ctx cx(sh.tuning);
   for (int l = 0; l < e.n_layers; ++l) {
     const d3pm_encoder_layer_weights& w = e.layers[l];
     D3PM_TRY(run_linear(cx, dt, projection(ws.x, w.in_w, w.in_b, ws.qkv, n, 3 * d, d), 0, s));
-    const AttnArgs a = self_attention(ws.qkv, ws.att, batch, seq, e.n_heads, hd, es);
+    AttnArgs a = self_attention(ws.qkv, ws.att, batch, seq, e.n_heads, hd, es);
+    a.key_len = key_len; a.masked_keeps_schedule = key_len != nullptr;
     if (encoder_pads_heads(sh, e) && ws.qkv_pad) {
       D3PM_TRY(pad_heads(ws.qkv, ws.qkv_pad, n, 3 * e.n_heads, hd, s));
       AttnArgs p = a;
@@ -850,9 +869,9 @@ size_t d3pm_cond_workspace_bytes(const d3pm_shape* sh, const d3pm_cond_weights* 
   return carve_cond(*sh, *cw, batch, nullptr).total;
 }
 
-int d3pm_encode_conditions(const d3pm_shape* sh, const d3pm_cond_weights* cw, int batch, const int32_t* text,
-                           const int32_t* prompt, void* cond_text, void* cond_prompt, void* workspace,
-                           size_t workspace_bytes, void* stream) {
+static int encode_conditions_impl(const d3pm_shape* sh, const d3pm_cond_weights* cw, int batch, const int32_t* text,
+                                  const int32_t* prompt, void* cond_text, void* cond_prompt, void* workspace,
+                                  size_t workspace_bytes, const KeyCounts& keys, void* stream) {
   D3PM_TRY(check_shape(sh, batch));
   D3PM_REQUIRE(cw && text && prompt && cond_text && cond_prompt && workspace && cw->text_emb && cw->proms_emb &&
                    cw->pe_text0 && cw->pe_prompt && cw->n_levels > 0,
@@ -862,17 +881,30 @@ int d3pm_encode_conditions(const d3pm_shape* sh, const d3pm_cond_weights* cw, in
   CondWs ws = carve_cond(*sh, *cw, batch, static_cast<char*>(workspace));
   D3PM_REQUIRE(workspace_bytes >= ws.total, D3PM_E_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, ws.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  D3PM_TRY(cond_embed_text(sh->dtype, text, cw->text_emb, cw->pe_text0, ws.x, batch * sh->s_text, sh->d_model, sh->n_classes, s));
-  D3PM_TRY(run_encoder(*sh, cw->text_encoder, batch, sh->s_text, ws, cond_text, s));
+  D3PM_TRY(cond_embed_text(sh->dtype, text, cw->text_emb, cw->pe_text0, ws.x, batch * sh->s_text, sh->s_text, sh->d_model, sh->n_classes,
+                           keys.text, s));
+  D3PM_TRY(run_encoder(*sh, cw->text_encoder, batch, sh->s_text, ws, cond_text, keys.text, s));
   D3PM_TRY(cond_embed_prompt(sh->dtype, prompt, cw->n_levels, cw->proms_emb, cw->pe_prompt, ws.x, batch * sh->s_prompt,
-                             sh->s_prompt, sh->d_model, sh->n_classes, s));
-  return run_encoder(*sh, cw->prompt_encoder, batch, sh->s_prompt, ws, cond_prompt, s);
+                             sh->s_prompt, sh->d_model, sh->n_classes, keys.prompt, s));
+  return run_encoder(*sh, cw->prompt_encoder, batch, sh->s_prompt, ws, cond_prompt, keys.prompt, s);
+}
+
+int d3pm_encode_conditions(const d3pm_shape* sh, const d3pm_cond_weights* cw, int batch, const int32_t* text,
+                           const int32_t* prompt, void* cond_text, void* cond_prompt, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  return encode_conditions_impl(sh, cw, batch, text, prompt, cond_text, cond_prompt, workspace, workspace_bytes, KeyCounts{}, stream);
+}
+
+int d3pm_encode_conditions_keys(const d3pm_shape* sh, const d3pm_cond_weights* cw, int batch, const int32_t* text,
+                                const int32_t* prompt, void* cond_text, void* cond_prompt, void* workspace,
+                                size_t workspace_bytes, const d3pm_keys* keys, void* stream) {
+  return encode_conditions_impl(sh, cw, batch, text, prompt, cond_text, cond_prompt, workspace, workspace_bytes, key_counts(keys), stream);
 }
 
 static int denoise_step_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, const int32_t* x_t,
                              const CanvasMask& cm, int t, const void* film, const void* kv_text, const void* kv_prompt,
                              void* workspace, size_t workspace_bytes, void* logits_out, void* hidden_out, int only_layers,
-                             uint32_t flags, void* stream, const d3pm_fp8_block_weights* f8) {
+                             uint32_t flags, void* stream, const d3pm_fp8_block_weights* f8, const KeyCounts& keys = KeyCounts{}) {
   D3PM_TRY(check_shape(sh, batch));
   D3PM_REQUIRE(w && w->blocks && x_t && cm.frame_mask && film && kv_text && kv_prompt && workspace, D3PM_E_ARG,
                "d3pm_denoise_step: null pointer");
@@ -881,7 +913,7 @@ static int denoise_step_impl(const d3pm_shape* sh, const d3pm_weights* w, int ba
   D3PM_REQUIRE(workspace_bytes >= ws.total, D3PM_E_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, ws.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int layers = (only_layers >= 0 && only_layers < sh->n_layers) ? only_layers : sh->n_layers;
-  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws};
+  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, keys};
   D3PM_TRY(denoiser_blocks(q, x_t, t, film, layers, flags, s, f8, fold_plan(q, flags, f8)));
   if (hidden_out)
     D3PM_CHECK_HIP(hipMemcpyAsync(hidden_out, ws.x, static_cast<size_t>(batch) * sh->canvas * sh->d_model * dtype_size(sh->dtype),
@@ -909,6 +941,14 @@ int d3pm_denoise_step_canvas(const d3pm_shape* sh, const d3pm_weights* w, int ba
   D3PM_REQUIRE(canvas, D3PM_E_ARG, "d3pm_denoise_step_canvas: null canvas");
   return denoise_step_impl(sh, w, batch, x_t, per_utterance_mask(sh, batch, canvas, false), t, film, kv_text, kv_prompt, workspace, workspace_bytes,
                            logits_out, hidden_out, only_layers, flags, stream, nullptr);
+}
+
+int d3pm_denoise_step_keys(const d3pm_shape* sh, const d3pm_weights* w, int batch, const int32_t* x_t, const d3pm_canvas* canvas, int t,
+                           const void* film, const void* kv_text, const void* kv_prompt, void* workspace, size_t workspace_bytes,
+                           void* logits_out, void* hidden_out, int only_layers, uint32_t flags, const d3pm_keys* keys, void* stream) {
+  D3PM_REQUIRE(canvas, D3PM_E_ARG, "d3pm_denoise_step_keys: null canvas");
+  return denoise_step_impl(sh, w, batch, x_t, per_utterance_mask(sh, batch, canvas, false), t, film, kv_text, kv_prompt, workspace, workspace_bytes,
+                           logits_out, hidden_out, only_layers, flags, stream, nullptr, key_counts(keys));
 }
 
 int d3pm_denoise_step_fp8(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch,
@@ -991,7 +1031,7 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
                             int t_start, int t_stop, const void* film, const void* kv_text, const void* kv_prompt,
                             const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace,
                             size_t workspace_bytes, int32_t* trace, void* stream, const d3pm_fp8_block_weights* f8,
-                            const d3pm_nucleus* sm = nullptr, const char* who = "d3pm_sample_loop_sampling") {
+                            const d3pm_nucleus* sm = nullptr, const char* who = "d3pm_sample_loop_sampling", const KeyCounts& keys = KeyCounts{}) {
   D3PM_TRY(check_shape(sh, batch));
   D3PM_TRY(check_sampling(sh, sm, who));
   D3PM_REQUIRE(w && w->blocks && x && cm.frame_mask && film && kv_text && kv_prompt && sched && workspace, D3PM_E_ARG,
@@ -1003,7 +1043,7 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rows = batch * sh->canvas;
   const Ctx cx(sh->tuning);
-  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws};
+  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, keys};
   const int plan = fold_plan(q, flags, f8);      // the same for every iteration: the blocks and the sampler's prep share it
   bool prepared = false;      // the previous iteration's sampler launch has already embedded x_t and folded fc1 for this t
   for (int t = t_start; t > t_stop; --t) {
@@ -1112,6 +1152,19 @@ int d3pm_sample_loop_nucleus(const d3pm_shape* sh, const d3pm_weights* w, const 
                           "d3pm_sample_loop_nucleus");
 }
 
+int d3pm_sample_loop_keys(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch, int32_t* x,
+                          const uint8_t* frame_mask, const d3pm_canvas* canvas, int t_start, int t_stop, const void* film,
+                          const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                          uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus,
+                          const d3pm_keys* keys, void* stream) {
+  D3PM_REQUIRE(sh && (frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
+               "d3pm_sample_loop_keys: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)");
+  D3PM_REQUIRE(!(keys && fp8_blocks), D3PM_E_ARG, "d3pm_sample_loop_keys: the fp8 fast path takes no key mask");
+  return sample_loop_impl(sh, w, batch, x, canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask), t_start, t_stop,
+                          film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks, nucleus,
+                          "d3pm_sample_loop_keys", key_counts(keys));
+}
+
 // ---- confidence-ordered reveal (d3pm_reveal) ------------------------------------------------------------------------------------------
 int d3pm_reveal_plan(const d3pm_schedule* sched, int n_steps, int32_t* t_out) {
   D3PM_REQUIRE(sched && t_out, D3PM_E_ARG, "d3pm_reveal_plan: null pointer");
@@ -1163,9 +1216,10 @@ int d3pm_reveal_step(const d3pm_shape* sh, int batch, const void* logits, int lo
   return reveal_commit(a, s);
 }
 
-int d3pm_reveal_loop(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
+static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
                      const void* film, const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags,
-                     void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus, const d3pm_reveal* reveal, void* stream) {
+                     void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus, const d3pm_reveal* reveal,
+                     const KeyCounts& keys, void* stream) {
   D3PM_REQUIRE(reveal, D3PM_E_ARG, "d3pm_reveal_loop: null d3pm_reveal");
   D3PM_TRY(check_reveal(sh, batch, sched, reveal->choice_temperature, flags, "d3pm_reveal_loop"));
   D3PM_TRY(check_sampling(sh, nucleus, "d3pm_reveal_loop"));
@@ -1188,7 +1242,7 @@ int d3pm_reveal_loop(const d3pm_shape* sh, const d3pm_weights* w, int batch, int
   hipStream_t s = static_cast<hipStream_t>(stream);
   const CanvasMask cm = canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask);
   const Ctx cx(sh->tuning);
-  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws};
+  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, keys};
   const int plan = fold_plan(q, flags, nullptr);
   bool prepared = false;
   int32_t* cur = x;      // where x_t of the step lives: the fused launch cannot store in place, so it alternates between x and x_alt
@@ -1230,6 +1284,21 @@ int d3pm_reveal_loop(const d3pm_shape* sh, const d3pm_weights* w, int batch, int
   }
   if (cx.prof) cx.prof->sample_now = false;
   return D3PM_OK;      // the last step is never fused (no next evaluation): the result is in x
+}
+
+int d3pm_reveal_loop(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
+                     const void* film, const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags,
+                     void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus, const d3pm_reveal* reveal, void* stream) {
+  return reveal_loop_impl(sh, w, batch, x, frame_mask, canvas, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          nucleus, reveal, KeyCounts{}, stream);
+}
+
+int d3pm_reveal_loop_keys(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
+                          const void* film, const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                          uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus,
+                          const d3pm_reveal* reveal, const d3pm_keys* keys, void* stream) {
+  return reveal_loop_impl(sh, w, batch, x, frame_mask, canvas, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          nucleus, reveal, key_counts(keys), stream);
 }
 
 int d3pm_q_sample(const d3pm_shape* sh, int batch, const int32_t* x0, int32_t* x_out, const uint8_t* frame_mask, int t,
@@ -1408,9 +1477,10 @@ int d3pm_op_attention_keylen(int dtype, int family, const void* Q, int ldq, cons
                            stream);
 }
 
-int d3pm_op_attention_pair(int dtype, const void* Q1, const void* K1, const void* V1, void* O1, int S1, const void* Q2, const void* K2,
-                           const void* V2, void* O2, int S2, int ldq, int ldkv, int ldo, int B, int Tq, int H, int hd, float scale,
-                           const d3pm_tuning* tuning, void* stream) {
+// key_len1 / key_len2 (device, [B]) are read by the kernels only: see d3pm_op_attention_keylen
+int d3pm_op_attention_pair_keylen(int dtype, const void* Q1, const void* K1, const void* V1, void* O1, int S1, const void* Q2, const void* K2,
+                                  const void* V2, void* O2, int S2, int ldq, int ldkv, int ldo, int B, int Tq, int H, int hd, float scale,
+                                  const int32_t* key_len1, const int32_t* key_len2, const d3pm_tuning* tuning, void* stream) {
   D3PM_REQUIRE(Q1 && K1 && V1 && O1 && Q2 && K2 && V2 && O2 && B > 0 && Tq > 0 && S1 > 0 && S2 > 0 && H > 0 && hd > 0, D3PM_E_ARG,
                "d3pm_op_attention_pair: bad arguments");
   const Ctx cx(tuning);
@@ -1419,7 +1489,15 @@ int d3pm_op_attention_pair(int dtype, const void* Q1, const void* K1, const void
   a.Q = Q1; a.ldq = ldq; a.K = K1; a.V = V1; a.ldkv = ldkv; a.O = O1; a.ldo = ldo; a.B = B; a.Tq = Tq; a.S = S1; a.H = H;
   a.hd = hd; a.scale = scale;
   a.Q2 = Q2; a.K2 = K2; a.V2 = V2; a.O2 = O2; a.S2 = S2;
+  a.key_len = key_len1; a.key_len2 = key_len2;
   return run_attention(cx, dtype, a, 0, static_cast<hipStream_t>(stream));
+}
+
+int d3pm_op_attention_pair(int dtype, const void* Q1, const void* K1, const void* V1, void* O1, int S1, const void* Q2, const void* K2,
+                           const void* V2, void* O2, int S2, int ldq, int ldkv, int ldo, int B, int Tq, int H, int hd, float scale,
+                           const d3pm_tuning* tuning, void* stream) {
+  return d3pm_op_attention_pair_keylen(dtype, Q1, K1, V1, O1, S1, Q2, K2, V2, O2, S2, ldq, ldkv, ldo, B, Tq, H, hd, scale, nullptr, nullptr,
+                                       tuning, stream);
 }
 
 int d3pm_op_layernorm(int dtype, const void* X, void* Y, const void* w, const void* b, const void* film, int M, int d,
@@ -1487,9 +1565,9 @@ int d3pm_op_cond_embed(int dtype, int which, const int32_t* tokens, int n_levels
                        int s_prompt, int d, int n_classes, void* stream) {
   D3PM_REQUIRE(tokens && tables && pe && y && rows > 0 && d > 0 && n_classes > 0, D3PM_E_ARG, "d3pm_op_cond_embed: bad arguments");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (which == 0) return cond_embed_text(dtype, tokens, tables, pe, y, rows, d, n_classes, s);
+  if (which == 0) return cond_embed_text(dtype, tokens, tables, pe, y, rows, rows, d, n_classes, nullptr, s);
   D3PM_REQUIRE(n_levels > 0 && s_prompt > 0, D3PM_E_ARG, "d3pm_op_cond_embed: bad prompt arguments");
-  return cond_embed_prompt(dtype, tokens, n_levels, tables, pe, y, rows, s_prompt, d, n_classes, s);
+  return cond_embed_prompt(dtype, tokens, n_levels, tables, pe, y, rows, s_prompt, d, n_classes, nullptr, s);
 }
 
 void d3pm_tuning_default(d3pm_tuning* t) {

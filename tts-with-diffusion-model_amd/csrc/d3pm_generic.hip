@@ -248,23 +248,27 @@ __global__ __launch_bounds__(256) void attention_rows(const T* __restrict__ Q, i
 }
 
 // text condition rows: W[tok] + PE(position 0) (the x.shape[0] quirk, ar_discrete.py:89,741)
+// key_len (or null): row r of utterance b with r >= key_len[b] is padding -- id 0, whatever tok holds there (it is not read)
 template <typename T>
 __global__ void cond_text_rows(const int32_t* __restrict__ tok, const T* __restrict__ table, const T* __restrict__ pe0,
-                               T* __restrict__ y, int rows, int d, int n_classes) {
+                               T* __restrict__ y, int rows, int s_text, int d, int n_classes, const int32_t* __restrict__ key_len) {
   int row = blockIdx.x;
   if (row >= rows) return;
-  int id = tok[row];
+  int id = (key_len && row % s_text >= key_len[row / s_text]) ? 0 : tok[row];
   id = id < 0 ? 0 : (id >= n_classes ? n_classes - 1 : id);
   for (int c = threadIdx.x; c < d; c += blockDim.x)
     stf(y + static_cast<size_t>(row) * d + c, ldf(table + static_cast<size_t>(id) * d + c) + ldf(pe0 + c));
 }
 
 // prompt condition rows: sum over quantizer levels (fp32, one rounding: base.py:255-274) + PE(position) (ar_discrete.py:745)
+// key_len (or null): row r of utterance b with r >= key_len[b] is padding -- every level absent (PE only), its codes are not read
 template <typename T>
 __global__ void cond_prompt_rows(const int32_t* __restrict__ codes, int n_levels, const T* __restrict__ tables,
-                                 const T* __restrict__ pe, T* __restrict__ y, int rows, int s_prompt, int d, int n_classes) {
+                                 const T* __restrict__ pe, T* __restrict__ y, int rows, int s_prompt, int d, int n_classes,
+                                 const int32_t* __restrict__ key_len) {
   int row = blockIdx.x;
   if (row >= rows) return;
+  if (key_len && row % s_prompt >= key_len[row / s_prompt]) n_levels = 0;
   const int32_t* cr = codes + static_cast<size_t>(row) * n_levels;
   const T* per = pe + static_cast<size_t>(row % s_prompt) * d;
   for (int c = threadIdx.x; c < d; c += blockDim.x) {
@@ -315,24 +319,24 @@ int embed_tokens(int dtype, const EmbedArgs& a, hipStream_t s) {
   });
 }
 
-int cond_embed_text(int dtype, const int32_t* tok, const void* table, const void* pe0, void* y, int rows, int d,
-                    int n_classes, hipStream_t s) {
+int cond_embed_text(int dtype, const int32_t* tok, const void* table, const void* pe0, void* y, int rows, int s_text, int d,
+                    int n_classes, const int32_t* key_len, hipStream_t s) {
   return dispatch(dtype, [&](auto* tag) {
     using T = std::remove_pointer_t<decltype(tag)>;
     cond_text_rows<T><<<rows, d >= 256 ? 256 : 64, 0, s>>>(tok, static_cast<const T*>(table), static_cast<const T*>(pe0),
-                                                        static_cast<T*>(y), rows, d, n_classes);
+                                                        static_cast<T*>(y), rows, s_text, d, n_classes, key_len);
     D3PM_LAUNCH_CHECK();
     return D3PM_OK;
   });
 }
 
 int cond_embed_prompt(int dtype, const int32_t* codes, int n_levels, const void* tables, const void* pe, void* y,
-                      int rows, int s_prompt, int d, int n_classes, hipStream_t s) {
+                      int rows, int s_prompt, int d, int n_classes, const int32_t* key_len, hipStream_t s) {
   return dispatch(dtype, [&](auto* tag) {
     using T = std::remove_pointer_t<decltype(tag)>;
     cond_prompt_rows<T><<<rows, d >= 256 ? 256 : 64, 0, s>>>(codes, n_levels, static_cast<const T*>(tables),
                                                           static_cast<const T*>(pe), static_cast<T*>(y), rows, s_prompt,
-                                                          d, n_classes);
+                                                          d, n_classes, key_len);
     D3PM_LAUNCH_CHECK();
     return D3PM_OK;
   });

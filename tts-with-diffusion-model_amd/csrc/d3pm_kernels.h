@@ -82,6 +82,12 @@ struct AttnArgs {
   // optional second, independent problem with the same B / Tq / H / hd launched in the same grid
   // (the text and prompt cross-attentions of one DiT block): its own Q, K/V (S2 keys) and output
   const void* Q2 = nullptr; const void* K2 = nullptr; const void* V2 = nullptr; void* O2 = nullptr; int S2 = 0;
+  // the same mask for the second problem (device int32[B], 1 .. S2); key_len then belongs to the first problem alone
+  const int32_t* key_len2 = nullptr;
+  // set by the denoiser plan (d3pm_api.hip, d3pm_keys): a masked self-attention takes the automatic choice of the unmasked one,
+  // so switching the mask on does not switch the instruction shape.  Unset, a masked call with attn_query_groups = 0 keeps the
+  // 16 x 16 x 32 kernel it has always had (the stock NAR stage, d3pm_op_attention_keylen).
+  bool masked_keeps_schedule = false;
   const d3pm_tuning* tune = nullptr;
 };
 
@@ -169,13 +175,15 @@ int generic_attention_dropout_f32(const AttnArgs& a, const DropoutArgs& dr, hipS
 int generic_layernorm(int dtype, const LayerNormArgs& a, hipStream_t s);
 int embed_tokens(int dtype, const EmbedArgs& a, hipStream_t s);
 // condition-side embeddings: text rows = rn(W[tok] + pe0); prompt rows = rn(rn(sum_l W[l][tok_l]) + pe[s])
+// key_len (device int32 [rows / s_text] or [rows / s_prompt], or null): the rows of an utterance behind its length are padding --
+// text id 0, prompt every level absent -- and their ids are not read (d3pm_keys.text / .prompt)
 // head_dim hd -> 2 hd re-layout around an attention call (d3pm_headpad.hip): [rows][groups][hd] <-> [rows][groups][2 hd], zeros above
 int pad_heads(const void* in, void* out, long long rows, int groups, int hd, hipStream_t s);
 int unpad_heads(const void* in, void* out, long long rows, int groups, int hd, hipStream_t s);
-int cond_embed_text(int dtype, const int32_t* tok, const void* table, const void* pe0, void* y, int rows, int d,
-                    int n_classes, hipStream_t s);
+int cond_embed_text(int dtype, const int32_t* tok, const void* table, const void* pe0, void* y, int rows, int s_text, int d,
+                    int n_classes, const int32_t* key_len, hipStream_t s);
 int cond_embed_prompt(int dtype, const int32_t* codes, int n_levels, const void* tables, const void* pe, void* y,
-                      int rows, int s_prompt, int d, int n_classes, hipStream_t s);
+                      int rows, int s_prompt, int d, int n_classes, const int32_t* key_len, hipStream_t s);
 int posterior_sample(const SampleArgs& a, hipStream_t s);
 // What the sampler launch of iteration t can prepare for iteration t - 1 (folded-LayerNorm path, n_q = 1; d3pm_sample.hip): the
 // embedding row of every id it has just drawn + the row's moments (ar_discrete.py:753,127), and -- in workgroups behind the

@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
                                                       int Tq, int S, float scale, int H, int n_qblocks,
                                                       const T* __restrict__ Q2, const T* __restrict__ K2,
                                                       const T* __restrict__ V2, T* __restrict__ O2, int S2, int n_first,
-                                                      const int32_t* __restrict__ key_len) {
+                                                      const int32_t* __restrict__ key_len, const int32_t* __restrict__ key_len2) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE];   // [buffer][K tile | V tile]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // 1-D grid, XCD-aware order: workgroups are dealt round-robin over the 8 XCDs, so give each XCD a contiguous
@@ -148,11 +148,11 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
   const bool sequential = PAIR && n_first < 0;
   if (!sequential && bid >= n_first) {   // block-uniform
     bid -= n_first;
-    Q = Q2; Kp = K2; Vp = V2; O = O2; S = S2;
+    Q = Q2; Kp = K2; Vp = V2; O = O2; S = S2; key_len = key_len2;
   }
   const int qb = bid % n_qblocks, h = (bid / n_qblocks) % H, b = bid / (n_qblocks * H);
   for (int prob = 0; prob < (PAIR ? 2 : 1); ++prob) {
-  if (prob == 1) { Q = Q2; Kp = K2; Vp = V2; O = O2; S = S2; }
+  if (prob == 1) { Q = Q2; Kp = K2; Vp = V2; O = O2; S = S2; key_len = key_len2; }
   const int S_pad = S;                                 // row stride of the K/V batches
   if (key_len) S = min(key_len[b], S_pad);             // valid keys of this utterance (>= 1)
   const int q0 = (qb * 4 + wave) * (16 * QG);
@@ -437,12 +437,16 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // V reads -> 20 MFMAs), which two waves per SIMD do not cover.  Exactness: the prefetched product starts from the -m_ref of the
 // moment; when the softmax of tile i then moves m_ref (always on the first tile, otherwise only if a score exceeds it by 2^8)
 // the product of tile i + 1 is issued again from the new -m_ref, so every number is the one the plain walk computes.
-template <typename T, bool PIPE = false>
+// MASK: key_len1 / key_len2 (device int32 [B], either may be null) = the valid keys of utterance b among the S1 / S2 padded ones.
+// S1 / S2 stay the row strides of the batches; behind them the kernel is the unmasked one on the valid counts (only their tiles
+// are fetched, the ragged last tile is masked as ever).
+template <typename T, bool PIPE = false, bool MASK = false>
 __global__ __launch_bounds__(512, 2) void attn_cross_hd64(const T* __restrict__ Q1, const T* __restrict__ K1, const T* __restrict__ V1,
                                                           T* __restrict__ O1, int S1, const T* __restrict__ Q2,
                                                           const T* __restrict__ K2, const T* __restrict__ V2, T* __restrict__ O2,
                                                           int S2, int ldq, int ldkv, int ldo, int Tq, float scale, int H,
-                                                          int n_qblocks, int n_qsplit) {
+                                                          int n_qblocks, int n_qsplit, const int32_t* __restrict__ key_len1,
+                                                          const int32_t* __restrict__ key_len2) {
   constexpr int QG = 2, MAXT = 5;                            // 1 text tile + up to 4 prompt tiles
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [tile][K | V], 16 KiB per tile
   const int tid = threadIdx.x, lane = tid & 63;
@@ -455,6 +459,11 @@ __global__ __launch_bounds__(512, 2) void attn_cross_hd64(const T* __restrict__ 
   // a workgroup keeps the K / V image of its (utterance, head) and walks the query blocks qs, qs + n_qsplit, ..: at the
   // throughput batch n_qsplit = 1 -- one workgroup per CU, one DMA flight per (utterance, head) instead of one per query block
   const int qs = bid % n_qsplit, h = (bid / n_qsplit) % H, b = bid / (n_qsplit * H);
+  const int S1_pad = S1, S2_pad = S2;                        // row strides of the K / V batches
+  if constexpr (MASK) {
+    if (key_len1) S1 = min(key_len1[b], S1_pad);
+    if (key_len2) S2 = min(key_len2[b], S2_pad);
+  }
   const int nt2 = (S2 + BKV - 1) / BKV, n_tiles = 1 + nt2;
   // ---- every K / V piece of both problems: 16 pieces (1 KiB = 8 rows x 128 B) per tile, dealt over the 8 waves
   {
@@ -465,10 +474,10 @@ __global__ __launch_bounds__(512, 2) void attn_cross_hd64(const T* __restrict__ 
       const int row = 8 * j + lrow;
       const int logical = which == 0 ? (cpos ^ ((row >> 1) & 7)) : (cpos ^ (((row >> 1) & 3) << 1));
       const T* base = tile == 0 ? (which == 0 ? K1 : V1) : (which == 0 ? K2 : V2);
-      const int S = tile == 0 ? S1 : S2;
+      const int S = tile == 0 ? S1 : S2, S_pad = tile == 0 ? S1_pad : S2_pad;
       int key = (tile == 0 ? 0 : (tile - 1) * BKV) + row;
       key = key < S ? key : S - 1;
-      const T* src = base + (static_cast<size_t>(b) * S + key) * ldkv + h * HD + logical * 8;
+      const T* src = base + (static_cast<size_t>(b) * S_pad + key) * ldkv + h * HD + logical * 8;
       __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)(smem + tile * 2 * TILE + which * TILE + j * 1024), 16, 0, 0);
     }
   }
@@ -691,11 +700,14 @@ int mfma_attention(int dtype, const AttnArgs& a, hipStream_t s) {
 #else
     const bool arm35 = false;
 #endif
-    if ((q == 32 || q == 33 || arm35 || (q == 0 && wgs32 >= 512)) && mfma_attention32_supported(dtype, a)) return mfma_attention32(dtype, a, s);
+    // key lengths: the masked instantiations on an explicit 32 / 33, or where the denoiser plan asks for the unmasked choice
+    // (AttnArgs::masked_keeps_schedule); any other masked call keeps the kernel below, as it always has
+    const bool auto32 = q == 0 && wgs32 >= 512 && (a.key_len == nullptr || a.masked_keeps_schedule);
+    if ((q == 32 || q == 33 || (arm35 && a.key_len == nullptr) || auto32) && mfma_attention32_supported(dtype, a)) return mfma_attention32(dtype, a, s);
   }
   const long long cross_wgs = static_cast<long long>((a.Tq + 255) / 256) * a.H * (tn.regime_batch > 0 ? tn.regime_batch : a.B);
-  if ((g_attn_cross_resident >= 2 || (g_attn_cross_resident == 1 && cross_wgs >= 256)) && a.Q2 != nullptr && a.key_len == nullptr &&
-      a.S <= BKV && a.S2 <= 4 * BKV) {
+  // (key lengths do not change the choice: S / S2 are the padded counts, which size the LDS image)
+  if ((g_attn_cross_resident >= 2 || (g_attn_cross_resident == 1 && cross_wgs >= 256)) && a.Q2 != nullptr && a.S <= BKV && a.S2 <= 4 * BKV) {
     const int n_qblocks = (a.Tq + 255) / 256;
     int n_qsplit = (256 + a.H * a.B - 1) / (a.H * a.B);            // workgroups per (utterance, head): enough to cover the CUs
     n_qsplit = n_qsplit < 1 ? 1 : n_qsplit > n_qblocks ? n_qblocks : n_qsplit;
@@ -709,19 +721,23 @@ int mfma_attention(int dtype, const AttnArgs& a, hipStream_t s) {
       return mfma_attention32_cross(dtype, a, n_qsplit, s);
     const dim3 grid(static_cast<unsigned>(n_qsplit * a.H * a.B)), block(512);
     const size_t lds = static_cast<size_t>(1 + (a.S2 + BKV - 1) / BKV) * 2 * TILE;
-#define D3PM_CROSS(T, PIPE)                                                                                                  \
+#define D3PM_CROSS(T, PIPE, MASK)                                                                                            \
     do {                                                                                                                     \
-      D3PM_LDS_ATTR((&attn_cross_hd64<T, PIPE>), 5 * 2 * TILE);                                                              \
-      attn_cross_hd64<T, PIPE><<<grid, block, lds, s>>>(static_cast<const T*>(a.Q), static_cast<const T*>(a.K),               \
+      D3PM_LDS_ATTR((&attn_cross_hd64<T, PIPE, MASK>), 5 * 2 * TILE);                                                        \
+      attn_cross_hd64<T, PIPE, MASK><<<grid, block, lds, s>>>(static_cast<const T*>(a.Q), static_cast<const T*>(a.K),         \
           static_cast<const T*>(a.V), static_cast<T*>(a.O), a.S, static_cast<const T*>(a.Q2), static_cast<const T*>(a.K2),    \
-          static_cast<const T*>(a.V2), static_cast<T*>(a.O2), a.S2, a.ldq, a.ldkv, a.ldo, a.Tq, a.scale, a.H, n_qblocks, n_qsplit); \
+          static_cast<const T*>(a.V2), static_cast<T*>(a.O2), a.S2, a.ldq, a.ldkv, a.ldo, a.Tq, a.scale, a.H, n_qblocks, n_qsplit, \
+          a.key_len, a.key_len2);                                                                                            \
     } while (0)
+    if (a.key_len || a.key_len2) {
+      if (dtype == D3PM_F16) D3PM_CROSS(f16, false, true); else D3PM_CROSS(bf16, false, true);
+    } else
 #ifdef D3PM_ABLATIONS
     if (ab_knobs().attn_arm == 300) {      // A/B: the software-pipelined walk
-      if (dtype == D3PM_F16) D3PM_CROSS(f16, true); else D3PM_CROSS(bf16, true);
+      if (dtype == D3PM_F16) D3PM_CROSS(f16, true, false); else D3PM_CROSS(bf16, true, false);
     } else
 #endif
-    if (dtype == D3PM_F16) D3PM_CROSS(f16, false); else D3PM_CROSS(bf16, false);
+    if (dtype == D3PM_F16) D3PM_CROSS(f16, false, false); else D3PM_CROSS(bf16, false, false);
 #undef D3PM_CROSS
     D3PM_LAUNCH_CHECK();
     return D3PM_OK;
@@ -744,7 +760,7 @@ int mfma_attention(int dtype, const AttnArgs& a, hipStream_t s) {
                                                      static_cast<const T*>(a.V), a.ldkv, static_cast<T*>(a.O), a.ldo, a.Tq, \
                                                      a.S, a.scale, a.H, n_qblocks, static_cast<const T*>(a.Q2),           \
                                                      static_cast<const T*>(a.K2), static_cast<const T*>(a.V2),           \
-                                                     static_cast<T*>(a.O2), a.S2, n_first, a.key_len)
+                                                     static_cast<T*>(a.O2), a.S2, n_first, a.key_len, a.key_len2)
 #define D3PM_ATTN_QG(T)                                                                    \
   do {                                                                                     \
     if (seq) { if (qg == 1) D3PM_ATTN(T, 1, true); else D3PM_ATTN(T, 2, true); }           \
@@ -755,7 +771,7 @@ int mfma_attention(int dtype, const AttnArgs& a, hipStream_t s) {
     D3PM_ATTN(bf16, 3, false);
   } else if ((g_attn_qg == 164 || g_attn_qg == 228) && dtype == D3PM_BF16 && !a.Q2) {      // the QG = 2 kernel with ABL bit 6 / bit 7
 #define D3PM_ABL(A) attn_mfma_hd64<bf16, 2, false, A><<<grid, block, 0, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), \
-      static_cast<const bf16*>(a.V), a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, nullptr, nullptr, nullptr, nullptr, 0, n_first, a.key_len)
+      static_cast<const bf16*>(a.V), a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, nullptr, nullptr, nullptr, nullptr, 0, n_first, a.key_len, nullptr)
     if (g_attn_qg == 164) D3PM_ABL(64); else D3PM_ABL(128);
 #undef D3PM_ABL
   } else

@@ -83,10 +83,15 @@ __device__ __forceinline__ void store_rows32(T* row_base /* O + row * ldo + h * 
   }
 }
 
-template <typename T>
+// MASK (both self-attention kernels): key_len[b] of the S keys of utterance b are valid (d3pm_keys.frames; 1 .. S).  Only the
+// ceil(key_len[b] / 64) tiles that hold a valid key are walked -- staged whole: the padded canvas makes the rows exist -- and in the
+// one ragged tile the scores of the keys >= key_len[b] become -inf before the maximum (lane: key 32 kb + 8 j + 4 hh + r of the tile
+// <-> register 4 j + r), so they add exactly 0 to the row sum and to P . V.  With key_len[b] a multiple of 64 no score is touched:
+// the walk is the unmasked kernel's on S = key_len[b], bit for bit.  MASK = false is the code it was.
+template <typename T, bool MASK = false>
 __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, int ldq, const T* __restrict__ Kp,
                                                       const T* __restrict__ Vp, int ldkv, T* __restrict__ O, int ldo, int Tq,
-                                                      int S, float scale, int H, int n_qblocks) {
+                                                      int S, float scale, int H, int n_qblocks, const int32_t* __restrict__ key_len) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE];   // [buffer][K tile | V tile]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // XCD-aware order: each XCD gets a contiguous range of (utterance, head, query-block) ids, so the query blocks that share
@@ -140,7 +145,9 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
     *reinterpret_cast<uint4*>(base + TILE + vo1) = st.v1;
   };
 
-  const int n_tiles = S / BKV;
+  int n_keys = S;
+  if constexpr (MASK) n_keys = min(key_len[b], S);
+  const int n_tiles = MASK ? (n_keys + BKV - 1) / BKV : S / BKV;
   Staged st = load_tile(0);
   store_tile(smem, st);
   __syncthreads();
@@ -183,6 +190,15 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
         const uint4 kf = *reinterpret_cast<const uint4*>(kb_ + ok[ks] + kb * 32 * ROWB);
         s[kb] = mma32<T>(kf, qf[ks], ks == 0 ? negm : s[kb]);
       }
+    if constexpr (MASK) {
+      if (tile == n_tiles - 1 && (n_keys & (BKV - 1))) {   // wave-uniform: only the last tile can be partial
+        const int lim = n_keys - tile * BKV - 4 * hh;      // this lane's key 32 kb + 8 j + r of the tile exists iff it is < lim
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) s[kb][i] = (32 * kb + 8 * (i >> 2) + (i & 3) < lim) ? s[kb][i] : -INFINITY;
+      }
+    }
     float mx = fmaxf(s[0][0], s[1][0]);
 #pragma unroll
     for (int i = 1; i < 16; ++i) mx = fmaxf(fmaxf(mx, s[0][i]), s[1][i]);
@@ -259,10 +275,14 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
 // NW = waves (32-query groups) per workgroup: 4 = 128 queries, three workgroups per CU; 6 = 192 queries, two workgroups per CU --
 // the same twelve waves per CU, but every staged K / V tile serves half as many queries again (a third fewer bytes L2 -> LDS and
 // staging instructions per query; waves 4 and 5 do not stage).  A query's arithmetic does not depend on NW: bit-identical.
-template <typename T, int NW = 4>
+// MASK: see attn32_hd64.  The scores of a block are produced, and tested against the deferral threshold, inside the block in front of
+// it, so the mask is applied there (MSK, in front of the maximum): in the prologue (block 0), in the second block of the last tile
+// but one (first block of the last tile) and in the first block of the last tile (its second block), the latter two peeled out of
+// the loop.  A block of the last tile that lies wholly behind key_len[b] is walked with every score -inf: probabilities 0.
+template <typename T, int NW = 4, bool MASK = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T* __restrict__ Q, int ldq, const T* __restrict__ Kp,
                                                        const T* __restrict__ Vp, int ldkv, T* __restrict__ O, int ldo, int Tq,
-                                                       int S, float scale, int H, int n_qblocks) {
+                                                       int S, float scale, int H, int n_qblocks, const int32_t* __restrict__ key_len) {
   __shared__ __attribute__((aligned(16))) char smem[3 * 2 * TILE];   // [buffer][K tile | V tile]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int bid;
@@ -313,7 +333,15 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
     *reinterpret_cast<uint4*>(base + TILE + vo1) = st.v1;
   };
 
-  const int n_tiles = S / BKV;
+  int n_keys = S;
+  if constexpr (MASK) n_keys = min(key_len[b], S);
+  const int n_tiles = MASK ? (n_keys + BKV - 1) / BKV : S / BKV;
+  // MASK: this lane's key 8 j + r of the first block of the last tile exists iff 8 j + r < lim_last (of its second block: - 32)
+  const int lim_last = n_keys - (n_tiles - 1) * BKV - 4 * hh;
+  auto mask_scores = [](floatx16& s, int lim) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s[i] = (8 * (i >> 2) + (i & 3) < lim) ? s[i] : -INFINITY;
+  };
   if (stager) {
     Staged st = load_tile(0);
     store_tile(smem, st);
@@ -358,6 +386,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) sA = mma32<T>(kf[ks], qf[ks], ks == 0 ? negm : sA);
   read_k(smem + 32 * ROWB);
+  if constexpr (MASK) mask_scores(sA, n_keys - 4 * hh);      // block 0 (no score is touched from 32 keys on); key 0 always exists
   {
     float a, c;
     halves(row_max(sA), a, c);
@@ -375,10 +404,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
   // vblock = the 32 V rows of block j
   // STG: which half of the tile staged two ahead this block carries through registers (0 none, 1 the K rows, 2 the V rows): a
   // half lives in 8 registers for one block instead of the whole tile in 16 for two (three waves per SIMD: 168 registers)
-  auto block = [&](floatx16& sc, floatx16& sn, const char* vblock, const char* knext, auto NEXT_, auto STG_, int stile, char* sdst)
-      __attribute__((always_inline)) {
+  // MSK (masked kernel only): S(j + 1) belongs to the last tile; its keys from lim_next on become -inf in front of the maximum
+  auto block = [&](floatx16& sc, floatx16& sn, const char* vblock, const char* knext, auto NEXT_, auto STG_, int stile, char* sdst,
+                   auto MSK_, int lim_next) __attribute__((always_inline)) {
     constexpr bool NEXT = decltype(NEXT_)::value;
     constexpr int STG = decltype(STG_)::value;
+    constexpr bool MSK = decltype(MSK_)::value;
     typedef short4v __attribute__((address_space(3))) * lds_ptr;
     uint4 vf[2], pf, h0, h1;
     auto read_v = [&](int t, int db) __attribute__((always_inline)) {
@@ -439,6 +470,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
     SB();
     pv(0);
     float mx = 0.f;
+    if constexpr (NEXT && MSK) mask_scores(sn, lim_next);
     if constexpr (NEXT) mx = row_max(sn);
     SB();
     pv(1);
@@ -461,7 +493,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
         // block on the COMMON path
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          asm volatile("v_sub_f32 %0, %0, %1" : "+v"(sn[i]) : "v"(delta));
+          asm volatile("v_sub_f32 %0, %0, %1" : "+v"(sn[i]) : "v"(delta));      // -inf (a masked key) stays -inf
           asm volatile("v_mul_f32 %0, %0, %1" : "+v"(acc_o[0][i]) : "v"(alpha));
           asm volatile("v_mul_f32 %0, %0, %1" : "+v"(acc_o[1][i]) : "v"(alpha));
           asm volatile("v_mov_b32 %0, %1" : "+v"(negm[i]) : "v"(nm));
@@ -479,20 +511,44 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
   using St0 = std::integral_constant<int, 0>;
 
   int cur = 0, nx1 = 2 * TILE, nx2 = 4 * TILE;               // byte offsets of the buffers of tiles i, i + 1, i + 2
+  if constexpr (!MASK) {
   // every tile but the last: both blocks have a successor (one straight-line body: with the last tile's shorter second block
   // inside the loop hipcc moves the output accumulators between two register sets in every block)
   for (int i = 0; i + 1 < n_tiles; ++i) {
     const char* vb = smem + cur + TILE;
-    block(sA, sB, vb, smem + nx1, Yes{}, StK{}, i + 2, smem + nx2);                     // keys 0..31 of tile i; then K(tile i + 1, first half)
-    block(sB, sA, vb + 32 * ROWB, smem + nx1 + 32 * ROWB, Yes{}, StV{}, i + 2, smem + nx2);
+    block(sA, sB, vb, smem + nx1, Yes{}, StK{}, i + 2, smem + nx2, No{}, 0);            // keys 0..31 of tile i; then K(tile i + 1, first half)
+    block(sB, sA, vb + 32 * ROWB, smem + nx1 + 32 * ROWB, Yes{}, StV{}, i + 2, smem + nx2, No{}, 0);
     __syncthreads();
     const int t = cur;
     cur = nx1; nx1 = nx2; nx2 = t;
   }
   {
     const char* vb = smem + cur + TILE;
-    block(sA, sB, vb, smem, Yes{}, St0{}, 0, smem);           // (the K fragments read here are not used)
-    block(sB, sA, vb + 32 * ROWB, smem, No{}, St0{}, 0, smem);
+    block(sA, sB, vb, smem, Yes{}, St0{}, 0, smem, No{}, 0);  // (the K fragments read here are not used)
+    block(sB, sA, vb + 32 * ROWB, smem, No{}, St0{}, 0, smem, No{}, 0);
+  }
+  } else {
+  // the same walk with the last tile but one peeled as well: 1 tile = prologue + last; 2 = prologue + last but one + last; >= 3 = the
+  // loop in front.  The loop stages tile i + 2 <= n_tiles - 1 (always a tile that is walked); the peeled tiles stage nothing.
+  for (int i = 0; i + 2 < n_tiles; ++i) {
+    const char* vb = smem + cur + TILE;
+    block(sA, sB, vb, smem + nx1, Yes{}, StK{}, i + 2, smem + nx2, No{}, 0);
+    block(sB, sA, vb + 32 * ROWB, smem + nx1 + 32 * ROWB, Yes{}, StV{}, i + 2, smem + nx2, No{}, 0);
+    __syncthreads();
+    const int t = cur;
+    cur = nx1; nx1 = nx2; nx2 = t;
+  }
+  if (n_tiles > 1) {                                          // block-uniform
+    const char* vb = smem + cur + TILE;
+    block(sA, sB, vb, smem + nx1, Yes{}, St0{}, 0, smem, No{}, 0);
+    block(sB, sA, vb + 32 * ROWB, smem + nx1 + 32 * ROWB, Yes{}, St0{}, 0, smem, Yes{}, lim_last);
+    cur = nx1;                                                // (its buffer was complete behind the previous barrier: none needed here)
+  }
+  {
+    const char* vb = smem + cur + TILE;
+    block(sA, sB, vb, smem, Yes{}, St0{}, 0, smem, Yes{}, lim_last - 32);
+    block(sB, sA, vb + 32 * ROWB, smem, No{}, St0{}, 0, smem, No{}, 0);
+  }
   }
 #undef SB
 #undef EXP2
@@ -516,12 +572,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
 typedef const __attribute__((address_space(1))) void* glb_ptr32_t;
 typedef __attribute__((address_space(3))) void* lds_ptr32_t;
 
-template <typename T>
+// MASK: key_len1 / key_len2 (device int32 [B], either may be null) = the valid keys of utterance b among the S1 / S2 padded ones
+// (d3pm_keys.text / .prompt).  S1 / S2 stay the row strides of the batches; behind them the kernel is the unmasked one on the valid
+// counts -- only their tiles are fetched (rows clamped to the last valid key), the last block is masked through cmask.
+template <typename T, bool MASK = false>
 __global__ __launch_bounds__(512, 2) void attn32_cross_hd64(const T* __restrict__ Q1, const T* __restrict__ K1, const T* __restrict__ V1,
                                                             T* __restrict__ O1, int S1, const T* __restrict__ Q2,
                                                             const T* __restrict__ K2, const T* __restrict__ V2, T* __restrict__ O2,
                                                             int S2, int ldq, int ldkv, int ldo, int Tq, float scale, int H,
-                                                            int n_qblocks, int n_qsplit) {
+                                                            int n_qblocks, int n_qsplit, const int32_t* __restrict__ key_len1,
+                                                            const int32_t* __restrict__ key_len2) {
   extern __shared__ __attribute__((aligned(16))) char smem_x[];   // [tile][K | V], 16 KiB per tile: tile 0 = text, 1.. = prompt
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -531,6 +591,11 @@ __global__ __launch_bounds__(512, 2) void attn32_cross_hd64(const T* __restrict_
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
   const int qs = bid % n_qsplit, h = (bid / n_qsplit) % H, b = bid / (n_qsplit * H);
+  const int S1_pad = S1, S2_pad = S2;                        // row strides of the K / V batches
+  if constexpr (MASK) {
+    if (key_len1) S1 = min(key_len1[b], S1_pad);
+    if (key_len2) S2 = min(key_len2[b], S2_pad);
+  }
   const int nt2 = (S2 + BKV - 1) / BKV, n_tiles = 1 + nt2;
   {   // every K / V piece of both problems: 16 pieces (1 KiB = 8 rows x 128 B) per tile, dealt over the 8 waves
     const int lrow = lane >> 3, cpos = lane & 7;
@@ -540,10 +605,10 @@ __global__ __launch_bounds__(512, 2) void attn32_cross_hd64(const T* __restrict_
       const int row = 8 * j + lrow;
       const int logical = which == 0 ? (cpos ^ ((row >> 1) & 7)) : (cpos ^ (((row >> 1) & 1) << 2));
       const T* base = tile == 0 ? (which == 0 ? K1 : V1) : (which == 0 ? K2 : V2);
-      const int S = tile == 0 ? S1 : S2;
+      const int S = tile == 0 ? S1 : S2, S_pad = tile == 0 ? S1_pad : S2_pad;
       int key = (tile == 0 ? 0 : (tile - 1) * BKV) + row;
       key = key < S ? key : S - 1;
-      const T* src = base + (static_cast<size_t>(b) * S + key) * ldkv + h * HD + logical * 8;
+      const T* src = base + (static_cast<size_t>(b) * S_pad + key) * ldkv + h * HD + logical * 8;
       __builtin_amdgcn_global_load_lds((glb_ptr32_t)src, (lds_ptr32_t)(smem_x + tile * 2 * TILE + which * TILE + j * 1024), 16, 0, 0);
     }
   }
@@ -752,19 +817,20 @@ inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_
 
 }  // namespace
 
-// whole 128-query blocks and whole 64-key tiles of a single problem without key lengths: the self-attention of a DiT block
+// whole 128-query blocks and whole 64-key tiles of a single problem: the self-attention of a DiT block.  With key lengths S is the
+// padded count (the tiles are staged whole, so it stays a multiple of 64) and the masked instantiations run.
 bool mfma_attention32_supported(int dtype, const AttnArgs& a) {
   if (dtype != D3PM_F16 && dtype != D3PM_BF16) return false;
-  if (a.hd != HD || a.Q2 != nullptr || a.key_len != nullptr) return false;
+  if (a.hd != HD || a.Q2 != nullptr) return false;
   if (a.Tq < 128 || a.Tq % 128 || a.S < BKV || a.S % BKV) return false;
   if (a.ldq % 8 || a.ldkv % 8 || a.ldo % 8) return false;      // 16-byte output stores
   return aligned(a.Q, 16) && aligned(a.K, 16) && aligned(a.V, 16) && aligned(a.O, 16);
 }
 
-// the cross-attention pair of a block with both K / V images resident (<= 64 text keys, <= 256 prompt keys), no key lengths
+// the cross-attention pair of a block with both K / V images resident (<= 64 text keys, <= 256 prompt keys, padded counts)
 bool mfma_attention32_cross_supported(int dtype, const AttnArgs& a) {
   if (dtype != D3PM_F16 && dtype != D3PM_BF16) return false;
-  if (a.hd != HD || a.Q2 == nullptr || a.key_len != nullptr) return false;
+  if (a.hd != HD || a.Q2 == nullptr) return false;
   if (a.S < 1 || a.S > BKV || a.S2 < 1 || a.S2 > 4 * BKV || a.Tq < 1) return false;
   if (a.ldq % 8 || a.ldkv % 8 || a.ldo % 8) return false;      // 16-byte output stores
   return aligned(a.Q, 16) && aligned(a.K, 16) && aligned(a.V, 16) && aligned(a.O, 16) && aligned(a.Q2, 16) && aligned(a.K2, 16) &&
@@ -775,54 +841,60 @@ int mfma_attention32_cross(int dtype, const AttnArgs& a, int n_qsplit, hipStream
   const int n_qblocks = (a.Tq + 255) / 256;
   const dim3 grid(static_cast<unsigned>(n_qsplit * a.H * a.B)), block(512);
   const size_t lds = static_cast<size_t>(1 + (a.S2 + BKV - 1) / BKV) * 2 * TILE;
-  auto go = [&](auto* tag) -> int {
+  auto go = [&](auto* tag, auto MASK_) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
-    D3PM_LDS_ATTR((&attn32_cross_hd64<U>), 5 * 2 * TILE);
-    attn32_cross_hd64<U><<<grid, block, lds, s>>>(static_cast<const U*>(a.Q), static_cast<const U*>(a.K), static_cast<const U*>(a.V),
-                                                  static_cast<U*>(a.O), a.S, static_cast<const U*>(a.Q2), static_cast<const U*>(a.K2),
-                                                  static_cast<const U*>(a.V2), static_cast<U*>(a.O2), a.S2, a.ldq, a.ldkv, a.ldo, a.Tq,
-                                                  a.scale, a.H, n_qblocks, n_qsplit);
+    constexpr bool MASK = decltype(MASK_)::value;
+    D3PM_LDS_ATTR((&attn32_cross_hd64<U, MASK>), 5 * 2 * TILE);
+    attn32_cross_hd64<U, MASK><<<grid, block, lds, s>>>(static_cast<const U*>(a.Q), static_cast<const U*>(a.K), static_cast<const U*>(a.V),
+                                                        static_cast<U*>(a.O), a.S, static_cast<const U*>(a.Q2), static_cast<const U*>(a.K2),
+                                                        static_cast<const U*>(a.V2), static_cast<U*>(a.O2), a.S2, a.ldq, a.ldkv, a.ldo, a.Tq,
+                                                        a.scale, a.H, n_qblocks, n_qsplit, a.key_len, a.key_len2);
     D3PM_LAUNCH_CHECK();
     return D3PM_OK;
   };
-  return dtype == D3PM_F16 ? go(static_cast<f16*>(nullptr)) : go(static_cast<bf16*>(nullptr));
+  using Yes = std::integral_constant<bool, true>;
+  using No = std::integral_constant<bool, false>;
+  if (a.key_len || a.key_len2) return dtype == D3PM_F16 ? go(static_cast<f16*>(nullptr), Yes{}) : go(static_cast<bf16*>(nullptr), Yes{});
+  return dtype == D3PM_F16 ? go(static_cast<f16*>(nullptr), No{}) : go(static_cast<bf16*>(nullptr), No{});
 }
 
 int mfma_attention32(int dtype, const AttnArgs& a, hipStream_t s) {
   const int n_qblocks = a.Tq / 128;
   const dim3 grid(static_cast<unsigned>(n_qblocks * a.H * a.B)), block(256);
+#define D3PM_ATTN32(KERNEL, T)                                                                                                       \
+  KERNEL<<<grid, block, 0, s>>>(static_cast<const T*>(a.Q), a.ldq, static_cast<const T*>(a.K), static_cast<const T*>(a.V), a.ldkv, \
+                                static_cast<T*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, a.key_len)
   if (tune_of(a.tune).attn_query_groups != 33) {           // 33: the plain walk (A/B against the pipelined one)
 #ifdef D3PM_ABLATIONS
     // A/B library only (attn_query_groups = 35): 192-query workgroups of six waves, two per CU -- a third fewer K / V bytes staged
     // per query, bit-identical, measured SLOWER (65.8 vs 52.8 us at 32 x 768, 23.0 vs 19.4 at 32 x 384: tests/ab_attn32.py,
     // profiles/round3_t_ab_attn32.txt): the staged bytes are not what this kernel waits for
-    if (tune_of(a.tune).attn_query_groups == 35 && a.Tq % 192 == 0) {
+    if (tune_of(a.tune).attn_query_groups == 35 && a.Tq % 192 == 0 && !a.key_len) {
       const dim3 grid6(static_cast<unsigned>(a.Tq / 192 * a.H * a.B)), block6(384);
       if (dtype == D3PM_F16)
         attn32p_hd64<f16, 6><<<grid6, block6, 0, s>>>(static_cast<const f16*>(a.Q), a.ldq, static_cast<const f16*>(a.K), static_cast<const f16*>(a.V),
-                                                      a.ldkv, static_cast<f16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, a.Tq / 192);
+                                                      a.ldkv, static_cast<f16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, a.Tq / 192, nullptr);
       else
         attn32p_hd64<bf16, 6><<<grid6, block6, 0, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), static_cast<const bf16*>(a.V),
-                                                       a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, a.Tq / 192);
+                                                       a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, a.Tq / 192, nullptr);
       D3PM_LAUNCH_CHECK();
       return D3PM_OK;
     }
 #endif
-    if (dtype == D3PM_F16)
-      attn32p_hd64<f16><<<grid, block, 0, s>>>(static_cast<const f16*>(a.Q), a.ldq, static_cast<const f16*>(a.K), static_cast<const f16*>(a.V),
-                                               a.ldkv, static_cast<f16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks);
-    else
-      attn32p_hd64<bf16><<<grid, block, 0, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), static_cast<const bf16*>(a.V),
-                                                a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks);
+    if (a.key_len) {
+      if (dtype == D3PM_F16) D3PM_ATTN32((attn32p_hd64<f16, 4, true>), f16); else D3PM_ATTN32((attn32p_hd64<bf16, 4, true>), bf16);
+    } else {
+      if (dtype == D3PM_F16) D3PM_ATTN32((attn32p_hd64<f16>), f16); else D3PM_ATTN32((attn32p_hd64<bf16>), bf16);
+    }
     D3PM_LAUNCH_CHECK();
     return D3PM_OK;
   }
-  if (dtype == D3PM_F16)
-    attn32_hd64<f16><<<grid, block, 0, s>>>(static_cast<const f16*>(a.Q), a.ldq, static_cast<const f16*>(a.K), static_cast<const f16*>(a.V),
-                                            a.ldkv, static_cast<f16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks);
-  else
-    attn32_hd64<bf16><<<grid, block, 0, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), static_cast<const bf16*>(a.V),
-                                             a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks);
+  if (a.key_len) {
+    if (dtype == D3PM_F16) D3PM_ATTN32((attn32_hd64<f16, true>), f16); else D3PM_ATTN32((attn32_hd64<bf16, true>), bf16);
+  } else {
+    if (dtype == D3PM_F16) D3PM_ATTN32((attn32_hd64<f16>), f16); else D3PM_ATTN32((attn32_hd64<bf16>), bf16);
+  }
+#undef D3PM_ATTN32
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

@@ -289,7 +289,7 @@ inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_
 // one problem or a pair, no key lengths; the caller (mfma_attention) decides by grid size when this schedule is the one to run
 bool mfma_attention_split_supported(int dtype, const AttnArgs& a) {
   if (dtype != D3PM_F16 && dtype != D3PM_BF16) return false;
-  if (a.hd != HD || a.key_len != nullptr || a.S < 1 || a.Tq < 1) return false;
+  if (a.hd != HD || a.key_len != nullptr || a.key_len2 != nullptr || a.S < 1 || a.Tq < 1) return false;
   if (a.ldq % 8 || a.ldkv % 8 || a.ldo % 4) return false;
   if (a.Q2 && !(a.S2 >= 1 && aligned(a.Q2, 16) && aligned(a.K2, 16) && aligned(a.V2, 16) && aligned(a.O2, 8))) return false;
   return aligned(a.Q, 16) && aligned(a.K, 16) && aligned(a.V, 16) && aligned(a.O, 8);

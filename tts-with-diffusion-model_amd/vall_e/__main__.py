@@ -33,6 +33,10 @@ The second form takes what those front-ends write (formats.py) and writes what E
                 run the D3PM stage as a confidence-ordered reveal in N denoiser evaluations (1 .. timesteps - 1; default: the
                 timesteps - 1 evaluations of the D3PM loop): every step reveals the frames the model is most sure of; F (>= 0,
                 default 0) adds annealed Gumbel noise to that order (include/d3pm_hip.h: d3pm_reveal)
+  --mask-padding
+                the utterance does not attend to its own padding: the keys of every attention are its live frames, its phonemes and
+                its prompt frames only (include/d3pm_hip.h: d3pm_keys).  Default off: upstream has the padded rows as keys, and the
+                weights were trained that way
 """
 import argparse
 from pathlib import Path
@@ -61,6 +65,7 @@ def main(argv=None):
     ap.add_argument("--top-p", type=float, default=1.0, help="D3PM stage: draw from the smallest set of classes that carries this share of the mass (1 = off)")
     ap.add_argument("--reveal-steps", type=int, default=None, help="D3PM stage: confidence-ordered reveal in this many denoiser evaluations")
     ap.add_argument("--choice-temperature", type=float, default=0.0, help="D3PM stage, with --reveal-steps: Gumbel noise on the reveal order (>= 0)")
+    ap.add_argument("--mask-padding", action="store_true", help="D3PM stage: key-padding masks, the utterance ignores its own padding")
     ap.add_argument("--native", action="store_true", help="the shape upstream's class really builds (d=32, 16 heads, 8 blocks)")
     args = ap.parse_args(argv)
 
@@ -115,7 +120,7 @@ def main(argv=None):
         phns = torch.tensor([int(p) for p in args.phonemes.split()], dtype=torch.long)
     n_frames = model.cfg.n_frames if args.frames is None else args.frames
     sampling = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, reveal_steps=args.reveal_steps,
-                    choice_temperature=args.choice_temperature)
+                    choice_temperature=args.choice_temperature, mask_padding=args.mask_padding)
     if args.frames is None and args.continue_from is None:
         codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed, **sampling)
     else:

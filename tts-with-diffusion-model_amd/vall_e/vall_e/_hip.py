@@ -103,6 +103,50 @@ class Canvas(C.Structure):
     _fields_ = [("frame_mask", C.c_void_p), ("known", C.c_void_p)]
 
 
+class Keys(C.Structure):
+    """d3pm_keys: per-utterance key counts (device int32 [batch] each, or NULL) of the DiT self-attention (frames), of the text
+    cross-attention / text encoder (text) and of the prompt cross-attention / prompt encoder (prompt) -- include/d3pm_hip.h."""
+    _fields_ = [("frames", C.c_void_p), ("text", C.c_void_p), ("prompt", C.c_void_p)]
+
+
+def key_lengths(n_frames, text_lens, prompt_lens, canvas, s_text, s_prompt):
+    """The three key counts of `mask_padding` from per-utterance lengths (host ints): frames[b] = L_b, text[b] = min(len(text_b),
+    s_text), prompt[b] = min(rows(prom_b), s_prompt) -> three lists of ints.  ValueError for an utterance without a frame, a
+    phoneme or a prompt frame (a softmax over no key is undefined), or with more frames than the canvas."""
+    n_frames, text_lens, prompt_lens = [int(v) for v in n_frames], [int(v) for v in text_lens], [int(v) for v in prompt_lens]
+    if not (len(n_frames) == len(text_lens) == len(prompt_lens)):
+        raise ValueError(f"mask_padding: {len(n_frames)} frame counts, {len(text_lens)} texts and {len(prompt_lens)} prompts")
+    for b, (f, t, p) in enumerate(zip(n_frames, text_lens, prompt_lens)):
+        if not 1 <= f <= canvas:
+            raise ValueError(f"mask_padding: utterance {b} has {f} frames, outside 1..{canvas}")
+        if t < 1:
+            raise ValueError(f"mask_padding: utterance {b} has an empty text")
+        if p < 1:
+            raise ValueError(f"mask_padding: utterance {b} has an empty prompt")
+    return n_frames, [min(t, s_text) for t in text_lens], [min(p, s_prompt) for p in prompt_lens]
+
+
+def _key_array(t, name, B, device):
+    """One d3pm_keys member: None, or a contiguous int32 [B] tensor on `device` (the values are read by the kernels only)."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (B,) or t.device != device or not t.is_contiguous():
+        raise D3PMError(f"keys.{name} must be a contiguous int32 [{B}] tensor on {device}")
+    return t
+
+
+def make_keys(keys, B, device):
+    """keys: None, or (frames, text, prompt) -- each None or int32 [B] on the device -> a Keys struct that keeps its tensors alive."""
+    if keys is None:
+        return None
+    if not isinstance(keys, (tuple, list)) or len(keys) != 3:
+        raise D3PMError("keys must be a (frames, text, prompt) triple of int32 [B] device tensors (None = that attention is not masked)")
+    kept = tuple(_key_array(t, n, B, device) for t, n in zip(keys, ("frames", "text", "prompt")))
+    ks = Keys(*(None if t is None else t.data_ptr() for t in kept))
+    ks._keep = kept
+    return ks
+
+
 class Sampling(C.Structure):
     """d3pm_sampling: temperature and top-k on the x0-logits of the D3PM sampler (include/d3pm_hip.h)."""
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32)]
@@ -199,6 +243,22 @@ SIGNATURES = {
     "d3pm_cond_workspace_bytes": (C.c_size_t, [C.POINTER(Shape), C.POINTER(CondWeights), C.c_int]),
     "d3pm_encode_conditions": (C.c_int, [C.POINTER(Shape), C.POINTER(CondWeights), C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "d3pm_encode_conditions_keys": (C.c_int, [C.POINTER(Shape), C.POINTER(CondWeights), C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(Keys), C.c_void_p]),
+    "d3pm_denoise_step_keys": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.POINTER(Canvas), C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.c_void_p, C.c_int, C.c_uint32, C.POINTER(Keys), C.c_void_p]),
+    "d3pm_sample_loop_keys": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.POINTER(Canvas), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.POINTER(Nucleus), C.POINTER(Keys), C.c_void_p]),
+    "d3pm_reveal_loop_keys": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Canvas),
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32,
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(Nucleus), C.POINTER(Reveal), C.POINTER(Keys),
+                                        C.c_void_p]),
+    "d3pm_op_attention_pair_keylen": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(Tuning), C.c_void_p]),
     "d3pm_denoise_step": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                     C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]),
@@ -576,19 +636,27 @@ class Sampler:
             ws = self._ws[slot] = torch.empty(need, dtype=torch.uint8, device=self.device)
         return ws
 
-    def encode_conditions(self, text: torch.Tensor, prompt: torch.Tensor):
+    def encode_conditions(self, text: torch.Tensor, prompt: torch.Tensor, text_len=None, prom_len=None):
         """text int32 [B,S_t] (zero padded), prompt int32 [B,S_p,n_levels] (-1 = level absent) ->
-        (cond_text [B,S_t,d], cond_prompt [B,S_p,d]) through d3pm_encode_conditions."""
+        (cond_text [B,S_t,d], cond_prompt [B,S_p,d]) through d3pm_encode_conditions.  text_len / prom_len: int32 [B] on the device
+        or None -- the valid rows of each utterance, the only keys of that encoder's self-attention (d3pm_encode_conditions_keys);
+        the ids behind a length are not read by the library (those rows are embedded as padding), so they may hold anything."""
         if self.cond_weights is None:
             raise D3PMError("this sampler was bound without condition-encoder weights")
         cfg, B = self.cfg, text.shape[0]
         assert text.shape == (B, cfg.s_text) and prompt.shape == (B, cfg.s_prompt, cfg.n_levels)
+        ks = make_keys((None, text_len, prom_len), B, self.device) if (text_len is not None or prom_len is not None) else None
         text, prompt = text.to(torch.int32).contiguous(), prompt.to(torch.int32).contiguous()
         need = lib().d3pm_cond_workspace_bytes(C.byref(self.shape), C.byref(self.cond_weights.c_struct), B)
         if self._cond_ws is None or self._cond_ws.numel() < need:
             self._cond_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         ct = torch.empty((B, cfg.s_text, cfg.d_model), dtype=self.dtype, device=self.device)
         cp = torch.empty((B, cfg.s_prompt, cfg.d_model), dtype=self.dtype, device=self.device)
+        if ks is not None:
+            check(lib().d3pm_encode_conditions_keys(C.byref(self.shape), C.byref(self.cond_weights.c_struct), B, _p(text),
+                                                    _p(prompt), _p(ct), _p(cp), _p(self._cond_ws), self._cond_ws.numel(),
+                                                    C.byref(ks), stream_ptr()), "d3pm_encode_conditions_keys")
+            return ct, cp
         check(lib().d3pm_encode_conditions(C.byref(self.shape), C.byref(self.cond_weights.c_struct), B, _p(text),
                                            _p(prompt), _p(ct), _p(cp), _p(self._cond_ws), self._cond_ws.numel(),
                                            stream_ptr()), "d3pm_encode_conditions")
@@ -655,15 +723,22 @@ class Sampler:
                                       _p(hidden), only_layers, flags, stream_ptr()), "d3pm_denoise_step")
         return logits, hidden
 
-    def denoise_canvas(self, x_t, frame_mask, t, kv_t, kv_p, *, want_logits=True, want_hidden=False, only_layers=-1, flags=0):
-        """`denoise` with one frame mask per utterance, uint8 [B, canvas] (d3pm_denoise_step_canvas)."""
+    def denoise_canvas(self, x_t, frame_mask, t, kv_t, kv_p, *, want_logits=True, want_hidden=False, only_layers=-1, flags=0, keys=None):
+        """`denoise` with one frame mask per utterance, uint8 [B, canvas] (d3pm_denoise_step_canvas).  keys: None or the (frames,
+        text, prompt) key counts of make_keys (d3pm_denoise_step_keys)."""
         cfg = self.cfg
         B = self._check_grid(x_t)
         cv = self._check_canvas(B, frame_mask)
         self._check_kv(kv_t, kv_p, B)
+        ks = make_keys(keys, B, self.device)
         ws = self.workspace(B)
         logits = torch.empty((B, cfg.canvas) + self._lvl() + (cfg.n_classes,), dtype=self.dtype, device=self.device) if want_logits else None
         hidden = torch.empty((B, cfg.canvas, cfg.d_model), dtype=self.dtype, device=self.device) if want_hidden else None
+        if ks is not None:
+            check(lib().d3pm_denoise_step_keys(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x_t), C.byref(cv),
+                                               int(t), _p(self.film), _p(kv_t), _p(kv_p), _p(ws), ws.numel(), _p(logits),
+                                               _p(hidden), only_layers, flags, C.byref(ks), stream_ptr()), "d3pm_denoise_step_keys")
+            return logits, hidden
         check(lib().d3pm_denoise_step_canvas(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x_t), C.byref(cv),
                                              int(t), _p(self.film), _p(kv_t), _p(kv_p), _p(ws), ws.numel(), _p(logits),
                                              _p(hidden), only_layers, flags, stream_ptr()), "d3pm_denoise_step_canvas")
@@ -724,19 +799,31 @@ class Sampler:
         return x_next
 
     def sample_loop(self, x, frame_mask, t_start, t_stop, kv_t, kv_p, seed, utt0=0, flags=0, trace=False, slot=0,
-                    fp8=False, known=None, temperature=1.0, top_k=0, top_p=1.0):
+                    fp8=False, known=None, temperature=1.0, top_k=0, top_p=1.0, keys=None):
         """frame_mask uint8 [canvas] (shared by the batch) runs d3pm_sample_loop(_fp8); a per-utterance mask [B, canvas] and / or a
         known-frame map `known` (uint8 [B, canvas]; `x` already carries the given ids) run the *_canvas entries.  temperature /
         top_k other than the neutral (1, 0) run d3pm_sample_loop_sampling, which covers the four of them; top_p other than 1 runs
-        d3pm_sample_loop_nucleus, which takes the same arguments."""
+        d3pm_sample_loop_nucleus, which takes the same arguments.  keys: None or the (frames, text, prompt) key counts of make_keys
+        (d3pm_sample_loop_keys, which covers all of the above but fp8)."""
         cfg = self.cfg
         smp = nucleus_options(temperature, top_k, top_p, cfg.n_classes)
+        if keys is not None and fp8:
+            raise ValueError("the fp8 fast path takes no key mask")
         per_utt = known is not None or (isinstance(frame_mask, torch.Tensor) and frame_mask.dim() == 2)
         B = self._check_grid(x, None if per_utt else frame_mask, "x")
         cv = self._check_canvas(B, frame_mask, known) if per_utt else None
         self._check_kv(kv_t, kv_p, B)
+        ks = make_keys(keys, B, self.device)
         ws = self.workspace(B, slot)
         tr = torch.empty((t_start - t_stop, B, cfg.canvas) + self._lvl(), dtype=torch.int32, device=self.device) if trace else None
+        if ks is not None:
+            nuc = self._as_nucleus(smp)
+            check(lib().d3pm_sample_loop_keys(C.byref(self.shape), C.byref(self.weights.c_struct), None, B, _p(x),
+                                              None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None,
+                                              int(t_start), int(t_stop), _p(self.film), _p(kv_t), _p(kv_p),
+                                              C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
+                                              None if nuc is None else C.byref(nuc), C.byref(ks), stream_ptr()), "d3pm_sample_loop_keys")
+            return tr
         if smp is not None:
             name = "d3pm_sample_loop_nucleus" if isinstance(smp, Nucleus) else "d3pm_sample_loop_sampling"
             check(getattr(lib(), name)(C.byref(self.shape), C.byref(self.weights.c_struct),
@@ -810,9 +897,10 @@ class Sampler:
         return x_next, cand, score
 
     def reveal_loop(self, x, frame_mask, n_steps, kv_t, kv_p, seed, utt0=0, flags=0, trace=False, slot=0, known=None, temperature=1.0,
-                    top_k=0, top_p=1.0, choice_temperature=0.0):
+                    top_k=0, top_p=1.0, choice_temperature=0.0, keys=None):
         """The reveal schedule in n_steps denoiser evaluations (d3pm_reveal_loop), in place on x; masks and known frames as for
-        sample_loop.  -> the trace int32 [n_steps, B, canvas] (x after every step) or None."""
+        sample_loop.  keys: None or the (frames, text, prompt) key counts of make_keys (d3pm_reveal_loop_keys).
+        -> the trace int32 [n_steps, B, canvas] (x after every step) or None."""
         cfg = self.cfg
         smp = self._as_nucleus(nucleus_options(temperature, top_k, top_p, cfg.n_classes))
         rv = reveal_options(n_steps, choice_temperature, self.schedule.timesteps)
@@ -826,6 +914,14 @@ class Sampler:
         self._check_kv(kv_t, kv_p, B)
         ws = self.workspace(B, slot)
         tr = torch.empty((rv.n_steps, B, cfg.canvas), dtype=torch.int32, device=self.device) if trace else None
+        ks = make_keys(keys, B, self.device)
+        if ks is not None:
+            check(lib().d3pm_reveal_loop_keys(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), None if per_utt else _p(frame_mask),
+                                              C.byref(cv) if per_utt else None, _p(self.film), _p(kv_t), _p(kv_p),
+                                              C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
+                                              None if smp is None else C.byref(smp), C.byref(rv), C.byref(ks), stream_ptr()),
+                  "d3pm_reveal_loop_keys")
+            return tr
         check(lib().d3pm_reveal_loop(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), None if per_utt else _p(frame_mask),
                                      C.byref(cv) if per_utt else None, _p(self.film), _p(kv_t), _p(kv_p),
                                      C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
@@ -1001,9 +1097,11 @@ def op_attention(q, k, v, n_heads, scale, *, family=0, key_len=None):
     return o
 
 
-def op_attention_pair(q1, k1, v1, q2, k2, v2, n_heads, scale):
+def op_attention_pair(q1, k1, v1, q2, k2, v2, n_heads, scale, *, key_len=None, key_len2=None):
     """The text / prompt cross-attention pair of a block as one launch: q1, q2 [B,Tq,d]; k1 / v1 [B,S1,d], k2 / v2 [B,S2,d] (K / V
-    views of one packed [.., 2d] cache row allowed) -> (o1, o2) [B,Tq,d]."""
+    views of one packed [.., 2d] cache row allowed) -> (o1, o2) [B,Tq,d].  key_len / key_len2: int32 [B] on the device, the valid
+    keys of each utterance in problem 1 / 2 (1 <= value <= S1 / S2; keys behind them are masked out), or None
+    (d3pm_op_attention_pair_keylen)."""
     B, Tq, d = q1.shape
     S1, S2 = k1.shape[1], k2.shape[1]
     for t in (q1, q2, k1, v1, k2, v2):
@@ -1013,6 +1111,15 @@ def op_attention_pair(q1, k1, v1, q2, k2, v2, n_heads, scale):
     assert k1.stride(0) == S1 * k1.stride(1) and k2.stride(0) == S2 * k2.stride(1)
     o1 = torch.empty((B, Tq, d), dtype=q1.dtype, device=q1.device)
     o2 = torch.empty_like(o1)
+    if key_len is not None or key_len2 is not None:
+        for name, kl in (("key_len", key_len), ("key_len2", key_len2)):
+            if kl is not None and (not isinstance(kl, torch.Tensor) or kl.dtype != torch.int32 or kl.shape != (B,) or kl.device != q1.device
+                                   or not kl.is_contiguous()):
+                raise D3PMError(f"{name} must be a contiguous int32 [{B}] tensor on {q1.device}")
+        check(lib().d3pm_op_attention_pair_keylen(dtype_code(q1.dtype), _p(q1), _p(k1), _p(v1), _p(o1), S1, _p(q2), _p(k2), _p(v2), _p(o2),
+                                                  S2, q1.stride(1), k1.stride(1), d, B, Tq, n_heads, d // n_heads, float(scale),
+                                                  _p(key_len), _p(key_len2), C.byref(TUNING), stream_ptr()), "d3pm_op_attention_pair_keylen")
+        return o1, o2
     check(lib().d3pm_op_attention_pair(dtype_code(q1.dtype), _p(q1), _p(k1), _p(v1), _p(o1), S1, _p(q2), _p(k2), _p(v2), _p(o2), S2,
                                        q1.stride(1), k1.stride(1), d, B, Tq, n_heads, d // n_heads, float(scale), C.byref(TUNING),
                                        stream_ptr()), "d3pm_op_attention_pair")

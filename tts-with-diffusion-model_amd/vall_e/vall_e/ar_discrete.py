@@ -228,16 +228,30 @@ class AR(SymmapState, nn.Module):
         prom = torch.stack([self._pad_rows(p.to(dev).long(), cfg.s_prompt) for p in proms_list])        # [B,S_p,l]
         return text, prom
 
-    def encode_conditions(self, text_list: Sequence[Tensor], proms_list: Sequence[Tensor]):
+    def encode_conditions(self, text_list: Sequence[Tensor], proms_list: Sequence[Tensor], text_len=None, prom_len=None):
         """-> (cond_text [B,S_t,d], cond_prompt [B,S_p,d]) through the HIP condition encoders
         (d3pm_encode_conditions).  Same statements as upstream (:711-746): zero pad / truncate, embed, text gets
         PE(position 0) on every phoneme (the x.shape[0] quirk at :89), the prompt true positions; two post-norm
-        encoder layers + Mlp.  Prompts with fewer than n_levels quantizer levels: the missing levels add nothing."""
+        encoder layers + Mlp.  Prompts with fewer than n_levels quantizer levels: the missing levels add nothing.
+        text_len / prom_len (int32 [B] on the device, or None): the rows of each utterance that are keys of the encoder's
+        self-attention (generate_audio(mask_padding=True)); upstream has every padded row as a key."""
         text, prom = self._padded_inputs(text_list, proms_list)
         if prom.shape[-1] < self.cfg.n_levels:
             prom = F.pad(prom, (0, self.cfg.n_levels - prom.shape[-1]), value=-1)
         with torch.cuda.device(self.device):
-            return self.sampler().encode_conditions(text, prom)
+            return self.sampler().encode_conditions(text, prom, text_len, prom_len)
+
+    def key_lengths(self, text_list, proms_list, n_frames: Union[int, Sequence[int], None] = None):
+        """The key counts of generate_audio(mask_padding=True) as three lists of B ints (host arithmetic only): frames[b] = the live
+        frames of utterance b, text[b] = min(len(text_b), s_text), prompt[b] = min(rows(prom_b), s_prompt).  ValueError for an
+        empty text or prompt and for a frame count outside 1..canvas."""
+        cfg, B = self.cfg, len(text_list)
+        if n_frames is None or isinstance(n_frames, Integral):
+            frames = [cfg.n_frames if n_frames is None else int(n_frames)] * B
+        else:
+            frames = [int(v) for v in n_frames]
+        return _hip.key_lengths(frames, [int(t.shape[0]) if t.dim() else 0 for t in text_list],
+                                [int(p.shape[0]) if p.dim() else 0 for p in proms_list], cfg.canvas, cfg.s_text, cfg.s_prompt)
 
     def encode_conditions_torch(self, text_list: Sequence[Tensor], proms_list: Sequence[Tensor]):
         """The same encoders on PyTorch-ROCm modules (tests cross-check the HIP path against it)."""
@@ -336,7 +350,8 @@ class AR(SymmapState, nn.Module):
                        graph: Optional[bool] = None, fp8: bool = False, global_batch: Optional[int] = None,
                        known: Optional[Sequence[Optional[Tensor]]] = None,
                        known_mask: Optional[Sequence[Optional[Tensor]]] = None, temperature: float = 1.0, top_k: int = 0,
-                       top_p: float = 1.0, reveal_steps: Optional[int] = None, choice_temperature: float = 0.0):
+                       top_p: float = 1.0, reveal_steps: Optional[int] = None, choice_temperature: float = 0.0,
+                       mask_padding: bool = False):
         """Reverse diffusion for len(text_list) utterances.  Positional behaviour as upstream:
         one utterance -> int64 [canvas] (squeezed, untrimmed; rows >= n_frames are sampled from
         final.bias and meaningless); with n_q > 1 (constructor) [canvas, n_q] / [B, canvas, n_q].  `resps_list` is ignored, as
@@ -381,10 +396,28 @@ class AR(SymmapState, nn.Module):
         they are NOT sampled from final.bias as on the default path.  It composes with n_frames sequences, known / known_mask,
         temperature / top_k / top_p, greedy, utt0 / global_batch, streams and return_trace (the trace then has N entries);
         with `steps`, graph=True, fp8=True or an n_q > 1 model it raises ValueError before any GPU work.  No statement about audio
-        quality is made for it."""
+        quality is made for it.
+        `mask_padding=True` (default False: upstream's behaviour, untouched) keeps an utterance from attending to its own padding
+        (include/d3pm_hip.h: d3pm_keys): the keys of every DiT self-attention are its n_frames[b] live frames, the keys of the text /
+        prompt cross-attention and of the text / prompt encoder are its min(len(text_b), s_text) phonemes / min(rows(prom_b),
+        s_prompt) prompt frames; a masked key has probability exactly 0.  Padded rows stay queries and are sampled as ever, so the
+        result keeps its shape.  No padded row is then a key of a live one: the live rows are what the model computes at canvas =
+        n_frames[b], s_text = len(text_b), s_prompt = rows(prom_b), within accumulation order (1e-3 of the oracle in fp32; bit for
+        bit only on the generic kernels: the MFMA kernels tile by the padded counts and padded query rows share waves with live
+        ones, so the last bits, and with them an occasional id, can still differ between two paddings).  It composes with
+        n_frames sequences, known / known_mask, temperature / top_k / top_p, reveal_steps, greedy, utt0 / global_batch, streams,
+        return_trace and n_q > 1; an empty text or prompt, graph=True and fp8=True raise ValueError before any GPU work.  The
+        synthetic and the upstream weights were trained with the padding as keys and the training step (forward, forward_backward)
+        does not take the mask: no statement about audio quality is made for it."""
         if len(text_list) != len(proms_list) or len(text_list) == 0:
             raise ValueError("text_list and proms_list must be non-empty and of equal length")
         B = len(text_list)
+        key_lens = None
+        if mask_padding:
+            for name, bad in (("graph=True", bool(graph)), ("fp8=True", bool(fp8))):
+                if bad:
+                    raise ValueError(f"mask_padding does not combine with {name}")
+            key_lens = self.key_lengths(text_list, proms_list, n_frames)      # host validation before any GPU work
         filtered = _hip.nucleus_options(temperature, top_k, top_p, N_CLASSES) is not None      # host validation before any GPU work
         if filtered and graph:
             raise ValueError("graph=True replays a loop captured per (batch, step range, utt0, flags): temperature / top_k / top_p run "
@@ -409,7 +442,13 @@ class AR(SymmapState, nn.Module):
         n_streams = max(1, min(B, self.loop_streams if streams is None else streams))
         regime = max(int(global_batch), B) if global_batch else (B if n_streams > 1 else 0)
         with torch.cuda.device(self.device), _hip.tuning(regime_batch=regime):
-            cond_text, cond_prompt = self.encode_conditions(text_list, proms_list)
+            keys = None      # d3pm_keys: (frames, text, prompt), int32 [B] on the device
+            if key_lens is not None:
+                keys = tuple(torch.tensor(v, dtype=torch.int32, device=self.device) for v in key_lens)
+            cond_text, cond_prompt = self.encode_conditions(text_list, proms_list, *(keys[1:] if keys else ()))
+
+            def chunk_keys(lo, hi):
+                return None if keys is None else tuple(k[lo:hi] for k in keys)
             if not per_utt:
                 x, frame_mask, kmap = self.canvas_init(B, n_frames) + (None,)
             fl = flags | (_hip.FLAG_GREEDY if greedy else 0)
@@ -425,10 +464,11 @@ class AR(SymmapState, nn.Module):
                 kv_t, kv_p = smp.cond_kv(cond_text, cond_prompt)
                 if rv is not None:
                     trace = smp.reveal_loop(x, frame_mask, rv.n_steps, kv_t, kv_p, seed, utt0, fl, trace=return_trace, known=kmap,
-                                            temperature=temperature, top_k=top_k, top_p=top_p, choice_temperature=rv.choice_temperature)
+                                            temperature=temperature, top_k=top_k, top_p=top_p, choice_temperature=rv.choice_temperature,
+                                            keys=keys)
                 else:
                     trace = smp.sample_loop(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl, trace=return_trace, fp8=fp8, known=kmap,
-                                            temperature=temperature, top_k=top_k, top_p=top_p)
+                                            temperature=temperature, top_k=top_k, top_p=top_p, keys=keys)
             else:
                 # utterances are independent: chunks of the batch run the whole loop on their own stream so that
                 # the short kernels of one chunk fill the ramp-up / epilogue bubbles of the others
@@ -446,11 +486,11 @@ class AR(SymmapState, nn.Module):
                         if rv is not None:
                             smp.reveal_loop(x[lo:hi], frame_mask[lo:hi] if per_utt else frame_mask, rv.n_steps, kv_t, kv_p, seed, utt0 + lo, fl,
                                             slot=i, known=None if kmap is None else kmap[lo:hi], temperature=temperature, top_k=top_k,
-                                            top_p=top_p, choice_temperature=rv.choice_temperature)
+                                            top_p=top_p, choice_temperature=rv.choice_temperature, keys=chunk_keys(lo, hi))
                         else:
                             smp.sample_loop(x[lo:hi], frame_mask[lo:hi] if per_utt else frame_mask, t_start, 0, kv_t, kv_p, seed, utt0 + lo, fl,
                                             slot=i, known=None if kmap is None else kmap[lo:hi], temperature=temperature, top_k=top_k,
-                                            top_p=top_p)
+                                            top_p=top_p, keys=chunk_keys(lo, hi))
                         for t_ in (kv_t, kv_p, cond_text, cond_prompt, x):
                             t_.record_stream(st)
                 for i in range(n_streams):
