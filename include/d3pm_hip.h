@@ -57,7 +57,8 @@ extern "C" {
  *    (d3pm_nucleus, d3pm_posterior_sample_nucleus, d3pm_sample_loop_nucleus); the confidence-ordered reveal schedule
  *    (d3pm_reveal, d3pm_reveal_plan, d3pm_reveal_step, d3pm_reveal_loop); the per-utterance key mask at kernel level
  *    (d3pm_op_attention_keylen); key-padding masks through the denoiser (d3pm_keys, d3pm_encode_conditions_keys,
- *    d3pm_denoise_step_keys, d3pm_sample_loop_keys, d3pm_reveal_loop_keys, d3pm_op_attention_pair_keylen) */
+ *    d3pm_denoise_step_keys, d3pm_sample_loop_keys, d3pm_reveal_loop_keys, d3pm_op_attention_pair_keylen); classifier-free guidance
+ *    inside the sampler launch (d3pm_guidance, d3pm_posterior_sample_guided, d3pm_sample_loop_guided) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -601,6 +602,56 @@ int d3pm_reveal_loop_keys(const d3pm_shape *shape, const d3pm_weights *weights, 
                           const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
                           size_t workspace_bytes, int32_t *trace, const d3pm_nucleus *nucleus, const d3pm_reveal *reveal,
                           const d3pm_keys *keys, void *stream);
+
+/* ---- classifier-free guidance (additions; ABI version unchanged) -------------------------------------------------------------------
+ * Each reverse step evaluates the denoiser with the utterance's conditions and with the NULL condition, and draws from the
+ * extrapolated logits (1 + w) cond - w uncond (Ho & Salimans 2022; the reference has no such option).  Exact definition:
+ *   null condition  the utterance with no phonemes and no prompt frames, padded the way every utterance is padded: what the condition
+ *                   encoders give for an empty text (int64 [0]) and an empty prompt ([0][n_levels]), i.e. d3pm_encode_conditions on
+ *                   the zero padding alone.  No new weights, no new embedding rule.  The library does not care what the second
+ *                   half holds: a caller may encode any "negative" condition.
+ *   guided logits   for weight w (finite, >= 0), a row's conditioned logits c_j and null logits u_j in the logits dtype:
+ *                       z_j = rn16( fmaf(w, float(c_j) - float(u_j), float(c_j)) )
+ *                   -- the subtraction in fp32, an explicit fma (no contraction left to the compiler), ONE rounding to fp16, at the
+ *                   point where the row routines round a plain logit today.  Everything downstream is the existing routine on z:
+ *                   temperature / top_k / top_p (d3pm_nucleus), softmax, posterior, Gumbel-max, the exact early-out of revealed rows,
+ *                   D3PM_FLAG_GREEDY, t = 0.  All n_classes are combined alike, the mask class included.  Where c == u (w = anything)
+ *                   z = rn16(c) exactly, and w = 0 gives the unguided ids from the conditioned half.
+ *   evaluation      a guided step is ONE denoiser evaluation of 2 * batch utterances, not two of batch: utterance batch + b is the
+ *                   null twin of b -- the same x_t, the same frame mask, its own K/V (and key counts).  What the caller sees -- x,
+ *                   trace, the known map, frame_mask -- stays [batch][canvas]; the noise of row r is keyed by utt0 * canvas + r as
+ *                   without guidance.  The attention regime rule sees twice the logical batch, 2 * max(regime_batch, batch), so a
+ *                   shard or a stream chunk of a guided batch reproduces the unsplit guided batch bit for bit (regime_batch keeps
+ *                   counting logical utterances).
+ * Refused with D3PM_E_ARG and a message, nothing launched: a NULL d3pm_guidance, a negative or non-finite weight, n_q > 1, fp8 block
+ * weights, D3PM_FLAG_SEED_IN_HBM (graph replay).  The reveal loop takes no guidance.  A call without d3pm_guidance runs none of this
+ * code: the guided launches are kernels of their own (they always carry the nucleus arm, which with the neutral triple changes no
+ * value).  No statement about audio quality is made: guidance is meaningful for weights trained with the conditions dropped some of
+ * the time (vall_e/vall_e/train.py: cond_drop). */
+typedef struct d3pm_guidance {
+  float weight;     /* w: finite, >= 0 */
+} d3pm_guidance;
+
+/* One guided posterior draw between two evaluations.  logits device [2 * batch * canvas][n_classes] of logits_dtype (any of the
+ * three): rows [0, batch * canvas) under the conditions, rows batch * canvas + r the null twin of row r.  x_t / x_next device int32
+ * [batch][canvas].  canvas NULL or a d3pm_canvas whose `known` map ([batch][canvas] or NULL) marks frames that keep x_t (frame_mask
+ * is not read); nucleus NULL = the neutral triple. */
+int d3pm_posterior_sample_guided(const d3pm_shape *shape, int batch, const void *logits, int logits_dtype,
+                                 const int32_t *x_t, int32_t *x_next, const d3pm_canvas *canvas, int t,
+                                 const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags,
+                                 const d3pm_nucleus *nucleus, const d3pm_guidance *guidance, void *stream);
+
+/* d3pm_sample_loop_keys under guidance.  kv_text / kv_prompt hold 2 * batch utterances per layer ([L][2 batch][S][2d]: the null
+ * twins behind the conditioned ones), keys (optional) 2 * batch entries per array, the workspace is
+ * d3pm_workspace_bytes(shape, 2 * batch); x, canvas / frame_mask and trace are those of `batch` utterances.  fp8_blocks must be
+ * NULL.  With the folded LayerNorms the sampler launch of iteration t also writes the embedding rows and moments of BOTH halves for
+ * iteration t - 1 and rebuilds fc1; the ids are those of d3pm_denoise_step at 2 * batch chained with d3pm_posterior_sample_guided. */
+int d3pm_sample_loop_guided(const d3pm_shape *shape, const d3pm_weights *weights, const d3pm_fp8_block_weights *fp8_blocks,
+                            int batch, int32_t *x, const uint8_t *frame_mask, const d3pm_canvas *canvas, int t_start,
+                            int t_stop, const void *film, const void *kv_text, const void *kv_prompt,
+                            const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
+                            size_t workspace_bytes, int32_t *trace, const d3pm_nucleus *nucleus, const d3pm_keys *keys,
+                            const d3pm_guidance *guidance, void *stream);
 
 /* Replaces AR.q_sample / q_probs (ar_discrete.py:467-502): forward noising of x0 at step t with
  * Philox stream 1.  x0, x_out device int32 [batch][canvas]. */

@@ -327,7 +327,19 @@ struct DenoiserArgs {      // what every block of one evaluation sees
   const d3pm_shape& sh; const d3pm_weights& w; int batch; const uint8_t* frame_mask; int mask_period; const void* kv_text; const void* kv_prompt;
   const Workspace& ws;
   KeyCounts keys = {};
+  // classifier-free guidance (d3pm_sample_loop_guided): x_t holds token_rows = batch / 2 * canvas rows and rows token_rows .. of the
+  // evaluation (the null twins) read the same ids; 0 = x_t has a row per row of the evaluation
+  int token_rows = 0;
 };
+// the token embedding of an evaluation whose two halves read the same x_t (token_rows > 0): the gather, once per half
+static int embed_twins(const DenoiserArgs& q, const int32_t* x_t, hipStream_t s) {
+  const d3pm_shape& sh = q.sh;
+  EmbedArgs e = embed_args(sh, q.w, q.batch / 2, x_t, q.frame_mask, q.mask_period, q.ws.x);
+  const int rc = embed_tokens(sh.dtype, e, s);
+  if (rc != D3PM_OK) return rc;
+  e.Y = at(q.ws.x, static_cast<size_t>(q.token_rows) * sh.d_model, dtype_size(sh.dtype));
+  return embed_tokens(sh.dtype, e, s);
+}
 
 // ---- the block sequence with the LayerNorms folded into the projections (ar_discrete.py:126-161; d3pm_mfma_tile.h EPI_LNF / EPI_STATS)
 //   embed (+ moments) -> n_layers x { QKV <- x [norm1 folded], self-attention, out-projection + x (+ moments),
@@ -427,7 +439,12 @@ static int denoiser_blocks_folded(const DenoiserArgs& q, const int32_t* x_t, int
   if (!prepared) {      // (inside the loop the previous iteration's sampler launch has done both: posterior_sample_prep)
     {
       ProfScope p(cx, D3PM_K_LN, s, 0.0, es * static_cast<double>(n) * d * 2.0);
-      D3PM_TRY(embed_tokens_stats(dt, embed_args(sh, q.w, q.batch, x_t, q.frame_mask, q.mask_period, q.ws.x), q.ws.stats, quads, s));
+      if (q.token_rows) {      // the first evaluation of a guided loop: both halves from the same ids, then the moments of all rows (same bits)
+        D3PM_TRY(embed_twins(q, x_t, s));
+        D3PM_TRY(row_stats_launch(dt, q.ws.x, d, n, d, q.ws.stats, s, quads));
+      } else {
+        D3PM_TRY(embed_tokens_stats(dt, embed_args(sh, q.w, q.batch, x_t, q.frame_mask, q.mask_period, q.ws.x), q.ws.stats, quads, s));
+      }
     }
     {   // fc1 of every block under norm3 + FiLM(t): the weights this evaluation's fc1 launches read
       ProfScope p(cx, D3PM_K_LN, s, 0.0, es * 2.0 * layers * 4.0 * d * d);
@@ -492,7 +509,7 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
   // the first block's norm1 reads the embedding rows straight from the table and writes x beside its own output: one launch and
   // one pass over x less per iteration (same bits: the gather is a copy)
   bool embed_fused = false;
-  if (!use8 && !(flags & D3PM_FLAG_FORCE_GENERIC) && layers > 0 && levels(sh) == 1) {
+  if (!use8 && !(flags & D3PM_FLAG_FORCE_GENERIC) && layers > 0 && levels(sh) == 1 && !q.token_rows) {
     LayerNormArgs ln0 = layernorm(w.blocks[0].norm1_w, w.blocks[0].norm1_b);
     ln0.X = w.resps_emb;
     ln0.tokens = x_t; ln0.frame_mask = frame_mask; ln0.mask_period = mask_period; ln0.n_classes = sh.n_classes; ln0.Xout = ws.x;
@@ -502,7 +519,8 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
       embed_fused = true;
     }
   }
-  if (!embed_fused) D3PM_TRY(embed_tokens(dt, embed_args(sh, w, batch, x_t, frame_mask, mask_period, ws.x), s));
+  if (q.token_rows) D3PM_TRY(embed_twins(q, x_t, s));      // (the gather is a copy: the rows norm1 reads are those of the fused launch)
+  else if (!embed_fused) D3PM_TRY(embed_tokens(dt, embed_args(sh, w, batch, x_t, frame_mask, mask_period, ws.x), s));
 
   // row-panel launches (D3PM_TUNE_ROW_PANEL): a projection that lands on the residual stream also writes the LayerNorm(s) the
   // block applies to the new rows next -- same bits, one launch and one pass over x less each
@@ -1031,19 +1049,34 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
                             int t_start, int t_stop, const void* film, const void* kv_text, const void* kv_prompt,
                             const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace,
                             size_t workspace_bytes, int32_t* trace, void* stream, const d3pm_fp8_block_weights* f8,
-                            const d3pm_nucleus* sm = nullptr, const char* who = "d3pm_sample_loop_sampling", const KeyCounts& keys = KeyCounts{}) {
+                            const d3pm_nucleus* sm = nullptr, const char* who = "d3pm_sample_loop_sampling", const KeyCounts& keys = KeyCounts{},
+                            const d3pm_guidance* guide = nullptr) {
   D3PM_TRY(check_shape(sh, batch));
   D3PM_TRY(check_sampling(sh, sm, who));
   D3PM_REQUIRE(w && w->blocks && x && cm.frame_mask && film && kv_text && kv_prompt && sched && workspace, D3PM_E_ARG,
                "d3pm_sample_loop: null pointer");
   D3PM_REQUIRE(t_start < sched->timesteps && t_start <= sh->timesteps && t_stop >= 0 && t_stop <= t_start, D3PM_E_ARG,
                "bad step range %d..%d", t_start, t_stop);
-  Workspace ws = carve(*sh, batch, static_cast<char*>(workspace));
+  // Classifier-free guidance (d3pm_guidance): one evaluation of 2 * batch utterances per step -- utterance batch + b is the null twin of
+  // b: the same x_t, the same frame mask (the mask period stays that of `batch`, so row r and row rows + r read the same byte), its own
+  // K/V and key counts -- and a sampler over `batch` utterances that reads both halves of the logits.  The attention regime rule sees
+  // twice the logical batch, so a shard of a guided batch takes the kernels of the unsplit one.
+  d3pm_shape gsh;
+  d3pm_tuning gtune;
+  if (guide) {
+    gtune = tune_of(sh->tuning);
+    gtune.regime_batch = 2 * (gtune.regime_batch > batch ? gtune.regime_batch : batch);
+    gsh = *sh;
+    gsh.tuning = &gtune;
+    sh = &gsh;
+  }
+  const int eval_batch = guide ? 2 * batch : batch;
+  Workspace ws = carve(*sh, eval_batch, static_cast<char*>(workspace));
   D3PM_REQUIRE(workspace_bytes >= ws.total, D3PM_E_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, ws.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rows = batch * sh->canvas;
   const Ctx cx(sh->tuning);
-  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, keys};
+  const DenoiserArgs q{*sh, *w, eval_batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, keys, guide ? rows : 0};
   const int plan = fold_plan(q, flags, f8);      // the same for every iteration: the blocks and the sampler's prep share it
   bool prepared = false;      // the previous iteration's sampler launch has already embedded x_t and folded fc1 for this t
   for (int t = t_start; t > t_stop; --t) {
@@ -1059,8 +1092,9 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     a.pc = make_posterior_consts(sched, t);
     a.known = cm.known;
     if (sm) { a.temperature = sm->temperature; a.top_k = sm->top_k; a.top_p = sm->top_p; }
+    if (guide) { a.guided = true; a.guidance = guide->weight; }
 #ifdef D3PM_ABLATIONS
-    if (!cm.known && !a.filtered() && !a.nucleus() && fused_final_sample_applies(*sh, *w, ws, flags)) {
+    if (!guide && !cm.known && !a.filtered() && !a.nucleus() && fused_final_sample_applies(*sh, *w, ws, flags)) {
       // final projection + posterior + draw in one kernel: the logits stay on chip (d3pm_final_sample.hip)
       ProfScope p(cx, D3PM_K_SAMPLE, s, 2.0 * rows * sh->n_classes * sh->d_model,
                   dtype_size(sh->dtype) * (static_cast<double>(rows) * sh->d_model + static_cast<double>(sh->n_classes) * sh->d_model) + 8.0 * rows);
@@ -1068,9 +1102,9 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     } else
 #endif
     {
-      D3PM_TRY(final_logits(*sh, *w, batch, ws, ws.logits, logits_ld(*sh), flags, s));
+      D3PM_TRY(final_logits(*sh, *w, eval_batch, ws, ws.logits, logits_ld(*sh), flags, s));
       ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0,
-                  static_cast<double>(rows) * levels(*sh) * (sh->n_classes * dtype_size(sh->dtype) + 8.0));
+                  static_cast<double>(rows) * levels(*sh) * ((guide ? 2.0 : 1.0) * sh->n_classes * dtype_size(sh->dtype) + 8.0));
       NextIterPrep nx;
       if (t - 1 > t_stop && plan != FOLD_NONE) {
         const size_t es = dtype_size(sh->dtype);
@@ -1081,10 +1115,11 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
         nx.Wf = ws.fc1f; nx.s_out = ws.fc1f_s; nx.b_out = ws.fc1f_b;
       }
       if (nx.table && posterior_sample_prep_supported(a, nx)) {
-        D3PM_TRY(posterior_sample_prep(a, nx, s));       // + the embedding rows, their moments and the fc1 fold of iteration t - 1
+        // + the embedding rows, their moments and the fc1 fold of iteration t - 1 (guided: the rows of both halves)
+        D3PM_TRY(guide ? posterior_sample_prep_guided(a, nx, s) : posterior_sample_prep(a, nx, s));
         prepared = true;
       } else {
-        D3PM_TRY(posterior_sample(a, s));
+        D3PM_TRY(guide ? posterior_sample_guided(a, s) : posterior_sample(a, s));
       }
     }
   }
@@ -1163,6 +1198,54 @@ int d3pm_sample_loop_keys(const d3pm_shape* sh, const d3pm_weights* w, const d3p
   return sample_loop_impl(sh, w, batch, x, canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask), t_start, t_stop,
                           film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks, nucleus,
                           "d3pm_sample_loop_keys", key_counts(keys));
+}
+
+// ---- classifier-free guidance (d3pm_guidance) -----------------------------------------------------------------------------------------
+// refused before anything is launched: a missing weight, a weight that is negative or not finite, more than one level
+static int check_guidance(const d3pm_shape* sh, const d3pm_guidance* g, const char* who) {
+  D3PM_REQUIRE(sh, D3PM_E_ARG, "null shape");
+  D3PM_REQUIRE(g, D3PM_E_ARG, "%s: null d3pm_guidance", who);
+  D3PM_REQUIRE(std::isfinite(g->weight) && g->weight >= 0.f, D3PM_E_ARG, "%s: guidance weight %g is not a finite number >= 0", who,
+               static_cast<double>(g->weight));
+  D3PM_REQUIRE(levels(*sh) == 1, D3PM_E_ARG, "%s: guidance is defined for n_q = 1 (got %d levels)", who, levels(*sh));
+  return D3PM_OK;
+}
+
+int d3pm_posterior_sample_guided(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t, int32_t* x_next,
+                                 const d3pm_canvas* canvas, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags,
+                                 const d3pm_nucleus* nucleus, const d3pm_guidance* guidance, void* stream) {
+  const char* who = "d3pm_posterior_sample_guided";
+  D3PM_TRY(check_guidance(sh, guidance, who));
+  D3PM_TRY(check_shape(sh, batch));
+  D3PM_TRY(check_sampling(sh, nucleus, who));
+  D3PM_REQUIRE(!(flags & D3PM_FLAG_SEED_IN_HBM), D3PM_E_ARG, "%s: D3PM_FLAG_SEED_IN_HBM (graph replay) is not supported under guidance", who);
+  D3PM_REQUIRE(logits && x_t && x_next && sched && sched->d && sched->c && sched->dbar && sched->cbar, D3PM_E_ARG, "%s: null pointer", who);
+  D3PM_REQUIRE(t >= 0 && t < sched->timesteps, D3PM_E_ARG, "t=%d outside the schedule", t);
+  SampleArgs a;
+  a.logits = logits; a.logits_dtype = logits_dtype; a.ldl = sh->n_classes; a.x_t = x_t; a.x_next = x_next;
+  a.rows = batch * sh->canvas; a.n_classes = sh->n_classes; a.mask_id = sh->mask_id; a.n_q = 1;
+  a.canvas = sh->canvas; a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas);
+  a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0; a.pc = make_posterior_consts(sched, t);
+  a.known = canvas ? canvas->known : nullptr;
+  if (nucleus) { a.temperature = nucleus->temperature; a.top_k = nucleus->top_k; a.top_p = nucleus->top_p; }
+  a.guided = true; a.guidance = guidance->weight;
+  return posterior_sample_guided(a, static_cast<hipStream_t>(stream));
+}
+
+int d3pm_sample_loop_guided(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch, int32_t* x,
+                            const uint8_t* frame_mask,
+                            const d3pm_canvas* canvas, int t_start, int t_stop, const void* film, const void* kv_text, const void* kv_prompt,
+                            const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace, size_t workspace_bytes,
+                            int32_t* trace, const d3pm_nucleus* nucleus, const d3pm_keys* keys, const d3pm_guidance* guidance, void* stream) {
+  const char* who = "d3pm_sample_loop_guided";
+  D3PM_TRY(check_guidance(sh, guidance, who));
+  D3PM_REQUIRE((frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
+               "%s: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)", who);
+  D3PM_REQUIRE(!(flags & D3PM_FLAG_SEED_IN_HBM), D3PM_E_ARG, "%s: D3PM_FLAG_SEED_IN_HBM (graph replay) is not supported under guidance", who);
+  D3PM_REQUIRE(!fp8_blocks, D3PM_E_ARG, "%s: the fp8 fast path takes no guidance", who);
+  return sample_loop_impl(sh, w, batch, x, canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask), t_start, t_stop,
+                          film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace, stream, nullptr, nucleus, who,
+                          key_counts(keys), guidance);
 }
 
 // ---- confidence-ordered reveal (d3pm_reveal) ------------------------------------------------------------------------------------------

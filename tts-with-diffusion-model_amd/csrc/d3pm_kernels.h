@@ -159,6 +159,9 @@ struct SampleArgs {
   // step entry's optional device float [rows] (theta per row, NaN for a known row).  Either one takes the kernels' nucleus arm.
   float top_p = 1.0f; float* theta_out = nullptr;
   bool nucleus() const { return top_p < 1.0f || theta_out != nullptr; }
+  // d3pm_guidance: `logits` holds 2 * rows rows (row rows + r = row r under the null condition) and the routine runs on
+  // rn16(fmaf(guidance, c - u, c)); x_t / x_next / known stay `rows` long.  posterior_sample_guided / posterior_sample_prep_guided only.
+  bool guided = false; float guidance = 0.f;
   PosteriorConsts pc{};
 };
 
@@ -198,6 +201,10 @@ struct NextIterPrep {
 };
 bool posterior_sample_prep_supported(const SampleArgs& a, const NextIterPrep& n);
 int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_t s);
+// the two launches under classifier-free guidance (SampleArgs.guided; kernels of their own: an unguided call runs none of their code).
+// The prep form embeds rows r and rows + r of n.x / n.stats and applies wherever posterior_sample_prep_supported(a, n) holds.
+int posterior_sample_guided(const SampleArgs& a, hipStream_t s);
+int posterior_sample_prep_guided(const SampleArgs& a, const NextIterPrep& n, hipStream_t s);
 
 // One step of the confidence-ordered reveal (d3pm_reveal, d3pm_reveal.hip; n_q = 1): reveal_candidates scores the masked free rows at
 // timestep t into cand / score, then reveal_commit (one wave per utterance) or reveal_commit_prep (one wave per row + NextIterPrep

@@ -187,6 +187,94 @@ __global__ __launch_bounds__(256) void nucleus_sample_prep_rows(
                                                           known, flt, RowNucleus{top_p, nullptr});
 }
 
+// ---- classifier-free guidance (d3pm_guidance) -------------------------------------------------------------------
+// The logits buffer holds 2 * rows rows: row r is utterance row r under its condition (c), row rows + r the same frame under the
+// null condition (u).  The accessor hands the row routines  fmaf(w, float(c_j) - float(u_j), float(c_j))  -- an fp32 subtraction and
+// an explicit fma, no contraction left to the compiler -- and the routines round it to fp16 as their first act, where they round a
+// plain logit today: one rounding, z_j = rn16(...).  Everything behind the load is the routine as it is.
+template <typename T>
+struct GuidedRow {
+  const T* c; const T* u; float w;
+  __device__ __forceinline__ GuidedRow(const T* c_, const T* u_, float w_) : c(c_), u(u_), w(w_) {}
+  __device__ __forceinline__ float operator[](int j) const {
+    const float cj = static_cast<float>(c[j]);
+    return __builtin_fmaf(w, cj - static_cast<float>(u[j]), cj);
+  }
+};
+
+// The guided kernels always carry the nucleus arm: with the neutral triple (1, 0, 1) filter_row and nucleus_row change no value (both
+// tests are kernel-uniform and skip; the maximum is taken again over the same numbers), so the ids are those of the unfiltered
+// routine -- tests/test_gpu_guidance.py compares exactly that pair.  n_q = 1, seed by value (the entries refuse anything else).
+// k1025: the reference's class count takes kernels with the predicate-free routine alone, any other K kernels with the general routine
+// alone.  (One kernel with both behind a kernel-uniform branch, as the unguided kernels have it, runs out of scalar registers here:
+// the lane masks of the general routine's per-class guards stay alive across two loads and an fma each.)
+template <typename T, bool k1025>
+__device__ __forceinline__ int guided_row_draw(const T* __restrict__ logits, int ldl, int row, int rows, int K, int mask_id, int x, uint64_t seed,
+                                               uint32_t grow, int greedy, const PosteriorConsts& pc, int lane, const RowFilter& flt, float top_p, float w) {
+  const GuidedRow<T> lr(logits + static_cast<size_t>(row) * ldl, logits + (static_cast<size_t>(rows) + row) * ldl, w);
+  const RowNucleus nuc{top_p, nullptr};
+  if constexpr (k1025)
+    return sample_row_1025<T, kNucleusArm>(lr, mask_id, x, seed, grow, greedy, pc, lane, 0u, D3PM_SAMPLER_EARLY_OUT != 0, flt, nuc);
+  else
+    return sample_row<T, kNucleusArm>(lr, K, mask_id, x, seed, grow, greedy, pc, nullptr, lane, 0u, flt, nuc);
+}
+
+template <typename T, bool kKnown, bool k1025>
+__global__ __launch_bounds__(256) void guided_sample_rows(
+    const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next, int32_t* x_next2, int rows, int K, int mask_id,
+    uint64_t seed, uint32_t row0, int greedy, PosteriorConsts pc, const uint8_t* __restrict__ known, RowFilter flt, float top_p, float w) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  int best_j;
+  bool keep = false;
+  if constexpr (kKnown) keep = row_is_known(known, row);      // wave-uniform: one wave per row
+  if (keep)
+    best_j = x_t[row];
+  else
+    best_j = guided_row_draw<T, k1025>(logits, ldl, row, rows, K, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, lane, flt, top_p, w);
+  if (lane == 0) {
+    x_next[row] = best_j;
+    if (x_next2) x_next2[row] = best_j;
+  }
+}
+
+// posterior_sample_prep_rows under guidance: the wave that draws row r writes the next iteration's embedding row and moments of rows
+// r AND rows + r (the null twin sees the same x); the fc1-fold workgroups are those of the unguided launch.
+// (The body repeats posterior_sample_prep_rows_body statement for statement instead of sharing it through a functor: with the shared
+// form the compiler allocates the registers of the UNGUIDED fused kernels differently, and those are to stay the code they were.
+// A change to either body belongs in both.)
+template <typename T, bool kKnown, bool k1025>
+__global__ __launch_bounds__(256) void guided_sample_prep_rows(
+    const T* __restrict__ logits, int ldl, const int32_t* x_t, int32_t* x_next, int32_t* x_next2, int rows, int K, int mask_id,
+    uint64_t seed, uint32_t row0, int greedy, PosteriorConsts pc, int mask_period, int sample_blocks,
+    const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
+    bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
+    const uint8_t* __restrict__ known, RowFilter flt, float top_p, float w) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (static_cast<int>(blockIdx.x) >= sample_blocks) {
+    const int r = (blockIdx.x - sample_blocks) * 4 + wave;
+    if (r < 4 * d * n_layers) fold_layer_row<T>(fp, film_t, 4 * d, d, r, lane, Wf, s_out, b_out);
+    return;
+  }
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  int best_j;
+  bool keep = false;
+  if constexpr (kKnown) keep = row_is_known(known, row);      // wave-uniform: one wave per row
+  if (keep)
+    best_j = x_t[row];
+  else
+    best_j = guided_row_draw<T, k1025>(logits, ldl, row, rows, K, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, lane, flt, top_p, w);
+  if (lane == 0) {
+    x_next[row] = best_j;
+    if (x_next2) x_next2[row] = best_j;
+  }
+  const bool live = frame_mask[row % mask_period] != 0;
+  embed_row_stats<T>(table, best_j, live, xres, row, d, K, stats, quads, lane);
+  embed_row_stats<T>(table, best_j, live, xres, rows + row, d, K, stats, quads, lane);
+}
+
 // forward noising: logits are log16(rn16(row_of_Qbar_t + eps)) with at most three distinct values
 __global__ __launch_bounds__(256) void q_sample_rows(const int32_t* __restrict__ x0, int32_t* __restrict__ out,
                                                      const uint8_t* __restrict__ frame_mask, int mask_period,
@@ -304,6 +392,67 @@ int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_
 #undef D3PM_PSP
 #undef D3PM_PSP_ARM
 #undef D3PM_PSP_ARGS
+  D3PM_LAUNCH_CHECK();
+  return D3PM_OK;
+}
+
+// a.guided: a.logits holds 2 * a.rows rows (the null twins behind the conditioned rows), x_t / x_next / known a.rows
+int posterior_sample_guided(const SampleArgs& a, hipStream_t s) {
+  D3PM_REQUIRE(a.guided && a.n_q == 1 && !a.seed_hbm && !a.posterior_out && !a.theta_out, D3PM_E_ARG, "guided sampler: one level, seed by value, ids only");
+  D3PM_REQUIRE(a.n_classes <= kWave * kMaxGroupsPerLane * 4, D3PM_E_SHAPE, "posterior_sample supports up to %d classes",
+               kWave * kMaxGroupsPerLane * 4);
+  const dim3 grid((a.rows + 3) / 4), block(256);
+  const RowFilter flt{a.temperature, a.top_k};
+  // the reference's class count takes kernels with the predicate-free routine alone, any other K kernels with the general one alone
+  const bool k1025 = a.n_classes == 1025 && a.mask_id < 1024;
+#define D3PM_GS_ARM(T, kKnown, kRef)                                                                                                          \
+  guided_sample_rows<T, kKnown, kRef><<<grid, block, 0, s>>>(static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next, a.x_next2, a.rows, a.n_classes, \
+                                                             a.mask_id, a.seed, a.row0, a.greedy, a.pc, a.known, flt, a.top_p, a.guidance)
+#define D3PM_GS(T)                                  \
+  do {                                              \
+    if (a.known && k1025) D3PM_GS_ARM(T, true, true);  \
+    else if (a.known) D3PM_GS_ARM(T, true, false);     \
+    else if (k1025) D3PM_GS_ARM(T, false, true);       \
+    else D3PM_GS_ARM(T, false, false);                 \
+  } while (0)
+  switch (a.logits_dtype) {
+    case D3PM_F32: D3PM_GS(float); break;
+    case D3PM_F16: D3PM_GS(f16); break;
+    case D3PM_BF16: D3PM_GS(bf16); break;
+    default: set_error("unknown logits dtype %d", a.logits_dtype); return D3PM_E_ARG;
+  }
+#undef D3PM_GS
+#undef D3PM_GS_ARM
+  D3PM_LAUNCH_CHECK();
+  return D3PM_OK;
+}
+
+// n.x / n.stats hold 2 * a.rows rows; supported where posterior_sample_prep_supported(a, n) holds
+int posterior_sample_prep_guided(const SampleArgs& a, const NextIterPrep& n, hipStream_t s) {
+  D3PM_REQUIRE(a.guided && !a.seed_hbm, D3PM_E_ARG, "guided sampler: seed by value");
+  FoldStepPtrs p{};
+  for (int l = 0; l < n.n_layers; ++l) {
+    p.W[l] = n.blocks[l].fc1_w; p.bias[l] = n.blocks[l].fc1_b; p.gamma[l] = n.blocks[l].norm3_w; p.beta[l] = n.blocks[l].norm3_b;
+  }
+  const int sample_blocks = (a.rows + 3) / 4, fold_blocks = (4 * n.d * n.n_layers + 3) / 4;
+  const dim3 grid(static_cast<unsigned>(sample_blocks + fold_blocks)), block(256);
+  const RowFilter flt{a.temperature, a.top_k};
+  const bool k1025 = a.n_classes == 1025 && a.mask_id < 1024;
+#define D3PM_GSP(T, kKnown, kRef)                                                                                                                \
+  guided_sample_prep_rows<T, kKnown, kRef><<<grid, block, 0, s>>>(                                                                                   \
+      static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next, a.x_next2, a.rows, a.n_classes, a.mask_id, a.seed, a.row0, a.greedy, a.pc,       \
+      n.mask_period, sample_blocks, static_cast<const T*>(n.table), static_cast<T*>(n.x), n.stats, n.frame_mask, n.d, n.quads, p,                \
+      static_cast<const T*>(n.film_t), n.n_layers, static_cast<T*>(n.Wf), n.s_out, n.b_out, a.known, flt, a.top_p, a.guidance)
+#define D3PM_GSP_T(T)                                  \
+  do {                                                 \
+    if (a.known && k1025) D3PM_GSP(T, true, true);      \
+    else if (a.known) D3PM_GSP(T, true, false);         \
+    else if (k1025) D3PM_GSP(T, false, true);           \
+    else D3PM_GSP(T, false, false);                     \
+  } while (0)
+  if (n.dtype == D3PM_F16) D3PM_GSP_T(f16); else D3PM_GSP_T(bf16);
+#undef D3PM_GSP_T
+#undef D3PM_GSP
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

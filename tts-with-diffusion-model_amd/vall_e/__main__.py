@@ -66,6 +66,7 @@ def main(argv=None):
     ap.add_argument("--reveal-steps", type=int, default=None, help="D3PM stage: confidence-ordered reveal in this many denoiser evaluations")
     ap.add_argument("--choice-temperature", type=float, default=0.0, help="D3PM stage, with --reveal-steps: Gumbel noise on the reveal order (>= 0)")
     ap.add_argument("--mask-padding", action="store_true", help="D3PM stage: key-padding masks, the utterance ignores its own padding")
+    ap.add_argument("--guidance", type=float, default=0.0, help="D3PM stage: classifier-free guidance weight w (>= 0, 0 = off): draw from (1 + w) cond - w null")
     ap.add_argument("--native", action="store_true", help="the shape upstream's class really builds (d=32, 16 heads, 8 blocks)")
     args = ap.parse_args(argv)
 
@@ -74,6 +75,8 @@ def main(argv=None):
     try:
         _hip.nucleus_options(args.temperature, args.top_k, args.top_p, 1025)
         _hip.reveal_options(args.reveal_steps, args.choice_temperature)
+        if _hip.guidance_options(args.guidance) is not None and args.reveal_steps is not None:
+            raise ValueError("--guidance does not combine with --reveal-steps")
     except ValueError as e:
         ap.error(str(e))
     if len(args.paths) not in (1, 3):
@@ -120,7 +123,7 @@ def main(argv=None):
         phns = torch.tensor([int(p) for p in args.phonemes.split()], dtype=torch.long)
     n_frames = model.cfg.n_frames if args.frames is None else args.frames
     sampling = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, reveal_steps=args.reveal_steps,
-                    choice_temperature=args.choice_temperature, mask_padding=args.mask_padding)
+                    choice_temperature=args.choice_temperature, mask_padding=args.mask_padding, guidance=args.guidance)
     if args.frames is None and args.continue_from is None:
         codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed, **sampling)
     else:

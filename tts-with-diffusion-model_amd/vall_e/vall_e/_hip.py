@@ -191,6 +191,23 @@ def nucleus_options(temperature=1.0, top_k=0, top_p=1.0, n_classes=None):
     return Nucleus(1.0, 0, p) if smp is None else Nucleus(smp.temperature, smp.top_k, p)
 
 
+class Guidance(C.Structure):
+    """d3pm_guidance: the weight w of classifier-free guidance, z = rn16(fmaf(w, c - u, c)) (include/d3pm_hip.h)."""
+    _fields_ = [("weight", C.c_float)]
+
+
+def guidance_options(guidance=0.0):
+    """Host validation of the guidance weight (ValueError, before any GPU work) -> None for 0 (the entries and kernels that know
+    nothing of guidance), a Guidance struct otherwise."""
+    if isinstance(guidance, bool) or not isinstance(guidance, (int, float)):
+        raise ValueError(f"guidance must be a number, got {guidance!r}")
+    w = float(guidance)
+    if not (math.isfinite(w) and w >= 0.0) or not math.isfinite(C.c_float(w).value):
+        raise ValueError(f"guidance must be finite and >= 0 (0 = off), got {guidance!r}")
+    w = C.c_float(w).value
+    return None if w == 0.0 else Guidance(w)
+
+
 class Reveal(C.Structure):
     """d3pm_reveal: the confidence-ordered reveal schedule, N denoiser evaluations (include/d3pm_hip.h)."""
     _fields_ = [("n_steps", C.c_int32), ("choice_temperature", C.c_float)]
@@ -259,6 +276,13 @@ SIGNATURES = {
     "d3pm_op_attention_pair_keylen": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(Tuning), C.c_void_p]),
+    "d3pm_posterior_sample_guided": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Canvas),
+                                               C.c_int, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(Nucleus),
+                                               C.POINTER(Guidance), C.c_void_p]),
+    "d3pm_sample_loop_guided": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.POINTER(Canvas), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.POINTER(Nucleus), C.POINTER(Keys), C.POINTER(Guidance), C.c_void_p]),
     "d3pm_denoise_step": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                     C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]),
@@ -748,19 +772,38 @@ class Sampler:
         return () if self.n_q == 1 else (self.n_q,)
 
     def posterior_sample(self, logits, x_t, t, seed, utt0=0, flags=0, want_posterior=False, known=None, temperature=1.0, top_k=0,
-                         top_p=1.0, want_theta=False):
+                         top_p=1.0, want_theta=False, guidance=0.0, null_logits=None):
         """known: uint8 [B, canvas] or None -- frames that keep x_t instead of being drawn (d3pm_posterior_sample_known).
+        guidance (> 0) with null_logits (the logits of the same rows under the null condition, shape and dtype of `logits`): the
+        draw runs on rn16(fmaf(guidance, logits - null_logits, logits)) (d3pm_posterior_sample_guided; ids only: no posterior, no theta).
         temperature / top_k: d3pm_sampling (d3pm_posterior_sample_sampling); the neutral pair takes the entries without them.
         top_p: d3pm_nucleus (d3pm_posterior_sample_nucleus); 1 takes the entries without it.  want_theta: a third result, the nucleus
         threshold of every row as float32 in the shape of x_t (-inf where top_p is 1, NaN for a known frame)."""
         cfg = self.cfg
         smp = nucleus_options(temperature, top_k, top_p, cfg.n_classes)
+        gd = guidance_options(guidance)
+        if (gd is None) != (null_logits is None):
+            raise ValueError("guidance and null_logits go together: a weight > 0 needs the null logits, and they need a weight")
+        if gd is not None and (want_posterior or want_theta or self.n_q > 1):
+            raise ValueError("the guided draw returns ids only (no posterior, no theta) and is defined for n_q = 1")
         B = self._check_grid(x_t)
         if known is not None:
             _require(known, "known", (B, cfg.canvas), (torch.uint8,), self.device)
         logits = logits.contiguous() if isinstance(logits, torch.Tensor) else logits
         _require(logits, "logits", (B, cfg.canvas) + self._lvl() + (cfg.n_classes,), tuple(_DTYPES), self.device)
         x_next = torch.empty_like(x_t)
+        if gd is not None:
+            _require(null_logits, "null_logits", tuple(logits.shape), (logits.dtype,), self.device)
+            both = torch.cat([logits, null_logits.contiguous()], 0)      # [2B, canvas, K]: the null twins behind the conditioned rows
+            cv = None
+            if known is not None:
+                cv = Canvas(None, known.data_ptr())
+            nuc = self._as_nucleus(smp)
+            check(lib().d3pm_posterior_sample_guided(C.byref(self.shape), B, _p(both), dtype_code(both.dtype), _p(x_t), _p(x_next),
+                                                     None if cv is None else C.byref(cv), int(t), C.byref(self.schedule.c_struct), seed,
+                                                     utt0, flags, None if nuc is None else C.byref(nuc), C.byref(gd), stream_ptr()),
+                  "d3pm_posterior_sample_guided")
+            return x_next, None
         post = torch.empty((B, cfg.canvas) + self._lvl() + (cfg.n_classes,), dtype=torch.int16, device=self.device) if want_posterior else None
         if want_theta or isinstance(smp, Nucleus):
             theta = torch.empty(x_t.shape, dtype=torch.float32, device=self.device) if want_theta else None
@@ -799,23 +842,38 @@ class Sampler:
         return x_next
 
     def sample_loop(self, x, frame_mask, t_start, t_stop, kv_t, kv_p, seed, utt0=0, flags=0, trace=False, slot=0,
-                    fp8=False, known=None, temperature=1.0, top_k=0, top_p=1.0, keys=None):
+                    fp8=False, known=None, temperature=1.0, top_k=0, top_p=1.0, keys=None, guidance=0.0):
         """frame_mask uint8 [canvas] (shared by the batch) runs d3pm_sample_loop(_fp8); a per-utterance mask [B, canvas] and / or a
         known-frame map `known` (uint8 [B, canvas]; `x` already carries the given ids) run the *_canvas entries.  temperature /
         top_k other than the neutral (1, 0) run d3pm_sample_loop_sampling, which covers the four of them; top_p other than 1 runs
         d3pm_sample_loop_nucleus, which takes the same arguments.  keys: None or the (frames, text, prompt) key counts of make_keys
-        (d3pm_sample_loop_keys, which covers all of the above but fp8)."""
+        (d3pm_sample_loop_keys, which covers all of the above but fp8).  guidance > 0 (classifier-free guidance,
+        d3pm_sample_loop_guided): kv_t / kv_p hold 2B utterances -- the null twins behind the conditioned ones -- and so do the three
+        arrays of `keys`; x, frame_mask, known and the trace stay those of B utterances.  No fp8, no n_q > 1."""
         cfg = self.cfg
         smp = nucleus_options(temperature, top_k, top_p, cfg.n_classes)
+        gd = guidance_options(guidance)
         if keys is not None and fp8:
             raise ValueError("the fp8 fast path takes no key mask")
+        if gd is not None and (fp8 or self.n_q > 1):
+            raise ValueError("guidance does not combine with " + ("fp8=True" if fp8 else "an n_q > 1 model"))
         per_utt = known is not None or (isinstance(frame_mask, torch.Tensor) and frame_mask.dim() == 2)
         B = self._check_grid(x, None if per_utt else frame_mask, "x")
         cv = self._check_canvas(B, frame_mask, known) if per_utt else None
-        self._check_kv(kv_t, kv_p, B)
-        ks = make_keys(keys, B, self.device)
-        ws = self.workspace(B, slot)
+        eval_B = B if gd is None else 2 * B
+        self._check_kv(kv_t, kv_p, eval_B)
+        ks = make_keys(keys, eval_B, self.device)
+        ws = self.workspace(eval_B, slot)
         tr = torch.empty((t_start - t_stop, B, cfg.canvas) + self._lvl(), dtype=torch.int32, device=self.device) if trace else None
+        if gd is not None:
+            nuc = self._as_nucleus(smp)
+            check(lib().d3pm_sample_loop_guided(C.byref(self.shape), C.byref(self.weights.c_struct), None, B, _p(x),
+                                                None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None,
+                                                int(t_start), int(t_stop), _p(self.film), _p(kv_t), _p(kv_p),
+                                                C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
+                                                None if nuc is None else C.byref(nuc), None if ks is None else C.byref(ks), C.byref(gd),
+                                                stream_ptr()), "d3pm_sample_loop_guided")
+            return tr
         if ks is not None:
             nuc = self._as_nucleus(smp)
             check(lib().d3pm_sample_loop_keys(C.byref(self.shape), C.byref(self.weights.c_struct), None, B, _p(x),

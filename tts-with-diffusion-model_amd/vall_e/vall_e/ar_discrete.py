@@ -342,6 +342,27 @@ class AR(SymmapState, nn.Module):
         dev = self.device
         return x.contiguous().to(dev), frame_mask.to(dev), (kmap.to(dev) if bool(kmap.any()) else None)
 
+    def _null_conditions(self, like, given, dims):
+        """The null twins' texts (dims 1) or prompts (dims 2): the caller's entries, the empty condition where there is none."""
+        def empty(ref):
+            ref = torch.as_tensor(ref)
+            return ref.new_zeros((0,)) if dims == 1 else ref.new_zeros((0,) + tuple(ref.shape[1:]) if ref.dim() == 2 else (0, self.cfg.n_levels))
+        return [empty(ref) if given is None or given[b] is None else given[b] for b, ref in enumerate(like)]
+
+    def _twin_key_lengths(self, key_lens, null_text_list, null_proms_list):
+        """The key counts of B utterances -> those of the 2B of a guided call: a twin has its partner's frames; an empty null text /
+        prompt keeps all of its padding as keys (it has nothing else), a caller-given one its own length."""
+        cfg = self.cfg
+        frames, text, prompt = (list(v) for v in key_lens)
+
+        def lens(given, cap):
+            out = []
+            for b in range(len(frames)):
+                n = 0 if given is None or given[b] is None else int(given[b].shape[0]) if given[b].dim() else 0
+                out.append(min(n, cap) if n > 0 else cap)
+            return out
+        return frames + frames, text + lens(null_text_list, cfg.s_text), prompt + lens(null_proms_list, cfg.s_prompt)
+
     # ------------------------------------------------------------------ the hot path
     @torch.no_grad()
     def generate_audio(self, text_list, proms_list, resps_list=None, *, steps: Optional[int] = None,
@@ -351,7 +372,8 @@ class AR(SymmapState, nn.Module):
                        known: Optional[Sequence[Optional[Tensor]]] = None,
                        known_mask: Optional[Sequence[Optional[Tensor]]] = None, temperature: float = 1.0, top_k: int = 0,
                        top_p: float = 1.0, reveal_steps: Optional[int] = None, choice_temperature: float = 0.0,
-                       mask_padding: bool = False):
+                       mask_padding: bool = False, guidance: float = 0.0,
+                       null_text_list: Optional[Sequence[Tensor]] = None, null_proms_list: Optional[Sequence[Tensor]] = None):
         """Reverse diffusion for len(text_list) utterances.  Positional behaviour as upstream:
         one utterance -> int64 [canvas] (squeezed, untrimmed; rows >= n_frames are sampled from
         final.bias and meaningless); with n_q > 1 (constructor) [canvas, n_q] / [B, canvas, n_q].  `resps_list` is ignored, as
@@ -408,10 +430,34 @@ class AR(SymmapState, nn.Module):
         n_frames sequences, known / known_mask, temperature / top_k / top_p, reveal_steps, greedy, utt0 / global_batch, streams,
         return_trace and n_q > 1; an empty text or prompt, graph=True and fp8=True raise ValueError before any GPU work.  The
         synthetic and the upstream weights were trained with the padding as keys and the training step (forward, forward_backward)
-        does not take the mask: no statement about audio quality is made for it."""
+        does not take the mask: no statement about audio quality is made for it.
+        `guidance=w` (finite, >= 0; 0 = the loop above, untouched) is classifier-free guidance (include/d3pm_hip.h: d3pm_guidance):
+        every reverse step evaluates the denoiser for 2B utterances in one evaluation -- each utterance and its null twin, which has
+        the same canvas but no phonemes and no prompt frames (the empty text and prompt, zero padded like any other) -- and the
+        sampler launch draws from rn16(fmaf(w, cond - null, cond)) of the two logit rows, with everything else (temperature / top_k /
+        top_p, posterior, noise) as without it.  `null_text_list` / `null_proms_list` (B entries each; None = the empty one) give
+        a caller-chosen "negative" condition per utterance instead.  The result, the trace and the noise keys stay those of B
+        utterances.  It composes with n_frames sequences, known / known_mask, temperature / top_k / top_p, greedy, utt0 /
+        global_batch (counted in logical utterances), streams (a chunk carries its twins), return_trace, steps and mask_padding
+        (the default null twin keeps all of its padding as keys: it has nothing else; a caller-given null keeps its own lengths;
+        its frames are its partner's); with graph=True, fp8=True, reveal_steps or an n_q > 1 model it raises ValueError before any
+        GPU work, as do a negative, non-finite or bool weight and null lists without guidance or of the wrong length.  Guidance
+        is meaningful for weights trained with the conditions dropped some of the time (forward_backward(cond_drop=...)); no
+        statement about audio quality is made for the synthetic or the upstream weights."""
         if len(text_list) != len(proms_list) or len(text_list) == 0:
             raise ValueError("text_list and proms_list must be non-empty and of equal length")
         B = len(text_list)
+        guided = _hip.guidance_options(guidance) is not None      # host validation before any GPU work
+        if not guided and (null_text_list is not None or null_proms_list is not None):
+            raise ValueError("null_text_list / null_proms_list without guidance")
+        if guided:
+            for name, bad in (("graph=True", bool(graph)), ("fp8=True", bool(fp8)), ("reveal_steps", reveal_steps is not None),
+                              ("an n_q > 1 model", self.cfg.n_q > 1)):
+                if bad:
+                    raise ValueError(f"guidance does not combine with {name}")
+            for name, lst in (("null_text_list", null_text_list), ("null_proms_list", null_proms_list)):
+                if lst is not None and len(lst) != B:
+                    raise ValueError(f"{name} has {len(lst)} entries for {B} utterances")
         key_lens = None
         if mask_padding:
             for name, bad in (("graph=True", bool(graph)), ("fp8=True", bool(fp8))):
@@ -441,14 +487,29 @@ class AR(SymmapState, nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())       # follows torch.manual_seed
         n_streams = max(1, min(B, self.loop_streams if streams is None else streams))
         regime = max(int(global_batch), B) if global_batch else (B if n_streams > 1 else 0)
+        if guided:
+            # the null twins: utterance B + b of every evaluation.  regime_batch keeps counting logical utterances (the library doubles
+            # it for the loop); the encoders run once over all 2B utterances under the doubled count
+            regime = max(regime, B)
+            text_list = list(text_list) + self._null_conditions(text_list, null_text_list, 1)
+            proms_list = list(proms_list) + self._null_conditions(proms_list, null_proms_list, 2)
+            if key_lens is not None:
+                key_lens = self._twin_key_lengths(key_lens, null_text_list, null_proms_list)
         with torch.cuda.device(self.device), _hip.tuning(regime_batch=regime):
-            keys = None      # d3pm_keys: (frames, text, prompt), int32 [B] on the device
+            keys = None      # d3pm_keys: (frames, text, prompt), int32 [B] on the device ([2B] under guidance)
             if key_lens is not None:
                 keys = tuple(torch.tensor(v, dtype=torch.int32, device=self.device) for v in key_lens)
-            cond_text, cond_prompt = self.encode_conditions(text_list, proms_list, *(keys[1:] if keys else ()))
+            if guided:      # the encoders see all 2B utterances at once, under the count the loop's evaluations run with
+                with _hip.tuning(regime_batch=2 * regime):
+                    cond_text, cond_prompt = self.encode_conditions(text_list, proms_list, *(keys[1:] if keys else ()))
+            else:
+                cond_text, cond_prompt = self.encode_conditions(text_list, proms_list, *(keys[1:] if keys else ()))
+
+            def chunk(t, lo, hi):      # under guidance a chunk carries its twins: rows [lo, hi) and [B + lo, B + hi) of a 2B-long array
+                return torch.cat([t[lo:hi], t[B + lo:B + hi]], 0) if guided else t[lo:hi]
 
             def chunk_keys(lo, hi):
-                return None if keys is None else tuple(k[lo:hi] for k in keys)
+                return None if keys is None else tuple(chunk(k, lo, hi) for k in keys)
             if not per_utt:
                 x, frame_mask, kmap = self.canvas_init(B, n_frames) + (None,)
             fl = flags | (_hip.FLAG_GREEDY if greedy else 0)
@@ -468,7 +529,7 @@ class AR(SymmapState, nn.Module):
                                             keys=keys)
                 else:
                     trace = smp.sample_loop(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl, trace=return_trace, fp8=fp8, known=kmap,
-                                            temperature=temperature, top_k=top_k, top_p=top_p, keys=keys)
+                                            temperature=temperature, top_k=top_k, top_p=top_p, keys=keys, guidance=guidance)
             else:
                 # utterances are independent: chunks of the batch run the whole loop on their own stream so that
                 # the short kernels of one chunk fill the ramp-up / epilogue bubbles of the others
@@ -482,7 +543,7 @@ class AR(SymmapState, nn.Module):
                     st = self._streams[i]
                     st.wait_stream(cur)
                     with torch.cuda.stream(st):
-                        kv_t, kv_p = smp.cond_kv(cond_text[lo:hi], cond_prompt[lo:hi])
+                        kv_t, kv_p = smp.cond_kv(chunk(cond_text, lo, hi), chunk(cond_prompt, lo, hi))
                         if rv is not None:
                             smp.reveal_loop(x[lo:hi], frame_mask[lo:hi] if per_utt else frame_mask, rv.n_steps, kv_t, kv_p, seed, utt0 + lo, fl,
                                             slot=i, known=None if kmap is None else kmap[lo:hi], temperature=temperature, top_k=top_k,
@@ -490,7 +551,7 @@ class AR(SymmapState, nn.Module):
                         else:
                             smp.sample_loop(x[lo:hi], frame_mask[lo:hi] if per_utt else frame_mask, t_start, 0, kv_t, kv_p, seed, utt0 + lo, fl,
                                             slot=i, known=None if kmap is None else kmap[lo:hi], temperature=temperature, top_k=top_k,
-                                            top_p=top_p, keys=chunk_keys(lo, hi))
+                                            top_p=top_p, keys=chunk_keys(lo, hi), guidance=guidance)
                         for t_ in (kv_t, kv_p, cond_text, cond_prompt, x):
                             t_.record_stream(st)
                 for i in range(n_streams):
@@ -502,14 +563,18 @@ class AR(SymmapState, nn.Module):
     # ------------------------------------------------------------------ upstream method names
     @torch.no_grad()
     def p_sample(self, model_logits: Tensor, t: Tensor, x: Tensor, *, seed: int = 0, utt0: int = 0, temperature: float = 1.0,
-                 top_k: int = 0, top_p: float = 1.0):
+                 top_k: int = 0, top_p: float = 1.0, guidance: float = 0.0, null_logits: Optional[Tensor] = None):
         """One reverse transition from x0-logits [B,T,K] at step t[0] (ar_discrete.py:401-420).
         Returns (sample int64 [B,T], softmax(logits)) like upstream (the softmax of the logits as given: `temperature` / `top_k` /
-        `top_p`, as in generate_audio, act on the draw only).  Bad values are a ValueError before any GPU work."""
+        `top_p`, as in generate_audio, act on the draw only).  `guidance` (> 0) with `null_logits` [B,T,K], the logits of the same
+        rows under the null condition, draws from rn16(fmaf(guidance, logits - null_logits, logits)) (the one-step entry of
+        generate_audio(guidance=...)).  Bad values are a ValueError before any GPU work."""
         _hip.nucleus_options(temperature, top_k, top_p, N_CLASSES)
+        if (_hip.guidance_options(guidance) is None) != (null_logits is None):
+            raise ValueError("guidance and null_logits go together")
         smp = self.sampler()
         x_next, _ = smp.posterior_sample(model_logits, x.to(torch.int32).contiguous(), int(t.reshape(-1)[0]), seed, utt0,
-                                         temperature=temperature, top_k=top_k, top_p=top_p)
+                                         temperature=temperature, top_k=top_k, top_p=top_p, guidance=guidance, null_logits=null_logits)
         return x_next.long(), F.softmax(model_logits, dim=-1)
 
     @torch.no_grad()
@@ -520,7 +585,7 @@ class AR(SymmapState, nn.Module):
         return smp.q_sample(x_start.to(torch.int32).contiguous(), fm, int(t.reshape(-1)[0]), seed, utt0).long()
 
     def forward_backward(self, text_list, proms_list, resps_list, *, seed: Optional[int] = None, timesteps: Optional[int] = None,
-                         dropout=False, utt0: int = 0):
+                         dropout=False, utt0: int = 0, cond_drop=0.0):
         """The training step's compute (reference: `engine.backward(engine(...))`, utils/engines.py:144-147 over
         ar_discrete.py:588-694): the loss of `forward` AND its gradient for every parameter the forward reads, accumulated
         into `param.grad` by the HIP backward kernels (vall_e/vall_e/train.py; fp32 model).  Follow it with
@@ -529,12 +594,15 @@ class AR(SymmapState, nn.Module):
         ar_discrete.py:216-230) from a Philox mask keyed by (seed, utterance, site); a (p_layer, p_mlp) pair sets other
         probabilities; the default False is eval-mode arithmetic (`self.training` is not consulted).  Upstream's masks come
         from torch's global generator, a stream that is not reproduced.  utt0: global index of the first utterance (a
-        data-parallel rank passes its shard offset), which keys the q_sample noise and the masks."""
+        data-parallel rank passes its shard offset), which keys the q_sample noise and the masks.
+        cond_drop: p or (p_text, p_prompt) -- the probability with which an utterance's text / prompt is replaced by the empty one
+        for this step (the null condition of generate_audio(guidance=...): what classifier-free guidance needs the weights to
+        have seen); decided per utterance from (seed, utt0 + b) on Philox stream 5; 0 (default) is the step without it."""
         from .train import D3PMTrainer
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         loss, _ = D3PMTrainer(self).forward_backward(text_list, proms_list, resps_list, seed=seed, timesteps=timesteps, dropout=dropout,
-                                                     utt0=utt0)
+                                                     utt0=utt0, cond_drop=cond_drop)
         return loss
 
     @torch.no_grad()

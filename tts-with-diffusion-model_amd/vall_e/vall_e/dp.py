@@ -26,7 +26,7 @@ def shard_bounds(n_items: int, world: int, rank: int) -> tuple[int, int]:
     return lo, lo + base + (1 if rank < extra else 0)
 
 
-_PER_UTTERANCE = ("n_frames", "known", "known_mask")
+_PER_UTTERANCE = ("n_frames", "known", "known_mask", "null_text_list", "null_proms_list")
 
 
 def _shard_kwargs(kw: dict, lo: int, hi: int) -> dict:

@@ -31,6 +31,7 @@ nn.Module is in train mode, and honouring the flag would change what every exist
 from __future__ import annotations
 
 import ctypes as C
+import math
 import numbers
 from typing import Optional, Sequence
 
@@ -172,6 +173,38 @@ def dropout_probs(dropout) -> tuple:
         if not 0.0 <= p < 1.0:
             raise ValueError(f"dropout: every probability must lie in [0, 1), got {dropout!r}")
     return p_layer, p_mlp
+
+
+COND_DROP_STREAM = 5      # Philox stream of the condition-drop decision (0..4 and 16..23 are taken: DESIGN.md section 7)
+
+
+def cond_drop_probs(cond_drop) -> tuple:
+    """The `cond_drop` argument of forward_backward -> (p_text, p_prompt): False / None / 0 -> (0, 0), a number p -> (p, p), a
+    (p_text, p_prompt) pair -> itself.  Every probability lies in [0, 1] (1 = always dropped)."""
+    if cond_drop is None or cond_drop is False:
+        return 0.0, 0.0
+    if isinstance(cond_drop, numbers.Real) and not isinstance(cond_drop, bool):
+        pair = (cond_drop, cond_drop)
+    elif isinstance(cond_drop, (tuple, list)) and len(cond_drop) == 2 and \
+            all(isinstance(p, numbers.Real) and not isinstance(p, bool) for p in cond_drop):
+        pair = tuple(cond_drop)
+    else:
+        raise ValueError(f"cond_drop: expected a probability or a (p_text, p_prompt) pair of numbers, got {cond_drop!r}")
+    p_text, p_prompt = float(pair[0]), float(pair[1])
+    for p in (p_text, p_prompt):
+        if not (math.isfinite(p) and 0.0 <= p <= 1.0):
+            raise ValueError(f"cond_drop: every probability must lie in [0, 1], got {cond_drop!r}")
+    return p_text, p_prompt
+
+
+def cond_drop_decision(seed: int, utt: int, p_text: float, p_prompt: float, device) -> tuple:
+    """(drop text?, drop prompt?) of global utterance `utt`: u = words 0 and 1 of Philox key (seed; group 0, row utt, t 0, stream 5)
+    drawn through d3pm_uniform; a condition is dropped <=> u < p (fp32 u in [0, 1) against the fp32 probability).  A function of
+    (seed, utt) alone, so data-parallel ranks agree with one process over the whole batch.  p = 0 draws nothing."""
+    if p_text == 0.0 and p_prompt == 0.0:
+        return False, False
+    u = _hip.uniform(_seed(seed), 0, int(utt), 1, 4, COND_DROP_STREAM, device)[0].cpu()
+    return bool(u[0] < torch.tensor(p_text, dtype=torch.float32)), bool(u[1] < torch.tensor(p_prompt, dtype=torch.float32))
 
 
 def dropout_site(which: int, layer: int, kind: int) -> int:
@@ -416,14 +449,19 @@ class D3PMTrainer:
 
     @torch.no_grad()
     def forward_backward(self, text_list: Sequence[torch.Tensor], proms_list: Sequence[torch.Tensor], resps_list: Sequence[torch.Tensor],
-                         *, seed: int = 0, timesteps: Optional[int] = None, dropout=False, utt0: int = 0):
+                         *, seed: int = 0, timesteps: Optional[int] = None, dropout=False, utt0: int = 0, cond_drop=0.0):
         """The loss of AR.forward (mean over the utterances) and its gradient, accumulated into `param.grad`.
+        cond_drop: p or (p_text, p_prompt) -- per utterance the text and / or the prompt is replaced by the empty one (no phonemes /
+        no prompt frames, zero padded like any other: the null condition of generate_audio(guidance=...)) with that probability;
+        a replaced condition still flows through its encoder, whose gradients accumulate as ever.  The decision is a function of
+        (seed, utt0 + b) (cond_drop_decision); 0 / False (default) is the step without it, bit for bit.
         dropout: False (default) = eval-mode arithmetic; True = the reference's train-mode condition encoders (p 0.1 in the
         encoder layers, 0.01 in the Mlp); a (p_layer, p_mlp) pair = those probabilities (dropout_probs; module docstring).
         utt0: global index of this call's first utterance -- utterance b keys its q_sample noise and its dropout masks with
         utt0 + b, so data-parallel ranks that pass their shard offset draw what one process over the whole batch would.
         Returns (loss fp32 scalar tensor, [(dcond_text, dcond_prompt)] per utterance)."""
         p_layer, p_mlp = dropout_probs(dropout)
+        p_text, p_prompt = cond_drop_probs(cond_drop)
         m, cfg = self.model, self.model.cfg
         smp = m.sampler()
         T = m.timesteps if timesteps is None else int(timesteps)
@@ -436,6 +474,11 @@ class D3PMTrainer:
                 fm = (x0[0] != 0).to(torch.uint8)
                 n_live = int(fm.sum().item())
                 targets = (x0[0] * fm.to(torch.int32)).contiguous()
+                drop_text, drop_prompt = cond_drop_decision(seed, utt0 + b, p_text, p_prompt, m.device)
+                if drop_text:
+                    text = text[:0]
+                if drop_prompt:
+                    prom = prom[:0]
                 text_p, prom_p = m._padded_inputs([text], [prom])
                 prom_p = prom_p[0].to(torch.int32)
                 if prom_p.shape[-1] < cfg.n_levels:
