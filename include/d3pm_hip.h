@@ -44,7 +44,8 @@ extern "C" {
  *    (and a trailing argument of d3pm_op_linear / d3pm_op_attention); the profiling hooks became a handle (d3pm_prof);
  *    the library keeps no mutable global state besides the thread-local error string.  The experiment-only entry points
  *    (d3pm_set_tuning's ablation arms, d3pm_op_final_sample, d3pm_op_linear_lnpro, d3pm_debug_gemm_clock) left the product:
- *    they live in libd3pm_hip_ab.so, include/d3pm_hip_ab.h (d3pm_debug_gemm_clock has since been removed there too). */
+ *    built, measured, not shipped; the experiment library that carried them afterwards (libd3pm_hip_ab.so) is retired, source up to
+ *    commit d54b189. */
 /* 5: + d3pm_op_attention_pair; new VALUES of existing tuning fields (row_panel bit 3, attn_query_groups 4, attn_cross_resident
  *    4 / 5); layouts unchanged */
 /* 6: LayerNorm folded into the projections (d3pm_fold_block, d3pm_weights.fold, d3pm_fold_bytes / d3pm_fold_build,

@@ -18,15 +18,15 @@ CLASSES = {"gemm": "gemm_mfma", "gemm_layernorm": "gemm_mfma_big", "gemm_mx": "g
 
 
 def fused_gemm(name):
-    """gemm_mfma_big<T, EPI, WM, WN, MODE, FUSE>: FUSE with a LayerNorm bit = the row-panel launches (projection + LayerNorms);
-    FUSE = 1 alone is the dual out-projection on ordinary tiles (a plain GEMM launch)."""
-    m = re.search(r"gemm_mfma_bigI\w+?Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EE", name)
+    """gemm_mfma_big<T, EPI, WM, WN, FUSE> (traces up to commit d54b189: <T, EPI, WM, WN, MODE, FUSE>): FUSE with a LayerNorm bit = the
+    row-panel launches (projection + LayerNorms); FUSE = 1 alone is the dual out-projection on ordinary tiles (a plain GEMM launch)."""
+    m = re.search(r"gemm_mfma_bigI\w+?Li(\d+)ELi(\d+)ELi(\d+)E(?:Li\d+E)?Li(\d+)EE", name)
     if m:
-        return (int(m.group(5)) & ~1) != 0
+        return (int(m.group(4)) & ~1) != 0
     m = re.search(r"gemm_mfma_big<([^>]*)>", name)
     if m:
         ints = re.findall(r"\b\d+\b", m.group(1))
-        return len(ints) >= 5 and int(ints[-1]) != 0
+        return len(ints) >= 4 and int(ints[-1]) != 0
     return False
 
 

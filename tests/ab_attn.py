@@ -1,7 +1,7 @@
 """Interleaved timing of the schedules of the MFMA self-attention kernel (not a test): python tests/ab_attn.py [arm ...]
-Runs on libd3pm_hip_ab.so (include/d3pm_hip_ab.h).  Arms: the shipped kernel (QG 2), QG 1 / 3, hand-placed fragment reads (164) and
-K / V by direct-to-LDS DMA (228); all give the same bits, which is asserted.  The builds with parts of the kernel removed (101 .. 160)
-and the occupancy probes (201 / 202) existed up to commit 4442690 and can be recovered from there; their figures are in profiles/."""
+Arms (d3pm_tuning.attn_query_groups): the shipped kernel (QG 2) and QG 1; both give the same bits, which is asserted.  QG 3, hand-placed
+fragment reads (164) and K / V by direct-to-LDS DMA (228) existed up to commit d54b189, the builds with parts of the kernel removed
+(101 .. 160) and the occupancy probes (201 / 202) up to commit 4442690; their figures are in profiles/."""
 import os
 import sys
 
@@ -9,11 +9,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "tts-with-diffusion-model_amd"), ROOT]
-import __graft_entry__ as g  # noqa: E402
-
-g.build_ab()                       # libd3pm_hip_ab.so: the experiment arms are not in the product
 from vall_e.vall_e import _hip  # noqa: E402
-_hip.use_ab_library()
 
 DEV = "cuda:0"
 B, T, H, d = 32, 768, 8, 512
@@ -35,7 +31,7 @@ def timeit(fn, reps=30):
     return e0.elapsed_time(e1) * 1e3 / reps
 
 
-ARMS = [(2, "shipped (QG 2)"), (228, "K/V tiles by direct-to-LDS DMA (same results)"), (164, "all fragment reads of a tile issued at its top (same results)"), (3, "QG 3 (48 queries per wave)"), (1, "QG 1")]
+ARMS = [(2, "shipped (QG 2)"), (1, "QG 1")]
 arms = [int(a) for a in sys.argv[1:]] or [a for a, _ in ARMS]
 names = dict(ARMS)
 for arm in arms:
@@ -44,14 +40,10 @@ for arm in arms:
 flops = 4.0 * B * H * T * T * 64
 ref = None
 for arm in arms:
-    if arm in (1, 2):
-        _hip.set_attn_arm(0); _hip.set_attn_query_groups(arm)
-    else:
-        _hip.set_attn_query_groups(0); _hip.set_attn_arm(arm)
+    _hip.set_attn_query_groups(arm)
     o = _hip.op_attention(q, k, v, H, 0.125, family=_hip.FAMILY_MFMA)      # every arm must give the shipped kernel's bits
     ref = o.clone() if ref is None else ref
     assert torch.equal(o, ref), f"arm {arm}: output differs from the first arm"
     t = timeit(lambda: _hip.op_attention(q, k, v, H, 0.125, family=_hip.FAMILY_MFMA))
     print("%-28s %7.1f us  %6.0f TFLOP/s-equivalent" % (names.get(arm, str(arm)), t, flops / t / 1e6), flush=True)
 _hip.set_attn_query_groups(0)
-_hip.set_attn_arm(0)

@@ -127,7 +127,7 @@ def test_gemm_schedules_are_bit_identical(built_lib):
 @pytest.mark.parametrize("M,N,K", [(9600, 1536, 512), (2496, 512, 2048), (192, 512, 256)])
 def test_gemm_big_tiles_match_one_tile_kernel(built_lib, dtype, epi, M, N, K):
     """The big-tile persistent schedules (192 x 256 / 96 x 512 tiles of eight waves, 192 x 128 tiles of four;
-    d3pm_mfma_gemm_big.hip; the experimental arms are compared the same way in tests/ab_bit_identity.py) against the
+    d3pm_mfma_gemm_big.hip) against the
     128 x 128 one-tile-per-workgroup kernel, bit for bit, for every epilogue: 300 / 300 tiles (a second tile for some
     workgroups, stores in flight into it), a long-K single round, and the smallest legal shape (K = 4 k-steps)."""
     from vall_e.vall_e import _hip

@@ -6,7 +6,6 @@ mkdir -p gpurun_out
 ok=1
 step() { [ $ok -eq 1 ] || return; echo "== $1"; shift; "$@"; rc=$?; echo "rc=$rc"; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then ok=0; fi; }
 t_tests() { timeout -k 10 900 python -m pytest tests -q -m gpu -p no:cacheprovider > gpurun_out/${tag}_gpu_tests.log 2>&1; r=$?; tail -4 gpurun_out/${tag}_gpu_tests.log; cp gpurun_out/parity_report.json gpurun_out/${tag}_parity_report.json; return $r; }
-t_ab() { timeout -k 10 600 python -m pytest tests/ab_bit_identity.py -q -m gpu -p no:cacheprovider > $OUT/${tag}_ab_tests.log 2>&1; r=$?; tail -3 $OUT/${tag}_ab_tests.log; return $r; }
 t_bench() { timeout -k 10 900 python bench.py --full --steps 10 --warmup 3 > $OUT/${tag}_bench.json 2> $OUT/${tag}_bench.err; r=$?; tail -3 $OUT/${tag}_bench.err; return $r; }
 t_b1() { timeout -k 10 300 python bench.py --full --batch 1 --steps 10 --warmup 2 --cpu-steps 0 --no-nar --no-fp8 --no-nq8 --no-vctk > $OUT/${tag}_bench_b1.json 2> $OUT/${tag}_bench_b1.err; }
 t_vctk() { timeout -k 10 400 python bench.py --full --config vctk --steps 5 --warmup 2 --cpu-steps 0 > $OUT/${tag}_bench_vctk_b32.json 2> $OUT/${tag}_bench_vctk.err; }
@@ -18,4 +17,4 @@ t_pmc() { cd /tmp && export TMPDIR=/tmp; r=0
     timeout -k 10 500 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/${tag}_pmc_$c -- python3 $REPO/bench.py --full --steps 1 --warmup 0 --cpu-steps 0 --no-latency --no-nar --no-nq8 --no-vctk --no-fp8 --profile-iters 3 > $OUT/${tag}_pmc_$c.log 2>&1 || r=$?
     find $OUT/${tag}_pmc_$c -name "*kernel_trace*" -delete
   done; cd $REPO; return $r; }
-for s in ${STAGES:-tests ab bench b1 vctk micro prof prof1 pmc}; do step $s t_$s; done
+for s in ${STAGES:-tests bench b1 vctk micro prof prof1 pmc}; do step $s t_$s; done

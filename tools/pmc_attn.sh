@@ -1,5 +1,5 @@
 # PMC counters of the self-attention kernel at the bench shape (separate passes): bash tools/pmc_attn.sh [arm]
-# arm: one of tests/ab_attn.py (2 shipped, 1, 3, 164, 228); that script refuses an arm that is not built any more
+# arm: one of tests/ab_attn.py (2 shipped, 1); that script refuses an arm that is not built any more
 : "${GRAFT_REPO_ROOT:=$(cd "$(dirname "$0")/.." && pwd)}"; cd /tmp; export TMPDIR=/tmp
 ARM=${1:-2}
 i=0

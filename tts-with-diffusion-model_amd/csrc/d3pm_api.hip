@@ -12,9 +12,6 @@
 #include <vector>
 
 #include "d3pm_kernels.h"
-#ifdef D3PM_ABLATIONS
-#include "../../include/d3pm_hip_ab.h"
-#endif
 
 namespace d3pm {
 
@@ -31,16 +28,6 @@ int q_sample_launch(const d3pm_shape*, int, const int32_t*, int32_t*, const uint
 int uniform_launch(uint64_t, int, uint32_t, int, int, int, float*, hipStream_t);
 int ce_loss_launch(int, const void*, int, const int32_t*, const uint8_t*, int, int, int, float*, hipStream_t);
 float host_h2f(uint16_t h);
-#ifdef D3PM_ABLATIONS
-bool final_sample_supported(int dtype, int n_classes, int d, const void* X, int ldx, const void* W);
-int final_sample(int dtype, const void* X, int ldx, const void* W, const void* bias, int d, const SampleArgs& a, hipStream_t s);
-// libd3pm_hip_ab.so only: the knobs of the experiments (include/d3pm_hip_ab.h).  Process-wide on purpose -- an A/B script toggles
-// them between interleaved arms; the product library does not contain this object.
-AbKnobs& ab_knobs() {
-  static AbKnobs k;
-  return k;
-}
-#endif
 
 }  // namespace d3pm
 
@@ -100,25 +87,6 @@ static int run_linear(const Ctx& cx, int dtype, LinearArgs a, uint32_t flags, hi
                a.M, a.N, a.K);
   return generic_linear(dtype, a, s);
 }
-#ifdef D3PM_ABLATIONS
-// D3PM_AB_LN_PROLOGUE: at one or two utterances the LayerNorm-fed projections normalise their operand rows themselves.
-// LayerNorm + projection in one launch of the latency GEMM (d3pm_mfma_gemm_lat.hip); a.X is the un-normalised stream
-static int run_ln_linear(const Ctx& cx, int dtype, LinearArgs a, const LnPrologue& ln, hipStream_t s) {
-  const size_t es = dtype_size(dtype);
-  a.tune = cx.tune;
-  ProfScope p(cx, D3PM_K_GEMM_LN, s, 2.0 * a.M * a.N * a.K,
-              es * (static_cast<double>(ln.period ? ln.period : a.M) * a.K + static_cast<double>(a.N) * a.K + static_cast<double>(a.M) * a.N));
-  return ln_prologue_linear(dtype, a, ln, s);
-}
-static bool ln_prologue_applies(const Ctx& cx, int dtype, LinearArgs a, const LnPrologue& ln) {
-  a.tune = cx.tune;
-  return ln_prologue_linear_applies(dtype, a, ln);
-}
-#else
-// the LayerNorm-prologue form of the latency GEMM was measured slower and lives in libd3pm_hip_ab.so only (include/d3pm_hip_ab.h)
-static int run_ln_linear(const Ctx&, int, const LinearArgs&, const LnPrologue&, hipStream_t) { return D3PM_E_SHAPE; }
-static bool ln_prologue_applies(const Ctx&, int, const LinearArgs&, const LnPrologue&) { return false; }
-#endif
 // projection onto the residual stream + the LayerNorm(s) of the new rows, one launch (d3pm_mfma_gemm_big.hip)
 static int run_row_panel(const Ctx& cx, int dtype, const LinearArgs& a, const RowPanelFuse& f, hipStream_t s) {
   const size_t es = dtype_size(dtype);
@@ -530,19 +498,9 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
   const int panel = (!(flags & D3PM_FLAG_FORCE_GENERIC) && d == 512 && rp_fills && (dt == D3PM_F16 || dt == D3PM_BF16))
                         ? (tune_of(sh.tuning).row_panel & (use8 ? 3 : 7)) : 0;      // fp8: fc2 is a block-scaled GEMM of its own
   bool norm1_done = embed_fused;   // norm1(x) of this block is already in ws.h (the embedding launch, or the previous block's fc2)
-  // the opposite regime (one or two utterances, latency GEMM): LayerNorm runs as the prologue of the projection it feeds
-#ifdef D3PM_ABLATIONS
-  const bool lnpro_on = ab_knobs().ln_prologue != 0;
-#else
-  const bool lnpro_on = false;
-#endif
-  const bool lnpro = lnpro_on && !use8 && !(flags & D3PM_FLAG_FORCE_GENERIC) && d == 512 && (dt == D3PM_F16 || dt == D3PM_BF16);
   // a LayerNorm-fed projection g (g.X = the LayerNorm output): LayerNorm launch + projection, unless an earlier launch has written
-  // the LayerNorm rows already (ablation build only: or the latency GEMM normalises the rows of x itself)
-  auto ln_linear = [&](bool ln_done, const LayerNormArgs& ln, const LnPrologue& lp, const LinearArgs& g) -> int {
-    LinearArgs gx = g;
-    gx.X = ws.x;
-    if (!ln_done && lnpro && ln_prologue_applies(cx, dt, gx, lp)) return run_ln_linear(cx, dt, gx, lp, s);
+  // the LayerNorm rows already
+  auto ln_linear = [&](bool ln_done, const LayerNormArgs& ln, const LinearArgs& g) -> int {
     if (!ln_done) D3PM_TRY(run_layernorm(cx, dt, ln, flags, s));
     return run_linear(cx, dt, g, flags, s);
   };
@@ -559,9 +517,7 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
       D3PM_TRY(mx_gemm(x8, d, sx8, f8[l].attn_in_w8, f8[l].attn_in_scale, b.attn_in_b, ws.qkv, 3 * d, nullptr, nullptr, 1, nullptr, nullptr,
                        n, 3 * d, d, ACT_NONE));
     } else {
-      LnPrologue lp;
-      lp.w = ln.w; lp.b = ln.b; lp.eps = ln.eps;
-      D3PM_TRY(ln_linear(norm1_done, ln, lp, projection(ws.h, b.attn_in_w, b.attn_in_b, ws.qkv, n, 3 * d, d)));
+      D3PM_TRY(ln_linear(norm1_done, ln, projection(ws.h, b.attn_in_w, b.attn_in_b, ws.qkv, n, 3 * d, d)));
     }
     norm1_done = false;
     D3PM_TRY(run_attention(cx, dt, with_frame_keys(self_attention(ws.qkv, ws.att, batch, T, H, hd, es), q.keys), flags, s));
@@ -591,9 +547,7 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
     } else if (ws.h2 == at(ws.h, static_cast<size_t>(n) * d, es)) {
       // both query projections share cross_attn's q rows: LN2|LN22 outputs and q_text|q_prompt are adjacent in
       // the workspace, so the pair is ONE [2n, d] x [d, d] GEMM (twice the workgroups of either alone)
-      LnPrologue lp;
-      lp.w = ln.w; lp.b = ln.b; lp.w2 = ln.w2; lp.b2 = ln.b2; lp.eps = ln.eps; lp.period = n;
-      D3PM_TRY(ln_linear(norm2_fused, ln, lp, projection(ws.h, b.cross_in_w, b.cross_in_b, q_text, 2 * n, d, d)));
+      D3PM_TRY(ln_linear(norm2_fused, ln, projection(ws.h, b.cross_in_w, b.cross_in_b, q_text, 2 * n, d, d)));
     } else {
       if (!norm2_fused) D3PM_TRY(run_layernorm(cx, dt, ln, flags, s));
       D3PM_TRY(run_linear(cx, dt, projection(ws.h, b.cross_in_w, b.cross_in_b, q_text, n, d, d), flags, s));
@@ -635,9 +589,7 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
       D3PM_TRY(mx_gemm(x8, d, sx8, f8[l].fc1_w8, f8[l].fc1_scale, b.fc1_b, ws.mlp, 4 * d, nullptr, nullptr, 1, fc2_mx ? h8 : nullptr,
                        fc2_mx ? sh8 : nullptr, n, 4 * d, d, ACT_GELU));
     } else {
-      LnPrologue lp;
-      lp.w = ln.w; lp.b = ln.b; lp.film = ln.film; lp.eps = ln.eps;
-      D3PM_TRY(ln_linear(norm3_fused, ln, lp, projection(ws.h, b.fc1_w, b.fc1_b, ws.mlp, n, 4 * d, d, ACT_GELU)));
+      D3PM_TRY(ln_linear(norm3_fused, ln, projection(ws.h, b.fc1_w, b.fc1_b, ws.mlp, n, 4 * d, d, ACT_GELU)));
     }
     g = with_row_mask(with_residual(projection(ws.mlp, b.fc2_w, b.fc2_b, ws.x, n, d, 4 * d), ws.x), frame_mask, mask_period);
     rp = RowPanelFuse();
@@ -653,16 +605,6 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
     }
   }
   return D3PM_OK;
-}
-
-// the fused final + sampler kernel takes over wherever the final projection would have run on the MFMA family
-static bool fused_final_sample_applies(const d3pm_shape& sh, const d3pm_weights& w, const Workspace& ws, uint32_t flags) {
-#ifdef D3PM_ABLATIONS
-  return ab_knobs().fused_final_sample && !(flags & D3PM_FLAG_FORCE_GENERIC) && sh.d_model >= 64 && levels(sh) == 1 &&
-         final_sample_supported(sh.dtype, sh.n_classes, sh.d_model, ws.x, sh.d_model, w.final_w);
-#else
-  return false;      // built, bit-identical, 253 us vs 30 + 87 us: lives in libd3pm_hip_ab.so only (include/d3pm_hip_ab.h)
-#endif
 }
 
 static int final_logits(const d3pm_shape& sh, const d3pm_weights& w, int batch, const Workspace& ws, void* logits,
@@ -1093,14 +1035,6 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     a.known = cm.known;
     if (sm) { a.temperature = sm->temperature; a.top_k = sm->top_k; a.top_p = sm->top_p; }
     if (guide) { a.guided = true; a.guidance = guide->weight; }
-#ifdef D3PM_ABLATIONS
-    if (!guide && !cm.known && !a.filtered() && !a.nucleus() && fused_final_sample_applies(*sh, *w, ws, flags)) {
-      // final projection + posterior + draw in one kernel: the logits stay on chip (d3pm_final_sample.hip)
-      ProfScope p(cx, D3PM_K_SAMPLE, s, 2.0 * rows * sh->n_classes * sh->d_model,
-                  dtype_size(sh->dtype) * (static_cast<double>(rows) * sh->d_model + static_cast<double>(sh->n_classes) * sh->d_model) + 8.0 * rows);
-      D3PM_TRY(final_sample(sh->dtype, ws.x, sh->d_model, w->final_w, w->final_b, sh->d_model, a, s));
-    } else
-#endif
     {
       D3PM_TRY(final_logits(*sh, *w, eval_batch, ws, ws.logits, logits_ld(*sh), flags, s));
       ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0,
@@ -1592,22 +1526,6 @@ int d3pm_op_layernorm(int dtype, const void* X, void* Y, const void* w, const vo
   return run_layernorm(cx, dtype, ln, 0, static_cast<hipStream_t>(stream));
 }
 
-#ifdef D3PM_ABLATIONS
-int d3pm_op_linear_lnpro(int dtype, const void* X, const void* W, const void* bias, void* Y, int M, int N, int act, const void* ln_w,
-                         const void* ln_b, const void* ln2_w, const void* ln2_b, const void* film, float eps, void* stream) {
-  D3PM_REQUIRE(X && W && Y && ln_w && ln_b && M > 0 && N > 0, D3PM_E_ARG, "d3pm_op_linear_lnpro: bad arguments");
-  LinearArgs g;
-  g.X = X; g.ldx = 512; g.W = W; g.bias = bias; g.Y = Y; g.ldy = N; g.M = M; g.N = N; g.K = 512; g.act = act;
-  LnPrologue lp;
-  lp.w = ln_w; lp.b = ln_b; lp.w2 = ln2_w; lp.b2 = ln2_b; lp.film = film; lp.eps = eps; lp.period = ln2_w ? M / 2 : 0;
-  D3PM_REQUIRE(panel64_ln_supported(dtype, g, lp), D3PM_E_SHAPE,
-               "d3pm_op_linear_lnpro: needs a 16-bit dtype, 16-byte aligned operands, N a multiple of 8, act 0 / 1 and, with a second "
-               "LayerNorm, M = 2 x a multiple of 64 rows and no FiLM");
-  return ln_prologue_linear(dtype, g, lp, static_cast<hipStream_t>(stream));
-}
-
-#endif
-
 int d3pm_op_linear_rowpanel(int dtype, const void* X, const void* X2, int ldx, const void* W, const void* bias, void* Y, const void* R1,
                             const uint8_t* row_mask, int mask_period, int M, int K, const void* ln_w, const void* ln_b, void* ln_y,
                             const void* ln2_w, const void* ln2_b, void* ln2_y, const void* film, float eps, void* ln_sx, void* ln2_sx,
@@ -1625,25 +1543,6 @@ int d3pm_op_linear_rowpanel(int dtype, const void* X, const void* X2, int ldx, c
   return row_panel_linear(dtype, g, f, static_cast<hipStream_t>(stream));
 }
 
-#ifdef D3PM_ABLATIONS
-int d3pm_op_final_sample(const d3pm_shape* sh, const d3pm_weights* w, int batch, const void* hidden, const int32_t* x_t,
-                         int32_t* x_next, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags,
-                         void* stream) {
-  D3PM_TRY(check_shape(sh, batch));
-  D3PM_REQUIRE(w && w->final_w && hidden && x_t && x_next && sched && sched->d && sched->c && sched->dbar && sched->cbar, D3PM_E_ARG,
-               "d3pm_op_final_sample: null pointer");
-  D3PM_REQUIRE(t >= 0 && t < sched->timesteps, D3PM_E_ARG, "t=%d outside the schedule", t);
-  D3PM_REQUIRE(final_sample_supported(sh->dtype, sh->n_classes, sh->d_model, hidden, sh->d_model, w->final_w), D3PM_E_SHAPE,
-               "d3pm_op_final_sample: needs a 16-bit model, 1025 classes and d_model a multiple of 32 (<= 1024)");
-  SampleArgs a;
-  a.x_t = x_t; a.x_next = x_next; a.rows = batch * sh->canvas; a.n_classes = sh->n_classes; a.mask_id = sh->mask_id;
-  a.canvas = sh->canvas; a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas);
-  a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0; a.pc = make_posterior_consts(sched, t);
-  return final_sample(sh->dtype, hidden, sh->d_model, w->final_w, w->final_b, sh->d_model, a, static_cast<hipStream_t>(stream));
-}
-
-#endif
-
 int d3pm_op_cond_embed(int dtype, int which, const int32_t* tokens, int n_levels, const void* tables, const void* pe, void* y, int rows,
                        int s_prompt, int d, int n_classes, void* stream) {
   D3PM_REQUIRE(tokens && tables && pe && y && rows > 0 && d > 0 && n_classes > 0, D3PM_E_ARG, "d3pm_op_cond_embed: bad arguments");
@@ -1656,24 +1555,6 @@ int d3pm_op_cond_embed(int dtype, int which, const int32_t* tokens, int n_levels
 void d3pm_tuning_default(d3pm_tuning* t) {
   if (t) *t = tune_of(nullptr);
 }
-
-#ifdef D3PM_ABLATIONS
-int d3pm_ab_set(int knob, int value) {
-  AbKnobs& k = ab_knobs();
-  static const int big_modes[] = {0, 1, 9, 513, 2049};
-  if (knob == D3PM_AB_GEMM_BIG_MODE) {
-    for (int m : big_modes)
-      if (m == value) { k.big_mode = value; return D3PM_OK; }
-  }
-  if (knob == D3PM_AB_ATTN_ARM && (value == 0 || value == 3 || value == 164 || value == 228 || value == 300 || value == 301)) { k.attn_arm = value; return D3PM_OK; }
-  if (knob == D3PM_AB_GEMM_RING && (value == 0 || value == 1)) { k.ring = value; return D3PM_OK; }
-  if (knob == D3PM_AB_GELU_TABLE && (value == 0 || value == 1)) { k.gelu_table = value; return D3PM_OK; }
-  if (knob == D3PM_AB_LN_PROLOGUE && (value == 0 || value == 1)) { k.ln_prologue = value; return D3PM_OK; }
-  if (knob == D3PM_AB_FUSED_FINAL_SAMPLE && (value == 0 || value == 1)) { k.fused_final_sample = value; return D3PM_OK; }
-  set_error("d3pm_ab_set: unknown knob %d / value %d", knob, value);
-  return D3PM_E_ARG;
-}
-#endif
 
 int d3pm_prof_create(int kclass, int max_events, d3pm_prof** out) {
   D3PM_REQUIRE(out && kclass >= 0 && kclass <= D3PM_K_COUNT && max_events > 0, D3PM_E_ARG, "d3pm_prof_create: bad arguments");

@@ -19,12 +19,6 @@ inline const d3pm_tuning& tune_of(const d3pm_tuning* t) {
   return t ? *t : kDefault;
 }
 
-#ifdef D3PM_ABLATIONS
-// libd3pm_hip_ab.so only (include/d3pm_hip_ab.h): process-wide knobs of the experiments that did not ship
-struct AbKnobs { int big_mode = 1, attn_arm = 0, ring = 0, gelu_table = 0, ln_prologue = 0, fused_final_sample = 0; };
-AbKnobs& ab_knobs();
-#endif
-
 // Y[M][N] = epilogue(X[M][K] . W[N][K]^T + bias)      (torch.nn.functional.linear layout)
 // epilogue, with rn() = round to the storage dtype exactly where the eager reference rounds:
 //   v = rn(acc + bias); if act: v = rn(act(v))   (exact-erf GELU, ReLU or SiLU);
@@ -115,13 +109,6 @@ struct RowPanelFuse {
   // fp8 fast path: with sx (and sx2) set, lny (lny2) receive the LayerNorm rows in the block-scaled fp8 format of d3pm_mx.hip --
   // codes [M][512] bytes -- and sx (sx2) their scales [M][4][4]
   void* sx = nullptr; void* sx2 = nullptr;
-};
-
-// LayerNorm applied to the operand rows inside the latency GEMM (d3pm_mfma_gemm_lat.hip): X is then the residual stream.
-// period > 0: M = 2 * period rows, rows >= period re-read source row m - period under the second LayerNorm (w2, b2).
-struct LnPrologue {
-  const void* w = nullptr; const void* b = nullptr; const void* w2 = nullptr; const void* b2 = nullptr;
-  const void* film = nullptr; float eps = 1e-6f; int period = 0;
 };
 
 struct EmbedArgs {
@@ -261,11 +248,6 @@ int mfma_attention32_cross(int dtype, const AttnArgs& a, int n_qsplit, hipStream
 // d3pm_mfma_attn_lat.hip: one or two utterances -- the key tiles of a 32-query group split over the four waves of a workgroup
 bool mfma_attention_split_supported(int dtype, const AttnArgs& a);
 int mfma_attention_split(int dtype, const AttnArgs& a, hipStream_t s);
-#ifdef D3PM_ABLATIONS
-bool panel64_ln_supported(int dtype, const LinearArgs& a, const LnPrologue& ln);
-bool ln_prologue_linear_applies(int dtype, const LinearArgs& a, const LnPrologue& ln);   // would mfma_linear pick the latency GEMM?
-int ln_prologue_linear(int dtype, const LinearArgs& a, const LnPrologue& ln, hipStream_t s);
-#endif
 // latency GEMM, two products through one weight panel: Y = rn(rn(R1 + rn(X W^T + b)) + rn(X2 W^T + b)) (d3pm_mfma_gemm_lat.hip)
 bool panel64_dual_supported(int dtype, const LinearArgs& a, const void* X2);
 int panel64_dual(int dtype, const LinearArgs& a, const void* X2, hipStream_t s);

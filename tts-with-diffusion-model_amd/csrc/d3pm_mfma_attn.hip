@@ -49,10 +49,6 @@ template <> __device__ __forceinline__ floatx4 mma<bf16>(uint4 a, uint4 b, float
 __device__ __forceinline__ int k_off(int row, int chunk) { return row * ROWB + ((chunk ^ ((row >> 1) & 7)) << 4); }
 __device__ __forceinline__ int v_off(int row, int chunk) { return row * ROWB + ((chunk ^ (((row >> 1) & 3) << 1)) << 4); }
 
-template <class F> __device__ __forceinline__ void static_for4(F&& f) {
-  f(std::integral_constant<int, 0>{}); f(std::integral_constant<int, 1>{}); f(std::integral_constant<int, 2>{}); f(std::integral_constant<int, 3>{});
-}
-
 constexpr float kDefer = 8.0f;   // log2 of the largest un-normalised probability tolerated before m_ref is raised
 
 // max over the four lanes l, l^16, l^32, l^48 on the VALU (no LDS round trip): after v_permlane16_swap of two copies
@@ -94,37 +90,7 @@ __device__ __forceinline__ void store_rows16(T* row_base /* O + row * ldo + h * 
   }
 }
 
-// ABL != 0 is instantiated in the A/B library only (-DD3PM_ABLATIONS; same results; tests/ab_attn.py): bits 6 and 7.
-// fragment reads whose completion is waited for by hand (ABL bit 6: every K and V fragment of a tile issued at the top of
-// the tile, counted lgkmcnt before each consumer) -- hipcc sinks a plain LDS load to the instruction before its first use
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void lds_read_b128(u32x4& dst, uint32_t addr, int off) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off));
-}
-__device__ __forceinline__ void lds_read_tr_b64(u32x2& dst, uint32_t addr, int off) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off));
-}
-template <int N> __device__ __forceinline__ void lds_wait2(u32x4& a, u32x4& b) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N)); }
-template <int N> __device__ __forceinline__ void lds_wait_v(u32x2 (&v)[2][4][2]) {
-  asm volatile("s_waitcnt lgkmcnt(%16)"
-               : "+v"(v[0][0][0]), "+v"(v[0][0][1]), "+v"(v[0][1][0]), "+v"(v[0][1][1]), "+v"(v[0][2][0]), "+v"(v[0][2][1]), "+v"(v[0][3][0]),
-                 "+v"(v[0][3][1]), "+v"(v[1][0][0]), "+v"(v[1][0][1]), "+v"(v[1][1][0]), "+v"(v[1][1][1]), "+v"(v[1][2][0]), "+v"(v[1][2][1]),
-                 "+v"(v[1][3][0]), "+v"(v[1][3][1])
-               : "n"(N));
-}
-
-// one 1-KiB direct-to-LDS piece (8 rows x 128 B: lane -> row lane >> 3, 16-byte chunk lane & 7) issued from asm: invisible to
-// hipcc's wait counters (a compiler-visible DMA is drained before the next ds_read), so the wait is placed by hand
-__device__ __forceinline__ void dma_piece(const void* gsrc, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds_dst)
-               : "memory");
-}
-
-template <typename T, int QG, bool PAIR, int ABL = 0>   // QG groups of 16 queries per wave (K/V fragments are read once per wave and reused)
+template <typename T, int QG, bool PAIR>   // QG groups of 16 queries per wave (K/V fragments are read once per wave and reused)
 __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* __restrict__ Q, int ldq, const T* __restrict__ Kp,
                                                       const T* __restrict__ Vp, int ldkv, T* __restrict__ O, int ldo,
                                                       int Tq, int S, float scale, int H, int n_qblocks,
@@ -216,31 +182,8 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
   };
 
   const int n_tiles = (S + BKV - 1) / BKV;
-  // ABL bit 7 (same results): K / V tiles go global -> LDS directly, four 1-KiB pieces per wave and tile (pieces wave, wave + 4
-  // = K rows, wave + 8, wave + 12 = V rows), issued at the top of the previous tile; a lane fetches the 16-byte chunk that the
-  // swizzled image wants at its position
-  constexpr bool kDma = (ABL & 128) != 0;
-  const uint32_t lds0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem));
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  auto dma_tile = [&](int tile, int buf) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int which = i >> 1, j = wave_u + 4 * (i & 1), row = 8 * j + (lane >> 3), cpos = lane & 7;
-      const int logical = which == 0 ? (cpos ^ ((row >> 1) & 7)) : (cpos ^ (((row >> 1) & 3) << 1));
-      int key = tile * BKV + row;
-      key = key < S ? key : S - 1;
-      const T* src = (which == 0 ? Kb : Vb) + static_cast<size_t>(key) * ldkv + logical * 8;
-      dma_piece(src, lds0 + buf * 2 * TILE + which * TILE + j * 1024);
-    }
-  };
-  Staged st;
-  if constexpr (kDma) {
-    dma_tile(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
-    st = load_tile(0);
-    store_tile(smem, st);
-  }
+  Staged st = load_tile(0);
+  store_tile(smem, st);
   __syncthreads();
 
   float m_ref[QG];
@@ -274,11 +217,7 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
     const char* kb = smem + BUF * 2 * TILE;
     const char* vb = kb + TILE;
     const bool more = tile + 1 < n_tiles;
-    if constexpr (kDma) {
-      if (more) dma_tile(tile + 1, BUF ^ 1);           // BUF ^ 1 was last read in the previous tile, behind its barrier
-    } else {
-      if (more) st = load_tile(tile + 1);
-    }
+    if (more) st = load_tile(tile + 1);
 
     // ---- S^T tile: 64 keys x (16 QG) queries per wave; each K fragment feeds QG MFMAs ----
     // The accumulator starts at -m_ref (one register quad per query group, shared by the four key tiles as the C
@@ -288,39 +227,10 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        if constexpr ((ABL & 64) == 0) {
         uint4 kf = *reinterpret_cast<const uint4*>(kb + ok[ks] + kt * 16 * ROWB);
 #pragma unroll
         for (int qg = 0; qg < QG; ++qg) s[qg][kt] = mma<T>(kf, qf[qg][ks], ks == 0 ? negm[qg] : s[qg][kt]);
-        }
       }
-    u32x2 vfr[2][4][2];
-    if constexpr ((ABL & 64) != 0) {
-      const uint32_t lbase = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem)) + BUF * 2 * TILE;
-      u32x4 kfr[4][2];
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) lds_read_b128(kfr[kt][ks], lbase + ok[ks], kt * 16 * ROWB);
-      // the LDS counter holds 15 operations: the 16 V reads go out four at a time behind each key block's MFMAs, so that
-      // they return under the softmax; counts = reads younger than the fragments a step consumes
-      static_for4([&](auto KT) {
-        constexpr int kt = decltype(KT)::value;
-        constexpr int kWaitK[4] = {6, 8, 10, 11};
-        lds_wait2<kWaitK[kt]>(kfr[kt][0], kfr[kt][1]);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-          for (int qg = 0; qg < QG; ++qg)
-            s[qg][kt] = mma<T>(__builtin_bit_cast(uint4, kfr[kt][ks]), qf[qg][ks], ks == 0 ? negm[qg] : s[qg][kt]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          constexpr int idx0 = kt * 4;
-          const int idx = idx0 + j, kb2 = idx >> 3, dt = (idx >> 1) & 3, half = idx & 1;   // constants after unrolling
-          lds_read_tr_b64(vfr[kb2][dt][half], lbase + TILE + ov[dt], (2 * kb2 + half) * 16 * ROWB);
-        }
-      });
-    }
     // lane holds scores (log2 domain, minus m_ref) of its query for keys tile*64 + kt*16 + 4g + r
     const bool ragged = (tile == n_tiles - 1) && (S & (BKV - 1));   // wave-uniform: only the last tile can be partial
     uint4 pf[QG][2];
@@ -375,22 +285,16 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
     }
 
     // ---- O^T += V^T . P^T ; each transposed V fragment feeds QG MFMAs ----
-    if constexpr ((ABL & 64) != 0) lds_wait_v<0>(vfr);
 #pragma unroll
     for (int kb2 = 0; kb2 < 2; ++kb2)
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         // 16-lane group g, lane qi: address of row (key0 + qi>>2), columns 16dt + 4(qi&3) .. +3
-        uint4 vf;
-        if constexpr ((ABL & 64) != 0) {
-          vf = uint4{vfr[kb2][dt][0].x, vfr[kb2][dt][0].y, vfr[kb2][dt][1].x, vfr[kb2][dt][1].y};
-        } else {
-          typedef short4v __attribute__((address_space(3))) * lds_ptr;
-          short4v va = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(vb + ov[dt] + (2 * kb2) * 16 * ROWB));
-          short4v vc = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(vb + ov[dt] + (2 * kb2 + 1) * 16 * ROWB));
-          uint2 lo = __builtin_bit_cast(uint2, va), hi = __builtin_bit_cast(uint2, vc);
-          vf = uint4{lo.x, lo.y, hi.x, hi.y};
-        }
+        typedef short4v __attribute__((address_space(3))) * lds_ptr;
+        short4v va = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(vb + ov[dt] + (2 * kb2) * 16 * ROWB));
+        short4v vc = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(vb + ov[dt] + (2 * kb2 + 1) * 16 * ROWB));
+        uint2 lo = __builtin_bit_cast(uint2, va), hi = __builtin_bit_cast(uint2, vc);
+        const uint4 vf = uint4{lo.x, lo.y, hi.x, hi.y};
 #pragma unroll
         for (int qg = 0; qg < QG; ++qg) acc_o[qg][dt] = mma<T>(vf, pf[qg][kb2], acc_o[qg][dt]);
       }
@@ -400,11 +304,7 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
     for (int kb2 = 0; kb2 < 2; ++kb2)
 #pragma unroll
       for (int qg = 0; qg < QG; ++qg) acc_l[qg] = mma<T>(ones, pf[qg][kb2], acc_l[qg]);
-    if constexpr (kDma) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the next tile have landed
-    } else {
-      if (more) store_tile(smem + (BUF ^ 1) * 2 * TILE, st);
-    }
+    if (more) store_tile(smem + (BUF ^ 1) * 2 * TILE, st);
     __syncthreads();
   };
   for (int tile = 0; tile < n_tiles; tile += 2) {
@@ -431,16 +331,12 @@ __global__ __launch_bounds__(256, QG == 1 ? 4 : 2) void attn_mfma_hd64(const T* 
 typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-// PIPE: software-pipelined walk -- the S^T = K . Q^T products of tile i + 1 are issued BEFORE the softmax of tile i (a second
-// set of score registers), so the matrix pipe works under the exponentials of the same wave instead of waiting for them: with
-// every K / V tile resident a wave's time per tile is its own dependency chain (LDS reads -> 16 MFMAs -> max -> 32 v_exp ->
-// V reads -> 20 MFMAs), which two waves per SIMD do not cover.  Exactness: the prefetched product starts from the -m_ref of the
-// moment; when the softmax of tile i then moves m_ref (always on the first tile, otherwise only if a score exceeds it by 2^8)
-// the product of tile i + 1 is issued again from the new -m_ref, so every number is the one the plain walk computes.
+// A software-pipelined walk (the products of tile i + 1 issued before the softmax of tile i) was built, measured and not shipped
+// (source up to commit d54b189).
 // MASK: key_len1 / key_len2 (device int32 [B], either may be null) = the valid keys of utterance b among the S1 / S2 padded ones.
 // S1 / S2 stay the row strides of the batches; behind them the kernel is the unmasked one on the valid counts (only their tiles
 // are fetched, the ragged last tile is masked as ever).
-template <typename T, bool PIPE = false, bool MASK = false>
+template <typename T, bool MASK = false>
 __global__ __launch_bounds__(512, 2) void attn_cross_hd64(const T* __restrict__ Q1, const T* __restrict__ K1, const T* __restrict__ V1,
                                                           T* __restrict__ O1, int S1, const T* __restrict__ Q2,
                                                           const T* __restrict__ K2, const T* __restrict__ V2, T* __restrict__ O2,
@@ -500,11 +396,10 @@ __global__ __launch_bounds__(512, 2) void attn_cross_hd64(const T* __restrict__ 
       for (int ks = 0; ks < 2; ++ks) qraw[qg][ks] = *reinterpret_cast<const uint4*>(qp + ks * 32 + g * 8);
     }
   };
-  if constexpr (!PIPE) fetch_q(qs, 0);
+  fetch_q(qs, 0);
   for (int qb = qs; qb < n_qblocks; qb += n_qsplit) {
   const int q0 = (qb * 8 + wave) * (16 * QG);
   for (int prob = 0; prob < 2; ++prob) {
-    if constexpr (PIPE) fetch_q(qb, prob);       // the pipelined walk spends its registers on the second score set: no query prefetch
     T* O = prob == 0 ? O1 : O2;
     const int S = prob == 0 ? S1 : S2, t0 = prob == 0 ? 0 : 1, nt = prob == 0 ? 1 : nt2;
     uint4 qf[QG][2];
@@ -519,10 +414,8 @@ __global__ __launch_bounds__(512, 2) void attn_cross_hd64(const T* __restrict__ 
                            pack2<T>(static_cast<float>(e[4]) * qscale, static_cast<float>(e[5]) * qscale),
                            pack2<T>(static_cast<float>(e[6]) * qscale, static_cast<float>(e[7]) * qscale)};
       }
-    if constexpr (!PIPE) {
-      if (prob == 0) fetch_q(qb, 1);
-      else if (qb + n_qsplit < n_qblocks) fetch_q(qb + n_qsplit, 0);
-    }
+    if (prob == 0) fetch_q(qb, 1);
+    else if (qb + n_qsplit < n_qblocks) fetch_q(qb + n_qsplit, 0);
     if (!landed) {                                           // one wait for the whole workgroup's K / V image
       __syncthreads();                                       // (drains this wave's DMA pieces, then the barrier)
       landed = true;
@@ -549,11 +442,10 @@ __global__ __launch_bounds__(512, 2) void attn_cross_hd64(const T* __restrict__ 
           for (int qg = 0; qg < QG; ++qg) s[qg][kt] = mma<T>(kf, qf[qg][ks], ks == 0 ? negm[qg] : s[qg][kt]);
         }
     };
-    // softmax of one tile's scores -> the 16-bit probabilities as PV operands; returns whether m_ref moved (wave-uniform)
-    auto softmax_tile = [&](int tile, floatx4 (&s)[QG][4], uint4 (&pf)[QG][2]) __attribute__((always_inline)) -> bool {
+    // softmax of one tile's scores -> the 16-bit probabilities as PV operands
+    auto softmax_tile = [&](int tile, floatx4 (&s)[QG][4], uint4 (&pf)[QG][2]) __attribute__((always_inline)) {
       const bool ragged = (tile == nt - 1) && (S & (BKV - 1));
       const int key_base = tile * BKV + 4 * g;
-      bool moved = false;
 #pragma unroll
       for (int qg = 0; qg < QG; ++qg) {
         if (ragged) {
@@ -570,7 +462,6 @@ __global__ __launch_bounds__(512, 2) void attn_cross_hd64(const T* __restrict__ 
           mx = fmaxf(fmaxf(mx, s[qg][kt][2]), s[qg][kt][3]);
         }
         if (tile == 0 || __any(mx > kDefer)) {
-          moved = true;
           mx = max_over_query_lanes(mx);
           const float delta = tile == 0 ? mx : fmaxf(mx, 0.f);
 #pragma unroll
@@ -599,7 +490,6 @@ __global__ __launch_bounds__(512, 2) void attn_cross_hd64(const T* __restrict__ 
           pf[qg][kb2] = uint4{pack2<T>(pa[0], pa[1]), pack2<T>(pa[2], pa[3]), pack2<T>(pb[0], pb[1]), pack2<T>(pb[2], pb[3])};
         }
       }
-      return moved;
     };
     auto pv_tile = [&](int tile, const uint4 (&pf)[QG][2]) __attribute__((always_inline)) {
       const char* vb = smem + (t0 + tile) * 2 * TILE + TILE;
@@ -622,30 +512,12 @@ __global__ __launch_bounds__(512, 2) void attn_cross_hd64(const T* __restrict__ 
 #pragma unroll
         for (int qg = 0; qg < QG; ++qg) acc_l[qg] = mma<T>(ones, pf[qg][kb2], acc_l[qg]);
     };
-    if constexpr (PIPE) {
-      floatx4 sa[QG][4], sb[QG][4];
+    for (int tile = 0; tile < nt; ++tile) {
+      floatx4 s[QG][4];
       uint4 pf[QG][2];
-      auto walk = [&](int tile, floatx4 (&cur)[QG][4], floatx4 (&nxt)[QG][4]) __attribute__((always_inline)) {
-        const bool more = tile + 1 < nt;
-        if (more && tile > 0) qk_tile(tile + 1, nxt);       // ahead of the exponentials of `tile` (the first tile always moves m_ref)
-        const bool moved = softmax_tile(tile, cur, pf);
-        if (more && (tile == 0 || moved)) qk_tile(tile + 1, nxt);       // m_ref moved: the product (again) from the new -m_ref
-        pv_tile(tile, pf);
-      };
-      qk_tile(0, sa);
-      for (int tile = 0; tile < nt; tile += 2) {           // two tiles per trip: the score sets trade places without copies
-        walk(tile, sa, sb);
-        if (tile + 1 >= nt) break;
-        walk(tile + 1, sb, sa);
-      }
-    } else {
-      for (int tile = 0; tile < nt; ++tile) {
-        floatx4 s[QG][4];
-        uint4 pf[QG][2];
-        qk_tile(tile, s);
-        softmax_tile(tile, s, pf);
-        pv_tile(tile, pf);
-      }
+      qk_tile(tile, s);
+      softmax_tile(tile, s, pf);
+      pv_tile(tile, pf);
     }
 #pragma unroll
     for (int qg = 0; qg < QG; ++qg) {
@@ -682,11 +554,7 @@ bool mfma_attention_supported(int dtype, const AttnArgs& a) {
 int mfma_attention(int dtype, const AttnArgs& a, hipStream_t s) {
   const d3pm_tuning& tn = tune_of(a.tune);
   const int g_attn_cross_resident = tn.attn_cross_resident, g_attn_pair_seq = tn.attn_pair_sequential;
-#ifdef D3PM_ABLATIONS
-  const int g_attn_qg = (ab_knobs().attn_arm && ab_knobs().attn_arm < 300) ? ab_knobs().attn_arm : tn.attn_query_groups;      // arms >= 3: include/d3pm_hip_ab.h
-#else
   const int g_attn_qg = (tn.attn_query_groups == 1 || tn.attn_query_groups == 2) ? tn.attn_query_groups : 0;
-#endif
   // The 32 x 32 x 16 kernel of d3pm_mfma_attn32.hip wherever it applies (whole 128-query blocks and 64-key tiles of a single
   // problem: the self-attention of a DiT block) once its grid has two workgroups per CU (measured: 55.3 vs 65.3 us at 32
   // utterances x 768 frames, 19.5 vs 20.3 at 32 x 384, 28.8 vs 30.8 at 16 x 768; tests/ab_attn32.py); below that the 64-query
@@ -695,15 +563,10 @@ int mfma_attention(int dtype, const AttnArgs& a, hipStream_t s) {
     // regime_batch: the batch the automatic choice is made for (a shard of a split batch takes the kernels of the whole batch)
     const long long wgs32 = static_cast<long long>(a.Tq / 128) * a.H * (tn.regime_batch > 0 ? tn.regime_batch : a.B);
     const int q = tn.attn_query_groups;
-#ifdef D3PM_ABLATIONS
-    const bool arm35 = q == 35;      // A/B library: the pipelined kernel with 192-query workgroups (d3pm_mfma_attn32.hip)
-#else
-    const bool arm35 = false;
-#endif
     // key lengths: the masked instantiations on an explicit 32 / 33, or where the denoiser plan asks for the unmasked choice
     // (AttnArgs::masked_keeps_schedule); any other masked call keeps the kernel below, as it always has
     const bool auto32 = q == 0 && wgs32 >= 512 && (a.key_len == nullptr || a.masked_keeps_schedule);
-    if ((q == 32 || q == 33 || (arm35 && a.key_len == nullptr) || auto32) && mfma_attention32_supported(dtype, a)) return mfma_attention32(dtype, a, s);
+    if ((q == 32 || q == 33 || auto32) && mfma_attention32_supported(dtype, a)) return mfma_attention32(dtype, a, s);
   }
   const long long cross_wgs = static_cast<long long>((a.Tq + 255) / 256) * a.H * (tn.regime_batch > 0 ? tn.regime_batch : a.B);
   // (key lengths do not change the choice: S / S2 are the padded counts, which size the LDS image)
@@ -721,23 +584,17 @@ int mfma_attention(int dtype, const AttnArgs& a, hipStream_t s) {
       return mfma_attention32_cross(dtype, a, n_qsplit, s);
     const dim3 grid(static_cast<unsigned>(n_qsplit * a.H * a.B)), block(512);
     const size_t lds = static_cast<size_t>(1 + (a.S2 + BKV - 1) / BKV) * 2 * TILE;
-#define D3PM_CROSS(T, PIPE, MASK)                                                                                            \
+#define D3PM_CROSS(T, MASK)                                                                                                  \
     do {                                                                                                                     \
-      D3PM_LDS_ATTR((&attn_cross_hd64<T, PIPE, MASK>), 5 * 2 * TILE);                                                        \
-      attn_cross_hd64<T, PIPE, MASK><<<grid, block, lds, s>>>(static_cast<const T*>(a.Q), static_cast<const T*>(a.K),         \
+      D3PM_LDS_ATTR((&attn_cross_hd64<T, MASK>), 5 * 2 * TILE);                                                              \
+      attn_cross_hd64<T, MASK><<<grid, block, lds, s>>>(static_cast<const T*>(a.Q), static_cast<const T*>(a.K),               \
           static_cast<const T*>(a.V), static_cast<T*>(a.O), a.S, static_cast<const T*>(a.Q2), static_cast<const T*>(a.K2),    \
           static_cast<const T*>(a.V2), static_cast<T*>(a.O2), a.S2, a.ldq, a.ldkv, a.ldo, a.Tq, a.scale, a.H, n_qblocks, n_qsplit, \
           a.key_len, a.key_len2);                                                                                            \
     } while (0)
     if (a.key_len || a.key_len2) {
-      if (dtype == D3PM_F16) D3PM_CROSS(f16, false, true); else D3PM_CROSS(bf16, false, true);
-    } else
-#ifdef D3PM_ABLATIONS
-    if (ab_knobs().attn_arm == 300) {      // A/B: the software-pipelined walk
-      if (dtype == D3PM_F16) D3PM_CROSS(f16, true, false); else D3PM_CROSS(bf16, true, false);
-    } else
-#endif
-    if (dtype == D3PM_F16) D3PM_CROSS(f16, false, false); else D3PM_CROSS(bf16, false, false);
+      if (dtype == D3PM_F16) D3PM_CROSS(f16, true); else D3PM_CROSS(bf16, true);
+    } else if (dtype == D3PM_F16) D3PM_CROSS(f16, false); else D3PM_CROSS(bf16, false);
 #undef D3PM_CROSS
     D3PM_LAUNCH_CHECK();
     return D3PM_OK;
@@ -749,7 +606,7 @@ int mfma_attention(int dtype, const AttnArgs& a, hipStream_t s) {
   // the schedule, and therefore the bits, of the batches up to ten.
   if (tn.attn_query_groups == 4 && mfma_attention_split_supported(dtype, a)) return mfma_attention_split(dtype, a, s);
   const long long wgs2 = static_cast<long long>((a.Tq + 127) / 128) * a.H * a.B * (a.Q2 ? 2 : 1);
-  const int qg = g_attn_qg == 0 ? (wgs2 >= 4 * 256 ? 2 : 1) : g_attn_qg >= 100 ? 2 : (g_attn_qg == 3 && (dtype != D3PM_BF16 || a.Q2)) ? 2 : g_attn_qg, per_block = 64 * qg;
+  const int qg = g_attn_qg == 0 ? (wgs2 >= 4 * 256 ? 2 : 1) : g_attn_qg, per_block = 64 * qg;
   const int n_qblocks = (a.Tq + per_block - 1) / per_block;
   const int n_blocks1 = n_qblocks * a.H * a.B;
   const bool seq = a.Q2 != nullptr && (g_attn_pair_seq == 2 || (g_attn_pair_seq == 1 && n_blocks1 >= 512));
@@ -766,16 +623,6 @@ int mfma_attention(int dtype, const AttnArgs& a, hipStream_t s) {
     if (seq) { if (qg == 1) D3PM_ATTN(T, 1, true); else D3PM_ATTN(T, 2, true); }           \
     else { if (qg == 1) D3PM_ATTN(T, 1, false); else D3PM_ATTN(T, 2, false); }             \
   } while (0)
-#ifdef D3PM_ABLATIONS
-  if (g_attn_qg == 3 && dtype == D3PM_BF16 && !a.Q2) {        // three query groups per wave (A/B: fewer LDS reads per MFMA, two waves per SIMD)
-    D3PM_ATTN(bf16, 3, false);
-  } else if ((g_attn_qg == 164 || g_attn_qg == 228) && dtype == D3PM_BF16 && !a.Q2) {      // the QG = 2 kernel with ABL bit 6 / bit 7
-#define D3PM_ABL(A) attn_mfma_hd64<bf16, 2, false, A><<<grid, block, 0, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), \
-      static_cast<const bf16*>(a.V), a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, nullptr, nullptr, nullptr, nullptr, 0, n_first, a.key_len, nullptr)
-    if (g_attn_qg == 164) D3PM_ABL(64); else D3PM_ABL(128);
-#undef D3PM_ABL
-  } else
-#endif
   if (dtype == D3PM_F16) D3PM_ATTN_QG(f16); else D3PM_ATTN_QG(bf16);
 #undef D3PM_ATTN_QG
 #undef D3PM_ATTN

@@ -272,15 +272,15 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
 // The groups are pinned with sched_barrier(0) (hipcc otherwise hoists the exponentials in front of the products).  K(j + 1)
 // of the next tile is read half a tile before that tile's turn: three LDS buffers, tiles staged two ahead, still one barrier
 // per tile.
-// NW = waves (32-query groups) per workgroup: 4 = 128 queries, three workgroups per CU; 6 = 192 queries, two workgroups per CU --
-// the same twelve waves per CU, but every staged K / V tile serves half as many queries again (a third fewer bytes L2 -> LDS and
-// staging instructions per query; waves 4 and 5 do not stage).  A query's arithmetic does not depend on NW: bit-identical.
+// Four waves (32-query groups) per workgroup: 128 queries, three workgroups per CU.  192-query workgroups of six waves (two per CU, a
+// third fewer K / V bytes staged per query, bit-identical) were built, measured and not shipped: 65.8 vs 52.8 us at 32 x 768, 23.0 vs
+// 19.4 at 32 x 384 (profiles/round3_t_ab_attn32.txt; source up to commit d54b189) -- the staged bytes are not what this kernel waits for.
 // MASK: see attn32_hd64.  The scores of a block are produced, and tested against the deferral threshold, inside the block in front of
 // it, so the mask is applied there (MSK, in front of the maximum): in the prologue (block 0), in the second block of the last tile
 // but one (first block of the last tile) and in the first block of the last tile (its second block), the latter two peeled out of
 // the loop.  A block of the last tile that lies wholly behind key_len[b] is walked with every score -inf: probabilities 0.
-template <typename T, int NW = 4, bool MASK = false>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T* __restrict__ Q, int ldq, const T* __restrict__ Kp,
+template <typename T, bool MASK = false>
+__global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, int ldq, const T* __restrict__ Kp,
                                                        const T* __restrict__ Vp, int ldkv, T* __restrict__ O, int ldo, int Tq,
                                                        int S, float scale, int H, int n_qblocks, const int32_t* __restrict__ key_len) {
   __shared__ __attribute__((aligned(16))) char smem[3 * 2 * TILE];   // [buffer][K tile | V tile]
@@ -291,8 +291,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
   const int qb = bid % n_qblocks, h = (bid / n_qblocks) % H, b = bid / (n_qblocks * H);
-  const int q0 = (qb * NW + wave) * 32;
-  const bool stager = NW == 4 || wave < 4;               // wave-uniform: 256 threads stage a tile
+  const int q0 = (qb * 4 + wave) * 32;
   const int qn = lane & 31, hh = lane >> 5;
   const T* Kb = Kp + static_cast<size_t>(b) * S * ldkv + h * HD;
   const T* Vb = Vp + static_cast<size_t>(b) * S * ldkv + h * HD;
@@ -342,7 +341,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
 #pragma unroll
     for (int i = 0; i < 16; ++i) s[i] = (8 * (i >> 2) + (i & 3) < lim) ? s[i] : -INFINITY;
   };
-  if (stager) {
+  {
     Staged st = load_tile(0);
     store_tile(smem, st);
     if (n_tiles > 1) {
@@ -436,11 +435,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
     SB();
     if constexpr (STG != 0) {      // unconditional in the tile index (a branch on it splits the block and hipcc sinks the vector work
       // behind it): past the end the last tile is staged again, into a buffer that is no longer read
-      if (NW == 4 || stager) {
-        const char* gt = reinterpret_cast<const char*>((STG == 1 ? Kb : Vb) + static_cast<size_t>(stile < n_tiles ? stile : n_tiles - 1) * BKV * ldkv);
-        h0 = *reinterpret_cast<const uint4*>(gt + lo0);
-        h1 = *reinterpret_cast<const uint4*>(gt + lo1);
-      }
+      const char* gt = reinterpret_cast<const char*>((STG == 1 ? Kb : Vb) + static_cast<size_t>(stile < n_tiles ? stile : n_tiles - 1) * BKV * ldkv);
+      h0 = *reinterpret_cast<const uint4*>(gt + lo0);
+      h1 = *reinterpret_cast<const uint4*>(gt + lo1);
     }
     read_v(0, 0);
     read_v(0, 1);
@@ -475,10 +472,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) void attn32p_hd64(const T
     SB();
     pv(1);
     if constexpr (STG != 0) {
-      if (NW == 4 || stager) {
-        *reinterpret_cast<uint4*>(sdst + (STG == 1 ? ko0 : TILE + vo0)) = h0;
-        *reinterpret_cast<uint4*>(sdst + (STG == 1 ? ko1 : TILE + vo1)) = h1;
-      }
+      *reinterpret_cast<uint4*>(sdst + (STG == 1 ? ko0 : TILE + vo0)) = h0;
+      *reinterpret_cast<uint4*>(sdst + (STG == 1 ? ko1 : TILE + vo1)) = h1;
     }
     SB();
     if constexpr (NEXT) {
@@ -865,24 +860,8 @@ int mfma_attention32(int dtype, const AttnArgs& a, hipStream_t s) {
   KERNEL<<<grid, block, 0, s>>>(static_cast<const T*>(a.Q), a.ldq, static_cast<const T*>(a.K), static_cast<const T*>(a.V), a.ldkv, \
                                 static_cast<T*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, a.key_len)
   if (tune_of(a.tune).attn_query_groups != 33) {           // 33: the plain walk (A/B against the pipelined one)
-#ifdef D3PM_ABLATIONS
-    // A/B library only (attn_query_groups = 35): 192-query workgroups of six waves, two per CU -- a third fewer K / V bytes staged
-    // per query, bit-identical, measured SLOWER (65.8 vs 52.8 us at 32 x 768, 23.0 vs 19.4 at 32 x 384: tests/ab_attn32.py,
-    // profiles/round3_t_ab_attn32.txt): the staged bytes are not what this kernel waits for
-    if (tune_of(a.tune).attn_query_groups == 35 && a.Tq % 192 == 0 && !a.key_len) {
-      const dim3 grid6(static_cast<unsigned>(a.Tq / 192 * a.H * a.B)), block6(384);
-      if (dtype == D3PM_F16)
-        attn32p_hd64<f16, 6><<<grid6, block6, 0, s>>>(static_cast<const f16*>(a.Q), a.ldq, static_cast<const f16*>(a.K), static_cast<const f16*>(a.V),
-                                                      a.ldkv, static_cast<f16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, a.Tq / 192, nullptr);
-      else
-        attn32p_hd64<bf16, 6><<<grid6, block6, 0, s>>>(static_cast<const bf16*>(a.Q), a.ldq, static_cast<const bf16*>(a.K), static_cast<const bf16*>(a.V),
-                                                       a.ldkv, static_cast<bf16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, a.Tq / 192, nullptr);
-      D3PM_LAUNCH_CHECK();
-      return D3PM_OK;
-    }
-#endif
     if (a.key_len) {
-      if (dtype == D3PM_F16) D3PM_ATTN32((attn32p_hd64<f16, 4, true>), f16); else D3PM_ATTN32((attn32p_hd64<bf16, 4, true>), bf16);
+      if (dtype == D3PM_F16) D3PM_ATTN32((attn32p_hd64<f16, true>), f16); else D3PM_ATTN32((attn32p_hd64<bf16, true>), bf16);
     } else {
       if (dtype == D3PM_F16) D3PM_ATTN32((attn32p_hd64<f16>), f16); else D3PM_ATTN32((attn32p_hd64<bf16>), bf16);
     }

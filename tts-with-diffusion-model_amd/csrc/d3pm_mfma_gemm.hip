@@ -126,16 +126,7 @@ __global__ __launch_bounds__(256, 4) void gemm_mfma_128_glds(const T* __restrict
     }
     __syncthreads();
   }
-#ifndef D3PM_EXP_NOSTORE
-  epilogue_store<T, EPI>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 64, n0 + wn * 64, lane, nullptr, nullptr, static_cast<const EpiPre<T, 4, 4>*>(nullptr), &ef);
-#else
-  {  // ablation build (tests/bench_kernels.py), never shipped: keep every accumulator live, store nothing
-    float sum = 0.f;
-    for (int a = 0; a < 4; ++a)
-      for (int b = 0; b < 4; ++b) sum += acc[a][b][0] + acc[a][b][1] + acc[a][b][2] + acc[a][b][3];
-    if (sum == 12345.f) Y[0] = static_cast<T>(1.f);
-  }
-#endif
+  epilogue_store<T, EPI>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 64, n0 + wn * 64, lane, nullptr, static_cast<const EpiPre<T, 4, 4>*>(nullptr), &ef);
 }
 
 
@@ -214,16 +205,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_128_pf(const T* __restrict__
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // all fragment reads of tile kt retired
     __builtin_amdgcn_s_barrier();                        // barrier B: tile kt's buffer may be overwritten
   }
-#ifndef D3PM_EXP_NOSTORE
-  epilogue_store<T, EPI>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 64, n0 + wn * 64, lane, nullptr, nullptr, static_cast<const EpiPre<T, 4, 4>*>(nullptr), &ef);
-#else
-  {  // ablation build (tests/bench_kernels.py), never shipped: keep every accumulator live, store nothing
-    float sum = 0.f;
-    for (int a = 0; a < 4; ++a)
-      for (int b = 0; b < 4; ++b) sum += acc[a][b][0] + acc[a][b][1] + acc[a][b][2] + acc[a][b][3];
-    if (sum == 12345.f) Y[0] = static_cast<T>(1.f);
-  }
-#endif
+  epilogue_store<T, EPI>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 64, n0 + wn * 64, lane, nullptr, static_cast<const EpiPre<T, 4, 4>*>(nullptr), &ef);
 }
 
 
@@ -320,7 +302,7 @@ __global__ __launch_bounds__(256, 4) void gemm_mfma_128_persist(const T* __restr
       issue(sx, sw);
     }
     epilogue_store<T, EPI, 4, 4, true>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 64,
-                                       n0 + wn * 64, lane, nullptr, nullptr, static_cast<const EpiPre<T, 4, 4>*>(nullptr), &ef);
+                                       n0 + wn * 64, lane, nullptr, static_cast<const EpiPre<T, 4, 4>*>(nullptr), &ef);
     if (!more) break;
     first = false;
   }
@@ -329,35 +311,7 @@ __global__ __launch_bounds__(256, 4) void gemm_mfma_128_persist(const T* __restr
 
 inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
-#ifdef D3PM_ABLATIONS
-__device__ uint16_t g_gelu_bf16[GELU_TAB_ENTRIES];
-__global__ void fill_gelu_table() {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= GELU_TAB_ENTRIES) return;
-  const uint32_t sign = i / (GELU_TAB_NE * 128), rem = i % (GELU_TAB_NE * 128);
-  const uint32_t bits = (sign << 15) | ((rem / 128 + GELU_TAB_E0) << 7) | (rem % 128);
-  const float v = __uint_as_float(bits << 16);
-  g_gelu_bf16[i] = static_cast<uint16_t>(__float_as_uint(rn<bf16>(gelu_erf(v))) >> 16);
-}
-#endif
-
 }  // namespace
-
-#ifdef D3PM_ABLATIONS
-// Device address of the bf16 GELU table (d3pm_mfma_tile.h), filled on first use on `s` (a static of the library: no
-// allocation; the fill kernel is idempotent, so a capture that happens to contain it replays harmlessly).
-const uint16_t* gelu_table_device(hipStream_t s) {
-  static const uint16_t* ptr = nullptr;
-  if (!ptr) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_gelu_bf16)) != hipSuccess) return nullptr;
-    fill_gelu_table<<<(GELU_TAB_ENTRIES + 255) / 256, 256, 0, s>>>();
-    if (hipGetLastError() != hipSuccess) return nullptr;
-    ptr = static_cast<const uint16_t*>(p);
-  }
-  return ptr;
-}
-#endif
 
 bool mfma_linear_supported(int dtype, const LinearArgs& a) {
   if (dtype != D3PM_F16 && dtype != D3PM_BF16) return false;
@@ -381,29 +335,12 @@ bool mfma_linear_supported(int dtype, const LinearArgs& a) {
 // workgroup, 6 / 7 / 8 big tiles (192 x 256 / 96 x 512 / 192 x 128, d3pm_mfma_gemm_big.hip) wherever they apply, else as auto
 // without big tiles.  gemm_persist_slots: resident workgroups of the persistent schedule (1024 = 4 per CU x 256 CUs).
 bool panel64_linear_supported(int dtype, const LinearArgs& a);
-int panel64_linear(int dtype, const LinearArgs& a, hipStream_t s, const LnPrologue* ln = nullptr);
+int panel64_linear(int dtype, const LinearArgs& a, hipStream_t s);
 int big_linear_tile(int dtype, const LinearArgs& a, int want);
 int big_linear(int dtype, const LinearArgs& a, int id, hipStream_t s);
 
-#ifdef D3PM_ABLATIONS
-bool ring_linear_supported(int dtype, const LinearArgs& a);
-int ring_linear(int dtype, const LinearArgs& a, hipStream_t s);
-// The LayerNorm-prologue form exists for the latency schedule only: true where mfma_linear would pick that schedule anyway
-bool ln_prologue_linear_applies(int dtype, const LinearArgs& a, const LnPrologue& ln) {
-  const int variant = tune_of(a.tune).gemm_variant;
-  const bool autosel = variant == 0;
-  if (!(variant == 4 || (autosel && a.M <= 1536))) return false;
-  if (autosel && big_linear_tile(dtype, a, 0)) return false;
-  return panel64_ln_supported(dtype, a, ln);
-}
-int ln_prologue_linear(int dtype, const LinearArgs& a, const LnPrologue& ln, hipStream_t s) { return panel64_linear(dtype, a, s, &ln); }
-#endif
-
 // the big-tile geometry mfma_linear takes for `a` (d3pm_mfma_gemm_big.hip), 0 = another family
 static int mfma_linear_big_id(int dtype, const LinearArgs& a) {
-#ifdef D3PM_ABLATIONS
-  if (ab_knobs().ring && ring_linear_supported(dtype, a)) return 0;
-#endif
   const int v = tune_of(a.tune).gemm_variant;
   if (!(v == 0 || (v >= 6 && v <= 8))) return 0;
   return big_linear_tile(dtype, a, v == 6 ? 2 : v == 7 ? 1 : v == 8 ? 3 : 0);
@@ -416,9 +353,6 @@ int mfma_linear(int dtype, const LinearArgs& a, hipStream_t s) {
   const bool ffn_act = a.act == ACT_RELU || a.act == ACT_SILU;
   const d3pm_tuning& tn = tune_of(a.tune);
   const int g_gemm_variant = tn.gemm_variant, g_persist_slots = tn.gemm_persist_slots >= 8 ? (tn.gemm_persist_slots & ~7) : 1024;
-#ifdef D3PM_ABLATIONS
-  if (ab_knobs().ring && ring_linear_supported(dtype, a) && !a.moment_quads) return ring_linear(dtype, a, s);   // experimental ring schedule
-#endif
   const bool autosel = g_gemm_variant == 0 || (g_gemm_variant >= 6 && g_gemm_variant <= 8);
   if (const int id = mfma_linear_big_id(dtype, a)) return big_linear(dtype, a, id, s);
   if (a.moment_quads) {            // the quad format of the row moments exists in the big-tile epilogues only

@@ -56,12 +56,9 @@ __device__ __forceinline__ void glds16_m0(const void* sbase, uint32_t voff, uint
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
 }
 
-// MODE: 1 is the shipped schedule; every other value is instantiated in the A/B library only (-DD3PM_ABLATIONS, include/d3pm_hip_ab.h).
-// bit 0 = hand-scheduled fragment reads (asm, counted lgkmcnt); bit 3 (8) = deferred stores: a tile's 12 output stores
-// per wave are issued a few per k-step inside the NEXT tile's main loop (all CUs finish their tiles together, so stores
-// issued in the epilogue arrive as one chip-wide burst that the HBM write path drains at ~5.5 TB/s while every MFMA pipe
-// idles: 4.5 us per 25 MB round; needs K >= 512); bit 11 (2048) = every DMA piece of the next k-step issued in front of the
-// first MFMA group instead of one per group.  Instantiated: 1, 0, 9 and 2049.
+// The schedule is the hand-placed one (fragment reads from asm with counted lgkmcnt, one DMA piece per MFMA group).  Built, measured,
+// not shipped (source up to commit d54b189, figures in DESIGN.md section 3): compiler-placed reads, deferred stores (a tile's 12 output
+// stores issued inside the next tile's first k-steps) and every DMA piece of the next k-step in front of the first MFMA group.
 
 // Row-panel fusion (FUSE != 0; 96 x 512 tiles, d_model = 512 only: a workgroup then owns whole rows of the residual stream):
 //   bit 0  a SECOND product with the same weights runs through the same tile before the epilogue -- the text and prompt
@@ -80,13 +77,12 @@ template <typename T> struct RowPanelArgs {
 };
 constexpr int FUSE_DUAL = 1, FUSE_LN = 2, FUSE_LN2 = 4, FUSE_FILM = 8, FUSE_MX = 32;
 
-template <typename T, int EPI, int WM, int WN, int MODE, int FUSE = 0>
+template <typename T, int EPI, int WM, int WN, int FUSE = 0>
 __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __restrict__ X, int ldx, const T* __restrict__ W,
                                                         const T* __restrict__ bias, T* Y, int ldy, const T* R1,
                                                         const T* R2, int ldr, const uint8_t* __restrict__ row_mask,
                                                         int mask_period, int M, int N, int K, int n_tiles,
-                                                        int tiles_total, const uint16_t* __restrict__ gelu_tab_g,
-                                                        RowPanelArgs<T> rp, EpiFold ef) {
+                                                        int tiles_total, RowPanelArgs<T> rp, EpiFold ef) {
   constexpr int NW = WM * WN, TM = 96 * WM, TN = 64 * WN;   // 8 waves: one workgroup per CU; 4 waves: two
   constexpr int XD = TM / 8, WD = TN / 8;              // 1-KiB DMA pieces (8 rows x 128 B) per k-step and operand
   constexpr int XPW = (XD + NW - 1) / NW, WPW = WD / NW;   // pieces per wave
@@ -94,8 +90,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
   static_assert(NW % 2 == 0 && WD % NW == 0 && (XD % NW == 0 || (XD % NW) % 2 == 0), "piece distribution keeps the parity of the wave");
   constexpr int X_BYTES = TM * ROW_BYTES, STAGE = (TM + TN) * ROW_BYTES;
   static_assert(NDMA <= 12, "one DMA piece per group of four MFMAs");
-  constexpr bool kHand = (MODE & 1) != 0;
-  constexpr bool kDrip = (MODE & 8) != 0;
   // EPI_LNF (K = 512: the launcher): the row moments a lane needs for its six row blocks are 24 x 8 bytes per tile -- 48 KB per
   // workgroup tile beside its 320 KB of operands, through the same CU <-> L2 path (EPI_QUADS: 6 x 8 bytes, 12 KB) -- and a round trip
   // the epilogue would start with.  Loaded where the epilogue needs them they cost qkv 36.7 -> 45.1 us and fc1 69.7 -> 84.8 us in the loop; requested at
@@ -114,15 +108,10 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
   constexpr bool kDual = (FUSE & FUSE_DUAL) != 0, kLn = (FUSE & FUSE_LN) != 0, kLn2 = (FUSE & FUSE_LN2) != 0, kFilm = (FUSE & FUSE_FILM) != 0;
   constexpr bool kMx = (FUSE & FUSE_MX) != 0;
   static_assert(!kMx || kLn, "the MX output is the LayerNorm output");
-  static_assert(FUSE == 0 || !kDrip, "fusions ride in the hand-placed schedule without deferred stores");
-  static_assert(FUSE == 0 || FUSE == FUSE_DUAL || (WM == 1 && WN == 8 && (MODE & 1)), "row-panel fusion: 96 x 512 tiles, hand-placed schedule");
-  static_assert((EPI & (EPI_LNF | EPI_STATS)) == 0 || ((FUSE == 0 || (FUSE == FUSE_DUAL && (EPI & EPI_LNF) == 0)) && !kDrip),
+  static_assert(FUSE == 0 || FUSE == FUSE_DUAL || (WM == 1 && WN == 8), "row-panel fusion: 96 x 512 tiles");
+  static_assert((EPI & (EPI_LNF | EPI_STATS)) == 0 || FUSE == 0 || (FUSE == FUSE_DUAL && (EPI & EPI_LNF) == 0),
                 "the folded-LayerNorm epilogues ride in the plain launches (and the row moments in the dual out-projection)");
   static_assert(!kLn2 || kLn, "the second LayerNorm shares the moments of the first");
-  static_assert(!kDrip || kHand, "deferred stores ride in the hand-placed schedule");
-  constexpr int SPS = 12 - NDMA;                        // deferred stores per k-step: the MFMA groups behind the last DMA piece
-  constexpr int DRIP_STEPS = kDrip ? (12 + SPS - 1) / SPS : 0;          // 3 (192 x 256) or 6
-  constexpr int PEEL = kDrip ? ((DRIP_STEPS + 1 + 1) & ~1) : 2;           // k-steps written out per tile (even)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -149,29 +138,24 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
     if (p < XPW) {
       int j = wave + NW * p;
       if (XD % NW != 0 && j >= XD) j = (XD / NW) * NW + wave % (XD % NW);   // same parity as `wave`: a harmless repeat
-      if (kHand) glds16_m0(px + static_cast<size_t>(8 * j) * ldx, ox, stage + j * 1024);
-      else glds16_asm_s(px + static_cast<size_t>(8 * j) * ldx, ox, stage + j * 1024);
+      glds16_m0(px + static_cast<size_t>(8 * j) * ldx, ox, stage + j * 1024);
     } else {
       const int j = wave + NW * (p - XPW);
-      if (kHand) glds16_m0(pw + static_cast<size_t>(8 * j) * K, ow, stage + X_BYTES + j * 1024);
-      else glds16_asm_s(pw + static_cast<size_t>(8 * j) * K, ow, stage + X_BYTES + j * 1024);
+      glds16_m0(pw + static_cast<size_t>(8 * j) * K, ow, stage + X_BYTES + j * 1024);
     }
   };
   // fragment addresses: row = base + 16 q + (lane & 15); the swizzle key (row >> 1) & 7 = (lane & 15) >> 1 because
   // every base is a multiple of 16
   const int frow = lane & 15, fch = lane >> 4, fkey = (frow >> 1) & 7;
   const int fo0 = frow * ROW_BYTES + ((fch ^ fkey) << 4), fo1 = frow * ROW_BYTES + (((4 + fch) ^ fkey) << 4);
+  // PINS, not code: no instruction comes from fx_base / fw_base here, from `pend` below or from their uses in the k-step lambda.  hipcc's
+  // early passes run before that lambda is inlined and see what it captures; with the operand bases and the twelve registers of the
+  // retired deferred-store schedule captured, the instantiations keep the instruction streams they were measured with (all but two
+  // unfolded bf16 GELU ones, which the epilogue's lost table arm moved) -- without them scalar code of every prologue moves
+  // (profiles/round12_experiment_library_retired_same_code.txt).  Drop them only with a new measurement.
   const char* const fx_base = smem + wm * 96 * ROW_BYTES;
   const char* const fw_base = smem + X_BYTES + wn * 64 * ROW_BYTES;
 
-  // bf16 GELU epilogue: the lookup table rides behind the two stages (only where it fits: 192 x 256 tiles)
-  const uint16_t* gelu_tab = nullptr;
-  if constexpr ((EPI & EPI_GELU) != 0 && std::is_same<T, bf16>::value && 2 * STAGE + GELU_TAB_BYTES <= 160 * 1024 && NW == 8) {
-    if (gelu_tab_g) {
-      gelu_table_to_lds(gelu_tab_g, smem + 2 * STAGE, tid, NW * 64);
-      gelu_tab = reinterpret_cast<const uint16_t*>(smem + 2 * STAGE);     // the first k-step's barrier publishes it
-    }
-  }
   const int nk = K / BK;                                             // even (checked by the launcher)
   int tile = lo + t;
   const T* sx = X + static_cast<size_t>((tile / n_tiles) * TM) * ldx;
@@ -201,7 +185,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
   // the first step of a tile waits with vmcnt(12): behind an epilogue the DMA pieces are older than its 12 stores; the very
   // first tile has no stores behind its pieces, so they are waited for here
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  uintx4 pend[12];                // deferred-store mode: the previous tile, finished and packed
+  uintx4 pend[12];                // pin (above)
 #pragma unroll
   for (int j = 0; j < 12; ++j) pend[j] = uintx4{0u, 0u, 0u, 0u};
   T* pend_y = Y;
@@ -244,23 +228,18 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
     const T* sw_next = W + static_cast<size_t>((tile_next % n_tiles) * TN) * K;
 
     // one k-step on stage S while the DMA pieces of the following k-step (px, pw) go to stage S ^ 1.  WAITN: what the wait at
-    // the top may leave in flight (the stores issued behind the previous k-step's last DMA piece); [ST0, ST0 + STN): the
-    // deferred stores of the previous tile that this k-step issues
-    auto step = [&](auto S_, auto WAITN_, auto ST0_, auto STN_, const T* px, const T* pw) __attribute__((always_inline)) {
-      constexpr int S = decltype(S_)::value, WAITN = decltype(WAITN_)::value, ST0 = decltype(ST0_)::value, STN = decltype(STN_)::value;
-      const char* bx = fx_base + S * STAGE;
-      const char* bw = fw_base + S * STAGE;
+    // the top may leave in flight (the previous tile's output stores, which are younger than this k-step's pieces)
+    auto step = [&](auto S_, auto WAITN_, const T* px, const T* pw) __attribute__((always_inline)) {
+      constexpr int S = decltype(S_)::value, WAITN = decltype(WAITN_)::value;
+      [[maybe_unused]] const char* bx = fx_base + S * STAGE;      // pins (top of the kernel)
+      [[maybe_unused]] const char* bw = fw_base + S * STAGE;
       const uint32_t nxt = lds_base + (S ^ 1) * STAGE;
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (WAITN > 0) {
-        if (!kDrip || pending) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAITN) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
+      if constexpr (WAITN > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAITN) : "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();      // every wave's pieces of this k-step have landed; stage S ^ 1 is no longer read
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (kHand) {
+      {
         // issue order of the 20 fragment reads of a k-step: W0..3 X0 X1 | g0: X2 | g1: X3 | g2: X4 W'0 | g3: X5 W'1 | g4: X6 W'2 |
         // g5: X7 W'3 | g6: X8 | g7: X9 | g8: X10 | g9: X11 (X six row blocks per k-half, W' = the second k-half's W fragments);
         // group g consumes X_g (and W at g = 0, W' at g = 6): the counts below are the reads younger than what it needs
@@ -274,41 +253,15 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
           constexpr int g = G.value, ks = g / 6, mt = g % 6;
           if constexpr (g + 2 < 12) lds_read16(fx[(g + 2) % 3], (g + 2) / 6 ? ax1 : ax0, ((g + 2) % 6) * 16 * ROW_BYTES);
           if constexpr (ks == 0 && mt >= 2) lds_read16(fw1[mt - 2], aw1, (mt - 2) * 16 * ROW_BYTES);
-          if constexpr ((MODE & 2048) != 0) {                // A/B: every piece of the next k-step issued in front of the first MFMA group
-            if constexpr (g == 0) {
-#pragma unroll
-              for (int p = 0; p < NDMA; ++p) dma(p, px, pw, nxt);
-            }
-          } else if constexpr (g < NDMA) dma(g, px, pw, nxt);
+          if constexpr (g < NDMA) dma(g, px, pw, nxt);
           constexpr int kWait[12] = {2, 2, 3, 4, 5, 5, 1, 2, 2, 2, 1, 0};
           if constexpr (g == 0) lds_wait<kWait[g]>(fw0[0], fw0[1], fw0[2], fw0[3], fx[0]);
           else if constexpr (g == 6) lds_wait<kWait[g]>(fw1[0], fw1[1], fw1[2], fw1[3], fx[g % 3]);
           else lds_wait<kWait[g]>(fx[g % 3]);
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) acc[nt][mt] = mma<T>(__builtin_bit_cast(uint4, ks ? fw1[nt] : fw0[nt]), __builtin_bit_cast(uint4, fx[g % 3]), acc[nt][mt]);
-          if constexpr (kDrip && g >= NDMA && g - NDMA < STN) {
-            constexpr int j = ST0 + g - NDMA;          // store j = (row block j / 2, column pair j % 2) of the previous tile
-            if (pending) *reinterpret_cast<uintx4*>(pend_y + static_cast<size_t>((j / 2) * 16) * ldy + (j % 2) * 32) = pend[j];
-          }
+          if constexpr (WAITN < 0 && g < 0) { if (pending) *reinterpret_cast<uintx4*>(pend_y + ldy) = pend[g]; }      // pin: never instantiated
         });
-      } else {
-      uint4 fw[2][4], fx[3];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) fw[0][nt] = *reinterpret_cast<const uint4*>(bw + nt * 16 * ROW_BYTES + fo0);
-      fx[0] = *reinterpret_cast<const uint4*>(bx + fo0);
-      fx[1] = *reinterpret_cast<const uint4*>(bx + 16 * ROW_BYTES + fo0);
-#pragma unroll
-      for (int g = 0; g < 12; ++g) {       // group g: k-half g / 6, row block g % 6, four MFMAs
-        const int ks = g / 6, mt = g % 6;
-        if (g + 2 < 12) {
-          const int g2 = g + 2;
-          fx[g2 % 3] = *reinterpret_cast<const uint4*>(bx + (g2 % 6) * 16 * ROW_BYTES + (g2 / 6 ? fo1 : fo0));
-        }
-        if (ks == 0 && mt >= 2) fw[1][mt - 2] = *reinterpret_cast<const uint4*>(bw + (mt - 2) * 16 * ROW_BYTES + fo1);
-        if (g < NDMA) dma(g, px, pw, nxt);
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt][mt] = mma<T>(fw[ks][nt], fx[g % 3], acc[nt][mt]);
-      }
       }
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -318,7 +271,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
     uintx4 h1p[kDual ? 12 : 1];
     // the nk k-steps of one product: operand rows `ax`, weights `sw`; (nx, nw) = the first k-step of whatever follows
     auto run_k = [&](const T* ax, const T* nx, const T* nw, auto FIRSTW) __attribute__((always_inline)) {
-      step(I0{}, FIRSTW, I0{}, I0{}, ax + BK, sw + BK);
+      step(I0{}, FIRSTW, ax + BK, sw + BK);
       if constexpr (kLnfPre) {
         // the first k-step waited for everything older than the previous tile's stores: this tile's moments, requested in front of
         // those stores, have landed (the "+v" operands keep every use behind that wait)
@@ -334,28 +287,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
           fold_row_scalars(add_xor32(a), add_xor32(q), 512, ef.eps, rows.ra[mt], rows.rc[mt]);
         }
       }
-      step(I1{}, I0{}, I0{}, I0{}, ax + 2 * BK, sw + 2 * BK);
+      step(I1{}, I0{}, ax + 2 * BK, sw + 2 * BK);
       for (int kt = 2; kt < nk; kt += 2) {                  // nk is even and >= 4
-        step(I0{}, I0{}, I0{}, I0{}, ax + (kt + 1) * BK, sw + (kt + 1) * BK);
+        step(I0{}, I0{}, ax + (kt + 1) * BK, sw + (kt + 1) * BK);
         const bool last = kt + 2 >= nk;
-        step(I1{}, I0{}, I0{}, I0{}, last ? nx : ax + (kt + 2) * BK, last ? nw : sw + (kt + 2) * BK);
+        step(I1{}, I0{}, last ? nx : ax + (kt + 2) * BK, last ? nw : sw + (kt + 2) * BK);
       }
     };
-    if constexpr (kDrip) {
-      static_for<PEEL>([&](auto SI) {                     // the k-steps that carry the previous tile's stores, written out
-        constexpr int si = SI.value;
-        constexpr int cnt = 12 - si * SPS < 0 ? 0 : (12 - si * SPS < SPS ? 12 - si * SPS : SPS);
-        constexpr int prev = si == 0 ? 0 : (12 - (si - 1) * SPS < 0 ? 0 : (12 - (si - 1) * SPS < SPS ? 12 - (si - 1) * SPS : SPS));
-        const bool lastk = si + 1 >= nk;
-        step(std::integral_constant<int, si & 1>{}, std::integral_constant<int, prev>{}, std::integral_constant<int, si * SPS>{},
-             std::integral_constant<int, cnt>{}, lastk ? sx_next : sx + (si + 1) * BK, lastk ? sw_next : sw + (si + 1) * BK);
-      });
-      for (int kt = PEEL; kt < nk; kt += 2) {               // nk is even and >= PEEL
-        step(I0{}, I0{}, I0{}, I0{}, sx + (kt + 1) * BK, sw + (kt + 1) * BK);
-        const bool last = kt + 2 >= nk;
-        step(I1{}, I0{}, I0{}, I0{}, last ? sx_next : sx + (kt + 2) * BK, last ? sw_next : sw + (kt + 2) * BK);
-      }
-    } else if constexpr (kDual) {
+    if constexpr (kDual) {
       // two products through the same weights, one loop so that the k-step code exists once: phase 0 ends with its result
       // packed in registers (h1p), phase 1 runs into the common epilogue below
       const T* sx2 = rp.X2 + static_cast<size_t>(m0) * ldx;
@@ -554,16 +493,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
         }   // 16-bit LayerNorm outputs
       }
     } else {
-      bool kept = false;
-      if constexpr (kDrip) {         // keep the finished tile in registers: its stores go out inside the next tile's first k-steps
-        if (more) {
-          epilogue_store<T, EPI, 4, 6, true, true>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 96,
-                                                   n0 + wn * 64, lane, pend, gelu_tab);
-          pend_y = Y + static_cast<size_t>(m0 + wm * 96 + (lane & 15)) * ldy + n0 + wn * 64 + epilogue_nq(lane);
-          pending = true;
-          kept = true;
-        }
-      }
       if constexpr (kLnfPre) {
         floatx4 bq[4], sq[4];
         const int ncol = n0 + wn * 64 + (lane >> 4) * 4;
@@ -586,14 +515,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
           for (int r = 0; r < 4; ++r) { pre.bv[nt][r] = bq[nt][r]; pre.sv[nt][r] = sq[nt][r]; }
         }
         epilogue_store<T, EPI, 4, 6, true, false, true, true>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 96,
-                                                              n0 + wn * 64, lane, nullptr, gelu_tab, &pre, &ef, &rows);
-      } else if (!kept) {
+                                                              n0 + wn * 64, lane, nullptr, &pre, &ef, &rows);
+      } else {
         // output rows leave as `sc1` stores (kNts): they are not read again by this launch, and left in the XCD's L2 they displace the
         // operand panels the other tiles of the launch still stream (in the loop: 103.8 k -> 106.2 k tokens/s with the stand-alone
-        // LayerNorms, 104.5 k -> 110.5 k with them folded; MODE bit 9 of the A/B library used to try `nt`, which keeps the line in L2)
+        // LayerNorms, 104.5 k -> 110.5 k with them folded; `nt`, which keeps the line in L2, was tried and lost)
         [[maybe_unused]] float z[12];
         epilogue_store<T, EPI, 4, 6, true, false, true>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 96,
-                                                          n0 + wn * 64, lane, nullptr, gelu_tab, &pre, &ef, nullptr, z);
+                                                          n0 + wn * 64, lane, nullptr, &pre, &ef, nullptr, z);
         if constexpr (kQuads && (EPI & EPI_STATS) != 0) quads_out(z, m0, n0);
       }
     }
@@ -616,16 +545,6 @@ static void big_geometry(int id, int& tm, int& tn, int& waves) {
   tn = id == 1 ? 512 : id == 2 ? 256 : 128;
   waves = id == 3 ? 4 : 8;
 }
-
-#ifdef D3PM_ABLATIONS
-const uint16_t* gelu_table_device(hipStream_t s);
-// D3PM_AB_GELU_TABLE: bf16 GELU epilogues read an LDS table (d3pm_mfma_tile.h).  Not shipped: measured SLOWER on MI355X -- fc1 +
-// GELU at M = 24576 with 192 x 256 tiles 86.4 us with the table vs 72.6 us with the polynomial (67.9 us for the shipped 192 x 128
-// geometry); 64 random 2-byte LDS reads per instruction cost more than the 17 vector instructions they replace
-int gelu_table_enabled() { return ab_knobs().gelu_table; }
-#else
-static int gelu_table_enabled() { return 0; }
-#endif
 
 // 0 = not applicable, else the geometry id.  `want` (tuning knob): 0 auto, 1 / 2 / 3 forced.
 int big_linear_tile(int dtype, const LinearArgs& a, int want) {
@@ -660,7 +579,6 @@ int big_linear_tile(int dtype, const LinearArgs& a, int want) {
   // (profiles/round3_w_ab_tune_geom.txt).  So: two 4-wave workgroups per CU wherever that geometry fills its rounds.
   if (fits(3, false)) return 3;
   if (fits(2, false)) return 2;
-  if (fits(3, false)) return 3;
   if (fits(1, false)) return 1;
   // Mid-size batches (the VCTK config: 32 x 384 rows; 8 .. 16 utterances of the libritts shape) leave the chip partly idle with
   // every big tile, yet 192 x 128 tiles of four waves still beat the 128 x 128 kernels there once at least half (long K) or all
@@ -673,54 +591,22 @@ int big_linear_tile(int dtype, const LinearArgs& a, int want) {
   return 0;
 }
 
-// kernel MODE template argument: 1 = the shipped schedule (hand-placed reads); every other value is an experiment that
-// exists in libd3pm_hip_ab.so only (include/d3pm_hip_ab.h, D3PM_AB_GEMM_BIG_MODE)
-#ifdef D3PM_ABLATIONS
-int big_gemm_mode() { return ab_knobs().big_mode; }
-#endif
-
-template <typename U, int E, int WM, int WN, int MD>
+template <typename U, int E, int WM, int WN>
 static int big_launch(const LinearArgs& a, int n_tiles, int tiles_total, dim3 grid, size_t lds, hipStream_t s) {
-  const uint16_t* tab = nullptr;
-#ifdef D3PM_ABLATIONS
-  if ((E & EPI_GELU) && std::is_same<U, bf16>::value && WM * WN == 8 && lds + GELU_TAB_BYTES <= 160 * 1024 && gelu_table_enabled()) {
-    tab = gelu_table_device(s);
-    if (tab) lds += GELU_TAB_BYTES;
-  }
-#endif
-  D3PM_LDS_ATTR((&gemm_mfma_big<U, E, WM, WN, MD>), 160 * 1024);
-  gemm_mfma_big<U, E, WM, WN, MD><<<grid, dim3(WM * WN * 64), lds, s>>>(
+  D3PM_LDS_ATTR((&gemm_mfma_big<U, E, WM, WN>), 160 * 1024);
+  gemm_mfma_big<U, E, WM, WN><<<grid, dim3(WM * WN * 64), lds, s>>>(
       static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
       static_cast<const U*>(a.R1), static_cast<const U*>(a.R2), a.ldr, a.row_mask, a.mask_period, a.M, a.N, a.K, n_tiles,
-      tiles_total, tab, RowPanelArgs<U>{}, epi_fold_of(a));
+      tiles_total, RowPanelArgs<U>{}, epi_fold_of(a));
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }
 
-// The folded-LayerNorm epilogues (EPI_LNF / EPI_STATS, d3pm_mfma_tile.h) run on the shipped schedule of each geometry only; for the
-// others the A/B library picks among MODE 0 / 1 / 9 / 2049 (2049: plain epilogue, 192 x 256 only; tests/ab_gemm.py)
 template <typename U, int E>
 static int big_launch_geometry(int id, const LinearArgs& a, int n_tiles, int tiles_total, dim3 grid, size_t lds, hipStream_t s) {
-#ifdef D3PM_ABLATIONS
-  if constexpr ((E & (EPI_LNF | EPI_STATS)) == 0) {
-    const int md = big_gemm_mode();
-    if (md == 2049 && E == 0 && id == 2) return big_launch<U, 0, 2, 4, 2049>(a, n_tiles, tiles_total, grid, lds, s);
-    // deferred stores need a next tile to hide in (more tiles than persistent workgroups) and K >= 8 k-steps
-    if (md == 9 && a.K >= 8 * BK && tiles_total > static_cast<int>(grid.x)) {
-      if (id == 1) return big_launch<U, E, 1, 8, 9>(a, n_tiles, tiles_total, grid, lds, s);
-      if (id == 2) return big_launch<U, E, 2, 4, 9>(a, n_tiles, tiles_total, grid, lds, s);
-      return big_launch<U, E, 2, 2, 9>(a, n_tiles, tiles_total, grid, lds, s);
-    }
-    if ((md & 1) == 0) {
-      if (id == 1) return big_launch<U, E, 1, 8, 0>(a, n_tiles, tiles_total, grid, lds, s);
-      if (id == 2) return big_launch<U, E, 2, 4, 0>(a, n_tiles, tiles_total, grid, lds, s);
-      return big_launch<U, E, 2, 2, 0>(a, n_tiles, tiles_total, grid, lds, s);
-    }
-  }
-#endif
-  if (id == 1) return big_launch<U, E, 1, 8, 1>(a, n_tiles, tiles_total, grid, lds, s);
-  if (id == 2) return big_launch<U, E, 2, 4, 1>(a, n_tiles, tiles_total, grid, lds, s);
-  return big_launch<U, E, 2, 2, 1>(a, n_tiles, tiles_total, grid, lds, s);
+  if (id == 1) return big_launch<U, E, 1, 8>(a, n_tiles, tiles_total, grid, lds, s);
+  if (id == 2) return big_launch<U, E, 2, 4>(a, n_tiles, tiles_total, grid, lds, s);
+  return big_launch<U, E, 2, 2>(a, n_tiles, tiles_total, grid, lds, s);
 }
 
 // Both cross-attention out-projections (ar_discrete.py:138,142: the SAME weights) in one launch of the ordinary big-tile geometry:
@@ -733,12 +619,12 @@ bool big_dual_supported(int dtype, const LinearArgs& a, const void* X2) {
 
 template <typename U, int E, int WM, int WN>
 static int big_dual_launch(const LinearArgs& a, const void* X2, int n_tiles, int tiles_total, dim3 grid, size_t lds, hipStream_t s) {
-  D3PM_LDS_ATTR((&gemm_mfma_big<U, E, WM, WN, 1, FUSE_DUAL>), 160 * 1024);
+  D3PM_LDS_ATTR((&gemm_mfma_big<U, E, WM, WN, FUSE_DUAL>), 160 * 1024);
   RowPanelArgs<U> rp{};
   rp.X2 = static_cast<const U*>(X2);
-  gemm_mfma_big<U, E, WM, WN, 1, FUSE_DUAL><<<grid, dim3(WM * WN * 64), lds, s>>>(
+  gemm_mfma_big<U, E, WM, WN, FUSE_DUAL><<<grid, dim3(WM * WN * 64), lds, s>>>(
       static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
-      static_cast<const U*>(a.R1), nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, n_tiles, tiles_total, nullptr, rp, epi_fold_of(a));
+      static_cast<const U*>(a.R1), nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, n_tiles, tiles_total, rp, epi_fold_of(a));
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }
@@ -831,13 +717,13 @@ static int row_panel_launch(const LinearArgs& a, const RowPanelFuse& f, hipStrea
   const int tiles_total = a.M / 96, want = (tiles_total + 7) & ~7;
   const dim3 grid(static_cast<unsigned>(want < 256 ? want : 256));
   const size_t lds = 2 * static_cast<size_t>(96 + 512) * ROW_BYTES + 2 * 96 * 8 * sizeof(float);
-  D3PM_LDS_ATTR((&gemm_mfma_big<U, E, 1, 8, 1, FUSE>), 160 * 1024);
+  D3PM_LDS_ATTR((&gemm_mfma_big<U, E, 1, 8, FUSE>), 160 * 1024);
   RowPanelArgs<U> rp{static_cast<const U*>(f.X2), static_cast<const U*>(f.lnw), static_cast<const U*>(f.lnb),
                      static_cast<const U*>(f.lnw2), static_cast<const U*>(f.lnb2), static_cast<const U*>(f.film),
                      static_cast<U*>(f.lny), static_cast<U*>(f.lny2), f.eps, static_cast<uint8_t*>(f.sx), static_cast<uint8_t*>(f.sx2)};
-  gemm_mfma_big<U, E, 1, 8, 1, FUSE><<<grid, dim3(512), lds, s>>>(
+  gemm_mfma_big<U, E, 1, 8, FUSE><<<grid, dim3(512), lds, s>>>(
       static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
-      static_cast<const U*>(a.R1), nullptr, a.ldr, a.row_mask, a.mask_period, a.M, a.N, a.K, 1, tiles_total, nullptr, rp, EpiFold{});
+      static_cast<const U*>(a.R1), nullptr, a.ldr, a.row_mask, a.mask_period, a.M, a.N, a.K, 1, tiles_total, rp, EpiFold{});
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

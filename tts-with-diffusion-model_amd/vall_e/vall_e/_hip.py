@@ -23,7 +23,6 @@ K_GEMM, K_ATTN, K_SAMPLE, K_LN, K_GEMM_LN, K_ALL = 0, 1, 2, 3, 4, 5
 _DTYPES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 _LIB_DIR = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "lib"))
 LIB_PATH = os.environ.get("D3PM_HIP_LIB") or os.path.join(_LIB_DIR, "libd3pm_hip.so")
-AB_LIB_PATH = os.path.join(_LIB_DIR, "libd3pm_hip_ab.so")      # the experiment build (include/d3pm_hip_ab.h); tests/ab_*.py only
 
 
 class Tuning(C.Structure):
@@ -399,16 +398,6 @@ SIGNATURES = {
     "d3pm_prof_destroy": (C.c_int, [C.c_void_p]),
 }
 
-# what libd3pm_hip_ab.so exports on top (include/d3pm_hip_ab.h): experiments that were measured and not shipped
-AB_SIGNATURES = {
-    "d3pm_ab_set": (C.c_int, [C.c_int, C.c_int]),
-    "d3pm_op_linear_lnpro": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
-    "d3pm_op_final_sample": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_int, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]),
-}
-AB_GEMM_BIG_MODE, AB_ATTN_ARM, AB_GEMM_RING, AB_GELU_TABLE, AB_LN_PROLOGUE, AB_FUSED_FINAL_SAMPLE = range(6)
-_is_ab = False
 TUNING = Tuning()        # filled by d3pm_tuning_default when the library loads
 TUNING_FIELDS = tuple(n for n, _ in Tuning._fields_ if n != "prof")
 
@@ -433,23 +422,6 @@ def lib():
         _lib = _load(LIB_PATH, SIGNATURES)
         _lib.d3pm_tuning_default(C.byref(TUNING))
     return _lib
-
-
-def use_ab_library():
-    """A/B scripts only (tests/ab_*.py): route this module to libd3pm_hip_ab.so -- the same sources built with
-    -DD3PM_ABLATIONS (__graft_entry__.build_ab()) -- which also carries the experiments of include/d3pm_hip_ab.h."""
-    global _lib, _is_ab
-    _lib = _load(AB_LIB_PATH, {**SIGNATURES, **AB_SIGNATURES})
-    _lib.d3pm_tuning_default(C.byref(TUNING))
-    _is_ab = True
-    return _lib
-
-
-def _ab_set(knob: int, value: int):
-    if not _is_ab:
-        raise D3PMError("this knob belongs to an experiment that lives in libd3pm_hip_ab.so only: call _hip.use_ab_library() "
-                        "(tests/ab_*.py); the product library has no such path")
-    check(lib().d3pm_ab_set(knob, int(value)), "d3pm_ab_set")
 
 
 class D3PMError(RuntimeError):
@@ -827,19 +799,6 @@ class Sampler:
                                           _p(x_next), int(t), C.byref(self.schedule.c_struct), seed, utt0, flags,
                                           _p(post), stream_ptr()), "d3pm_posterior_sample")
         return x_next, post
-
-    def final_sample(self, hidden, x_t, t, seed, utt0=0, flags=0):
-        """hidden [B, canvas, d] (masked) -> x_{t-1} int32 [B, canvas] through the fused final + sampler kernel."""
-        cfg = self.cfg
-        B = self._check_grid(x_t)
-        _require(hidden, "hidden", (B, cfg.canvas, cfg.d_model), (self.dtype,), self.device)
-        x_next = torch.empty_like(x_t)
-        if not _is_ab:
-            raise D3PMError("the fused final + sampler kernel is an experiment of libd3pm_hip_ab.so (use_ab_library())")
-        check(lib().d3pm_op_final_sample(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(hidden), _p(x_t), _p(x_next),
-                                         int(t), C.byref(self.schedule.c_struct), seed, utt0, flags, stream_ptr()),
-              "d3pm_op_final_sample")
-        return x_next
 
     def sample_loop(self, x, frame_mask, t_start, t_stop, kv_t, kv_p, seed, utt0=0, flags=0, trace=False, slot=0,
                     fp8=False, known=None, temperature=1.0, top_k=0, top_p=1.0, keys=None, guidance=0.0):
@@ -1241,21 +1200,6 @@ def op_layernorm(x, w, b, film=None, eps=1e-6):
     return y
 
 
-def op_linear_lnpro(x, w, bias, ln_w, ln_b, *, ln2_w=None, ln2_b=None, film=None, act=0, eps=1e-6):
-    """act(LN(x) @ w.T + bias) in one launch of the latency GEMM; x [m, 512] is the un-normalised stream.  With a second
-    LayerNorm the result has 2 m rows (x under ln, then x under ln2)."""
-    m = x.shape[0]
-    if not (x.shape[1] == 512 and w.shape[1] == 512 and x.is_contiguous() and w.is_contiguous()):
-        raise ValueError("op_linear_lnpro: x [m,512], w [N,512], contiguous")
-    M, N = (2 * m if ln2_w is not None else m), w.shape[0]
-    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    if not _is_ab:
-        raise D3PMError("the LayerNorm-prologue GEMM is an experiment of libd3pm_hip_ab.so (use_ab_library())")
-    check(lib().d3pm_op_linear_lnpro(dtype_code(x.dtype), _p(x), _p(w), _p(bias), _p(y), M, N, act, _p(ln_w), _p(ln_b), _p(ln2_w),
-                                     _p(ln2_b), _p(film), eps, stream_ptr()), "d3pm_op_linear_lnpro")
-    return y
-
-
 def op_linear_rowpanel(x, w, bias, r1, ln_w, ln_b, *, x2=None, ln2_w=None, ln2_b=None, film=None, row_mask=None, eps=1e-6, mx=False):
     """Projection onto the residual stream + the LayerNorm(s) of the new rows in one launch (include/d3pm_hip.h).
     Returns (y, ln_y, ln2_y | None); with mx=True the LayerNorm rows come back in the block-scaled fp8 format:
@@ -1343,7 +1287,7 @@ def set_gemm_variant(v: int):
 
 
 def set_attn_query_groups(v: int):
-    if v not in (0, 1, 2, 4, 32, 33) and not (v == 35 and _is_ab):      # 35: A/B library only (192-query workgroups)
+    if v not in (0, 1, 2, 4, 32, 33):
         raise D3PMError(f"attn_query_groups {v}: not a shipped schedule (include/d3pm_hip.h)")
     lib()
     TUNING.attn_query_groups = v
@@ -1394,7 +1338,7 @@ def tuning(**fields):
         if name not in TUNING_FIELDS:
             raise D3PMError(f"unknown tuning field {name!r}: one of {TUNING_FIELDS}")
         ok = _TUNING_VALUES.get(name)
-        if ok is not None and int(value) not in ok and not (_is_ab and name == "attn_query_groups" and int(value) == 35):
+        if ok is not None and int(value) not in ok:
             raise D3PMError(f"{name} = {value}: not a shipped schedule (include/d3pm_hip.h)")
     saved = {name: getattr(TUNING, name) for name in fields}
     try:
@@ -1420,31 +1364,6 @@ def set_tuning_field(name: str, value: int):
         raise D3PMError(f"unknown tuning field {name!r}: one of {TUNING_FIELDS}")
     lib()
     setattr(TUNING, name, int(value))
-
-
-# ---- experiments (libd3pm_hip_ab.so only) ------------------------------------------------------------------------------------
-def set_ln_prologue(v: bool):
-    _ab_set(AB_LN_PROLOGUE, 1 if v else 0)
-
-
-def set_gelu_table(v: bool):
-    _ab_set(AB_GELU_TABLE, 1 if v else 0)
-
-
-def set_fused_final_sample(v: bool):
-    _ab_set(AB_FUSED_FINAL_SAMPLE, 1 if v else 0)
-
-
-def set_gemm_big_mode(v: int):
-    _ab_set(AB_GEMM_BIG_MODE, v)
-
-
-def set_attn_arm(v: int):
-    _ab_set(AB_ATTN_ARM, v)
-
-
-def set_gemm_ring(v: bool):
-    _ab_set(AB_GEMM_RING, 1 if v else 0)
 
 
 # ---- timing hooks: a d3pm_prof handle attached to the default Tuning ------------------------------------------------------
