@@ -59,7 +59,9 @@ extern "C" {
  *    (d3pm_reveal, d3pm_reveal_plan, d3pm_reveal_step, d3pm_reveal_loop); the per-utterance key mask at kernel level
  *    (d3pm_op_attention_keylen); key-padding masks through the denoiser (d3pm_keys, d3pm_encode_conditions_keys,
  *    d3pm_denoise_step_keys, d3pm_sample_loop_keys, d3pm_reveal_loop_keys, d3pm_op_attention_pair_keylen); classifier-free guidance
- *    inside the sampler launch (d3pm_guidance, d3pm_posterior_sample_guided, d3pm_sample_loop_guided) */
+ *    inside the sampler launch (d3pm_guidance, d3pm_posterior_sample_guided, d3pm_sample_loop_guided); block-0 QKV from a per-id
+ *    table (d3pm_op_embed_qkv_bytes, d3pm_op_embed_qkv; ln_fold value 2; d3pm_workspace_bytes grew by the table and one
+ *    [rows][d_model] region for 16-bit models with d_model a multiple of 256 and n_q <= 1) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -143,6 +145,14 @@ enum {
  *                      epilogue from row moments the producing projection left behind (d3pm_fold_block): no LayerNorm launch and
  *                      no row-panel launch in a block (one small launch per evaluation rebuilds fc1's FiLM-folded weights for
  *                      the timestep); 0 = the stand-alone / row-panel LayerNorm launches (the eager rounding points).  Ignored (= 0) for fp32 models, D3PM_FLAG_FORCE_GENERIC and the fp8 entry points.
+ *                      With 1 the unguided sampler loops (d3pm_sample_loop and its _canvas / _sampling / _nucleus / _keys forms, n_q <= 1,
+ *                      two iterations or more) also take the QKV rows of the FIRST block from a table: that projection reads
+ *                      resps_emb[id] (zeros on a padded frame) under norm1 and nothing else, so it has n_classes + 1 distinct rows;
+ *                      the loop computes them once per call with the folded projection itself and the launch that embeds a row
+ *                      (the sampler launch of the previous iteration) copies its 3 d_model values.  One projection over all rows
+ *                      less per iteration, same bits.  2 = the fold without the table: every block projects its QKV rows (the
+ *                      guided loop, the reveal loop and d3pm_denoise_step do so under 1 as well).  1 and 2 give identical results;
+ *                      d3pm_workspace_bytes is the same for every value.
  *   prof               optional timing hooks (d3pm_prof_create below), NULL = none. */
 struct d3pm_prof;
 typedef struct d3pm_tuning {
@@ -755,6 +765,15 @@ int d3pm_op_linear_stats(int dtype, const void *X, int ldx, const void *W, const
 int d3pm_op_linear_fold(int dtype, const void *X, int ldx, const void *Wf, const float *fold_s, const float *fold_b,
                         const float *stats_in, float eps, void *Y, int ldy, int M, int N, int K, int act, const d3pm_tuning *tuning,
                         void *stream);
+/* The block-0 QKV rows of `n` token ids as the sampler loop makes them under ln_fold = 1 (tests): builds the table [rows][3 d_model]
+ * (row id = the folded QKV projection of resps_emb[id] with that row's moments, row n_classes = that of a zero row) in `storage`
+ * (device, 256-byte aligned, >= d3pm_op_embed_qkv_bytes(shape, n)), then q_out[r] [n][d_model] | kv_out[r] [n][2 d_model] = the q and
+ * the k | v columns of row (frame_mask[r] ? tokens[r] clamped to the classes : n_classes), as the loop keeps them.  weights->fold
+ * must be set; 16-bit dtype, d_model a multiple of 256, n_q <= 1.  q | k | v of a row equal d3pm_op_linear_fold on the gathered
+ * embedding rows with their d3pm_op_row_stats moments, bit for bit. */
+size_t d3pm_op_embed_qkv_bytes(const d3pm_shape *shape, int n);
+int d3pm_op_embed_qkv(const d3pm_shape *shape, const d3pm_weights *weights, const int32_t *tokens, const uint8_t *frame_mask, int n,
+                      void *storage, size_t storage_bytes, void *q_out, void *kv_out, void *stream);
 /* One projection's tables as d3pm_fold_build makes them (tests): W [N][K], bias [N] or NULL, gamma / beta [K], film NULL or
  * (scale [K] | shift [K]) -> Wf [N][K], fold_s / fold_b [N]. */
 int d3pm_op_fold_weights(int dtype, const void *W, const void *bias, const void *gamma, const void *beta, const void *film, int N, int K,

@@ -124,6 +124,10 @@ struct Workspace {
   float* stats;       // [n][d / 32][2] row moments of the residual stream (LayerNorm folded into the projections, d3pm_mfma_tile.h)
   char* fc1f;         // [L][4d][d] fc1 under norm3 + FiLM(t), rebuilt per evaluation (d3pm_fold.hip); then fp32 [L][4d] s and b'
   float *fc1f_s, *fc1f_b;
+  // block-0 QKV from a per-id table (build_qkv_table; folded path, n_q = 1): the table's input rows [qkv_table_rows][d], their moments
+  // (parts), the table [qkv_table_rows][3d], and the q rows [n][d] and k | v rows [n][2d] of block 0 of the next evaluation
+  char *tab_x, *tab_qkv, *q0, *kv0;
+  float* tab_stats;
   uint8_t* mxs;       // fp8 fast path: block scales [2n][d / 32] of the LayerNorm rows (a slot of their own: nothing else ever lives here)
   size_t total;
 };
@@ -165,6 +169,18 @@ static Workspace carve(const d3pm_shape& sh, int batch, char* base) {
     w.fc1f = take(L * 4 * d * d * es);
     w.fc1f_s = reinterpret_cast<float*>(take(L * 4 * d * sizeof(float)));
     w.fc1f_b = reinterpret_cast<float*>(take(L * 4 * d * sizeof(float)));
+    if (levels(sh) == 1) {      // whatever d3pm_tuning.ln_fold says: a caller never has to know
+      const size_t mt = qkv_table_rows(sh.n_classes);
+      w.tab_x = take(mt * d * es);
+      w.tab_stats = reinterpret_cast<float*>(take(mt * (d / 32) * 2 * sizeof(float)));
+      w.tab_qkv = take(mt * 3 * d * es);
+      // The sampler launch writes these rows while it reads the logits, which alias ws.qkv: q takes a region of its own, k | v
+      // the adjacent h | h2 -- the folded sequence writes no LayerNorm output, so nothing lives there between the last block of
+      // an evaluation and the first out-projection of the next (h: o_text of the two-launch cross-attention output; h2 = att2 under
+      // workspace_alias: the prompt cross-attention output, both dead behind their block)
+      w.q0 = take(n * d * es);
+      w.kv0 = w.h;
+    }
   }
   w.total = off;
   return w;
@@ -298,6 +314,9 @@ struct DenoiserArgs {      // what every block of one evaluation sees
   // classifier-free guidance (d3pm_sample_loop_guided): x_t holds token_rows = batch / 2 * canvas rows and rows token_rows .. of the
   // evaluation (the null twins) read the same ids; 0 = x_t has a row per row of the evaluation
   int token_rows = 0;
+  // the block-0 QKV table of the call (ws.tab_qkv once build_qkv_table has filled it) or null: with it, an embedding launch of the
+  // evaluation also gathers ws.q0 | ws.kv0
+  const void* qkv_table = nullptr;
 };
 // the token embedding of an evaluation whose two halves read the same x_t (token_rows > 0): the gather, once per half
 static int embed_twins(const DenoiserArgs& q, const int32_t* x_t, hipStream_t s) {
@@ -315,8 +334,10 @@ static int embed_twins(const DenoiserArgs& q, const int32_t* x_t, hipStream_t s)
 //   fc1 + GELU <- x [norm3 + FiLM(t) folded], fc2 + x, frame mask (+ moments) }: ten launches per block, none of them a LayerNorm.
 // The launches of block l, written ONCE and handed to a visitor in order: FoldPlanner asks whether and on which tiles they would run,
 // FoldLauncher enqueues them.  Every LinearArgs that reads or writes ws.stats is constructed here and nowhere else.
+// qkv_ready (block 0 only): ws.q0 | ws.kv0 already hold the q and k | v rows of ALL rows of this evaluation (gathered from the
+// block-0 QKV table by the launch that embedded them), so the QKV projection is skipped and the self-attention reads them there.
 template <class Visitor>
-static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v) {
+static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v, bool qkv_ready = false) {
   const d3pm_shape& sh = q.sh;
   const Workspace& ws = q.ws;
   const int dt = sh.dtype, d = sh.d_model, H = sh.n_heads, hd = d / H, T = sh.canvas, n = q.batch * T;
@@ -331,8 +352,11 @@ static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v) {
     return with_moments_out(with_residual(projection(X, W, bias, ws.x, n, d, K), ws.x, R2), ws.stats, quads);
   };
   // ---- self-attention ----
-  D3PM_TRY(consumer(f.qkv_w, f.qkv_s, f.qkv_b, ws.qkv, 3 * d, ACT_NONE));
-  D3PM_TRY(v.attention(with_frame_keys(self_attention(ws.qkv, ws.att, q.batch, T, H, hd, es), q.keys)));
+  const bool from_table = l == 0 && qkv_ready;
+  if (!from_table) D3PM_TRY(consumer(f.qkv_w, f.qkv_s, f.qkv_b, ws.qkv, 3 * d, ACT_NONE));
+  AttnArgs sa = self_attention(ws.qkv, ws.att, q.batch, T, H, hd, es);
+  if (from_table) { sa.Q = ws.q0; sa.ldq = d; sa.K = ws.kv0; sa.V = at(ws.kv0, d, es); sa.ldkv = 2 * d; }
+  D3PM_TRY(v.attention(with_frame_keys(sa, q.keys)));
   D3PM_TRY(v.linear(producer(ws.att, d, b.attn_out_w, b.attn_out_b)));
   // ---- cross-attention: q_text | q_prompt are the two halves of ONE [n][2d] projection of x (the same q rows under norm2 / norm22)
   D3PM_TRY(consumer(f.q2_w, f.q2_s, f.q2_b, ws.qkv, 2 * d, ACT_NONE));
@@ -398,8 +422,22 @@ static int fold_plan(const DenoiserArgs& q, uint32_t flags, const d3pm_fp8_block
   return plan.big ? FOLD_QUADS : FOLD_PARTS;
 }
 
+// qkv_ready: with `prepared`, whether the launch that prepared this evaluation also gathered ws.q0 | ws.kv0 for all of its rows
+// The block-0 QKV table of a reverse process.  Block 0 reads x[row] = resps_emb[id] (zeros on a padded frame): no positional term, no
+// time term and no FiLM enters before norm1, so its QKV projection takes at most n_classes + 1 distinct values, which depend on the
+// weights alone.  They are computed once per call -- the folded projection itself over the n_classes embedding rows and the zero row,
+// whose inputs embed_row_stats writes as it does for canvas rows, so the bits are those of the launch this replaces (every GEMM family
+// accumulates in the same order, d3pm_mfma_gemm.hip; the moments travel as parts, which every family reads) -- and the launches that
+// embed a row copy its 3d values into ws.q0 | ws.kv0 instead of the loop projecting all rows again at every iteration.
+static int build_qkv_table(const Ctx& cx, const d3pm_shape& sh, const d3pm_weights& w, const Workspace& ws, hipStream_t s) {
+  const int dt = sh.dtype, d = sh.d_model, mt = qkv_table_rows(sh.n_classes);
+  D3PM_TRY(qkv_table_rows_launch(dt, w.resps_emb, ws.tab_x, ws.tab_stats, mt, d, sh.n_classes, s));
+  const d3pm_fold_block& f = w.fold[0];
+  return run_linear(cx, dt, folded_projection(ws.tab_x, f.qkv_w, f.qkv_s, f.qkv_b, ws.tab_stats, false, ws.tab_qkv, mt, 3 * d, d, ACT_NONE), 0, s);
+}
+
 static int denoiser_blocks_folded(const DenoiserArgs& q, const int32_t* x_t, int t, const void* film, int layers, hipStream_t s, bool prepared,
-                                  bool quads) {
+                                  bool quads, bool qkv_ready) {
   const d3pm_shape& sh = q.sh;
   const int dt = sh.dtype, d = sh.d_model, n = q.batch * sh.canvas;
   const Ctx cx(sh.tuning);
@@ -407,11 +445,15 @@ static int denoiser_blocks_folded(const DenoiserArgs& q, const int32_t* x_t, int
   if (!prepared) {      // (inside the loop the previous iteration's sampler launch has done both: posterior_sample_prep)
     {
       ProfScope p(cx, D3PM_K_LN, s, 0.0, es * static_cast<double>(n) * d * 2.0);
+      qkv_ready = false;
       if (q.token_rows) {      // the first evaluation of a guided loop: both halves from the same ids, then the moments of all rows (same bits)
         D3PM_TRY(embed_twins(q, x_t, s));
         D3PM_TRY(row_stats_launch(dt, q.ws.x, d, n, d, q.ws.stats, s, quads));
       } else {
-        D3PM_TRY(embed_tokens_stats(dt, embed_args(sh, q.w, q.batch, x_t, q.frame_mask, q.mask_period, q.ws.x), q.ws.stats, quads, s));
+        EmbedArgs e = embed_args(sh, q.w, q.batch, x_t, q.frame_mask, q.mask_period, q.ws.x);
+        if (q.qkv_table && e.n_q == 1 && q.ws.q0) { e.qkv_table = q.qkv_table; e.q0 = q.ws.q0; e.kv0 = q.ws.kv0; }
+        D3PM_TRY(embed_tokens_stats(dt, e, q.ws.stats, quads, s));
+        qkv_ready = e.q0 != nullptr;
       }
     }
     {   // fc1 of every block under norm3 + FiLM(t): the weights this evaluation's fc1 launches read
@@ -421,17 +463,17 @@ static int denoiser_blocks_folded(const DenoiserArgs& q, const int32_t* x_t, int
     }
   }
   FoldLauncher launch{cx, dt, s};
-  for (int l = 0; l < layers; ++l) D3PM_TRY(folded_block(q, l, quads, launch));
+  for (int l = 0; l < layers; ++l) D3PM_TRY(folded_block(q, l, quads, launch, qkv_ready));
   return D3PM_OK;
 }
 
 // One denoiser evaluation up to the final projection: the hidden state after `layers` blocks is left in ws.x.  `plan` is the caller's
 // fold_plan(): FOLD_NONE runs the LayerNorm / row-panel launches below (and the fp8 fast path, BASELINE.json configs[4]).
 static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, const void* film, int layers, uint32_t flags, hipStream_t s,
-                           const d3pm_fp8_block_weights* f8, int plan, bool prepared = false) {
+                           const d3pm_fp8_block_weights* f8, int plan, bool prepared = false, bool qkv_ready = false) {
   // LayerNorm folded into the projections (d3pm_tuning.ln_fold, d3pm_fold_block): every LayerNorm-fed projection reads the raw
   // residual stream and normalises in its epilogue; every projection that lands on the residual stream leaves the row moments
-  if (plan != FOLD_NONE) return denoiser_blocks_folded(q, x_t, t, film, layers, s, prepared, plan == FOLD_QUADS);
+  if (plan != FOLD_NONE) return denoiser_blocks_folded(q, x_t, t, film, layers, s, prepared, plan == FOLD_QUADS, prepared && qkv_ready);
 
   const d3pm_shape& sh = q.sh;
   const d3pm_weights& w = q.w;
@@ -732,6 +774,41 @@ int d3pm_op_linear_fold(int dtype, const void* X, int ldx, const void* Wf, const
   return mfma_linear(dtype, g, static_cast<hipStream_t>(stream));
 }
 
+size_t d3pm_op_embed_qkv_bytes(const d3pm_shape* sh, int n) {
+  if (check_shape(sh, 1) != D3PM_OK || n < 1 || !fold_shape_ok(sh->dtype, sh->d_model) || levels(*sh) != 1) return 0;
+  const size_t es = dtype_size(sh->dtype), d = sh->d_model, mt = qkv_table_rows(sh->n_classes), rows = (static_cast<size_t>(n) + 15) & ~static_cast<size_t>(15);
+  return align256(mt * d * es) + align256(mt * (d / 32) * 2 * sizeof(float)) + align256(mt * 3 * d * es) + align256(rows * d * es) +
+         align256(rows * (d / 32) * 2 * sizeof(float));
+}
+
+int d3pm_op_embed_qkv(const d3pm_shape* sh, const d3pm_weights* w, const int32_t* tokens, const uint8_t* frame_mask, int n, void* storage,
+                      size_t storage_bytes, void* q_out, void* kv_out, void* stream) {
+  D3PM_TRY(check_shape(sh, 1));
+  D3PM_REQUIRE(w && w->resps_emb && w->fold && tokens && frame_mask && storage && q_out && kv_out && n > 0, D3PM_E_ARG, "d3pm_op_embed_qkv: null pointer");
+  D3PM_REQUIRE(fold_shape_ok(sh->dtype, sh->d_model) && levels(*sh) == 1, D3PM_E_SHAPE,
+               "d3pm_op_embed_qkv: needs a 16-bit dtype, d_model a multiple of 256 and n_q <= 1");
+  const size_t need = d3pm_op_embed_qkv_bytes(sh, n);
+  D3PM_REQUIRE(storage_bytes >= need, D3PM_E_WORKSPACE, "d3pm_op_embed_qkv: storage %zu < required %zu", storage_bytes, need);
+  D3PM_REQUIRE(reinterpret_cast<uintptr_t>(storage) % 256 == 0 && reinterpret_cast<uintptr_t>(q_out) % 16 == 0 &&
+                   reinterpret_cast<uintptr_t>(kv_out) % 16 == 0,
+               D3PM_E_ARG, "d3pm_op_embed_qkv: storage must be 256-byte aligned, q_out and kv_out 16-byte aligned");
+  const size_t es = dtype_size(sh->dtype), d = sh->d_model, mt = qkv_table_rows(sh->n_classes), rows = (static_cast<size_t>(n) + 15) & ~static_cast<size_t>(15);
+  Workspace ws{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char* p = static_cast<char*>(storage) + off; off += align256(bytes); return p; };
+  ws.tab_x = take(mt * d * es);
+  ws.tab_stats = reinterpret_cast<float*>(take(mt * (d / 32) * 2 * sizeof(float)));
+  ws.tab_qkv = take(mt * 3 * d * es);
+  ws.x = take(rows * d * es);
+  ws.stats = reinterpret_cast<float*>(take(rows * (d / 32) * 2 * sizeof(float)));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  D3PM_TRY(build_qkv_table(Ctx(sh->tuning), *sh, *w, ws, s));
+  EmbedArgs e;
+  e.tokens = tokens; e.frame_mask = frame_mask; e.mask_period = n; e.table = w->resps_emb; e.Y = ws.x; e.M = n; e.d = sh->d_model;
+  e.n_classes = sh->n_classes; e.qkv_table = ws.tab_qkv; e.q0 = q_out; e.kv0 = kv_out;
+  return embed_tokens_stats(sh->dtype, e, ws.stats, false, s);
+}
+
 int d3pm_cond_kv(const d3pm_shape* sh, const d3pm_weights* w, int batch, const void* cond_text, const void* cond_prompt,
                  void* kv_text, void* kv_prompt, void* stream) {
   D3PM_TRY(check_shape(sh, batch));
@@ -1018,13 +1095,21 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rows = batch * sh->canvas;
   const Ctx cx(sh->tuning);
-  const DenoiserArgs q{*sh, *w, eval_batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, keys, guide ? rows : 0};
+  DenoiserArgs q{*sh, *w, eval_batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, keys, guide ? rows : 0};
   const int plan = fold_plan(q, flags, f8);      // the same for every iteration: the blocks and the sampler's prep share it
+  // Block-0 QKV from the per-id table (build_qkv_table; ln_fold = 2 keeps the projection): every unguided loop -- plain, canvas / known
+  // frames, keys, sampling / nucleus, trace -- once it runs two iterations.  The GUIDED loop keeps the projection: its first evaluation
+  // embeds through embed_twins and its sampler launch (posterior_sample_prep_guided) does not gather.
+  if (plan != FOLD_NONE && tune_of(sh->tuning).ln_fold != 2 && levels(*sh) == 1 && !guide && t_start - t_stop >= 2 && ws.tab_qkv) {
+    D3PM_TRY(build_qkv_table(cx, *sh, *w, ws, s));
+    q.qkv_table = ws.tab_qkv;
+  }
   bool prepared = false;      // the previous iteration's sampler launch has already embedded x_t and folded fc1 for this t
+  bool qkv_ready = false;     // ... and gathered ws.q0 | ws.kv0 for every row of this evaluation
   for (int t = t_start; t > t_stop; --t) {
     if (cx.prof) cx.prof->sample_now = (t % cx.prof->stride) == 0;
-    D3PM_TRY(denoiser_blocks(q, x, t, film, sh->n_layers, flags, s, f8, plan, prepared));
-    prepared = false;
+    D3PM_TRY(denoiser_blocks(q, x, t, film, sh->n_layers, flags, s, f8, plan, prepared, qkv_ready));
+    prepared = qkv_ready = false;
     SampleArgs a;
     a.logits = ws.logits; a.logits_dtype = sh->dtype; a.ldl = logits_ld(*sh); a.x_t = x; a.x_next = x;
     a.x_next2 = trace ? trace + static_cast<size_t>(t_start - t) * rows * levels(*sh) : nullptr;
@@ -1037,21 +1122,26 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     if (guide) { a.guided = true; a.guidance = guide->weight; }
     {
       D3PM_TRY(final_logits(*sh, *w, eval_batch, ws, ws.logits, logits_ld(*sh), flags, s));
+      const bool preps = t - 1 > t_stop && plan != FOLD_NONE;
+      // (+ the block-0 q | k | v rows the launch stores for the next evaluation; their source, the table, stays in L2)
       ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0,
-                  static_cast<double>(rows) * levels(*sh) * ((guide ? 2.0 : 1.0) * sh->n_classes * dtype_size(sh->dtype) + 8.0));
+                  static_cast<double>(rows) * levels(*sh) * ((guide ? 2.0 : 1.0) * sh->n_classes * dtype_size(sh->dtype) + 8.0) +
+                      (preps && q.qkv_table ? static_cast<double>(rows) * 3.0 * sh->d_model * dtype_size(sh->dtype) : 0.0));
       NextIterPrep nx;
-      if (t - 1 > t_stop && plan != FOLD_NONE) {
+      if (preps) {
         const size_t es = dtype_size(sh->dtype);
         nx.dtype = sh->dtype; nx.table = w->resps_emb; nx.x = ws.x; nx.stats = ws.stats; nx.frame_mask = cm.frame_mask; nx.mask_period = cm.period; nx.d = sh->d_model;
         nx.quads = plan == FOLD_QUADS;
         nx.blocks = w->blocks; nx.n_layers = sh->n_layers;
         nx.film_t = at(film, static_cast<size_t>(t - 1) * sh->n_layers * 2 * sh->d_model, es);
         nx.Wf = ws.fc1f; nx.s_out = ws.fc1f_s; nx.b_out = ws.fc1f_b;
+        if (q.qkv_table) { nx.qkv_table = q.qkv_table; nx.q0 = ws.q0; nx.kv0 = ws.kv0; }      // (never under guidance)
       }
       if (nx.table && posterior_sample_prep_supported(a, nx)) {
         // + the embedding rows, their moments and the fc1 fold of iteration t - 1 (guided: the rows of both halves)
         D3PM_TRY(guide ? posterior_sample_prep_guided(a, nx, s) : posterior_sample_prep(a, nx, s));
         prepared = true;
+        qkv_ready = nx.q0 != nullptr;
       } else {
         D3PM_TRY(guide ? posterior_sample_guided(a, s) : posterior_sample(a, s));
       }
@@ -1261,6 +1351,7 @@ static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   const Ctx cx(sh->tuning);
   const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, keys};
   const int plan = fold_plan(q, flags, nullptr);
+  // (The reveal loop keeps the block-0 QKV projection: reveal_commit_prep does not gather from the table of sample_loop_impl.)
   bool prepared = false;
   int32_t* cur = x;      // where x_t of the step lives: the fused launch cannot store in place, so it alternates between x and x_alt
   for (int i = 0; i < N; ++i) {

@@ -88,11 +88,22 @@ __global__ __launch_bounds__(256) void row_stats(const T* __restrict__ x, int ld
 template <typename T>
 __global__ __launch_bounds__(256) void embed_rows_stats(const int32_t* __restrict__ tok, const uint8_t* __restrict__ frame_mask,
                                                         int mask_period, const T* __restrict__ table, T* __restrict__ y, int M, int d,
-                                                        int n_classes, float* __restrict__ stats, bool quads) {
+                                                        int n_classes, float* __restrict__ stats, bool quads,
+                                                        const T* __restrict__ qkv_table, T* __restrict__ q0, T* __restrict__ kv0) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + wave;
   if (row >= M) return;
-  embed_row_stats<T>(table, tok[row], frame_mask[row % mask_period] != 0, y, row, d, n_classes, stats, quads, lane);
+  embed_row_stats<T>(table, tok[row], frame_mask[row % mask_period] != 0, y, row, d, n_classes, stats, quads, lane, qkv_table, q0, kv0);
+}
+
+// the inputs of the block-0 QKV table: row r = what embed_row_stats leaves for id r (a padded frame's zero row from n_classes on)
+template <typename T>
+__global__ __launch_bounds__(256) void qkv_table_input_rows(const T* __restrict__ table, T* __restrict__ x, int rows, int d, int n_classes,
+                                                            float* __restrict__ stats) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  embed_row_stats<T>(table, row, row < n_classes, x, row, d, n_classes, stats, false, lane);
 }
 
 }  // namespace
@@ -151,6 +162,7 @@ int row_stats_launch(int dtype, const void* x, int ldx, int M, int d, float* sta
 
 int embed_tokens_stats(int dtype, const EmbedArgs& a, float* stats, bool quads, hipStream_t s) {
   if (quads && a.d != 512) return D3PM_E_SHAPE;
+  if ((a.qkv_table != nullptr) != (a.q0 != nullptr) || (a.q0 != nullptr) != (a.kv0 != nullptr) || (a.qkv_table && a.n_q > 1)) return D3PM_E_ARG;
   if (a.n_q > 1) {                 // level-summed rows (extension): the generic gather, then the moments of the rows it wrote
     int rc = embed_tokens(dtype, a, s);
     return rc != D3PM_OK ? rc : row_stats_launch(dtype, a.Y, a.d, a.M, a.d, stats, s, quads);
@@ -158,10 +170,22 @@ int embed_tokens_stats(int dtype, const EmbedArgs& a, float* stats, bool quads, 
   const dim3 grid(static_cast<unsigned>((a.M + 3) / 4)), block(256);
   if (dtype == D3PM_F16)
     embed_rows_stats<f16><<<grid, block, 0, s>>>(a.tokens, a.frame_mask, a.mask_period, static_cast<const f16*>(a.table), static_cast<f16*>(a.Y),
-                                                 a.M, a.d, a.n_classes, stats, quads);
+                                                 a.M, a.d, a.n_classes, stats, quads, static_cast<const f16*>(a.qkv_table), static_cast<f16*>(a.q0),
+                                                 static_cast<f16*>(a.kv0));
   else
     embed_rows_stats<bf16><<<grid, block, 0, s>>>(a.tokens, a.frame_mask, a.mask_period, static_cast<const bf16*>(a.table),
-                                                  static_cast<bf16*>(a.Y), a.M, a.d, a.n_classes, stats, quads);
+                                                  static_cast<bf16*>(a.Y), a.M, a.d, a.n_classes, stats, quads,
+                                                  static_cast<const bf16*>(a.qkv_table), static_cast<bf16*>(a.q0), static_cast<bf16*>(a.kv0));
+  D3PM_LAUNCH_CHECK();
+  return D3PM_OK;
+}
+
+int qkv_table_rows_launch(int dtype, const void* table, void* x, float* stats, int rows, int d, int n_classes, hipStream_t s) {
+  const dim3 grid(static_cast<unsigned>((rows + 3) / 4)), block(256);
+  if (dtype == D3PM_F16)
+    qkv_table_input_rows<f16><<<grid, block, 0, s>>>(static_cast<const f16*>(table), static_cast<f16*>(x), rows, d, n_classes, stats);
+  else
+    qkv_table_input_rows<bf16><<<grid, block, 0, s>>>(static_cast<const bf16*>(table), static_cast<bf16*>(x), rows, d, n_classes, stats);
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

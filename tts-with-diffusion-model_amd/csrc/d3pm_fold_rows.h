@@ -84,10 +84,15 @@ __device__ __forceinline__ void store_row_moments(float a, float q, float* __res
   }
 }
 
-// one wave, one canvas row: x[row] = table[id] (zeros on a padded frame), and the row's moments (embed_rows_vec + row_stats)
+// one wave, one canvas row: x[row] = table[id] (zeros on a padded frame), and the row's moments (embed_rows_vec + row_stats).
+// With (qkv_table, q0, kv0) -- all or none, the same for every wave of the launch -- also the row's block-0 QKV projection, copied
+// from row `live ? id : n_classes` of the table [.][3d] (d3pm_kernels.h qkv_table_rows): q0[row] [.][d] = its q columns, kv0[row]
+// [.][2d] = its k | v columns.  No positional or time term enters before norm1 of block 0, so that projection is a function of the
+// id alone.
 template <typename T>
 __device__ __forceinline__ void embed_row_stats(const T* __restrict__ table, int id, bool live, T* __restrict__ y, int row, int d, int n_classes,
-                                                float* __restrict__ stats, bool quads, int lane) {
+                                                float* __restrict__ stats, bool quads, int lane, const T* __restrict__ qkv_table = nullptr,
+                                                T* __restrict__ q0 = nullptr, T* __restrict__ kv0 = nullptr) {
   id = id < 0 ? 0 : (id >= n_classes ? n_classes - 1 : id);
   const Vec8<T>* src = reinterpret_cast<const Vec8<T>*>(table + static_cast<size_t>(id) * d);
   Vec8<T>* dst = reinterpret_cast<Vec8<T>*>(y + static_cast<size_t>(row) * d);
@@ -98,6 +103,16 @@ __device__ __forceinline__ void embed_row_stats(const T* __restrict__ table, int
     float a, q;
     part_moments(raw, a, q);
     store_row_moments(a, q, stats, row, c, d, quads, lane);
+  }
+  if (qkv_table) {      // wave-uniform
+    const Vec8<T>* ts = reinterpret_cast<const Vec8<T>*>(qkv_table + static_cast<size_t>(live ? id : n_classes) * 3 * d);
+    Vec8<T>* tq = reinterpret_cast<Vec8<T>*>(q0 + static_cast<size_t>(row) * d);
+    Vec8<T>* tkv = reinterpret_cast<Vec8<T>*>(kv0 + static_cast<size_t>(row) * 2 * d);
+    const int qc = d >> 3;
+    for (int c = lane; c < 3 * qc; c += kWave) {
+      const Vec8<T> v = ts[c];
+      if (c < qc) tq[c] = v; else tkv[c - qc] = v;
+    }
   }
 }
 

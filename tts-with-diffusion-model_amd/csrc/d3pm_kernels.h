@@ -115,7 +115,13 @@ struct EmbedArgs {
   const int32_t* tokens = nullptr; const uint8_t* frame_mask = nullptr; int mask_period = 0;      // frame_mask[row % mask_period]
   const void* table = nullptr; void* Y = nullptr; int M = 0, d = 0, n_classes = 0;
   int n_q = 1;      // > 1: tokens [M][n_q], table [n_q][n_classes][d], row = rn(sum over the levels) (d3pm_shape.n_q)
+  // embed_tokens_stats, n_q = 1 only: all or none -- also q0[row] [M][d] | kv0[row] [M][2d] = row (live ? id : n_classes) of the
+  // block-0 QKV table [.][3d]
+  const void* qkv_table = nullptr; void* q0 = nullptr; void* kv0 = nullptr;
 };
+// rows of the block-0 QKV table [rows][3d] (d3pm_api.hip build_qkv_table): one per id, the zero row of a padded frame at n_classes,
+// then zero rows up to a multiple of both GEMM tile heights (192 and 128)
+inline int qkv_table_rows(int n_classes) { return (n_classes + 1 + 383) / 384 * 384; }
 
 // per-step scalars of the closed-form posterior (host-built from d3pm_schedule)
 struct PosteriorConsts {
@@ -185,6 +191,9 @@ struct NextIterPrep {
   bool quads = false;                                                                               // stats in the quad format
   const d3pm_block_weights* blocks = nullptr; int n_layers = 0; const void* film_t = nullptr;      // film_t: the FiLM table's row of the next evaluation's timestep (t - 1; the reveal loop: t_{i+1})
   void* Wf = nullptr; float* s_out = nullptr; float* b_out = nullptr;
+  // optional, all or none: the block-0 QKV table and the [rows][d] | [rows][2d] regions that receive each drawn row's projection
+  // (EmbedArgs).  posterior_sample_prep only: the guided and the reveal launches ignore them, and their loops keep the projection.
+  const void* qkv_table = nullptr; void* q0 = nullptr; void* kv0 = nullptr;
 };
 bool posterior_sample_prep_supported(const SampleArgs& a, const NextIterPrep& n);
 int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_t s);
@@ -271,6 +280,8 @@ int fold_fc1_step_launch(int dtype, const d3pm_block_weights* blocks, int n_laye
 // quads: the moments in the quad format of d3pm_mfma_tile.h (EpiFold; d = 512) instead of 32-column parts
 int row_stats_launch(int dtype, const void* x, int ldx, int M, int d, float* stats, hipStream_t s, bool quads = false);
 int embed_tokens_stats(int dtype, const EmbedArgs& a, float* stats, bool quads, hipStream_t s);
+// the inputs of the block-0 QKV table: x [rows][d] = the embedding row of id `row` (zeros from n_classes on) and its moments (parts)
+int qkv_table_rows_launch(int dtype, const void* table, void* x, float* stats, int rows, int d, int n_classes, hipStream_t s);
 
 // ---- stock NAR model (levels 1..7): input assembly, AdaLN, temperature sampling (d3pm_nar.hip) ----
 struct NarEmbedArgs {

@@ -122,7 +122,8 @@ __device__ __forceinline__ void posterior_sample_prep_rows_body(
     uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, const PosteriorConsts& pc, int mask_period, int sample_blocks,
     const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
     bool quads, const FoldStepPtrs& fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
-    const uint8_t* __restrict__ known, const RowFilter& flt, const RowNucleus& nuc = RowNucleus{}) {
+    const uint8_t* __restrict__ known, const T* __restrict__ qkv_table, T* __restrict__ q0, T* __restrict__ kv0, const RowFilter& flt,
+    const RowNucleus& nuc = RowNucleus{}) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (static_cast<int>(blockIdx.x) >= sample_blocks) {
     const int r = (blockIdx.x - sample_blocks) * 4 + wave;
@@ -147,7 +148,7 @@ __device__ __forceinline__ void posterior_sample_prep_rows_body(
     x_next[row] = best_j;
     if (x_next2) x_next2[row] = best_j;
   }
-  embed_row_stats<T>(table, best_j, frame_mask[row % mask_period] != 0, xres, row, d, K, stats, quads, lane);
+  embed_row_stats<T>(table, best_j, frame_mask[row % mask_period] != 0, xres, row, d, K, stats, quads, lane, qkv_table, q0, kv0);
 }
 
 template <typename T, bool kKnown>
@@ -156,10 +157,10 @@ __global__ __launch_bounds__(256) void posterior_sample_prep_rows(
     uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int mask_period, int sample_blocks,
     const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
     bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
-    const uint8_t* __restrict__ known) {
+    const uint8_t* __restrict__ known, const T* __restrict__ qkv_table, T* __restrict__ q0, T* __restrict__ kv0) {
   posterior_sample_prep_rows_body<T, kKnown, 0>(logits, ldl, x_t, x_next, x_next2, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, mask_period,
                                                     sample_blocks, table, xres, stats, frame_mask, d, quads, fp, film_t, n_layers, Wf, s_out, b_out, known,
-                                                    RowFilter{});
+                                                    qkv_table, q0, kv0, RowFilter{});
 }
 
 template <typename T, bool kKnown>
@@ -168,10 +169,10 @@ __global__ __launch_bounds__(256) void posterior_sample_prep_rows_filtered(
     uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int mask_period, int sample_blocks,
     const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
     bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
-    const uint8_t* __restrict__ known, RowFilter flt) {
+    const uint8_t* __restrict__ known, const T* __restrict__ qkv_table, T* __restrict__ q0, T* __restrict__ kv0, RowFilter flt) {
   posterior_sample_prep_rows_body<T, kKnown, kFilterArm>(logits, ldl, x_t, x_next, x_next2, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, mask_period,
                                                          sample_blocks, table, xres, stats, frame_mask, d, quads, fp, film_t, n_layers, Wf, s_out, b_out,
-                                                         known, flt);
+                                                         known, qkv_table, q0, kv0, flt);
 }
 
 // the loop's launch with top_p: no theta output (the loop has none), so `top_p` travels alone
@@ -181,10 +182,10 @@ __global__ __launch_bounds__(256) void nucleus_sample_prep_rows(
     uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int mask_period, int sample_blocks,
     const T* __restrict__ table, T* __restrict__ xres, float* __restrict__ stats, const uint8_t* __restrict__ frame_mask, int d,
     bool quads, FoldStepPtrs fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
-    const uint8_t* __restrict__ known, RowFilter flt, float top_p) {
+    const uint8_t* __restrict__ known, const T* __restrict__ qkv_table, T* __restrict__ q0, T* __restrict__ kv0, RowFilter flt, float top_p) {
   posterior_sample_prep_rows_body<T, kKnown, kNucleusArm>(logits, ldl, x_t, x_next, x_next2, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, mask_period,
                                                           sample_blocks, table, xres, stats, frame_mask, d, quads, fp, film_t, n_layers, Wf, s_out, b_out,
-                                                          known, flt, RowNucleus{top_p, nullptr});
+                                                          known, qkv_table, q0, kv0, flt, RowNucleus{top_p, nullptr});
 }
 
 // ---- classifier-free guidance (d3pm_guidance) -------------------------------------------------------------------
@@ -362,7 +363,8 @@ int posterior_sample(const SampleArgs& a, hipStream_t s) {
 
 bool posterior_sample_prep_supported(const SampleArgs& a, const NextIterPrep& n) {
   return a.n_q == 1 && !a.posterior_out && !a.theta_out && a.logits_dtype == n.dtype && (n.dtype == D3PM_F16 || n.dtype == D3PM_BF16) && n.n_layers <= 16 &&
-         n.d % 256 == 0 && (!n.quads || n.d == 512) && a.n_classes <= kWave * kMaxGroupsPerLane * 4 && n.table && n.x && n.stats && n.frame_mask && n.mask_period > 0 && n.blocks && n.film_t && n.Wf;
+         n.d % 256 == 0 && (!n.quads || n.d == 512) && a.n_classes <= kWave * kMaxGroupsPerLane * 4 && n.table && n.x && n.stats && n.frame_mask && n.mask_period > 0 && n.blocks && n.film_t && n.Wf &&
+         (n.qkv_table != nullptr) == (n.q0 != nullptr) && (n.q0 != nullptr) == (n.kv0 != nullptr);
 }
 
 int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_t s) {
@@ -376,7 +378,8 @@ int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_
 #define D3PM_PSP_ARGS(T)                                                                                                                            \
   static_cast<const T*>(a.logits), a.ldl, a.x_t, a.x_next, a.x_next2, a.rows, a.n_classes, a.mask_id, a.seed, a.seed_hbm, a.row0, a.greedy, a.pc, \
       n.mask_period, sample_blocks, static_cast<const T*>(n.table), static_cast<T*>(n.x), n.stats, n.frame_mask, n.d, n.quads, p,                 \
-      static_cast<const T*>(n.film_t), n.n_layers, static_cast<T*>(n.Wf), n.s_out, n.b_out, a.known
+      static_cast<const T*>(n.film_t), n.n_layers, static_cast<T*>(n.Wf), n.s_out, n.b_out, a.known, static_cast<const T*>(n.qkv_table),         \
+      static_cast<T*>(n.q0), static_cast<T*>(n.kv0)
 #define D3PM_PSP_ARM(T, kKnown)                                                                                  \
   do {                                                                                                           \
     if (a.nucleus()) nucleus_sample_prep_rows<T, kKnown><<<grid, block, 0, s>>>(D3PM_PSP_ARGS(T), flt, a.top_p);    \

@@ -253,6 +253,9 @@ SIGNATURES = {
                                        C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(Tuning), C.c_void_p]),
     "d3pm_op_linear_fold": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Tuning), C.c_void_p]),
+    "d3pm_op_embed_qkv_bytes": (C.c_size_t, [C.POINTER(Shape), C.c_int]),
+    "d3pm_op_embed_qkv": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "d3pm_op_fold_weights": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "d3pm_cond_kv": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int] + [C.c_void_p] * 5),
@@ -1193,6 +1196,22 @@ def op_linear_fold(x, wf, fold_s, fold_b, stats, *, act=0, eps=1e-6):
     return y
 
 
+def op_embed_qkv(shape, weights, tokens, frame_mask):
+    """The block-0 q | k | v rows [n, 3 d_model] of `tokens` int32 [n] under `frame_mask` uint8 [n], gathered from the per-id table the
+    sampler loop builds under ln_fold = 1 (d3pm_op_embed_qkv).  shape: Shape, weights: DeviceWeights with build_fold done."""
+    n = tokens.numel()
+    need = lib().d3pm_op_embed_qkv_bytes(C.byref(shape), n)
+    if need == 0:
+        raise D3PMError("d3pm_op_embed_qkv: needs a 16-bit model, d_model a multiple of 256 and n_q <= 1")
+    dtype = {v: k for k, v in _DTYPES.items()}[shape.dtype]
+    storage = torch.empty(need, dtype=torch.uint8, device=tokens.device)
+    q = torch.empty((n, shape.d_model), dtype=dtype, device=tokens.device)
+    kv = torch.empty((n, 2 * shape.d_model), dtype=dtype, device=tokens.device)
+    check(lib().d3pm_op_embed_qkv(C.byref(shape), C.byref(weights.c_struct), _p(tokens), _p(frame_mask), n, _p(storage), need, _p(q),
+                                  _p(kv), stream_ptr()), "d3pm_op_embed_qkv")
+    return torch.cat([q, kv], dim=1)
+
+
 def op_layernorm(x, w, b, film=None, eps=1e-6):
     y = torch.empty_like(x)
     check(lib().d3pm_op_layernorm(dtype_code(x.dtype), _p(x), _p(y), _p(w), _p(b), _p(film), x.shape[0], x.shape[1],
@@ -1326,7 +1345,7 @@ def set_workspace_alias(v: bool):
 
 
 _TUNING_VALUES = {"gemm_variant": (0, 2, 3, 4, 5, 6, 7, 8), "attn_query_groups": (0, 1, 2, 4, 32, 33), "lat_tile": (0, 1, 2, 3),
-                  "attn_pair_sequential": (0, 1, 2), "attn_cross_resident": (0, 1, 2, 3, 4, 5), "workspace_alias": (0, 1), "ln_fold": (0, 1)}
+                  "attn_pair_sequential": (0, 1, 2), "attn_cross_resident": (0, 1, 2, 3, 4, 5), "workspace_alias": (0, 1), "ln_fold": (0, 1, 2)}
 
 
 @contextlib.contextmanager
