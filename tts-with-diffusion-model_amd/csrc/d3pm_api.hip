@@ -11,7 +11,7 @@
 #include <new>
 #include <vector>
 
-#include "d3pm_kernels.h"
+#include "d3pm_plan.h"
 
 namespace d3pm {
 
@@ -74,14 +74,16 @@ struct ProfScope {
   }
 };
 
-// ---- kernel-family dispatch ----------------------------------------------------------------
+// ---- kernel-family dispatch: the planner (d3pm_plan.cpp) names the kernel; "generic" is its answer like any other -----------------
+static bool forced_generic(uint32_t flags) { return (flags & D3PM_FLAG_FORCE_GENERIC) != 0; }
 static int run_linear(const Ctx& cx, int dtype, LinearArgs a, uint32_t flags, hipStream_t s) {
   const size_t es = dtype_size(dtype);
   a.tune = cx.tune;
   ProfScope p(cx, D3PM_K_GEMM, s, 2.0 * a.M * a.N * a.K,
               es * (static_cast<double>(a.M) * a.K + static_cast<double>(a.N) * a.K +
                     static_cast<double>(a.M) * a.N * (1 + (a.R1 ? 1 : 0) + (a.R2 ? 1 : 0))));
-  if (!(flags & D3PM_FLAG_FORCE_GENERIC) && mfma_linear_supported(dtype, a)) return mfma_linear(dtype, a, s);
+  const LinearPlan plan = plan_linear(dtype, a, forced_generic(flags));
+  if (plan.mfma()) return mfma_linear(dtype, a, plan, s);
   // the generic family has no folded-LayerNorm epilogues: it would ignore the moments (read stale ones, or leave them unwritten)
   D3PM_REQUIRE(!a.fold_s && !a.stats_out && !a.moment_quads, D3PM_E_SHAPE, "folded-LayerNorm projection %d x %d x %d needs the MFMA family",
                a.M, a.N, a.K);
@@ -101,7 +103,8 @@ static int run_attention(const Ctx& cx, int dtype, AttnArgs a, uint32_t flags, h
   // pair look like 1.3x wasted traffic -- PMC says 118.8 MB against 118.6) + keys and values
   ProfScope p(cx, D3PM_K_ATTN, s, 4.0 * a.B * a.H * a.Tq * static_cast<double>(a.S + a.S2) * a.hd,
               dtype_size(dtype) * ((a.Q2 ? 4.0 : 2.0) * a.B * a.Tq * a.H * a.hd + 2.0 * a.B * (a.S + a.S2) * a.H * a.hd));
-  if (!(flags & D3PM_FLAG_FORCE_GENERIC) && mfma_attention_supported(dtype, a)) return mfma_attention(dtype, a, s);
+  const AttnPlan plan = plan_attention(dtype, a, forced_generic(flags));
+  if (plan.mfma()) return mfma_attention(dtype, a, plan, s);
   if (a.Q2) {   // the generic kernel takes one problem per launch
     AttnArgs first = a, second = a;
     first.Q2 = first.K2 = first.V2 = nullptr; first.O2 = nullptr; first.S2 = 0; first.key_len2 = nullptr;
@@ -262,22 +265,11 @@ static EmbedArgs embed_args(const d3pm_shape& sh, const d3pm_weights& w, int bat
   return e;
 }
 
-// ---- the cross-attention out-projection pair: x = (x + o_text) + o_prompt through the same weights --------------------------------
-// Three forms with the same bits.  `g` is the o_text projection onto the residual stream (R1 = Y = x, tune set), X2 the o_prompt rows.
-enum { CROSS_OUT_TWO_LAUNCHES = 0, CROSS_OUT_PANEL64_DUAL, CROSS_OUT_BIG_DUAL };
-static int cross_out_form(int dt, const LinearArgs& g, const void* X2, uint32_t flags, bool big_dual_allowed) {
-  const d3pm_tuning& tn = tune_of(g.tune);
-  if (flags & D3PM_FLAG_FORCE_GENERIC) return CROSS_OUT_TWO_LAUNCHES;
-  // one or two utterances: both products through one resident weight panel of the latency GEMM (o_text stays in registers)
-  if ((tn.row_panel & 8) && tn.gemm_variant == 0 && panel64_dual_supported(dt, g, X2)) return CROSS_OUT_PANEL64_DUAL;
-  // throughput batches: the same two products through one tile of the ordinary big-tile launch
-  if (big_dual_allowed && (tn.row_panel & 2) && big_dual_supported(dt, g, X2)) return CROSS_OUT_BIG_DUAL;
-  return CROSS_OUT_TWO_LAUNCHES;      // o_text -> ws.h, then o_prompt with R1 = x, R2 = h
-}
-static int run_cross_out_dual(const Ctx& cx, int dt, int form, const LinearArgs& g, const void* X2, hipStream_t s) {
+// ---- the cross-attention out-projection pair: x = (x + o_text) + o_prompt through the same weights (plan_cross_out, d3pm_plan.h) ----
+static int run_cross_out_dual(const Ctx& cx, int dt, const CrossOutPlan& c, const LinearArgs& g, const void* X2, hipStream_t s) {
   ProfScope p(cx, D3PM_K_GEMM, s, 2.0 * 2.0 * g.M * g.N * g.K,
               dtype_size(dt) * (2.0 * g.M * g.K + static_cast<double>(g.N) * g.K + 2.0 * g.M * g.N));
-  return form == CROSS_OUT_PANEL64_DUAL ? panel64_dual(dt, g, X2, s) : big_dual(dt, g, X2, s);
+  return c.form == CROSS_OUT_PANEL64_DUAL ? panel64_dual(dt, g, X2, c.dual, s) : big_dual(dt, g, X2, c.dual, s);
 }
 
 // The frame mask of a call and the period it repeats with over the packed [batch * canvas] rows: one mask [canvas] shared by every
@@ -366,10 +358,10 @@ static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v, bo
                                       q.keys)));
   // ---- x = (x + o_text) + o_prompt, rounded at each add like the eager sum ----
   LinearArgs g = producer(ws.att, d, b.cross_out_w, b.cross_out_b);
-  g.tune = sh.tuning;      // big_dual_supported reads it
-  const int form = cross_out_form(dt, g, ws.att2, 0, true);
-  if (form != CROSS_OUT_TWO_LAUNCHES) {
-    D3PM_TRY(v.dual(form, g, ws.att2));
+  g.tune = sh.tuning;      // plan_cross_out reads it
+  const CrossOutPlan out = plan_cross_out(dt, g, ws.att2, false, true);
+  if (out.form != CROSS_OUT_TWO_LAUNCHES) {
+    D3PM_TRY(v.dual(out, g, ws.att2));
   } else {
     g.Y = ws.h; g.R1 = nullptr; g.stats_out = nullptr; g.moment_quads = false;   // o_text -> h (free: no LayerNorm output lives there any more)
     D3PM_TRY(v.linear(g));
@@ -387,13 +379,14 @@ struct FoldPlanner {
   int linear(LinearArgs g) {
     if (!g.fold_s && !g.stats_out) return D3PM_OK;      // no moments: any family will do
     g.tune = tune;
-    if (!mfma_linear_supported(dt, g)) return D3PM_E_SHAPE;
-    big = big && mfma_linear_takes_big_tiles(dt, g);
+    const LinearPlan plan = plan_linear(dt, g);
+    if (!plan.mfma()) return D3PM_E_SHAPE;
+    big = big && plan.big();
     return D3PM_OK;
   }
   int attention(const AttnArgs&) { return D3PM_OK; }
-  int dual(int form, const LinearArgs&, const void*) {
-    if (form == CROSS_OUT_PANEL64_DUAL) big = false;      // the 64 x 64 family keeps the 32-column parts
+  int dual(const CrossOutPlan& c, const LinearArgs&, const void*) {
+    big = big && c.dual.big();      // the 64 x 64 family keeps the 32-column parts
     return D3PM_OK;
   }
 };
@@ -401,7 +394,7 @@ struct FoldLauncher {
   const Ctx& cx; int dt; hipStream_t s;
   int linear(const LinearArgs& g) { return run_linear(cx, dt, g, 0, s); }      // (fails rather than take the generic family with moments)
   int attention(const AttnArgs& a) { return run_attention(cx, dt, a, 0, s); }
-  int dual(int form, const LinearArgs& g, const void* X2) { return run_cross_out_dual(cx, dt, form, g, X2, s); }
+  int dual(const CrossOutPlan& c, const LinearArgs& g, const void* X2) { return run_cross_out_dual(cx, dt, c, g, X2, s); }
 };
 
 // Is this evaluation taking the folded-LayerNorm launch sequence, and in which format do its row moments travel?  FOLD_NONE: the
@@ -534,9 +527,8 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
 
   // row-panel launches (D3PM_TUNE_ROW_PANEL): a projection that lands on the residual stream also writes the LayerNorm(s) the
   // block applies to the new rows next -- same bits, one launch and one pass over x less each
-  // (one 96-row tile per workgroup: only when the tiles fill >= 85 % of whole rounds over the 256 CUs, as for the other big tiles)
-  const long long rp_tiles = n / 96, rp_rounds = (rp_tiles + 255) / 256;
-  const bool rp_fills = n % 96 == 0 && rp_tiles * 5 >= 256 * 4 && rp_tiles * 100 >= rp_rounds * 256 * 85;
+  // (one 96-row tile per workgroup: only when the tiles fill >= 85 % of whole rounds over the CUs, as for the other big tiles)
+  const bool rp_fills = n % 96 == 0 && fills_rounds(n / 96, kCUs);
   const int panel = (!(flags & D3PM_FLAG_FORCE_GENERIC) && d == 512 && rp_fills && (dt == D3PM_F16 || dt == D3PM_BF16))
                         ? (tune_of(sh.tuning).row_panel & (use8 ? 3 : 7)) : 0;      // fp8: fc2 is a block-scaled GEMM of its own
   bool norm1_done = embed_fused;   // norm1(x) of this block is already in ws.h (the embedding launch, or the previous block's fc2)
@@ -613,9 +605,9 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
       D3PM_TRY(run_row_panel(cx, dt, g, rp, s));
     } else {
       g.tune = cx.tune;
-      const int form = cross_out_form(dt, g, ws.att2, flags, false);      // (throughput batches have the row-panel launch above: no big_dual here)
-      if (form != CROSS_OUT_TWO_LAUNCHES) {
-        D3PM_TRY(run_cross_out_dual(cx, dt, form, g, ws.att2, s));
+      const CrossOutPlan out = plan_cross_out(dt, g, ws.att2, forced_generic(flags), false);      // (throughput batches have the row-panel launch above: no big_dual here)
+      if (out.form != CROSS_OUT_TWO_LAUNCHES) {
+        D3PM_TRY(run_cross_out_dual(cx, dt, out, g, ws.att2, s));
       } else {
         D3PM_TRY(run_linear(cx, dt, projection(ws.att, b.cross_out_w, b.cross_out_b, ws.h, n, d, d), flags, s));
         D3PM_TRY(run_linear(cx, dt, with_residual(projection(ws.att2, b.cross_out_w, b.cross_out_b, ws.x, n, d, d), ws.x, ws.h), flags, s));
@@ -758,8 +750,9 @@ int d3pm_op_linear_stats(int dtype, const void* X, int ldx, const void* W, const
   g.tune = tuning;
   g.X = X; g.ldx = ldx; g.W = W; g.bias = bias; g.Y = Y; g.ldy = ldy; g.R1 = R1; g.R2 = R2; g.ldr = ldr;
   g.row_mask = row_mask; g.mask_period = mask_period > 0 ? mask_period : 1; g.M = M; g.N = N; g.K = K; g.stats_out = stats_out;
-  D3PM_REQUIRE(mfma_linear_supported(dtype, g), D3PM_E_SHAPE, "d3pm_op_linear_stats: needs the MFMA family (16-bit, K %% 64 == 0, N %% 32 == 0)");
-  return mfma_linear(dtype, g, static_cast<hipStream_t>(stream));
+  const LinearPlan plan = plan_linear(dtype, g);
+  D3PM_REQUIRE(plan.mfma(), D3PM_E_SHAPE, "d3pm_op_linear_stats: needs the MFMA family (16-bit, K %% 64 == 0, N %% 32 == 0)");
+  return mfma_linear(dtype, g, plan, static_cast<hipStream_t>(stream));
 }
 
 int d3pm_op_linear_fold(int dtype, const void* X, int ldx, const void* Wf, const float* fold_s, const float* fold_b, const float* stats_in,
@@ -769,9 +762,10 @@ int d3pm_op_linear_fold(int dtype, const void* X, int ldx, const void* Wf, const
   g.tune = tuning;
   g.X = X; g.ldx = ldx; g.W = Wf; g.Y = Y; g.ldy = ldy; g.M = M; g.N = N; g.K = K; g.act = act;
   g.fold_s = fold_s; g.fold_b = fold_b; g.stats_in = stats_in; g.fold_eps = eps;
-  D3PM_REQUIRE(mfma_linear_supported(dtype, g), D3PM_E_SHAPE,
+  const LinearPlan plan = plan_linear(dtype, g);
+  D3PM_REQUIRE(plan.mfma(), D3PM_E_SHAPE,
                "d3pm_op_linear_fold: needs the MFMA family (16-bit), K a multiple of 256, N of 4, act 0 / 1 and 16-byte aligned tables");
-  return mfma_linear(dtype, g, static_cast<hipStream_t>(stream));
+  return mfma_linear(dtype, g, plan, static_cast<hipStream_t>(stream));
 }
 
 size_t d3pm_op_embed_qkv_bytes(const d3pm_shape* sh, int n) {
@@ -1522,8 +1516,9 @@ int d3pm_op_linear(int dtype, int family, const void* X, int ldx, const void* W,
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (family == 1) return generic_linear(dtype, g, s);
   if (family == 2) {
-    D3PM_REQUIRE(mfma_linear_supported(dtype, g), D3PM_E_SHAPE, "d3pm_op_linear: shape not supported by the MFMA kernel");
-    return mfma_linear(dtype, g, s);
+    const LinearPlan plan = plan_linear(dtype, g);
+    D3PM_REQUIRE(plan.mfma(), D3PM_E_SHAPE, "d3pm_op_linear: shape not supported by the MFMA kernel");
+    return mfma_linear(dtype, g, plan, s);
   }
   return run_linear(cx, dtype, g, 0, s);
 }
@@ -1566,8 +1561,9 @@ static int op_attention_impl(const char* who, int dtype, int family, const void*
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (family == 1) return generic_attention(dtype, a, s);
   if (family == 2) {
-    D3PM_REQUIRE(mfma_attention_supported(dtype, a), D3PM_E_SHAPE, "%s: shape not supported by the MFMA kernel", who);
-    return mfma_attention(dtype, a, s);
+    const AttnPlan plan = plan_attention(dtype, a);
+    D3PM_REQUIRE(plan.mfma(), D3PM_E_SHAPE, "%s: shape not supported by the MFMA kernel", who);
+    return mfma_attention(dtype, a, plan, s);
   }
   return run_attention(cx, dtype, a, 0, s);
 }

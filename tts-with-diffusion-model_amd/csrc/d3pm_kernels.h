@@ -40,7 +40,7 @@ struct LinearArgs {
   // moments of the rows this launch stores (N = d_model, after residual / mask): stats_out [M][N / 32][2] partial (sum, sum of squares)
   float* stats_out = nullptr;
   // stats_in / stats_out in the quad format [M / 16][d / 128][16][2] (d3pm_mfma_tile.h EpiFold) instead of 32-column parts: d_model = 512,
-  // big-tile GEMM only (mfma_linear fails with D3PM_E_SHAPE on any other family); one host decision per folded sequence (d3pm_api.hip)
+  // big-tile GEMM only (LIN_QUADS_REFUSED, d3pm_plan.h: mfma_linear fails with D3PM_E_SHAPE on any other family); one host decision per folded sequence (d3pm_api.hip)
   bool moment_quads = false;
 };
 // which LayerNorm-fold combinations the MFMA epilogues instantiate: LNF [+ GELU] without residual / mask; STATS with R1, R1 + R2, R1 + mask
@@ -245,25 +245,22 @@ int layernorm_mx(int dtype, const void* x, uint8_t* y8, uint8_t* sx, const void*
                  const void* w2, const void* b2, uint8_t* y8_2, uint8_t* sx_2, int M, int d, float eps, hipStream_t s);
 int quantize_mx(int dtype, const void* x, int ldx, uint8_t* y8, uint8_t* sx, int M, int K, hipStream_t s);
 
-// MFMA family: return D3PM_E_SHAPE when the shape does not fit (caller falls back to generic)
-bool mfma_linear_supported(int dtype, const LinearArgs& a);
-int mfma_linear(int dtype, const LinearArgs& a, hipStream_t s);
-bool mfma_attention_supported(int dtype, const AttnArgs& a);
-int mfma_attention(int dtype, const AttnArgs& a, hipStream_t s);
-bool mfma_attention32_supported(int dtype, const AttnArgs& a);   // d3pm_mfma_attn32.hip: self-attention on the 32 x 32 x 16 instruction
-int mfma_attention32(int dtype, const AttnArgs& a, hipStream_t s);
-bool mfma_attention32_cross_supported(int dtype, const AttnArgs& a);   // the resident cross-attention pair on the same instruction
-int mfma_attention32_cross(int dtype, const AttnArgs& a, int n_qsplit, hipStream_t s);
-// d3pm_mfma_attn_lat.hip: one or two utterances -- the key tiles of a 32-query group split over the four waves of a workgroup
-bool mfma_attention_split_supported(int dtype, const AttnArgs& a);
-int mfma_attention_split(int dtype, const AttnArgs& a, hipStream_t s);
-// latency GEMM, two products through one weight panel: Y = rn(rn(R1 + rn(X W^T + b)) + rn(X2 W^T + b)) (d3pm_mfma_gemm_lat.hip)
-bool panel64_dual_supported(int dtype, const LinearArgs& a, const void* X2);
-int panel64_dual(int dtype, const LinearArgs& a, const void* X2, hipStream_t s);
-// big-tile GEMM, the same two products at throughput batch sizes (d3pm_mfma_gemm_big.hip); stats_out optional
-bool big_dual_supported(int dtype, const LinearArgs& a, const void* X2);
-bool mfma_linear_takes_big_tiles(int dtype, const LinearArgs& a);     // would mfma_linear run `a` on the big-tile GEMM?
-int big_dual(int dtype, const LinearArgs& a, const void* X2, hipStream_t s);
+// MFMA family.  Which kernel runs, on which grid, is a plan (d3pm_plan.h: plan_linear / plan_cross_out / plan_attention, host-only);
+// the launchers instantiate what the plan names.  mfma_linear and mfma_attention take any plan with mfma() and forward to the others.
+struct LinearPlan;
+struct AttnPlan;
+int mfma_linear(int dtype, const LinearArgs& a, const LinearPlan& p, hipStream_t s);
+int big_linear(int dtype, const LinearArgs& a, const LinearPlan& p, hipStream_t s);             // d3pm_mfma_gemm_big.hip
+int panel64_linear(int dtype, const LinearArgs& a, const LinearPlan& p, hipStream_t s);         // d3pm_mfma_gemm_lat.hip
+int mfma_attention(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_t s);
+int mfma_attention32(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_t s);           // d3pm_mfma_attn32.hip: self-attention on the 32 x 32 x 16 instruction
+int mfma_attention32_cross(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_t s);     // the resident cross-attention pair on the same instruction
+// d3pm_mfma_attn_lat.hip: the key tiles of a 32-query group split over the four waves of a workgroup
+int mfma_attention_split(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_t s);
+// two products through one weight panel or tile, Y = rn(rn(R1 + rn(X W^T + b)) + rn(X2 W^T + b)); `p` = CrossOutPlan::dual:
+// the latency GEMM (d3pm_mfma_gemm_lat.hip) and the big-tile GEMM at throughput batch sizes (d3pm_mfma_gemm_big.hip; stats_out optional)
+int panel64_dual(int dtype, const LinearArgs& a, const void* X2, const LinearPlan& p, hipStream_t s);
+int big_dual(int dtype, const LinearArgs& a, const void* X2, const LinearPlan& p, hipStream_t s);
 bool row_panel_supported(int dtype, const LinearArgs& a, const RowPanelFuse& f);
 int row_panel_linear(int dtype, const LinearArgs& a, const RowPanelFuse& f, hipStream_t s);
 bool fast_layernorm_supported(int dtype, const LayerNormArgs& a);

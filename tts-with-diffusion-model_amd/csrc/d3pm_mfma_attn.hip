@@ -25,7 +25,7 @@
 // The softmax is VALU-bound at head_dim 64 (256 flop of MFMA per score), so it is kept to ~6 VALU issue
 // slots per score: max, sub, v_exp_f32, add, half a cvt_pk; the O rescale is skipped when no maximum moved
 // and the key-padding compare/select only runs on a ragged last tile.
-#include "d3pm_kernels.h"
+#include "d3pm_plan.h"      // HD, BKV, ROWB, TILE and the AttnPlan the launchers take
 
 namespace d3pm {
 namespace {
@@ -35,8 +35,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef short short4v __attribute__((ext_vector_type(4)));
 
-constexpr int HD = 64, BKV = 64, ROWB = 128;
-constexpr int TILE = BKV * ROWB;   // 8 KiB per K or V tile
 
 template <typename T> __device__ __forceinline__ floatx4 mma(uint4 a, uint4 b, floatx4 c);
 template <> __device__ __forceinline__ floatx4 mma<f16>(uint4 a, uint4 b, floatx4 c) {
@@ -530,88 +528,41 @@ __global__ __launch_bounds__(512, 2) void attn_cross_hd64(const T* __restrict__ 
   (void)MAXT;
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 }  // namespace
 
-bool mfma_attention_supported(int dtype, const AttnArgs& a) {
-  if (dtype != D3PM_F16 && dtype != D3PM_BF16) return false;
-  if (a.hd != HD || a.S < 1 || a.Tq < 1) return false;
-  if (a.ldq % 8 || a.ldkv % 8 || a.ldo % 8) return false;      // 16-byte output stores
-  if (a.Q2 && !(a.S2 >= 1 && aligned(a.Q2, 16) && aligned(a.K2, 16) && aligned(a.V2, 16) && aligned(a.O2, 16))) return false;
-  return aligned(a.Q, 16) && aligned(a.K, 16) && aligned(a.V, 16) && aligned(a.O, 16);
-}
-
-// d3pm_tuning.attn_query_groups: 0 = auto: two 16-query groups per wave (each K / V fragment read from LDS feeds two MFMAs;
-// 63.8 vs 65.8 us on the 768 x 768 x 256-head self-attention, 27.7 vs 30.1 us on the 225-key prompt attention) once that still
-// leaves >= 4 workgroups per CU, one group otherwise (a single utterance is 48 workgroups of two groups: latency regime).
-// attn_pair_sequential: 0 never, 1 auto (when the paired grid still has >= 2 workgroups per CU), 2 always.
-// attn_cross_resident: cross-attention pair with every K / V tile resident in LDS (attn_cross_hd64): 0 never, 1 auto, 2 always.
-// Auto = when its grid (256 queries per workgroup) has at least one workgroup per CU: at one utterance it is 24 workgroups of
-// eight waves and the tile-by-tile kernel's 192 small ones finish sooner (p50 latency 46.7 -> 42.2 ms,
-// profiles/round2_d_latency_ab.txt)
-
-int mfma_attention(int dtype, const AttnArgs& a, hipStream_t s) {
-  const d3pm_tuning& tn = tune_of(a.tune);
-  const int g_attn_cross_resident = tn.attn_cross_resident, g_attn_pair_seq = tn.attn_pair_sequential;
-  const int g_attn_qg = (tn.attn_query_groups == 1 || tn.attn_query_groups == 2) ? tn.attn_query_groups : 0;
-  // The 32 x 32 x 16 kernel of d3pm_mfma_attn32.hip wherever it applies (whole 128-query blocks and 64-key tiles of a single
-  // problem: the self-attention of a DiT block) once its grid has two workgroups per CU (measured: 55.3 vs 65.3 us at 32
-  // utterances x 768 frames, 19.5 vs 20.3 at 32 x 384, 28.8 vs 30.8 at 16 x 768; tests/ab_attn32.py); below that the 64-query
-  // workgroups of the kernel below finish sooner.  attn_query_groups: 0 auto, 32 always, 33 always and the plain walk, 1 / 2 never.
-  {
-    // regime_batch: the batch the automatic choice is made for (a shard of a split batch takes the kernels of the whole batch)
-    const long long wgs32 = static_cast<long long>(a.Tq / 128) * a.H * (tn.regime_batch > 0 ? tn.regime_batch : a.B);
-    const int q = tn.attn_query_groups;
-    // key lengths: the masked instantiations on an explicit 32 / 33, or where the denoiser plan asks for the unmasked choice
-    // (AttnArgs::masked_keeps_schedule); any other masked call keeps the kernel below, as it always has
-    const bool auto32 = q == 0 && wgs32 >= 512 && (a.key_len == nullptr || a.masked_keeps_schedule);
-    if ((q == 32 || q == 33 || auto32) && mfma_attention32_supported(dtype, a)) return mfma_attention32(dtype, a, s);
+// Which kernel, which grid, how much LDS: plan_attention (d3pm_plan.cpp), where the tuning fields and the measurements behind the
+// automatic choices are described.  What is left here is the plan -> instantiation table.
+int mfma_attention(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_t s) {
+  switch (p.kernel) {
+    case ATTN_32P: case ATTN_32: return mfma_attention32(dtype, a, p, s);
+    case ATTN_32_CROSS: return mfma_attention32_cross(dtype, a, p, s);
+    case ATTN_SPLIT: return mfma_attention_split(dtype, a, p, s);
+    case ATTN_CROSS: case ATTN_TILES: break;
+    default:
+      set_error("attention: not planned for the MFMA family");
+      return D3PM_E_SHAPE;
   }
-  const long long cross_wgs = static_cast<long long>((a.Tq + 255) / 256) * a.H * (tn.regime_batch > 0 ? tn.regime_batch : a.B);
-  // (key lengths do not change the choice: S / S2 are the padded counts, which size the LDS image)
-  if ((g_attn_cross_resident >= 2 || (g_attn_cross_resident == 1 && cross_wgs >= 256)) && a.Q2 != nullptr && a.S <= BKV && a.S2 <= 4 * BKV) {
-    const int n_qblocks = (a.Tq + 255) / 256;
-    int n_qsplit = (256 + a.H * a.B - 1) / (a.H * a.B);            // workgroups per (utterance, head): enough to cover the CUs
-    n_qsplit = n_qsplit < 1 ? 1 : n_qsplit > n_qblocks ? n_qblocks : n_qsplit;
-    if (g_attn_cross_resident == 3) n_qsplit = n_qblocks;              // tuning: one query block per workgroup (the first form)
-    // the same residency on the 32 x 32 x 16 instruction with the software-pipelined block of d3pm_mfma_attn32.hip (the shipped
-    // form: 34.9 vs 35.8 us per pair in the microbenchmark, 43.1 vs 44.1 us per attention launch in the loop, tests/ab_cross32.py,
-    // profiles/round3_r_ab_cross32.txt; it takes over at the batch size where the self-attention changes instruction shape too):
-    // 5 always, 4 = the 16 x 16 x 32 form (bit-identical to the tile-by-tile kernel)
-    constexpr bool kCross32 = true;
-    if ((g_attn_cross_resident == 5 || (kCross32 && g_attn_cross_resident != 4)) && mfma_attention32_cross_supported(dtype, a))
-      return mfma_attention32_cross(dtype, a, n_qsplit, s);
-    const dim3 grid(static_cast<unsigned>(n_qsplit * a.H * a.B)), block(512);
-    const size_t lds = static_cast<size_t>(1 + (a.S2 + BKV - 1) / BKV) * 2 * TILE;
+  const int n_qblocks = p.n_qblocks, n_qsplit = p.n_qsplit, n_first = p.n_first;
+  if (p.kernel == ATTN_CROSS) {
+    const dim3 grid(p.grid), block(512);
 #define D3PM_CROSS(T, MASK)                                                                                                  \
     do {                                                                                                                     \
       D3PM_LDS_ATTR((&attn_cross_hd64<T, MASK>), 5 * 2 * TILE);                                                              \
-      attn_cross_hd64<T, MASK><<<grid, block, lds, s>>>(static_cast<const T*>(a.Q), static_cast<const T*>(a.K),               \
+      attn_cross_hd64<T, MASK><<<grid, block, p.lds, s>>>(static_cast<const T*>(a.Q), static_cast<const T*>(a.K),             \
           static_cast<const T*>(a.V), static_cast<T*>(a.O), a.S, static_cast<const T*>(a.Q2), static_cast<const T*>(a.K2),    \
           static_cast<const T*>(a.V2), static_cast<T*>(a.O2), a.S2, a.ldq, a.ldkv, a.ldo, a.Tq, a.scale, a.H, n_qblocks, n_qsplit, \
           a.key_len, a.key_len2);                                                                                            \
     } while (0)
-    if (a.key_len || a.key_len2) {
+    if (p.masked) {
       if (dtype == D3PM_F16) D3PM_CROSS(f16, true); else D3PM_CROSS(bf16, true);
     } else if (dtype == D3PM_F16) D3PM_CROSS(f16, false); else D3PM_CROSS(bf16, false);
 #undef D3PM_CROSS
     D3PM_LAUNCH_CHECK();
     return D3PM_OK;
   }
-  // Opt-in (attn_query_groups = 4): the key-split kernel of d3pm_mfma_attn_lat.hip -- four waves share 32 queries and take every
-  // fourth key tile.  Measured at one utterance 0.8 ms of 38.8 faster (p50), at two utterances 2 ms slower (tests/ab_latency.py,
-  // profiles/round3_o_ab_latency.txt): the launch is bound by the K / V bytes each workgroup streams through its CU (196 KB per
-  // (head, query group) at 768 keys), not by the length of the tile chain, so it is not an automatic choice -- one utterance keeps
-  // the schedule, and therefore the bits, of the batches up to ten.
-  if (tn.attn_query_groups == 4 && mfma_attention_split_supported(dtype, a)) return mfma_attention_split(dtype, a, s);
-  const long long wgs2 = static_cast<long long>((a.Tq + 127) / 128) * a.H * a.B * (a.Q2 ? 2 : 1);
-  const int qg = g_attn_qg == 0 ? (wgs2 >= 4 * 256 ? 2 : 1) : g_attn_qg, per_block = 64 * qg;
-  const int n_qblocks = (a.Tq + per_block - 1) / per_block;
-  const int n_blocks1 = n_qblocks * a.H * a.B;
-  const bool seq = a.Q2 != nullptr && (g_attn_pair_seq == 2 || (g_attn_pair_seq == 1 && n_blocks1 >= 512));
-  const int n_first = seq ? -1 : n_blocks1;
-  dim3 grid(static_cast<unsigned>(n_blocks1) * ((a.Q2 && !seq) ? 2 : 1)), block(256);
+  const int qg = p.qg;
+  const bool seq = p.pair_seq;
+  const dim3 grid(p.grid), block(256);
 #define D3PM_ATTN(T, QG, PAIR)                                                                                       \
   attn_mfma_hd64<T, QG, PAIR><<<grid, block, 0, s>>>(static_cast<const T*>(a.Q), a.ldq, static_cast<const T*>(a.K),  \
                                                      static_cast<const T*>(a.V), a.ldkv, static_cast<T*>(a.O), a.ldo, a.Tq, \

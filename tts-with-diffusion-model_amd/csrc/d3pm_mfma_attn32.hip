@@ -24,7 +24,7 @@
 //   * K / V tiles are staged global -> registers -> LDS one tile ahead, one barrier per tile; 128-byte LDS rows with the
 //     16-byte chunks XOR-swizzled (K: (row >> 1) & 7 -- the b128 fragment reads of 32 rows x one chunk; V: ((row >> 1) & 1)
 //     << 2 -- the transposed reads of 4 rows x 64 bytes), both conflict-free by construction.
-#include "d3pm_kernels.h"
+#include "d3pm_plan.h"      // HD, BKV, ROWB, TILE and the AttnPlan the launchers take
 
 namespace d3pm {
 namespace {
@@ -34,8 +34,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef short short4v __attribute__((ext_vector_type(4)));
 
-constexpr int HD = 64, BKV = 64, ROWB = 128;
-constexpr int TILE = BKV * ROWB;   // 8 KiB per K or V tile
 constexpr float kDefer = 8.0f;     // log2 of the largest un-normalised probability tolerated before m_ref is raised
 
 template <typename T> __device__ __forceinline__ floatx16 mma32(uint4 a, uint4 b, floatx16 c);
@@ -808,59 +806,36 @@ __global__ __launch_bounds__(512, 2) void attn32_cross_hd64(const T* __restrict_
 #undef SB
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 }  // namespace
 
-// whole 128-query blocks and whole 64-key tiles of a single problem: the self-attention of a DiT block.  With key lengths S is the
-// padded count (the tiles are staged whole, so it stays a multiple of 64) and the masked instantiations run.
-bool mfma_attention32_supported(int dtype, const AttnArgs& a) {
-  if (dtype != D3PM_F16 && dtype != D3PM_BF16) return false;
-  if (a.hd != HD || a.Q2 != nullptr) return false;
-  if (a.Tq < 128 || a.Tq % 128 || a.S < BKV || a.S % BKV) return false;
-  if (a.ldq % 8 || a.ldkv % 8 || a.ldo % 8) return false;      // 16-byte output stores
-  return aligned(a.Q, 16) && aligned(a.K, 16) && aligned(a.V, 16) && aligned(a.O, 16);
-}
-
-// the cross-attention pair of a block with both K / V images resident (<= 64 text keys, <= 256 prompt keys, padded counts)
-bool mfma_attention32_cross_supported(int dtype, const AttnArgs& a) {
-  if (dtype != D3PM_F16 && dtype != D3PM_BF16) return false;
-  if (a.hd != HD || a.Q2 == nullptr) return false;
-  if (a.S < 1 || a.S > BKV || a.S2 < 1 || a.S2 > 4 * BKV || a.Tq < 1) return false;
-  if (a.ldq % 8 || a.ldkv % 8 || a.ldo % 8) return false;      // 16-byte output stores
-  return aligned(a.Q, 16) && aligned(a.K, 16) && aligned(a.V, 16) && aligned(a.O, 16) && aligned(a.Q2, 16) && aligned(a.K2, 16) &&
-         aligned(a.V2, 16) && aligned(a.O2, 16);
-}
-
-int mfma_attention32_cross(int dtype, const AttnArgs& a, int n_qsplit, hipStream_t s) {
-  const int n_qblocks = (a.Tq + 255) / 256;
-  const dim3 grid(static_cast<unsigned>(n_qsplit * a.H * a.B)), block(512);
-  const size_t lds = static_cast<size_t>(1 + (a.S2 + BKV - 1) / BKV) * 2 * TILE;
+// Where these kernels apply: plan_attention (d3pm_plan.cpp).
+int mfma_attention32_cross(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_t s) {
+  const dim3 grid(p.grid), block(512);
   auto go = [&](auto* tag, auto MASK_) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
     constexpr bool MASK = decltype(MASK_)::value;
     D3PM_LDS_ATTR((&attn32_cross_hd64<U, MASK>), 5 * 2 * TILE);
-    attn32_cross_hd64<U, MASK><<<grid, block, lds, s>>>(static_cast<const U*>(a.Q), static_cast<const U*>(a.K), static_cast<const U*>(a.V),
+    attn32_cross_hd64<U, MASK><<<grid, block, p.lds, s>>>(static_cast<const U*>(a.Q), static_cast<const U*>(a.K), static_cast<const U*>(a.V),
                                                         static_cast<U*>(a.O), a.S, static_cast<const U*>(a.Q2), static_cast<const U*>(a.K2),
                                                         static_cast<const U*>(a.V2), static_cast<U*>(a.O2), a.S2, a.ldq, a.ldkv, a.ldo, a.Tq,
-                                                        a.scale, a.H, n_qblocks, n_qsplit, a.key_len, a.key_len2);
+                                                        a.scale, a.H, p.n_qblocks, p.n_qsplit, a.key_len, a.key_len2);
     D3PM_LAUNCH_CHECK();
     return D3PM_OK;
   };
   using Yes = std::integral_constant<bool, true>;
   using No = std::integral_constant<bool, false>;
-  if (a.key_len || a.key_len2) return dtype == D3PM_F16 ? go(static_cast<f16*>(nullptr), Yes{}) : go(static_cast<bf16*>(nullptr), Yes{});
+  if (p.masked) return dtype == D3PM_F16 ? go(static_cast<f16*>(nullptr), Yes{}) : go(static_cast<bf16*>(nullptr), Yes{});
   return dtype == D3PM_F16 ? go(static_cast<f16*>(nullptr), No{}) : go(static_cast<bf16*>(nullptr), No{});
 }
 
-int mfma_attention32(int dtype, const AttnArgs& a, hipStream_t s) {
-  const int n_qblocks = a.Tq / 128;
-  const dim3 grid(static_cast<unsigned>(n_qblocks * a.H * a.B)), block(256);
+int mfma_attention32(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_t s) {
+  const int n_qblocks = p.n_qblocks;
+  const dim3 grid(p.grid), block(256);
 #define D3PM_ATTN32(KERNEL, T)                                                                                                       \
   KERNEL<<<grid, block, 0, s>>>(static_cast<const T*>(a.Q), a.ldq, static_cast<const T*>(a.K), static_cast<const T*>(a.V), a.ldkv, \
                                 static_cast<T*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, a.key_len)
-  if (tune_of(a.tune).attn_query_groups != 33) {           // 33: the plain walk (A/B against the pipelined one)
-    if (a.key_len) {
+  if (p.kernel == ATTN_32P) {           // the pipelined walk; ATTN_32: the plain one (A/B)
+    if (p.masked) {
       if (dtype == D3PM_F16) D3PM_ATTN32((attn32p_hd64<f16, true>), f16); else D3PM_ATTN32((attn32p_hd64<bf16, true>), bf16);
     } else {
       if (dtype == D3PM_F16) D3PM_ATTN32((attn32p_hd64<f16>), f16); else D3PM_ATTN32((attn32p_hd64<bf16>), bf16);
@@ -868,7 +843,7 @@ int mfma_attention32(int dtype, const AttnArgs& a, hipStream_t s) {
     D3PM_LAUNCH_CHECK();
     return D3PM_OK;
   }
-  if (a.key_len) {
+  if (p.masked) {
     if (dtype == D3PM_F16) D3PM_ATTN32((attn32_hd64<f16, true>), f16); else D3PM_ATTN32((attn32_hd64<bf16, true>), bf16);
   } else {
     if (dtype == D3PM_F16) D3PM_ATTN32((attn32_hd64<f16>), f16); else D3PM_ATTN32((attn32_hd64<bf16>), bf16);

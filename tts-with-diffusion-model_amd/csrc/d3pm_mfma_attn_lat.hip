@@ -21,7 +21,7 @@
 // 3 us at the 60-70 GB/s one CU reads from L2), not the tile chain.  Hence opt-in: the automatic choice keeps one utterance on the
 // schedule -- and the bits -- of the batches up to ten.  Same numerics class as the other flash-style kernels (fp32 scores in the
 // log2 domain, un-normalised 16-bit probabilities, fp32 row sums): results agree with them to rounding noise, not bit for bit.
-#include "d3pm_kernels.h"
+#include "d3pm_plan.h"      // HD, BKV, ROWB, TILE and the AttnPlan the launcher takes
 
 namespace d3pm {
 namespace {
@@ -31,8 +31,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef short short4v __attribute__((ext_vector_type(4)));
 
-constexpr int HD = 64, BKV = 64, ROWB = 128, NS = 4;
-constexpr int TILE = BKV * ROWB;   // 8 KiB per K or V tile
+constexpr int NS = 4;
 constexpr int OSTR = 68;           // floats per query row of a partial O in LDS (64 + 4: 16-byte reads of 16 rows spread over the banks)
 constexpr float kDefer = 8.0f;
 
@@ -282,23 +281,12 @@ __global__ __launch_bounds__(256, 2) void attn_split_hd64(const T* __restrict__ 
   }
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 }  // namespace
 
-// one problem or a pair, no key lengths; the caller (mfma_attention) decides by grid size when this schedule is the one to run
-bool mfma_attention_split_supported(int dtype, const AttnArgs& a) {
-  if (dtype != D3PM_F16 && dtype != D3PM_BF16) return false;
-  if (a.hd != HD || a.key_len != nullptr || a.key_len2 != nullptr || a.S < 1 || a.Tq < 1) return false;
-  if (a.ldq % 8 || a.ldkv % 8 || a.ldo % 4) return false;
-  if (a.Q2 && !(a.S2 >= 1 && aligned(a.Q2, 16) && aligned(a.K2, 16) && aligned(a.V2, 16) && aligned(a.O2, 8))) return false;
-  return aligned(a.Q, 16) && aligned(a.K, 16) && aligned(a.V, 16) && aligned(a.O, 8);
-}
-
-int mfma_attention_split(int dtype, const AttnArgs& a, hipStream_t s) {
-  const int n_qblocks = (a.Tq + 31) / 32;
-  const int n_first = n_qblocks * a.H * a.B;
-  const dim3 grid(static_cast<unsigned>(n_first) * (a.Q2 ? 2 : 1)), block(256);
+// one problem or a pair, no key lengths; plan_attention (d3pm_plan.cpp) decides when this schedule is the one to run
+int mfma_attention_split(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_t s) {
+  const int n_qblocks = p.n_qblocks, n_first = p.n_first;
+  const dim3 grid(p.grid), block(256);
   if (dtype == D3PM_F16)
     attn_split_hd64<f16><<<grid, block, 0, s>>>(static_cast<const f16*>(a.Q), a.ldq, static_cast<const f16*>(a.K), static_cast<const f16*>(a.V),
                                                 a.ldkv, static_cast<f16*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks,

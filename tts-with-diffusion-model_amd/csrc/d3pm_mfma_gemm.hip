@@ -48,7 +48,6 @@
 namespace d3pm {
 namespace {
 
-constexpr int BM = 128, BN = 128;
 constexpr int TILE_BYTES = BM * ROW_BYTES;              // 16 KiB per operand tile
 
 
@@ -309,70 +308,26 @@ __global__ __launch_bounds__(256, 4) void gemm_mfma_128_persist(const T* __restr
 }
 
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 }  // namespace
 
-bool mfma_linear_supported(int dtype, const LinearArgs& a) {
-  if (dtype != D3PM_F16 && dtype != D3PM_BF16) return false;
-  if (a.M < 1 || a.N < 1 || a.K < BK || a.K % BK != 0) return false;
-  if (a.ldx % 8 != 0 || a.ldy % 8 != 0 || !aligned(a.X, 16) || !aligned(a.W, 16) || !aligned(a.Y, 16)) return false;
-  if (a.R1 && (a.ldr % 8 != 0 || a.N % 8 != 0 || !aligned(a.R1, 16))) return false;
-  if (a.R2 && !aligned(a.R2, 16)) return false;
-  if (static_cast<long long>(a.M) * a.N < 128 * 128) return false;     // not worth a 128^2 tile
-  const bool gelu = a.act == ACT_GELU, r1 = a.R1 != nullptr, r2 = a.R2 != nullptr, mk = a.row_mask != nullptr;
-  if (!fold_args_ok(a)) return false;
-  if (a.act == ACT_RELU || a.act == ACT_SILU) return !r1 && !mk && !a.fold_s && !a.stats_out;   // condition-encoder FFN epilogues
-  if (r2 && !r1) return false;
-  // instantiated epilogues: plain, GELU, R1, R1+R2, R1+mask
-  if (gelu && (r1 || mk)) return false;
-  if (mk && (!r1 || r2)) return false;
-  return true;
-}
-
-// d3pm_tuning.gemm_variant: 0 auto, 2 throughput (128 x 128 persistent over whole tiles), 3 the round-1 latency schedule
-// (128 x 128, two stages), 4 the latency schedule (64 x 64 tiles, whole-K panels), 5 throughput with one 128 x 128 tile per
-// workgroup, 6 / 7 / 8 big tiles (192 x 256 / 96 x 512 / 192 x 128, d3pm_mfma_gemm_big.hip) wherever they apply, else as auto
-// without big tiles.  gemm_persist_slots: resident workgroups of the persistent schedule (1024 = 4 per CU x 256 CUs).
-bool panel64_linear_supported(int dtype, const LinearArgs& a);
-int panel64_linear(int dtype, const LinearArgs& a, hipStream_t s);
-int big_linear_tile(int dtype, const LinearArgs& a, int want);
-int big_linear(int dtype, const LinearArgs& a, int id, hipStream_t s);
-
-// the big-tile geometry mfma_linear takes for `a` (d3pm_mfma_gemm_big.hip), 0 = another family
-static int mfma_linear_big_id(int dtype, const LinearArgs& a) {
-  const int v = tune_of(a.tune).gemm_variant;
-  if (!(v == 0 || (v >= 6 && v <= 8))) return 0;
-  return big_linear_tile(dtype, a, v == 6 ? 2 : v == 7 ? 1 : v == 8 ? 3 : 0);
-}
-
-bool mfma_linear_takes_big_tiles(int dtype, const LinearArgs& a) { return mfma_linear_supported(dtype, a) && mfma_linear_big_id(dtype, a) != 0; }
-
-int mfma_linear(int dtype, const LinearArgs& a, hipStream_t s) {
-  // All schedules accumulate in the same order, so the choice never changes a bit of the result.
-  const bool ffn_act = a.act == ACT_RELU || a.act == ACT_SILU;
-  const d3pm_tuning& tn = tune_of(a.tune);
-  const int g_gemm_variant = tn.gemm_variant, g_persist_slots = tn.gemm_persist_slots >= 8 ? (tn.gemm_persist_slots & ~7) : 1024;
-  const bool autosel = g_gemm_variant == 0 || (g_gemm_variant >= 6 && g_gemm_variant <= 8);
-  if (const int id = mfma_linear_big_id(dtype, a)) return big_linear(dtype, a, id, s);
-  if (a.moment_quads) {            // the quad format of the row moments exists in the big-tile epilogues only
-    set_error("row-moment quads: %d x %d x %d does not run on big tiles", a.M, a.N, a.K);
-    return D3PM_E_SHAPE;
+// The launch the plan names (d3pm_plan.cpp: plan_linear chose the family, the schedule, the grid and the LDS).  All schedules
+// accumulate in the same order, so the choice never changes a bit of the result.
+int mfma_linear(int dtype, const LinearArgs& a, const LinearPlan& p, hipStream_t s) {
+  switch (p.kernel) {
+    case LIN_BIG: return big_linear(dtype, a, p, s);
+    case LIN_PANEL64: return panel64_linear(dtype, a, p, s);
+    case LIN_128_PF: case LIN_128_PERSIST: case LIN_128_GLDS: break;
+    case LIN_QUADS_REFUSED:
+      set_error("row-moment quads: %d x %d x %d does not run on big tiles", a.M, a.N, a.K);
+      return D3PM_E_SHAPE;
+    default:
+      set_error("projection %d x %d x %d: not planned for the MFMA family", a.M, a.N, a.K);
+      return D3PM_E_SHAPE;
   }
-  // one or two utterances: 64 x 64 tiles with whole-K panels in flight (d3pm_mfma_gemm_lat.hip); 4 forces it for any M
-  if ((g_gemm_variant == 4 || (autosel && a.M <= 1536)) && panel64_linear_supported(dtype, a)) return panel64_linear(dtype, a, s);
-  const bool latency = !ffn_act && (g_gemm_variant == 3 || (autosel && a.M <= 1536));
-  const int n_tiles = (a.N + BN - 1) / BN, m_tiles = (a.M + BM - 1) / BM;
-  // shapes made of whole tiles go through the persistent kernel once there are enough tiles to fill the chip twice
-  // over (a ragged edge would need a second launch that costs more than persistence gains: measured on N = 1025)
-  const bool persist = !latency && !ffn_act && (autosel || g_gemm_variant == 2) && a.M % BM == 0 &&
-                       a.N % BN == 0 && static_cast<long long>(n_tiles) * m_tiles >= 2 * 256 &&
-                       static_cast<long long>(BM) * a.ldx * 2 < (1ll << 31) && static_cast<long long>(BN) * a.K * 2 < (1ll << 31);
-  const size_t lds = (latency ? 4 : 2) * TILE_BYTES;   // 64 KiB: two workgroups per CU; 32 KiB: four
-  const int tiles_total = n_tiles * m_tiles, want = (tiles_total + 7) & ~7;
-  const dim3 grid(static_cast<unsigned>(persist ? (want < g_persist_slots ? want : g_persist_slots) : tiles_total)), block(256);
-  const int epi = (a.act == ACT_GELU ? EPI_GELU : a.act == ACT_RELU ? EPI_RELU : a.act == ACT_SILU ? EPI_SILU : 0) |
-                  (a.R1 ? (a.R2 ? EPI_R2 : EPI_R1) : 0) | (a.row_mask ? EPI_MASK : 0) | (a.fold_s ? EPI_LNF : 0) | (a.stats_out ? EPI_STATS : 0);
+  const bool latency = p.kernel == LIN_128_PF, persist = p.kernel == LIN_128_PERSIST;
+  const size_t lds = p.lds;
+  const int n_tiles = p.n_tiles, tiles_total = p.tiles_total;
+  const dim3 grid(p.grid), block(256);
   const EpiFold ef = epi_fold_of(a);
 
 #define D3PM_GEMM(KERNEL, ...)                                                                                  \
@@ -392,7 +347,7 @@ int mfma_linear(int dtype, const LinearArgs& a, hipStream_t s) {
   } while (0)
   auto go = [&](auto* tag) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
-    switch (epi) {   // the epilogues the denoiser and the condition encoders use
+    switch (p.epi) {   // kEpi128 (d3pm_plan.cpp): the epilogues the denoiser and the condition encoders use
       case 0: D3PM_GEMM_EPI(0);
       case EPI_GELU: D3PM_GEMM_EPI(EPI_GELU);
       case EPI_R1: D3PM_GEMM_EPI(EPI_R1);
@@ -405,7 +360,7 @@ int mfma_linear(int dtype, const LinearArgs& a, hipStream_t s) {
       case EPI_R1 | EPI_MASK | EPI_STATS: D3PM_GEMM_EPI(EPI_R1 | EPI_MASK | EPI_STATS);
       case EPI_RELU: D3PM_GEMM((gemm_mfma_128_glds<U, EPI_RELU>));
       case EPI_SILU: D3PM_GEMM((gemm_mfma_128_glds<U, EPI_SILU>));
-      default: break;
+      default: break;      // no plan names another one (tests/test_launch_plan_api.py)
     }
     return D3PM_E_SHAPE;
   };

@@ -10,7 +10,7 @@
 // (profiles/round1_*: 577 .. 853 TFLOP/s by shape, 0.30 of peak over the loop).  The lever is bytes per flop:
 //   * a wave owns a 96 x 64 sub-tile (6 x 4 MFMA tiles of 16 x 16, 96 accumulator registers); a workgroup is 2 x 2 of them (192 x 128,
 //     77 flop per staged byte, TWO workgroups per CU: the default since round 3 -- in the sampler's loop two independent
-//     workgroups hide cold operands and each other's epilogue better than one, big_linear_tile below) or eight (192 x 256 / 96 x 512,
+//     workgroups hide cold operands and each other's epilogue better than one, big_tile in d3pm_plan.cpp) or eight (192 x 256 / 96 x 512,
 //     110 / 81 flop per staged byte, one workgroup per CU);
 //   * the tile shapes divide the bench workload exactly: M = 32 utterances x 768 canvas rows = 128 x 192 rows, N = 512 / 1024 /
 //     1536 / 2048 = 4 / 8 / 12 / 16 x 128 columns, i.e. 512 / 1024 / 1536 / 2048 tiles = 1 / 2 / 3 / 4 whole rounds over the 512
@@ -539,147 +539,78 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 
 
 }  // namespace
 
-// Tile geometries: id 1 = 96 x 512 (1 x 8 waves), 2 = 192 x 256 (2 x 4 waves), 3 = 192 x 128 (2 x 2 waves, two workgroups per CU)
-static void big_geometry(int id, int& tm, int& tn, int& waves) {
-  tm = id == 1 ? 96 : 192;
-  tn = id == 1 ? 512 : id == 2 ? 256 : 128;
-  waves = id == 3 ? 4 : 8;
-}
-
-// 0 = not applicable, else the geometry id.  `want` (tuning knob): 0 auto, 1 / 2 / 3 forced.
-int big_linear_tile(int dtype, const LinearArgs& a, int want) {
-  if (dtype != D3PM_F16 && dtype != D3PM_BF16) return 0;
-  if (a.K < 4 * BK || a.K % (2 * BK) != 0 || a.M < 96 || a.N < 128) return 0;
-  if (a.ldx % 8 != 0 || a.ldy % 8 != 0 || !aligned16(a.X) || !aligned16(a.W) || !aligned16(a.Y)) return 0;
-  if (a.R1 && (a.ldr % 8 != 0 || !aligned16(a.R1))) return 0;
-  if (a.R2 && (!a.R1 || !aligned16(a.R2))) return 0;
-  if (!fold_args_ok(a) || (a.fold_s && a.K != 512)) return 0;      // the big tile prefetches the 16 moment parts of a 512-wide row
-  const bool gelu = a.act == ACT_GELU, r1 = a.R1 != nullptr, r2 = a.R2 != nullptr, mk = a.row_mask != nullptr;
-  if (a.act != ACT_NONE && !gelu) return 0;
-  if (gelu && (r1 || mk)) return 0;                       // instantiated epilogues: plain, GELU, R1, R1+R2, R1+mask
-  if (mk && (!r1 || r2)) return 0;
-  if (a.ldx >= (1 << 24) || a.K >= (1 << 24)) return 0;       // 32-bit per-lane DMA offsets
-  auto fits = [&](int id, bool forced) {
-    int tm, tn, waves;
-    big_geometry(id, tm, tn, waves);
-    if (a.M % tm != 0 || a.N % tn != 0) return false;
-    if (forced) return true;                                        // tuning knob / kernel tests: any shape of whole tiles
-    const long long slots = 256 * (8 / waves);
-    const long long tiles = static_cast<long long>(a.M / tm) * (a.N / tn), rounds = (tiles + slots - 1) / slots;
-    return tiles * 5 >= slots * 4 && tiles * 100 >= rounds * slots * 85;   // >= 85 % of the slot-rounds do work
-  };
-  if (want >= 1 && want <= 3) return fits(want, true) ? want : 0;
-  // Under the GELU epilogue 192 x 128 tiles win clearly: its VALU work only overlaps with MFMAs when a second workgroup shares the
-  // CU (two 4-wave workgroups per CU).  For the other K = 512 projections the microbenchmark cannot tell 192 x 128 from 192 x 256
-  // (qkv 43.3 vs 44.5 us, merged q 30.5 vs 31.4: profiles/round3_v_ab_gemm_geometries.txt) but the sampler's loop can, where the
-  // operands arrive cold from the previous launch and two independent workgroups per CU hide that better than one: GEMM class
-  // 1317 -> 1241 us per iteration, 97.8 k -> 101.2 k tokens/s with 192 x 128 everywhere (interleaved arms of bench.py --tune
-  // gemm_variant=8, profiles/round3_v_ab_tune_geom.txt)
-  // -- and fc2 (K = 2048) likewise: with 192 x 128 for the K = 512 projections only the class is at 1294 us, with fc2 too at 1249
-  // (profiles/round3_w_ab_tune_geom.txt).  So: two 4-wave workgroups per CU wherever that geometry fills its rounds.
-  if (fits(3, false)) return 3;
-  if (fits(2, false)) return 2;
-  if (fits(1, false)) return 1;
-  // Mid-size batches (the VCTK config: 32 x 384 rows; 8 .. 16 utterances of the libritts shape) leave the chip partly idle with
-  // every big tile, yet 192 x 128 tiles of four waves still beat the 128 x 128 kernels there once at least half (long K) or all
-  // of the CUs get one: measured at M = 12288 / 6144 (tests/ab_gemm_shapes.py, profiles/round3_f_ab_gemm_shapes.txt): qkv 24.1 vs
-  // 26.6 / 15.6 vs 17.2 us, out-projection 12.8 vs 15.8 us, fc2 31.8 vs 39.0 / 29.5 vs 35.4 us
-  if (a.M % 192 == 0 && a.N % 128 == 0) {
-    const long long tiles = static_cast<long long>(a.M / 192) * (a.N / 128);
-    if (tiles >= (a.K >= 1024 ? 128 : 256)) return 3;
-  }
-  return 0;
-}
-
+// Which shapes take which geometry (1 = 96 x 512, 1 x 8 waves; 2 = 192 x 256, 2 x 4; 3 = 192 x 128, 2 x 2, two workgroups per CU),
+// with which grid and LDS: d3pm_plan.cpp (big_tile, big_plan).  The launchers below instantiate what a plan names.
 template <typename U, int E, int WM, int WN>
-static int big_launch(const LinearArgs& a, int n_tiles, int tiles_total, dim3 grid, size_t lds, hipStream_t s) {
+static int big_launch(const LinearArgs& a, const LinearPlan& p, hipStream_t s) {
   D3PM_LDS_ATTR((&gemm_mfma_big<U, E, WM, WN>), 160 * 1024);
-  gemm_mfma_big<U, E, WM, WN><<<grid, dim3(WM * WN * 64), lds, s>>>(
+  gemm_mfma_big<U, E, WM, WN><<<dim3(p.grid), dim3(WM * WN * 64), p.lds, s>>>(
       static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
-      static_cast<const U*>(a.R1), static_cast<const U*>(a.R2), a.ldr, a.row_mask, a.mask_period, a.M, a.N, a.K, n_tiles,
-      tiles_total, RowPanelArgs<U>{}, epi_fold_of(a));
+      static_cast<const U*>(a.R1), static_cast<const U*>(a.R2), a.ldr, a.row_mask, a.mask_period, a.M, a.N, a.K, p.n_tiles,
+      p.tiles_total, RowPanelArgs<U>{}, epi_fold_of(a));
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }
 
 template <typename U, int E>
-static int big_launch_geometry(int id, const LinearArgs& a, int n_tiles, int tiles_total, dim3 grid, size_t lds, hipStream_t s) {
-  if (id == 1) return big_launch<U, E, 1, 8>(a, n_tiles, tiles_total, grid, lds, s);
-  if (id == 2) return big_launch<U, E, 2, 4>(a, n_tiles, tiles_total, grid, lds, s);
-  return big_launch<U, E, 2, 2>(a, n_tiles, tiles_total, grid, lds, s);
+static int big_launch_geometry(const LinearArgs& a, const LinearPlan& p, hipStream_t s) {
+  if (p.geom == 1) return big_launch<U, E, 1, 8>(a, p, s);
+  if (p.geom == 2) return big_launch<U, E, 2, 4>(a, p, s);
+  return big_launch<U, E, 2, 2>(a, p, s);
 }
 
 // Both cross-attention out-projections (ar_discrete.py:138,142: the SAME weights) in one launch of the ordinary big-tile geometry:
 // a second product through the tile, the first result kept packed in 48 registers, x' = rn(rn(R1 + rn(X W^T + b)) + rn(X2 W^T + b))
 // -- the bits of the two launches it replaces -- and, with stats_out, the row moments of x' for the folded norm3 of fc1.
-bool big_dual_supported(int dtype, const LinearArgs& a, const void* X2) {
-  if (!X2 || !aligned16(X2) || !a.R1 || a.R2 || a.row_mask || a.act != ACT_NONE || !a.bias || a.fold_s) return false;
-  return big_linear_tile(dtype, a, tune_of(a.tune).gemm_variant == 6 ? 2 : tune_of(a.tune).gemm_variant == 8 ? 3 : 0) >= 2;
-}
-
 template <typename U, int E, int WM, int WN>
-static int big_dual_launch(const LinearArgs& a, const void* X2, int n_tiles, int tiles_total, dim3 grid, size_t lds, hipStream_t s) {
+static int big_dual_launch(const LinearArgs& a, const void* X2, const LinearPlan& p, hipStream_t s) {
   D3PM_LDS_ATTR((&gemm_mfma_big<U, E, WM, WN, FUSE_DUAL>), 160 * 1024);
   RowPanelArgs<U> rp{};
   rp.X2 = static_cast<const U*>(X2);
-  gemm_mfma_big<U, E, WM, WN, FUSE_DUAL><<<grid, dim3(WM * WN * 64), lds, s>>>(
+  gemm_mfma_big<U, E, WM, WN, FUSE_DUAL><<<dim3(p.grid), dim3(WM * WN * 64), p.lds, s>>>(
       static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
-      static_cast<const U*>(a.R1), nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, n_tiles, tiles_total, rp, epi_fold_of(a));
+      static_cast<const U*>(a.R1), nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, p.n_tiles, p.tiles_total, rp, epi_fold_of(a));
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }
 
-int big_dual(int dtype, const LinearArgs& a, const void* X2, hipStream_t s) {
-  const int id = big_linear_tile(dtype, a, tune_of(a.tune).gemm_variant == 6 ? 2 : tune_of(a.tune).gemm_variant == 8 ? 3 : 0);
-  int tm, tn, waves;
-  big_geometry(id, tm, tn, waves);
-  const int n_tiles = a.N / tn, tiles_total = (a.M / tm) * n_tiles;
-  const int slots = 256 * (8 / waves), want = (tiles_total + 7) & ~7;
-  const dim3 grid(static_cast<unsigned>(want < slots ? want : slots));
-  const size_t lds = 2 * static_cast<size_t>(tm + tn) * ROW_BYTES;
+int big_dual(int dtype, const LinearArgs& a, const void* X2, const LinearPlan& p, hipStream_t s) {
   auto go = [&](auto* tag) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
-    if (a.stats_out && a.moment_quads)
-      return id == 2 ? big_dual_launch<U, EPI_R2 | EPI_STATS | EPI_QUADS, 2, 4>(a, X2, n_tiles, tiles_total, grid, lds, s)
-                     : big_dual_launch<U, EPI_R2 | EPI_STATS | EPI_QUADS, 2, 2>(a, X2, n_tiles, tiles_total, grid, lds, s);
-    if (a.stats_out)
-      return id == 2 ? big_dual_launch<U, EPI_R2 | EPI_STATS, 2, 4>(a, X2, n_tiles, tiles_total, grid, lds, s)
-                     : big_dual_launch<U, EPI_R2 | EPI_STATS, 2, 2>(a, X2, n_tiles, tiles_total, grid, lds, s);
-    return id == 2 ? big_dual_launch<U, EPI_R2, 2, 4>(a, X2, n_tiles, tiles_total, grid, lds, s)
-                   : big_dual_launch<U, EPI_R2, 2, 2>(a, X2, n_tiles, tiles_total, grid, lds, s);
+    switch (p.epi) {      // kEpiBigDual (d3pm_plan.cpp); geometry 2 or 3
+      case EPI_R2 | EPI_STATS | EPI_QUADS:
+        return p.geom == 2 ? big_dual_launch<U, EPI_R2 | EPI_STATS | EPI_QUADS, 2, 4>(a, X2, p, s)
+                           : big_dual_launch<U, EPI_R2 | EPI_STATS | EPI_QUADS, 2, 2>(a, X2, p, s);
+      case EPI_R2 | EPI_STATS:
+        return p.geom == 2 ? big_dual_launch<U, EPI_R2 | EPI_STATS, 2, 4>(a, X2, p, s) : big_dual_launch<U, EPI_R2 | EPI_STATS, 2, 2>(a, X2, p, s);
+      case EPI_R2: return p.geom == 2 ? big_dual_launch<U, EPI_R2, 2, 4>(a, X2, p, s) : big_dual_launch<U, EPI_R2, 2, 2>(a, X2, p, s);
+      default: break;      // no plan names another one (tests/test_launch_plan_api.py)
+    }
+    return D3PM_E_SHAPE;
   };
   return dtype == D3PM_F16 ? go(static_cast<f16*>(nullptr)) : go(static_cast<bf16*>(nullptr));
 }
 
-int big_linear(int dtype, const LinearArgs& a, int id, hipStream_t s) {
-  int tm, tn, waves;
-  big_geometry(id, tm, tn, waves);
-  const int n_tiles = a.N / tn, tiles_total = (a.M / tm) * n_tiles;
-  const int slots = 256 * (8 / waves), want = (tiles_total + 7) & ~7;
-  const dim3 grid(static_cast<unsigned>(want < slots ? want : slots));
-  const size_t lds = 2 * static_cast<size_t>(tm + tn) * ROW_BYTES;
-  const int epi = (a.act == ACT_GELU ? EPI_GELU : 0) | (a.R1 ? (a.R2 ? EPI_R2 : EPI_R1) : 0) | (a.row_mask ? EPI_MASK : 0) |
-                  (a.fold_s ? EPI_LNF : 0) | (a.stats_out ? EPI_STATS : 0) | (a.moment_quads ? EPI_QUADS : 0);
+int big_linear(int dtype, const LinearArgs& a, const LinearPlan& p, hipStream_t s) {
   auto go = [&](auto* tag) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
-    switch (epi) {
-      case EPI_LNF: return big_launch_geometry<U, EPI_LNF>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_LNF | EPI_GELU: return big_launch_geometry<U, EPI_LNF | EPI_GELU>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R1 | EPI_STATS: return big_launch_geometry<U, EPI_R1 | EPI_STATS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R2 | EPI_STATS: return big_launch_geometry<U, EPI_R2 | EPI_STATS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R1 | EPI_MASK | EPI_STATS: return big_launch_geometry<U, EPI_R1 | EPI_MASK | EPI_STATS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_LNF | EPI_QUADS: return big_launch_geometry<U, EPI_LNF | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_LNF | EPI_GELU | EPI_QUADS: return big_launch_geometry<U, EPI_LNF | EPI_GELU | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R1 | EPI_STATS | EPI_QUADS: return big_launch_geometry<U, EPI_R1 | EPI_STATS | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R2 | EPI_STATS | EPI_QUADS: return big_launch_geometry<U, EPI_R2 | EPI_STATS | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R1 | EPI_MASK | EPI_STATS | EPI_QUADS:
-        return big_launch_geometry<U, EPI_R1 | EPI_MASK | EPI_STATS | EPI_QUADS>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case 0: return big_launch_geometry<U, 0>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_GELU: return big_launch_geometry<U, EPI_GELU>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R1: return big_launch_geometry<U, EPI_R1>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R2: return big_launch_geometry<U, EPI_R2>(id, a, n_tiles, tiles_total, grid, lds, s);
-      case EPI_R1 | EPI_MASK: return big_launch_geometry<U, EPI_R1 | EPI_MASK>(id, a, n_tiles, tiles_total, grid, lds, s);
-      default: break;
+    switch (p.epi) {      // kEpiBig (d3pm_plan.cpp)
+      case EPI_LNF: return big_launch_geometry<U, EPI_LNF>(a, p, s);
+      case EPI_LNF | EPI_GELU: return big_launch_geometry<U, EPI_LNF | EPI_GELU>(a, p, s);
+      case EPI_R1 | EPI_STATS: return big_launch_geometry<U, EPI_R1 | EPI_STATS>(a, p, s);
+      case EPI_R2 | EPI_STATS: return big_launch_geometry<U, EPI_R2 | EPI_STATS>(a, p, s);
+      case EPI_R1 | EPI_MASK | EPI_STATS: return big_launch_geometry<U, EPI_R1 | EPI_MASK | EPI_STATS>(a, p, s);
+      case EPI_LNF | EPI_QUADS: return big_launch_geometry<U, EPI_LNF | EPI_QUADS>(a, p, s);
+      case EPI_LNF | EPI_GELU | EPI_QUADS: return big_launch_geometry<U, EPI_LNF | EPI_GELU | EPI_QUADS>(a, p, s);
+      case EPI_R1 | EPI_STATS | EPI_QUADS: return big_launch_geometry<U, EPI_R1 | EPI_STATS | EPI_QUADS>(a, p, s);
+      case EPI_R2 | EPI_STATS | EPI_QUADS: return big_launch_geometry<U, EPI_R2 | EPI_STATS | EPI_QUADS>(a, p, s);
+      case EPI_R1 | EPI_MASK | EPI_STATS | EPI_QUADS: return big_launch_geometry<U, EPI_R1 | EPI_MASK | EPI_STATS | EPI_QUADS>(a, p, s);
+      case 0: return big_launch_geometry<U, 0>(a, p, s);
+      case EPI_GELU: return big_launch_geometry<U, EPI_GELU>(a, p, s);
+      case EPI_R1: return big_launch_geometry<U, EPI_R1>(a, p, s);
+      case EPI_R2: return big_launch_geometry<U, EPI_R2>(a, p, s);
+      case EPI_R1 | EPI_MASK: return big_launch_geometry<U, EPI_R1 | EPI_MASK>(a, p, s);
+      default: break;      // no plan names another one (tests/test_launch_plan_api.py)
     }
     return D3PM_E_SHAPE;
   };

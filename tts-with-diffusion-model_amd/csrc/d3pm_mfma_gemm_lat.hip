@@ -28,7 +28,6 @@
 namespace d3pm {
 namespace {
 
-constexpr int KC = 256;                      // k per round
 // Tile geometries (TM x TN, four waves as 2 x 2): 64 x 64 is the base; 96 x 64 turns the 288 / 384 tiles of the qkv / fc1
 // projections of one utterance (two rounds over 256 CUs at one workgroup per CU) into 192 / 256 (one round, one DMA flight);
 // 32 x 64 gives the N = 512 projections (out-proj, fc2: 96 tiles of 64 x 64) 192 workgroups with half the X panel each.
@@ -189,112 +188,70 @@ __global__ __launch_bounds__(256, 1) void gemm_mfma_panel64(const T* __restrict_
                                                             n0 + wn * (TN / 2), lane, nullptr, &pre, &ef);
 }
 
-inline bool aligned16l(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; }
-
 }  // namespace
 
-bool panel64_linear_supported(int dtype, const LinearArgs& a) {
-  if (dtype != D3PM_F16 && dtype != D3PM_BF16) return false;
-  if (a.M < 1 || a.N < 16 || a.K < KC || a.K % KC != 0) return false;
-  if (a.ldx % 8 != 0 || a.ldy % 8 != 0 || !aligned16l(a.X) || !aligned16l(a.W) || !aligned16l(a.Y)) return false;
-  if (a.R1 && (a.ldr % 8 != 0 || a.N % 8 != 0 || !aligned16l(a.R1))) return false;
-  if (a.R2 && (!a.R1 || !aligned16l(a.R2))) return false;
-  const bool gelu = a.act == ACT_GELU, r1 = a.R1 != nullptr, r2 = a.R2 != nullptr, mk = a.row_mask != nullptr;
-  if (a.act != ACT_NONE && !gelu) return false;
-  if (gelu && (r1 || mk)) return false;       // instantiated epilogues: plain, GELU, R1, R1+R2, R1+mask; LNF, LNF+GELU; R1 / R2 / R1+mask + STATS
-  if (mk && (!r1 || r2)) return false;
-  return fold_args_ok(a);
-}
-
-// d3pm_tuning.lat_tile: 0 auto, 1 / 2 / 3 = always 64 x 64 / 96 x 64 / 32 x 64.  Auto: the geometry with the fewest rounds over the
-// 256 CUs (one workgroup per CU), then the one with the most workgroups (the time of a launch here is the latency of one
-// workgroup's chain -- DMA flight, k-steps, epilogue -- so a round less or a shorter chain is what pays; flops do not matter)
-static int lat_geometry(const LinearArgs& a) {
-  const int g_lat_tile = tune_of(a.tune).lat_tile;
-  if (g_lat_tile >= 1 && g_lat_tile <= 3) return g_lat_tile - 1;
-  static const int tm[3] = {64, 96, 32};
-  int best = 0;
-  long long best_rounds = 0, best_tiles = 0;
-  for (int g = 0; g < 3; ++g) {
-    const long long tiles = static_cast<long long>((a.M + tm[g] - 1) / tm[g]) * ((a.N + 63) / 64), rounds = (tiles + 255) / 256;
-    if (g == 0 || rounds < best_rounds || (rounds == best_rounds && tiles > best_tiles)) { best = g; best_rounds = rounds; best_tiles = tiles; }
-  }
-  return best;
-}
-
+// Which projections come here, with which of the three geometries: d3pm_plan.cpp (panel64_ok, panel64_geometry).
 template <typename U, int E, int TM, int TN>
-static int panel64_launch(const LinearArgs& a, hipStream_t s) {
+static int panel64_launch(const LinearArgs& a, const LinearPlan& p, hipStream_t s) {
   using G = LatGeom<TM, TN>;
-  constexpr size_t lds = 2 * G::BUF;
-  const int n_tiles = (a.N + TN - 1) / TN, m_tiles = (a.M + TM - 1) / TM;
-  D3PM_LDS_ATTR((&gemm_mfma_panel64<U, E, TM, TN>), lds);
-  gemm_mfma_panel64<U, E, TM, TN><<<dim3(static_cast<unsigned>(n_tiles * m_tiles)), dim3(256), lds, s>>>(
+  D3PM_LDS_ATTR((&gemm_mfma_panel64<U, E, TM, TN>), 2 * G::BUF);
+  gemm_mfma_panel64<U, E, TM, TN><<<dim3(p.grid), dim3(256), p.lds, s>>>(
       static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
-      static_cast<const U*>(a.R1), static_cast<const U*>(a.R2), a.ldr, a.row_mask, a.mask_period, a.M, a.N, a.K, n_tiles,
+      static_cast<const U*>(a.R1), static_cast<const U*>(a.R2), a.ldr, a.row_mask, a.mask_period, a.M, a.N, a.K, p.n_tiles,
       epi_fold_of(a));
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }
 
-template <typename U, int E> static int panel64_geometry(const LinearArgs& a, hipStream_t s) {
-  switch (lat_geometry(a)) {
-    case 1: return panel64_launch<U, E, 96, 64>(a, s);
-    case 2: return panel64_launch<U, E, 32, 64>(a, s);
-    default: return panel64_launch<U, E, 64, 64>(a, s);
+template <typename U, int E> static int panel64_geometry(const LinearArgs& a, const LinearPlan& p, hipStream_t s) {
+  switch (p.geom) {
+    case 1: return panel64_launch<U, E, 96, 64>(a, p, s);
+    case 2: return panel64_launch<U, E, 32, 64>(a, p, s);
+    default: return panel64_launch<U, E, 64, 64>(a, p, s);
   }
 }
 
 // x' = rn(rn(R1 + rn(X W^T + b)) + rn(X2 W^T + b)) in one launch (the two cross-attention out-projections of a DiT block at one or
 // two utterances): whole 32 x 64 tiles, K = 512 (both operand panels and the weight panel resident: 128 KiB)
-bool panel64_dual_supported(int dtype, const LinearArgs& a, const void* X2) {
-  if (!panel64_linear_supported(dtype, a) || !X2 || !aligned16l(X2)) return false;
-  if (a.K != 2 * KC || a.M % 32 != 0 || a.N % 64 != 0 || a.M > 2048) return false;
-  if (a.fold_s || a.M % 32 != 0) return false;
-  return a.R1 && !a.R2 && !a.row_mask && a.act == ACT_NONE && a.bias;
+template <typename U, int E>
+static int panel64_dual_launch(const LinearArgs& a, const void* X2, const LinearPlan& p, const EpiFold& ef, hipStream_t s) {
+  using G = LatGeom<32, 64>;
+  D3PM_LDS_ATTR((&gemm_mfma_panel64<U, E, 32, 64, true>), 2 * G::BUF + 2 * G::XOPER);
+  gemm_mfma_panel64<U, E, 32, 64, true><<<dim3(p.grid), dim3(256), p.lds, s>>>(
+      static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
+      static_cast<const U*>(a.R1), nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, p.n_tiles, ef, static_cast<const U*>(X2));
+  D3PM_LAUNCH_CHECK();
+  return D3PM_OK;
 }
 
-int panel64_dual(int dtype, const LinearArgs& a, const void* X2, hipStream_t s) {
-  using G = LatGeom<32, 64>;
-  constexpr size_t lds = 2 * G::BUF + 2 * G::XOPER;
-  const int n_tiles = a.N / 64, m_tiles = a.M / 32;
+int panel64_dual(int dtype, const LinearArgs& a, const void* X2, const LinearPlan& p, hipStream_t s) {
   auto go = [&](auto* tag) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
-    if (a.stats_out) {
-      D3PM_LDS_ATTR((&gemm_mfma_panel64<U, EPI_R1 | EPI_STATS, 32, 64, true>), lds);
-      gemm_mfma_panel64<U, EPI_R1 | EPI_STATS, 32, 64, true><<<dim3(static_cast<unsigned>(n_tiles * m_tiles)), dim3(256), lds, s>>>(
-          static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
-          static_cast<const U*>(a.R1), nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, n_tiles, epi_fold_of(a),
-          static_cast<const U*>(X2));
-    } else {
-      D3PM_LDS_ATTR((&gemm_mfma_panel64<U, EPI_R1, 32, 64, true>), lds);
-      gemm_mfma_panel64<U, EPI_R1, 32, 64, true><<<dim3(static_cast<unsigned>(n_tiles * m_tiles)), dim3(256), lds, s>>>(
-          static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
-          static_cast<const U*>(a.R1), nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, n_tiles, EpiFold{},
-          static_cast<const U*>(X2));
+    switch (p.epi) {      // kEpiPanel64Dual (d3pm_plan.cpp)
+      case EPI_R1 | EPI_STATS: return panel64_dual_launch<U, EPI_R1 | EPI_STATS>(a, X2, p, epi_fold_of(a), s);
+      case EPI_R1: return panel64_dual_launch<U, EPI_R1>(a, X2, p, EpiFold{}, s);
+      default: break;      // no plan names another one (tests/test_launch_plan_api.py)
     }
-    D3PM_LAUNCH_CHECK();
-    return D3PM_OK;
+    return D3PM_E_SHAPE;
   };
   return dtype == D3PM_F16 ? go(static_cast<f16*>(nullptr)) : go(static_cast<bf16*>(nullptr));
 }
 
-int panel64_linear(int dtype, const LinearArgs& a, hipStream_t s) {
-  const int epi = (a.act == ACT_GELU ? EPI_GELU : 0) | (a.R1 ? (a.R2 ? EPI_R2 : EPI_R1) : 0) | (a.row_mask ? EPI_MASK : 0) |
-                  (a.fold_s ? EPI_LNF : 0) | (a.stats_out ? EPI_STATS : 0);
+int panel64_linear(int dtype, const LinearArgs& a, const LinearPlan& p, hipStream_t s) {
   auto go = [&](auto* tag) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
-    switch (epi) {
-      case 0: return panel64_geometry<U, 0>(a, s);
-      case EPI_GELU: return panel64_geometry<U, EPI_GELU>(a, s);
-      case EPI_R1: return panel64_geometry<U, EPI_R1>(a, s);
-      case EPI_R2: return panel64_geometry<U, EPI_R2>(a, s);
-      case EPI_R1 | EPI_MASK: return panel64_geometry<U, EPI_R1 | EPI_MASK>(a, s);
-      case EPI_LNF: return panel64_geometry<U, EPI_LNF>(a, s);
-      case EPI_LNF | EPI_GELU: return panel64_geometry<U, EPI_LNF | EPI_GELU>(a, s);
-      case EPI_R1 | EPI_STATS: return panel64_geometry<U, EPI_R1 | EPI_STATS>(a, s);
-      case EPI_R2 | EPI_STATS: return panel64_geometry<U, EPI_R2 | EPI_STATS>(a, s);
-      case EPI_R1 | EPI_MASK | EPI_STATS: return panel64_geometry<U, EPI_R1 | EPI_MASK | EPI_STATS>(a, s);
-      default: break;
+    switch (p.epi) {      // kEpiPanel64 (d3pm_plan.cpp)
+      case 0: return panel64_geometry<U, 0>(a, p, s);
+      case EPI_GELU: return panel64_geometry<U, EPI_GELU>(a, p, s);
+      case EPI_R1: return panel64_geometry<U, EPI_R1>(a, p, s);
+      case EPI_R2: return panel64_geometry<U, EPI_R2>(a, p, s);
+      case EPI_R1 | EPI_MASK: return panel64_geometry<U, EPI_R1 | EPI_MASK>(a, p, s);
+      case EPI_LNF: return panel64_geometry<U, EPI_LNF>(a, p, s);
+      case EPI_LNF | EPI_GELU: return panel64_geometry<U, EPI_LNF | EPI_GELU>(a, p, s);
+      case EPI_R1 | EPI_STATS: return panel64_geometry<U, EPI_R1 | EPI_STATS>(a, p, s);
+      case EPI_R2 | EPI_STATS: return panel64_geometry<U, EPI_R2 | EPI_STATS>(a, p, s);
+      case EPI_R1 | EPI_MASK | EPI_STATS: return panel64_geometry<U, EPI_R1 | EPI_MASK | EPI_STATS>(a, p, s);
+      default: break;      // no plan names another one (tests/test_launch_plan_api.py)
     }
     return D3PM_E_SHAPE;
   };

@@ -4,7 +4,7 @@
 #pragma once
 #include <type_traits>
 
-#include "d3pm_kernels.h"
+#include "d3pm_plan.h"      // BK, ROW_BYTES and the EPI_* bits: the launch planner reads them too
 
 namespace d3pm {
 namespace {
@@ -12,9 +12,6 @@ namespace {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-constexpr int BK = 64;                                  // k-step: one 128-byte LDS row per tile row
-constexpr int ROW_BYTES = BK * 2;
 
 __device__ __forceinline__ int lds_off(int row, int chunk) { return row * ROW_BYTES + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
@@ -72,8 +69,7 @@ __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + e
 // EPI bits: 1 = exact-erf GELU, 2 = one residual (R1), 4 = two residuals (R1, R2), 8 = frame mask, 16 = ReLU, 32 = SiLU
 //           64 = LayerNorm folded into this projection (EPI_LNF), 128 = row moments of the output rows (EPI_STATS): below
 //           256 = the moments in and out of this launch are in the quad format (EPI_QUADS, big-tile GEMM only: below)
-constexpr int EPI_GELU = 1, EPI_R1 = 2, EPI_R2 = 4, EPI_MASK = 8, EPI_RELU = 16, EPI_SILU = 32, EPI_LNF = 64, EPI_STATS = 128;
-constexpr int EPI_QUADS = 256;
+//           (the constants: d3pm_plan.h)
 
 // LayerNorm taken out of the launch list algebraically (ar_discrete.py:131-132, 136-142, 153-159: LayerNorm -> Linear).  With
 // W' = W o gamma (rounded to the storage type once, at weight-preparation time), s_n = sum_k W'[n][k] and
@@ -457,7 +453,7 @@ __device__ __forceinline__ void epilogue_store(floatx4 (&acc)[NT][MT], const T* 
     if constexpr (kPre) mk = pre->mk[mt];
     else if constexpr (kMask) mk = row_mask[mc % mask_period] ? 1.f : 0.f;
     Pack8<T> p1[NP], p2[NP];
-    if (kR1) {   // N % 8 == 0 is guaranteed by mfma_linear_supported when a residual is given
+    if (kR1) {   // N % 8 == 0 is guaranteed by plan_linear (d3pm_plan.cpp operands_ok) when a residual is given
 #pragma unroll
       for (int np = 0; np < NP; ++np) {
         if constexpr (kPre) {
