@@ -61,7 +61,8 @@ extern "C" {
  *    d3pm_denoise_step_keys, d3pm_sample_loop_keys, d3pm_reveal_loop_keys, d3pm_op_attention_pair_keylen); classifier-free guidance
  *    inside the sampler launch (d3pm_guidance, d3pm_posterior_sample_guided, d3pm_sample_loop_guided); block-0 QKV from a per-id
  *    table (d3pm_op_embed_qkv_bytes, d3pm_op_embed_qkv; ln_fold value 2; d3pm_workspace_bytes grew by the table and one
- *    [rows][d_model] region for 16-bit models with d_model a multiple of 256 and n_q <= 1) */
+ *    [rows][d_model] region for 16-bit models with d_model a multiple of 256 and n_q <= 1); one row per distinct token of an
+ *    utterance in the unguided loops (d3pm_op_dedup_index, d3pm_op_linear_live; ln_fold value 3 = every row) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -153,6 +154,15 @@ enum {
  *                      less per iteration, same bits.  2 = the fold without the table: every block projects its QKV rows (the
  *                      guided loop, the reveal loop and d3pm_denoise_step do so under 1 as well).  1 and 2 give identical results;
  *                      d3pm_workspace_bytes is the same for every value.
+ *                      With 1 those loops also evaluate ONE ROW PER DISTINCT TOKEN of an utterance wherever their launches run on
+ *                      the big-tile GEMMs (moments as quads) and the 32 x 32 x 16 attention kernels: the denoiser adds no positional
+ *                      term to the frames, so two frames of one utterance with the same id (or both padded) get the same logits bit
+ *                      for bit; per iteration an index of the distinct rows is built on the device, every projection and attention
+ *                      query runs on those rows alone (keys stay in canvas order), and the sampler, which is per position, reads
+ *                      each frame's logits through the index.  3 = fold + table on every row (the launch list without the
+ *                      deduplication).  1, 2 and 3 give identical ids.  3 is an A/B value OUTSIDE the shipped list: the library and
+ *                      `bench.py --tune ln_fold=3` take it for measurements and tests, the Python `tuning()` context, which
+ *                      admits shipped schedules only, refuses it (0, 1 and 2 are the shipped values).
  *   prof               optional timing hooks (d3pm_prof_create below), NULL = none. */
 struct d3pm_prof;
 typedef struct d3pm_tuning {
@@ -765,6 +775,25 @@ int d3pm_op_linear_stats(int dtype, const void *X, int ldx, const void *W, const
 int d3pm_op_linear_fold(int dtype, const void *X, int ldx, const void *Wf, const float *fold_s, const float *fold_b,
                         const float *stats_in, float eps, void *Y, int ldy, int M, int N, int K, int act, const d3pm_tuning *tuning,
                         void *stream);
+/* Row deduplication (tests; the unguided sampler loop runs it under ln_fold = 1, see d3pm_tuning).  tokens / frame_mask [batch][canvas].
+ * The class of a position is its id (clamped to the classes), or n_classes where frame_mask is 0; the first position of each class of an
+ * utterance is its representative, ranked in position order.  Utterance b owns the compact rows seg_start[b] .. + seg_len[b] (its class
+ * count rounded up to 128), m_live = their sum, row_of [batch * canvas] maps a position to its compact row, cid / cmask
+ * [batch * canvas] hold the class and the frame-mask byte of compact row r < the next multiple of 384 of m_live (n_classes / 0 on rows
+ * no class owns).  With `table` [n_classes][d]: x [batch * canvas][d] receives the embedding rows of the compact rows (zeros on padded
+ * or unowned rows) and stats their moments (quads when d = 512, else parts).  scratch: int32 [batch * canvas + batch].  canvas must be a
+ * multiple of 128 and batch * canvas of 384, n_classes at most 4095. */
+int d3pm_op_dedup_index(int dtype, const int32_t *tokens, const uint8_t *frame_mask, int batch, int canvas, int n_classes, int d,
+                        const void *table, int32_t *seg_start, int32_t *seg_len, int32_t *m_live, int32_t *row_of, int32_t *cid,
+                        uint8_t *cmask, void *x, float *stats, int32_t *scratch, void *stream);
+/* A projection whose live row count is read from device memory at kernel entry (tests): the arguments of d3pm_op_linear_stats /
+ * d3pm_op_linear_fold (X2: the second operand of the dual out-projection or NULL; moments travel as quads at width 512), M = the
+ * capacity the launch is planned for; only the tiles that hold a row < *m_live run.  Big-tile family or the 128 x 128 one-tile-per-
+ * workgroup kernel, D3PM_E_SHAPE otherwise. */
+int d3pm_op_linear_live(int dtype, const void *X, const void *X2, int ldx, const void *W, const void *bias, void *Y, int ldy,
+                        const void *R1, int ldr, const uint8_t *row_mask, int mask_period, int M, int N, int K, int act,
+                        const float *fold_s, const float *fold_b, const float *stats_in, float *stats_out, const int32_t *m_live,
+                        const d3pm_tuning *tuning, void *stream);
 /* The block-0 QKV rows of `n` token ids as the sampler loop makes them under ln_fold = 1 (tests): builds the table [rows][3 d_model]
  * (row id = the folded QKV projection of resps_emb[id] with that row's moments, row n_classes = that of a zero row) in `storage`
  * (device, 256-byte aligned, >= d3pm_op_embed_qkv_bytes(shape, n)), then q_out[r] [n][d_model] | kv_out[r] [n][2 d_model] = the q and

@@ -104,6 +104,9 @@ static int run_attention(const Ctx& cx, int dtype, AttnArgs a, uint32_t flags, h
   ProfScope p(cx, D3PM_K_ATTN, s, 4.0 * a.B * a.H * a.Tq * static_cast<double>(a.S + a.S2) * a.hd,
               dtype_size(dtype) * ((a.Q2 ? 4.0 : 2.0) * a.B * a.Tq * a.H * a.hd + 2.0 * a.B * (a.S + a.S2) * a.H * a.hd));
   const AttnPlan plan = plan_attention(dtype, a, forced_generic(flags));
+  // query segments exist in two kernels only: any other choice would read Q at b * Tq and ignore them
+  D3PM_REQUIRE(!a.seg_len || plan.kernel == ATTN_32P || plan.kernel == ATTN_32_CROSS, D3PM_E_SHAPE,
+               "query segments: the planner names attention kernel %d, which does not take them", plan.kernel);
   if (plan.mfma()) return mfma_attention(dtype, a, plan, s);
   if (a.Q2) {   // the generic kernel takes one problem per launch
     AttnArgs first = a, second = a;
@@ -132,6 +135,8 @@ struct Workspace {
   char *tab_x, *tab_qkv, *q0, *kv0;
   float* tab_stats;
   uint8_t* mxs;       // fp8 fast path: block scales [2n][d / 32] of the LayerNorm rows (a slot of their own: nothing else ever lives here)
+  // row deduplication (d3pm_dedup.hip; never together with fp8): its index arrays live in the mxs slot, all null when they do not fit
+  DedupIndex dd;
   size_t total;
 };
 static size_t align256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
@@ -167,6 +172,11 @@ static Workspace carve(const d3pm_shape& sh, int batch, char* base) {
   }
   w.stats = reinterpret_cast<float*>(take(((n + 15) & ~static_cast<size_t>(15)) * ((d + 31) / 32) * 2 * sizeof(float)));
   w.mxs = reinterpret_cast<uint8_t*>(take(2 * n * ((d + 31) / 32)));
+  if (base && 13 * n + 12 * static_cast<size_t>(batch) + 16 <= 2 * n * ((d + 31) / 32)) {
+    int32_t* ip = reinterpret_cast<int32_t*>(w.mxs);
+    w.dd.row_of = ip; w.dd.rep_pos = ip + n; w.dd.cid = ip + 2 * n; w.dd.cnt = ip + 3 * n; w.dd.seg_start = w.dd.cnt + batch;
+    w.dd.seg_len = w.dd.seg_start + batch; w.dd.m_live = w.dd.seg_len + batch; w.dd.cmask = reinterpret_cast<uint8_t*>(w.dd.m_live + 4);
+  }
   if (fold_shape_ok(sh.dtype, sh.d_model)) {
     const size_t L = sh.n_layers;
     w.fc1f = take(L * 4 * d * d * es);
@@ -309,6 +319,10 @@ struct DenoiserArgs {      // what every block of one evaluation sees
   // the block-0 QKV table of the call (ws.tab_qkv once build_qkv_table has filled it) or null: with it, an embedding launch of the
   // evaluation also gathers ws.q0 | ws.kv0
   const void* qkv_table = nullptr;
+  // row deduplication (sample_loop_impl decides, d3pm_dedup.hip): the index of this evaluation's compact rows, or null.  With it every
+  // projection and attention query of the folded sequence runs on the compact rows (live count and segments read from device memory),
+  // and the launch that prepares an evaluation is dedup_index.
+  const DedupIndex* dd = nullptr;
 };
 // the token embedding of an evaluation whose two halves read the same x_t (token_rows > 0): the gather, once per half
 static int embed_twins(const DenoiserArgs& q, const int32_t* x_t, hipStream_t s) {
@@ -336,26 +350,41 @@ static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v, bo
   const size_t es = dtype_size(dt);
   const d3pm_block_weights& b = q.w.blocks[l];
   const d3pm_fold_block& f = q.w.fold[l];
+  const int* m_live = q.dd ? q.dd->m_live : nullptr;
   auto consumer = [&](const void* Wf, const float* fs, const float* fb, void* Y, int N, int act) {
-    return v.linear(folded_projection(ws.x, Wf, fs, fb, ws.stats, quads, Y, n, N, d, act));
+    LinearArgs g = folded_projection(ws.x, Wf, fs, fb, ws.stats, quads, Y, n, N, d, act);
+    g.m_live = m_live;
+    return v.linear(g);
+  };
+  auto segments = [&](AttnArgs a) {
+    if (q.dd) { a.seg_start = q.dd->seg_start; a.seg_len = q.dd->seg_len; }
+    return a;
   };
   // a projection onto the residual stream: x += X . W^T + bias (+ R2), then the moments of the new rows
   auto producer = [&](const void* X, int K, const void* W, const void* bias, const void* R2 = nullptr) {
-    return with_moments_out(with_residual(projection(X, W, bias, ws.x, n, d, K), ws.x, R2), ws.stats, quads);
+    LinearArgs g = with_moments_out(with_residual(projection(X, W, bias, ws.x, n, d, K), ws.x, R2), ws.stats, quads);
+    g.m_live = m_live;
+    return g;
   };
   // ---- self-attention ----
   const bool from_table = l == 0 && qkv_ready;
   if (!from_table) D3PM_TRY(consumer(f.qkv_w, f.qkv_s, f.qkv_b, ws.qkv, 3 * d, ACT_NONE));
   AttnArgs sa = self_attention(ws.qkv, ws.att, q.batch, T, H, hd, es);
   if (from_table) { sa.Q = ws.q0; sa.ldq = d; sa.K = ws.kv0; sa.V = at(ws.kv0, d, es); sa.ldkv = 2 * d; }
-  D3PM_TRY(v.attention(with_frame_keys(sa, q.keys)));
+  if (q.dd && !from_table) {
+    // the keys in canvas order: k | v of the compact rows expanded through row_of into h | h2, which nothing holds between the
+    // out-projections of one block and the cross-attention of the next (ws.kv0 lives there in block 0)
+    D3PM_TRY(v.expand(ws.qkv, ws.h));
+    sa.K = ws.h; sa.V = at(ws.h, d, es); sa.ldkv = 2 * d;
+  }
+  D3PM_TRY(v.attention(segments(with_frame_keys(sa, q.keys))));
   D3PM_TRY(v.linear(producer(ws.att, d, b.attn_out_w, b.attn_out_b)));
   // ---- cross-attention: q_text | q_prompt are the two halves of ONE [n][2d] projection of x (the same q rows under norm2 / norm22)
   D3PM_TRY(consumer(f.q2_w, f.q2_s, f.q2_b, ws.qkv, 2 * d, ACT_NONE));
   const void* kvt = at(q.kv_text, static_cast<size_t>(l) * q.batch * sh.s_text * 2 * d, es);
   const void* kvp = at(q.kv_prompt, static_cast<size_t>(l) * q.batch * sh.s_prompt * 2 * d, es);
-  D3PM_TRY(v.attention(with_cond_keys(cross_attention_pair(ws.qkv, at(ws.qkv, d, es), 2 * d, kvt, sh.s_text, kvp, sh.s_prompt, ws.att, ws.att2, q.batch, T, H, hd, es),
-                                      q.keys)));
+  D3PM_TRY(v.attention(segments(with_cond_keys(cross_attention_pair(ws.qkv, at(ws.qkv, d, es), 2 * d, kvt, sh.s_text, kvp, sh.s_prompt, ws.att, ws.att2, q.batch, T, H, hd, es),
+                                               q.keys))));
   // ---- x = (x + o_text) + o_prompt, rounded at each add like the eager sum ----
   LinearArgs g = producer(ws.att, d, b.cross_out_w, b.cross_out_b);
   g.tune = sh.tuning;      // plan_cross_out reads it
@@ -363,13 +392,15 @@ static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v, bo
   if (out.form != CROSS_OUT_TWO_LAUNCHES) {
     D3PM_TRY(v.dual(out, g, ws.att2));
   } else {
-    g.Y = ws.h; g.R1 = nullptr; g.stats_out = nullptr; g.moment_quads = false;   // o_text -> h (free: no LayerNorm output lives there any more)
+    g.Y = ws.h; g.R1 = nullptr; g.stats_out = nullptr; g.moment_quads = false;   // o_text -> h (free: no LayerNorm output lives there any more; the expanded keys are behind their attention)
     D3PM_TRY(v.linear(g));
     D3PM_TRY(v.linear(producer(ws.att2, d, b.cross_out_w, b.cross_out_b, ws.h)));
   }
   // ---- FiLM-modulated MLP: the (layer, t) copy of fc1 carries norm3 and the modulation ----
   const size_t ln = static_cast<size_t>(l) * 4 * d;
   D3PM_TRY(consumer(at(ws.fc1f, ln * d, es), ws.fc1f_s + ln, ws.fc1f_b + ln, ws.mlp, 4 * d, ACT_GELU));
+  // (deduplicated: the mask byte of a compact row, period = the capacity)
+  if (q.dd) return v.linear(with_row_mask(producer(ws.mlp, 4 * d, b.fc2_w, b.fc2_b), q.dd->cmask, n));
   return v.linear(with_row_mask(producer(ws.mlp, 4 * d, b.fc2_w, b.fc2_b), q.frame_mask, q.mask_period));
 }
 
@@ -385,8 +416,29 @@ struct FoldPlanner {
     return D3PM_OK;
   }
   int attention(const AttnArgs&) { return D3PM_OK; }
+  int expand(const void*, void*) { return D3PM_OK; }
   int dual(const CrossOutPlan& c, const LinearArgs&, const void*) {
     big = big && c.dual.big();      // the 64 x 64 family keeps the 32-column parts
+    return D3PM_OK;
+  }
+};
+// asks: would the sequence run on the kernels that read a live row count and query segments from device memory -- every projection on
+// big tiles, the self-attention on attn32p_hd64, the cross pair on attn32_cross_hd64?
+struct DedupPlanner {
+  int dt; const d3pm_tuning* tune; bool ok;
+  int linear(LinearArgs g) {
+    g.tune = tune;
+    ok = ok && plan_linear(dt, g).big();
+    return D3PM_OK;
+  }
+  int attention(AttnArgs a) {
+    a.tune = tune;
+    ok = ok && plan_attention(dt, a).kernel == (a.Q2 ? ATTN_32_CROSS : ATTN_32P);
+    return D3PM_OK;
+  }
+  int expand(const void*, void*) { return D3PM_OK; }
+  int dual(const CrossOutPlan& c, const LinearArgs&, const void*) {
+    ok = ok && c.dual.big();
     return D3PM_OK;
   }
 };
@@ -395,6 +447,11 @@ struct FoldLauncher {
   int linear(const LinearArgs& g) { return run_linear(cx, dt, g, 0, s); }      // (fails rather than take the generic family with moments)
   int attention(const AttnArgs& a) { return run_attention(cx, dt, a, 0, s); }
   int dual(const CrossOutPlan& c, const LinearArgs& g, const void* X2) { return run_cross_out_dual(cx, dt, c, g, X2, s); }
+  const int32_t* row_of; int n, d;
+  int expand(const void* qkv, void* kv_full) {
+    ProfScope p(cx, D3PM_K_LN, s, 0.0, dtype_size(dt) * 4.0 * n * d);
+    return dedup_expand_kv(dt, qkv, row_of, kv_full, n, d, s);
+  }
 };
 
 // Is this evaluation taking the folded-LayerNorm launch sequence, and in which format do its row moments travel?  FOLD_NONE: the
@@ -429,6 +486,19 @@ static int build_qkv_table(const Ctx& cx, const d3pm_shape& sh, const d3pm_weigh
   return run_linear(cx, dt, folded_projection(ws.tab_x, f.qkv_w, f.qkv_s, f.qkv_b, ws.tab_stats, false, ws.tab_qkv, mt, 3 * d, d, ACT_NONE), 0, s);
 }
 
+// the index of an evaluation's compact rows + their embedding, moments and block-0 q | k | v (two launches, d3pm_dedup.hip)
+static int run_dedup_index(const DenoiserArgs& q, const int32_t* x_t, bool quads, hipStream_t s) {
+  const d3pm_shape& sh = q.sh;
+  const Ctx cx(sh.tuning);
+  ProfScope p(cx, D3PM_K_LN, s, 0.0, dtype_size(sh.dtype) * static_cast<double>(q.batch) * sh.canvas * sh.d_model * 4.0);
+  DedupArgs a;
+  a.tokens = x_t; a.frame_mask = q.frame_mask; a.mask_period = q.mask_period; a.batch = q.batch; a.canvas = sh.canvas; a.n_classes = sh.n_classes;
+  a.d = sh.d_model; a.ix = *q.dd; a.table = q.w.resps_emb; a.x = q.ws.x; a.stats = q.ws.stats; a.quads = quads;
+  // (under workspace_alias att2 is h2, the upper half of kv0 and of the expanded keys: defined rows already, and not to be cleared)
+  a.qkv_table = q.qkv_table; a.q0 = q.ws.q0; a.kv0 = q.ws.kv0; a.zero[0] = q.ws.att; a.zero[1] = q.ws.att2 == q.ws.h2 ? nullptr : q.ws.att2;
+  return dedup_index(sh.dtype, a, s);
+}
+
 static int denoiser_blocks_folded(const DenoiserArgs& q, const int32_t* x_t, int t, const void* film, int layers, hipStream_t s, bool prepared,
                                   bool quads, bool qkv_ready) {
   const d3pm_shape& sh = q.sh;
@@ -442,6 +512,9 @@ static int denoiser_blocks_folded(const DenoiserArgs& q, const int32_t* x_t, int
       if (q.token_rows) {      // the first evaluation of a guided loop: both halves from the same ids, then the moments of all rows (same bits)
         D3PM_TRY(embed_twins(q, x_t, s));
         D3PM_TRY(row_stats_launch(dt, q.ws.x, d, n, d, q.ws.stats, s, quads));
+      } else if (q.dd) {
+        D3PM_TRY(run_dedup_index(q, x_t, quads, s));
+        qkv_ready = true;
       } else {
         EmbedArgs e = embed_args(sh, q.w, q.batch, x_t, q.frame_mask, q.mask_period, q.ws.x);
         if (q.qkv_table && e.n_q == 1 && q.ws.q0) { e.qkv_table = q.qkv_table; e.q0 = q.ws.q0; e.kv0 = q.ws.kv0; }
@@ -455,7 +528,7 @@ static int denoiser_blocks_folded(const DenoiserArgs& q, const int32_t* x_t, int
                                     q.ws.fc1f_b, s));
     }
   }
-  FoldLauncher launch{cx, dt, s};
+  FoldLauncher launch{cx, dt, s, q.dd ? q.dd->row_of : nullptr, n, d};
   for (int l = 0; l < layers; ++l) D3PM_TRY(folded_block(q, l, quads, launch, qkv_ready));
   return D3PM_OK;
 }
@@ -642,7 +715,7 @@ static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, con
 }
 
 static int final_logits(const d3pm_shape& sh, const d3pm_weights& w, int batch, const Workspace& ws, void* logits,
-                        int ldl, uint32_t flags, hipStream_t s) {
+                        int ldl, uint32_t flags, hipStream_t s, const int* m_live = nullptr) {
   // x is already multiplied by the frame mask at the end of every block (ar_discrete.py:161,773).
   // n_q > 1: one projection per level (final_w [n_q][n_classes][d]) into the level's [ldl]-wide slot of a frame's n_q * ldl logits
   const Ctx cx(sh.tuning);
@@ -652,6 +725,7 @@ static int final_logits(const d3pm_shape& sh, const d3pm_weights& w, int batch, 
                               at(w.final_b, static_cast<size_t>(l) * sh.n_classes, es), at(logits, static_cast<size_t>(l) * ldl, es),
                               batch * sh.canvas, sh.n_classes, sh.d_model);
     g.ldy = levels(sh) * ldl;
+    g.m_live = m_live;
     D3PM_TRY(run_linear(cx, sh.dtype, g, flags, s));
   }
   return D3PM_OK;
@@ -766,6 +840,39 @@ int d3pm_op_linear_fold(int dtype, const void* X, int ldx, const void* Wf, const
   D3PM_REQUIRE(plan.mfma(), D3PM_E_SHAPE,
                "d3pm_op_linear_fold: needs the MFMA family (16-bit), K a multiple of 256, N of 4, act 0 / 1 and 16-byte aligned tables");
   return mfma_linear(dtype, g, plan, static_cast<hipStream_t>(stream));
+}
+
+int d3pm_op_dedup_index(int dtype, const int32_t* tokens, const uint8_t* frame_mask, int batch, int canvas, int n_classes, int d,
+                        const void* table, int32_t* seg_start, int32_t* seg_len, int32_t* m_live, int32_t* row_of, int32_t* cid, uint8_t* cmask,
+                        void* x, float* stats, int32_t* scratch, void* stream) {
+  D3PM_REQUIRE(batch > 0 && canvas > 0 && scratch && (!table || (x && stats)), D3PM_E_ARG, "d3pm_op_dedup_index: bad arguments");
+  DedupArgs a;
+  a.tokens = tokens; a.frame_mask = frame_mask; a.mask_period = batch * canvas; a.batch = batch; a.canvas = canvas; a.n_classes = n_classes; a.d = d;
+  a.ix.cnt = scratch; a.ix.rep_pos = scratch + batch; a.ix.seg_start = seg_start; a.ix.seg_len = seg_len; a.ix.m_live = m_live; a.ix.row_of = row_of;
+  a.ix.cid = cid; a.ix.cmask = cmask;
+  a.table = table; a.x = x; a.stats = stats; a.quads = d == 512;
+  return dedup_index(dtype, a, static_cast<hipStream_t>(stream));
+}
+
+int d3pm_op_linear_live(int dtype, const void* X, const void* X2, int ldx, const void* W, const void* bias, void* Y, int ldy, const void* R1, int ldr,
+                        const uint8_t* row_mask, int mask_period, int M, int N, int K, int act, const float* fold_s, const float* fold_b,
+                        const float* stats_in, float* stats_out, const int32_t* m_live, const d3pm_tuning* tuning, void* stream) {
+  D3PM_REQUIRE(X && W && Y && m_live && M > 0 && N > 0 && K > 0, D3PM_E_ARG, "d3pm_op_linear_live: bad arguments");
+  LinearArgs g;
+  g.tune = tuning;
+  g.X = X; g.ldx = ldx; g.W = W; g.bias = bias; g.Y = Y; g.ldy = ldy; g.R1 = R1; g.ldr = ldr; g.M = M; g.N = N; g.K = K; g.act = act;
+  g.row_mask = row_mask; g.mask_period = mask_period > 0 ? mask_period : 1;
+  g.fold_s = fold_s; g.fold_b = fold_b; g.stats_in = stats_in; g.stats_out = stats_out; g.moment_quads = (fold_s || stats_out) && (fold_s ? K : N) == 512;
+  g.m_live = m_live;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (X2) {      // both cross-attention out-projections in one launch
+    const CrossOutPlan c = plan_cross_out(dtype, g, X2, false, true);
+    D3PM_REQUIRE(c.form == CROSS_OUT_BIG_DUAL, D3PM_E_SHAPE, "d3pm_op_linear_live: the dual form needs the big-tile family");
+    return big_dual(dtype, g, X2, c.dual, s);
+  }
+  const LinearPlan plan = plan_linear(dtype, g);
+  D3PM_REQUIRE(plan.big() || plan.kernel == LIN_128_GLDS, D3PM_E_SHAPE, "d3pm_op_linear_live: %d x %d x %d takes a kernel without a device-side row count", M, N, K);
+  return mfma_linear(dtype, g, plan, s);
 }
 
 size_t d3pm_op_embed_qkv_bytes(const d3pm_shape* sh, int n) {
@@ -1098,7 +1205,20 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     D3PM_TRY(build_qkv_table(cx, *sh, *w, ws, s));
     q.qkv_table = ws.tab_qkv;
   }
-  bool prepared = false;      // the previous iteration's sampler launch has already embedded x_t and folded fc1 for this t
+  // Row deduplication (d3pm_dedup.hip; ln_fold = 3 keeps every row): the unguided 16-bit n_q = 1 loop with the table, moments as quads,
+  // and every launch of the sequence on a kernel that reads the live count / the query segments from device memory.  One decision per
+  // call; otherwise the launch list above runs untouched.
+  const int n_rows = eval_batch * sh->canvas;
+  if (q.qkv_table && plan == FOLD_QUADS && tune_of(sh->tuning).ln_fold == 1 && !f8 && !guide && ws.dd.row_of && n_rows % 384 == 0 && sh->n_layers <= 16 &&
+      sh->n_classes <= kDedupMaxClasses && ws.h2 == at(ws.h, static_cast<size_t>(n_rows) * sh->d_model, dtype_size(sh->dtype))) {
+    DedupPlanner dp{sh->dtype, sh->tuning, true};
+    for (int l = 0; l < sh->n_layers; ++l) (void)folded_block(q, l, true, dp, l == 0);
+    LinearArgs fin = projection(ws.x, w->final_w, w->final_b, ws.logits, n_rows, sh->n_classes, sh->d_model);
+    fin.ldy = logits_ld(*sh); fin.tune = sh->tuning;
+    const LinearPlan fp = plan_linear(sh->dtype, fin);
+    if (dp.ok && (fp.big() || fp.kernel == LIN_128_GLDS)) q.dd = &ws.dd;
+  }
+  bool prepared = false;     // the previous iteration's sampler launch has already embedded x_t and folded fc1 for this t
   bool qkv_ready = false;     // ... and gathered ws.q0 | ws.kv0 for every row of this evaluation
   for (int t = t_start; t > t_stop; --t) {
     if (cx.prof) cx.prof->sample_now = (t % cx.prof->stride) == 0;
@@ -1115,8 +1235,27 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     if (sm) { a.temperature = sm->temperature; a.top_k = sm->top_k; a.top_p = sm->top_p; }
     if (guide) { a.guided = true; a.guidance = guide->weight; }
     {
-      D3PM_TRY(final_logits(*sh, *w, eval_batch, ws, ws.logits, logits_ld(*sh), flags, s));
+      D3PM_TRY(final_logits(*sh, *w, eval_batch, ws, ws.logits, logits_ld(*sh), flags, s, q.dd ? q.dd->m_live : nullptr));
       const bool preps = t - 1 > t_stop && plan != FOLD_NONE;
+      if (q.dd) {
+        // every canvas row draws from the logits of its compact row; then the index, the compact embedding and (inside the sampler
+        // launch) the fc1 fold of iteration t - 1
+        NextIterPrep nx;
+        if (preps) {
+          nx.dtype = sh->dtype; nx.d = sh->d_model; nx.blocks = w->blocks; nx.n_layers = sh->n_layers;
+          nx.film_t = at(film, static_cast<size_t>(t - 1) * sh->n_layers * 2 * sh->d_model, dtype_size(sh->dtype));
+          nx.Wf = ws.fc1f; nx.s_out = ws.fc1f_s; nx.b_out = ws.fc1f_b;
+        }
+        {
+          ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0, static_cast<double>(rows) * (sh->n_classes * dtype_size(sh->dtype) + 8.0));
+          D3PM_TRY(posterior_sample_dedup(a, q.dd->row_of, nx, s));
+        }
+        if (preps) {
+          D3PM_TRY(run_dedup_index(q, x, plan == FOLD_QUADS, s));
+          prepared = qkv_ready = true;
+        }
+        continue;
+      }
       // (+ the block-0 q | k | v rows the launch stores for the next evaluation; their source, the table, stays in L2)
       ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0,
                   static_cast<double>(rows) * levels(*sh) * ((guide ? 2.0 : 1.0) * sh->n_classes * dtype_size(sh->dtype) + 8.0) +

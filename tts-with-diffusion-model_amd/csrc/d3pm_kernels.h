@@ -42,6 +42,9 @@ struct LinearArgs {
   // stats_in / stats_out in the quad format [M / 16][d / 128][16][2] (d3pm_mfma_tile.h EpiFold) instead of 32-column parts: d_model = 512,
   // big-tile GEMM only (LIN_QUADS_REFUSED, d3pm_plan.h: mfma_linear fails with D3PM_E_SHAPE on any other family); one host decision per folded sequence (d3pm_api.hip)
   bool moment_quads = false;
+  // optional live row count in device memory (row deduplication, d3pm_dedup.hip): only the tiles that hold a row < *m_live run; M stays
+  // the capacity the plan was made for.  Big-tile family and gemm_mfma_128_glds only (mfma_linear refuses it elsewhere).
+  const int* m_live = nullptr;
 };
 // which LayerNorm-fold combinations the MFMA epilogues instantiate: LNF [+ GELU] without residual / mask; STATS with R1, R1 + R2, R1 + mask
 inline bool fold_args_ok(const LinearArgs& a) {
@@ -82,6 +85,9 @@ struct AttnArgs {
   // so switching the mask on does not switch the instruction shape.  Unset, a masked call with attn_query_groups = 0 keeps the
   // 16 x 16 x 32 kernel it has always had (the stock NAR stage, d3pm_op_attention_keylen).
   bool masked_keeps_schedule = false;
+  // optional query segments (device int32 [B] each; row deduplication, attn32p_hd64 and attn32_cross_hd64 only): the queries and the
+  // output rows of utterance b are the seg_len[b] rows (a multiple of 128, <= Tq) from row seg_start[b] of Q / O; keys stay [B][S]
+  const int32_t* seg_start = nullptr; const int32_t* seg_len = nullptr;
   const d3pm_tuning* tune = nullptr;
 };
 
@@ -200,6 +206,38 @@ int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_
 // the two launches under classifier-free guidance (SampleArgs.guided; kernels of their own: an unguided call runs none of their code).
 // The prep form embeds rows r and rows + r of n.x / n.stats and applies wherever posterior_sample_prep_supported(a, n) holds.
 int posterior_sample_guided(const SampleArgs& a, hipStream_t s);
+
+// ---- row deduplication (d3pm_dedup.hip): one compact row per distinct (id | padded) class of an utterance -------------------------
+// The denoiser adds no positional term, so two frames of one utterance with the same id get the same logits bit for bit; every
+// projection and every attention query runs on the compact rows, only the keys and the sampler stay per canvas position.
+struct DedupIndex {      // all device memory, [n = batch * canvas] unless noted; carved from the workspace (d3pm_api.hip)
+  int32_t* cnt = nullptr;         // [batch] distinct classes of an utterance
+  int32_t* seg_start = nullptr;   // [batch] first compact row of an utterance
+  int32_t* seg_len = nullptr;     // [batch] cnt rounded up to 128 (one self-attention workgroup)
+  int32_t* m_live = nullptr;      // [1] sum of seg_len
+  int32_t* row_of = nullptr;      // canvas position -> compact row
+  int32_t* rep_pos = nullptr;     // [batch][canvas]: position of the k-th representative (first occurrences in position order)
+  int32_t* cid = nullptr;         // class of a compact row (n_classes = padded / unused)
+  uint8_t* cmask = nullptr;       // frame-mask byte of a compact row (0 on unused rows)
+};
+struct DedupArgs {
+  const int32_t* tokens = nullptr; const uint8_t* frame_mask = nullptr; int mask_period = 0;
+  int batch = 0, canvas = 0, n_classes = 0, d = 0;
+  DedupIndex ix;
+  // the compact embedding (all or none): table [n_classes][d]; x [n][d] + moments; block-0 q rows of the compact rows (q0 [n][d]) and
+  // k | v rows per canvas position (kv0 [n][2d]) from qkv_table [.][3d]; zero [2] = buffers [n][d] whose rows m_live .. the next
+  // multiple of 384 are cleared (attention outputs: no attention workgroup writes them, the out-projections' last tile reads them)
+  const void* table = nullptr; void* x = nullptr; float* stats = nullptr; bool quads = false;
+  const void* qkv_table = nullptr; void* q0 = nullptr; void* kv0 = nullptr;
+  void* zero[2] = {nullptr, nullptr};
+};
+constexpr int kDedupMaxClasses = 4095;      // classes + the padded one fit the index kernel's LDS table
+int dedup_index(int dtype, const DedupArgs& a, hipStream_t s);      // two launches: per-utterance index, then segments + embedding
+// kv_full[b][j] = qkv[row_of[b][j]][d : 3d] for every canvas position (qkv: compact rows [.][3d])
+int dedup_expand_kv(int dtype, const void* qkv, const int32_t* row_of, void* kv_full, int n, int d, hipStream_t s);
+// the sampler launch of the deduplicated loop: row r reads logits[row_of[r]]; with n.Wf set, the workgroups behind the sampler's fold
+// fc1 of every block for the next timestep (NextIterPrep; nothing is embedded here)
+int posterior_sample_dedup(const SampleArgs& a, const int32_t* row_of, const NextIterPrep& n, hipStream_t s);
 int posterior_sample_prep_guided(const SampleArgs& a, const NextIterPrep& n, hipStream_t s);
 
 // One step of the confidence-ordered reveal (d3pm_reveal, d3pm_reveal.hip; n_q = 1): reveal_candidates scores the masked free rows at

@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
       float a, c;
       halves(mx, a, c);                                  // lanes l and l ^ 32 share a query
       mx = fmaxf(a, c);
-      const float delta = tile == 0 ? mx : fmaxf(mx, 0.f);
+      const float delta = tile == 0 ? mx : (mx > kDefer ? mx : 0.f);      // row-local: a row that did not trigger keeps alpha = 1 (exact)
 #pragma unroll
       for (int i = 0; i < 16; ++i) { s[0][i] -= delta; s[1][i] -= delta; }
       if (tile != 0) {
@@ -277,10 +277,13 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
 // it, so the mask is applied there (MSK, in front of the maximum): in the prologue (block 0), in the second block of the last tile
 // but one (first block of the last tile) and in the first block of the last tile (its second block), the latter two peeled out of
 // the loop.  A block of the last tile that lies wholly behind key_len[b] is walked with every score -inf: probabilities 0.
-template <typename T, bool MASK = false>
+// SEG (row deduplication, AttnArgs::seg_start / seg_len): the queries and output rows of utterance b are the seg_len[b] rows from
+// row seg_start[b]; a workgroup whose 128 queries lie behind them leaves in front of its first barrier.  Keys as without it.
+template <typename T, bool MASK = false, bool SEG = false>
 __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, int ldq, const T* __restrict__ Kp,
                                                        const T* __restrict__ Vp, int ldkv, T* __restrict__ O, int ldo, int Tq,
-                                                       int S, float scale, int H, int n_qblocks, const int32_t* __restrict__ key_len) {
+                                                       int S, float scale, int H, int n_qblocks, const int32_t* __restrict__ key_len,
+                                                       const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_len) {
   __shared__ __attribute__((aligned(16))) char smem[3 * 2 * TILE];   // [buffer][K tile | V tile]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int bid;
@@ -289,6 +292,11 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
   const int qb = bid % n_qblocks, h = (bid / n_qblocks) % H, b = bid / (n_qblocks * H);
+  size_t qbase = static_cast<size_t>(b) * Tq;
+  if constexpr (SEG) {
+    if (qb * 128 >= seg_len[b]) return;      // block-uniform
+    qbase = static_cast<size_t>(seg_start[b]);
+  }
   const int q0 = (qb * 4 + wave) * 32;
   const int qn = lane & 31, hh = lane >> 5;
   const T* Kb = Kp + static_cast<size_t>(b) * S * ldkv + h * HD;
@@ -297,7 +305,7 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
   const float qscale = scale * 1.4426950408889634f;
   uint4 qf[4];
   {
-    const T* qp = Q + (static_cast<size_t>(b) * Tq + q0 + qn) * ldq + h * HD + hh * 8;
+    const T* qp = Q + (qbase + q0 + qn) * ldq + h * HD + hh * 8;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       typedef T tvec8 __attribute__((ext_vector_type(8)));
@@ -478,7 +486,8 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
       if (__builtin_expect(__any(mx > kDefer), 0)) {       // wave-uniform, rare
         float a, c;
         halves(mx, a, c);                                  // lanes l and l ^ 32 share a query
-        const float delta = fmaxf(fmaxf(a, c), 0.f);
+        const float own = fmaxf(a, c);
+        const float delta = own > kDefer ? own : 0.f;      // row-local: a row that did not trigger keeps alpha = 1 (exact)
         const float alpha = __builtin_amdgcn_exp2f(-delta);
         m_ref += delta;
         const float nm = -m_ref;
@@ -549,7 +558,7 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
   float la, lc;
   halves((ls[0] + ls[1]) + (ls[2] + ls[3]), la, lc);
   const float inv = 1.0f / (la + lc);
-  store_rows32<T>(O + (static_cast<size_t>(b) * Tq + q0 + qn) * ldo + h * HD, acc_o, inv, hh, true);
+  store_rows32<T>(O + (qbase + q0 + qn) * ldo + h * HD, acc_o, inv, hh, true);
 }
 
 // ---- the cross-attention pair of a block on the same instruction: attn32_cross_hd64 ------------------------------------------
@@ -568,13 +577,15 @@ typedef __attribute__((address_space(3))) void* lds_ptr32_t;
 // MASK: key_len1 / key_len2 (device int32 [B], either may be null) = the valid keys of utterance b among the S1 / S2 padded ones
 // (d3pm_keys.text / .prompt).  S1 / S2 stay the row strides of the batches; behind them the kernel is the unmasked one on the valid
 // counts -- only their tiles are fetched (rows clamped to the last valid key), the last block is masked through cmask.
-template <typename T, bool MASK = false>
+// SEG: as attn32p_hd64 -- seg_len[b] queries from row seg_start[b] of Q1 / Q2 / O1 / O2; the clamp and the store predicate use seg_len[b]
+template <typename T, bool MASK = false, bool SEG = false>
 __global__ __launch_bounds__(512, 2) void attn32_cross_hd64(const T* __restrict__ Q1, const T* __restrict__ K1, const T* __restrict__ V1,
                                                             T* __restrict__ O1, int S1, const T* __restrict__ Q2,
                                                             const T* __restrict__ K2, const T* __restrict__ V2, T* __restrict__ O2,
                                                             int S2, int ldq, int ldkv, int ldo, int Tq, float scale, int H,
                                                             int n_qblocks, int n_qsplit, const int32_t* __restrict__ key_len1,
-                                                            const int32_t* __restrict__ key_len2) {
+                                                            const int32_t* __restrict__ key_len2,
+                                                            const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_len) {
   extern __shared__ __attribute__((aligned(16))) char smem_x[];   // [tile][K | V], 16 KiB per tile: tile 0 = text, 1.. = prompt
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -584,7 +595,14 @@ __global__ __launch_bounds__(512, 2) void attn32_cross_hd64(const T* __restrict_
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
   const int qs = bid % n_qsplit, h = (bid / n_qsplit) % H, b = bid / (n_qsplit * H);
-  const int S1_pad = S1, S2_pad = S2;                        // row strides of the K / V batches
+  size_t qbase = static_cast<size_t>(b) * Tq;
+  if constexpr (SEG) {
+    Tq = seg_len[b];
+    n_qblocks = (Tq + 255) / 256;
+    if (qs >= n_qblocks) return;      // block-uniform, in front of the first DMA piece
+    qbase = static_cast<size_t>(seg_start[b]);
+  }
+  const int S1_pad = S1, S2_pad = S2;                       // row strides of the K / V batches
   if constexpr (MASK) {
     if (key_len1) S1 = min(key_len1[b], S1_pad);
     if (key_len2) S2 = min(key_len2[b], S2_pad);
@@ -623,7 +641,7 @@ __global__ __launch_bounds__(512, 2) void attn32_cross_hd64(const T* __restrict_
     const T* Q = prob == 0 ? Q1 : Q2;
     int qrow = (qb * 8 + wave) * 32 + qn;
     qrow = qrow < Tq ? qrow : Tq - 1;
-    const T* qp = Q + (static_cast<size_t>(b) * Tq + qrow) * ldq + h * HD + hh * 8;
+    const T* qp = Q + (qbase + qrow) * ldq + h * HD + hh * 8;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) qraw[ks] = *reinterpret_cast<const uint4*>(qp + ks * 16);
   };
@@ -760,7 +778,8 @@ __global__ __launch_bounds__(512, 2) void attn32_cross_hd64(const T* __restrict_
         if (__builtin_expect(__any(mx > kDefer), 0)) {       // wave-uniform, rare
           float a, c;
           halves(mx, a, c);
-          const float delta = fmaxf(fmaxf(a, c), 0.f);
+          const float own = fmaxf(a, c);
+          const float delta = own > kDefer ? own : 0.f;      // row-local, as in attn32p_hd64
           const float alpha = __builtin_amdgcn_exp2f(-delta);
           m_ref += delta;
           const float nm = -m_ref;
@@ -800,7 +819,7 @@ __global__ __launch_bounds__(512, 2) void attn32_cross_hd64(const T* __restrict_
     halves((ls[0] + ls[1]) + (ls[2] + ls[3]), la, lc);
     const float inv = 1.0f / (la + lc);
     const int qrow = (qb * 8 + wave) * 32 + qn;              // (the swaps need every lane; only the store is predicated)
-    store_rows32<T>(O + (static_cast<size_t>(b) * Tq + (qrow < Tq ? qrow : Tq - 1)) * ldo + h * HD, acc_o, inv, hh, qrow < Tq);
+    store_rows32<T>(O + (qbase + (qrow < Tq ? qrow : Tq - 1)) * ldo + h * HD, acc_o, inv, hh, qrow < Tq);
   }
   }   // query blocks
 #undef SB
@@ -814,11 +833,18 @@ int mfma_attention32_cross(int dtype, const AttnArgs& a, const AttnPlan& p, hipS
   auto go = [&](auto* tag, auto MASK_) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
     constexpr bool MASK = decltype(MASK_)::value;
-    D3PM_LDS_ATTR((&attn32_cross_hd64<U, MASK>), 5 * 2 * TILE);
-    attn32_cross_hd64<U, MASK><<<grid, block, p.lds, s>>>(static_cast<const U*>(a.Q), static_cast<const U*>(a.K), static_cast<const U*>(a.V),
-                                                        static_cast<U*>(a.O), a.S, static_cast<const U*>(a.Q2), static_cast<const U*>(a.K2),
-                                                        static_cast<const U*>(a.V2), static_cast<U*>(a.O2), a.S2, a.ldq, a.ldkv, a.ldo, a.Tq,
-                                                        a.scale, a.H, p.n_qblocks, p.n_qsplit, a.key_len, a.key_len2);
+#define D3PM_CROSS32_ARGS                                                                                                                  \
+  static_cast<const U*>(a.Q), static_cast<const U*>(a.K), static_cast<const U*>(a.V), static_cast<U*>(a.O), a.S, static_cast<const U*>(a.Q2), \
+      static_cast<const U*>(a.K2), static_cast<const U*>(a.V2), static_cast<U*>(a.O2), a.S2, a.ldq, a.ldkv, a.ldo, a.Tq, a.scale, a.H,       \
+      p.n_qblocks, p.n_qsplit, a.key_len, a.key_len2, a.seg_start, a.seg_len
+    if (a.seg_len) {      // query segments: instantiations of their own, the others stay the code they were
+      D3PM_LDS_ATTR((&attn32_cross_hd64<U, MASK, true>), 5 * 2 * TILE);
+      attn32_cross_hd64<U, MASK, true><<<grid, block, p.lds, s>>>(D3PM_CROSS32_ARGS);
+    } else {
+      D3PM_LDS_ATTR((&attn32_cross_hd64<U, MASK>), 5 * 2 * TILE);
+      attn32_cross_hd64<U, MASK><<<grid, block, p.lds, s>>>(D3PM_CROSS32_ARGS);
+    }
+#undef D3PM_CROSS32_ARGS
     D3PM_LAUNCH_CHECK();
     return D3PM_OK;
   };
@@ -834,15 +860,30 @@ int mfma_attention32(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_
 #define D3PM_ATTN32(KERNEL, T)                                                                                                       \
   KERNEL<<<grid, block, 0, s>>>(static_cast<const T*>(a.Q), a.ldq, static_cast<const T*>(a.K), static_cast<const T*>(a.V), a.ldkv, \
                                 static_cast<T*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, a.key_len)
-  if (p.kernel == ATTN_32P) {           // the pipelined walk; ATTN_32: the plain one (A/B)
+#define D3PM_ATTN32P(KERNEL, T) \
+  KERNEL<<<grid, block, 0, s>>>(static_cast<const T*>(a.Q), a.ldq, static_cast<const T*>(a.K), static_cast<const T*>(a.V), a.ldkv, \
+                                static_cast<T*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, a.key_len, a.seg_start, a.seg_len)
+  D3PM_REQUIRE((a.seg_len != nullptr) == (a.seg_start != nullptr) && (!a.seg_len || p.kernel == ATTN_32P), D3PM_E_SHAPE,
+               "query segments: the pipelined 32 x 32 x 16 self-attention only");
+  if (p.kernel == ATTN_32P && a.seg_len) {      // query segments: instantiations of their own, the others stay the code they were
     if (p.masked) {
-      if (dtype == D3PM_F16) D3PM_ATTN32((attn32p_hd64<f16, true>), f16); else D3PM_ATTN32((attn32p_hd64<bf16, true>), bf16);
+      if (dtype == D3PM_F16) D3PM_ATTN32P((attn32p_hd64<f16, true, true>), f16); else D3PM_ATTN32P((attn32p_hd64<bf16, true, true>), bf16);
     } else {
-      if (dtype == D3PM_F16) D3PM_ATTN32((attn32p_hd64<f16>), f16); else D3PM_ATTN32((attn32p_hd64<bf16>), bf16);
+      if (dtype == D3PM_F16) D3PM_ATTN32P((attn32p_hd64<f16, false, true>), f16); else D3PM_ATTN32P((attn32p_hd64<bf16, false, true>), bf16);
     }
     D3PM_LAUNCH_CHECK();
     return D3PM_OK;
   }
+  if (p.kernel == ATTN_32P) {           // the pipelined walk; ATTN_32: the plain one (A/B)
+    if (p.masked) {
+      if (dtype == D3PM_F16) D3PM_ATTN32P((attn32p_hd64<f16, true>), f16); else D3PM_ATTN32P((attn32p_hd64<bf16, true>), bf16);
+    } else {
+      if (dtype == D3PM_F16) D3PM_ATTN32P((attn32p_hd64<f16>), f16); else D3PM_ATTN32P((attn32p_hd64<bf16>), bf16);
+    }
+    D3PM_LAUNCH_CHECK();
+    return D3PM_OK;
+  }
+#undef D3PM_ATTN32P
   if (p.masked) {
     if (dtype == D3PM_F16) D3PM_ATTN32((attn32_hd64<f16, true>), f16); else D3PM_ATTN32((attn32_hd64<bf16, true>), bf16);
   } else {

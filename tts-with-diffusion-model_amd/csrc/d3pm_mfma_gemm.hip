@@ -69,11 +69,20 @@ template <typename T, int EPI>
 __global__ __launch_bounds__(256, 4) void gemm_mfma_128_glds(const T* __restrict__ X, int ldx, const T* __restrict__ W,
                                                              const T* __restrict__ bias, T* Y, int ldy, const T* R1,
                                                              const T* R2, int ldr, const uint8_t* __restrict__ row_mask,
-                                                             int mask_period, int M, int N, int K, int n_tiles, EpiFold ef) {
+                                                             int mask_period, int M, int N, int K, int n_tiles, EpiFold ef,
+                                                             const int* __restrict__ m_live) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
+  int bid;
+  if (m_live) {      // live row count from device memory (LinearArgs::m_live): the XCD ranges of the live tiles, the rest of the grid leaves
+    const int live = min(((*m_live + BM - 1) / BM) * n_tiles, static_cast<int>(gridDim.x));
+    const int q = live >> 3, r = live & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+    if (idx >= q + (xcd < r ? 1 : 0)) return;      // block-uniform, in front of the first barrier
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  } else {
+    bid = xcd_remap(blockIdx.x, gridDim.x);
+  }
   const int tile_n = bid % n_tiles, tile_m = bid / n_tiles;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -315,7 +324,9 @@ __global__ __launch_bounds__(256, 4) void gemm_mfma_128_persist(const T* __restr
 int mfma_linear(int dtype, const LinearArgs& a, const LinearPlan& p, hipStream_t s) {
   switch (p.kernel) {
     case LIN_BIG: return big_linear(dtype, a, p, s);
-    case LIN_PANEL64: return panel64_linear(dtype, a, p, s);
+    case LIN_PANEL64:
+      D3PM_REQUIRE(!a.m_live, D3PM_E_SHAPE, "device-side live row count: %d x %d x %d takes a kernel without it", a.M, a.N, a.K);
+      return panel64_linear(dtype, a, p, s);
     case LIN_128_PF: case LIN_128_PERSIST: case LIN_128_GLDS: break;
     case LIN_QUADS_REFUSED:
       set_error("row-moment quads: %d x %d x %d does not run on big tiles", a.M, a.N, a.K);
@@ -325,6 +336,7 @@ int mfma_linear(int dtype, const LinearArgs& a, const LinearPlan& p, hipStream_t
       return D3PM_E_SHAPE;
   }
   const bool latency = p.kernel == LIN_128_PF, persist = p.kernel == LIN_128_PERSIST;
+  D3PM_REQUIRE(!a.m_live || p.kernel == LIN_128_GLDS, D3PM_E_SHAPE, "device-side live row count: %d x %d x %d takes a kernel without it", a.M, a.N, a.K);
   const size_t lds = p.lds;
   const int n_tiles = p.n_tiles, tiles_total = p.tiles_total;
   const dim3 grid(p.grid), block(256);
@@ -343,7 +355,7 @@ int mfma_linear(int dtype, const LinearArgs& a, const LinearPlan& p, hipStream_t
   do {                                                                  \
     if (latency) D3PM_GEMM((gemm_mfma_128_pf<U, E>));                   \
     else if (persist) D3PM_GEMM((gemm_mfma_128_persist<U, E>), tiles_total); \
-    else D3PM_GEMM((gemm_mfma_128_glds<U, E>));                         \
+    else D3PM_GEMM((gemm_mfma_128_glds<U, E>), a.m_live);                         \
   } while (0)
   auto go = [&](auto* tag) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
@@ -358,8 +370,8 @@ int mfma_linear(int dtype, const LinearArgs& a, const LinearPlan& p, hipStream_t
       case EPI_R1 | EPI_STATS: D3PM_GEMM_EPI(EPI_R1 | EPI_STATS);   // residual rows + their moments for the next folded LayerNorm
       case EPI_R2 | EPI_STATS: D3PM_GEMM_EPI(EPI_R2 | EPI_STATS);
       case EPI_R1 | EPI_MASK | EPI_STATS: D3PM_GEMM_EPI(EPI_R1 | EPI_MASK | EPI_STATS);
-      case EPI_RELU: D3PM_GEMM((gemm_mfma_128_glds<U, EPI_RELU>));
-      case EPI_SILU: D3PM_GEMM((gemm_mfma_128_glds<U, EPI_SILU>));
+      case EPI_RELU: D3PM_GEMM((gemm_mfma_128_glds<U, EPI_RELU>), a.m_live);
+      case EPI_SILU: D3PM_GEMM((gemm_mfma_128_glds<U, EPI_SILU>), a.m_live);
       default: break;      // no plan names another one (tests/test_launch_plan_api.py)
     }
     return D3PM_E_SHAPE;

@@ -82,8 +82,12 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
                                                         const T* __restrict__ bias, T* Y, int ldy, const T* R1,
                                                         const T* R2, int ldr, const uint8_t* __restrict__ row_mask,
                                                         int mask_period, int M, int N, int K, int n_tiles,
-                                                        int tiles_total, RowPanelArgs<T> rp, EpiFold ef) {
+                                                        int tiles_total, RowPanelArgs<T> rp, EpiFold ef,
+                                                        const int* __restrict__ m_live = nullptr) {
   constexpr int NW = WM * WN, TM = 96 * WM, TN = 64 * WN;   // 8 waves: one workgroup per CU; 4 waves: two
+  // live row count from device memory (LinearArgs::m_live): the tiles that hold a row below it, walked over the XCD ranges of THAT total
+  // (never more than the plan's: M is the capacity of every operand)
+  if (m_live) tiles_total = min(((*m_live + TM - 1) / TM) * n_tiles, tiles_total);
   constexpr int XD = TM / 8, WD = TN / 8;              // 1-KiB DMA pieces (8 rows x 128 B) per k-step and operand
   constexpr int XPW = (XD + NW - 1) / NW, WPW = WD / NW;   // pieces per wave
   constexpr int NDMA = XPW + WPW;                      // 7 (192 x 256), 10 (96 x 512: waves 4..7 repeat an X piece), 10 (192 x 128)
@@ -547,7 +551,7 @@ static int big_launch(const LinearArgs& a, const LinearPlan& p, hipStream_t s) {
   gemm_mfma_big<U, E, WM, WN><<<dim3(p.grid), dim3(WM * WN * 64), p.lds, s>>>(
       static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
       static_cast<const U*>(a.R1), static_cast<const U*>(a.R2), a.ldr, a.row_mask, a.mask_period, a.M, a.N, a.K, p.n_tiles,
-      p.tiles_total, RowPanelArgs<U>{}, epi_fold_of(a));
+      p.tiles_total, RowPanelArgs<U>{}, epi_fold_of(a), a.m_live);
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }
@@ -569,7 +573,7 @@ static int big_dual_launch(const LinearArgs& a, const void* X2, const LinearPlan
   rp.X2 = static_cast<const U*>(X2);
   gemm_mfma_big<U, E, WM, WN, FUSE_DUAL><<<dim3(p.grid), dim3(WM * WN * 64), p.lds, s>>>(
       static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
-      static_cast<const U*>(a.R1), nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, p.n_tiles, p.tiles_total, rp, epi_fold_of(a));
+      static_cast<const U*>(a.R1), nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, p.n_tiles, p.tiles_total, rp, epi_fold_of(a), a.m_live);
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

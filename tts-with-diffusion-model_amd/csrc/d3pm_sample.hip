@@ -188,6 +188,66 @@ __global__ __launch_bounds__(256) void nucleus_sample_prep_rows(
                                                           known, qkv_table, q0, kv0, flt, RowNucleus{top_p, nullptr});
 }
 
+// The sampler launch of the deduplicated loop (d3pm_dedup.hip): canvas row `row` reads the logits of compact row row_of[row] -- the same
+// bits its own row would hold -- and everything per position stays per position: the Philox row, the known frames, x_next, the trace.
+// Nothing is embedded here (the index of the next iteration comes first); the workgroups behind the sampler's fold fc1 as in
+// posterior_sample_prep_rows (sample_blocks = the whole grid when there is no next iteration).
+template <typename T, bool kKnown, int kFilter>
+__device__ __forceinline__ void dedup_sample_rows_body(
+    const T* __restrict__ logits, int ldl, const int32_t* __restrict__ row_of, const int32_t* x_t, int32_t* x_next, int32_t* x_next2, int rows, int K,
+    int mask_id, uint64_t seed, const uint64_t* __restrict__ seed_hbm, uint32_t row0, int greedy, const PosteriorConsts& pc, int sample_blocks, int d,
+    const FoldStepPtrs& fp, const T* __restrict__ film_t, int n_layers, T* __restrict__ Wf, float* __restrict__ s_out, float* __restrict__ b_out,
+    const uint8_t* __restrict__ known, const RowFilter& flt, const RowNucleus& nuc = RowNucleus{}) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (static_cast<int>(blockIdx.x) >= sample_blocks) {
+    const int r = (blockIdx.x - sample_blocks) * 4 + wave;
+    if (r < 4 * d * n_layers) fold_layer_row<T>(fp, film_t, 4 * d, d, r, lane, Wf, s_out, b_out);
+    return;
+  }
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  if (seed_hbm) seed = *seed_hbm;
+  int best_j;
+  bool keep = false;
+  if constexpr (kKnown) keep = row_is_known(known, row);      // wave-uniform: one wave per row
+  if (keep) {
+    best_j = x_t[row];
+  } else {
+    int src = __builtin_amdgcn_readfirstlane(row_of[row]);
+    src = src < 0 ? 0 : (src >= rows ? rows - 1 : src);
+    const T* lr = logits + static_cast<size_t>(src) * ldl;
+    best_j = (K == 1025 && mask_id < 1024)
+        ? sample_row_1025<T, kFilter>(lr, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, lane, 0u, D3PM_SAMPLER_EARLY_OUT != 0, flt, nuc)
+        : sample_row<T, kFilter>(lr, K, mask_id, x_t[row], seed, row0 + static_cast<uint32_t>(row), greedy, pc, nullptr, lane, 0u, flt, nuc);
+  }
+  if (lane == 0) {
+    x_next[row] = best_j;
+    if (x_next2) x_next2[row] = best_j;
+  }
+}
+
+#define D3PM_DEDUP_SAMPLE_PARAMS                                                                                                                  \
+  const T *__restrict__ logits, int ldl, const int32_t *__restrict__ row_of, const int32_t *x_t, int32_t *x_next, int32_t *x_next2, int rows, int K, \
+      int mask_id, uint64_t seed, const uint64_t *__restrict__ seed_hbm, uint32_t row0, int greedy, PosteriorConsts pc, int sample_blocks, int d,     \
+      FoldStepPtrs fp, const T *__restrict__ film_t, int n_layers, T *__restrict__ Wf, float *__restrict__ s_out, float *__restrict__ b_out,          \
+      const uint8_t *__restrict__ known
+#define D3PM_DEDUP_SAMPLE_PASS \
+  logits, ldl, row_of, x_t, x_next, x_next2, rows, K, mask_id, seed, seed_hbm, row0, greedy, pc, sample_blocks, d, fp, film_t, n_layers, Wf, s_out, b_out, known
+template <typename T, bool kKnown>
+__global__ __launch_bounds__(256) void dedup_sample_rows(D3PM_DEDUP_SAMPLE_PARAMS) {
+  dedup_sample_rows_body<T, kKnown, 0>(D3PM_DEDUP_SAMPLE_PASS, RowFilter{});
+}
+template <typename T, bool kKnown>
+__global__ __launch_bounds__(256) void dedup_sample_rows_filtered(D3PM_DEDUP_SAMPLE_PARAMS, RowFilter flt) {
+  dedup_sample_rows_body<T, kKnown, kFilterArm>(D3PM_DEDUP_SAMPLE_PASS, flt);
+}
+template <typename T, bool kKnown>
+__global__ __launch_bounds__(256) void dedup_sample_rows_top_p(D3PM_DEDUP_SAMPLE_PARAMS, RowFilter flt, float top_p) {
+  dedup_sample_rows_body<T, kKnown, kNucleusArm>(D3PM_DEDUP_SAMPLE_PASS, flt, RowNucleus{top_p, nullptr});
+}
+#undef D3PM_DEDUP_SAMPLE_PARAMS
+#undef D3PM_DEDUP_SAMPLE_PASS
+
 // ---- classifier-free guidance (d3pm_guidance) -------------------------------------------------------------------
 // The logits buffer holds 2 * rows rows: row r is utterance row r under its condition (c), row rows + r the same frame under the
 // null condition (u).  The accessor hands the row routines  fmaf(w, float(c_j) - float(u_j), float(c_j))  -- an fp32 subtraction and
@@ -395,6 +455,43 @@ int posterior_sample_prep(const SampleArgs& a, const NextIterPrep& n, hipStream_
 #undef D3PM_PSP
 #undef D3PM_PSP_ARM
 #undef D3PM_PSP_ARGS
+  D3PM_LAUNCH_CHECK();
+  return D3PM_OK;
+}
+
+int posterior_sample_dedup(const SampleArgs& a, const int32_t* row_of, const NextIterPrep& n, hipStream_t s) {
+  D3PM_REQUIRE(row_of && a.n_q == 1 && !a.posterior_out && !a.theta_out && !a.guided && (a.logits_dtype == D3PM_F16 || a.logits_dtype == D3PM_BF16) &&
+                   a.n_classes <= kWave * kMaxGroupsPerLane * 4 && n.n_layers <= 16,
+               D3PM_E_ARG, "deduplicated sampler: one level, 16-bit logits, ids only");
+  const bool folds = n.Wf != nullptr;
+  D3PM_REQUIRE(!folds || (n.blocks && n.film_t && n.s_out && n.b_out && n.d % 256 == 0 && n.dtype == a.logits_dtype), D3PM_E_ARG,
+               "deduplicated sampler: bad fc1 fold arguments");
+  FoldStepPtrs p{};
+  if (folds)
+    for (int l = 0; l < n.n_layers; ++l) {
+      p.W[l] = n.blocks[l].fc1_w; p.bias[l] = n.blocks[l].fc1_b; p.gamma[l] = n.blocks[l].norm3_w; p.beta[l] = n.blocks[l].norm3_b;
+    }
+  const int sample_blocks = (a.rows + 3) / 4, fold_blocks = folds ? (4 * n.d * n.n_layers + 3) / 4 : 0;
+  const dim3 grid(static_cast<unsigned>(sample_blocks + fold_blocks)), block(256);
+  const RowFilter flt{a.temperature, a.top_k};
+#define D3PM_DS_ARGS(T)                                                                                                                          \
+  static_cast<const T*>(a.logits), a.ldl, row_of, a.x_t, a.x_next, a.x_next2, a.rows, a.n_classes, a.mask_id, a.seed, a.seed_hbm, a.row0, a.greedy, \
+      a.pc, sample_blocks, n.d, p, static_cast<const T*>(n.film_t), folds ? n.n_layers : 0, static_cast<T*>(n.Wf), n.s_out, n.b_out, a.known
+#define D3PM_DS_ARM(T, kKnown)                                                                                   \
+  do {                                                                                                           \
+    if (a.nucleus()) dedup_sample_rows_top_p<T, kKnown><<<grid, block, 0, s>>>(D3PM_DS_ARGS(T), flt, a.top_p);    \
+    else if (a.filtered()) dedup_sample_rows_filtered<T, kKnown><<<grid, block, 0, s>>>(D3PM_DS_ARGS(T), flt);      \
+    else dedup_sample_rows<T, kKnown><<<grid, block, 0, s>>>(D3PM_DS_ARGS(T));                                      \
+  } while (0)
+#define D3PM_DS(T)                     \
+  do {                                 \
+    if (a.known) D3PM_DS_ARM(T, true);  \
+    else D3PM_DS_ARM(T, false);        \
+  } while (0)
+  if (a.logits_dtype == D3PM_F16) D3PM_DS(f16); else D3PM_DS(bf16);
+#undef D3PM_DS
+#undef D3PM_DS_ARM
+#undef D3PM_DS_ARGS
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

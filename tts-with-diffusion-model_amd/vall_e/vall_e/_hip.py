@@ -253,6 +253,10 @@ SIGNATURES = {
                                        C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(Tuning), C.c_void_p]),
     "d3pm_op_linear_fold": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Tuning), C.c_void_p]),
+    "d3pm_op_dedup_index": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11),
+    "d3pm_op_linear_live": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.POINTER(Tuning), C.c_void_p]),
     "d3pm_op_embed_qkv_bytes": (C.c_size_t, [C.POINTER(Shape), C.c_int]),
     "d3pm_op_embed_qkv": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1175,6 +1179,39 @@ def op_linear_stats(x, w, bias, r1, *, r2=None, row_mask=None, mask_period=1):
     return y, st
 
 
+def op_dedup_index(tokens, frame_mask, n_classes, table=None):
+    """Row deduplication index of tokens / frame_mask [batch, canvas] (d3pm_op_dedup_index): dict of seg_start, seg_len [batch], m_live [1],
+    row_of, cid [batch * canvas] (int32), cmask [batch * canvas] (uint8) and, with `table` [n_classes, d], x [batch * canvas, d] and its
+    moments `stats` (fp32, the library's layout).  Rows the index does not define keep the sentinels they are created with here."""
+    batch, canvas = tokens.shape
+    n, dev = batch * canvas, tokens.device
+    i32 = lambda k, fill: torch.full((k,), fill, dtype=torch.int32, device=dev)      # noqa: E731
+    out = {"seg_start": i32(batch, -1), "seg_len": i32(batch, -1), "m_live": i32(1, -1), "row_of": i32(n, -1), "cid": i32(n, -7),
+           "cmask": torch.full((n,), 7, dtype=torch.uint8, device=dev)}
+    scratch = i32(n + batch, 0)
+    d, dt = 0, BF16 if table is None else dtype_code(table.dtype)
+    if table is not None:
+        d = table.shape[1]
+        out["x"] = torch.full((n, d), 3.0, dtype=table.dtype, device=dev)
+        out["stats"] = torch.full((((n + 15) // 16) * 16 * (d // 32) * 2,), 5.0, dtype=torch.float32, device=dev)
+    check(lib().d3pm_op_dedup_index(dt, _p(tokens), _p(frame_mask), batch, canvas, n_classes, d, _p(table), _p(out["seg_start"]), _p(out["seg_len"]),
+                                    _p(out["m_live"]), _p(out["row_of"]), _p(out["cid"]), _p(out["cmask"]), _p(out.get("x")), _p(out.get("stats")),
+                                    _p(scratch), stream_ptr()), "d3pm_op_dedup_index")
+    return out
+
+
+def op_linear_live(x, w, bias, y, m_live, x2=None, r1=None, row_mask=None, act=0, fold_s=None, fold_b=None, stats_in=None, stats_out=None):
+    """y [M, N] (written in place: only the tiles that hold a row < m_live[0]) = the projection of d3pm_op_linear_live; M = x.shape[0]
+    is the capacity.  The schedule is the module's TUNING."""
+    M, K = x.shape
+    N = w.shape[0]
+    check(lib().d3pm_op_linear_live(dtype_code(x.dtype), _p(x), _p(x2), x.stride(0), _p(w), _p(bias), _p(y), y.stride(0), _p(r1),
+                                    r1.stride(0) if r1 is not None else 0, _p(row_mask), row_mask.numel() if row_mask is not None else 1, M, N, K, act,
+                                    _p(fold_s), _p(fold_b), _p(stats_in), _p(stats_out), _p(m_live), C.byref(TUNING), stream_ptr()),
+          "d3pm_op_linear_live")
+    return y
+
+
 def op_fold_weights(w, bias, gamma, beta, film=None):
     """(Wf [N, K] in w's dtype, fold_s [N] fp32, fold_b [N] fp32) of one LayerNorm-fed projection (d3pm_op_fold_weights)."""
     N, K = w.shape
@@ -1344,6 +1381,7 @@ def set_workspace_alias(v: bool):
     TUNING.workspace_alias = 1 if v else 0
 
 
+# (ln_fold = 3, the every-row arm of the row deduplication, is an A/B value: set_tuning_field / bench.py --tune take it, tuning() does not)
 _TUNING_VALUES = {"gemm_variant": (0, 2, 3, 4, 5, 6, 7, 8), "attn_query_groups": (0, 1, 2, 4, 32, 33), "lat_tile": (0, 1, 2, 3),
                   "attn_pair_sequential": (0, 1, 2), "attn_cross_resident": (0, 1, 2, 3, 4, 5), "workspace_alias": (0, 1), "ln_fold": (0, 1, 2)}
 
