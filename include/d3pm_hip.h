@@ -62,7 +62,8 @@ extern "C" {
  *    inside the sampler launch (d3pm_guidance, d3pm_posterior_sample_guided, d3pm_sample_loop_guided); block-0 QKV from a per-id
  *    table (d3pm_op_embed_qkv_bytes, d3pm_op_embed_qkv; ln_fold value 2; d3pm_workspace_bytes grew by the table and one
  *    [rows][d_model] region for 16-bit models with d_model a multiple of 256 and n_q <= 1); one row per distinct token of an
- *    utterance in the unguided loops (d3pm_op_dedup_index, d3pm_op_linear_live; ln_fold value 3 = every row) */
+ *    utterance in the unguided loops (d3pm_op_dedup_index, d3pm_op_linear_live; ln_fold value 3 = every row); its self-attention
+ *    with the keys read through a row index (d3pm_op_attention_gather) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -820,6 +821,16 @@ int d3pm_op_attention(int dtype, int family, const void *Q, int ldq, const void 
 int d3pm_op_attention_keylen(int dtype, int family, const void *Q, int ldq, const void *K, const void *V, int ldkv, void *O, int ldo,
                              int B, int Tq, int S, int H, int hd, float scale, const int32_t *key_len, const d3pm_tuning *tuning,
                              void *stream);
+/* The self-attention of the deduplicated loop (tests): the pipelined 32 x 32 x 16 kernel with query segments and its keys read through
+ * a row index, whatever the grid size.  Q / O [rows][ldq / ldo]: the queries and output rows of utterance b are the seg_len[b] rows (a
+ * multiple of 128, at most Tq) from row seg_start[b]; rows no segment owns are not written.  K / V [kv_rows][ldkv], views of one pool:
+ * key j of utterance b is row key_row[b * S + j] (device int32 [B][S]), clamped into [0, kv_rows - 1]; kv_rows * ldkv * the element
+ * size must stay under 2^32 and S at or under 4096.  key_len as d3pm_op_attention_keylen, or NULL.  16-bit dtype, head width 64, Tq a
+ * multiple of 128 and S of 64, D3PM_E_SHAPE otherwise.  The same key values in the same order as d3pm_op_attention on the gathered
+ * rows under attn_query_groups = 32: the same bits. */
+int d3pm_op_attention_gather(int dtype, const void *Q, int ldq, const void *K, const void *V, int ldkv, int kv_rows,
+                             const int32_t *key_row, const int32_t *seg_start, const int32_t *seg_len, void *O, int ldo, int B, int Tq,
+                             int S, int H, int hd, float scale, const int32_t *key_len, const d3pm_tuning *tuning, void *stream);
 /* The text and prompt cross-attentions of a DiT block (ar_discrete.py:138,142) as the block launches them: two independent
  * problems with the same B / Tq / H / hd -- queries Q1 / Q2 [B][Tq][ldq], keys and values K / V [B][S][ldkv] with S1 / S2 keys,
  * outputs O1 / O2 [B][Tq][ldo] -- in ONE launch (tuning->attn_cross_resident / attn_pair_sequential pick the schedule). */

@@ -107,6 +107,9 @@ static int run_attention(const Ctx& cx, int dtype, AttnArgs a, uint32_t flags, h
   // query segments exist in two kernels only: any other choice would read Q at b * Tq and ignore them
   D3PM_REQUIRE(!a.seg_len || plan.kernel == ATTN_32P || plan.kernel == ATTN_32_CROSS, D3PM_E_SHAPE,
                "query segments: the planner names attention kernel %d, which does not take them", plan.kernel);
+  // ... and a key index in one: attn32p_hd64 with segments
+  D3PM_REQUIRE(!a.key_row || (plan.kernel == ATTN_32P && a.seg_len && !a.Q2), D3PM_E_SHAPE,
+               "gathered keys: the planner names attention kernel %d, or the call has no query segments", plan.kernel);
   if (plan.mfma()) return mfma_attention(dtype, a, plan, s);
   if (a.Q2) {   // the generic kernel takes one problem per launch
     AttnArgs first = a, second = a;
@@ -172,9 +175,9 @@ static Workspace carve(const d3pm_shape& sh, int batch, char* base) {
   }
   w.stats = reinterpret_cast<float*>(take(((n + 15) & ~static_cast<size_t>(15)) * ((d + 31) / 32) * 2 * sizeof(float)));
   w.mxs = reinterpret_cast<uint8_t*>(take(2 * n * ((d + 31) / 32)));
-  if (base && 13 * n + 12 * static_cast<size_t>(batch) + 16 <= 2 * n * ((d + 31) / 32)) {
+  if (base && 17 * n + 12 * static_cast<size_t>(batch) + 16 <= 2 * n * ((d + 31) / 32)) {
     int32_t* ip = reinterpret_cast<int32_t*>(w.mxs);
-    w.dd.row_of = ip; w.dd.rep_pos = ip + n; w.dd.cid = ip + 2 * n; w.dd.cnt = ip + 3 * n; w.dd.seg_start = w.dd.cnt + batch;
+    w.dd.row_of = ip; w.dd.rep_pos = ip + n; w.dd.cid = ip + 2 * n; w.dd.key_cls = ip + 3 * n; w.dd.cnt = ip + 4 * n; w.dd.seg_start = w.dd.cnt + batch;
     w.dd.seg_len = w.dd.seg_start + batch; w.dd.m_live = w.dd.seg_len + batch; w.dd.cmask = reinterpret_cast<uint8_t*>(w.dd.m_live + 4);
   }
   if (fold_shape_ok(sh.dtype, sh.d_model)) {
@@ -371,11 +374,12 @@ static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v, bo
   if (!from_table) D3PM_TRY(consumer(f.qkv_w, f.qkv_s, f.qkv_b, ws.qkv, 3 * d, ACT_NONE));
   AttnArgs sa = self_attention(ws.qkv, ws.att, q.batch, T, H, hd, es);
   if (from_table) { sa.Q = ws.q0; sa.ldq = d; sa.K = ws.kv0; sa.V = at(ws.kv0, d, es); sa.ldkv = 2 * d; }
-  if (q.dd && !from_table) {
-    // the keys in canvas order: k | v of the compact rows expanded through row_of into h | h2, which nothing holds between the
-    // out-projections of one block and the cross-attention of the next (ws.kv0 lives there in block 0)
-    D3PM_TRY(v.expand(ws.qkv, ws.h));
-    sa.K = ws.h; sa.V = at(ws.h, d, es); sa.ldkv = 2 * d;
+  if (q.dd) {
+    // the keys stay where they lie and the attention walks them through an index (attn32p_hd64 GATHER): the k | v columns of the compact
+    // QKV rows through row_of, in block 0 those of the block-0 QKV table through the class of a canvas position (q: ws.q0, the compact copy)
+    if (from_table) { sa.K = at(q.qkv_table, d, es); sa.V = at(q.qkv_table, 2 * d, es); sa.key_row = q.dd->key_cls; sa.kv_rows = qkv_table_rows(sh.n_classes); }
+    else { sa.key_row = q.dd->row_of; sa.kv_rows = n; }
+    sa.ldkv = 3 * d;
   }
   D3PM_TRY(v.attention(segments(with_frame_keys(sa, q.keys))));
   D3PM_TRY(v.linear(producer(ws.att, d, b.attn_out_w, b.attn_out_b)));
@@ -392,7 +396,7 @@ static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v, bo
   if (out.form != CROSS_OUT_TWO_LAUNCHES) {
     D3PM_TRY(v.dual(out, g, ws.att2));
   } else {
-    g.Y = ws.h; g.R1 = nullptr; g.stats_out = nullptr; g.moment_quads = false;   // o_text -> h (free: no LayerNorm output lives there any more; the expanded keys are behind their attention)
+    g.Y = ws.h; g.R1 = nullptr; g.stats_out = nullptr; g.moment_quads = false;   // o_text -> h (free: no LayerNorm output lives there any more)
     D3PM_TRY(v.linear(g));
     D3PM_TRY(v.linear(producer(ws.att2, d, b.cross_out_w, b.cross_out_b, ws.h)));
   }
@@ -416,7 +420,6 @@ struct FoldPlanner {
     return D3PM_OK;
   }
   int attention(const AttnArgs&) { return D3PM_OK; }
-  int expand(const void*, void*) { return D3PM_OK; }
   int dual(const CrossOutPlan& c, const LinearArgs&, const void*) {
     big = big && c.dual.big();      // the 64 x 64 family keeps the 32-column parts
     return D3PM_OK;
@@ -436,7 +439,6 @@ struct DedupPlanner {
     ok = ok && plan_attention(dt, a).kernel == (a.Q2 ? ATTN_32_CROSS : ATTN_32P);
     return D3PM_OK;
   }
-  int expand(const void*, void*) { return D3PM_OK; }
   int dual(const CrossOutPlan& c, const LinearArgs&, const void*) {
     ok = ok && c.dual.big();
     return D3PM_OK;
@@ -447,11 +449,6 @@ struct FoldLauncher {
   int linear(const LinearArgs& g) { return run_linear(cx, dt, g, 0, s); }      // (fails rather than take the generic family with moments)
   int attention(const AttnArgs& a) { return run_attention(cx, dt, a, 0, s); }
   int dual(const CrossOutPlan& c, const LinearArgs& g, const void* X2) { return run_cross_out_dual(cx, dt, c, g, X2, s); }
-  const int32_t* row_of; int n, d;
-  int expand(const void* qkv, void* kv_full) {
-    ProfScope p(cx, D3PM_K_LN, s, 0.0, dtype_size(dt) * 4.0 * n * d);
-    return dedup_expand_kv(dt, qkv, row_of, kv_full, n, d, s);
-  }
 };
 
 // Is this evaluation taking the folded-LayerNorm launch sequence, and in which format do its row moments travel?  FOLD_NONE: the
@@ -486,16 +483,18 @@ static int build_qkv_table(const Ctx& cx, const d3pm_shape& sh, const d3pm_weigh
   return run_linear(cx, dt, folded_projection(ws.tab_x, f.qkv_w, f.qkv_s, f.qkv_b, ws.tab_stats, false, ws.tab_qkv, mt, 3 * d, d, ACT_NONE), 0, s);
 }
 
-// the index of an evaluation's compact rows + their embedding, moments and block-0 q | k | v (two launches, d3pm_dedup.hip)
+// the index of an evaluation's compact rows + their embedding, moments and block-0 q (two launches, d3pm_dedup.hip)
 static int run_dedup_index(const DenoiserArgs& q, const int32_t* x_t, bool quads, hipStream_t s) {
   const d3pm_shape& sh = q.sh;
   const Ctx cx(sh.tuning);
-  ProfScope p(cx, D3PM_K_LN, s, 0.0, dtype_size(sh.dtype) * static_cast<double>(q.batch) * sh.canvas * sh.d_model * 4.0);
+  // (algorithmic bytes at the capacity: the x and q0 rows written)
+  ProfScope p(cx, D3PM_K_LN, s, 0.0, dtype_size(sh.dtype) * static_cast<double>(q.batch) * sh.canvas * sh.d_model * 2.0);
   DedupArgs a;
   a.tokens = x_t; a.frame_mask = q.frame_mask; a.mask_period = q.mask_period; a.batch = q.batch; a.canvas = sh.canvas; a.n_classes = sh.n_classes;
   a.d = sh.d_model; a.ix = *q.dd; a.table = q.w.resps_emb; a.x = q.ws.x; a.stats = q.ws.stats; a.quads = quads;
-  // (under workspace_alias att2 is h2, the upper half of kv0 and of the expanded keys: defined rows already, and not to be cleared)
-  a.qkv_table = q.qkv_table; a.q0 = q.ws.q0; a.kv0 = q.ws.kv0; a.zero[0] = q.ws.att; a.zero[1] = q.ws.att2 == q.ws.h2 ? nullptr : q.ws.att2;
+  // (no k | v row is gathered: the self-attention reads the table through key_cls.  att2 is h2 under workspace_alias, which nothing else of
+  // this sequence writes any more, so both attention outputs are cleared behind the live rows)
+  a.qkv_table = q.qkv_table; a.q0 = q.ws.q0; a.zero[0] = q.ws.att; a.zero[1] = q.ws.att2;
   return dedup_index(sh.dtype, a, s);
 }
 
@@ -528,7 +527,7 @@ static int denoiser_blocks_folded(const DenoiserArgs& q, const int32_t* x_t, int
                                     q.ws.fc1f_b, s));
     }
   }
-  FoldLauncher launch{cx, dt, s, q.dd ? q.dd->row_of : nullptr, n, d};
+  FoldLauncher launch{cx, dt, s};
   for (int l = 0; l < layers; ++l) D3PM_TRY(folded_block(q, l, quads, launch, qkv_ready));
   return D3PM_OK;
 }
@@ -1216,7 +1215,11 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     LinearArgs fin = projection(ws.x, w->final_w, w->final_b, ws.logits, n_rows, sh->n_classes, sh->d_model);
     fin.ldy = logits_ld(*sh); fin.tune = sh->tuning;
     const LinearPlan fp = plan_linear(sh->dtype, fin);
-    if (dp.ok && (fp.big() || fp.kernel == LIN_128_GLDS)) q.dd = &ws.dd;
+    // the self-attention walks its keys through an index (attn32p_hd64 GATHER): the staged index beside the tiles, and 32-bit byte
+    // offsets into the rows it reads -- the compact QKV rows [n_rows][3d] or the block-0 QKV table
+    const unsigned long long kv_rows = std::max<unsigned long long>(n_rows, qkv_table_rows(sh->n_classes));
+    const bool gather_ok = static_cast<size_t>(sh->canvas) * 4 <= kGatherIndexBytes && kv_rows * 3 * sh->d_model * dtype_size(sh->dtype) < (1ull << 32);
+    if (dp.ok && gather_ok && (fp.big() || fp.kernel == LIN_128_GLDS)) q.dd = &ws.dd;
   }
   bool prepared = false;     // the previous iteration's sampler launch has already embedded x_t and folded fc1 for this t
   bool qkv_ready = false;     // ... and gathered ws.q0 | ws.kv0 for every row of this evaluation
@@ -1718,6 +1721,24 @@ int d3pm_op_attention_keylen(int dtype, int family, const void* Q, int ldq, cons
                              const d3pm_tuning* tuning, void* stream) {
   return op_attention_impl("d3pm_op_attention_keylen", dtype, family, Q, ldq, K, V, ldkv, O, ldo, B, Tq, S, H, hd, scale, key_len, tuning,
                            stream);
+}
+
+// the gathered attn32p_hd64 whatever the grid size: the planner is asked with attn_query_groups = 32 (always the 32 x 32 x 16 walk)
+int d3pm_op_attention_gather(int dtype, const void* Q, int ldq, const void* K, const void* V, int ldkv, int kv_rows, const int32_t* key_row,
+                             const int32_t* seg_start, const int32_t* seg_len, void* O, int ldo, int B, int Tq, int S, int H, int hd, float scale,
+                             const int32_t* key_len, const d3pm_tuning* tuning, void* stream) {
+  D3PM_REQUIRE(Q && K && V && O && key_row && seg_start && seg_len && kv_rows > 0 && B > 0 && Tq > 0 && S > 0 && H > 0 && hd > 0, D3PM_E_ARG,
+               "d3pm_op_attention_gather: bad arguments");
+  d3pm_tuning tn = tune_of(tuning);
+  tn.attn_query_groups = 32;
+  AttnArgs a;
+  a.tune = &tn;
+  a.Q = Q; a.ldq = ldq; a.K = K; a.V = V; a.ldkv = ldkv; a.O = O; a.ldo = ldo; a.B = B; a.Tq = Tq; a.S = S; a.H = H;
+  a.hd = hd; a.scale = scale; a.key_len = key_len; a.seg_start = seg_start; a.seg_len = seg_len; a.key_row = key_row; a.kv_rows = kv_rows;
+  const AttnPlan plan = plan_attention(dtype, a);
+  D3PM_REQUIRE(plan.kernel == ATTN_32P, D3PM_E_SHAPE,
+               "d3pm_op_attention_gather: needs a 16-bit dtype, head width 64, Tq a multiple of 128, S of 64 and 16-byte aligned rows");
+  return mfma_attention(dtype, a, plan, static_cast<hipStream_t>(stream));
 }
 
 // key_len1 / key_len2 (device, [B]) are read by the kernels only: see d3pm_op_attention_keylen

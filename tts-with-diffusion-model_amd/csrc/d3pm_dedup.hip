@@ -5,13 +5,13 @@
 // one utterance that carry the same id at the top of an iteration get the same logits, bit for bit.  Per iteration:
 //   dedup_index_utt     one workgroup per utterance: class of a position = its id, or n_classes on a padded frame; the first canvas
 //                       position of each class is its representative, ranked in position order; row_of (still local to the utterance),
-//                       the representatives' positions, the count
+//                       key_cls (the class of every position), the representatives' positions, the count
 //   dedup_embed_rows    one wave per index r, which is both a compact row and a canvas position: the segments (an utterance owns its
 //                       count rounded up to 128 compact rows, back to back), the embedding row + moments + block-0 q of compact row r
 //                       (a zero row with zero moments where the segment is padding, and from m_live up to the next multiple of 384, the
-//                       least common multiple of the 192- and 128-row GEMM tiles), the block-0 k | v rows of canvas position r, and
-//                       row_of[r] made global
-//   dedup_expand_rows   blocks 1..: the k | v columns of the compact QKV rows back in canvas order for the self-attention's key walk
+//                       least common multiple of the 192- and 128-row GEMM tiles), and row_of[r] made global
+// No k | v row is copied into canvas order: the self-attention walks its keys through an index (attn32p_hd64 GATHER, d3pm_mfma_attn32.hip)
+// -- in block 0 row key_cls[position] of the block-0 QKV table, in the later blocks row row_of[position] of the compact QKV rows.
 // Nothing here reads anything back to the host: the counts stay in device memory and the GEMMs / attentions read them there.
 #include <climits>
 
@@ -25,7 +25,7 @@ __device__ __forceinline__ int clamp_id(int id, int n_classes) { return id < 0 ?
 
 __global__ __launch_bounds__(256) void dedup_index_utt(const int32_t* __restrict__ tokens, const uint8_t* __restrict__ frame_mask, int mask_period,
                                                        int canvas, int n_classes, int32_t* __restrict__ cnt, int32_t* __restrict__ row_of,
-                                                       int32_t* __restrict__ rep_pos) {
+                                                       int32_t* __restrict__ rep_pos, int32_t* __restrict__ key_cls) {
   extern __shared__ int dedup_sm[];
   int* first = dedup_sm;                      // [n_classes + 1] first position of a class
   int* rank = first + n_classes + 1;          // [n_classes + 1] rank of its representative
@@ -59,7 +59,11 @@ __global__ __launch_bounds__(256) void dedup_index_utt(const int32_t* __restrict
     base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
     __syncthreads();
   }
-  for (int j = tid; j < canvas; j += 256) row_of[row0 + j] = rank[class_of(j)];
+  for (int j = tid; j < canvas; j += 256) {
+    const int c = class_of(j);
+    row_of[row0 + j] = rank[c];
+    if (key_cls) key_cls[row0 + j] = c;      // kernel-uniform
+  }
   if (tid == 0) cnt[b] = base;
 }
 
@@ -70,7 +74,7 @@ __global__ __launch_bounds__(256) void dedup_embed_rows(const int32_t* __restric
                                                         int32_t* __restrict__ row_of, const int32_t* __restrict__ rep_pos, int32_t* __restrict__ cid,
                                                         uint8_t* __restrict__ cmask, const T* __restrict__ table, T* __restrict__ x,
                                                         float* __restrict__ stats, bool quads, const T* __restrict__ qkv_table, T* __restrict__ q0,
-                                                        T* __restrict__ kv0, T* __restrict__ zero0, T* __restrict__ zero1) {
+                                                        T* __restrict__ zero0, T* __restrict__ zero1) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int n = batch * canvas;
   const int r = blockIdx.x * 4 + wave;      // wave-uniform
@@ -90,17 +94,8 @@ __global__ __launch_bounds__(256) void dedup_embed_rows(const int32_t* __restric
     if (r < batch) { seg_start[r] = own_start; seg_len[r] = own_len; }
     if (r == 0) *m_live_out = m_live;
   }
-  // ---- canvas position r: global row_of, block-0 k | v from the table
-  {
-    const bool live = frame_mask[r % mask_period] != 0;
-    const int cls = live ? clamp_id(tokens[r], n_classes) : n_classes;
-    if (lane == 0) row_of[r] += pos_start;
-    if (qkv_table) {      // kernel-uniform
-      const Vec8<T>* ts = reinterpret_cast<const Vec8<T>*>(qkv_table + (static_cast<size_t>(cls) * 3 + 1) * d);
-      Vec8<T>* tkv = reinterpret_cast<Vec8<T>*>(kv0 + static_cast<size_t>(r) * 2 * d);
-      for (int c = lane; c < (d >> 2); c += kWave) tkv[c] = ts[c];
-    }
-  }
+  // ---- canvas position r: global row_of
+  if (lane == 0) row_of[r] += pos_start;
   // ---- compact row r
   if (r >= m_pad) return;
   int id = 0;
@@ -126,18 +121,6 @@ __global__ __launch_bounds__(256) void dedup_embed_rows(const int32_t* __restric
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void dedup_expand_rows(const T* __restrict__ qkv, const int32_t* __restrict__ row_of, T* __restrict__ kv_full, int n, int d) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int r = blockIdx.x * 4 + wave;
-  if (r >= n) return;
-  int src = row_of[r];
-  src = src < 0 ? 0 : (src >= n ? n - 1 : src);
-  const Vec8<T>* sp = reinterpret_cast<const Vec8<T>*>(qkv + (static_cast<size_t>(src) * 3 + 1) * d);
-  Vec8<T>* dp = reinterpret_cast<Vec8<T>*>(kv_full + static_cast<size_t>(r) * 2 * d);
-  for (int c = lane; c < (d >> 2); c += kWave) dp[c] = sp[c];
-}
-
 }  // namespace
 
 int dedup_index(int dtype, const DedupArgs& a, hipStream_t s) {
@@ -149,30 +132,21 @@ int dedup_index(int dtype, const DedupArgs& a, hipStream_t s) {
   D3PM_REQUIRE(a.n_classes <= kDedupMaxClasses && a.canvas % 128 == 0 && (static_cast<long long>(a.batch) * a.canvas) % 384 == 0, D3PM_E_SHAPE,
                "row deduplication: at most %d classes, canvas a multiple of 128 and batch * canvas a multiple of 384", kDedupMaxClasses);
   D3PM_REQUIRE((dtype == D3PM_F16 || dtype == D3PM_BF16) && a.d % 8 == 0 && (!a.quads || a.d == 512) && (!a.table || (a.x && a.stats)) &&
-                   (a.qkv_table != nullptr) == (a.q0 != nullptr) && (a.q0 != nullptr) == (a.kv0 != nullptr),
+                   (a.qkv_table != nullptr) == (a.q0 != nullptr),
                D3PM_E_ARG, "row deduplication: bad embedding arguments");
   const int n = a.batch * a.canvas;
   const size_t lds = (2 * static_cast<size_t>(a.n_classes + 1) + 4) * sizeof(int);
-  dedup_index_utt<<<dim3(a.batch), dim3(256), lds, s>>>(a.tokens, a.frame_mask, a.mask_period, a.canvas, a.n_classes, ix.cnt, ix.row_of, ix.rep_pos);
+  dedup_index_utt<<<dim3(a.batch), dim3(256), lds, s>>>(a.tokens, a.frame_mask, a.mask_period, a.canvas, a.n_classes, ix.cnt, ix.row_of, ix.rep_pos, ix.key_cls);
   D3PM_LAUNCH_CHECK();
   const dim3 grid(static_cast<unsigned>((n + 3) / 4)), block(256);
   auto go = [&](auto* tag) {
     using U = std::remove_pointer_t<decltype(tag)>;
     dedup_embed_rows<U><<<grid, block, 0, s>>>(a.tokens, a.frame_mask, a.mask_period, a.batch, a.canvas, a.n_classes, a.d, ix.cnt, ix.seg_start, ix.seg_len,
                                                ix.m_live, ix.row_of, ix.rep_pos, ix.cid, ix.cmask, static_cast<const U*>(a.table), static_cast<U*>(a.x),
-                                               a.stats, a.quads, static_cast<const U*>(a.qkv_table), static_cast<U*>(a.q0), static_cast<U*>(a.kv0),
+                                               a.stats, a.quads, static_cast<const U*>(a.qkv_table), static_cast<U*>(a.q0),
                                                static_cast<U*>(a.zero[0]), static_cast<U*>(a.zero[1]));
   };
   if (dtype == D3PM_F16) go(static_cast<f16*>(nullptr)); else go(static_cast<bf16*>(nullptr));
-  D3PM_LAUNCH_CHECK();
-  return D3PM_OK;
-}
-
-int dedup_expand_kv(int dtype, const void* qkv, const int32_t* row_of, void* kv_full, int n, int d, hipStream_t s) {
-  D3PM_REQUIRE(qkv && row_of && kv_full && n > 0 && d % 8 == 0 && (dtype == D3PM_F16 || dtype == D3PM_BF16), D3PM_E_ARG, "row deduplication: bad expansion arguments");
-  const dim3 grid(static_cast<unsigned>((n + 3) / 4)), block(256);
-  if (dtype == D3PM_F16) dedup_expand_rows<f16><<<grid, block, 0, s>>>(static_cast<const f16*>(qkv), row_of, static_cast<f16*>(kv_full), n, d);
-  else dedup_expand_rows<bf16><<<grid, block, 0, s>>>(static_cast<const bf16*>(qkv), row_of, static_cast<bf16*>(kv_full), n, d);
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

@@ -88,6 +88,10 @@ struct AttnArgs {
   // optional query segments (device int32 [B] each; row deduplication, attn32p_hd64 and attn32_cross_hd64 only): the queries and the
   // output rows of utterance b are the seg_len[b] rows (a multiple of 128, <= Tq) from row seg_start[b] of Q / O; keys stay [B][S]
   const int32_t* seg_start = nullptr; const int32_t* seg_len = nullptr;
+  // optional key gather (device int32 [B][S]; attn32p_hd64 with query segments only): key j of utterance b is row key_row[b * S + j]
+  // of K / V, which are then [kv_rows][ldkv] with no per-utterance base; the kernel clamps the index into [0, kv_rows - 1];
+  // kv_rows * ldkv * the element size < 2^32
+  const int32_t* key_row = nullptr; int kv_rows = 0;
   const d3pm_tuning* tune = nullptr;
 };
 
@@ -216,6 +220,7 @@ struct DedupIndex {      // all device memory, [n = batch * canvas] unless noted
   int32_t* seg_len = nullptr;     // [batch] cnt rounded up to 128 (one self-attention workgroup)
   int32_t* m_live = nullptr;      // [1] sum of seg_len
   int32_t* row_of = nullptr;      // canvas position -> compact row
+  int32_t* key_cls = nullptr;     // class of a canvas position (n_classes on a padded frame) = its row of the block-0 QKV table; null: not written
   int32_t* rep_pos = nullptr;     // [batch][canvas]: position of the k-th representative (first occurrences in position order)
   int32_t* cid = nullptr;         // class of a compact row (n_classes = padded / unused)
   uint8_t* cmask = nullptr;       // frame-mask byte of a compact row (0 on unused rows)
@@ -224,17 +229,15 @@ struct DedupArgs {
   const int32_t* tokens = nullptr; const uint8_t* frame_mask = nullptr; int mask_period = 0;
   int batch = 0, canvas = 0, n_classes = 0, d = 0;
   DedupIndex ix;
-  // the compact embedding (all or none): table [n_classes][d]; x [n][d] + moments; block-0 q rows of the compact rows (q0 [n][d]) and
-  // k | v rows per canvas position (kv0 [n][2d]) from qkv_table [.][3d]; zero [2] = buffers [n][d] whose rows m_live .. the next
+  // the compact embedding (all or none): table [n_classes][d]; x [n][d] + moments; block-0 q rows of the compact rows (q0 [n][d]) from
+  // qkv_table [.][3d] (its k | v rows are read in place, through ix.key_cls); zero [2] = buffers [n][d] whose rows m_live .. the next
   // multiple of 384 are cleared (attention outputs: no attention workgroup writes them, the out-projections' last tile reads them)
   const void* table = nullptr; void* x = nullptr; float* stats = nullptr; bool quads = false;
-  const void* qkv_table = nullptr; void* q0 = nullptr; void* kv0 = nullptr;
+  const void* qkv_table = nullptr; void* q0 = nullptr;
   void* zero[2] = {nullptr, nullptr};
 };
 constexpr int kDedupMaxClasses = 4095;      // classes + the padded one fit the index kernel's LDS table
 int dedup_index(int dtype, const DedupArgs& a, hipStream_t s);      // two launches: per-utterance index, then segments + embedding
-// kv_full[b][j] = qkv[row_of[b][j]][d : 3d] for every canvas position (qkv: compact rows [.][3d])
-int dedup_expand_kv(int dtype, const void* qkv, const int32_t* row_of, void* kv_full, int n, int d, hipStream_t s);
 // the sampler launch of the deduplicated loop: row r reads logits[row_of[r]]; with n.Wf set, the workgroups behind the sampler's fold
 // fc1 of every block for the next timestep (NextIterPrep; nothing is embedded here)
 int posterior_sample_dedup(const SampleArgs& a, const int32_t* row_of, const NextIterPrep& n, hipStream_t s);

@@ -279,11 +279,20 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
 // the loop.  A block of the last tile that lies wholly behind key_len[b] is walked with every score -inf: probabilities 0.
 // SEG (row deduplication, AttnArgs::seg_start / seg_len): the queries and output rows of utterance b are the seg_len[b] rows from
 // row seg_start[b]; a workgroup whose 128 queries lie behind them leaves in front of its first barrier.  Keys as without it.
-template <typename T, bool MASK = false, bool SEG = false>
+// GATHER (with SEG only; AttnArgs::key_row / kv_rows): key j of utterance b is row key_row[b * S + j] of Kp / Vp (row stride ldkv, no
+// per-utterance base), clamped into [0, kv_rows - 1] -- the compact QKV rows of the deduplicated loop read where the projection left
+// them, or the block-0 QKV table read through the class of a position.  The workgroup stages the utterance's S indices into LDS once,
+// as byte offsets of their rows (the launcher keeps kv_rows * ldkv * sizeof(T) under 2^32), in front of the first K / V load: 4 S bytes
+// of dynamic LDS behind the 48 KiB of tiles, three workgroups per CU up to S = 1344.  load_tile and the STG halves of `block` take
+// their two row offsets per thread from there; LDS layout, swizzles, barriers and the walk are those of GATHER = false, and so is
+// every bit of the result on the same key values.  GATHER = false is the code it was.
+template <typename T, bool MASK = false, bool SEG = false, bool GATHER = false>
 __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, int ldq, const T* __restrict__ Kp,
                                                        const T* __restrict__ Vp, int ldkv, T* __restrict__ O, int ldo, int Tq,
                                                        int S, float scale, int H, int n_qblocks, const int32_t* __restrict__ key_len,
-                                                       const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_len) {
+                                                       const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_len,
+                                                       const int32_t* __restrict__ key_row, int kv_rows) {
+  static_assert(!GATHER || SEG, "gathered keys: the segment form only");
   __shared__ __attribute__((aligned(16))) char smem[3 * 2 * TILE];   // [buffer][K tile | V tile]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int bid;
@@ -299,8 +308,21 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
   }
   const int q0 = (qb * 4 + wave) * 32;
   const int qn = lane & 31, hh = lane >> 5;
-  const T* Kb = Kp + static_cast<size_t>(b) * S * ldkv + h * HD;
-  const T* Vb = Vp + static_cast<size_t>(b) * S * ldkv + h * HD;
+  const T* Kb = Kp + (GATHER ? 0 : static_cast<size_t>(b) * S * ldkv) + h * HD;
+  const T* Vb = Vp + (GATHER ? 0 : static_cast<size_t>(b) * S * ldkv) + h * HD;
+  const uint32_t* kidx = nullptr;      // GATHER: [S] byte offset of the row of key j in Kp / Vp
+  if constexpr (GATHER) {
+    extern __shared__ __attribute__((aligned(16))) char smem_idx[];
+    uint32_t* w = reinterpret_cast<uint32_t*>(smem_idx);
+    const int32_t* src = key_row + static_cast<size_t>(b) * S;
+    for (int j = tid; j < S; j += 256) {
+      int r = src[j];
+      r = r < 0 ? 0 : (r >= kv_rows ? kv_rows - 1 : r);
+      w[j] = static_cast<uint32_t>(r) * static_cast<uint32_t>(ldkv) * static_cast<uint32_t>(sizeof(T));
+    }
+    kidx = w;
+    __syncthreads();
+  }
 
   const float qscale = scale * 1.4426950408889634f;
   uint4 qf[4];
@@ -323,6 +345,16 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
   const uint32_t lo0 = static_cast<uint32_t>(r0s * ldkv + chs * 8) * 2u, lo1 = lo0 + static_cast<uint32_t>(32 * ldkv) * 2u;
   auto load_tile = [=](int tile) -> Staged {
     Staged st;
+    if constexpr (GATHER) {
+      const uint32_t g0 = kidx[tile * BKV + r0s] + chs * 16u, g1 = kidx[tile * BKV + r0s + 32] + chs * 16u;
+      const char* kt = reinterpret_cast<const char*>(Kb);
+      const char* vt = reinterpret_cast<const char*>(Vb);
+      st.k0 = *reinterpret_cast<const uint4*>(kt + g0);
+      st.k1 = *reinterpret_cast<const uint4*>(kt + g1);
+      st.v0 = *reinterpret_cast<const uint4*>(vt + g0);
+      st.v1 = *reinterpret_cast<const uint4*>(vt + g1);
+      return st;
+    }
     const char* kt = reinterpret_cast<const char*>(Kb + static_cast<size_t>(tile) * BKV * ldkv);
     const char* vt = reinterpret_cast<const char*>(Vb + static_cast<size_t>(tile) * BKV * ldkv);
     st.k0 = *reinterpret_cast<const uint4*>(kt + lo0);
@@ -441,9 +473,16 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
     SB();
     if constexpr (STG != 0) {      // unconditional in the tile index (a branch on it splits the block and hipcc sinks the vector work
       // behind it): past the end the last tile is staged again, into a buffer that is no longer read
-      const char* gt = reinterpret_cast<const char*>((STG == 1 ? Kb : Vb) + static_cast<size_t>(stile < n_tiles ? stile : n_tiles - 1) * BKV * ldkv);
-      h0 = *reinterpret_cast<const uint4*>(gt + lo0);
-      h1 = *reinterpret_cast<const uint4*>(gt + lo1);
+      const int stc = stile < n_tiles ? stile : n_tiles - 1;
+      if constexpr (GATHER) {
+        const char* gt = reinterpret_cast<const char*>(STG == 1 ? Kb : Vb);
+        h0 = *reinterpret_cast<const uint4*>(gt + (kidx[stc * BKV + r0s] + chs * 16u));
+        h1 = *reinterpret_cast<const uint4*>(gt + (kidx[stc * BKV + r0s + 32] + chs * 16u));
+      } else {
+        const char* gt = reinterpret_cast<const char*>((STG == 1 ? Kb : Vb) + static_cast<size_t>(stc) * BKV * ldkv);
+        h0 = *reinterpret_cast<const uint4*>(gt + lo0);
+        h1 = *reinterpret_cast<const uint4*>(gt + lo1);
+      }
     }
     read_v(0, 0);
     read_v(0, 1);
@@ -862,9 +901,31 @@ int mfma_attention32(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_
                                 static_cast<T*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, a.key_len)
 #define D3PM_ATTN32P(KERNEL, T) \
   KERNEL<<<grid, block, 0, s>>>(static_cast<const T*>(a.Q), a.ldq, static_cast<const T*>(a.K), static_cast<const T*>(a.V), a.ldkv, \
-                                static_cast<T*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, a.key_len, a.seg_start, a.seg_len)
+                                static_cast<T*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, a.key_len, a.seg_start, a.seg_len, nullptr, 0)
   D3PM_REQUIRE((a.seg_len != nullptr) == (a.seg_start != nullptr) && (!a.seg_len || p.kernel == ATTN_32P), D3PM_E_SHAPE,
                "query segments: the pipelined 32 x 32 x 16 self-attention only");
+  D3PM_REQUIRE(!a.key_row || (p.kernel == ATTN_32P && a.seg_len), D3PM_E_SHAPE,
+               "gathered keys: the pipelined 32 x 32 x 16 self-attention with query segments only");
+  if (a.key_row) {      // keys through a row index: instantiations of their own again
+    // the staged index holds 32-bit byte offsets of the rows; 4 S bytes of LDS behind the tiles stay inside a workgroup's 64 KiB
+    const size_t es = dtype == D3PM_F16 ? sizeof(f16) : sizeof(bf16);
+    D3PM_REQUIRE(a.kv_rows > 0 && static_cast<unsigned long long>(a.kv_rows) * static_cast<unsigned long long>(a.ldkv) * es < (1ull << 32) &&
+                     static_cast<size_t>(a.S) * 4 <= kGatherIndexBytes && p.lds == static_cast<size_t>(a.S) * 4,
+                 D3PM_E_SHAPE, "gathered keys: kv_rows * ldkv * sizeof(T) must stay under 2^32 and S (%d) under %d", a.S,
+                 static_cast<int>(kGatherIndexBytes / 4) + 1);
+#define D3PM_ATTN32G(MASK, T)                                                                                                             \
+  attn32p_hd64<T, MASK, true, true><<<grid, block, p.lds, s>>>(static_cast<const T*>(a.Q), a.ldq, static_cast<const T*>(a.K),            \
+                                                               static_cast<const T*>(a.V), a.ldkv, static_cast<T*>(a.O), a.ldo, a.Tq, a.S, \
+                                                               a.scale, a.H, n_qblocks, a.key_len, a.seg_start, a.seg_len, a.key_row, a.kv_rows)
+    if (p.masked) {
+      if (dtype == D3PM_F16) D3PM_ATTN32G(true, f16); else D3PM_ATTN32G(true, bf16);
+    } else {
+      if (dtype == D3PM_F16) D3PM_ATTN32G(false, f16); else D3PM_ATTN32G(false, bf16);
+    }
+#undef D3PM_ATTN32G
+    D3PM_LAUNCH_CHECK();
+    return D3PM_OK;
+  }
   if (p.kernel == ATTN_32P && a.seg_len) {      // query segments: instantiations of their own, the others stay the code they were
     if (p.masked) {
       if (dtype == D3PM_F16) D3PM_ATTN32P((attn32p_hd64<f16, true, true>), f16); else D3PM_ATTN32P((attn32p_hd64<bf16, true, true>), bf16);

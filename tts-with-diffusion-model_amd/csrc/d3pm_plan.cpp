@@ -278,6 +278,7 @@ AttnPlan plan_attention(int dtype, const AttnArgs& a, bool force_generic) {
     p.masked = a.key_len != nullptr;
     p.n_qblocks = a.Tq / 128;
     p.grid = static_cast<unsigned>(p.n_qblocks * a.H * a.B);
+    if (a.key_row && !plain_walk32) p.lds = static_cast<size_t>(a.S) * 4;      // the staged key index behind the static tiles
     return p;
   }
   // The resident cross pair (<= 64 text keys, <= 256 prompt keys; key lengths do not change the choice: S / S2 are the padded

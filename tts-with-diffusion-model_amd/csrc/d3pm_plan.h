@@ -17,6 +17,8 @@ constexpr int BM = 128, BN = 128;                       // the 128 x 128 GEMM fa
 constexpr int KC = 256;                                 // k per round of the panel64 family (d3pm_mfma_gemm_lat.hip)
 constexpr int HD = 64, BKV = 64, ROWB = 128;            // attention: head width, keys per tile, bytes per K / V row
 constexpr int TILE = BKV * ROWB;                        // 8 KiB per K or V tile
+// gathered keys (AttnArgs::key_row, attn32p_hd64): the staged index, 4 bytes per key, shares a workgroup's 64 KiB with 48 KiB of tiles
+constexpr size_t kGatherIndexBytes = 16 * 1024;
 
 // epilogue bits = the EPI template argument of every GEMM kernel (d3pm_mfma_tile.h epilogue_store)
 constexpr int EPI_GELU = 1, EPI_R1 = 2, EPI_R2 = 4, EPI_MASK = 8, EPI_RELU = 16, EPI_SILU = 32, EPI_LNF = 64, EPI_STATS = 128;

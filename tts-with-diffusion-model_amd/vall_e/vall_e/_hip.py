@@ -362,6 +362,9 @@ SIGNATURES = {
     "d3pm_op_attention_keylen": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                            C.c_void_p, C.POINTER(Tuning), C.c_void_p]),
+    "d3pm_op_attention_gather": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                           C.c_void_p, C.POINTER(Tuning), C.c_void_p]),
     "d3pm_op_attention_pair": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_float, C.POINTER(Tuning), C.c_void_p]),
@@ -1119,6 +1122,30 @@ def op_attention(q, k, v, n_heads, scale, *, family=0, key_len=None):
                                          B, Tq, S, n_heads, d // n_heads, float(scale), _p(key_len), C.byref(TUNING), stream_ptr()),
           "d3pm_op_attention_keylen")
     return o
+
+
+def op_attention_gather(q, k, v, key_row, seg_start, seg_len, n_heads, scale, out, *, key_len=None):
+    """The self-attention of the deduplicated loop (d3pm_op_attention_gather): q / out [rows, d], where utterance b owns the seg_len[b]
+    rows (a multiple of 128) from row seg_start[b]; k / v [kv_rows, d], views of one packed pool that share a row stride; key j of
+    utterance b is row key_row[b, j] of them (int32 [B, S], clamped into the pool by the kernel).  Writes `out` in place (rows no segment
+    owns keep what they hold) and returns it.  The query capacity per utterance handed to the launch is rows rounded down to 128."""
+    rows, d = q.shape
+    B, S = key_row.shape
+    dev = q.device
+    if k.shape != v.shape or k.shape[1] != d or out.shape != q.shape or out.dtype != q.dtype or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise D3PMError("op_attention_gather: q / out [rows, d] and k / v [kv_rows, d] of one dtype")
+    if k.stride(0) != v.stride(0) or any(t.stride(1) != 1 for t in (q, k, v, out)) or any(t.device != dev for t in (k, v, out, key_row)):
+        raise D3PMError("op_attention_gather: k and v share a row stride; unit column strides; one device")
+    ints = [("key_row", key_row, (B, S)), ("seg_start", seg_start, (B,)), ("seg_len", seg_len, (B,))]
+    if key_len is not None:
+        ints.append(("key_len", key_len, (B,)))
+    for name, t, shape in ints:
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise D3PMError(f"{name} must be a contiguous int32 {list(shape)} tensor on {dev}")
+    check(lib().d3pm_op_attention_gather(dtype_code(q.dtype), _p(q), q.stride(0), _p(k), _p(v), k.stride(0), k.shape[0], _p(key_row),
+                                         _p(seg_start), _p(seg_len), _p(out), out.stride(0), B, rows // 128 * 128, S, n_heads, d // n_heads,
+                                         float(scale), _p(key_len), C.byref(TUNING), stream_ptr()), "d3pm_op_attention_gather")
+    return out
 
 
 def op_attention_pair(q1, k1, v1, q2, k2, v2, n_heads, scale, *, key_len=None, key_len2=None):
