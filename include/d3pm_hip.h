@@ -844,6 +844,27 @@ int d3pm_op_attention_pair_keylen(int dtype, const void *Q1, const void *K1, con
                                   const void *K2, const void *V2, void *O2, int S2, int ldq, int ldkv, int ldo, int B, int Tq,
                                   int H, int hd, float scale, const int32_t *key_len1, const int32_t *key_len2,
                                   const d3pm_tuning *tuning, void *stream);
+/* The cross pair of the deduplicated loop (tests): d3pm_op_attention_pair_keylen with query segments.  Q1 / Q2 / O1 / O2 [rows][ldq / ldo]:
+ * the queries and output rows of utterance b are the seg_len[b] rows (a multiple of 128, at most Tq, the capacity per utterance) from row
+ * seg_start[b] (device int32 [B] each); rows no segment owns are neither read nor written.  K / V [B][S][ldkv] and key_len1 / key_len2
+ * (either may be NULL) as in d3pm_op_attention_pair_keylen.  The kernel is the planner's choice under `tuning` like every other call;
+ * only the resident 32 x 32 x 16 pair takes segments (S1 <= 64, S2 <= 256, attn_cross_resident on), any other plan is D3PM_E_SHAPE
+ * with nothing launched.  A row's bits are those of d3pm_op_attention_pair on the segment's rows alone under attn_cross_resident = 5. */
+int d3pm_op_attention_pair_segments(int dtype, const void *Q1, const void *K1, const void *V1, void *O1, int S1, const void *Q2,
+                                    const void *K2, const void *V2, void *O2, int S2, int ldq, int ldkv, int ldo, int B, int Tq,
+                                    int H, int hd, float scale, const int32_t *seg_start, const int32_t *seg_len,
+                                    const int32_t *key_len1, const int32_t *key_len2, const d3pm_tuning *tuning, void *stream);
+/* The sampler launch of the deduplicated loop on its own (tests; no fold of the next iteration): canvas row r of batch * canvas draws
+ * x_next[r] from the logits of compact row row_of[r] (device int32 [batch * canvas], clamped into [0, batch * canvas - 1] by the
+ * kernel); logits device [batch * canvas][ldl] of a 16-bit logits_dtype, ldl >= n_classes.  Everything else stays per canvas row: x_t,
+ * the Philox row utt0 * canvas + r, `known` (uint8 [batch * canvas] or NULL: a marked row keeps x_t and reads neither its index nor
+ * any logits).  x_next2 (or NULL) receives the same ids (the loop's trace).  flags: D3PM_FLAG_GREEDY; nucleus NULL = the neutral
+ * triple.  The ids are those of d3pm_posterior_sample(_known / _sampling / _nucleus) on the gathered rows.  Refused with D3PM_E_ARG,
+ * nothing launched: a NULL row_of, fp32 logits, n_q > 1, a non-NULL guidance (the deduplicated launch has no guided form). */
+int d3pm_op_posterior_sample_rows(const d3pm_shape *shape, int batch, const void *logits, int logits_dtype, int ldl,
+                                  const int32_t *row_of, const int32_t *x_t, int32_t *x_next, int32_t *x_next2, const uint8_t *known,
+                                  int t, const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags,
+                                  const d3pm_nucleus *nucleus, const d3pm_guidance *guidance, void *stream);
 int d3pm_op_layernorm(int dtype, const void *X, void *Y, const void *w, const void *b, const void *film,
                       int M, int d, float eps, void *stream);
 /* Row-panel projection (d_model = 512): a Linear whose output is added to the residual stream, together with the LayerNorm(s)

@@ -8,7 +8,14 @@ output is the probability matrix, compared entry by entry with float64 under a b
 and their derivation: tests/attention_ref.py; that the bound catches the mistakes it is meant to catch: tests/test_attention_ref_api.py.
 
 Two utterances, two heads of 64, at most 300 queries and 256 keys; K / V are views of packed [.., 2 d] rows; every (utterance,
-head) has different data."""
+head) has different data.
+
+"Every schedule" means every schedule these three entries reach.  Two forms are launched by the deduplicated sampler loop alone and
+have entries and tests of their own: the resident 32 x 32 x 16 pair with query segments (attn32_cross_hd64 SEG,
+d3pm_op_attention_pair_segments) in tests/test_gpu_segment_ops.py, and the pipelined 32 x 32 x 16 self-attention with query segments
+and its keys read through a row index (attn32p_hd64 SEG / GATHER, d3pm_op_attention_gather) in tests/test_gpu_attention_gather.py.
+Both are compared bit for bit with the fixed-stride schedules pinned here, and tests/test_gpu_segment_ops.py runs the selector
+inputs of this file through both."""
 import pytest
 import torch
 

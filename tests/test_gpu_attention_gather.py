@@ -9,7 +9,12 @@ The key pool is the slice [8 : 8 + R] of a tensor with 8 guard rows on each side
 a guard row, which changes bits instead of leaving the allocation.
 
 Two utterances, two heads of 64 (d = 128), R = 384 pool rows; S = 64 ends in the prologue, 128 walks two tiles without staging a
-third, 256 runs the loop with tiles staged two ahead and the clamp of the staged tile index behind the last one."""
+third, 256 runs the loop with tiles staged two ahead and the clamp of the staged tile index behind the last one.
+
+Two more cases at the kernel's design point: the geometry the loop launches at the benchmark's model (768 keys, 8 heads, [rows][3 d]
+stride, query segments of 128 and 768 rows), and a pool of 3.07 GB -- strictly between 2^31 and 2^32 bytes -- in which key_row names
+rows on both sides of byte 2^31, the row that straddles it and the last row, with indices beyond kv_rows - 1 that clamp onto it.  Only
+the indexed rows of that pool are written; it is freed when the module is done."""
 import pytest
 import torch
 
@@ -49,7 +54,7 @@ def _pool(dtype, width):
     return _POOLS[key]
 
 
-def _index(kind, S, seed=0):
+def _index(kind, S, seed=0, R=R):
     gen = torch.Generator().manual_seed(100 + S + seed)
     if kind == "identity":      # consecutive rows per utterance: what the fixed-stride kernel walks
         idx = torch.stack([torch.arange(S) + b * (R - S) for b in range(B)])
@@ -72,29 +77,30 @@ def _i32(values):
     return torch.tensor(values, dtype=torch.int32, device=DEV)
 
 
-def _expected(q, k, v, key_row, seg_start, seg_len, key_len=None):
-    """per utterance: the fixed-stride 32 x 32 x 16 kernel on the materialised keys of its clamped index"""
+def _expected(q, k, v, key_row, seg_start, seg_len, key_len=None, heads=H):
+    """per utterance: the fixed-stride 32 x 32 x 16 kernel on the materialised keys of its clamped index (the pool is k's rows)"""
     from vall_e.vall_e import _hip
     out = torch.full_like(q, SENTINEL)
-    idx = key_row.long().clamp(0, R - 1)
+    d = q.shape[1]
+    idx = key_row.long().clamp(0, k.shape[0] - 1)
     with _hip.tuning(attn_query_groups=32):
         for b, (s0, n) in enumerate(zip(seg_start, seg_len)):
             kv = torch.cat([k[idx[b]], v[idx[b]]], dim=-1).unsqueeze(0).contiguous()      # [1, S, 2 d]
             kl = None if key_len is None else key_len[b:b + 1].contiguous()
-            out[s0:s0 + n] = _hip.op_attention(q[s0:s0 + n].unsqueeze(0), kv[..., :D], kv[..., D:], H, SCALE, family=32, key_len=kl)[0]
+            out[s0:s0 + n] = _hip.op_attention(q[s0:s0 + n].unsqueeze(0), kv[..., :d], kv[..., d:], heads, SCALE, family=32, key_len=kl)[0]
     return out
 
 
-def _gathered(q, k, v, key_row, seg_start, seg_len, key_len=None):
+def _gathered(q, k, v, key_row, seg_start, seg_len, key_len=None, heads=H):
     from vall_e.vall_e import _hip
     out = torch.full_like(q, SENTINEL)
-    _hip.op_attention_gather(q, k, v, key_row, _i32(seg_start), _i32(seg_len), H, SCALE, out, key_len=key_len)
+    _hip.op_attention_gather(q, k, v, key_row, _i32(seg_start), _i32(seg_len), heads, SCALE, out, key_len=key_len)
     return out
 
 
-def _check(q, k, v, key_row, seg_start, seg_len, key_len=None):
-    want = _expected(q, k, v, key_row, seg_start, seg_len, key_len)
-    got = _gathered(q, k, v, key_row, seg_start, seg_len, key_len)
+def _check(q, k, v, key_row, seg_start, seg_len, key_len=None, heads=H):
+    want = _expected(q, k, v, key_row, seg_start, seg_len, key_len, heads)
+    got = _gathered(q, k, v, key_row, seg_start, seg_len, key_len, heads)
     torch.cuda.synchronize()
     covered = torch.zeros(q.shape[0], dtype=torch.bool, device=DEV)
     for s0, n in zip(seg_start, seg_len):
@@ -135,3 +141,64 @@ def test_packed_qkv_stride(dtype):
     assert k.stride(0) == 3 * D and v.stride(0) == 3 * D
     _check(q[:256], k, v, _index("random", 256, seed=5), (0, 128), (128, 128))
     _check(q[:256], k, v, _index("outside", 192, seed=6), (0, 128), (128, 128), key_len=_i32((192, 65)))
+
+
+# ---- the loop's own geometry ------------------------------------------------------------------------------------------------------
+LOOP_H, LOOP_S, LOOP_R = 8, 768, 2048
+LOOP_D = LOOP_H * HD
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("kind", ["random", "outside"])
+def test_loop_geometry(kind, dtype):
+    """what the deduplicated loop launches at the benchmark's model: 768 keys per utterance (twelve tiles, the staged index 3 KiB behind
+    the static tiles), 8 heads of 64, k / v the columns d : 2 d and 2 d : 3 d of a [rows][3 d] pool (2048 rows between 8 guard rows of 50
+    on each side), two utterances with query segments of 128 and 768 rows"""
+    gen = torch.Generator().manual_seed(21)
+    full = torch.full((LOOP_R + 2 * GUARD, 3 * LOOP_D), 50.0, dtype=dtype)
+    full[GUARD:GUARD + LOOP_R] = torch.randn(LOOP_R, 3 * LOOP_D, generator=gen).to(dtype)
+    live = full.to(DEV)[GUARD:GUARD + LOOP_R]
+    k, v = live[:, LOOP_D:2 * LOOP_D], live[:, 2 * LOOP_D:]
+    assert k.stride(0) == 3 * LOOP_D and v.stride(0) == 3 * LOOP_D
+    q = torch.randn(128 + 768, LOOP_D, generator=gen).to(dtype).to(DEV)
+    _check(q, k, v, _index(kind, LOOP_S, seed=7, R=LOOP_R), (0, 128), (128, 768), heads=LOOP_H)
+
+
+# ---- 32-bit byte offsets across 2^31 ----------------------------------------------------------------------------------------------
+BIG_ROWS = 1_000_000                     # x 3 * 512 columns x 2 bytes = 3 072 000 000 bytes: between 2^31 and 2^32
+BIG_LINE = 2 ** 31 // (3 * LOOP_D * 2)   # row 699 050 starts below byte 2^31 and ends above it
+BIG_NAMED = [0, 1, 2 ** 30 // (3 * LOOP_D * 2), BIG_LINE - 1, BIG_LINE, BIG_LINE + 1, BIG_LINE + 2, BIG_ROWS - 2, BIG_ROWS - 1]
+BIG_BEYOND = [BIG_ROWS, BIG_ROWS + 7, 2 ** 31 - 1]      # clamp onto the last row
+BIG_BELOW = [-1, -2 ** 31]                              # clamp onto row 0
+
+
+@pytest.fixture(scope="module")
+def big_pool(built_lib):
+    """one uninitialised allocation for both dtypes, freed when the module is done; only the rows a test indexes are ever written"""
+    assert 2 ** 31 < BIG_ROWS * 3 * LOOP_D * 2 < 2 ** 32 and BIG_LINE * 3 * LOOP_D * 2 < 2 ** 31 < (BIG_LINE + 1) * 3 * LOOP_D * 2
+    holder = [torch.empty((BIG_ROWS, 3 * LOOP_D), dtype=torch.int16, device=DEV)]
+    yield holder
+    holder.clear()
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_row_offsets_across_2_to_the_31_bytes(big_pool, dtype):
+    """The design point of the 32-bit byte offsets: a pool of 3.07 GB.  key_row names rows on both sides of byte 2^31, the row that
+    straddles it, the last row (whose v columns end with the allocation), and indices beyond kv_rows - 1 and below 0, which must clamp
+    to the last and the first row.  An offset that went through a signed 32-bit intermediate would turn negative from row 699 051 on."""
+    pool = big_pool[0].view(dtype)
+    gen = torch.Generator().manual_seed(31)
+    named = torch.tensor(BIG_NAMED)
+    pool[named.to(DEV)] = torch.randn(len(named), 3 * LOOP_D, generator=gen).to(dtype).to(DEV)
+    k, v = pool[:, LOOP_D:2 * LOOP_D], pool[:, 2 * LOOP_D:]
+    S = 128
+    choice = torch.tensor(BIG_NAMED + BIG_BEYOND + BIG_BELOW)
+    idx = choice[torch.randint(0, len(choice), (B, S), generator=gen)]
+    idx[0, :len(choice)] = choice                       # every one of them at least once, the straddling row in both utterances
+    idx[1, S - len(choice):] = choice.flip(0)
+    q = torch.randn(256, LOOP_D, generator=gen).to(dtype).to(DEV)
+    key_row = idx.to(torch.int32).to(DEV)
+    assert int(key_row.max()) == 2 ** 31 - 1 and int(key_row.min()) == -2 ** 31
+    _check(q, k, v, key_row, (0, 128), (128, 128), heads=LOOP_H)
+    _check(q, k, v, key_row, (0, 128), (128, 128), key_len=_i32((S, 65)), heads=LOOP_H)

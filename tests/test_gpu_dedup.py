@@ -376,6 +376,91 @@ def test_graph_captured_loop(models):
     assert sum(counts[3]) > 0 and counts[1] != counts[3], counts
 
 
+# ---- the deduplicated evaluation against the CPU oracle ---------------------------------------------------------------------------
+def _half_denoised(cfg, rng):
+    """[B, canvas] canvases with every other live frame carrying an id.  Utterance 0 draws its ids from eight values, so nearly all of
+    its rows merge; the ids of utterance 1 are all distinct, so none of its revealed rows do; the others draw from all 1024."""
+    x = np.zeros((B, cfg.canvas), np.int64)
+    x[:, : cfg.n_frames] = cfg.mask_id
+    live = np.arange(0, cfg.n_frames, 2)
+    for b in range(B):
+        if b == 0:
+            x[b, live] = rng.choice([3, 1023, 17, 900, 5, 6, 640, 1], size=live.shape)
+        elif b == 1:
+            x[b, live] = rng.permutation(np.setdiff1d(np.arange(1024), [cfg.mask_id]))[: len(live)]
+        else:
+            x[b, live] = rng.integers(0, 1024, size=live.shape)
+    return x
+
+
+@pytest.mark.parametrize("tag,dtype,tie,frac", [("f16", torch.float16, 0.06, 0.01), ("bf16", torch.bfloat16, 0.5, 0.05)])
+def test_deduplicated_step_against_the_oracle(models, tag, dtype, tie, frac):
+    """x_49 of sample_loop(x_50, .., 50, 48, trace=True) -- iteration 50 of a call that runs the deduplicated launch list: table rows,
+    compact projections, segment attention, gathered keys, the sampler through row_of -- against the CPU oracle's own draw from its own
+    logits, conditions and Philox noise, exactly as test_libritts_shape_step_against_the_oracle compares the every-row evaluation:
+    an id may differ only where the oracle's Gumbel race was a near-tie.  The bounds are that test's (worst gap < 0.06 fp16 / 0.5
+    bf16, mismatch fraction < 0.01 / 0.05), set on the six-layer model; two layers accumulate less rounding.
+    Measured here (two layers, utterances 0 and 1, 1400 live frames), fp16 and bf16 alike, ln_fold = 1 and 3 alike: worst gap 0.0,
+    mismatch fraction 0.0 (0 of 1400).  What that covers: 700 of the 1400 frames are masked and race; at t = 50 the oracle lets 3 + 13 of
+    them leave the mask, and it decided 2 of the 700 races by less than 0.06 and 19 by less than 0.5 (smallest 0.039).  The revealed
+    frames keep their id whatever the logits are."""
+    from oracle import d3pm_oracle as O
+    from oracle import philox
+    from util import REPORT
+    from vall_e.vall_e import synth
+    cfg, get = models
+    m, texts, proms, ct, cp = get(dtype)
+    smp = m.sampler()
+    kv = smp.cond_kv(ct, cp)
+    _, fm = m.canvas_init(B)
+    xs = _half_denoised(cfg, np.random.default_rng(7))
+    x0 = torch.from_numpy(xs.astype(np.int32)).to(DEV)
+    assert len(set(xs[0].tolist())) <= 10 and len(set(xs[1, : cfg.n_frames : 2].tolist())) == (cfg.n_frames + 1) // 2
+    t, seed = 50, 321
+    traces = {}
+    for ln_fold in (1, 3):
+        x = x0.clone()
+        with _ln_fold(ln_fold):
+            traces[ln_fold] = smp.sample_loop(x, fm, t, t - 2, kv[0], kv[1], seed=seed, trace=True)
+        torch.cuda.synchronize()
+    # the launch counters are read in iterations with t % 16 == 0 only, and the two lists differ in count where an iteration prepares
+    # the next one (the index launches): the same call extended by two iterations has t = 48 as such an iteration (the choice of the
+    # launch list is made once per call and does not look at the step range beyond "at least two iterations")
+    assert _deduplicates(smp, x0, fm, kv, t, t - 4)
+    orc = O.Oracle({k: v.to(dtype) for k, v in synth.make_state_dict(cfg, 0).items()}, O.Shape.of(cfg))
+    mask = torch.zeros(cfg.canvas, dtype=torch.bool)
+    mask[: cfg.n_frames] = True
+    assert torch.equal(fm.cpu().bool().view(-1)[-cfg.canvas:], mask)
+    live = slice(0, cfg.n_frames)
+    stats = {}
+    wants = []
+    for b in range(2):
+        with torch.no_grad():
+            ocp, oct_ = orc.conditions(texts[b], proms[b])
+            ref = orc.logits(torch.from_numpy(xs[b]), t, ocp, oct_, mask)
+            post = orc.posterior(ref, torch.from_numpy(xs[b]), t)
+        u = torch.from_numpy(philox.uniform_batch(seed, t, b, 1, cfg.canvas)[0])
+        v = post.float() + -torch.log(-torch.log(torch.clamp(u, min=torch.finfo(torch.float32).tiny, max=1.0)))
+        wants.append((v, torch.argmax(v, dim=-1).numpy()))
+    for ln_fold, tr in traces.items():
+        worst_gap, mism, total = 0.0, 0, 0
+        for b, (v, want) in enumerate(wants):
+            nxt = tr[0, b].cpu().numpy()
+            for r in np.nonzero(nxt[live] != want[live])[0]:      # position by position: how clearly had the oracle's race been decided?
+                worst_gap = max(worst_gap, (v[r, want[r]] - v[r, nxt[r]]).item())
+            mism += int((nxt[live] != want[live]).sum())
+            total += cfg.n_frames
+        stats[ln_fold] = (worst_gap, mism / total)
+        REPORT[f"dedup_{tag}_ln_fold{ln_fold}_sampled_id_worst_gap"] = worst_gap
+        REPORT[f"dedup_{tag}_ln_fold{ln_fold}_sampled_id_mismatch_frac"] = mism / total
+        print(f"[dedup oracle] {tag} ln_fold={ln_fold}: worst gap {worst_gap:.4f}, mismatch fraction {mism / total:.5f} ({mism} of {total})")
+    # the every-row arm first: if IT misses a bound the inputs are at fault, not the deduplicated evaluation
+    assert stats[3][0] < tie and stats[3][1] < frac, f"ln_fold = 3 misses the bounds on these inputs: {stats[3]}"
+    assert stats[1][0] < tie, f"a sampled id differs where the oracle's race was decided by {stats[1][0]}"
+    assert stats[1][1] < frac, stats[1]
+    assert torch.equal(traces[1], traces[3])
+
+
 # ---- attention: a query row's bits do not depend on its wave-mates ------------------------------------------------------------------
 def _hostile_inputs(dtype):
     """128 queries, 96 keys, one head of 64.  Every query carries the direction w (|w| = 1) and the keys of the third 32-key block

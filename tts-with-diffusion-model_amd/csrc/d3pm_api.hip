@@ -1164,6 +1164,29 @@ int d3pm_posterior_sample_nucleus(const d3pm_shape* sh, int batch, const void* l
                                theta_out, "d3pm_posterior_sample_nucleus");
 }
 
+// the sampler launch of the deduplicated loop on its own (tests): posterior_sample_dedup with no next-iteration fold
+int d3pm_op_posterior_sample_rows(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, int ldl, const int32_t* row_of,
+                                  const int32_t* x_t, int32_t* x_next, int32_t* x_next2, const uint8_t* known, int t,
+                                  const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, const d3pm_nucleus* nucleus,
+                                  const d3pm_guidance* guidance, void* stream) {
+  const char* who = "d3pm_op_posterior_sample_rows";
+  D3PM_TRY(check_shape(sh, batch));
+  D3PM_TRY(check_sampling(sh, nucleus, who));
+  D3PM_REQUIRE(logits && x_t && x_next && sched && sched->d && sched->c && sched->dbar && sched->cbar, D3PM_E_ARG, "%s: null pointer", who);
+  D3PM_REQUIRE(t >= 0 && t < sched->timesteps, D3PM_E_ARG, "t=%d outside the schedule", t);
+  D3PM_REQUIRE(ldl >= sh->n_classes, D3PM_E_ARG, "%s: row stride %d below n_classes %d", who, ldl, sh->n_classes);
+  D3PM_REQUIRE(!(flags & D3PM_FLAG_SEED_IN_HBM), D3PM_E_ARG, "%s: the seed travels by value", who);
+  SampleArgs a;
+  a.logits = logits; a.logits_dtype = logits_dtype; a.ldl = ldl; a.x_t = x_t; a.x_next = x_next; a.x_next2 = x_next2;
+  a.rows = batch * sh->canvas * levels(*sh); a.n_classes = sh->n_classes; a.mask_id = sh->mask_id; a.n_q = levels(*sh);
+  a.canvas = sh->canvas; a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas);
+  a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0; a.pc = make_posterior_consts(sched, t);
+  a.known = known;
+  if (nucleus) { a.temperature = nucleus->temperature; a.top_k = nucleus->top_k; a.top_p = nucleus->top_p; }
+  if (guidance) { a.guided = true; a.guidance = guidance->weight; }      // refused below: the deduplicated launch has no guided form
+  return posterior_sample_dedup(a, row_of, NextIterPrep{}, static_cast<hipStream_t>(stream));
+}
+
 static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const CanvasMask& cm,
                             int t_start, int t_stop, const void* film, const void* kv_text, const void* kv_prompt,
                             const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace,
@@ -1762,6 +1785,24 @@ int d3pm_op_attention_pair(int dtype, const void* Q1, const void* K1, const void
                            const d3pm_tuning* tuning, void* stream) {
   return d3pm_op_attention_pair_keylen(dtype, Q1, K1, V1, O1, S1, Q2, K2, V2, O2, S2, ldq, ldkv, ldo, B, Tq, H, hd, scale, nullptr, nullptr,
                                        tuning, stream);
+}
+
+// the cross pair of the deduplicated loop (tests): query segments through the planner and the launcher like any other call -- a plan
+// other than the resident 32 x 32 x 16 pair is refused by run_attention, which knows which kernels take segments
+int d3pm_op_attention_pair_segments(int dtype, const void* Q1, const void* K1, const void* V1, void* O1, int S1, const void* Q2,
+                                    const void* K2, const void* V2, void* O2, int S2, int ldq, int ldkv, int ldo, int B, int Tq, int H,
+                                    int hd, float scale, const int32_t* seg_start, const int32_t* seg_len, const int32_t* key_len1,
+                                    const int32_t* key_len2, const d3pm_tuning* tuning, void* stream) {
+  D3PM_REQUIRE(Q1 && K1 && V1 && O1 && Q2 && K2 && V2 && O2 && seg_start && seg_len && B > 0 && Tq > 0 && S1 > 0 && S2 > 0 && H > 0 && hd > 0,
+               D3PM_E_ARG, "d3pm_op_attention_pair_segments: bad arguments");
+  const Ctx cx(tuning);
+  AttnArgs a;
+  a.tune = tuning;
+  a.Q = Q1; a.ldq = ldq; a.K = K1; a.V = V1; a.ldkv = ldkv; a.O = O1; a.ldo = ldo; a.B = B; a.Tq = Tq; a.S = S1; a.H = H;
+  a.hd = hd; a.scale = scale;
+  a.Q2 = Q2; a.K2 = K2; a.V2 = V2; a.O2 = O2; a.S2 = S2;
+  a.key_len = key_len1; a.key_len2 = key_len2; a.seg_start = seg_start; a.seg_len = seg_len;
+  return run_attention(cx, dtype, a, 0, static_cast<hipStream_t>(stream));
 }
 
 int d3pm_op_layernorm(int dtype, const void* X, void* Y, const void* w, const void* b, const void* film, int M, int d,

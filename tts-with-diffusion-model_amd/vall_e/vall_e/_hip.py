@@ -368,6 +368,13 @@ SIGNATURES = {
     "d3pm_op_attention_pair": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_float, C.POINTER(Tuning), C.c_void_p]),
+    "d3pm_op_attention_pair_segments": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Tuning),
+                                                  C.c_void_p]),
+    "d3pm_op_posterior_sample_rows": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32,
+                                                C.POINTER(Nucleus), C.POINTER(Guidance), C.c_void_p]),
     "d3pm_op_layernorm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_int, C.c_float, C.c_void_p]),
     "d3pm_op_linear_rowpanel": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1175,6 +1182,72 @@ def op_attention_pair(q1, k1, v1, q2, k2, v2, n_heads, scale, *, key_len=None, k
                                        q1.stride(1), k1.stride(1), d, B, Tq, n_heads, d // n_heads, float(scale), C.byref(TUNING),
                                        stream_ptr()), "d3pm_op_attention_pair")
     return o1, o2
+
+
+def _require_int32(pairs, dev):
+    for name, t, shape in pairs:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or t.device != dev or not t.is_contiguous():
+            raise D3PMError(f"{name} must be a contiguous int32 {list(shape)} tensor on {dev}")
+
+
+def op_attention_pair_segments(q1, k1, v1, q2, k2, v2, seg_start, seg_len, n_heads, scale, out1, out2, capacity, *, key_len=None,
+                               key_len2=None):
+    """The cross pair of the deduplicated loop (d3pm_op_attention_pair_segments): q1 / q2 / out1 / out2 [rows, d], where utterance b owns
+    the seg_len[b] rows (a multiple of 128, at most `capacity`) from row seg_start[b]; k1 / v1 [B, S1, d], k2 / v2 [B, S2, d] as in
+    op_attention_pair; key_len / key_len2 int32 [B] or None.  Writes out1 / out2 in place (rows no segment owns keep what they hold)
+    and returns them.  The kernel is the planner's choice under the current tuning; a plan that takes no segments raises D3PMError."""
+    if q1.dim() != 2 or k1.dim() != 3 or k2.dim() != 3:
+        raise D3PMError("op_attention_pair_segments: q / out [rows, d] and k / v [B, S, d]")
+    rows, d = q1.shape
+    B, S1, S2 = k1.shape[0], k1.shape[1], k2.shape[1]
+    dev = q1.device
+    same = (q2, out1, out2)
+    if any(t.shape != q1.shape for t in same) or k1.shape != v1.shape or k2.shape != v2.shape or k2.shape[0] != B or k1.shape[2] != d or k2.shape[2] != d:
+        raise D3PMError("op_attention_pair_segments: q1 / q2 / out1 / out2 [rows, d], k1 / v1 [B, S1, d], k2 / v2 [B, S2, d]")
+    tensors = (q1, q2, out1, out2, k1, v1, k2, v2)
+    if any(t.dtype != q1.dtype or t.device != dev or t.stride(-1) != 1 for t in tensors):
+        raise D3PMError("op_attention_pair_segments: one dtype, one device, unit column strides")
+    if q1.stride(0) != q2.stride(0) or out1.stride(0) != out2.stride(0) or len({t.stride(1) for t in (k1, v1, k2, v2)}) != 1 or \
+            k1.stride(0) != S1 * k1.stride(1) or v1.stride(0) != S1 * v1.stride(1) or k2.stride(0) != S2 * k2.stride(1) or v2.stride(0) != S2 * v2.stride(1):
+        raise D3PMError("op_attention_pair_segments: q1 / q2, out1 / out2 and the four K / V views share their row strides; K / V batches are dense")
+    if not isinstance(capacity, int) or capacity <= 0 or capacity % 128 or capacity > rows:
+        raise D3PMError(f"op_attention_pair_segments: capacity {capacity!r} must be a multiple of 128 within the {rows} rows")
+    ints = [("seg_start", seg_start, (B,)), ("seg_len", seg_len, (B,))]
+    ints += [(n, t, (B,)) for n, t in (("key_len", key_len), ("key_len2", key_len2)) if t is not None]
+    _require_int32(ints, dev)
+    check(lib().d3pm_op_attention_pair_segments(dtype_code(q1.dtype), _p(q1), _p(k1), _p(v1), _p(out1), S1, _p(q2), _p(k2), _p(v2), _p(out2), S2,
+                                                q1.stride(0), k1.stride(1), out1.stride(0), B, capacity, n_heads, d // n_heads, float(scale),
+                                                _p(seg_start), _p(seg_len), _p(key_len), _p(key_len2), C.byref(TUNING), stream_ptr()),
+          "d3pm_op_attention_pair_segments")
+    return out1, out2
+
+
+def op_posterior_sample_rows(shape, schedule, logits, row_of, x_t, t, seed, *, utt0=0, flags=0, known=None, temperature=1.0, top_k=0,
+                             top_p=1.0, guidance=0.0, want_second=False):
+    """The sampler launch of the deduplicated loop on its own (d3pm_op_posterior_sample_rows): x_t int32 [B, shape.canvas]; logits
+    [B * canvas, n_classes] f16 / bf16 (a view with a wider row stride allowed); row_of int32 [B * canvas]: canvas row r draws from
+    logits[row_of[r]] (clamped into the rows by the kernel).  known uint8 [B, canvas] or None.  Returns x_next, or (x_next, second)
+    with want_second, the second output being what the loop writes into its trace.  `schedule` a Schedule; guidance is refused by the
+    library (the deduplicated launch has no guided form)."""
+    if not isinstance(x_t, torch.Tensor) or x_t.dim() != 2 or x_t.shape[1] != shape.canvas or x_t.dtype != torch.int32 or not x_t.is_contiguous():
+        raise D3PMError(f"x_t must be a contiguous int32 [B, {shape.canvas}] tensor")
+    dev, rows = x_t.device, x_t.numel()
+    if not isinstance(logits, torch.Tensor) or tuple(logits.shape) != (rows, shape.n_classes) or logits.dtype not in (torch.float16, torch.bfloat16) or \
+            logits.device != dev or logits.stride(1) != 1 or logits.stride(0) < shape.n_classes:
+        raise D3PMError(f"logits must be a float16 / bfloat16 [{rows}, {shape.n_classes}] tensor on {dev} with unit column stride")
+    _require_int32([("row_of", row_of, (rows,))], dev)
+    if known is not None:
+        _require(known, "known", tuple(x_t.shape), (torch.uint8,), dev)
+    smp = nucleus_options(temperature, top_k, top_p, shape.n_classes)
+    nuc = None if smp is None else smp if isinstance(smp, Nucleus) else Nucleus(smp.temperature, smp.top_k, 1.0)
+    gd = guidance_options(guidance)
+    x_next = torch.empty_like(x_t)
+    second = torch.empty_like(x_t) if want_second else None
+    check(lib().d3pm_op_posterior_sample_rows(C.byref(shape), x_t.shape[0], _p(logits), dtype_code(logits.dtype), logits.stride(0), _p(row_of),
+                                              _p(x_t), _p(x_next), _p(second), _p(known), int(t), C.byref(schedule.c_struct), seed, utt0, flags,
+                                              None if nuc is None else C.byref(nuc), None if gd is None else C.byref(gd), stream_ptr()),
+          "d3pm_op_posterior_sample_rows")
+    return (x_next, second) if want_second else x_next
 
 
 def stats_buffer(M: int, parts: int, device) -> torch.Tensor:
