@@ -63,7 +63,9 @@ extern "C" {
  *    table (d3pm_op_embed_qkv_bytes, d3pm_op_embed_qkv; ln_fold value 2; d3pm_workspace_bytes grew by the table and one
  *    [rows][d_model] region for 16-bit models with d_model a multiple of 256 and n_q <= 1); one row per distinct token of an
  *    utterance in the unguided loops (d3pm_op_dedup_index, d3pm_op_linear_live; ln_fold value 3 = every row); its self-attention
- *    with the keys read through a row index (d3pm_op_attention_gather) */
+ *    with the keys read through a row index (d3pm_op_attention_gather); the segment granularity of that index
+ *    (d3pm_op_dedup_index_align: 1 = dense segments, what the loop runs; d3pm_op_attention_gather and
+ *    d3pm_op_attention_pair_segments take a segment of any length at any row) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -787,6 +789,13 @@ int d3pm_op_linear_fold(int dtype, const void *X, int ldx, const void *Wf, const
 int d3pm_op_dedup_index(int dtype, const int32_t *tokens, const uint8_t *frame_mask, int batch, int canvas, int n_classes, int d,
                         const void *table, int32_t *seg_start, int32_t *seg_len, int32_t *m_live, int32_t *row_of, int32_t *cid,
                         uint8_t *cmask, void *x, float *stats, int32_t *scratch, void *stream);
+/* The same index with the segment granularity chosen: seg_align = 128 is d3pm_op_dedup_index array for array; seg_align = 1 is the
+ * layout the sampler loop runs on -- seg_len[b] = the class count of utterance b, seg_start[b] = the exclusive prefix sum of the
+ * counts, m_live = their sum, no zero row inside a segment; rows m_live .. the next multiple of 384 stay zero rows with zero moments,
+ * cid = n_classes, cmask = 0.  Any other seg_align is D3PM_E_ARG. */
+int d3pm_op_dedup_index_align(int dtype, const int32_t *tokens, const uint8_t *frame_mask, int batch, int canvas, int n_classes, int d,
+                              int seg_align, const void *table, int32_t *seg_start, int32_t *seg_len, int32_t *m_live, int32_t *row_of,
+                              int32_t *cid, uint8_t *cmask, void *x, float *stats, int32_t *scratch, void *stream);
 /* A projection whose live row count is read from device memory at kernel entry (tests): the arguments of d3pm_op_linear_stats /
  * d3pm_op_linear_fold (X2: the second operand of the dual out-projection or NULL; moments travel as quads at width 512), M = the
  * capacity the launch is planned for; only the tiles that hold a row < *m_live run.  Big-tile family or the 128 x 128 one-tile-per-
@@ -822,8 +831,8 @@ int d3pm_op_attention_keylen(int dtype, int family, const void *Q, int ldq, cons
                              int B, int Tq, int S, int H, int hd, float scale, const int32_t *key_len, const d3pm_tuning *tuning,
                              void *stream);
 /* The self-attention of the deduplicated loop (tests): the pipelined 32 x 32 x 16 kernel with query segments and its keys read through
- * a row index, whatever the grid size.  Q / O [rows][ldq / ldo]: the queries and output rows of utterance b are the seg_len[b] rows (a
- * multiple of 128, at most Tq) from row seg_start[b]; rows no segment owns are not written.  K / V [kv_rows][ldkv], views of one pool:
+ * a row index, whatever the grid size.  Q / O [rows][ldq / ldo]: the queries and output rows of utterance b are the seg_len[b] rows (any
+ * count from 1 to Tq) from row seg_start[b] (any row); rows no segment owns are neither read nor written.  K / V [kv_rows][ldkv], views of one pool:
  * key j of utterance b is row key_row[b * S + j] (device int32 [B][S]), clamped into [0, kv_rows - 1]; kv_rows * ldkv * the element
  * size must stay under 2^32 and S at or under 4096.  key_len as d3pm_op_attention_keylen, or NULL.  16-bit dtype, head width 64, Tq a
  * multiple of 128 and S of 64, D3PM_E_SHAPE otherwise.  The same key values in the same order as d3pm_op_attention on the gathered
@@ -845,8 +854,8 @@ int d3pm_op_attention_pair_keylen(int dtype, const void *Q1, const void *K1, con
                                   int H, int hd, float scale, const int32_t *key_len1, const int32_t *key_len2,
                                   const d3pm_tuning *tuning, void *stream);
 /* The cross pair of the deduplicated loop (tests): d3pm_op_attention_pair_keylen with query segments.  Q1 / Q2 / O1 / O2 [rows][ldq / ldo]:
- * the queries and output rows of utterance b are the seg_len[b] rows (a multiple of 128, at most Tq, the capacity per utterance) from row
- * seg_start[b] (device int32 [B] each); rows no segment owns are neither read nor written.  K / V [B][S][ldkv] and key_len1 / key_len2
+ * the queries and output rows of utterance b are the seg_len[b] rows (any count from 1 to Tq, the capacity per utterance) from row
+ * seg_start[b] (any row; device int32 [B] each); rows no segment owns are neither read nor written.  K / V [B][S][ldkv] and key_len1 / key_len2
  * (either may be NULL) as in d3pm_op_attention_pair_keylen.  The kernel is the planner's choice under `tuning` like every other call;
  * only the resident 32 x 32 x 16 pair takes segments (S1 <= 64, S2 <= 256, attn_cross_resident on), any other plan is D3PM_E_SHAPE
  * with nothing launched.  A row's bits are those of d3pm_op_attention_pair on the segment's rows alone under attn_cross_resident = 5. */

@@ -495,6 +495,9 @@ static int run_dedup_index(const DenoiserArgs& q, const int32_t* x_t, bool quads
   // (no k | v row is gathered: the self-attention reads the table through key_cls.  att2 is h2 under workspace_alias, which nothing else of
   // this sequence writes any more, so both attention outputs are cleared behind the live rows)
   a.qkv_table = q.qkv_table; a.q0 = q.ws.q0; a.zero[0] = q.ws.att; a.zero[1] = q.ws.att2;
+  // dense segments: every launch of the iteration costs in proportion to the live rows, and none of them needs a segment to be whole
+  // 128-row workgroups (attn32p_hd64 SEG clamps its query rows and predicates its stores like the cross pair)
+  a.seg_align = 1;
   return dedup_index(sh.dtype, a, s);
 }
 
@@ -844,8 +847,16 @@ int d3pm_op_linear_fold(int dtype, const void* X, int ldx, const void* Wf, const
 int d3pm_op_dedup_index(int dtype, const int32_t* tokens, const uint8_t* frame_mask, int batch, int canvas, int n_classes, int d,
                         const void* table, int32_t* seg_start, int32_t* seg_len, int32_t* m_live, int32_t* row_of, int32_t* cid, uint8_t* cmask,
                         void* x, float* stats, int32_t* scratch, void* stream) {
+  return d3pm_op_dedup_index_align(dtype, tokens, frame_mask, batch, canvas, n_classes, d, 128, table, seg_start, seg_len, m_live, row_of, cid, cmask, x,
+                                   stats, scratch, stream);
+}
+
+int d3pm_op_dedup_index_align(int dtype, const int32_t* tokens, const uint8_t* frame_mask, int batch, int canvas, int n_classes, int d, int seg_align,
+                              const void* table, int32_t* seg_start, int32_t* seg_len, int32_t* m_live, int32_t* row_of, int32_t* cid,
+                              uint8_t* cmask, void* x, float* stats, int32_t* scratch, void* stream) {
   D3PM_REQUIRE(batch > 0 && canvas > 0 && scratch && (!table || (x && stats)), D3PM_E_ARG, "d3pm_op_dedup_index: bad arguments");
   DedupArgs a;
+  a.seg_align = seg_align;      // (dedup_index refuses anything but 1 and 128)
   a.tokens = tokens; a.frame_mask = frame_mask; a.mask_period = batch * canvas; a.batch = batch; a.canvas = canvas; a.n_classes = n_classes; a.d = d;
   a.ix.cnt = scratch; a.ix.rep_pos = scratch + batch; a.ix.seg_start = seg_start; a.ix.seg_len = seg_len; a.ix.m_live = m_live; a.ix.row_of = row_of;
   a.ix.cid = cid; a.ix.cmask = cmask;

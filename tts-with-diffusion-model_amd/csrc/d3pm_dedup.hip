@@ -7,9 +7,11 @@
 //                       position of each class is its representative, ranked in position order; row_of (still local to the utterance),
 //                       key_cls (the class of every position), the representatives' positions, the count
 //   dedup_embed_rows    one wave per index r, which is both a compact row and a canvas position: the segments (an utterance owns its
-//                       count rounded up to 128 compact rows, back to back), the embedding row + moments + block-0 q of compact row r
-//                       (a zero row with zero moments where the segment is padding, and from m_live up to the next multiple of 384, the
-//                       least common multiple of the 192- and 128-row GEMM tiles), and row_of[r] made global
+//                       count rounded up to seg_align compact rows, back to back: seg_align = 1, the loop's, packs the rows densely --
+//                       seg_len = cnt, seg_start = the exclusive prefix sum of the counts, m_live = their sum, no zero row inside a
+//                       segment; 128 gives every utterance whole self-attention workgroups), the embedding row + moments + block-0 q
+//                       of compact row r (a zero row with zero moments where a segment is padding, and from m_live up to the next
+//                       multiple of 384, the least common multiple of the 192- and 128-row GEMM tiles), and row_of[r] made global
 // No k | v row is copied into canvas order: the self-attention walks its keys through an index (attn32p_hd64 GATHER, d3pm_mfma_attn32.hip)
 // -- in block 0 row key_cls[position] of the block-0 QKV table, in the later blocks row row_of[position] of the compact QKV rows.
 // Nothing here reads anything back to the host: the counts stay in device memory and the GEMMs / attentions read them there.
@@ -69,7 +71,7 @@ __global__ __launch_bounds__(256) void dedup_index_utt(const int32_t* __restrict
 
 template <typename T>
 __global__ __launch_bounds__(256) void dedup_embed_rows(const int32_t* __restrict__ tokens, const uint8_t* __restrict__ frame_mask, int mask_period,
-                                                        int batch, int canvas, int n_classes, int d, const int32_t* __restrict__ cnt,
+                                                        int batch, int canvas, int n_classes, int d, int seg_align, const int32_t* __restrict__ cnt,
                                                         int32_t* __restrict__ seg_start, int32_t* __restrict__ seg_len, int32_t* __restrict__ m_live_out,
                                                         int32_t* __restrict__ row_of, const int32_t* __restrict__ rep_pos, int32_t* __restrict__ cid,
                                                         uint8_t* __restrict__ cmask, const T* __restrict__ table, T* __restrict__ x,
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(256) void dedup_embed_rows(const int32_t* __restric
   const int ub = r / canvas;
   int start = 0, u = -1, u_start = 0, u_cnt = 0, pos_start = 0, own_start = 0, own_len = 0;
   for (int b = 0; b < batch; ++b) {
-    const int c = cnt[b], pad = (c + 127) & ~127;
+    const int c = cnt[b], pad = (c + seg_align - 1) & ~(seg_align - 1);      // seg_align is 1 or 128 (dedup_index): a power of two
     if (r >= start && r < start + pad) { u = b; u_start = start; u_cnt = c; }
     if (b == ub) pos_start = start;
     if (b == r) { own_start = start; own_len = pad; }
@@ -97,7 +99,7 @@ __global__ __launch_bounds__(256) void dedup_embed_rows(const int32_t* __restric
   // ---- canvas position r: global row_of
   if (lane == 0) row_of[r] += pos_start;
   // ---- compact row r
-  if (r >= m_pad) return;
+  if (r >= m_pad) return;      // (m_pad <= n also with seg_align = 128: a padded count never exceeds the canvas, a multiple of 128)
   int id = 0;
   bool live = false;
   if (u >= 0 && r - u_start < u_cnt) {
@@ -128,7 +130,8 @@ int dedup_index(int dtype, const DedupArgs& a, hipStream_t s) {
   D3PM_REQUIRE(a.tokens && a.frame_mask && a.mask_period > 0 && a.batch > 0 && a.canvas > 0 && a.n_classes > 0 && ix.cnt && ix.seg_start && ix.seg_len &&
                    ix.m_live && ix.row_of && ix.rep_pos && ix.cid && ix.cmask,
                D3PM_E_ARG, "row deduplication: null pointer");
-  // (canvas a multiple of 128: a segment never exceeds its utterance's canvas, so the compact rows fit the capacity)
+  D3PM_REQUIRE(a.seg_align == 1 || a.seg_align == 128, D3PM_E_ARG, "row deduplication: seg_align is 1 or 128, not %d", a.seg_align);
+  // (canvas a multiple of 128: a segment never exceeds its utterance's canvas at either alignment, so the compact rows fit the capacity)
   D3PM_REQUIRE(a.n_classes <= kDedupMaxClasses && a.canvas % 128 == 0 && (static_cast<long long>(a.batch) * a.canvas) % 384 == 0, D3PM_E_SHAPE,
                "row deduplication: at most %d classes, canvas a multiple of 128 and batch * canvas a multiple of 384", kDedupMaxClasses);
   D3PM_REQUIRE((dtype == D3PM_F16 || dtype == D3PM_BF16) && a.d % 8 == 0 && (!a.quads || a.d == 512) && (!a.table || (a.x && a.stats)) &&
@@ -141,8 +144,8 @@ int dedup_index(int dtype, const DedupArgs& a, hipStream_t s) {
   const dim3 grid(static_cast<unsigned>((n + 3) / 4)), block(256);
   auto go = [&](auto* tag) {
     using U = std::remove_pointer_t<decltype(tag)>;
-    dedup_embed_rows<U><<<grid, block, 0, s>>>(a.tokens, a.frame_mask, a.mask_period, a.batch, a.canvas, a.n_classes, a.d, ix.cnt, ix.seg_start, ix.seg_len,
-                                               ix.m_live, ix.row_of, ix.rep_pos, ix.cid, ix.cmask, static_cast<const U*>(a.table), static_cast<U*>(a.x),
+    dedup_embed_rows<U><<<grid, block, 0, s>>>(a.tokens, a.frame_mask, a.mask_period, a.batch, a.canvas, a.n_classes, a.d, a.seg_align, ix.cnt, ix.seg_start,
+                                               ix.seg_len, ix.m_live, ix.row_of, ix.rep_pos, ix.cid, ix.cmask, static_cast<const U*>(a.table), static_cast<U*>(a.x),
                                                a.stats, a.quads, static_cast<const U*>(a.qkv_table), static_cast<U*>(a.q0),
                                                static_cast<U*>(a.zero[0]), static_cast<U*>(a.zero[1]));
   };

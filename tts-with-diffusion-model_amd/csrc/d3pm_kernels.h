@@ -86,7 +86,8 @@ struct AttnArgs {
   // 16 x 16 x 32 kernel it has always had (the stock NAR stage, d3pm_op_attention_keylen).
   bool masked_keeps_schedule = false;
   // optional query segments (device int32 [B] each; row deduplication, attn32p_hd64 and attn32_cross_hd64 only): the queries and the
-  // output rows of utterance b are the seg_len[b] rows (a multiple of 128, <= Tq) from row seg_start[b] of Q / O; keys stay [B][S]
+  // output rows of utterance b are the seg_len[b] rows (any count in 1 .. Tq) from row seg_start[b] (any row) of Q / O: a query behind
+  // its segment reads the segment's last row and stores nothing; keys stay [B][S]
   const int32_t* seg_start = nullptr; const int32_t* seg_len = nullptr;
   // optional key gather (device int32 [B][S]; attn32p_hd64 with query segments only): key j of utterance b is row key_row[b * S + j]
   // of K / V, which are then [kv_rows][ldkv] with no per-utterance base; the kernel clamps the index into [0, kv_rows - 1];
@@ -216,9 +217,9 @@ int posterior_sample_guided(const SampleArgs& a, hipStream_t s);
 // projection and every attention query runs on the compact rows, only the keys and the sampler stay per canvas position.
 struct DedupIndex {      // all device memory, [n = batch * canvas] unless noted; carved from the workspace (d3pm_api.hip)
   int32_t* cnt = nullptr;         // [batch] distinct classes of an utterance
-  int32_t* seg_start = nullptr;   // [batch] first compact row of an utterance
-  int32_t* seg_len = nullptr;     // [batch] cnt rounded up to 128 (one self-attention workgroup)
-  int32_t* m_live = nullptr;      // [1] sum of seg_len
+  int32_t* seg_start = nullptr;   // [batch] first compact row of an utterance: the exclusive prefix sum of seg_len
+  int32_t* seg_len = nullptr;     // [batch] cnt rounded up to DedupArgs::seg_align (1: cnt itself, no zero row inside a segment)
+  int32_t* m_live = nullptr;      // [1] sum of seg_len (seg_align = 1: the distinct classes of the batch)
   int32_t* row_of = nullptr;      // canvas position -> compact row
   int32_t* key_cls = nullptr;     // class of a canvas position (n_classes on a padded frame) = its row of the block-0 QKV table; null: not written
   int32_t* rep_pos = nullptr;     // [batch][canvas]: position of the k-th representative (first occurrences in position order)
@@ -229,6 +230,9 @@ struct DedupArgs {
   const int32_t* tokens = nullptr; const uint8_t* frame_mask = nullptr; int mask_period = 0;
   int batch = 0, canvas = 0, n_classes = 0, d = 0;
   DedupIndex ix;
+  // rows of a segment: 1 = the count itself (dense, the loop's: every kernel that reads segments takes any length at any row), or 128 =
+  // whole 128-query self-attention workgroups (the layout d3pm_op_dedup_index has always written)
+  int seg_align = 128;
   // the compact embedding (all or none): table [n_classes][d]; x [n][d] + moments; block-0 q rows of the compact rows (q0 [n][d]) from
   // qkv_table [.][3d] (its k | v rows are read in place, through ix.key_cls); zero [2] = buffers [n][d] whose rows m_live .. the next
   // multiple of 384 are cleared (attention outputs: no attention workgroup writes them, the out-projections' last tile reads them)

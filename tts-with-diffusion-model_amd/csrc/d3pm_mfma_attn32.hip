@@ -278,7 +278,9 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
 // but one (first block of the last tile) and in the first block of the last tile (its second block), the latter two peeled out of
 // the loop.  A block of the last tile that lies wholly behind key_len[b] is walked with every score -inf: probabilities 0.
 // SEG (row deduplication, AttnArgs::seg_start / seg_len): the queries and output rows of utterance b are the seg_len[b] rows from
-// row seg_start[b]; a workgroup whose 128 queries lie behind them leaves in front of its first barrier.  Keys as without it.
+// row seg_start[b], any length at any row; a workgroup whose 128 queries lie behind them leaves in front of its first barrier.  In the
+// workgroup that overhangs the segment a query behind it reads the segment's last row and stores nothing (store_rows32's predicate);
+// a wave whose 32 queries all lie behind it still stages its share of every tile and takes every barrier.  Keys as without it.
 // GATHER (with SEG only; AttnArgs::key_row / kv_rows): key j of utterance b is row key_row[b * S + j] of Kp / Vp (row stride ldkv, no
 // per-utterance base), clamped into [0, kv_rows - 1] -- the compact QKV rows of the deduplicated loop read where the projection left
 // them, or the block-0 QKV table read through the class of a position.  The workgroup stages the utterance's S indices into LDS once,
@@ -327,7 +329,9 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
   const float qscale = scale * 1.4426950408889634f;
   uint4 qf[4];
   {
-    const T* qp = Q + (qbase + q0 + qn) * ldq + h * HD + hh * 8;
+    int qrow = q0 + qn;
+    if constexpr (SEG) qrow = min(qrow, seg_len[b] - 1);      // a query behind the segment reads the segment's last row, never behind the pool
+    const T* qp = Q + (qbase + qrow) * ldq + h * HD + hh * 8;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       typedef T tvec8 __attribute__((ext_vector_type(8)));
@@ -597,7 +601,12 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
   float la, lc;
   halves((ls[0] + ls[1]) + (ls[2] + ls[3]), la, lc);
   const float inv = 1.0f / (la + lc);
-  store_rows32<T>(O + (qbase + q0 + qn) * ldo + h * HD, acc_o, inv, hh, true);
+  if constexpr (SEG) {      // seg_len[b] read again here (a scalar): nothing about the segment stays in a vector register across the walk
+    const int live_rows = seg_len[b];
+    store_rows32<T>(O + (qbase + min(q0 + qn, live_rows - 1)) * ldo + h * HD, acc_o, inv, hh, q0 + qn < live_rows);
+  } else {
+    store_rows32<T>(O + (qbase + q0 + qn) * ldo + h * HD, acc_o, inv, hh, true);
+  }
 }
 
 // ---- the cross-attention pair of a block on the same instruction: attn32_cross_hd64 ------------------------------------------

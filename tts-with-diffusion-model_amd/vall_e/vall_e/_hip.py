@@ -254,6 +254,7 @@ SIGNATURES = {
     "d3pm_op_linear_fold": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Tuning), C.c_void_p]),
     "d3pm_op_dedup_index": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11),
+    "d3pm_op_dedup_index_align": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11),
     "d3pm_op_linear_live": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.POINTER(Tuning), C.c_void_p]),
@@ -1133,7 +1134,7 @@ def op_attention(q, k, v, n_heads, scale, *, family=0, key_len=None):
 
 def op_attention_gather(q, k, v, key_row, seg_start, seg_len, n_heads, scale, out, *, key_len=None):
     """The self-attention of the deduplicated loop (d3pm_op_attention_gather): q / out [rows, d], where utterance b owns the seg_len[b]
-    rows (a multiple of 128) from row seg_start[b]; k / v [kv_rows, d], views of one packed pool that share a row stride; key j of
+    rows (any count from 1 up to the capacity) from row seg_start[b] (any row); k / v [kv_rows, d], views of one packed pool that share a row stride; key j of
     utterance b is row key_row[b, j] of them (int32 [B, S], clamped into the pool by the kernel).  Writes `out` in place (rows no segment
     owns keep what they hold) and returns it.  The query capacity per utterance handed to the launch is rows rounded down to 128."""
     rows, d = q.shape
@@ -1193,7 +1194,7 @@ def _require_int32(pairs, dev):
 def op_attention_pair_segments(q1, k1, v1, q2, k2, v2, seg_start, seg_len, n_heads, scale, out1, out2, capacity, *, key_len=None,
                                key_len2=None):
     """The cross pair of the deduplicated loop (d3pm_op_attention_pair_segments): q1 / q2 / out1 / out2 [rows, d], where utterance b owns
-    the seg_len[b] rows (a multiple of 128, at most `capacity`) from row seg_start[b]; k1 / v1 [B, S1, d], k2 / v2 [B, S2, d] as in
+    the seg_len[b] rows (any count from 1 up to `capacity`) from row seg_start[b] (any row); k1 / v1 [B, S1, d], k2 / v2 [B, S2, d] as in
     op_attention_pair; key_len / key_len2 int32 [B] or None.  Writes out1 / out2 in place (rows no segment owns keep what they hold)
     and returns them.  The kernel is the planner's choice under the current tuning; a plan that takes no segments raises D3PMError."""
     if q1.dim() != 2 or k1.dim() != 3 or k2.dim() != 3:
@@ -1279,10 +1280,12 @@ def op_linear_stats(x, w, bias, r1, *, r2=None, row_mask=None, mask_period=1):
     return y, st
 
 
-def op_dedup_index(tokens, frame_mask, n_classes, table=None):
-    """Row deduplication index of tokens / frame_mask [batch, canvas] (d3pm_op_dedup_index): dict of seg_start, seg_len [batch], m_live [1],
+def op_dedup_index(tokens, frame_mask, n_classes, table=None, seg_align=128):
+    """Row deduplication index of tokens / frame_mask [batch, canvas] (d3pm_op_dedup_index_align): dict of seg_start, seg_len [batch], m_live [1],
     row_of, cid [batch * canvas] (int32), cmask [batch * canvas] (uint8) and, with `table` [n_classes, d], x [batch * canvas, d] and its
-    moments `stats` (fp32, the library's layout).  Rows the index does not define keep the sentinels they are created with here."""
+    moments `stats` (fp32, the library's layout).  Rows the index does not define keep the sentinels they are created with here.
+    seg_align: 128 = an utterance owns its class count rounded up to 128 rows (d3pm_op_dedup_index); 1 = the count itself, the dense
+    segments the sampler loop runs on; anything else is refused by the library."""
     batch, canvas = tokens.shape
     n, dev = batch * canvas, tokens.device
     i32 = lambda k, fill: torch.full((k,), fill, dtype=torch.int32, device=dev)      # noqa: E731
@@ -1294,9 +1297,10 @@ def op_dedup_index(tokens, frame_mask, n_classes, table=None):
         d = table.shape[1]
         out["x"] = torch.full((n, d), 3.0, dtype=table.dtype, device=dev)
         out["stats"] = torch.full((((n + 15) // 16) * 16 * (d // 32) * 2,), 5.0, dtype=torch.float32, device=dev)
-    check(lib().d3pm_op_dedup_index(dt, _p(tokens), _p(frame_mask), batch, canvas, n_classes, d, _p(table), _p(out["seg_start"]), _p(out["seg_len"]),
-                                    _p(out["m_live"]), _p(out["row_of"]), _p(out["cid"]), _p(out["cmask"]), _p(out.get("x")), _p(out.get("stats")),
-                                    _p(scratch), stream_ptr()), "d3pm_op_dedup_index")
+    check(lib().d3pm_op_dedup_index_align(dt, _p(tokens), _p(frame_mask), batch, canvas, n_classes, d, int(seg_align), _p(table),
+                                          _p(out["seg_start"]), _p(out["seg_len"]), _p(out["m_live"]), _p(out["row_of"]), _p(out["cid"]),
+                                          _p(out["cmask"]), _p(out.get("x")), _p(out.get("stats")), _p(scratch), stream_ptr()),
+          "d3pm_op_dedup_index_align")
     return out
 
 
