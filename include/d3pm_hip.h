@@ -65,7 +65,8 @@ extern "C" {
  *    utterance in the unguided loops (d3pm_op_dedup_index, d3pm_op_linear_live; ln_fold value 3 = every row); its self-attention
  *    with the keys read through a row index (d3pm_op_attention_gather); the segment granularity of that index
  *    (d3pm_op_dedup_index_align: 1 = dense segments, what the loop runs; d3pm_op_attention_gather and
- *    d3pm_op_attention_pair_segments take a segment of any length at any row) */
+ *    d3pm_op_attention_pair_segments take a segment of any length at any row); key-padding masks in the training step
+ *    (d3pm_op_attention_bwd_keylen_f32, d3pm_op_attention_dropout_keylen_f32) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -939,7 +940,21 @@ int d3pm_prof_destroy(struct d3pm_prof *prof);
  *                         ldy = ldx).  The backward pass of a site is the same call on the gradient.
  * d3pm_op_attention_dropout_f32  d3pm_op_attention (generic family, fp32) with every normalised probability multiplied by
  *                         z(h, i, j) before P V; utterance b draws with utt = utt0 + b
- * d3pm_op_attention_bwd_dropout_f32  d3pm_op_attention_bwd_f32 of that forward (O = (P o Z) V); Tq, S <= 4096 */
+ * d3pm_op_attention_bwd_dropout_f32  d3pm_op_attention_bwd_f32 of that forward (O = (P o Z) V); Tq, S <= 4096
+ *
+ * Key-padding masks in the training step (forward_backward(mask_padding=True)).  key_len is a device int32 [B] with
+ * 1 <= key_len[b] <= S, the caller's contract as in d3pm_op_attention_keylen (the values are read by the kernels only), or NULL =
+ * unmasked.  S stays the padded key count: the row count of the K / V / dK / dV batches and the S of the mask index (h Tq + i) S + j,
+ * so masking changes no draw of any other key.
+ * d3pm_op_attention_dropout_keylen_f32  d3pm_op_attention_dropout_f32 with the mask: a key j >= key_len[b] is outside the softmax
+ *                         (probability exactly 0), no factor is drawn for it and its K / V rows are not read; every query row is
+ *                         written.  p = 0 is d3pm_op_attention_keylen on the generic fp32 family.
+ * d3pm_op_attention_bwd_keylen_f32  the backward pass of d3pm_op_attention_keylen (generic family, fp32; p = 0, nothing drawn) or of
+ *                         d3pm_op_attention_dropout_keylen_f32 (p > 0; Tq, S <= 4096 and the 32-bit mask index as above).  A masked
+ *                         key reads nothing -- not its K / V rows, not Q / dO / stats, no dropout factor -- and its rows of dK / dV
+ *                         receive exactly 0 (beta_kv = 0) or beta_kv * old, as the live rows' old contents are scaled; dQ and
+ *                         stats are written for every query row from the live keys alone.  key_len = NULL with p = 0 runs the
+ *                         kernels of d3pm_op_attention_bwd_f32, with p > 0 those of d3pm_op_attention_bwd_dropout_f32. */
 /* The condition-side embeddings as a single op (ar_discrete.py:736-741): which = 0 text rows W[tok] + pe0 (`tables` [n_classes][d],
  * `pe` [d]); which = 1 prompt rows sum_l W[l][tok_l] + pe[s] (`tokens` [rows][n_levels], -1 = level absent; `tables`
  * [n_levels][n_classes][d]; `pe` [s_prompt][d]).  Used by the training step, which needs the encoder inputs it stashes. */
@@ -969,6 +984,13 @@ int d3pm_op_attention_bwd_dropout_f32(const float *Q, int ldq, const float *K, c
                                       float *dQ, int lddq, float *dK, float *dV, int lddkv, float *stats, int B, int Tq, int S, int H,
                                       int hd, float scale, float beta_kv, float p, uint64_t seed, uint32_t utt0, uint32_t site,
                                       void *stream);
+int d3pm_op_attention_dropout_keylen_f32(const float *Q, int ldq, const float *K, const float *V, int ldkv, float *O, int ldo, int B,
+                                         int Tq, int S, int H, int hd, float scale, const int32_t *key_len, float p, uint64_t seed,
+                                         uint32_t utt0, uint32_t site, void *stream);
+int d3pm_op_attention_bwd_keylen_f32(const float *Q, int ldq, const float *K, const float *V, int ldkv, const float *dO, int ldo,
+                                     float *dQ, int lddq, float *dK, float *dV, int lddkv, float *stats, int B, int Tq, int S, int H,
+                                     int hd, float scale, float beta_kv, const int32_t *key_len, float p, uint64_t seed,
+                                     uint32_t utt0, uint32_t site, void *stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

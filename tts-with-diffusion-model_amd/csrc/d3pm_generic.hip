@@ -228,7 +228,8 @@ __global__ __launch_bounds__(256) void attention_rows(const T* __restrict__ Q, i
       sum = wave_sum(sum);
       for (int j = lane; j < S; j += kWave) sc[j] = rn<T>(sc[j] / sum);
       if constexpr (DROP) {
-        const uint32_t row = (static_cast<uint32_t>(h) * Tq + i) * static_cast<uint32_t>(S), utt = dr.utt0 + b;
+        // the mask index keeps the padded extent: masking a key changes no other key's draw, and none is drawn for it
+        const uint32_t row = (static_cast<uint32_t>(h) * Tq + i) * static_cast<uint32_t>(S_pad), utt = dr.utt0 + b;
         for (int j = lane; j < S; j += kWave) sc[j] *= dropout_z(dr.seed, utt, dr.site, row + j, dr.p, dr.s);
       }
     }
@@ -399,7 +400,7 @@ int generic_attention_dropout_f32(const AttnArgs& a, const DropoutArgs& dr, hipS
   size_t lds = static_cast<size_t>(nw) * (a.S + a.hd) * sizeof(float);
   attention_rows<float, true><<<grid, nw * kWave, lds, s>>>(static_cast<const float*>(a.Q), a.ldq, static_cast<const float*>(a.K),
                                                             static_cast<const float*>(a.V), a.ldkv, static_cast<float*>(a.O), a.ldo,
-                                                            a.Tq, a.S, a.hd, a.scale, qpw, nullptr, dr);
+                                                            a.Tq, a.S, a.hd, a.scale, qpw, a.key_len, dr);
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

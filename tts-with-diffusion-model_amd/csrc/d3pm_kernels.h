@@ -177,7 +177,9 @@ struct DropoutArgs {
   uint64_t seed = 0;
   uint32_t utt0 = 0, site = 0;
 };
-// the fp32 generic attention with sc = rn(e / sum) * z(h, i, j) before P.V (training step; key_len / Q2 unsupported)
+// the fp32 generic attention with sc = rn(e / sum) * z(h, i, j) before P.V (training step; Q2 unsupported).  a.key_len as in
+// generic_attention: a masked key is outside the softmax, draws no factor and its K / V rows are not read; z keeps its index
+// (h Tq + i) S + j with the padded S
 int generic_attention_dropout_f32(const AttnArgs& a, const DropoutArgs& dr, hipStream_t s);
 int generic_layernorm(int dtype, const LayerNormArgs& a, hipStream_t s);
 int embed_tokens(int dtype, const EmbedArgs& a, hipStream_t s);

@@ -219,21 +219,27 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows(const float* __restric
 // DROP (O = (P o Z) V, Z the probability-dropout factors of the forward, d3pm_common.h dropout_z): D = sum_j P_j Z_j (dO . v_j),
 // dQ = scale * sum_j P_j (Z_j (dO . v_j) - D) k_j.  The mask is drawn once per (query, key) into a bit set -- bit n of a lane is
 // key lane + 64 n, S <= 4096 -- so the column loop below only reads bits.  DROP = false is the kernel as it always was.
-template <bool DROP = false>
+// KEYS (key_len device int32 [B]): the keys of utterance b are its first S_b = min(key_len[b], S) rows -- every key loop stops there,
+// so a masked key is outside the softmax and the sums, its K / V rows are not read and no dropout factor is drawn for it; S stays
+// the row count of the K / V batches and of the mask index (h Tq + i) S + j.  S_b is the same in every lane of a wave (a wave is one
+// (b, h, i)), so each wave_max / wave_sum still runs with all 64 lanes.  KEYS = false is the kernel as it always was.
+template <bool DROP = false, bool KEYS = false>
 __global__ __launch_bounds__(256) void attn_bwd_q_rows(const float* __restrict__ Q, int ldq, const float* __restrict__ Kp,
                                                        const float* __restrict__ Vp, int ldkv, const float* __restrict__ dO, int ldo,
                                                        float* __restrict__ dQ, int lddq, float* __restrict__ stats, int B, int Tq,
-                                                       int S, int H, int hd, float scale, DropoutArgs dr = DropoutArgs{}) {
+                                                       int S, int H, int hd, float scale, DropoutArgs dr = DropoutArgs{},
+                                                       const int32_t* __restrict__ key_len = nullptr) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const long idx = static_cast<long>(blockIdx.x) * 4 + wave;
   if (idx >= static_cast<long>(B) * H * Tq) return;
   const int i = static_cast<int>(idx % Tq), h = static_cast<int>((idx / Tq) % H), b = static_cast<int>(idx / (static_cast<long>(Tq) * H));
+  const int Sb = KEYS ? min(key_len[b], S) : S;      // the keys of this utterance (wave-uniform)
   const float* q = Q + (static_cast<size_t>(b) * Tq + i) * ldq + h * hd;
   const float* go = dO + (static_cast<size_t>(b) * Tq + i) * ldo + h * hd;
   const float* kb = Kp + static_cast<size_t>(b) * S * ldkv + h * hd;
   const float* vb = Vp + static_cast<size_t>(b) * S * ldkv + h * hd;
   float mx = -INFINITY;
-  for (int j = lane; j < S; j += kWave) {
+  for (int j = lane; j < Sb; j += kWave) {
     float sc = 0.f;
     for (int c = 0; c < hd; ++c) sc = fmaf(q[c] * scale, kb[static_cast<size_t>(j) * ldkv + c], sc);
     mx = fmaxf(mx, sc);
@@ -241,7 +247,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_rows(const float* __restrict__
   mx = wave_max(mx);
   uint64_t keep = 0;
   float l = 0.f, dsum = 0.f;
-  for (int j = lane; j < S; j += kWave) {
+  for (int j = lane; j < Sb; j += kWave) {
     float sc = 0.f, dp = 0.f;
     for (int c = 0; c < hd; ++c) {
       sc = fmaf(q[c] * scale, kb[static_cast<size_t>(j) * ldkv + c], sc);
@@ -262,7 +268,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_rows(const float* __restrict__
   float* dq = dQ + (static_cast<size_t>(b) * Tq + i) * lddq + h * hd;
   for (int c0 = 0; c0 < hd; ++c0) {
     float part = 0.f;
-    for (int j = lane; j < S; j += kWave) {
+    for (int j = lane; j < Sb; j += kWave) {
       float sc = 0.f, dp = 0.f;
       for (int c = 0; c < hd; ++c) {
         sc = fmaf(q[c] * scale, kb[static_cast<size_t>(j) * ldkv + c], sc);
@@ -280,12 +286,15 @@ __global__ __launch_bounds__(256) void attn_bwd_q_rows(const float* __restrict__
 // pass 2: one wave per (utterance, head, key):  dV_j = sum_i P_ij dO_i,  dK_j = scale * sum_i P_ij ((dO_i . v_j) - D_i) q_i
 // DROP: dV_j = sum_i P_ij Z_ij dO_i,  dK_j = scale * sum_i P_ij (Z_ij (dO_i . v_j) - D_i) q_i  (bit n of a lane: query lane + 64 n,
 // Tq <= 4096)
-template <bool DROP = false>
+// KEYS: the wave of a masked key (j >= key_len[b]) recomputes nothing and reads neither its K / V row nor Q / dO / stats; it leaves
+// dK_j = dV_j = 0 (beta = 0) or beta * old, scaled like every other row of an accumulating call, and returns (no barrier in this kernel).
+template <bool DROP = false, bool KEYS = false>
 __global__ __launch_bounds__(256) void attn_bwd_kv_rows(const float* __restrict__ Q, int ldq, const float* __restrict__ Kp,
                                                         const float* __restrict__ Vp, int ldkv, const float* __restrict__ dO, int ldo,
                                                         float* __restrict__ dK, float* __restrict__ dV, int lddkv,
                                                         const float* __restrict__ stats, int B, int Tq, int S, int H, int hd,
-                                                        float scale, float beta, DropoutArgs dr = DropoutArgs{}) {
+                                                        float scale, float beta, DropoutArgs dr = DropoutArgs{},
+                                                        const int32_t* __restrict__ key_len = nullptr) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const long idx = static_cast<long>(blockIdx.x) * 4 + wave;
   if (idx >= static_cast<long>(B) * H * S) return;
@@ -297,6 +306,15 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_rows(const float* __restrict_
   const float* st = stats + (static_cast<size_t>(b) * H + h) * Tq * 2;
   float* dk = dK + (static_cast<size_t>(b) * S + j) * lddkv + h * hd;
   float* dv = dV + (static_cast<size_t>(b) * S + j) * lddkv + h * hd;
+  if constexpr (KEYS)
+    if (j >= key_len[b]) {      // wave-uniform: a wave is one (b, h, j)
+      if (lane == 0)
+        for (int c = 0; c < hd; ++c) {
+          dk[c] = beta == 0.f ? 0.f : fmaf(beta, dk[c], 0.f);
+          dv[c] = beta == 0.f ? 0.f : fmaf(beta, dv[c], 0.f);
+        }
+      return;
+    }
   uint64_t keep = 0;
   if constexpr (DROP)
     for (int i = lane; i < Tq; i += kWave)
@@ -549,6 +567,56 @@ int d3pm_op_attention_bwd_dropout_f32(const float* Q, int ldq, const float* K, c
                                                                              scale, dr);
   attn_bwd_kv_rows<true><<<static_cast<unsigned>((nk + 3) / 4), 256, 0, s>>>(Q, ldq, K, V, ldkv, dO, ldo, dK, dV, lddkv, stats, B, Tq, S,
                                                                               H, hd, scale, beta_kv, dr);
+  D3PM_LAUNCH_CHECK();
+  return D3PM_OK;
+}
+
+int d3pm_op_attention_dropout_keylen_f32(const float* Q, int ldq, const float* K, const float* V, int ldkv, float* O, int ldo, int B, int Tq,
+                                         int S, int H, int hd, float scale, const int32_t* key_len, float p, uint64_t seed, uint32_t utt0,
+                                         uint32_t site, void* stream) {
+  D3PM_REQUIRE(Q && K && V && O && B > 0 && Tq > 0 && S > 0 && H > 0 && hd > 0, D3PM_E_ARG,
+               "d3pm_op_attention_dropout_keylen_f32: bad arguments");
+  D3PM_REQUIRE(static_cast<uint64_t>(H) * Tq * S <= kMaxIdx, D3PM_E_SHAPE,
+               "d3pm_op_attention_dropout_keylen_f32: %d x %d x %d probabilities exceed the 32-bit mask index", H, Tq, S);
+  DropoutArgs dr;
+  if (int rc = dropout_args(p, seed, utt0, site, dr)) return rc;
+  AttnArgs a;
+  a.Q = Q; a.ldq = ldq; a.K = K; a.V = V; a.ldkv = ldkv; a.O = O; a.ldo = ldo; a.B = B; a.Tq = Tq; a.S = S; a.H = H;
+  a.hd = hd; a.scale = scale; a.key_len = key_len;
+  if (p == 0.f) return generic_attention(D3PM_F32, a, static_cast<hipStream_t>(stream));      // nothing drawn
+  return generic_attention_dropout_f32(a, dr, static_cast<hipStream_t>(stream));
+}
+
+int d3pm_op_attention_bwd_keylen_f32(const float* Q, int ldq, const float* K, const float* V, int ldkv, const float* dO, int ldo, float* dQ,
+                                     int lddq, float* dK, float* dV, int lddkv, float* stats, int B, int Tq, int S, int H, int hd,
+                                     float scale, float beta_kv, const int32_t* key_len, float p, uint64_t seed, uint32_t utt0,
+                                     uint32_t site, void* stream) {
+  D3PM_REQUIRE(Q && K && V && dO && dQ && dK && dV && stats && B > 0 && Tq > 0 && S > 0 && H > 0 && hd > 0, D3PM_E_ARG,
+               "d3pm_op_attention_bwd_keylen_f32: bad arguments");
+  DropoutArgs dr;
+  if (int rc = dropout_args(p, seed, utt0, site, dr)) return rc;
+  const bool drop = p > 0.f;      // p == 0: the arm without dropout, nothing drawn
+  if (drop) {
+    D3PM_REQUIRE(static_cast<uint64_t>(H) * Tq * S <= kMaxIdx, D3PM_E_SHAPE,
+                 "d3pm_op_attention_bwd_keylen_f32: %d x %d x %d probabilities exceed the 32-bit mask index", H, Tq, S);
+    D3PM_REQUIRE(Tq <= 64 * kWave && S <= 64 * kWave, D3PM_E_SHAPE,
+                 "d3pm_op_attention_bwd_keylen_f32: the per-lane mask bits hold at most 4096 queries and keys (got %d, %d)", Tq, S);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long nq = static_cast<long>(B) * H * Tq, nk = static_cast<long>(B) * H * S;
+  const unsigned gq = static_cast<unsigned>((nq + 3) / 4), gk = static_cast<unsigned>((nk + 3) / 4);
+#define D3PM_BWD_ARM(DROP, KEYS)                                                                                                         \
+  do {                                                                                                                                    \
+    attn_bwd_q_rows<DROP, KEYS><<<gq, 256, 0, s>>>(Q, ldq, K, V, ldkv, dO, ldo, dQ, lddq, stats, B, Tq, S, H, hd, scale, dr, key_len);    \
+    attn_bwd_kv_rows<DROP, KEYS><<<gk, 256, 0, s>>>(Q, ldq, K, V, ldkv, dO, ldo, dK, dV, lddkv, stats, B, Tq, S, H, hd, scale, beta_kv,  \
+                                                    dr, key_len);                                                                        \
+  } while (0)
+  if (key_len) {
+    if (drop) D3PM_BWD_ARM(true, true); else D3PM_BWD_ARM(false, true);
+  } else {
+    if (drop) D3PM_BWD_ARM(true, false); else D3PM_BWD_ARM(false, false);
+  }
+#undef D3PM_BWD_ARM
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

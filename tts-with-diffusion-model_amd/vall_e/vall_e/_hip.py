@@ -407,6 +407,13 @@ SIGNATURES = {
                                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                     C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_uint32,
                                                     C.c_uint32, C.c_void_p]),
+    "d3pm_op_attention_dropout_keylen_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_float, C.c_uint64,
+                                                       C.c_uint32, C.c_uint32, C.c_void_p]),
+    "d3pm_op_attention_bwd_keylen_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                   C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_uint64,
+                                                   C.c_uint32, C.c_uint32, C.c_void_p]),
     "d3pm_tuning_default": (None, [C.POINTER(Tuning)]),
     "d3pm_prof_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "d3pm_prof_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -973,9 +980,10 @@ class Sampler:
                                       _p(frame_mask), _p(out), stream_ptr()), "d3pm_ce_loss_rows")
         return out
 
-    def training_forward(self, x0, frame_mask, kv_t, kv_p, seed, utt0=0, timesteps=None):
+    def training_forward(self, x0, frame_mask, kv_t, kv_p, seed, utt0=0, timesteps=None, keys=None):
         """The training-side forward of AR.forward (ar_discrete.py:655-693) for utterances that share one frame mask:
         sum over t = 1 .. timesteps-1 of mean_rows CE(denoiser(q_sample(x0, t)), x0 * mask), divided by mask.sum().
+        keys: None or the (frames, text, prompt) key counts of make_keys -- every evaluation then runs through d3pm_denoise_step_keys.
         Returns (loss fp32 [B], logits of the last step [B, canvas, K] with padded frames zeroed)."""
         T = self.schedule.timesteps if timesteps is None else int(timesteps)
         fm = frame_mask.to(torch.uint8)
@@ -985,7 +993,10 @@ class Sampler:
         logits = None
         for t in range(1, T):
             x_t = self.q_sample(x0, fm, t, seed, utt0)
-            logits, _ = self.denoise(x_t, fm, t, kv_t, kv_p)
+            if keys is None:
+                logits, _ = self.denoise(x_t, fm, t, kv_t, kv_p)
+            else:
+                logits, _ = self.denoise_canvas(x_t, fm, t, kv_t, kv_p, keys=keys)
             total += self.ce_loss_rows(logits, targets, fm).mean(dim=1)
         if logits is not None:
             logits = logits * live[None, :, None].to(logits.dtype)

@@ -429,8 +429,9 @@ class AR(SymmapState, nn.Module):
         ones, so the last bits, and with them an occasional id, can still differ between two paddings).  It composes with
         n_frames sequences, known / known_mask, temperature / top_k / top_p, reveal_steps, greedy, utt0 / global_batch, streams,
         return_trace and n_q > 1; an empty text or prompt, graph=True and fp8=True raise ValueError before any GPU work.  The
-        synthetic and the upstream weights were trained with the padding as keys and the training step (forward, forward_backward)
-        does not take the mask: no statement about audio quality is made for it.
+        synthetic and the upstream weights were trained with the padding as keys: no statement about audio quality is made for it.
+        Weights for this mode come from the training step with the same mask, forward_backward(mask_padding=True) (forward takes
+        it too, for the evaluation-only loss).
         `guidance=w` (finite, >= 0; 0 = the loop above, untouched) is classifier-free guidance (include/d3pm_hip.h: d3pm_guidance):
         every reverse step evaluates the denoiser for 2B utterances in one evaluation -- each utterance and its null twin, which has
         the same canvas but no phonemes and no prompt frames (the empty text and prompt, zero padded like any other) -- and the
@@ -585,7 +586,7 @@ class AR(SymmapState, nn.Module):
         return smp.q_sample(x_start.to(torch.int32).contiguous(), fm, int(t.reshape(-1)[0]), seed, utt0).long()
 
     def forward_backward(self, text_list, proms_list, resps_list, *, seed: Optional[int] = None, timesteps: Optional[int] = None,
-                         dropout=False, utt0: int = 0, cond_drop=0.0):
+                         dropout=False, utt0: int = 0, cond_drop=0.0, mask_padding: bool = False):
         """The training step's compute (reference: `engine.backward(engine(...))`, utils/engines.py:144-147 over
         ar_discrete.py:588-694): the loss of `forward` AND its gradient for every parameter the forward reads, accumulated
         into `param.grad` by the HIP backward kernels (vall_e/vall_e/train.py; fp32 model).  Follow it with
@@ -597,25 +598,38 @@ class AR(SymmapState, nn.Module):
         data-parallel rank passes its shard offset), which keys the q_sample noise and the masks.
         cond_drop: p or (p_text, p_prompt) -- the probability with which an utterance's text / prompt is replaced by the empty one
         for this step (the null condition of generate_audio(guidance=...): what classifier-free guidance needs the weights to
-        have seen); decided per utterance from (seed, utt0 + b) on Philox stream 5; 0 (default) is the step without it."""
+        have seen); decided per utterance from (seed, utt0 + b) on Philox stream 5; 0 (default) is the step without it.
+        mask_padding=True trains the model generate_audio(mask_padding=True) evaluates: an utterance's padding is no key of any
+        attention -- the DiT self-attention keeps its first min(len(resps_b), canvas) frames, the text / prompt cross-attention
+        and the two encoders its min(len(text_b), s_text) phonemes / min(rows(prom_b), s_prompt) prompt frames; a condition that
+        cond_drop replaced keeps all of its padding, as the default null twin of guidance does.  Masked keys get probability 0
+        and gradient 0, padded rows stay queries; loss and gradients are those of the model at the truncated shape, scaled as
+        DESIGN.md "Key masks in the training step" states.  It composes with dropout (no draw changes), cond_drop and utt0; an
+        empty text or prompt, or a mask_padding that is not a bool, is a ValueError before any GPU work.  False (default) is the
+        step without it, launch for launch."""
         from .train import D3PMTrainer
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         loss, _ = D3PMTrainer(self).forward_backward(text_list, proms_list, resps_list, seed=seed, timesteps=timesteps, dropout=dropout,
-                                                     utt0=utt0, cond_drop=cond_drop)
+                                                     utt0=utt0, cond_drop=cond_drop, mask_padding=mask_padding)
         return loss
 
     @torch.no_grad()
-    def forward(self, text_list, proms_list, resps_list=None, spkr_name=None, *, seed: Optional[int] = None):
+    def forward(self, text_list, proms_list, resps_list=None, spkr_name=None, *, seed: Optional[int] = None, mask_padding: bool = False):
         """Training-side forward, evaluation only (forward half; ar_discrete.py:588-694): for every
         utterance, x_0 = the target codes zero-padded / truncated to the canvas, mask = (x_0 != 0), and
             loss = sum_{t=1}^{timesteps-1} mean_canvas CE(final(blocks(q_sample(x_0, t))) * mask, x_0 * mask) / mask.sum().
         Sets `self.loss` (mean over the utterances; upstream indexes `[0]` throughout, so for one utterance this is its
         value) and returns the masked logits of the last step of the last utterance, `[canvas, n_classes]`, as upstream.
         q_sample draws Philox stream 1 keyed by `seed` instead of torch.rand.  No autograd graph is built: gradients come from
-        `forward_backward` (hand-written backward kernels), not from torch.autograd."""
+        `forward_backward` (hand-written backward kernels), not from torch.autograd.
+        mask_padding=True evaluates the loss forward_backward(mask_padding=True) trains (in every dtype forward runs in): the keys
+        of every attention are the utterance's own frames, phonemes and prompt frames (train.key_mask_lengths; d3pm_keys), padded
+        rows stay queries and the returned logits keep their shape.  An empty text or prompt is a ValueError before any GPU work."""
         if resps_list is None or not (len(text_list) == len(proms_list) == len(resps_list)) or len(text_list) == 0:
             raise ValueError("text_list, proms_list and resps_list must be non-empty and of equal length")
+        from .train import key_mask_lengths
+        key_lens = key_mask_lengths(self.cfg, text_list, proms_list, resps_list, mask_padding=mask_padding)      # host validation first
         smp = self.sampler()
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -625,9 +639,12 @@ class AR(SymmapState, nn.Module):
                 r = resps.reshape(-1).to(self.device).long()[: self.cfg.canvas]
                 x0 = F.pad(r, (0, self.cfg.canvas - r.shape[0])).to(torch.int32)[None].contiguous()
                 frame_mask = (x0[0] != 0).to(torch.uint8)
-                cond_text, cond_prompt = self.encode_conditions([text], [prom])
+                keys = None      # (frames, text, prompt) of this utterance, int32 [1] on the device
+                if key_lens is not None:
+                    keys = tuple(torch.tensor([v[b]], dtype=torch.int32, device=self.device) for v in key_lens)
+                cond_text, cond_prompt = self.encode_conditions([text], [prom], *(keys[1:] if keys else ()))
                 kv_t, kv_p = smp.cond_kv(cond_text, cond_prompt)
-                loss, logits = smp.training_forward(x0, frame_mask, kv_t, kv_p, seed, utt0=b, timesteps=self.timesteps)
+                loss, logits = smp.training_forward(x0, frame_mask, kv_t, kv_p, seed, utt0=b, timesteps=self.timesteps, keys=keys)
                 losses.append(loss[0])
                 last = logits[0]
         self.loss = torch.stack(losses).mean()

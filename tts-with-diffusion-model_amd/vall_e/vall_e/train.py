@@ -27,6 +27,12 @@ site) (include/d3pm_hip.h, DESIGN.md "Dropout mask stream"), drawn once per utte
 per forward, and regenerated in the backward pass rather than stored.  Upstream draws them from torch's global generator; that
 stream itself is not reproduced.  The argument is explicit on purpose: `model.training` is not consulted (a freshly built
 nn.Module is in train mode, and honouring the flag would change what every existing caller computes).
+
+Key masks: `forward_backward(mask_padding=True)` trains the model `generate_audio(mask_padding=True)` evaluates -- the keys of every
+attention of the step are the utterance's own frames, phonemes and prompt frames (`key_mask_lengths`, host arithmetic), through the
+masked forward ops and the masked backward kernels (`attn_bwd_q_rows` / `attn_bwd_kv_rows` with the KEYS arm).  A masked key has
+probability 0 and gradient 0, padded rows stay queries, and the dropout stream keeps its padded indexing; the step equals the model
+at the truncated shape (DESIGN.md "Key masks in the training step").  The default False is the step without it, launch for launch.
 """
 from __future__ import annotations
 
@@ -103,14 +109,29 @@ def layernorm_bwd(x, dout, w, b, dx, dw, db, film=None, dfilm=None, eps=1e-6, ac
                                                     _hip.stream_ptr()), "d3pm_op_layernorm_bwd_f32")
 
 
-def attention_bwd(q, k, v, do, dq, dk, dv, n_heads, scale, beta_kv=0.0, drop=None):
+def _key_len(key_len, B, device):
+    if key_len.dtype != torch.int32 or key_len.shape != (B,) or key_len.device != device or not key_len.is_contiguous():
+        raise _hip.D3PMError(f"key_len must be a contiguous int32 [{B}] tensor on {device}")
+    return key_len
+
+
+def attention_bwd(q, k, v, do, dq, dk, dv, n_heads, scale, beta_kv=0.0, drop=None, key_len=None):
     """q [B,Tq,d], k / v [B,S,d] views (row strides free), do [B,Tq,d]; dq / dk / dv views of the same shapes.  drop = (p, seed,
-    utt0, site): the backward pass of attention_dropout with those arguments."""
+    utt0, site): the backward pass of attention_dropout with those arguments.  key_len (int32 [B] on the device, 1 .. S, or None):
+    the backward pass of the masked forward (d3pm_op_attention_bwd_keylen_f32) -- keys behind key_len[b] are not read and their
+    dk / dv rows receive 0 (beta_kv * old); None launches the entries without it."""
     B, Tq, d = q.shape
     S = k.shape[1]
     hd = d // n_heads
     stats = torch.empty(B * n_heads * Tq * 2, dtype=torch.float32, device=q.device)
     assert k.stride(1) == v.stride(1) and dk.stride(1) == dv.stride(1)
+    if key_len is not None:
+        p, seed, utt0, site = (0.0, 0, 0, 0) if drop is None else drop
+        _hip.check(_hip.lib().d3pm_op_attention_bwd_keylen_f32(
+            _ptr(_f32(q, "q")), q.stride(1), _ptr(_f32(k, "k")), _ptr(_f32(v, "v")), k.stride(1), _ptr(_f32(do, "do")), do.stride(1), _ptr(dq),
+            dq.stride(1), _ptr(dk), _ptr(dv), dk.stride(1), _ptr(stats), B, Tq, S, n_heads, hd, float(scale), float(beta_kv),
+            _ptr(_key_len(key_len, B, q.device)), float(p), _seed(seed), utt0, site, _hip.stream_ptr()), "d3pm_op_attention_bwd_keylen_f32")
+        return
     if drop is not None:
         p, seed, utt0, site = drop
         _hip.check(_hip.lib().d3pm_op_attention_bwd_dropout_f32(
@@ -123,14 +144,22 @@ def attention_bwd(q, k, v, do, dq, dk, dv, n_heads, scale, beta_kv=0.0, drop=Non
                                                     float(scale), float(beta_kv), _hip.stream_ptr()), "d3pm_op_attention_bwd_f32")
 
 
-def attention_dropout(q, k, v, n_heads, scale, p, seed, utt0, site):
+def attention_dropout(q, k, v, n_heads, scale, p, seed, utt0, site, key_len=None):
     """softmax(scale q k^T) with probability dropout, times v (d3pm_op_attention_dropout_f32): q [B,Tq,d], k / v [B,S,d] views
-    (row strides free); utterance b draws its mask with utt0 + b.  -> [B,Tq,d]."""
+    (row strides free); utterance b draws its mask with utt0 + b.  key_len (int32 [B] on the device, 1 .. S, or None): keys behind
+    key_len[b] are outside the softmax and draw nothing, every other key keeps its draw (d3pm_op_attention_dropout_keylen_f32).
+    -> [B,Tq,d]."""
     B, Tq, d = q.shape
     S = k.shape[1]
     assert k.stride(1) == v.stride(1) and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
     assert q.stride(0) == Tq * q.stride(1) and k.stride(0) == S * k.stride(1) and v.stride(0) == S * v.stride(1)
     o = torch.empty((B, Tq, d), dtype=torch.float32, device=q.device)
+    if key_len is not None:
+        _hip.check(_hip.lib().d3pm_op_attention_dropout_keylen_f32(
+            _ptr(_f32(q, "q")), q.stride(1), _ptr(_f32(k, "k")), _ptr(_f32(v, "v")), k.stride(1), _ptr(o), d, B, Tq, S, n_heads,
+            d // n_heads, float(scale), _ptr(_key_len(key_len, B, q.device)), float(p), _seed(seed), utt0, site, _hip.stream_ptr()),
+            "d3pm_op_attention_dropout_keylen_f32")
+        return o
     _hip.check(_hip.lib().d3pm_op_attention_dropout_f32(_ptr(_f32(q, "q")), q.stride(1), _ptr(_f32(k, "k")), _ptr(_f32(v, "v")), k.stride(1),
                                                         _ptr(o), d, B, Tq, S, n_heads, d // n_heads, float(scale), float(p), _seed(seed),
                                                         utt0, site, _hip.stream_ptr()), "d3pm_op_attention_dropout_f32")
@@ -207,6 +236,35 @@ def cond_drop_decision(seed: int, utt: int, p_text: float, p_prompt: float, devi
     return bool(u[0] < torch.tensor(p_text, dtype=torch.float32)), bool(u[1] < torch.tensor(p_prompt, dtype=torch.float32))
 
 
+def key_mask_lengths(cfg, text_list, proms_list, resps_list, dropped=None, mask_padding=True):
+    """Host side of `mask_padding` in the training step (no GPU work): the key counts of every utterance as three lists of ints,
+    (frames, text, prompt) with frames[b] = min(len(resps_b), canvas) -- counted by length, a code 0 inside the utterance stays a
+    key --, text[b] = min(len(text_b), s_text) and prompt[b] = min(rows(prom_b), s_prompt): the numbers of _hip.key_lengths.
+    dropped (or None): per utterance the (text dropped?, prompt dropped?) pair of cond_drop_decision -- a dropped condition keeps
+    all of its padding as keys (s_text / s_prompt), the rule AR._twin_key_lengths applies to the default null twin of guidance.
+    mask_padding=False returns None.  ValueError: a mask_padding that is not a bool, lists of different lengths, an utterance
+    without a frame, a phoneme or a prompt frame (what the caller passes: validation comes before the drop)."""
+    if not isinstance(mask_padding, bool):
+        raise ValueError(f"mask_padding must be a bool, got {mask_padding!r}")
+    if not mask_padding:
+        return None
+    B = len(text_list)
+    if not (B == len(proms_list) == len(resps_list)) or (dropped is not None and len(dropped) != B):
+        raise ValueError(f"mask_padding: {B} texts, {len(proms_list)} prompts, {len(resps_list)} targets"
+                         + ("" if dropped is None else f", {len(dropped)} drop decisions"))
+
+    def rows(t):
+        return int(t.shape[0]) if t.dim() else 0
+    frames, text, prompt = _hip.key_lengths([min(int(r.numel()), cfg.canvas) for r in resps_list], [rows(t) for t in text_list],
+                                            [rows(p) for p in proms_list], cfg.canvas, cfg.s_text, cfg.s_prompt)
+    for b, (drop_text, drop_prompt) in enumerate(dropped or ()):
+        if drop_text:
+            text[b] = cfg.s_text
+        if drop_prompt:
+            prompt[b] = cfg.s_prompt
+    return frames, text, prompt
+
+
 def dropout_site(which: int, layer: int, kind: int) -> int:
     """Site number of the mask stream: which 0 text / 1 prompt encoder; layer 0 .. cond_layers - 1 with kind 0 attention
     probabilities, 1 after out_proj, 2 FFN hidden, 3 after linear2; layer MLP_LAYER with kind 0 after SiLU, 1 after fc2."""
@@ -251,10 +309,11 @@ class D3PMTrainer:
         self.model = model
 
     # ---- condition encoders (once per utterance) with a stash ------------------------------------------------
-    def _encode(self, which, tokens, drop=(0.0, 0.0, 0, 0)):
+    def _encode(self, which, tokens, drop=(0.0, 0.0, 0, 0), key_len=None):
         """which 0: text int32 [S_t]; 1: prompt int32 [S_p, n_levels] -> (cond [S, d], stash).  drop = (p_layer, p_mlp, seed,
         utt): the six dropout sites (module docstring); a site with p = 0 is the eval-mode op.  The stash keeps the dropped
-        tensors that the weight gradients read (linear2's and fc2's inputs)."""
+        tensors that the weight gradients read (linear2's and fc2's inputs).  key_len (int32 [1] on the device, or None): the rows
+        that are keys of the encoder's self-attention (mask_padding); every row stays a query."""
         p_layer, p_mlp, seed, utt = drop
         m, cfg = self.model, self.model.cfg
         d = cfg.d_model
@@ -277,11 +336,11 @@ class D3PMTrainer:
             qkv = s["qkv"].view(1, rows, 3 * d)
             q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
             if p_layer > 0:                 # t1 = x + dropout1(out_proj(attention with dropped probabilities))
-                s["att"] = attention_dropout(q, k, v, H, scale, p_layer, seed, utt, dropout_site(which, l, 0)).view(rows, d)
+                s["att"] = attention_dropout(q, k, v, H, scale, p_layer, seed, utt, dropout_site(which, l, 0), key_len=key_len).view(rows, d)
                 s["t1"] = dropout(lin(s["att"], layer.self_attn.out_proj.weight, layer.self_attn.out_proj.bias), p_layer, seed, utt,
                                   dropout_site(which, l, 1), residual=x)
             else:
-                s["att"] = _hip.op_attention(q, k, v, H, scale, family=G).view(rows, d)
+                s["att"] = _hip.op_attention(q, k, v, H, scale, family=G, key_len=key_len).view(rows, d)
                 s["t1"] = lin(s["att"], layer.self_attn.out_proj.weight, layer.self_attn.out_proj.bias, r1=x)
             s["x1"] = _hip.op_layernorm(s["t1"], layer.norm1.weight, layer.norm1.bias, eps=1e-5)
             s["ff"] = lin(s["x1"], layer.linear1.weight, layer.linear1.bias, act=RELU)
@@ -300,7 +359,7 @@ class D3PMTrainer:
         cond = lin(top["h"], mlp.fc2.weight, mlp.fc2.bias)
         if p_mlp > 0:                       # drop2 after fc2
             dropout(cond, p_mlp, seed, utt, dropout_site(which, MLP_LAYER, 1), out=cond)
-        return cond, {"which": which, "tokens": tokens, "layers": layers, "top": top, "drop": drop}
+        return cond, {"which": which, "tokens": tokens, "layers": layers, "top": top, "drop": drop, "key_len": key_len}
 
     def _encode_backward(self, stash, dcond):
         m, cfg = self.model, self.model.cfg
@@ -345,7 +404,8 @@ class D3PMTrainer:
                        _grad(layer.self_attn.out_proj.bias), datt)
             qkv, dqkv = s["qkv"].view(1, rows, 3 * d), new(1, rows, 3 * d)
             attention_bwd(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], datt.view(1, rows, d), dqkv[..., :d], dqkv[..., d:2 * d],
-                          dqkv[..., 2 * d:], H, scale, drop=(p_layer, seed, utt, dropout_site(which, l, 0)) if p_layer > 0 else None)
+                          dqkv[..., 2 * d:], H, scale, drop=(p_layer, seed, utt, dropout_site(which, l, 0)) if p_layer > 0 else None,
+                          key_len=stash["key_len"])
             dx = dt1                                             # residual branch; the in-projection adds its part
             linear_bwd(s["x"], layer.self_attn.in_proj_weight, dqkv.view(rows, 3 * d), _grad(layer.self_attn.in_proj_weight),
                        _grad(layer.self_attn.in_proj_bias), dx, dx_beta=1.0)
@@ -357,7 +417,10 @@ class D3PMTrainer:
                 embed_bwd(tokens[:, lvl].contiguous(), None, dx, gp[lvl], padding_idx=-1)
 
     # ---- one denoiser evaluation with a stash ---------------------------------------------------------------
-    def _forward(self, x_t, fm, t, kv_t, kv_p, film):
+    def _forward(self, x_t, fm, t, kv_t, kv_p, film, keys=(None, None, None)):
+        """keys: the (frames, text, prompt) key counts of mask_padding, int32 [1] on the device each (None = that attention has every
+        padded row as a key, the step without the mask)."""
+        k_frames, k_text, k_prompt = keys
         m, cfg = self.model, self.model.cfg
         d, H = cfg.d_model, cfg.n_heads
         scale = (1.0 / (d // H)) ** 0.5
@@ -370,14 +433,16 @@ class D3PMTrainer:
             s["h1"] = _hip.op_layernorm(x, blk.norm1.weight, blk.norm1.bias)
             s["qkv"] = lin(s["h1"], blk.attn.in_proj_weight, blk.attn.in_proj_bias)
             qkv = s["qkv"].view(1, -1, 3 * d)
-            s["att"] = _hip.op_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale, family=G).view(-1, d)
+            s["att"] = _hip.op_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale, family=G, key_len=k_frames).view(-1, d)
             s["x1"] = lin(s["att"], blk.attn.out_proj.weight, blk.attn.out_proj.bias, r1=x)
             s["h2"] = _hip.op_layernorm(s["x1"], blk.norm2.weight, blk.norm2.bias)
             s["h22"] = _hip.op_layernorm(s["x1"], blk.norm22.weight, blk.norm22.bias)
             wq, bq = blk.cross_attn.in_proj_weight[:d], blk.cross_attn.in_proj_bias[:d]
             s["qt"], s["qp"] = lin(s["h2"], wq, bq), lin(s["h22"], wq, bq)
-            s["at"] = _hip.op_attention(s["qt"].view(1, -1, d), kv_t[l][..., :d], kv_t[l][..., d:], H, scale, family=G).view(-1, d)
-            s["ap"] = _hip.op_attention(s["qp"].view(1, -1, d), kv_p[l][..., :d], kv_p[l][..., d:], H, scale, family=G).view(-1, d)
+            s["at"] = _hip.op_attention(s["qt"].view(1, -1, d), kv_t[l][..., :d], kv_t[l][..., d:], H, scale, family=G,
+                                        key_len=k_text).view(-1, d)
+            s["ap"] = _hip.op_attention(s["qp"].view(1, -1, d), kv_p[l][..., :d], kv_p[l][..., d:], H, scale, family=G,
+                                        key_len=k_prompt).view(-1, d)
             wo, bo = blk.cross_attn.out_proj.weight, blk.cross_attn.out_proj.bias
             ot = lin(s["at"], wo, bo)
             s["x2"] = lin(s["ap"], wo, bo, r1=s["x1"], r2=ot)
@@ -390,7 +455,9 @@ class D3PMTrainer:
         logits = lin(x, m.final.weight, m.final.bias)
         return x, logits, stash
 
-    def _backward(self, x_t, fm, t, kv_t, kv_p, cond_t, cond_p, dcond_t, dcond_p, x_last, logits, stash, targets, gscale):
+    def _backward(self, x_t, fm, t, kv_t, kv_p, cond_t, cond_p, dcond_t, dcond_p, x_last, logits, stash, targets, gscale,
+                  keys=(None, None, None)):
+        k_frames, k_text, k_prompt = keys
         m, cfg = self.model, self.model.cfg
         d, H = cfg.d_model, cfg.n_heads
         scale = (1.0 / (d // H)) ** 0.5
@@ -425,11 +492,12 @@ class D3PMTrainer:
             linear_bwd(s["ap"], wo, dx, gwo, gbo, dap)
             gin_w, gin_b = _grad(blk.cross_attn.in_proj_weight), _grad(blk.cross_attn.in_proj_bias)
             wq, wkv = blk.cross_attn.in_proj_weight[:d], blk.cross_attn.in_proj_weight[d:]
-            for q_name, h_name, datt, kv, cond, dcond, norm in (("qt", "h2", dat, kv_t[l], cond_t, dcond_t, blk.norm2),
-                                                               ("qp", "h22", dap, kv_p[l], cond_p, dcond_p, blk.norm22)):
+            for q_name, h_name, datt, kv, cond, dcond, norm, k_len in (("qt", "h2", dat, kv_t[l], cond_t, dcond_t, blk.norm2, k_text),
+                                                                      ("qp", "h22", dap, kv_p[l], cond_p, dcond_p, blk.norm22, k_prompt)):
                 S = kv.shape[1]
                 dq, dkv = new(1, n, d), new(1, S, 2 * d)
-                attention_bwd(s[q_name].view(1, n, d), kv[..., :d], kv[..., d:], datt.view(1, n, d), dq, dkv[..., :d], dkv[..., d:], H, scale)
+                attention_bwd(s[q_name].view(1, n, d), kv[..., :d], kv[..., d:], datt.view(1, n, d), dq, dkv[..., :d], dkv[..., d:], H, scale,
+                              key_len=k_len)
                 dq2, dkv2 = dq.view(n, d), dkv.view(S, 2 * d)
                 dh = new(n, d)
                 linear_bwd(s[h_name], wq, dq2, gin_w[:d], gin_b[:d], dh)
@@ -440,7 +508,7 @@ class D3PMTrainer:
             linear_bwd(s["att"], blk.attn.out_proj.weight, dx, _grad(blk.attn.out_proj.weight), _grad(blk.attn.out_proj.bias), datt)
             qkv, dqkv = s["qkv"].view(1, n, 3 * d), new(1, n, 3 * d)
             attention_bwd(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], datt.view(1, n, d), dqkv[..., :d], dqkv[..., d:2 * d],
-                          dqkv[..., 2 * d:], H, scale)
+                          dqkv[..., 2 * d:], H, scale, key_len=k_frames)
             dh1 = new(n, d)
             linear_bwd(s["h1"], blk.attn.in_proj_weight, dqkv.view(n, 3 * d), _grad(blk.attn.in_proj_weight), _grad(blk.attn.in_proj_bias), dh1)
             layernorm_bwd(s["xin"], dh1, blk.norm1.weight, blk.norm1.bias, dx, _grad(blk.norm1.weight), _grad(blk.norm1.bias))
@@ -449,7 +517,8 @@ class D3PMTrainer:
 
     @torch.no_grad()
     def forward_backward(self, text_list: Sequence[torch.Tensor], proms_list: Sequence[torch.Tensor], resps_list: Sequence[torch.Tensor],
-                         *, seed: int = 0, timesteps: Optional[int] = None, dropout=False, utt0: int = 0, cond_drop=0.0):
+                         *, seed: int = 0, timesteps: Optional[int] = None, dropout=False, utt0: int = 0, cond_drop=0.0,
+                         mask_padding: bool = False):
         """The loss of AR.forward (mean over the utterances) and its gradient, accumulated into `param.grad`.
         cond_drop: p or (p_text, p_prompt) -- per utterance the text and / or the prompt is replaced by the empty one (no phonemes /
         no prompt frames, zero padded like any other: the null condition of generate_audio(guidance=...)) with that probability;
@@ -459,9 +528,18 @@ class D3PMTrainer:
         encoder layers, 0.01 in the Mlp); a (p_layer, p_mlp) pair = those probabilities (dropout_probs; module docstring).
         utt0: global index of this call's first utterance -- utterance b keys its q_sample noise and its dropout masks with
         utt0 + b, so data-parallel ranks that pass their shard offset draw what one process over the whole batch would.
+        mask_padding: True keeps an utterance from attending to its own padding, as generate_audio(mask_padding=True) does: the keys
+        of every DiT self-attention are its first min(len(resps_b), canvas) frames, those of the text / prompt cross-attention and
+        of the two encoders' self-attention its min(len(text_b), s_text) phonemes / min(rows(prom_b), s_prompt) prompt frames
+        (key_mask_lengths); a text or prompt that cond_drop replaced keeps all of its padding as keys, the rule of the null twin
+        of guidance.  A masked key has probability 0 and receives no gradient; padded rows stay queries.  The step is then the
+        model at the truncated shape: loss = (L / C) loss' + (T - 1) (C - L) ln(K) / (C L'), every gradient (L / C) times that
+        model's (DESIGN.md "Key masks in the training step").  An empty text or prompt is a ValueError before any GPU work.
+        False (default) is the step without it: the same launches.
         Returns (loss fp32 scalar tensor, [(dcond_text, dcond_prompt)] per utterance)."""
         p_layer, p_mlp = dropout_probs(dropout)
         p_text, p_prompt = cond_drop_probs(cond_drop)
+        masked = key_mask_lengths(self.model.cfg, text_list, proms_list, resps_list, mask_padding=mask_padding) is not None
         m, cfg = self.model, self.model.cfg
         smp = m.sampler()
         T = m.timesteps if timesteps is None else int(timesteps)
@@ -475,6 +553,10 @@ class D3PMTrainer:
                 n_live = int(fm.sum().item())
                 targets = (x0[0] * fm.to(torch.int32)).contiguous()
                 drop_text, drop_prompt = cond_drop_decision(seed, utt0 + b, p_text, p_prompt, m.device)
+                keys = (None, None, None)
+                if masked:      # one-element int32 tensors: the ops of this utterance run with B = 1
+                    lens = key_mask_lengths(cfg, [text], [prom], [resps], dropped=[(drop_text, drop_prompt)])
+                    keys = tuple(torch.tensor(v, dtype=torch.int32, device=m.device) for v in lens)
                 if drop_text:
                     text = text[:0]
                 if drop_prompt:
@@ -484,17 +566,17 @@ class D3PMTrainer:
                 if prom_p.shape[-1] < cfg.n_levels:
                     prom_p = F.pad(prom_p, (0, cfg.n_levels - prom_p.shape[-1]), value=-1)
                 drop = (p_layer, p_mlp, seed, utt0 + b)
-                cond_t2, st_t = self._encode(0, text_p[0].to(torch.int32).contiguous(), drop)
-                cond_p2, st_p = self._encode(1, prom_p.contiguous(), drop)
+                cond_t2, st_t = self._encode(0, text_p[0].to(torch.int32).contiguous(), drop, keys[1])
+                cond_p2, st_p = self._encode(1, prom_p.contiguous(), drop, keys[2])
                 kv_t, kv_p = smp.cond_kv(cond_t2[None], cond_p2[None])
                 dcond_t, dcond_p = torch.zeros_like(cond_t2), torch.zeros_like(cond_p2)
                 gscale = 1.0 / (cfg.canvas * max(n_live, 1) * B)
                 total = torch.zeros((), dtype=torch.float32, device=m.device)
                 for t in range(1, T):
                     x_t = smp.q_sample(x0, fm, t, seed, utt0 + b)
-                    x_last, logits, stash = self._forward(x_t, fm, t, kv_t, kv_p, smp.film)
+                    x_last, logits, stash = self._forward(x_t, fm, t, kv_t, kv_p, smp.film, keys)
                     total += smp.ce_loss_rows(logits.view(1, cfg.canvas, cfg.n_classes), targets.view(1, -1), fm).mean()
-                    self._backward(x_t, fm, t, kv_t, kv_p, cond_t2, cond_p2, dcond_t, dcond_p, x_last, logits, stash, targets, gscale)
+                    self._backward(x_t, fm, t, kv_t, kv_p, cond_t2, cond_p2, dcond_t, dcond_p, x_last, logits, stash, targets, gscale, keys)
                 self._encode_backward(st_t, dcond_t)
                 self._encode_backward(st_p, dcond_p)
                 losses.append(total / max(n_live, 1))
