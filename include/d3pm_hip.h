@@ -66,7 +66,8 @@ extern "C" {
  *    with the keys read through a row index (d3pm_op_attention_gather); the segment granularity of that index
  *    (d3pm_op_dedup_index_align: 1 = dense segments, what the loop runs; d3pm_op_attention_gather and
  *    d3pm_op_attention_pair_segments take a segment of any length at any row); key-padding masks in the training step
- *    (d3pm_op_attention_bwd_keylen_f32, d3pm_op_attention_dropout_keylen_f32) */
+ *    (d3pm_op_attention_bwd_keylen_f32, d3pm_op_attention_dropout_keylen_f32); the NAR stage's own kernels one at a time
+ *    (d3pm_op_nar_embed, d3pm_op_adaln, d3pm_op_nar_sample) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -875,6 +876,30 @@ int d3pm_op_posterior_sample_rows(const d3pm_shape *shape, int batch, const void
                                   const int32_t *row_of, const int32_t *x_t, int32_t *x_next, int32_t *x_next2, const uint8_t *known,
                                   int t, const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags,
                                   const d3pm_nucleus *nucleus, const d3pm_guidance *guidance, void *stream);
+/* The three kernels of the stock NAR stage one at a time (tests): each entry validates on the host and then makes the one call
+ * d3pm_nar_level makes, with no kernel choice of its own.  Refused with D3PM_E_ARG, nothing launched: a NULL pointer, an unknown
+ * dtype, a size that is not positive, and what each entry names below.
+ *   d3pm_op_nar_embed   the input assembly: arrays as in d3pm_nar_level (resp [batch][tr_max][resp_stride], levels 0 .. n_given - 1
+ *                       summed; prom levels with a code < 0 skipped; ids clamped into [0, n_tokens - 1]); tables of `dtype`: w_text
+ *                       [n_tokens][d], w_prom [n_prom_levels][n_tokens][d], w_resp [>= n_given][n_tokens][d], sep [d], pe [>= t_max][d].
+ *                       Writes x [batch][t_max][d] (rows at or past an utterance's total = t_text + t_prompt + t_response + 2 are
+ *                       zero; an utterance longer than t_max is cut at the grid), row_mask uint8 [batch][t_max] = (pos < total) and
+ *                       key_len int32 [batch] = total.  1 <= n_given <= resp_stride.
+ *   d3pm_op_adaln       y[r] = row_mask[r] ? AdaLN(x[r]) : 0 over [M][d] with emb_row [2d] = (log gamma | beta) of one level, every
+ *                       intermediate rounded to `dtype`.  16-bit rows of width 512 / 1024 take the 16-byte kernels when x, y and
+ *                       emb_row are 16-byte aligned and the scalar kernel otherwise (the launcher's rule, not this entry's).
+ *   d3pm_op_nar_sample  the draw of level `level + 1`: logits [batch][t_max][ldl] of `dtype`, ldl >= n_tokens; frame f < t_response of
+ *                       utterance b reads grid row t_text + t_prompt + 2 + f (a row outside the grid is skipped) and writes
+ *                       resp[b][f][level + 1] = first-index argmax_j rn(logit_j / temperature) + gumbel(u_j), u from the Philox
+ *                       counter (j >> 2, (utt0 + b) * 65536 + f, level, stream 2); flags: D3PM_FLAG_GREEDY = no noise.
+ *                       temperature > 0, 0 <= level, level + 1 < resp_stride. */
+int d3pm_op_nar_embed(int dtype, const int32_t *lens, const int32_t *text, int tt_max, const int32_t *prom, int tp_max, int n_prom_levels,
+                      const int32_t *resp, int tr_max, int resp_stride, int n_given, const void *w_text, const void *w_prom,
+                      const void *w_resp, const void *sep, const void *pe, void *x, uint8_t *row_mask, int32_t *key_len, int batch,
+                      int t_max, int d, int n_tokens, void *stream);
+int d3pm_op_adaln(int dtype, const void *x, void *y, const void *emb_row, const uint8_t *row_mask, int M, int d, void *stream);
+int d3pm_op_nar_sample(int dtype, const void *logits, int ldl, const int32_t *lens, int32_t *resp, int tr_max, int resp_stride, int t_max,
+                       int n_tokens, int level, float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, int batch, void *stream);
 int d3pm_op_layernorm(int dtype, const void *X, void *Y, const void *w, const void *b, const void *film,
                       int M, int d, float eps, void *stream);
 /* Row-panel projection (d_model = 512): a Linear whose output is added to the residual stream, together with the LayerNorm(s)

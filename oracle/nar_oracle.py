@@ -105,10 +105,12 @@ def sample_torch(logits_list, temperature: float):
 
 
 def sample_gumbel(logits_list, temperature: float, seed: int, level: int, utt0: int = 0, greedy: bool = False):
-    """Gumbel-max over the Philox stream: counter row = (utt0 + b) * 65536 + frame, t = level, stream 2."""
+    """Gumbel-max over the Philox stream: counter row = (utt0 + b) * 65536 + frame, t = level, stream 2.  `h / temperature` is
+    evaluated in h's dtype like the reference's `Categorical(logits=hi / sampling_temperature)` (base.py:491-494): a 16-bit model
+    rounds the quotient to its storage type before anything else happens to it."""
     out = []
     for b, h in enumerate(logits_list):
-        z = h.float() / temperature
+        z = (h / temperature).float()
         if not greedy:
             u = torch.from_numpy(philox.uniform_rows(seed, level, (utt0 + b) * 65536, h.shape[0], h.shape[1], STREAM_NAR))
             u = torch.clamp(u, min=torch.finfo(torch.float32).tiny, max=1.0)

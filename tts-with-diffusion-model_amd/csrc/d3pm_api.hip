@@ -1680,6 +1680,44 @@ int d3pm_nar_level(const d3pm_nar_shape* sh, const d3pm_nar_weights* w, int batc
                     (flags & D3PM_FLAG_GREEDY) ? 1 : 0, batch, s);
 }
 
+// the three kernels of the stage one at a time (tests): host validation, then the call d3pm_nar_level makes
+static bool storage_dtype(int dtype) { return dtype == D3PM_F32 || dtype == D3PM_F16 || dtype == D3PM_BF16; }
+
+int d3pm_op_nar_embed(int dtype, const int32_t* lens, const int32_t* text, int tt_max, const int32_t* prom, int tp_max, int n_prom_levels,
+                      const int32_t* resp, int tr_max, int resp_stride, int n_given, const void* w_text, const void* w_prom,
+                      const void* w_resp, const void* sep, const void* pe, void* x, uint8_t* row_mask, int32_t* key_len, int batch,
+                      int t_max, int d, int n_tokens, void* stream) {
+  D3PM_REQUIRE(storage_dtype(dtype), D3PM_E_ARG, "d3pm_op_nar_embed: bad dtype %d", dtype);
+  D3PM_REQUIRE(lens && text && prom && resp && w_text && w_prom && w_resp && sep && pe && x && row_mask && key_len, D3PM_E_ARG,
+               "d3pm_op_nar_embed: null pointer");
+  D3PM_REQUIRE(batch > 0 && t_max > 0 && tt_max > 0 && tp_max > 0 && tr_max > 0 && d > 0 && n_tokens > 0 && n_prom_levels > 0 &&
+                   n_given >= 1 && n_given <= resp_stride,
+               D3PM_E_ARG, "d3pm_op_nar_embed: sizes must be positive and 1 <= n_given <= resp_stride");
+  NarEmbedArgs e;
+  e.lens = lens; e.text = text; e.tt_max = tt_max; e.prom = prom; e.tp_max = tp_max; e.n_prom_levels = n_prom_levels;
+  e.resp = resp; e.tr_max = tr_max; e.resp_stride = resp_stride; e.n_given = n_given;
+  e.w_text = w_text; e.w_prom = w_prom; e.w_resp = w_resp; e.sep = sep; e.pe = pe;
+  e.x = x; e.row_mask = row_mask; e.key_len = key_len; e.batch = batch; e.t_max = t_max; e.d = d; e.n_tokens = n_tokens;
+  return nar_embed(dtype, e, static_cast<hipStream_t>(stream));
+}
+
+int d3pm_op_adaln(int dtype, const void* x, void* y, const void* emb_row, const uint8_t* row_mask, int M, int d, void* stream) {
+  D3PM_REQUIRE(storage_dtype(dtype), D3PM_E_ARG, "d3pm_op_adaln: bad dtype %d", dtype);
+  D3PM_REQUIRE(x && y && emb_row && row_mask && M > 0 && d > 0, D3PM_E_ARG, "d3pm_op_adaln: bad arguments");
+  return adaln(dtype, x, y, emb_row, row_mask, M, d, static_cast<hipStream_t>(stream));
+}
+
+int d3pm_op_nar_sample(int dtype, const void* logits, int ldl, const int32_t* lens, int32_t* resp, int tr_max, int resp_stride, int t_max,
+                       int n_tokens, int level, float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, int batch, void* stream) {
+  D3PM_REQUIRE(storage_dtype(dtype), D3PM_E_ARG, "d3pm_op_nar_sample: bad dtype %d", dtype);
+  D3PM_REQUIRE(logits && lens && resp, D3PM_E_ARG, "d3pm_op_nar_sample: null pointer");
+  D3PM_REQUIRE(batch > 0 && t_max > 0 && tr_max > 0 && n_tokens > 0 && ldl >= n_tokens && level >= 0 && level + 1 < resp_stride &&
+                   temperature > 0.f,
+               D3PM_E_ARG, "d3pm_op_nar_sample: sizes must be positive, ldl >= n_tokens, 0 <= level < resp_stride - 1, temperature > 0");
+  return nar_sample(dtype, logits, ldl, lens, resp, tr_max, resp_stride, t_max, n_tokens, level, temperature, seed, utt0,
+                    (flags & D3PM_FLAG_GREEDY) ? 1 : 0, batch, static_cast<hipStream_t>(stream));
+}
+
 int d3pm_op_linear(int dtype, int family, const void* X, int ldx, const void* W, const void* bias, void* Y, int ldy,
                    const void* R1, const void* R2, int ldr, const uint8_t* row_mask, int mask_period, int M, int N, int K,
                    int act, const d3pm_tuning* tuning, void* stream) {

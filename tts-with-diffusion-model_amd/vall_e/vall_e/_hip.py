@@ -376,6 +376,12 @@ SIGNATURES = {
     "d3pm_op_posterior_sample_rows": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32,
                                                 C.POINTER(Nucleus), C.POINTER(Guidance), C.c_void_p]),
+    "d3pm_op_nar_embed": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "d3pm_op_adaln": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "d3pm_op_nar_sample": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "d3pm_op_layernorm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_int, C.c_float, C.c_void_p]),
     "d3pm_op_linear_rowpanel": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1260,6 +1266,86 @@ def op_posterior_sample_rows(shape, schedule, logits, row_of, x_t, t, seed, *, u
                                               None if nuc is None else C.byref(nuc), None if gd is None else C.byref(gd), stream_ptr()),
           "d3pm_op_posterior_sample_rows")
     return (x_next, second) if want_second else x_next
+
+
+def _require_table(t, name, shape, dtype, dev, min_rows=None):
+    """A contiguous table of `dtype` on `dev`; with min_rows the leading extent may be anything from min_rows up."""
+    ok = isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == dev and t.is_contiguous() and t.dim() == len(shape) and \
+        tuple(t.shape[1:]) == tuple(shape[1:]) and (t.shape[0] >= min_rows if min_rows is not None else t.shape[0] == shape[0])
+    if not ok:
+        lead = [f">= {min_rows}"] + list(shape[1:]) if min_rows is not None else list(shape)
+        raise D3PMError(f"{name} must be a contiguous {dtype} {lead} tensor on {dev}")
+
+
+def op_nar_embed(lens, text, prom, resp, n_given, w_text, w_prom, w_resp, sep, pe, t_max, *, x=None, row_mask=None, key_len=None):
+    """The NAR stage's input assembly on its own (d3pm_op_nar_embed): lens int32 [B, 3]; text int32 [B, tt_max]; prom int32
+    [B, tp_max, n_prom_levels] (-1 = level absent); resp int32 [B, tr_max, resp_stride], levels 0 .. n_given - 1 summed; tables of one
+    float dtype: w_text [n_tokens, d], w_prom [n_prom_levels, n_tokens, d], w_resp [>= n_given, n_tokens, d], sep [d], pe [>= t_max, d].
+    Returns (x [B, t_max, d], row_mask uint8 [B, t_max], key_len int32 [B]); each may be handed in (a contiguous view of a larger
+    buffer is fine: nothing outside the view is written)."""
+    if not isinstance(lens, torch.Tensor) or lens.dim() != 2 or lens.shape[1] != 3 or lens.shape[0] == 0:
+        raise D3PMError("lens must be an int32 [B, 3] tensor")
+    if not isinstance(w_text, torch.Tensor) or w_text.dim() != 2 or w_text.dtype not in _DTYPES:
+        raise D3PMError(f"w_text must be a [n_tokens, d] tensor of one of {tuple(_DTYPES)}")
+    if not all(isinstance(t, torch.Tensor) and t.dim() == n for t, n in ((text, 2), (prom, 3), (resp, 3))):
+        raise D3PMError("text [B, tt_max], prom [B, tp_max, n_prom_levels] and resp [B, tr_max, resp_stride] must be tensors")
+    B, dev, dtype = lens.shape[0], lens.device, w_text.dtype
+    (n_tokens, d), levels, stride = w_text.shape, prom.shape[2], resp.shape[2]
+    if not isinstance(n_given, int) or not isinstance(t_max, int) or t_max <= 0 or not 1 <= n_given <= stride:
+        raise D3PMError(f"op_nar_embed: t_max {t_max!r} must be positive and n_given {n_given!r} within 1 .. {stride}")
+    _require_int32([("lens", lens, (B, 3)), ("text", text, (B, text.shape[1])), ("prom", prom, (B, prom.shape[1], levels)),
+                    ("resp", resp, (B, resp.shape[1], stride))], dev)
+    _require_table(w_text, "w_text", (n_tokens, d), dtype, dev)
+    _require_table(w_prom, "w_prom", (levels, n_tokens, d), dtype, dev)
+    _require_table(w_resp, "w_resp", (n_given, n_tokens, d), dtype, dev, min_rows=n_given)
+    _require_table(sep, "sep", (d,), dtype, dev)
+    _require_table(pe, "pe", (t_max, d), dtype, dev, min_rows=t_max)
+    x = torch.empty((B, t_max, d), dtype=dtype, device=dev) if x is None else x
+    row_mask = torch.empty((B, t_max), dtype=torch.uint8, device=dev) if row_mask is None else row_mask
+    key_len = torch.empty((B,), dtype=torch.int32, device=dev) if key_len is None else key_len
+    _require(x, "x", (B, t_max, d), (dtype,), dev)
+    _require(row_mask, "row_mask", (B, t_max), (torch.uint8,), dev)
+    _require_int32([("key_len", key_len, (B,))], dev)
+    check(lib().d3pm_op_nar_embed(dtype_code(dtype), _p(lens), _p(text), text.shape[1], _p(prom), prom.shape[1], levels, _p(resp), resp.shape[1],
+                                  stride, n_given, _p(w_text), _p(w_prom), _p(w_resp), _p(sep), _p(pe), _p(x), _p(row_mask), _p(key_len), B,
+                                  t_max, d, n_tokens, stream_ptr()), "d3pm_op_nar_embed")
+    return x, row_mask, key_len
+
+
+def op_adaln(x, emb_row, row_mask, *, out=None):
+    """AdaLN of the NAR stage on its own (d3pm_op_adaln): x [M, d] with dense rows, emb_row [2 d] = (log gamma | beta) of one level,
+    row_mask uint8 [M]; returns y [M, d] (or `out`), rows with a zero mask entry zero.  The addresses go to the library as they are:
+    a view whose storage offset breaks the 16-byte alignment of x, out or emb_row takes the scalar kernel at d = 512 / 1024."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype not in _DTYPES or not x.is_contiguous() or x.numel() == 0:
+        raise D3PMError(f"x must be a contiguous [M, d] tensor of one of {tuple(_DTYPES)}")
+    M, d = x.shape
+    dev = x.device
+    _require(emb_row, "emb_row", (2 * d,), (x.dtype,), dev)
+    _require(row_mask, "row_mask", (M,), (torch.uint8,), dev)
+    out = torch.empty_like(x) if out is None else out
+    _require(out, "out", (M, d), (x.dtype,), dev)
+    check(lib().d3pm_op_adaln(dtype_code(x.dtype), _p(x), _p(out), _p(emb_row), _p(row_mask), M, d, stream_ptr()), "d3pm_op_adaln")
+    return out
+
+
+def op_nar_sample(logits, lens, resp, level, temperature, seed, *, utt0=0, flags=0):
+    """The NAR stage's level draw on its own (d3pm_op_nar_sample): logits [B, t_max, n_tokens] of a float dtype (a view with a wider
+    row stride allowed, dense in t), lens int32 [B, 3], resp int32 [B, tr_max, resp_stride]: column level + 1 of every response frame
+    inside the grid is written in place; returns resp.  flags: FLAG_GREEDY."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3 or logits.dtype not in _DTYPES or logits.numel() == 0:
+        raise D3PMError(f"logits must be a [B, t_max, n_tokens] tensor of one of {tuple(_DTYPES)}")
+    B, t_max, n_tokens = logits.shape
+    dev, ldl = logits.device, logits.stride(1)
+    if logits.stride(2) != 1 or ldl < n_tokens or logits.stride(0) != t_max * ldl:
+        raise D3PMError("logits: unit column stride, a row stride >= n_tokens, utterances t_max rows apart")
+    if not isinstance(resp, torch.Tensor) or resp.dim() != 3:
+        raise D3PMError("resp must be an int32 [B, tr_max, resp_stride] tensor")
+    _require_int32([("lens", lens, (B, 3)), ("resp", resp, (B, resp.shape[1], resp.shape[2]))], dev)
+    if not isinstance(level, int) or not 0 <= level < resp.shape[2] - 1:
+        raise D3PMError(f"level {level!r} must be within 0 .. {resp.shape[2] - 2}")
+    check(lib().d3pm_op_nar_sample(dtype_code(logits.dtype), _p(logits), ldl, _p(lens), _p(resp), resp.shape[1], resp.shape[2], t_max,
+                                   n_tokens, level, float(temperature), seed, utt0, flags, B, stream_ptr()), "d3pm_op_nar_sample")
+    return resp
 
 
 def stats_buffer(M: int, parts: int, device) -> torch.Tensor:
