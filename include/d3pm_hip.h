@@ -67,7 +67,8 @@ extern "C" {
  *    (d3pm_op_dedup_index_align: 1 = dense segments, what the loop runs; d3pm_op_attention_gather and
  *    d3pm_op_attention_pair_segments take a segment of any length at any row); key-padding masks in the training step
  *    (d3pm_op_attention_bwd_keylen_f32, d3pm_op_attention_dropout_keylen_f32); the NAR stage's own kernels one at a time
- *    (d3pm_op_nar_embed, d3pm_op_adaln, d3pm_op_nar_sample) */
+ *    (d3pm_op_nar_embed, d3pm_op_adaln, d3pm_op_nar_sample); the latency GEMM family in the iterations of the deduplicated loop
+ *    that have few live rows (d3pm_op_linear_live_est; ln_fold value 4 = the deduplicated loop without that switch) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -168,6 +169,11 @@ enum {
  *                      deduplication).  1, 2 and 3 give identical ids.  3 is an A/B value OUTSIDE the shipped list: the library and
  *                      `bench.py --tune ln_fold=3` take it for measurements and tests, the Python `tuning()` context, which
  *                      admits shipped schedules only, refuses it (0, 1 and 2 are the shipped values).
+ *                      With 1 an iteration of that loop whose live rows the host bounds by a small number -- batch * min(canvas,
+ *                      2 + ceil(canvas * (1 - cbar[t]))) from the schedule, no read-back; loops without known frames -- runs the
+ *                      projections of its blocks on the 64 x 64 latency family (moments as 32-column parts in that iteration) instead
+ *                      of big tiles.  4 = the deduplicated loop with that switch off (big tiles in every iteration): like 3 an A/B
+ *                      value outside the shipped list.  1, 3 and 4 give identical ids.
  *   prof               optional timing hooks (d3pm_prof_create below), NULL = none. */
 struct d3pm_prof;
 typedef struct d3pm_tuning {
@@ -806,6 +812,14 @@ int d3pm_op_linear_live(int dtype, const void *X, const void *X2, int ldx, const
                         const void *R1, int ldr, const uint8_t *row_mask, int mask_period, int M, int N, int K, int act,
                         const float *fold_s, const float *fold_b, const float *stats_in, float *stats_out, const int32_t *m_live,
                         const d3pm_tuning *tuning, void *stream);
+/* The same with the host's estimate of *m_live (tests; 0 = none, which is d3pm_op_linear_live): an estimate within the latency bound of
+ * the sampler loop (or gemm_variant = 4 with any estimate) plans the 64 x 64 latency family, whose grid covers min(M, m_est) rows and
+ * whose workgroups walk the live tiles in rounds -- any *m_live in 0 .. M gives the same rows as every other family.  On that family the
+ * moments travel as 32-column parts (the layout of d3pm_op_row_stats), and the dual form takes M a multiple of 32. */
+int d3pm_op_linear_live_est(int dtype, const void *X, const void *X2, int ldx, const void *W, const void *bias, void *Y, int ldy,
+                            const void *R1, int ldr, const uint8_t *row_mask, int mask_period, int M, int N, int K, int act,
+                            const float *fold_s, const float *fold_b, const float *stats_in, float *stats_out, const int32_t *m_live,
+                            int m_est, const d3pm_tuning *tuning, void *stream);
 /* The block-0 QKV rows of `n` token ids as the sampler loop makes them under ln_fold = 1 (tests): builds the table [rows][3 d_model]
  * (row id = the folded QKV projection of resps_emb[id] with that row's moments, row n_classes = that of a zero row) in `storage`
  * (device, 256-byte aligned, >= d3pm_op_embed_qkv_bytes(shape, n)), then q_out[r] [n][d_model] | kv_out[r] [n][2 d_model] = the q and

@@ -326,6 +326,9 @@ struct DenoiserArgs {      // what every block of one evaluation sees
   // projection and attention query of the folded sequence runs on the compact rows (live count and segments read from device memory),
   // and the launch that prepares an evaluation is dedup_index.
   const DedupIndex* dd = nullptr;
+  // with dd, per iteration: the host's estimate of the live rows (plan_live_rows) when the iteration takes the latency launch list --
+  // every projection of a block on gemm_mfma_panel64, sized for the estimate, moments as parts -- or 0: the big-tile list, quads
+  int m_est = 0;
 };
 // the token embedding of an evaluation whose two halves read the same x_t (token_rows > 0): the gather, once per half
 static int embed_twins(const DenoiserArgs& q, const int32_t* x_t, hipStream_t s) {
@@ -356,7 +359,7 @@ static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v, bo
   const int* m_live = q.dd ? q.dd->m_live : nullptr;
   auto consumer = [&](const void* Wf, const float* fs, const float* fb, void* Y, int N, int act) {
     LinearArgs g = folded_projection(ws.x, Wf, fs, fb, ws.stats, quads, Y, n, N, d, act);
-    g.m_live = m_live;
+    g.m_live = m_live; g.m_est = q.m_est;
     return v.linear(g);
   };
   auto segments = [&](AttnArgs a) {
@@ -366,7 +369,7 @@ static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v, bo
   // a projection onto the residual stream: x += X . W^T + bias (+ R2), then the moments of the new rows
   auto producer = [&](const void* X, int K, const void* W, const void* bias, const void* R2 = nullptr) {
     LinearArgs g = with_moments_out(with_residual(projection(X, W, bias, ws.x, n, d, K), ws.x, R2), ws.stats, quads);
-    g.m_live = m_live;
+    g.m_live = m_live; g.m_est = q.m_est;
     return g;
   };
   // ---- self-attention ----
@@ -426,12 +429,13 @@ struct FoldPlanner {
   }
 };
 // asks: would the sequence run on the kernels that read a live row count and query segments from device memory -- every projection on
-// big tiles, the self-attention on attn32p_hd64, the cross pair on attn32_cross_hd64?
+// `family` (big tiles; gemm_mfma_panel64 for the latency iterations, asked with DenoiserArgs::m_est set and the moments as parts), the
+// self-attention on attn32p_hd64, the cross pair on attn32_cross_hd64?
 struct DedupPlanner {
-  int dt; const d3pm_tuning* tune; bool ok;
+  int dt; const d3pm_tuning* tune; bool ok; int family = LIN_BIG;
   int linear(LinearArgs g) {
     g.tune = tune;
-    ok = ok && plan_linear(dt, g).big();
+    ok = ok && plan_linear(dt, g).kernel == family;
     return D3PM_OK;
   }
   int attention(AttnArgs a) {
@@ -440,7 +444,7 @@ struct DedupPlanner {
     return D3PM_OK;
   }
   int dual(const CrossOutPlan& c, const LinearArgs&, const void*) {
-    ok = ok && c.dual.big();
+    ok = ok && c.dual.kernel == family;
     return D3PM_OK;
   }
 };
@@ -459,6 +463,9 @@ struct FoldLauncher {
 // ws.stats, the sampler's embedding rows included, must use the same format -- taken once per call by denoise_step_impl /
 // sample_loop_impl over ALL layers (only_layers never changes the format).  The walk asks with the parts format and the sequence
 // launches with the answer; at d = 512, the only width that gets quads, fold_args_ok accepts both formats for these arguments.
+// The deduplicated loop alone refines the answer per ITERATION (sample_loop_impl): an iteration on the latency launch list runs its
+// whole chain -- the index launch that prepares it included -- on parts, every other one on quads.  The consumers compute the same bits
+// from either format, so the switch changes no id.
 enum { FOLD_NONE = 0, FOLD_PARTS = 1, FOLD_QUADS = 2 };
 static int fold_plan(const DenoiserArgs& q, uint32_t flags, const d3pm_fp8_block_weights* f8) {
   const d3pm_shape& sh = q.sh;
@@ -867,21 +874,38 @@ int d3pm_op_dedup_index_align(int dtype, const int32_t* tokens, const uint8_t* f
 int d3pm_op_linear_live(int dtype, const void* X, const void* X2, int ldx, const void* W, const void* bias, void* Y, int ldy, const void* R1, int ldr,
                         const uint8_t* row_mask, int mask_period, int M, int N, int K, int act, const float* fold_s, const float* fold_b,
                         const float* stats_in, float* stats_out, const int32_t* m_live, const d3pm_tuning* tuning, void* stream) {
-  D3PM_REQUIRE(X && W && Y && m_live && M > 0 && N > 0 && K > 0, D3PM_E_ARG, "d3pm_op_linear_live: bad arguments");
+  return d3pm_op_linear_live_est(dtype, X, X2, ldx, W, bias, Y, ldy, R1, ldr, row_mask, mask_period, M, N, K, act, fold_s, fold_b, stats_in, stats_out,
+                                 m_live, 0, tuning, stream);
+}
+
+int d3pm_op_linear_live_est(int dtype, const void* X, const void* X2, int ldx, const void* W, const void* bias, void* Y, int ldy, const void* R1,
+                            int ldr, const uint8_t* row_mask, int mask_period, int M, int N, int K, int act, const float* fold_s, const float* fold_b,
+                            const float* stats_in, float* stats_out, const int32_t* m_live, int m_est, const d3pm_tuning* tuning, void* stream) {
+  D3PM_REQUIRE(X && W && Y && m_live && M > 0 && N > 0 && K > 0 && m_est >= 0, D3PM_E_ARG, "d3pm_op_linear_live: bad arguments");
   LinearArgs g;
   g.tune = tuning;
   g.X = X; g.ldx = ldx; g.W = W; g.bias = bias; g.Y = Y; g.ldy = ldy; g.R1 = R1; g.ldr = ldr; g.M = M; g.N = N; g.K = K; g.act = act;
   g.row_mask = row_mask; g.mask_period = mask_period > 0 ? mask_period : 1;
-  g.fold_s = fold_s; g.fold_b = fold_b; g.stats_in = stats_in; g.stats_out = stats_out; g.moment_quads = (fold_s || stats_out) && (fold_s ? K : N) == 512;
-  g.m_live = m_live;
+  g.fold_s = fold_s; g.fold_b = fold_b; g.stats_in = stats_in; g.stats_out = stats_out;
+  g.m_live = m_live; g.m_est = m_est;
+  // gemm_mfma_panel64 reads and writes the moments as parts; where the planner names another family they travel as quads at width 512
+  const bool quads = (fold_s || stats_out) && (fold_s ? K : N) == 512;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (X2) {      // both cross-attention out-projections in one launch
-    const CrossOutPlan c = plan_cross_out(dtype, g, X2, false, true);
-    D3PM_REQUIRE(c.form == CROSS_OUT_BIG_DUAL, D3PM_E_SHAPE, "d3pm_op_linear_live: the dual form needs the big-tile family");
+    CrossOutPlan c = plan_cross_out(dtype, g, X2, false, true);
+    if (c.form == CROSS_OUT_PANEL64_DUAL) return panel64_dual(dtype, g, X2, c.dual, s);
+    g.moment_quads = quads;
+    c = plan_cross_out(dtype, g, X2, false, true);
+    D3PM_REQUIRE(c.form == CROSS_OUT_BIG_DUAL, D3PM_E_SHAPE, "d3pm_op_linear_live: the dual form needs the big-tile or the panel64 family");
     return big_dual(dtype, g, X2, c.dual, s);
   }
-  const LinearPlan plan = plan_linear(dtype, g);
-  D3PM_REQUIRE(plan.big() || plan.kernel == LIN_128_GLDS, D3PM_E_SHAPE, "d3pm_op_linear_live: %d x %d x %d takes a kernel without a device-side row count", M, N, K);
+  LinearPlan plan = plan_linear(dtype, g);
+  if (plan.kernel != LIN_PANEL64) {
+    g.moment_quads = quads;
+    plan = plan_linear(dtype, g);
+  }
+  D3PM_REQUIRE(plan.big() || plan.kernel == LIN_128_GLDS || plan.kernel == LIN_PANEL64, D3PM_E_SHAPE,
+               "d3pm_op_linear_live: %d x %d x %d takes a kernel without a device-side row count", M, N, K);
   return mfma_linear(dtype, g, plan, s);
 }
 
@@ -1238,11 +1262,12 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     D3PM_TRY(build_qkv_table(cx, *sh, *w, ws, s));
     q.qkv_table = ws.tab_qkv;
   }
-  // Row deduplication (d3pm_dedup.hip; ln_fold = 3 keeps every row): the unguided 16-bit n_q = 1 loop with the table, moments as quads,
+  // Row deduplication (d3pm_dedup.hip; ln_fold = 3 keeps every row, 4 keeps the big-tile list in every iteration): the unguided 16-bit n_q = 1 loop with the table, moments as quads,
   // and every launch of the sequence on a kernel that reads the live count / the query segments from device memory.  One decision per
   // call; otherwise the launch list above runs untouched.
   const int n_rows = eval_batch * sh->canvas;
-  if (q.qkv_table && plan == FOLD_QUADS && tune_of(sh->tuning).ln_fold == 1 && !f8 && !guide && ws.dd.row_of && n_rows % 384 == 0 && sh->n_layers <= 16 &&
+  const int ln_fold = tune_of(sh->tuning).ln_fold;
+  if (q.qkv_table && plan == FOLD_QUADS && (ln_fold == 1 || ln_fold == 4) && !f8 && !guide && ws.dd.row_of && n_rows % 384 == 0 && sh->n_layers <= 16 &&
       sh->n_classes <= kDedupMaxClasses && ws.h2 == at(ws.h, static_cast<size_t>(n_rows) * sh->d_model, dtype_size(sh->dtype))) {
     DedupPlanner dp{sh->dtype, sh->tuning, true};
     for (int l = 0; l < sh->n_layers; ++l) (void)folded_block(q, l, true, dp, l == 0);
@@ -1255,11 +1280,33 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     const bool gather_ok = static_cast<size_t>(sh->canvas) * 4 <= kGatherIndexBytes && kv_rows * 3 * sh->d_model * dtype_size(sh->dtype) < (1ull << 32);
     if (dp.ok && gather_ok && (fp.big() || fp.kernel == LIN_128_GLDS)) q.dd = &ws.dd;
   }
+  // The regime of an iteration of the deduplicated loop, decided here with no read-back (the loop is graph-captured): iteration t
+  // evaluates x_t, which the sampler launch of iteration t + 1 drew with cbar_prev = cbar[t] (make_posterior_consts), so a frame of it is
+  // still masked with probability float(cbar[t]) -- the index of the iteration itself, also for t_start, whose canvas the caller
+  // brings (all mask in a full reverse process).  An estimate within live_latency_rows() takes the latency launch list when every
+  // projection of a block plans onto gemm_mfma_panel64 for it (the final projection keeps its kernel).  The estimate chooses speed
+  // only: every kernel reads the live count from the device.  Known frames (cm.known) are the caller's and cannot be counted here:
+  // such a loop keeps the big-tile list, as does ln_fold = 4 (the A/B arm).
+  bool latency_ok = false;
+  if (q.dd && ln_fold == 1 && !cm.known) {
+    DenoiserArgs ql = q;
+    ql.m_est = live_latency_rows();
+    DedupPlanner lp{sh->dtype, sh->tuning, true, LIN_PANEL64};
+    for (int l = 0; l < sh->n_layers; ++l) (void)folded_block(ql, l, false, lp, l == 0);
+    latency_ok = lp.ok;
+  }
+  auto latency_est = [&](int t) {      // the iteration's DenoiserArgs::m_est
+    if (!latency_ok || t <= t_stop) return 0;
+    const int est = plan_live_rows(eval_batch, sh->canvas, host_h2f(sched->cbar[t]));
+    return live_latency(est) ? est : 0;
+  };
   bool prepared = false;     // the previous iteration's sampler launch has already embedded x_t and folded fc1 for this t
   bool qkv_ready = false;     // ... and gathered ws.q0 | ws.kv0 for every row of this evaluation
   for (int t = t_start; t > t_stop; --t) {
     if (cx.prof) cx.prof->sample_now = (t % cx.prof->stride) == 0;
-    D3PM_TRY(denoiser_blocks(q, x, t, film, sh->n_layers, flags, s, f8, plan, prepared, qkv_ready));
+    q.m_est = latency_est(t);
+    // (a latency iteration's moments travel as parts: its producers and consumers, and the index launch that prepared it)
+    D3PM_TRY(denoiser_blocks(q, x, t, film, sh->n_layers, flags, s, f8, q.m_est ? FOLD_PARTS : plan, prepared, qkv_ready));
     prepared = qkv_ready = false;
     SampleArgs a;
     a.logits = ws.logits; a.logits_dtype = sh->dtype; a.ldl = logits_ld(*sh); a.x_t = x; a.x_next = x;
@@ -1288,7 +1335,7 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
           D3PM_TRY(posterior_sample_dedup(a, q.dd->row_of, nx, s));
         }
         if (preps) {
-          D3PM_TRY(run_dedup_index(q, x, plan == FOLD_QUADS, s));
+          D3PM_TRY(run_dedup_index(q, x, plan == FOLD_QUADS && !latency_est(t - 1), s));
           prepared = qkv_ready = true;
         }
         continue;

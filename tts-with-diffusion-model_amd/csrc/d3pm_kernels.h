@@ -43,8 +43,12 @@ struct LinearArgs {
   // big-tile GEMM only (LIN_QUADS_REFUSED, d3pm_plan.h: mfma_linear fails with D3PM_E_SHAPE on any other family); one host decision per folded sequence (d3pm_api.hip)
   bool moment_quads = false;
   // optional live row count in device memory (row deduplication, d3pm_dedup.hip): only the tiles that hold a row < *m_live run; M stays
-  // the capacity the plan was made for.  Big-tile family and gemm_mfma_128_glds only (mfma_linear refuses it elsewhere).
+  // the capacity the plan was made for.  Big-tile family, gemm_mfma_128_glds and gemm_mfma_panel64 (mfma_linear refuses it elsewhere).
   const int* m_live = nullptr;
+  // host-side estimate of *m_live (d3pm_plan.h plan_live_rows), 0 = none: the planner chooses the family and sizes the grid of
+  // gemm_mfma_panel64 for min(M, m_est) rows.  It only chooses speed: the kernel walks every live tile whatever the grid.  Without
+  // an estimate a launch plans for the capacity, as it did before the field existed.
+  int m_est = 0;
 };
 // which LayerNorm-fold combinations the MFMA epilogues instantiate: LNF [+ GELU] without residual / mask; STATS with R1, R1 + R2, R1 + mask
 inline bool fold_args_ok(const LinearArgs& a) {

@@ -324,9 +324,7 @@ __global__ __launch_bounds__(256, 4) void gemm_mfma_128_persist(const T* __restr
 int mfma_linear(int dtype, const LinearArgs& a, const LinearPlan& p, hipStream_t s) {
   switch (p.kernel) {
     case LIN_BIG: return big_linear(dtype, a, p, s);
-    case LIN_PANEL64:
-      D3PM_REQUIRE(!a.m_live, D3PM_E_SHAPE, "device-side live row count: %d x %d x %d takes a kernel without it", a.M, a.N, a.K);
-      return panel64_linear(dtype, a, p, s);
+    case LIN_PANEL64: return panel64_linear(dtype, a, p, s);      // (reads LinearArgs::m_live itself)
     case LIN_128_PF: case LIN_128_PERSIST: case LIN_128_GLDS: break;
     case LIN_QUADS_REFUSED:
       set_error("row-moment quads: %d x %d x %d does not run on big tiles", a.M, a.N, a.K);

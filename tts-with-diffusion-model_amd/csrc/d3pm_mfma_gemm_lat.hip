@@ -1,4 +1,5 @@
-// d3pm_mfma_gemm_lat.hip -- latency GEMM for one or two utterances (M <= 1536 rows): 64 x 64 tiles, whole-K panels.
+// d3pm_mfma_gemm_lat.hip -- latency GEMM for one or two utterances (M <= 1536 rows) and for the iterations of the deduplicated loop
+// that have as few live rows (LinearArgs::m_live / m_est): 64 x 64 tiles, whole-K panels.
 //
 //   Y[M][N] = epilogue(X[M][K] . W[N][K]^T + bias)      same contract and epilogue as d3pm_mfma_gemm.hip
 //
@@ -42,12 +43,12 @@ __device__ __forceinline__ int xcd_remap_lat(int bid, int nblocks) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-template <typename T, int EPI, int TM = 64, int TN = 64, bool DUAL = false>
-__global__ __launch_bounds__(256, 1) void gemm_mfma_panel64(const T* __restrict__ X, int ldx, const T* __restrict__ W,
-                                                            const T* __restrict__ bias, T* Y, int ldy, const T* R1,
-                                                            const T* R2, int ldr, const uint8_t* __restrict__ row_mask,
-                                                            int mask_period, int M, int N, int K, int n_tiles,
-                                                            EpiFold ef, const T* __restrict__ X2 = nullptr) {
+// one output tile (tile index `bid`: row tile bid / n_tiles, column tile bid % n_tiles) by the whole workgroup
+template <typename T, int EPI, int TM, int TN, bool DUAL>
+__device__ __forceinline__ void panel64_tile(const T* __restrict__ X, int ldx, const T* __restrict__ W, const T* __restrict__ bias, T* Y,
+                                             int ldy, const T* R1, const T* R2, int ldr, const uint8_t* __restrict__ row_mask,
+                                             int mask_period, int M, int N, int K, int n_tiles, const EpiFold& ef,
+                                             const T* __restrict__ X2, int bid) {
   using G = LatGeom<TM, TN>;
   static_assert(!DUAL || ((EPI & ~EPI_STATS) == EPI_R1 && TN == 64), "two products: whole tiles, K = 2 rounds, x' = (R1 + h) + y2");
   static_assert(TM % 32 == 0 && TN % 64 == 0, "four waves as 2 x 2, column blocks regrouped in pairs");
@@ -56,7 +57,6 @@ __global__ __launch_bounds__(256, 1) void gemm_mfma_panel64(const T* __restrict_
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int bid = xcd_remap_lat(blockIdx.x, gridDim.x);
   const int m0 = (bid / n_tiles) * TM, n0 = (bid % n_tiles) * TN;
   const uint32_t lds_base = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem));
   // DMA piece (sub-tile s, rows 8j .. 8j+7): a wave takes the pieces j = wave + 4 i of every sub-tile of both operands
@@ -188,6 +188,32 @@ __global__ __launch_bounds__(256, 1) void gemm_mfma_panel64(const T* __restrict_
                                                             n0 + wn * (TN / 2), lane, nullptr, &pre, &ef);
 }
 
+// Live row count from device memory (LinearArgs::m_live, or null): only the row tiles that hold a row below it run, never more than the
+// capacity's (M sizes every operand; rows behind the count inside the last live tile are computed like any row).  The grid is the
+// planner's ESTIMATE of the live tiles (LinearArgs::m_est; the capacity's without one), so a workgroup walks tile, tile + grid, ..:
+// more live rows than estimated cost further rounds, never a row.  A workgroup without a tile leaves in front of its first barrier.
+// The XCD ranges are those of the live total, as in the big-tile kernel.  Without a count the grid is the tile count and the walk
+// is one tile long.
+template <typename T, int EPI, int TM = 64, int TN = 64, bool DUAL = false>
+__global__ __launch_bounds__(256, 1) void gemm_mfma_panel64(const T* __restrict__ X, int ldx, const T* __restrict__ W,
+                                                            const T* __restrict__ bias, T* Y, int ldy, const T* R1,
+                                                            const T* R2, int ldr, const uint8_t* __restrict__ row_mask,
+                                                            int mask_period, int M, int N, int K, int n_tiles,
+                                                            EpiFold ef, const T* __restrict__ X2 = nullptr,
+                                                            const int* __restrict__ m_live = nullptr) {
+  const int m_tiles = (M + TM - 1) / TM;
+  const int live_tiles = (m_live ? max(min((*m_live + TM - 1) / TM, m_tiles), 0) : m_tiles) * n_tiles;
+  const int step = static_cast<int>(gridDim.x);
+  for (int vt = blockIdx.x; vt < live_tiles; vt += step) {      // block-uniform
+    panel64_tile<T, EPI, TM, TN, DUAL>(X, ldx, W, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, K, n_tiles, ef, X2,
+                                       xcd_remap_lat(vt, live_tiles));
+    if (vt + step < live_tiles) {      // a further round: the panels are reused
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();      // every wave has read its last fragments and its stores have left
+    }
+  }
+}
+
 }  // namespace
 
 // Which projections come here, with which of the three geometries: d3pm_plan.cpp (panel64_ok, panel64_geometry).
@@ -198,7 +224,7 @@ static int panel64_launch(const LinearArgs& a, const LinearPlan& p, hipStream_t 
   gemm_mfma_panel64<U, E, TM, TN><<<dim3(p.grid), dim3(256), p.lds, s>>>(
       static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
       static_cast<const U*>(a.R1), static_cast<const U*>(a.R2), a.ldr, a.row_mask, a.mask_period, a.M, a.N, a.K, p.n_tiles,
-      epi_fold_of(a));
+      epi_fold_of(a), nullptr, a.m_live);
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }
@@ -219,7 +245,7 @@ static int panel64_dual_launch(const LinearArgs& a, const void* X2, const Linear
   D3PM_LDS_ATTR((&gemm_mfma_panel64<U, E, 32, 64, true>), 2 * G::BUF + 2 * G::XOPER);
   gemm_mfma_panel64<U, E, 32, 64, true><<<dim3(p.grid), dim3(256), p.lds, s>>>(
       static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
-      static_cast<const U*>(a.R1), nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, p.n_tiles, ef, static_cast<const U*>(X2));
+      static_cast<const U*>(a.R1), nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, p.n_tiles, ef, static_cast<const U*>(X2), a.m_live);
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

@@ -3,6 +3,9 @@
 // attention instruction shape (16 x 16 x 32 or 32 x 32 x 16) does, which is why it follows the LOGICAL batch.
 #include "d3pm_plan.h"
 
+#include <cmath>
+#include <cstdint>
+
 namespace d3pm {
 namespace {
 
@@ -113,13 +116,17 @@ bool panel64_ok(int dtype, const LinearArgs& a) {
 // d3pm_tuning.lat_tile: 0 auto, 1 / 2 / 3 = always 64 x 64 / 96 x 64 / 32 x 64.  Auto: the geometry with the fewest rounds over the
 // CUs (one workgroup per CU), then the one with the most workgroups (the time of a launch here is the latency of one
 // workgroup's chain -- DMA flight, k-steps, epilogue -- so a round less or a shorter chain is what pays; flops do not matter)
+// the rows a panel64 launch is sized for: the capacity, or the estimate of the live rows below it (LinearArgs::m_est)
+inline int panel64_rows(const LinearArgs& a) { return a.m_est > 0 && a.m_est < a.M ? a.m_est : a.M; }
+
 int panel64_geometry(const LinearArgs& a) {
   const int lat_tile = tune_of(a.tune).lat_tile;
   if (lat_tile >= 1 && lat_tile <= 3) return lat_tile - 1;
+  const int rows = panel64_rows(a);
   int best = 0;
   long long best_rounds = 0, best_tiles = 0;
   for (int g = 0; g < 3; ++g) {
-    const long long tiles = static_cast<long long>((a.M + kPanelTm[g] - 1) / kPanelTm[g]) * ((a.N + 63) / 64), rounds = (tiles + kCUs - 1) / kCUs;
+    const long long tiles = static_cast<long long>((rows + kPanelTm[g] - 1) / kPanelTm[g]) * ((a.N + 63) / 64), rounds = (tiles + kCUs - 1) / kCUs;
     if (g == 0 || rounds < best_rounds || (rounds == best_rounds && tiles > best_tiles)) { best = g; best_rounds = rounds; best_tiles = tiles; }
   }
   return best;
@@ -129,7 +136,8 @@ LinearPlan panel64_plan(const LinearArgs& a, int geom, int epi, bool dual) {
   LinearPlan p;
   p.kernel = LIN_PANEL64; p.geom = geom; p.tm = kPanelTm[geom]; p.tn = 64; p.epi = epi;
   p.n_tiles = (a.N + 63) / 64; p.tiles_total = ((a.M + p.tm - 1) / p.tm) * p.n_tiles;
-  p.grid = static_cast<unsigned>(p.tiles_total);
+  // the grid covers the estimated live rows; the kernel walks tile, tile + grid, .. over the live tiles it reads from the device
+  p.grid = static_cast<unsigned>(((panel64_rows(a) + p.tm - 1) / p.tm) * p.n_tiles);
   p.lds = 2 * panel64_buf(p.tm) + (dual ? 2 * panel64_xoper(p.tm) : 0);      // dual: the second operand's panel rides in beside
   return p;
 }
@@ -178,6 +186,9 @@ LinearPlan plan_linear(int dtype, const LinearArgs& a, bool force_generic) {
   const int persist_slots = tn.gemm_persist_slots >= 8 ? (tn.gemm_persist_slots & ~7) : 4 * kCUs;
   const bool autosel = variant == 0 || (variant >= 6 && variant <= 8);
   const int epi = epi_of(a);
+  // an iteration of the deduplicated loop with few live rows: the latency family whatever the capacity (moments as parts: the loop
+  // chooses the format per iteration, d3pm_api.hip)
+  if (variant == 0 && live_latency(a.m_est) && !a.moment_quads && panel64_ok(dtype, a)) return panel64_plan(a, panel64_geometry(a), epi, false);
   if (autosel)
     if (const int id = big_tile(dtype, a, big_want(variant))) return big_plan(a, id, epi | (a.moment_quads ? EPI_QUADS : 0));
   if (a.moment_quads) {            // the quad format of the row moments exists in the big-tile epilogues only
@@ -215,7 +226,8 @@ CrossOutPlan plan_cross_out(int dtype, const LinearArgs& g, const void* X2, bool
   // whole 32 x 64 tiles, K = 512 (both operand panels and the weight panel resident: 128 KiB)
   // (g.moment_quads is not looked at, as it never was: this form writes parts, and fold_plan, which asks in the parts format, answers
   // FOLD_PARTS whenever it is chosen -- d3pm_api.hip FoldPlanner::dual)
-  if ((tn.row_panel & 8) && tn.gemm_variant == 0 && panel64_ok(dtype, g) && g.K == 2 * KC && g.M % 32 == 0 && g.N % 64 == 0 && g.M <= 2048) {
+  if ((tn.row_panel & 8) && tn.gemm_variant == 0 && panel64_ok(dtype, g) && g.K == 2 * KC && g.M % 32 == 0 && g.N % 64 == 0 &&
+      (g.M <= 2048 || live_latency(g.m_est))) {
     c.form = CROSS_OUT_PANEL64_DUAL;
     c.dual = panel64_plan(g, 2, EPI_R1 | (g.stats_out ? EPI_STATS : 0), true);
     return c;
@@ -231,6 +243,33 @@ CrossOutPlan plan_cross_out(int dtype, const LinearArgs& g, const void* X2, bool
   }
   return c;      // two launches: o_text -> ws.h, then o_prompt with R1 = x, R2 = h
 }
+
+// ---- the live rows of a deduplicated iteration ----
+int plan_live_rows(int batch, int canvas, float cbar_t) {
+  const float revealed = static_cast<float>(canvas) * (1.0f - cbar_t);
+  long long per_utt = 2 + static_cast<long long>(std::ceil(revealed > 0.f ? revealed : 0.f));
+  if (per_utt > canvas) per_utt = canvas;
+  const long long rows = static_cast<long long>(batch) * per_utt;
+  return rows > INT32_MAX ? INT32_MAX : static_cast<int>(rows);
+}
+
+// R, the largest estimate that takes the latency launch list: measured, not derived (profiles/round19_live_regime_ab_interleaved.txt).
+// Interleaved arms of the 32 x 750-frame bf16 loop over library builds that differ in this constant alone (tools/build_variant.py), ms
+// per step: R = 1536 (the planner's few_rows bound) 120.1, 3072 118.8, 4608 118.3, 6144 118.4 against the parent's 125.9 on one box;
+// 4608 116.4, 6144 116.6, 7680 118.0, 9216 119.0, 12288 122.6 against 124.0 on another.  The step time is flat from 3072 to 6144,
+// so the bound comes from the kernel trace of the R = 4608 build: an iteration's kernels take 890 us against the parent's 956 at
+// t = 75 (estimate 3520), 995 against 983 at t = 73 (4064: break-even) and 1040 against 979 at t = 72 (4352: a loss; fc1 on 96 x 64
+// tiles 29.6 us against 18.8 on big tiles, QKV 20.9 against 12.3, while fc2 still wins with 25.4 against 31.9).  3840 lies between
+// the estimates of t = 74 (3776), the last iteration that gains, and of t = 73.  The estimate runs a quarter or more above the live rows of that loop (duplicates among
+// the revealed frames: 3520 estimated, about 2794 live at t = 75), so in live rows the crossover lies near 3000: below it an
+// iteration is the latency of its launches, which one flight of whole-K panels cuts; above it 64-column tiles re-read the weight
+// panel once per 32 .. 96 rows and lose to the 192-row tiles.  A bound on the low side of the flat stretch also costs a caller whose
+// canvas holds more distinct ids than a reverse process would (further rounds in every launch) the least.  (A compile-time constant so
+// that A/B builds can move it; it is no tuning field.)
+#ifndef D3PM_LIVE_LATENCY_ROWS
+#define D3PM_LIVE_LATENCY_ROWS 3840
+#endif
+int live_latency_rows() { return D3PM_LIVE_LATENCY_ROWS; }
 
 // ---- attention ----
 namespace {

@@ -41,6 +41,15 @@ struct LinearPlan {
 };
 LinearPlan plan_linear(int dtype, const LinearArgs& a, bool force_generic = false);
 
+// ---- the live rows of an iteration of the deduplicated loop, bounded on the host (the loop is graph-captured: no read-back) ----
+// batch * min(canvas, 2 + ceil(canvas * (1 - cbar_t))): the revealed frames of an utterance in expectation (each at most one class of
+// its own) plus the mask class and the padded one.  cbar_t = float(cbar[t]) of the schedule for the iteration that evaluates x_t.
+int plan_live_rows(int batch, int canvas, float cbar_t);
+// the regime rule: an iteration whose estimate is at most live_latency_rows() takes the latency launch list (every projection of a block
+// on gemm_mfma_panel64, moments as parts); LinearArgs::m_est carries the estimate to plan_linear / plan_cross_out.  0 = no estimate.
+int live_latency_rows();
+inline bool live_latency(int m_est) { return m_est > 0 && m_est <= live_latency_rows(); }
+
 // the instantiated epilogues of each family (the switch of its launcher has exactly these cases), 0-terminated after the first entry
 extern const int kEpi128[], kEpiBig[], kEpiPanel64[], kEpiBigDual[], kEpiPanel64Dual[];
 bool epi_listed(const int* table, int epi);
