@@ -793,7 +793,8 @@ int d3pm_op_linear_fold(int dtype, const void *X, int ldx, const void *Wf, const
  * [batch * canvas] hold the class and the frame-mask byte of compact row r < the next multiple of 384 of m_live (n_classes / 0 on rows
  * no class owns).  With `table` [n_classes][d]: x [batch * canvas][d] receives the embedding rows of the compact rows (zeros on padded
  * or unowned rows) and stats their moments (quads when d = 512, else parts).  scratch: int32 [batch * canvas + batch].  canvas must be a
- * multiple of 128 and batch * canvas of 384, n_classes at most 4095. */
+ * multiple of 128 and batch * canvas of 384, n_classes at most 4095, batch at most 12283 (the embedding launch keeps the prefix of the
+ * counts in 48 KiB of LDS); D3PM_E_SHAPE otherwise, nothing launched. */
 int d3pm_op_dedup_index(int dtype, const int32_t *tokens, const uint8_t *frame_mask, int batch, int canvas, int n_classes, int d,
                         const void *table, int32_t *seg_start, int32_t *seg_len, int32_t *m_live, int32_t *row_of, int32_t *cid,
                         uint8_t *cmask, void *x, float *stats, int32_t *scratch, void *stream);

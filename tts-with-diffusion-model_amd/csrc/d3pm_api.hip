@@ -1268,7 +1268,7 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   const int n_rows = eval_batch * sh->canvas;
   const int ln_fold = tune_of(sh->tuning).ln_fold;
   if (q.qkv_table && plan == FOLD_QUADS && (ln_fold == 1 || ln_fold == 4) && !f8 && !guide && ws.dd.row_of && n_rows % 384 == 0 && sh->n_layers <= 16 &&
-      sh->n_classes <= kDedupMaxClasses && ws.h2 == at(ws.h, static_cast<size_t>(n_rows) * sh->d_model, dtype_size(sh->dtype))) {
+      sh->n_classes <= kDedupMaxClasses && eval_batch <= kDedupMaxBatch && ws.h2 == at(ws.h, static_cast<size_t>(n_rows) * sh->d_model, dtype_size(sh->dtype))) {
     DedupPlanner dp{sh->dtype, sh->tuning, true};
     for (int l = 0; l < sh->n_layers; ++l) (void)folded_block(q, l, true, dp, l == 0);
     LinearArgs fin = projection(ws.x, w->final_w, w->final_b, ws.logits, n_rows, sh->n_classes, sh->d_model);

@@ -247,6 +247,7 @@ struct DedupArgs {
   void* zero[2] = {nullptr, nullptr};
 };
 constexpr int kDedupMaxClasses = 4095;      // classes + the padded one fit the index kernel's LDS table
+constexpr int kDedupMaxBatch = 12 * 1024 - 5;      // the embedding launch's prefix of the counts (batch + 1 ints) and four wave sums fit 48 KiB of LDS
 int dedup_index(int dtype, const DedupArgs& a, hipStream_t s);      // two launches: per-utterance index, then segments + embedding
 // the sampler launch of the deduplicated loop: row r reads logits[row_of[r]]; with n.Wf set, the workgroups behind the sampler's fold
 // fc1 of every block for the next timestep (NextIterPrep; nothing is embedded here)
