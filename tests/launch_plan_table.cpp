@@ -1,11 +1,18 @@
-// launch_plan_table.cpp -- prints the launch planner's choices (csrc/d3pm_plan.cpp) for tests/test_launch_plan_api.py.
-// Host only: compiled with `hipcc -x hip --cuda-host-only` together with d3pm_plan.cpp, it needs no device and no HIP runtime.
+// launch_plan_table.cpp -- prints the launch planner's choices (csrc/d3pm_plan.cpp), the launches of a folded block and the plan of a
+// sampler loop (csrc/d3pm_sequence.{h,cpp}) for tests/test_launch_plan_api.py.
+// Host only: compiled with `hipcc -x hip --cuda-host-only` and linked with d3pm_plan.cpp, d3pm_sequence.cpp and d3pm_schedule.cpp, it
+// needs no device and no HIP runtime, and defines no function of the library itself.
 // One `key=value ...` line per case; the sweep at the end checks properties of every plan itself and prints what it saw.
+#include <sys/mman.h>
+
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <set>
 #include <tuple>
+#include <vector>
 
-#include "d3pm_plan.h"
+#include "d3pm_sequence.h"
 
 using namespace d3pm;
 
@@ -60,28 +67,187 @@ static void linear_case(const char* name, int M, int N, int K, int epi = 0, cons
   print_linear(name, a, plan_linear(D3PM_BF16, a));
 }
 
-// the six moment-touching launches of folded_block (d3pm_api.hip) at n rows, d = 512, as the fold planner asks them (parts format)
-static void fold_cases(int B) {
-  const int n = B * 768, d = 512;
-  char name[64];
-  auto one = [&](const char* what, int N, int K, int epi) {
-    std::snprintf(name, sizeof name, "fold_%s/%d", what, B);
-    linear_case(name, n, N, K, epi);
-  };
-  one("qkv", 3 * d, d, EPI_LNF);
-  one("out", d, d, EPI_R1 | EPI_STATS);
-  one("q2", 2 * d, d, EPI_LNF);
-  const LinearArgs g = linear_args(n, d, d, EPI_R1 | EPI_STATS, nullptr);
-  const CrossOutPlan c = plan_cross_out(D3PM_BF16, g, g_buf, false, true);
-  std::snprintf(name, sizeof name, "fold_cross/%d", B);
-  if (c.form != CROSS_OUT_TWO_LAUNCHES) print_linear(name, g, c.dual);
-  else linear_case(name, n, d, d, EPI_R2 | EPI_STATS);      // the second of the two launches writes the moments
-  std::printf("cross case=%d form=%d\n", B, c.form);
-  one("fc1", 4 * d, d, EPI_LNF | EPI_GELU);
-  one("fc2", d, 4 * d, EPI_R1 | EPI_MASK | EPI_STATS);
+static d3pm_tuning default_tuning() { return tune_of(nullptr); }
+
+// ---- the launch sequence and the loop plan (csrc/d3pm_sequence.h), walked as the library walks them ----
+// address space that is never touched: the workspace carve() is run over, and 256-byte aligned stand-ins for the weights
+static char* reserve(size_t bytes) {
+  void* p = mmap(nullptr, bytes, PROT_NONE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+  if (p == MAP_FAILED) { std::perror("mmap"); std::exit(1); }
+  return static_cast<char*>(p);
+}
+static const void* fake_weight() {
+  static char* pool = reserve(1 << 20);
+  static size_t used = 0;
+  used += 256;
+  return pool + used;
 }
 
-static d3pm_tuning default_tuning() { return tune_of(nullptr); }
+// the d = 512, 8-head, 6-layer, 768-frame, 50 + 225-key, 1025-class bf16 model with `batch` utterances per evaluation
+struct Model {
+  d3pm_tuning tn = default_tuning();
+  d3pm_shape sh{};
+  d3pm_block_weights blocks[6];
+  d3pm_fold_block fold[6];
+  d3pm_weights w{};
+  Workspace ws{};
+  int batch;
+  const void *kv_text, *kv_prompt;
+  const uint8_t* mask;
+  Model(int batch_, int n_q = 1, int ln_fold = 1, int regime_batch = 0) : batch(batch_) {
+    tn.ln_fold = ln_fold; tn.regime_batch = regime_batch;
+    sh.d_model = 512; sh.n_heads = 8; sh.n_layers = 6; sh.canvas = 768; sh.s_text = 50; sh.s_prompt = 225; sh.n_classes = 1025; sh.mask_id = 1024;
+    sh.timesteps = 100; sh.dtype = D3PM_BF16; sh.n_q = n_q; sh.tuning = &tn;
+    for (auto& b : blocks) {      // (a struct of pointers and nothing else)
+      const void** p = reinterpret_cast<const void**>(&b);
+      for (size_t i = 0; i < sizeof b / sizeof *p; ++i) p[i] = fake_weight();
+    }
+    for (auto& f : fold) {
+      f.qkv_w = fake_weight(); f.q2_w = fake_weight();
+      f.qkv_s = static_cast<const float*>(fake_weight()); f.qkv_b = static_cast<const float*>(fake_weight());
+      f.q2_s = static_cast<const float*>(fake_weight()); f.q2_b = static_cast<const float*>(fake_weight());
+    }
+    w.resps_emb = fake_weight(); w.time_emb = fake_weight(); w.final_w = fake_weight(); w.final_b = fake_weight(); w.blocks = blocks; w.fold = fold;
+    ws = carve(sh, batch, reserve(carve(sh, batch, nullptr).total));
+    const size_t kv = static_cast<size_t>(sh.n_layers) * batch * 2 * sh.d_model * 2;
+    kv_text = reserve(kv * sh.s_text); kv_prompt = reserve(kv * sh.s_prompt);
+    mask = reinterpret_cast<const uint8_t*>(reserve(sh.canvas));
+  }
+  DenoiserArgs args(int token_rows = 0) const { return DenoiserArgs{sh, w, batch, mask, sh.canvas, kv_text, kv_prompt, ws, KeyCounts{}, token_rows}; }
+};
+
+// a visitor of folded_block that plans each launch as the library's launcher does (the caller's tuning, no forced family) and keeps it
+struct Step {
+  char kind;      // 'L' projection, 'D' dual out-projection, 'A' attention
+  LinearArgs g; LinearPlan lp; int form;
+  AttnArgs a; AttnPlan ap;
+};
+struct Recorder {
+  int dt; const d3pm_tuning* tune;
+  std::vector<Step> steps;
+  int linear(LinearArgs g) {
+    g.tune = tune;
+    steps.push_back(Step{'L', g, plan_linear(dt, g), 0, AttnArgs{}, AttnPlan{}});
+    return D3PM_OK;
+  }
+  int attention(AttnArgs a) {
+    a.tune = tune;
+    steps.push_back(Step{'A', LinearArgs{}, LinearPlan{}, 0, a, plan_attention(dt, a)});
+    return D3PM_OK;
+  }
+  int dual(const CrossOutPlan& c, const LinearArgs& g, const void*) {
+    steps.push_back(Step{'D', g, c.dual, c.form, AttnArgs{}, AttnPlan{}});
+    return D3PM_OK;
+  }
+};
+// a recorded launch by the workspace regions it reads and writes
+static const char* step_name(const Step& s, const Workspace& ws) {
+  if (s.kind == 'A') return s.a.Q2 ? "cross_attn" : "self_attn";
+  if (s.kind == 'D') return "cross";
+  if (s.g.Y == ws.h) return "cross_text";                            // o_text of the two-launch form: no moments
+  if (s.g.fold_s) return s.g.act == ACT_GELU ? "fc1" : s.g.N == 3 * s.g.K ? "qkv" : "q2";
+  return s.g.X == ws.mlp ? "fc2" : s.g.X == ws.att2 ? "cross" : "out";
+}
+static std::vector<Step> walk_block(const Model& m, const DenoiserArgs& q, int l, bool quads, bool qkv_ready) {
+  Recorder r{m.sh.dtype, m.sh.tuning, {}};
+  if (folded_block(q, l, quads, r, qkv_ready) != D3PM_OK) std::exit(1);
+  return r.steps;
+}
+
+// the moment-touching launches of block 1 as fold_plan asks them (parts format, every row), under the names they have always had here
+static void fold_cases(int B) {
+  const Model m(B);
+  char name[64];
+  for (const Step& s : walk_block(m, m.args(), 1, false, false)) {
+    if (s.kind == 'A' || (!s.g.fold_s && !s.g.stats_out)) continue;
+    const char* what = step_name(s, m.ws);
+    std::snprintf(name, sizeof name, "fold_%s/%d", what, B);
+    print_linear(name, s.g, s.lp);
+    if (!std::strcmp(what, "cross")) std::printf("cross case=%d form=%d\n", B, s.form);      // (of two launches, the one that writes the moments)
+  }
+}
+
+// every launch of blocks 0 and 1, and the launch count of every block, of an evaluation whose DenoiserArgs are `q`
+static void block_cases(const char* name, const Model& m, const DenoiserArgs& q, bool quads) {
+  for (int l = 0; l < m.sh.n_layers; ++l) {
+    const std::vector<Step> steps = walk_block(m, q, l, quads, q.qkv_table != nullptr);
+    std::printf("block case=%s l=%d launches=%zu\n", name, l, steps.size());
+    for (size_t i = 0; l < 2 && i < steps.size(); ++i) {
+      const Step& s = steps[i];
+      if (s.kind == 'A')
+        std::printf("step case=%s l=%d i=%zu name=%s kind=attn kernel=%s segments=%d gather=%d\n", name, l, i, step_name(s, m.ws), attn_name(s.ap.kernel),
+                    s.a.seg_len ? 1 : 0, s.a.key_row ? 1 : 0);
+      else
+        std::printf("step case=%s l=%d i=%zu name=%s kind=%s kernel=%s tile=%dx%d epi=%d form=%d live=%d\n", name, l, i, step_name(s, m.ws),
+                    s.kind == 'D' ? "dual" : "linear", linear_name(s.lp.kernel), s.lp.tm, s.lp.tn, s.lp.epi, s.form, s.g.m_live ? 1 : 0);
+    }
+  }
+}
+
+struct Schedule {
+  uint16_t betas[101], d[100], c[100], dbar[100], cbar[100];
+  d3pm_schedule s{100, d, c, dbar, cbar};
+  Schedule() { if (d3pm_schedule_build(100, betas, d, c, dbar, cbar) != D3PM_OK) std::exit(1); }
+};
+
+static LoopCall full_loop() {
+  LoopCall c;
+  c.t_start = 99; c.t_stop = 0;
+  return c;
+}
+// the plan of a call, and its latency iterations
+static LoopPlan plan_case(const char* name, const DenoiserArgs& q, uint32_t flags, const LoopCall& call, const Schedule& sched) {
+  const LoopPlan p = loop_plan(q, flags, call);
+  int first = -1, last = -1, count = 0;
+  for (int t = call.t_start; t > call.t_stop; --t)
+    if (p.m_est(&sched.s, t)) { if (first < 0) first = t; last = t; ++count; }
+  std::printf("plan case=%s fold=%d table=%d dedup=%d latency=%d first=%d last=%d count=%d\n", name, p.fold, p.table ? 1 : 0, p.dedup ? 1 : 0,
+              p.latency ? 1 : 0, first, last, count);
+  return p;
+}
+static void sequence_cases() {
+  const Schedule sched;
+  char name[64];
+  for (int B : {2, 8, 16, 32}) {
+    const Model m(B);
+    DenoiserArgs q = m.args();
+    std::snprintf(name, sizeof name, "b%d", B);
+    const LoopPlan p = plan_case(name, q, 0, full_loop(), sched);
+    if (p.table) q.qkv_table = m.ws.tab_qkv;
+    if (p.dedup) q.dd = &m.ws.dd;
+    block_cases(name, m, q, p.fold == FOLD_QUADS);
+    if (!p.dedup) continue;
+    q.m_est = 64;      // a latency iteration: moments as parts
+    std::snprintf(name, sizeof name, "lat%d", B);
+    block_cases(name, m, q, false);
+  }
+  for (int ln_fold : {4, 3, 2, 0}) {
+    const Model m(32, 1, ln_fold);
+    std::snprintf(name, sizeof name, "ln_fold%d", ln_fold);
+    plan_case(name, m.args(), 0, full_loop(), sched);
+  }
+  const Model m(32);
+  const LoopPlan p32 = loop_plan(m.args(), 0, full_loop());
+  for (int t : {74, 73})
+    std::printf("est case=b32 t=%d rows=%d m_est=%d\n", t, plan_live_rows(32, 768, host_h2f(sched.cbar[t])), p32.m_est(&sched.s, t));
+  LoopCall call = full_loop();
+  call.fp8 = true;
+  plan_case("fp8", m.args(), 0, call, sched);
+  plan_case("force_generic", m.args(), D3PM_FLAG_FORCE_GENERIC, full_loop(), sched);
+  call = full_loop();
+  call.known = true;
+  plan_case("known", m.args(), 0, call, sched);
+  call = full_loop();
+  call.t_stop = 98;
+  plan_case("one_iteration", m.args(), 0, call, sched);
+  // guided: the evaluation of 2 x 32 utterances under regime_batch = 64, x_t with a row per pair
+  const Model g(64, 1, 1, 64);
+  call = full_loop();
+  call.guided = true;
+  plan_case("guided", g.args(32 * 768), 0, call, sched);
+  const Model q8(32, 8);
+  plan_case("n_q8", q8.args(), 0, full_loop(), sched);
+}
 
 static void attn_case(const char* name, int B, bool cross, const d3pm_tuning& tn, bool key_len = false, bool keeps = false) {
   AttnArgs a;
@@ -209,6 +375,7 @@ int main() {
   linear_case("out_rows32", 32, 512, 512);
   linear_case("native_qkv", 448, 96, 32);
   for (int B : {8, 10, 11, 16, 32}) fold_cases(B);
+  sequence_cases();
 
   d3pm_tuning tn = default_tuning();
   for (int B : {10, 11, 32}) attn_case("self", B, false, tn);

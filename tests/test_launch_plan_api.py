@@ -30,11 +30,21 @@ def table(tmp_path_factory):
     plan_o, main_o, exe = (str(tmp / n) for n in ("d3pm_plan.o", "launch_plan_table.o", "launch_plan_table"))
     subprocess.run(HOST_ONLY + ["-c", os.path.join(CSRC, "d3pm_plan.cpp"), "-o", plan_o], check=True, timeout=600)
     subprocess.run(HOST_ONLY + ["-c", os.path.join(ROOT, "tests", "launch_plan_table.cpp"), "-o", main_o], check=True, timeout=600)
+    # the program walks the real launch sequence and loop plan: the two other host-only units of the library are linked with it, named
+    # to the linker in a response file beside the program's own object
+    program_o, unit_o = main_o, [str(tmp / n) for n in ("d3pm_sequence.o", "d3pm_schedule.o")]
+    for obj in unit_o:
+        subprocess.run(HOST_ONLY + ["-c", os.path.join(CSRC, os.path.basename(obj)[:-2] + ".cpp"), "-o", obj], check=True, timeout=600)
+    (tmp / "objects.rsp").write_text("\n".join(f'"{o}"' for o in [program_o] + unit_o))
+    main_o = "@" + str(tmp / "objects.rsp")
     subprocess.run([HIPCC, plan_o, main_o, "-o", exe], check=True, timeout=600)
     out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=600).stdout
     nm = shutil.which("nm") or os.path.join(os.path.dirname(os.path.realpath(HIPCC)), "..", "lib", "llvm", "bin", "llvm-nm")
     t = {"linear": {}, "attn": {}, "cross": {}, "seen": set(), "violations": [], "sweep": None,
          "symbols": subprocess.run([nm, plan_o], check=True, capture_output=True, text=True).stdout}
+    t.update({"sequence_symbols": subprocess.run([nm, unit_o[0]], check=True, capture_output=True, text=True).stdout,
+              "program_symbols": subprocess.run([nm, program_o], check=True, capture_output=True, text=True).stdout,
+              "block": {}, "step": {}, "plan": {}, "est": {}})
     for line in out.splitlines():
         kind, f = line.split()[0], _fields(line)
         if kind == "linear":
@@ -49,6 +59,14 @@ def table(tmp_path_factory):
             t["violations"].append(line)
         elif kind == "sweep":
             t["sweep"] = {k: int(v) for k, v in f.items()}
+        elif kind == "block":
+            t["block"][(f["case"], int(f["l"]))] = int(f["launches"])
+        elif kind == "step":
+            t["step"].setdefault((f["case"], int(f["l"])), []).append(f)
+        elif kind == "plan":
+            t["plan"][f["case"]] = {k: int(v) for k, v in f.items() if k != "case"}
+        elif kind == "est":
+            t["est"][int(f["t"])] = (int(f["rows"]), int(f["m_est"]))
     return t
 
 
@@ -58,6 +76,16 @@ def test_the_planner_holds_no_kernel(table):
     src = open(os.path.join(CSRC, "d3pm_plan.cpp")).read() + open(os.path.join(CSRC, "d3pm_plan.h")).read()
     src = re.sub(r"//[^\n]*", "", src)      # the comments may speak of launches
     assert "__global__" not in src and "<<<" not in src and not re.search(r"\bhip[A-Z]\w*\(", src)
+    # ... and the same three checks for the launch sequence and the loop plan (csrc/d3pm_sequence.{h,cpp})
+    assert "__hip_fatbin" not in table["sequence_symbols"] and "__hipRegister" not in table["sequence_symbols"]
+    src = open(os.path.join(CSRC, "d3pm_sequence.cpp")).read() + open(os.path.join(CSRC, "d3pm_sequence.h")).read()
+    src = re.sub(r"//[^\n]*", "", src)
+    assert "__global__" not in src and "<<<" not in src and not re.search(r"\bhip[A-Z]\w*\(", src)
+    # the program that walks them defines no function of the library (namespace d3pm, or the C ABI) itself: it would test a copy
+    defined = [ln.split()[-1] for ln in table["program_symbols"].splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TW"]
+    assert "main" in defined and not [s for s in defined if s.startswith("d3pm_")], defined
+    ours = ("carve", "fold_plan", "loop_plan", "fold_features", "plan_linear", "plan_attention", "plan_cross_out", "set_error")
+    assert not [s for s in defined if any(f"4d3pm{len(n)}{n}" in s for n in ours)], defined
 
 
 BIG, GLDS = "big 192x128", "128glds 128x128"
@@ -167,3 +195,105 @@ def test_every_plan_of_the_sweep_is_a_case_of_its_launcher(table):
         assert seen[k] == cases[k], (k, sorted(cases[k] - seen[k]))      # and the sweep reached every instantiated epilogue
     assert {g for fam, _, g in table["seen"] if fam == 1} == {1, 2, 3} and {g for fam, _, g in table["seen"] if fam == 2} == {0, 1, 2}
     assert {g for fam, _, g in table["seen"] if fam == 3} == {2, 3} and {g for fam, _, g in table["seen"] if fam == 4} == {2}
+
+
+# ---- the launches of a folded block and the plan of a sampler loop (csrc/d3pm_sequence.{h,cpp}), walked by the program ----
+# d = 512, 8 heads, 6 layers, 768 frames, 50 + 225 condition keys, 1025 classes, bf16, default tuning, the 100-step schedule
+FOLD_NONE, FOLD_PARTS, FOLD_QUADS = 0, 1, 2
+PROJECTIONS = ("qkv", "out", "q2", "fc1", "fc2")
+
+
+def _block(table, case, l):
+    steps = table["step"][(case, l)]
+    assert len(steps) == table["block"][(case, l)] and [int(s["i"]) for s in steps] == list(range(len(steps)))
+    return {s["name"]: s for s in steps}, [s["name"] for s in steps]
+
+
+@pytest.mark.parametrize("utterances,per_block", [(2, 8), (8, 9), (16, 8), (32, 8)])
+def test_launches_of_a_block(table, utterances, per_block):
+    """folded_block as the loop launches it: block 0 reads its QKV rows from the table (one launch fewer), every other block projects."""
+    case = f"b{utterances}"
+    assert [table["block"][(case, l)] for l in range(6)] == [per_block - 1] + [per_block] * 5
+    first, order0 = _block(table, case, 0)
+    by_name, order = _block(table, case, 1)
+    print(case, order)
+    assert order[0] == "qkv" and order0 == order[1:] and "qkv" not in first
+    cross = by_name["cross"]
+    if utterances == 2:
+        assert all(by_name[n]["kernel"] == "panel64" for n in PROJECTIONS)
+        assert (cross["kind"], cross["kernel"], cross["form"]) == ("dual", "panel64", "1")
+    elif utterances == 8:
+        # two launches: o_text onto ws.h with no epilogue bit, then o_prompt + x + h with the moments
+        text = by_name["cross_text"]
+        assert (text["kind"], text["epi"]) == ("linear", "0") and order.index("cross_text") + 1 == order.index("cross")
+        assert (cross["kind"], int(cross["epi"])) == ("linear", EPI["EPI_R2"] | EPI["EPI_STATS"])
+    else:
+        for n in PROJECTIONS:
+            assert (by_name[n]["kernel"], by_name[n]["tile"]) == ("big", "192x128") and int(by_name[n]["epi"]) & EPI["EPI_QUADS"], n
+        assert (cross["kind"], cross["kernel"], cross["tile"], cross["form"]) == ("dual", "big", "192x128", "2")
+        assert int(cross["epi"]) & EPI["EPI_QUADS"]
+
+
+def test_one_iteration_is_49_launches(table):
+    """6 blocks of 8 launches, block 0 without its QKV projection, the final projection and the sampler launch."""
+    assert sum(table["block"][("b32", l)] for l in range(6)) + 1 + 1 == 49
+
+
+@pytest.mark.parametrize("utterances", [16, 32])
+def test_latency_launch_list(table, utterances):
+    """With the dedup index set and an estimate of 64 live rows: every projection on the 32 x 64 panel64 tile, the panel64 dual, and
+    the two attention kernels of the deduplicated loop."""
+    for l in (0, 1):
+        by_name, order = _block(table, f"lat{utterances}", l)
+        for n in PROJECTIONS[1 if l == 0 else 0:]:
+            assert (by_name[n]["kernel"], by_name[n]["tile"], by_name[n]["live"]) == ("panel64", "32x64", "1"), (l, n)
+        cross = by_name["cross"]
+        assert (cross["kind"], cross["kernel"], cross["form"]) == ("dual", "panel64", "1")      # CROSS_OUT_PANEL64_DUAL
+        assert (by_name["self_attn"]["kernel"], by_name["self_attn"]["segments"], by_name["self_attn"]["gather"]) == ("attn32p_hd64", "1", "1")
+        assert (by_name["cross_attn"]["kernel"], by_name["cross_attn"]["segments"]) == ("attn32_cross_hd64", "1")
+
+
+def _plan(fold, table, dedup, latency=None):
+    first, last = latency if latency else (-1, -1)
+    return dict(fold=fold, table=int(table), dedup=int(dedup), latency=int(latency is not None), first=first, last=last,
+                count=first - last + 1 if latency else 0)
+
+
+LOOP_PLANS = {
+    "b32": _plan(FOLD_QUADS, True, True, (99, 74)),      # exactly 26 latency iterations
+    "b16": _plan(FOLD_QUADS, True, True, (99, 62)),      # exactly 38
+    "b8": _plan(FOLD_PARTS, True, False),
+    "b2": _plan(FOLD_PARTS, True, False),
+    # 32 utterances otherwise
+    "ln_fold4": _plan(FOLD_QUADS, True, True),
+    "ln_fold3": _plan(FOLD_QUADS, True, False),
+    "ln_fold2": _plan(FOLD_QUADS, False, False),
+    "ln_fold0": _plan(FOLD_NONE, False, False),
+    "fp8": _plan(FOLD_NONE, False, False),
+    "force_generic": _plan(FOLD_NONE, False, False),
+    "known": _plan(FOLD_QUADS, True, True),
+    "guided": _plan(FOLD_QUADS, False, False),
+    "n_q8": _plan(FOLD_QUADS, False, False),
+    "one_iteration": _plan(FOLD_QUADS, False, False),
+}
+
+
+@pytest.mark.parametrize("case", sorted(LOOP_PLANS))
+def test_loop_plan(table, case):
+    print(case, table["plan"][case])
+    assert table["plan"][case] == LOOP_PLANS[case]
+    assert LOOP_PLANS["b32"]["count"] == 26 and LOOP_PLANS["b16"]["count"] == 38
+
+
+def test_live_row_estimates_at_the_switch(table):
+    """The numbers of d3pm_plan.cpp's comment on D3PM_LIVE_LATENCY_ROWS: t = 74 is the last latency iteration of 32 utterances."""
+    assert table["est"][74] == (3776, 3776) and table["est"][73] == (4064, 0)
+
+
+def test_ln_fold_codes_are_read_in_one_function():
+    """The integer codes of d3pm_tuning.ln_fold are compared with a number in fold_features (d3pm_plan.cpp) and nowhere else."""
+    hits = {}
+    for name in sorted(os.listdir(CSRC)):
+        for m in re.finditer(r"ln_fold\s*(==|!=)\s*[0-9]", re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, name)).read())):
+            hits.setdefault(name, []).append(m.group(0))
+    assert list(hits) == ["d3pm_plan.cpp"] and len(hits["d3pm_plan.cpp"]) == 5, hits

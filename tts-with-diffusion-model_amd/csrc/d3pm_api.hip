@@ -1,33 +1,24 @@
-// d3pm_api.hip -- extern "C" entry points (include/d3pm_hip.h) and the per-step launch sequence.
+// d3pm_api.hip -- extern "C" entry points (include/d3pm_hip.h) and everything that enqueues a launch.
 //
 // One denoiser evaluation = the loop body of AR.generate_audio (ar_discrete.py:752-776):
 //   embed -> n_layers x { LN1, QKV GEMM, self-attention, out GEMM(+res), LN2/LN22, 2 x Q GEMM,
 //   2 x cross-attention against the cached condition K/V, 2 x out GEMM(+res), LN3+FiLM,
 //   fc1 GEMM(+GELU), fc2 GEMM(+res, *mask) } -> final GEMM -> posterior/sample.
+// The workspace, the argument builders, the launches of a folded block (folded_block) and what a call decides before it loops
+// (loop_plan) are host-only code in d3pm_sequence.{h,cpp}; which kernel a launch runs on is d3pm_plan.{h,cpp}.
 // Nothing here allocates or synchronises; everything is enqueued on the caller's stream.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <new>
 #include <vector>
 
-#include "d3pm_plan.h"
+#include "d3pm_sequence.h"
 
 namespace d3pm {
-
-static thread_local char g_err[512] = "";
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
 
 int q_sample_launch(const d3pm_shape*, int, const int32_t*, int32_t*, const uint8_t*, int, const d3pm_schedule*,
                     uint64_t, uint32_t, hipStream_t);
 int uniform_launch(uint64_t, int, uint32_t, int, int, int, float*, hipStream_t);
 int ce_loss_launch(int, const void*, int, const int32_t*, const uint8_t*, int, int, int, float*, hipStream_t);
-float host_h2f(uint16_t h);
 
 }  // namespace d3pm
 
@@ -127,81 +118,6 @@ static int run_layernorm(const Ctx& cx, int dtype, const LayerNormArgs& a, uint3
   return generic_layernorm(dtype, a, s);
 }
 
-// ---- workspace carve-up ----------------------------------------------------------------------
-struct Workspace {
-  char *x, *h, *h2, *qkv, *att, *att2, *mlp, *logits;
-  float* stats;       // [n][d / 32][2] row moments of the residual stream (LayerNorm folded into the projections, d3pm_mfma_tile.h)
-  char* fc1f;         // [L][4d][d] fc1 under norm3 + FiLM(t), rebuilt per evaluation (d3pm_fold.hip); then fp32 [L][4d] s and b'
-  float *fc1f_s, *fc1f_b;
-  // block-0 QKV from a per-id table (build_qkv_table; folded path, n_q = 1): the table's input rows [qkv_table_rows][d], their moments
-  // (parts), the table [qkv_table_rows][3d], and the q rows [n][d] and k | v rows [n][2d] of block 0 of the next evaluation
-  char *tab_x, *tab_qkv, *q0, *kv0;
-  float* tab_stats;
-  uint8_t* mxs;       // fp8 fast path: block scales [2n][d / 32] of the LayerNorm rows (a slot of their own: nothing else ever lives here)
-  // row deduplication (d3pm_dedup.hip; never together with fp8): its index arrays live in the mxs slot, all null when they do not fit
-  DedupIndex dd;
-  size_t total;
-};
-static size_t align256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
-// internal logits rows are padded to a multiple of 8 elements (16-B aligned rows for vector stores/loads)
-static int logits_ld(const d3pm_shape& sh) { return (sh.n_classes + 7) & ~7; }
-// quantizer levels generated jointly (d3pm_shape.n_q; 0 and 1 = the upstream level-0 path)
-static int levels(const d3pm_shape& sh) { return sh.n_q > 1 ? sh.n_q : 1; }
-static Workspace carve(const d3pm_shape& sh, int batch, char* base) {
-  const size_t es = dtype_size(sh.dtype), n = static_cast<size_t>(batch) * sh.canvas, d = sh.d_model;
-  Workspace w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-  w.x = take(n * d * es);
-  w.h = take(n * d * es);
-  w.h2 = take(n * d * es);           // adjacent to h: norm2 | norm22 outputs feed ONE [2n, d] query projection
-  // Regions that are never live together share memory (D3PM_TUNE_WORKSPACE_ALIAS): 350 -> 200 MB per 32 utterances beside a
-  // 256-MB Infinity Cache, +1.6 % tokens/s measured for the first pair alone (profiles/round2_c_ab_throughput.txt):
-  //   packed qkv rows -> cross-attention queries -> MLP hidden rows -> logits of the iteration;
-  //   norm22 output (dead once the query projection ran) -> prompt cross-attention output
-  if (tune_of(sh.tuning).workspace_alias) {
-    const size_t big = n * 4 * d * es, lg = n * levels(sh) * logits_ld(sh) * es;
-    w.mlp = take(big > lg ? big : lg);
-    w.qkv = w.mlp;
-    w.logits = w.mlp;
-    w.att = take(n * d * es);
-    w.att2 = w.h2;
-  } else {
-    w.qkv = take(n * 3 * d * es);
-    w.att = take(n * d * es);
-    w.att2 = take(n * d * es);
-    w.mlp = take(n * 4 * d * es);
-    w.logits = take(n * levels(sh) * logits_ld(sh) * es);
-  }
-  w.stats = reinterpret_cast<float*>(take(((n + 15) & ~static_cast<size_t>(15)) * ((d + 31) / 32) * 2 * sizeof(float)));
-  w.mxs = reinterpret_cast<uint8_t*>(take(2 * n * ((d + 31) / 32)));
-  if (base && 17 * n + 12 * static_cast<size_t>(batch) + 16 <= 2 * n * ((d + 31) / 32)) {
-    int32_t* ip = reinterpret_cast<int32_t*>(w.mxs);
-    w.dd.row_of = ip; w.dd.rep_pos = ip + n; w.dd.cid = ip + 2 * n; w.dd.key_cls = ip + 3 * n; w.dd.cnt = ip + 4 * n; w.dd.seg_start = w.dd.cnt + batch;
-    w.dd.seg_len = w.dd.seg_start + batch; w.dd.m_live = w.dd.seg_len + batch; w.dd.cmask = reinterpret_cast<uint8_t*>(w.dd.m_live + 4);
-  }
-  if (fold_shape_ok(sh.dtype, sh.d_model)) {
-    const size_t L = sh.n_layers;
-    w.fc1f = take(L * 4 * d * d * es);
-    w.fc1f_s = reinterpret_cast<float*>(take(L * 4 * d * sizeof(float)));
-    w.fc1f_b = reinterpret_cast<float*>(take(L * 4 * d * sizeof(float)));
-    if (levels(sh) == 1) {      // whatever d3pm_tuning.ln_fold says: a caller never has to know
-      const size_t mt = qkv_table_rows(sh.n_classes);
-      w.tab_x = take(mt * d * es);
-      w.tab_stats = reinterpret_cast<float*>(take(mt * (d / 32) * 2 * sizeof(float)));
-      w.tab_qkv = take(mt * 3 * d * es);
-      // The sampler launch writes these rows while it reads the logits, which alias ws.qkv: q takes a region of its own, k | v
-      // the adjacent h | h2 -- the folded sequence writes no LayerNorm output, so nothing lives there between the last block of
-      // an evaluation and the first out-projection of the next (h: o_text of the two-launch cross-attention output; h2 = att2 under
-      // workspace_alias: the prompt cross-attention output, both dead behind their block)
-      w.q0 = take(n * d * es);
-      w.kv0 = w.h;
-    }
-  }
-  w.total = off;
-  return w;
-}
-
 static int check_shape(const d3pm_shape* sh, int batch) {
   D3PM_REQUIRE(sh, D3PM_E_ARG, "null shape");
   D3PM_REQUIRE(batch > 0 && sh->d_model > 0 && sh->n_heads > 0 && sh->d_model % sh->n_heads == 0 && sh->n_layers > 0 &&
@@ -213,71 +129,6 @@ static int check_shape(const d3pm_shape* sh, int batch) {
   return D3PM_OK;
 }
 
-#define D3PM_TRY(expr)            \
-  do {                            \
-    int rc_ = (expr);             \
-    if (rc_ != D3PM_OK) return rc_; \
-  } while (0)
-
-static const char* at(const void* p, size_t elems, size_t es) { return static_cast<const char*>(p) + elems * es; }
-static char* at(void* p, size_t elems, size_t es) { return static_cast<char*>(p) + elems * es; }
-
-// ---- argument builders: the shapes the launch sequences below repeat -----------------------------------------------------
-// Y[M][N] = X[M][K] . W[N][K]^T + bias over packed rows (ldx = K, ldy = N); a caller with a wider output row sets ldy afterwards
-static LinearArgs projection(const void* X, const void* W, const void* bias, void* Y, int M, int N, int K, int act = ACT_NONE) {
-  LinearArgs g;
-  g.X = X; g.ldx = K; g.W = W; g.bias = bias; g.Y = Y; g.ldy = N; g.M = M; g.N = N; g.K = K; g.act = act;
-  return g;
-}
-// ... + R1 (+ R2): rows of the output's width
-static LinearArgs with_residual(LinearArgs g, const void* R1, const void* R2 = nullptr) {
-  g.R1 = R1; g.R2 = R2; g.ldr = g.N;
-  return g;
-}
-// ... * row_mask[row % period]
-static LinearArgs with_row_mask(LinearArgs g, const uint8_t* mask, int period) {
-  g.row_mask = mask; g.mask_period = period;
-  return g;
-}
-// ... leaving the moments of the rows it stores (a producer of the folded LayerNorm, d3pm_mfma_tile.h EPI_STATS)
-static LinearArgs with_moments_out(LinearArgs g, float* stats, bool quads) {
-  g.stats_out = stats; g.moment_quads = quads;
-  return g;
-}
-// a LayerNorm-fed projection of the raw residual rows X [M][K] (a consumer, EPI_LNF): Wf = W o gamma, no bias operand
-static LinearArgs folded_projection(const void* X, const void* Wf, const float* fold_s, const float* fold_b, const float* stats, bool quads,
-                                    void* Y, int M, int N, int K, int act) {
-  LinearArgs g = projection(X, Wf, nullptr, Y, M, N, K, act);
-  g.fold_s = fold_s; g.fold_b = fold_b; g.stats_in = stats; g.moment_quads = quads;
-  return g;
-}
-static float attn_scale(int hd) { return static_cast<float>(std::sqrt(1.0 / static_cast<double>(hd))); }
-// self-attention over a packed [B * T][3 H hd] buffer of q | k | v rows
-static AttnArgs self_attention(const void* qkv, void* O, int B, int T, int H, int hd, size_t es) {
-  const int d = H * hd;
-  AttnArgs a;
-  a.Q = qkv; a.ldq = 3 * d; a.K = at(qkv, d, es); a.V = at(qkv, 2 * d, es); a.ldkv = 3 * d; a.O = O; a.ldo = d;
-  a.B = B; a.Tq = T; a.S = T; a.H = H; a.hd = hd; a.scale = attn_scale(hd);
-  return a;
-}
-// the text | prompt cross-attentions of one block in one launch: queries with row stride ldq, keys and values packed [B * S][2 H hd]
-static AttnArgs cross_attention_pair(const void* q_text, const void* q_prompt, int ldq, const void* kv_text, int s_text, const void* kv_prompt,
-                                     int s_prompt, void* o_text, void* o_prompt, int B, int T, int H, int hd, size_t es) {
-  const int d = H * hd;
-  AttnArgs a;
-  a.Q = q_text; a.ldq = ldq; a.K = kv_text; a.V = at(kv_text, d, es); a.ldkv = 2 * d; a.O = o_text; a.ldo = d;
-  a.B = B; a.Tq = T; a.S = s_text; a.H = H; a.hd = hd; a.scale = attn_scale(hd);
-  a.Q2 = q_prompt; a.K2 = kv_prompt; a.V2 = at(kv_prompt, d, es); a.O2 = o_prompt; a.S2 = s_prompt;
-  return a;
-}
-static EmbedArgs embed_args(const d3pm_shape& sh, const d3pm_weights& w, int batch, const int32_t* x_t, const uint8_t* frame_mask, int mask_period,
-                            void* Y) {
-  EmbedArgs e;
-  e.tokens = x_t; e.frame_mask = frame_mask; e.mask_period = mask_period; e.table = w.resps_emb; e.Y = Y;
-  e.M = batch * sh.canvas; e.d = sh.d_model; e.n_classes = sh.n_classes; e.n_q = levels(sh);
-  return e;
-}
-
 // ---- the cross-attention out-projection pair: x = (x + o_text) + o_prompt through the same weights (plan_cross_out, d3pm_plan.h) ----
 static int run_cross_out_dual(const Ctx& cx, int dt, const CrossOutPlan& c, const LinearArgs& g, const void* X2, hipStream_t s) {
   ProfScope p(cx, D3PM_K_GEMM, s, 2.0 * 2.0 * g.M * g.N * g.K,
@@ -285,51 +136,6 @@ static int run_cross_out_dual(const Ctx& cx, int dt, const CrossOutPlan& c, cons
   return c.form == CROSS_OUT_PANEL64_DUAL ? panel64_dual(dt, g, X2, c.dual, s) : big_dual(dt, g, X2, c.dual, s);
 }
 
-// The frame mask of a call and the period it repeats with over the packed [batch * canvas] rows: one mask [canvas] shared by every
-// utterance (period canvas: d3pm_denoise_step, d3pm_sample_loop) or one per utterance [batch][canvas] (period batch * canvas: the
-// *_canvas entries).  `known` is the known-frame map of d3pm_canvas ([batch][canvas] or null), read by the sampler only.
-struct CanvasMask {
-  const uint8_t* frame_mask; int period; const uint8_t* known;
-};
-static CanvasMask shared_mask(const d3pm_shape* sh, const uint8_t* frame_mask) { return CanvasMask{frame_mask, sh ? sh->canvas : 0, nullptr}; }
-static CanvasMask per_utterance_mask(const d3pm_shape* sh, int batch, const d3pm_canvas* cv, bool with_known) {
-  if (!cv || !sh) return CanvasMask{nullptr, 0, nullptr};
-  return CanvasMask{cv->frame_mask, batch * sh->canvas, with_known ? cv->known : nullptr};
-}
-
-// d3pm_keys of a call (all null without one): the key counts of the self-attention and of the two cross-attentions
-struct KeyCounts {
-  const int32_t *frames = nullptr, *text = nullptr, *prompt = nullptr;
-};
-static KeyCounts key_counts(const d3pm_keys* k) { return k ? KeyCounts{k->frames, k->text, k->prompt} : KeyCounts{}; }
-// a masked self-attention of the denoiser: the schedule of the unmasked one
-static AttnArgs with_frame_keys(AttnArgs a, const KeyCounts& kc) {
-  a.key_len = kc.frames; a.masked_keeps_schedule = kc.frames != nullptr;
-  return a;
-}
-static AttnArgs with_cond_keys(AttnArgs a, const KeyCounts& kc) {
-  a.key_len = kc.text; a.key_len2 = kc.prompt;
-  return a;
-}
-
-struct DenoiserArgs {      // what every block of one evaluation sees
-  const d3pm_shape& sh; const d3pm_weights& w; int batch; const uint8_t* frame_mask; int mask_period; const void* kv_text; const void* kv_prompt;
-  const Workspace& ws;
-  KeyCounts keys = {};
-  // classifier-free guidance (d3pm_sample_loop_guided): x_t holds token_rows = batch / 2 * canvas rows and rows token_rows .. of the
-  // evaluation (the null twins) read the same ids; 0 = x_t has a row per row of the evaluation
-  int token_rows = 0;
-  // the block-0 QKV table of the call (ws.tab_qkv once build_qkv_table has filled it) or null: with it, an embedding launch of the
-  // evaluation also gathers ws.q0 | ws.kv0
-  const void* qkv_table = nullptr;
-  // row deduplication (sample_loop_impl decides, d3pm_dedup.hip): the index of this evaluation's compact rows, or null.  With it every
-  // projection and attention query of the folded sequence runs on the compact rows (live count and segments read from device memory),
-  // and the launch that prepares an evaluation is dedup_index.
-  const DedupIndex* dd = nullptr;
-  // with dd, per iteration: the host's estimate of the live rows (plan_live_rows) when the iteration takes the latency launch list --
-  // every projection of a block on gemm_mfma_panel64, sized for the estimate, moments as parts -- or 0: the big-tile list, quads
-  int m_est = 0;
-};
 // the token embedding of an evaluation whose two halves read the same x_t (token_rows > 0): the gather, once per half
 static int embed_twins(const DenoiserArgs& q, const int32_t* x_t, hipStream_t s) {
   const d3pm_shape& sh = q.sh;
@@ -340,114 +146,6 @@ static int embed_twins(const DenoiserArgs& q, const int32_t* x_t, hipStream_t s)
   return embed_tokens(sh.dtype, e, s);
 }
 
-// ---- the block sequence with the LayerNorms folded into the projections (ar_discrete.py:126-161; d3pm_mfma_tile.h EPI_LNF / EPI_STATS)
-//   embed (+ moments) -> n_layers x { QKV <- x [norm1 folded], self-attention, out-projection + x (+ moments),
-//   merged query projection <- x [norm2 | norm22 folded, N = 2d], paired cross-attention, both out-projections + x (+ moments),
-//   fc1 + GELU <- x [norm3 + FiLM(t) folded], fc2 + x, frame mask (+ moments) }: ten launches per block, none of them a LayerNorm.
-// The launches of block l, written ONCE and handed to a visitor in order: FoldPlanner asks whether and on which tiles they would run,
-// FoldLauncher enqueues them.  Every LinearArgs that reads or writes ws.stats is constructed here and nowhere else.
-// qkv_ready (block 0 only): ws.q0 | ws.kv0 already hold the q and k | v rows of ALL rows of this evaluation (gathered from the
-// block-0 QKV table by the launch that embedded them), so the QKV projection is skipped and the self-attention reads them there.
-template <class Visitor>
-static int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v, bool qkv_ready = false) {
-  const d3pm_shape& sh = q.sh;
-  const Workspace& ws = q.ws;
-  const int dt = sh.dtype, d = sh.d_model, H = sh.n_heads, hd = d / H, T = sh.canvas, n = q.batch * T;
-  const size_t es = dtype_size(dt);
-  const d3pm_block_weights& b = q.w.blocks[l];
-  const d3pm_fold_block& f = q.w.fold[l];
-  const int* m_live = q.dd ? q.dd->m_live : nullptr;
-  auto consumer = [&](const void* Wf, const float* fs, const float* fb, void* Y, int N, int act) {
-    LinearArgs g = folded_projection(ws.x, Wf, fs, fb, ws.stats, quads, Y, n, N, d, act);
-    g.m_live = m_live; g.m_est = q.m_est;
-    return v.linear(g);
-  };
-  auto segments = [&](AttnArgs a) {
-    if (q.dd) { a.seg_start = q.dd->seg_start; a.seg_len = q.dd->seg_len; }
-    return a;
-  };
-  // a projection onto the residual stream: x += X . W^T + bias (+ R2), then the moments of the new rows
-  auto producer = [&](const void* X, int K, const void* W, const void* bias, const void* R2 = nullptr) {
-    LinearArgs g = with_moments_out(with_residual(projection(X, W, bias, ws.x, n, d, K), ws.x, R2), ws.stats, quads);
-    g.m_live = m_live; g.m_est = q.m_est;
-    return g;
-  };
-  // ---- self-attention ----
-  const bool from_table = l == 0 && qkv_ready;
-  if (!from_table) D3PM_TRY(consumer(f.qkv_w, f.qkv_s, f.qkv_b, ws.qkv, 3 * d, ACT_NONE));
-  AttnArgs sa = self_attention(ws.qkv, ws.att, q.batch, T, H, hd, es);
-  if (from_table) { sa.Q = ws.q0; sa.ldq = d; sa.K = ws.kv0; sa.V = at(ws.kv0, d, es); sa.ldkv = 2 * d; }
-  if (q.dd) {
-    // the keys stay where they lie and the attention walks them through an index (attn32p_hd64 GATHER): the k | v columns of the compact
-    // QKV rows through row_of, in block 0 those of the block-0 QKV table through the class of a canvas position (q: ws.q0, the compact copy)
-    if (from_table) { sa.K = at(q.qkv_table, d, es); sa.V = at(q.qkv_table, 2 * d, es); sa.key_row = q.dd->key_cls; sa.kv_rows = qkv_table_rows(sh.n_classes); }
-    else { sa.key_row = q.dd->row_of; sa.kv_rows = n; }
-    sa.ldkv = 3 * d;
-  }
-  D3PM_TRY(v.attention(segments(with_frame_keys(sa, q.keys))));
-  D3PM_TRY(v.linear(producer(ws.att, d, b.attn_out_w, b.attn_out_b)));
-  // ---- cross-attention: q_text | q_prompt are the two halves of ONE [n][2d] projection of x (the same q rows under norm2 / norm22)
-  D3PM_TRY(consumer(f.q2_w, f.q2_s, f.q2_b, ws.qkv, 2 * d, ACT_NONE));
-  const void* kvt = at(q.kv_text, static_cast<size_t>(l) * q.batch * sh.s_text * 2 * d, es);
-  const void* kvp = at(q.kv_prompt, static_cast<size_t>(l) * q.batch * sh.s_prompt * 2 * d, es);
-  D3PM_TRY(v.attention(segments(with_cond_keys(cross_attention_pair(ws.qkv, at(ws.qkv, d, es), 2 * d, kvt, sh.s_text, kvp, sh.s_prompt, ws.att, ws.att2, q.batch, T, H, hd, es),
-                                               q.keys))));
-  // ---- x = (x + o_text) + o_prompt, rounded at each add like the eager sum ----
-  LinearArgs g = producer(ws.att, d, b.cross_out_w, b.cross_out_b);
-  g.tune = sh.tuning;      // plan_cross_out reads it
-  const CrossOutPlan out = plan_cross_out(dt, g, ws.att2, false, true);
-  if (out.form != CROSS_OUT_TWO_LAUNCHES) {
-    D3PM_TRY(v.dual(out, g, ws.att2));
-  } else {
-    g.Y = ws.h; g.R1 = nullptr; g.stats_out = nullptr; g.moment_quads = false;   // o_text -> h (free: no LayerNorm output lives there any more)
-    D3PM_TRY(v.linear(g));
-    D3PM_TRY(v.linear(producer(ws.att2, d, b.cross_out_w, b.cross_out_b, ws.h)));
-  }
-  // ---- FiLM-modulated MLP: the (layer, t) copy of fc1 carries norm3 and the modulation ----
-  const size_t ln = static_cast<size_t>(l) * 4 * d;
-  D3PM_TRY(consumer(at(ws.fc1f, ln * d, es), ws.fc1f_s + ln, ws.fc1f_b + ln, ws.mlp, 4 * d, ACT_GELU));
-  // (deduplicated: the mask byte of a compact row, period = the capacity)
-  if (q.dd) return v.linear(with_row_mask(producer(ws.mlp, 4 * d, b.fc2_w, b.fc2_b), q.dd->cmask, n));
-  return v.linear(with_row_mask(producer(ws.mlp, 4 * d, b.fc2_w, b.fc2_b), q.frame_mask, q.mask_period));
-}
-
-// asks: would every launch that touches the moments run on the MFMA family (D3PM_E_SHAPE if not), and all of them on big tiles?
-struct FoldPlanner {
-  int dt; const d3pm_tuning* tune; bool big;
-  int linear(LinearArgs g) {
-    if (!g.fold_s && !g.stats_out) return D3PM_OK;      // no moments: any family will do
-    g.tune = tune;
-    const LinearPlan plan = plan_linear(dt, g);
-    if (!plan.mfma()) return D3PM_E_SHAPE;
-    big = big && plan.big();
-    return D3PM_OK;
-  }
-  int attention(const AttnArgs&) { return D3PM_OK; }
-  int dual(const CrossOutPlan& c, const LinearArgs&, const void*) {
-    big = big && c.dual.big();      // the 64 x 64 family keeps the 32-column parts
-    return D3PM_OK;
-  }
-};
-// asks: would the sequence run on the kernels that read a live row count and query segments from device memory -- every projection on
-// `family` (big tiles; gemm_mfma_panel64 for the latency iterations, asked with DenoiserArgs::m_est set and the moments as parts), the
-// self-attention on attn32p_hd64, the cross pair on attn32_cross_hd64?
-struct DedupPlanner {
-  int dt; const d3pm_tuning* tune; bool ok; int family = LIN_BIG;
-  int linear(LinearArgs g) {
-    g.tune = tune;
-    ok = ok && plan_linear(dt, g).kernel == family;
-    return D3PM_OK;
-  }
-  int attention(AttnArgs a) {
-    a.tune = tune;
-    ok = ok && plan_attention(dt, a).kernel == (a.Q2 ? ATTN_32_CROSS : ATTN_32P);
-    return D3PM_OK;
-  }
-  int dual(const CrossOutPlan& c, const LinearArgs&, const void*) {
-    ok = ok && c.dual.kernel == family;
-    return D3PM_OK;
-  }
-};
 struct FoldLauncher {
   const Ctx& cx; int dt; hipStream_t s;
   int linear(const LinearArgs& g) { return run_linear(cx, dt, g, 0, s); }      // (fails rather than take the generic family with moments)
@@ -455,28 +153,6 @@ struct FoldLauncher {
   int dual(const CrossOutPlan& c, const LinearArgs& g, const void* X2) { return run_cross_out_dual(cx, dt, c, g, X2, s); }
 };
 
-// Is this evaluation taking the folded-LayerNorm launch sequence, and in which format do its row moments travel?  FOLD_NONE: the
-// LayerNorm launches (the fold is off, or a projection of the sequence would not run on the MFMA family, whose epilogues alone read
-// and write moments).  FOLD_QUADS: every projection that reads or writes moments runs on big tiles (128-column aligned, d = 512), so
-// the producers can leave one quad per 128 columns (d3pm_mfma_tile.h EpiFold).  FOLD_PARTS: 32-column parts, which the 128 x 128 and
-// 64 x 64 (panel64, one or two utterances) families need.  One decision for the whole sequence -- every producer and consumer of
-// ws.stats, the sampler's embedding rows included, must use the same format -- taken once per call by denoise_step_impl /
-// sample_loop_impl over ALL layers (only_layers never changes the format).  The walk asks with the parts format and the sequence
-// launches with the answer; at d = 512, the only width that gets quads, fold_args_ok accepts both formats for these arguments.
-// The deduplicated loop alone refines the answer per ITERATION (sample_loop_impl): an iteration on the latency launch list runs its
-// whole chain -- the index launch that prepares it included -- on parts, every other one on quads.  The consumers compute the same bits
-// from either format, so the switch changes no id.
-enum { FOLD_NONE = 0, FOLD_PARTS = 1, FOLD_QUADS = 2 };
-static int fold_plan(const DenoiserArgs& q, uint32_t flags, const d3pm_fp8_block_weights* f8) {
-  const d3pm_shape& sh = q.sh;
-  if (f8 || !q.w.fold || !tune_of(sh.tuning).ln_fold || (flags & D3PM_FLAG_FORCE_GENERIC) || !fold_shape_ok(sh.dtype, sh.d_model)) return FOLD_NONE;
-  FoldPlanner plan{sh.dtype, sh.tuning, sh.d_model == 512};
-  for (int l = 0; l < sh.n_layers; ++l)
-    if (folded_block(q, l, false, plan) != D3PM_OK) return FOLD_NONE;
-  return plan.big ? FOLD_QUADS : FOLD_PARTS;
-}
-
-// qkv_ready: with `prepared`, whether the launch that prepared this evaluation also gathered ws.q0 | ws.kv0 for all of its rows
 // The block-0 QKV table of a reverse process.  Block 0 reads x[row] = resps_emb[id] (zeros on a padded frame): no positional term, no
 // time term and no FiLM enters before norm1, so its QKV projection takes at most n_classes + 1 distinct values, which depend on the
 // weights alone.  They are computed once per call -- the folded projection itself over the n_classes embedding rows and the zero row,
@@ -542,8 +218,8 @@ static int denoiser_blocks_folded(const DenoiserArgs& q, const int32_t* x_t, int
   return D3PM_OK;
 }
 
-// One denoiser evaluation up to the final projection: the hidden state after `layers` blocks is left in ws.x.  `plan` is the caller's
-// fold_plan(): FOLD_NONE runs the LayerNorm / row-panel launches below (and the fp8 fast path, BASELINE.json configs[4]).
+// One denoiser evaluation up to the final projection: the hidden state after `layers` blocks is left in ws.x.  `plan` is the moment format
+// of the evaluation (LoopPlan::fold; FOLD_PARTS in a latency iteration): FOLD_NONE runs the LayerNorm / row-panel launches below (and the fp8 fast path, BASELINE.json configs[4]).
 static int denoiser_blocks(const DenoiserArgs& q, const int32_t* x_t, int t, const void* film, int layers, uint32_t flags, hipStream_t s,
                            const d3pm_fp8_block_weights* f8, int plan, bool prepared = false, bool qkv_ready = false) {
   // LayerNorm folded into the projections (d3pm_tuning.ln_fold, d3pm_fold_block): every LayerNorm-fed projection reads the raw
@@ -747,7 +423,6 @@ using namespace d3pm;
 extern "C" {
 
 int d3pm_abi_version(void) { return D3PM_ABI_VERSION; }
-const char* d3pm_last_error(void) { return g_err; }
 
 size_t d3pm_workspace_bytes(const d3pm_shape* shape, int batch) {
   if (check_shape(shape, batch) != D3PM_OK) return 0;
@@ -1073,10 +748,25 @@ int d3pm_encode_conditions_keys(const d3pm_shape* sh, const d3pm_cond_weights* c
   return encode_conditions_impl(sh, cw, batch, text, prompt, cond_text, cond_prompt, workspace, workspace_bytes, key_counts(keys), stream);
 }
 
-static int denoise_step_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, const int32_t* x_t,
-                             const CanvasMask& cm, int t, const void* film, const void* kv_text, const void* kv_prompt,
-                             void* workspace, size_t workspace_bytes, void* logits_out, void* hidden_out, int only_layers,
-                             uint32_t flags, void* stream, const d3pm_fp8_block_weights* f8, const KeyCounts& keys = KeyCounts{}) {
+// What the forms of an entry point add to the arguments they share; each extern "C" entry fills the fields it has.
+struct CallOptions {
+  const char* who;                                  // the entry's name, for messages
+  CanvasMask mask;                                  // the frame mask (either_mask) and, for a sampler, the known frames
+  const d3pm_fp8_block_weights* f8 = nullptr;       // the fp8 fast path
+  const d3pm_nucleus* nucleus = nullptr;            // temperature, top-k, top-p (null = the neutral triple)
+  KeyCounts keys = {};
+  const d3pm_guidance* guide = nullptr;
+  float* theta_out = nullptr;                       // d3pm_posterior_sample_nucleus
+};
+// one mask [canvas] shared by the batch, or one per utterance (+ the known frames): the entries that take either check that one is given
+static CanvasMask either_mask(const d3pm_shape* sh, int batch, const uint8_t* frame_mask, const d3pm_canvas* canvas) {
+  return canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask);
+}
+
+static int denoise_step_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, const int32_t* x_t, int t, const void* film,
+                             const void* kv_text, const void* kv_prompt, void* workspace, size_t workspace_bytes, void* logits_out,
+                             void* hidden_out, int only_layers, uint32_t flags, void* stream, const CallOptions& o) {
+  const CanvasMask& cm = o.mask;
   D3PM_TRY(check_shape(sh, batch));
   D3PM_REQUIRE(w && w->blocks && x_t && cm.frame_mask && film && kv_text && kv_prompt && workspace, D3PM_E_ARG,
                "d3pm_denoise_step: null pointer");
@@ -1085,8 +775,9 @@ static int denoise_step_impl(const d3pm_shape* sh, const d3pm_weights* w, int ba
   D3PM_REQUIRE(workspace_bytes >= ws.total, D3PM_E_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, ws.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int layers = (only_layers >= 0 && only_layers < sh->n_layers) ? only_layers : sh->n_layers;
-  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, keys};
-  D3PM_TRY(denoiser_blocks(q, x_t, t, film, layers, flags, s, f8, fold_plan(q, flags, f8)));
+  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, o.keys};
+  // (one evaluation: the moment format is all there is to plan)
+  D3PM_TRY(denoiser_blocks(q, x_t, t, film, layers, flags, s, o.f8, loop_plan(q, flags, LoopCall{o.f8 != nullptr}).fold));
   if (hidden_out)
     D3PM_CHECK_HIP(hipMemcpyAsync(hidden_out, ws.x, static_cast<size_t>(batch) * sh->canvas * sh->d_model * dtype_size(sh->dtype),
                                   hipMemcpyDeviceToDevice, s));
@@ -1103,24 +794,24 @@ int d3pm_denoise_step(const d3pm_shape* sh, const d3pm_weights* w, int batch, co
                       const uint8_t* frame_mask, int t, const void* film, const void* kv_text, const void* kv_prompt,
                       void* workspace, size_t workspace_bytes, void* logits_out, void* hidden_out, int only_layers,
                       uint32_t flags, void* stream) {
-  return denoise_step_impl(sh, w, batch, x_t, shared_mask(sh, frame_mask), t, film, kv_text, kv_prompt, workspace, workspace_bytes, logits_out,
-                           hidden_out, only_layers, flags, stream, nullptr);
+  return denoise_step_impl(sh, w, batch, x_t, t, film, kv_text, kv_prompt, workspace, workspace_bytes, logits_out, hidden_out, only_layers, flags,
+                           stream, CallOptions{"d3pm_denoise_step", shared_mask(sh, frame_mask)});
 }
 
 int d3pm_denoise_step_canvas(const d3pm_shape* sh, const d3pm_weights* w, int batch, const int32_t* x_t, const d3pm_canvas* canvas, int t,
                              const void* film, const void* kv_text, const void* kv_prompt, void* workspace, size_t workspace_bytes,
                              void* logits_out, void* hidden_out, int only_layers, uint32_t flags, void* stream) {
   D3PM_REQUIRE(canvas, D3PM_E_ARG, "d3pm_denoise_step_canvas: null canvas");
-  return denoise_step_impl(sh, w, batch, x_t, per_utterance_mask(sh, batch, canvas, false), t, film, kv_text, kv_prompt, workspace, workspace_bytes,
-                           logits_out, hidden_out, only_layers, flags, stream, nullptr);
+  return denoise_step_impl(sh, w, batch, x_t, t, film, kv_text, kv_prompt, workspace, workspace_bytes, logits_out, hidden_out, only_layers, flags,
+                           stream, CallOptions{"d3pm_denoise_step_canvas", per_utterance_mask(sh, batch, canvas, false)});
 }
 
 int d3pm_denoise_step_keys(const d3pm_shape* sh, const d3pm_weights* w, int batch, const int32_t* x_t, const d3pm_canvas* canvas, int t,
                            const void* film, const void* kv_text, const void* kv_prompt, void* workspace, size_t workspace_bytes,
                            void* logits_out, void* hidden_out, int only_layers, uint32_t flags, const d3pm_keys* keys, void* stream) {
   D3PM_REQUIRE(canvas, D3PM_E_ARG, "d3pm_denoise_step_keys: null canvas");
-  return denoise_step_impl(sh, w, batch, x_t, per_utterance_mask(sh, batch, canvas, false), t, film, kv_text, kv_prompt, workspace, workspace_bytes,
-                           logits_out, hidden_out, only_layers, flags, stream, nullptr, key_counts(keys));
+  return denoise_step_impl(sh, w, batch, x_t, t, film, kv_text, kv_prompt, workspace, workspace_bytes, logits_out, hidden_out, only_layers, flags,
+                           stream, CallOptions{"d3pm_denoise_step_keys", per_utterance_mask(sh, batch, canvas, false), nullptr, nullptr, key_counts(keys)});
 }
 
 int d3pm_denoise_step_fp8(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch,
@@ -1128,8 +819,8 @@ int d3pm_denoise_step_fp8(const d3pm_shape* sh, const d3pm_weights* w, const d3p
                           const void* kv_prompt, void* workspace, size_t workspace_bytes, void* logits_out, void* hidden_out,
                           int only_layers, uint32_t flags, void* stream) {
   D3PM_REQUIRE(fp8_blocks, D3PM_E_ARG, "d3pm_denoise_step_fp8: null fp8 weights");
-  return denoise_step_impl(sh, w, batch, x_t, shared_mask(sh, frame_mask), t, film, kv_text, kv_prompt, workspace, workspace_bytes, logits_out,
-                           hidden_out, only_layers, flags, stream, fp8_blocks);
+  return denoise_step_impl(sh, w, batch, x_t, t, film, kv_text, kv_prompt, workspace, workspace_bytes, logits_out, hidden_out, only_layers, flags,
+                           stream, CallOptions{"d3pm_denoise_step_fp8", shared_mask(sh, frame_mask), fp8_blocks});
 }
 
 // d3pm_nucleus of the *_nucleus entries (the *_sampling entries forward their pair with top_p = 1): NULL = the neutral triple.
@@ -1151,52 +842,63 @@ static const d3pm_nucleus* with_top_p_off(const d3pm_sampling* sm, d3pm_nucleus*
   return out;
 }
 
+// The sampler launch of `batch` utterances at timestep t, whichever kernel takes it: logits rows of stride ldl, one Philox row per
+// frame from utt0 * canvas on.  What only some callers have -- the trace grid, posterior_out, theta_out, the seed in HBM -- they set.
+static SampleArgs sample_args(const d3pm_shape& sh, int batch, const void* logits, int logits_dtype, int ldl, const int32_t* x_t, int32_t* x_next,
+                              const uint8_t* known, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags,
+                              const d3pm_nucleus* sm, const d3pm_guidance* guide) {
+  SampleArgs a;
+  a.logits = logits; a.logits_dtype = logits_dtype; a.ldl = ldl; a.x_t = x_t; a.x_next = x_next;
+  a.rows = batch * sh.canvas * levels(sh); a.n_q = levels(sh); a.n_classes = sh.n_classes; a.mask_id = sh.mask_id; a.canvas = sh.canvas;
+  a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh.canvas); a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0;
+  a.pc = make_posterior_consts(sched, t);
+  a.known = known;
+  if (sm) { a.temperature = sm->temperature; a.top_k = sm->top_k; a.top_p = sm->top_p; }
+  if (guide) { a.guided = true; a.guidance = guide->weight; }
+  return a;
+}
+
 static int posterior_sample_impl(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
-                                 int32_t* x_next, const uint8_t* known, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
-                                 uint32_t flags, uint16_t* posterior_out, void* stream, const d3pm_nucleus* sm = nullptr,
-                                 float* theta_out = nullptr, const char* who = "d3pm_posterior_sample_sampling") {
+                                 int32_t* x_next, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                                 uint32_t flags, uint16_t* posterior_out, void* stream, const CallOptions& o) {
   D3PM_TRY(check_shape(sh, batch));
-  D3PM_TRY(check_sampling(sh, sm, who));
+  D3PM_TRY(check_sampling(sh, o.nucleus, o.who));
   D3PM_REQUIRE(logits && x_t && x_next && sched && sched->d && sched->c && sched->dbar && sched->cbar, D3PM_E_ARG,
                "d3pm_posterior_sample: null pointer");
   D3PM_REQUIRE(t >= 0 && t < sched->timesteps, D3PM_E_ARG, "t=%d outside the schedule", t);
-  SampleArgs a;
-  a.logits = logits; a.logits_dtype = logits_dtype; a.ldl = sh->n_classes; a.x_t = x_t; a.x_next = x_next;
-  a.posterior_out = posterior_out; a.rows = batch * sh->canvas * levels(*sh); a.n_classes = sh->n_classes; a.mask_id = sh->mask_id;
-  a.n_q = levels(*sh);
-  a.canvas = sh->canvas; a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas);
-  a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0; a.pc = make_posterior_consts(sched, t);
-  a.known = known;
-  if (sm) { a.temperature = sm->temperature; a.top_k = sm->top_k; a.top_p = sm->top_p; }
-  a.theta_out = theta_out;
+  SampleArgs a = sample_args(*sh, batch, logits, logits_dtype, sh->n_classes, x_t, x_next, o.mask.known, t, sched, seed, utt0, flags, o.nucleus, nullptr);
+  a.posterior_out = posterior_out;
+  a.theta_out = o.theta_out;
   return posterior_sample(a, static_cast<hipStream_t>(stream));
 }
 
 int d3pm_posterior_sample(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
                           int32_t* x_next, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
                           uint32_t flags, uint16_t* posterior_out, void* stream) {
-  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, nullptr, t, sched, seed, utt0, flags, posterior_out, stream);
+  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, t, sched, seed, utt0, flags, posterior_out, stream,
+                               CallOptions{"d3pm_posterior_sample", CanvasMask{}});
 }
 
 int d3pm_posterior_sample_known(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
                                 int32_t* x_next, const uint8_t* known, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
                                 uint32_t flags, uint16_t* posterior_out, void* stream) {
-  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, known, t, sched, seed, utt0, flags, posterior_out, stream);
+  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, t, sched, seed, utt0, flags, posterior_out, stream,
+                               CallOptions{"d3pm_posterior_sample_known", CanvasMask{nullptr, 0, known}});
 }
 
 int d3pm_posterior_sample_sampling(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
                                    int32_t* x_next, const uint8_t* known, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
                                    uint32_t flags, uint16_t* posterior_out, const d3pm_sampling* sampling, void* stream) {
   d3pm_nucleus nu;
-  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, known, t, sched, seed, utt0, flags, posterior_out, stream,
-                               with_top_p_off(sampling, &nu));
+  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, t, sched, seed, utt0, flags, posterior_out, stream,
+                               CallOptions{"d3pm_posterior_sample_sampling", CanvasMask{nullptr, 0, known}, nullptr, with_top_p_off(sampling, &nu)});
 }
 
 int d3pm_posterior_sample_nucleus(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t,
                                   int32_t* x_next, const uint8_t* known, int t, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
                                   uint32_t flags, uint16_t* posterior_out, const d3pm_nucleus* nucleus, float* theta_out, void* stream) {
-  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, known, t, sched, seed, utt0, flags, posterior_out, stream, nucleus,
-                               theta_out, "d3pm_posterior_sample_nucleus");
+  return posterior_sample_impl(sh, batch, logits, logits_dtype, x_t, x_next, t, sched, seed, utt0, flags, posterior_out, stream,
+                               CallOptions{"d3pm_posterior_sample_nucleus", CanvasMask{nullptr, 0, known}, nullptr, nucleus, {}, nullptr, theta_out});
 }
 
 // the sampler launch of the deduplicated loop on its own (tests): posterior_sample_dedup with no next-iteration fold
@@ -1211,25 +913,69 @@ int d3pm_op_posterior_sample_rows(const d3pm_shape* sh, int batch, const void* l
   D3PM_REQUIRE(t >= 0 && t < sched->timesteps, D3PM_E_ARG, "t=%d outside the schedule", t);
   D3PM_REQUIRE(ldl >= sh->n_classes, D3PM_E_ARG, "%s: row stride %d below n_classes %d", who, ldl, sh->n_classes);
   D3PM_REQUIRE(!(flags & D3PM_FLAG_SEED_IN_HBM), D3PM_E_ARG, "%s: the seed travels by value", who);
-  SampleArgs a;
-  a.logits = logits; a.logits_dtype = logits_dtype; a.ldl = ldl; a.x_t = x_t; a.x_next = x_next; a.x_next2 = x_next2;
-  a.rows = batch * sh->canvas * levels(*sh); a.n_classes = sh->n_classes; a.mask_id = sh->mask_id; a.n_q = levels(*sh);
-  a.canvas = sh->canvas; a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas);
-  a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0; a.pc = make_posterior_consts(sched, t);
-  a.known = known;
-  if (nucleus) { a.temperature = nucleus->temperature; a.top_k = nucleus->top_k; a.top_p = nucleus->top_p; }
-  if (guidance) { a.guided = true; a.guidance = guidance->weight; }      // refused below: the deduplicated launch has no guided form
+  // (guidance is refused below: the deduplicated launch has no guided form)
+  SampleArgs a = sample_args(*sh, batch, logits, logits_dtype, ldl, x_t, x_next, known, t, sched, seed, utt0, flags, nucleus, guidance);
+  a.x_next2 = x_next2;
   return posterior_sample_dedup(a, row_of, NextIterPrep{}, static_cast<hipStream_t>(stream));
 }
 
-static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const CanvasMask& cm,
-                            int t_start, int t_stop, const void* film, const void* kv_text, const void* kv_prompt,
-                            const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace,
-                            size_t workspace_bytes, int32_t* trace, void* stream, const d3pm_fp8_block_weights* f8,
-                            const d3pm_nucleus* sm = nullptr, const char* who = "d3pm_sample_loop_sampling", const KeyCounts& keys = KeyCounts{},
-                            const d3pm_guidance* guide = nullptr) {
+// What the launch that ends an evaluation prepares for the evaluation at t_next (NextIterPrep): fc1 of every block under norm3 +
+// FiLM(t_next), and the embedding rows of the ids it draws with their moments -- in the block-0 QKV table's loop their q | k | v rows
+// too (never under guidance).  The deduplicated loop embeds nothing here: run_dedup_index follows the launch.
+static NextIterPrep next_iter_prep(const DenoiserArgs& q, const void* film, int t_next, bool quads) {
+  const d3pm_shape& sh = q.sh;
+  NextIterPrep nx;
+  nx.dtype = sh.dtype; nx.d = sh.d_model; nx.blocks = q.w.blocks; nx.n_layers = sh.n_layers;
+  nx.film_t = at(film, static_cast<size_t>(t_next) * sh.n_layers * 2 * sh.d_model, dtype_size(sh.dtype));
+  nx.Wf = q.ws.fc1f; nx.s_out = q.ws.fc1f_s; nx.b_out = q.ws.fc1f_b;
+  if (q.dd) return nx;
+  nx.table = q.w.resps_emb; nx.x = q.ws.x; nx.stats = q.ws.stats; nx.frame_mask = q.frame_mask; nx.mask_period = q.mask_period;
+  nx.quads = quads;
+  if (q.qkv_table) { nx.qkv_table = q.qkv_table; nx.q0 = q.ws.q0; nx.kv0 = q.ws.kv0; }
+  return nx;
+}
+
+// The sampler launch of an iteration in whichever of its five forms applies -- deduplicated (every canvas row draws from the logits of
+// its compact row; then the index and the compact embedding of the next iteration), with the next iteration's preparation inside the
+// launch (plain or guided), or alone (plain or guided).  `preps`: there is a next iteration on the folded path, at t_next, whose moments
+// travel as quads_next says.  *prepared: the launch (or the index launch behind it) has embedded x_t and folded fc1 for t_next;
+// *qkv_ready: ... and gathered ws.q0 | ws.kv0 for every row of that evaluation.
+static int run_sampler(const Ctx& cx, const DenoiserArgs& q, const SampleArgs& a, const void* film, int t_next, bool preps, bool quads_next,
+                       hipStream_t s, bool* prepared, bool* qkv_ready) {
+  const d3pm_shape& sh = q.sh;
+  const size_t es = dtype_size(sh.dtype);
+  const NextIterPrep nx = preps ? next_iter_prep(q, film, t_next, quads_next) : NextIterPrep{};
+  *prepared = *qkv_ready = false;
+  {
+    // (+ the block-0 q | k | v rows the launch stores for the next evaluation; their source, the table, stays in L2)
+    ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0,
+                static_cast<double>(a.rows) * ((a.guided ? 2.0 : 1.0) * sh.n_classes * es + 8.0) +
+                    (nx.q0 ? static_cast<double>(a.rows) * 3.0 * sh.d_model * es : 0.0));
+    if (q.dd) {
+      D3PM_TRY(posterior_sample_dedup(a, q.dd->row_of, nx, s));
+    } else if (nx.table && posterior_sample_prep_supported(a, nx)) {
+      // + the embedding rows, their moments and the fc1 fold of t_next (guided: the rows of both halves)
+      D3PM_TRY(a.guided ? posterior_sample_prep_guided(a, nx, s) : posterior_sample_prep(a, nx, s));
+      *prepared = true;
+      *qkv_ready = nx.q0 != nullptr;
+    } else {
+      D3PM_TRY(a.guided ? posterior_sample_guided(a, s) : posterior_sample(a, s));
+    }
+  }
+  if (q.dd && preps) {
+    D3PM_TRY(run_dedup_index(q, a.x_next, quads_next, s));
+    *prepared = *qkv_ready = true;
+  }
+  return D3PM_OK;
+}
+
+static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, int t_start, int t_stop, const void* film,
+                            const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                            uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, void* stream, const CallOptions& o) {
+  const CanvasMask& cm = o.mask;
+  const d3pm_guidance* guide = o.guide;
   D3PM_TRY(check_shape(sh, batch));
-  D3PM_TRY(check_sampling(sh, sm, who));
+  D3PM_TRY(check_sampling(sh, o.nucleus, o.who));
   D3PM_REQUIRE(w && w->blocks && x && cm.frame_mask && film && kv_text && kv_prompt && sched && workspace, D3PM_E_ARG,
                "d3pm_sample_loop: null pointer");
   D3PM_REQUIRE(t_start < sched->timesteps && t_start <= sh->timesteps && t_stop >= 0 && t_stop <= t_start, D3PM_E_ARG,
@@ -1253,116 +999,24 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rows = batch * sh->canvas;
   const Ctx cx(sh->tuning);
-  DenoiserArgs q{*sh, *w, eval_batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, keys, guide ? rows : 0};
-  const int plan = fold_plan(q, flags, f8);      // the same for every iteration: the blocks and the sampler's prep share it
-  // Block-0 QKV from the per-id table (build_qkv_table; ln_fold = 2 keeps the projection): every unguided loop -- plain, canvas / known
-  // frames, keys, sampling / nucleus, trace -- once it runs two iterations.  The GUIDED loop keeps the projection: its first evaluation
-  // embeds through embed_twins and its sampler launch (posterior_sample_prep_guided) does not gather.
-  if (plan != FOLD_NONE && tune_of(sh->tuning).ln_fold != 2 && levels(*sh) == 1 && !guide && t_start - t_stop >= 2 && ws.tab_qkv) {
+  DenoiserArgs q{*sh, *w, eval_batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, o.keys, guide ? rows : 0};
+  const LoopPlan plan = loop_plan(q, flags, LoopCall{o.f8 != nullptr, guide != nullptr, cm.known != nullptr, t_start, t_stop});
+  if (plan.table) {
     D3PM_TRY(build_qkv_table(cx, *sh, *w, ws, s));
     q.qkv_table = ws.tab_qkv;
   }
-  // Row deduplication (d3pm_dedup.hip; ln_fold = 3 keeps every row, 4 keeps the big-tile list in every iteration): the unguided 16-bit n_q = 1 loop with the table, moments as quads,
-  // and every launch of the sequence on a kernel that reads the live count / the query segments from device memory.  One decision per
-  // call; otherwise the launch list above runs untouched.
-  const int n_rows = eval_batch * sh->canvas;
-  const int ln_fold = tune_of(sh->tuning).ln_fold;
-  if (q.qkv_table && plan == FOLD_QUADS && (ln_fold == 1 || ln_fold == 4) && !f8 && !guide && ws.dd.row_of && n_rows % 384 == 0 && sh->n_layers <= 16 &&
-      sh->n_classes <= kDedupMaxClasses && eval_batch <= kDedupMaxBatch && ws.h2 == at(ws.h, static_cast<size_t>(n_rows) * sh->d_model, dtype_size(sh->dtype))) {
-    DedupPlanner dp{sh->dtype, sh->tuning, true};
-    for (int l = 0; l < sh->n_layers; ++l) (void)folded_block(q, l, true, dp, l == 0);
-    LinearArgs fin = projection(ws.x, w->final_w, w->final_b, ws.logits, n_rows, sh->n_classes, sh->d_model);
-    fin.ldy = logits_ld(*sh); fin.tune = sh->tuning;
-    const LinearPlan fp = plan_linear(sh->dtype, fin);
-    // the self-attention walks its keys through an index (attn32p_hd64 GATHER): the staged index beside the tiles, and 32-bit byte
-    // offsets into the rows it reads -- the compact QKV rows [n_rows][3d] or the block-0 QKV table
-    const unsigned long long kv_rows = std::max<unsigned long long>(n_rows, qkv_table_rows(sh->n_classes));
-    const bool gather_ok = static_cast<size_t>(sh->canvas) * 4 <= kGatherIndexBytes && kv_rows * 3 * sh->d_model * dtype_size(sh->dtype) < (1ull << 32);
-    if (dp.ok && gather_ok && (fp.big() || fp.kernel == LIN_128_GLDS)) q.dd = &ws.dd;
-  }
-  // The regime of an iteration of the deduplicated loop, decided here with no read-back (the loop is graph-captured): iteration t
-  // evaluates x_t, which the sampler launch of iteration t + 1 drew with cbar_prev = cbar[t] (make_posterior_consts), so a frame of it is
-  // still masked with probability float(cbar[t]) -- the index of the iteration itself, also for t_start, whose canvas the caller
-  // brings (all mask in a full reverse process).  An estimate within live_latency_rows() takes the latency launch list when every
-  // projection of a block plans onto gemm_mfma_panel64 for it (the final projection keeps its kernel).  The estimate chooses speed
-  // only: every kernel reads the live count from the device.  Known frames (cm.known) are the caller's and cannot be counted here:
-  // such a loop keeps the big-tile list, as does ln_fold = 4 (the A/B arm).
-  bool latency_ok = false;
-  if (q.dd && ln_fold == 1 && !cm.known) {
-    DenoiserArgs ql = q;
-    ql.m_est = live_latency_rows();
-    DedupPlanner lp{sh->dtype, sh->tuning, true, LIN_PANEL64};
-    for (int l = 0; l < sh->n_layers; ++l) (void)folded_block(ql, l, false, lp, l == 0);
-    latency_ok = lp.ok;
-  }
-  auto latency_est = [&](int t) {      // the iteration's DenoiserArgs::m_est
-    if (!latency_ok || t <= t_stop) return 0;
-    const int est = plan_live_rows(eval_batch, sh->canvas, host_h2f(sched->cbar[t]));
-    return live_latency(est) ? est : 0;
-  };
-  bool prepared = false;     // the previous iteration's sampler launch has already embedded x_t and folded fc1 for this t
-  bool qkv_ready = false;     // ... and gathered ws.q0 | ws.kv0 for every row of this evaluation
+  if (plan.dedup) q.dd = &ws.dd;
+  bool prepared = false, qkv_ready = false;      // by the previous iteration's sampler launch
   for (int t = t_start; t > t_stop; --t) {
     if (cx.prof) cx.prof->sample_now = (t % cx.prof->stride) == 0;
-    q.m_est = latency_est(t);
-    // (a latency iteration's moments travel as parts: its producers and consumers, and the index launch that prepared it)
-    D3PM_TRY(denoiser_blocks(q, x, t, film, sh->n_layers, flags, s, f8, q.m_est ? FOLD_PARTS : plan, prepared, qkv_ready));
-    prepared = qkv_ready = false;
-    SampleArgs a;
-    a.logits = ws.logits; a.logits_dtype = sh->dtype; a.ldl = logits_ld(*sh); a.x_t = x; a.x_next = x;
+    q.m_est = plan.m_est(sched, t);
+    D3PM_TRY(denoiser_blocks(q, x, t, film, sh->n_layers, flags, s, o.f8, q.m_est ? FOLD_PARTS : plan.fold, prepared, qkv_ready));
+    D3PM_TRY(final_logits(*sh, *w, eval_batch, ws, ws.logits, logits_ld(*sh), flags, s, q.dd ? q.dd->m_live : nullptr));
+    SampleArgs a = sample_args(*sh, batch, ws.logits, sh->dtype, logits_ld(*sh), x, x, cm.known, t, sched, seed, utt0, flags, o.nucleus, guide);
     a.x_next2 = trace ? trace + static_cast<size_t>(t_start - t) * rows * levels(*sh) : nullptr;
-    a.rows = rows * levels(*sh); a.n_q = levels(*sh); a.n_classes = sh->n_classes; a.mask_id = sh->mask_id; a.canvas = sh->canvas; a.seed = seed;
     if (flags & D3PM_FLAG_SEED_IN_HBM) a.seed_hbm = reinterpret_cast<const uint64_t*>(static_cast<uintptr_t>(seed));
-    a.row0 = utt0 * static_cast<uint32_t>(sh->canvas); a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0;
-    a.pc = make_posterior_consts(sched, t);
-    a.known = cm.known;
-    if (sm) { a.temperature = sm->temperature; a.top_k = sm->top_k; a.top_p = sm->top_p; }
-    if (guide) { a.guided = true; a.guidance = guide->weight; }
-    {
-      D3PM_TRY(final_logits(*sh, *w, eval_batch, ws, ws.logits, logits_ld(*sh), flags, s, q.dd ? q.dd->m_live : nullptr));
-      const bool preps = t - 1 > t_stop && plan != FOLD_NONE;
-      if (q.dd) {
-        // every canvas row draws from the logits of its compact row; then the index, the compact embedding and (inside the sampler
-        // launch) the fc1 fold of iteration t - 1
-        NextIterPrep nx;
-        if (preps) {
-          nx.dtype = sh->dtype; nx.d = sh->d_model; nx.blocks = w->blocks; nx.n_layers = sh->n_layers;
-          nx.film_t = at(film, static_cast<size_t>(t - 1) * sh->n_layers * 2 * sh->d_model, dtype_size(sh->dtype));
-          nx.Wf = ws.fc1f; nx.s_out = ws.fc1f_s; nx.b_out = ws.fc1f_b;
-        }
-        {
-          ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0, static_cast<double>(rows) * (sh->n_classes * dtype_size(sh->dtype) + 8.0));
-          D3PM_TRY(posterior_sample_dedup(a, q.dd->row_of, nx, s));
-        }
-        if (preps) {
-          D3PM_TRY(run_dedup_index(q, x, plan == FOLD_QUADS && !latency_est(t - 1), s));
-          prepared = qkv_ready = true;
-        }
-        continue;
-      }
-      // (+ the block-0 q | k | v rows the launch stores for the next evaluation; their source, the table, stays in L2)
-      ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0,
-                  static_cast<double>(rows) * levels(*sh) * ((guide ? 2.0 : 1.0) * sh->n_classes * dtype_size(sh->dtype) + 8.0) +
-                      (preps && q.qkv_table ? static_cast<double>(rows) * 3.0 * sh->d_model * dtype_size(sh->dtype) : 0.0));
-      NextIterPrep nx;
-      if (preps) {
-        const size_t es = dtype_size(sh->dtype);
-        nx.dtype = sh->dtype; nx.table = w->resps_emb; nx.x = ws.x; nx.stats = ws.stats; nx.frame_mask = cm.frame_mask; nx.mask_period = cm.period; nx.d = sh->d_model;
-        nx.quads = plan == FOLD_QUADS;
-        nx.blocks = w->blocks; nx.n_layers = sh->n_layers;
-        nx.film_t = at(film, static_cast<size_t>(t - 1) * sh->n_layers * 2 * sh->d_model, es);
-        nx.Wf = ws.fc1f; nx.s_out = ws.fc1f_s; nx.b_out = ws.fc1f_b;
-        if (q.qkv_table) { nx.qkv_table = q.qkv_table; nx.q0 = ws.q0; nx.kv0 = ws.kv0; }      // (never under guidance)
-      }
-      if (nx.table && posterior_sample_prep_supported(a, nx)) {
-        // + the embedding rows, their moments and the fc1 fold of iteration t - 1 (guided: the rows of both halves)
-        D3PM_TRY(guide ? posterior_sample_prep_guided(a, nx, s) : posterior_sample_prep(a, nx, s));
-        prepared = true;
-        qkv_ready = nx.q0 != nullptr;
-      } else {
-        D3PM_TRY(guide ? posterior_sample_guided(a, s) : posterior_sample(a, s));
-      }
-    }
+    const bool preps = t - 1 > t_stop && plan.fold != FOLD_NONE;
+    D3PM_TRY(run_sampler(cx, q, a, film, t - 1, preps, plan.fold == FOLD_QUADS && !plan.m_est(sched, t - 1), s, &prepared, &qkv_ready));
   }
   if (cx.prof) cx.prof->sample_now = false;
   return D3PM_OK;
@@ -1372,8 +1026,8 @@ int d3pm_sample_loop(const d3pm_shape* sh, const d3pm_weights* w, int batch, int
                      int t_start, int t_stop, const void* film, const void* kv_text, const void* kv_prompt,
                      const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace,
                      size_t workspace_bytes, int32_t* trace, void* stream) {
-  return sample_loop_impl(sh, w, batch, x, shared_mask(sh, frame_mask), t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags,
-                          workspace, workspace_bytes, trace, stream, nullptr);
+  return sample_loop_impl(sh, w, batch, x, t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          stream, CallOptions{"d3pm_sample_loop", shared_mask(sh, frame_mask)});
 }
 
 int d3pm_sample_loop_canvas(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const d3pm_canvas* canvas,
@@ -1381,8 +1035,8 @@ int d3pm_sample_loop_canvas(const d3pm_shape* sh, const d3pm_weights* w, int bat
                             const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace,
                             size_t workspace_bytes, int32_t* trace, void* stream) {
   D3PM_REQUIRE(canvas, D3PM_E_ARG, "d3pm_sample_loop_canvas: null canvas");
-  return sample_loop_impl(sh, w, batch, x, per_utterance_mask(sh, batch, canvas, true), t_start, t_stop, film, kv_text, kv_prompt, sched, seed,
-                          utt0, flags, workspace, workspace_bytes, trace, stream, nullptr);
+  return sample_loop_impl(sh, w, batch, x, t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          stream, CallOptions{"d3pm_sample_loop_canvas", per_utterance_mask(sh, batch, canvas, true)});
 }
 
 int d3pm_sample_loop_fp8(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch,
@@ -1390,8 +1044,8 @@ int d3pm_sample_loop_fp8(const d3pm_shape* sh, const d3pm_weights* w, const d3pm
                          const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
                          uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, void* stream) {
   D3PM_REQUIRE(fp8_blocks, D3PM_E_ARG, "d3pm_sample_loop_fp8: null fp8 weights");
-  return sample_loop_impl(sh, w, batch, x, shared_mask(sh, frame_mask), t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags,
-                          workspace, workspace_bytes, trace, stream, fp8_blocks);
+  return sample_loop_impl(sh, w, batch, x, t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          stream, CallOptions{"d3pm_sample_loop_fp8", shared_mask(sh, frame_mask), fp8_blocks});
 }
 
 int d3pm_sample_loop_fp8_canvas(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch,
@@ -1399,8 +1053,8 @@ int d3pm_sample_loop_fp8_canvas(const d3pm_shape* sh, const d3pm_weights* w, con
                                 const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
                                 uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, void* stream) {
   D3PM_REQUIRE(fp8_blocks && canvas, D3PM_E_ARG, "d3pm_sample_loop_fp8_canvas: null fp8 weights or canvas");
-  return sample_loop_impl(sh, w, batch, x, per_utterance_mask(sh, batch, canvas, true), t_start, t_stop, film, kv_text, kv_prompt, sched, seed,
-                          utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks);
+  return sample_loop_impl(sh, w, batch, x, t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          stream, CallOptions{"d3pm_sample_loop_fp8_canvas", per_utterance_mask(sh, batch, canvas, true), fp8_blocks});
 }
 
 int d3pm_sample_loop_sampling(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch, int32_t* x,
@@ -1411,9 +1065,8 @@ int d3pm_sample_loop_sampling(const d3pm_shape* sh, const d3pm_weights* w, const
   D3PM_REQUIRE(sh && (frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
                "d3pm_sample_loop_sampling: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)");
   d3pm_nucleus nu;
-  return sample_loop_impl(sh, w, batch, x, canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask), t_start, t_stop,
-                          film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks,
-                          with_top_p_off(sampling, &nu));
+  return sample_loop_impl(sh, w, batch, x, t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          stream, CallOptions{"d3pm_sample_loop_sampling", either_mask(sh, batch, frame_mask, canvas), fp8_blocks, with_top_p_off(sampling, &nu)});
 }
 
 int d3pm_sample_loop_nucleus(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch, int32_t* x,
@@ -1423,9 +1076,8 @@ int d3pm_sample_loop_nucleus(const d3pm_shape* sh, const d3pm_weights* w, const 
                              void* stream) {
   D3PM_REQUIRE(sh && (frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
                "d3pm_sample_loop_nucleus: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)");
-  return sample_loop_impl(sh, w, batch, x, canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask), t_start, t_stop,
-                          film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks, nucleus,
-                          "d3pm_sample_loop_nucleus");
+  return sample_loop_impl(sh, w, batch, x, t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          stream, CallOptions{"d3pm_sample_loop_nucleus", either_mask(sh, batch, frame_mask, canvas), fp8_blocks, nucleus});
 }
 
 int d3pm_sample_loop_keys(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch, int32_t* x,
@@ -1436,9 +1088,8 @@ int d3pm_sample_loop_keys(const d3pm_shape* sh, const d3pm_weights* w, const d3p
   D3PM_REQUIRE(sh && (frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
                "d3pm_sample_loop_keys: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)");
   D3PM_REQUIRE(!(keys && fp8_blocks), D3PM_E_ARG, "d3pm_sample_loop_keys: the fp8 fast path takes no key mask");
-  return sample_loop_impl(sh, w, batch, x, canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask), t_start, t_stop,
-                          film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace, stream, fp8_blocks, nucleus,
-                          "d3pm_sample_loop_keys", key_counts(keys));
+  return sample_loop_impl(sh, w, batch, x, t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          stream, CallOptions{"d3pm_sample_loop_keys", either_mask(sh, batch, frame_mask, canvas), fp8_blocks, nucleus, key_counts(keys)});
 }
 
 // ---- classifier-free guidance (d3pm_guidance) -----------------------------------------------------------------------------------------
@@ -1462,14 +1113,9 @@ int d3pm_posterior_sample_guided(const d3pm_shape* sh, int batch, const void* lo
   D3PM_REQUIRE(!(flags & D3PM_FLAG_SEED_IN_HBM), D3PM_E_ARG, "%s: D3PM_FLAG_SEED_IN_HBM (graph replay) is not supported under guidance", who);
   D3PM_REQUIRE(logits && x_t && x_next && sched && sched->d && sched->c && sched->dbar && sched->cbar, D3PM_E_ARG, "%s: null pointer", who);
   D3PM_REQUIRE(t >= 0 && t < sched->timesteps, D3PM_E_ARG, "t=%d outside the schedule", t);
-  SampleArgs a;
-  a.logits = logits; a.logits_dtype = logits_dtype; a.ldl = sh->n_classes; a.x_t = x_t; a.x_next = x_next;
-  a.rows = batch * sh->canvas; a.n_classes = sh->n_classes; a.mask_id = sh->mask_id; a.n_q = 1;
-  a.canvas = sh->canvas; a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas);
-  a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0; a.pc = make_posterior_consts(sched, t);
-  a.known = canvas ? canvas->known : nullptr;
-  if (nucleus) { a.temperature = nucleus->temperature; a.top_k = nucleus->top_k; a.top_p = nucleus->top_p; }
-  a.guided = true; a.guidance = guidance->weight;
+  // (one level: check_guidance)
+  const SampleArgs a = sample_args(*sh, batch, logits, logits_dtype, sh->n_classes, x_t, x_next, canvas ? canvas->known : nullptr, t, sched, seed,
+                                   utt0, flags, nucleus, guidance);
   return posterior_sample_guided(a, static_cast<hipStream_t>(stream));
 }
 
@@ -1484,9 +1130,8 @@ int d3pm_sample_loop_guided(const d3pm_shape* sh, const d3pm_weights* w, const d
                "%s: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)", who);
   D3PM_REQUIRE(!(flags & D3PM_FLAG_SEED_IN_HBM), D3PM_E_ARG, "%s: D3PM_FLAG_SEED_IN_HBM (graph replay) is not supported under guidance", who);
   D3PM_REQUIRE(!fp8_blocks, D3PM_E_ARG, "%s: the fp8 fast path takes no guidance", who);
-  return sample_loop_impl(sh, w, batch, x, canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask), t_start, t_stop,
-                          film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace, stream, nullptr, nucleus, who,
-                          key_counts(keys), guidance);
+  return sample_loop_impl(sh, w, batch, x, t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          stream, CallOptions{who, either_mask(sh, batch, frame_mask, canvas), nullptr, nucleus, key_counts(keys), guidance});
 }
 
 // ---- confidence-ordered reveal (d3pm_reveal) ------------------------------------------------------------------------------------------
@@ -1510,11 +1155,21 @@ static int check_reveal(const d3pm_shape* sh, int batch, const d3pm_schedule* sc
   return D3PM_OK;
 }
 
-// the scalars of the step that evaluates at t and is followed by t_next (0: the last step, which keeps nothing and draws no v)
-static void reveal_step_scalars(RevealArgs& a, const d3pm_schedule* sched, int t, int t_next, float choice_temperature) {
+// The two launches of the reveal step that evaluates at t and is followed by t_next (0: the last step, which keeps nothing and draws
+// no v): logits rows of stride ldl.  The caller sets x_next (and the loop its trace grid).
+static RevealArgs reveal_args(const d3pm_shape& sh, int batch, const void* logits, int logits_dtype, int ldl, const int32_t* x_t, const CanvasMask& cm,
+                              int32_t* cand, float* score, int t, int t_next, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                              uint32_t flags, const d3pm_nucleus* nucleus, float choice_temperature) {
+  RevealArgs a;
+  a.logits = logits; a.logits_dtype = logits_dtype; a.ldl = ldl; a.x_t = x_t;
+  a.frame_mask = cm.frame_mask; a.mask_period = cm.period; a.known = cm.known; a.cand = cand; a.score = score;
+  a.rows = batch * sh.canvas; a.canvas = sh.canvas; a.n_classes = sh.n_classes; a.mask_id = sh.mask_id;
+  a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh.canvas); a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0;
+  if (nucleus) { a.temperature = nucleus->temperature; a.top_k = nucleus->top_k; a.top_p = nucleus->top_p; }
   a.t = t;
   a.keep_frac = t_next > 0 ? host_h2f(sched->cbar[t_next]) : 0.f;
   a.lambda = t_next > 0 ? choice_temperature * a.keep_frac : 0.f;
+  return a;
 }
 
 int d3pm_reveal_step(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t, int32_t* x_next,
@@ -1527,14 +1182,9 @@ int d3pm_reveal_step(const d3pm_shape* sh, int batch, const void* logits, int lo
   D3PM_REQUIRE(logits && x_t && x_next && cand_out && score_out && (!canvas || canvas->frame_mask), D3PM_E_ARG, "d3pm_reveal_step: null pointer");
   D3PM_REQUIRE(t >= 1 && t < sched->timesteps && t_next >= 0 && t_next < t, D3PM_E_ARG, "d3pm_reveal_step: t = %d, t_next = %d outside %d > t > t_next >= 0", t,
                t_next, sched->timesteps);
-  const CanvasMask cm = canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask);
-  RevealArgs a;
-  a.logits = logits; a.logits_dtype = logits_dtype; a.ldl = sh->n_classes; a.x_t = x_t; a.x_next = x_next;
-  a.frame_mask = cm.frame_mask; a.mask_period = cm.period; a.known = cm.known; a.cand = cand_out; a.score = score_out;
-  a.rows = batch * sh->canvas; a.canvas = sh->canvas; a.n_classes = sh->n_classes; a.mask_id = sh->mask_id;
-  a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas); a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0;
-  if (nucleus) { a.temperature = nucleus->temperature; a.top_k = nucleus->top_k; a.top_p = nucleus->top_p; }
-  reveal_step_scalars(a, sched, t, t_next, choice_temperature);
+  RevealArgs a = reveal_args(*sh, batch, logits, logits_dtype, sh->n_classes, x_t, either_mask(sh, batch, frame_mask, canvas), cand_out, score_out, t,
+                             t_next, sched, seed, utt0, flags, nucleus, choice_temperature);
+  a.x_next = x_next;
   hipStream_t s = static_cast<hipStream_t>(stream);
   D3PM_TRY(reveal_candidates(a, s));
   return reveal_commit(a, s);
@@ -1564,11 +1214,12 @@ static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   float* score = reinterpret_cast<float*>(ws.att) + rows;
   int32_t* x_alt = reinterpret_cast<int32_t*>(ws.mxs);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const CanvasMask cm = canvas ? per_utterance_mask(sh, batch, canvas, true) : shared_mask(sh, frame_mask);
+  const CanvasMask cm = either_mask(sh, batch, frame_mask, canvas);
   const Ctx cx(sh->tuning);
   const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, keys};
-  const int plan = fold_plan(q, flags, nullptr);
-  // (The reveal loop keeps the block-0 QKV projection: reveal_commit_prep does not gather from the table of sample_loop_impl.)
+  // Asked as for one evaluation: the reveal loop keeps the block-0 QKV projection and every row (reveal_commit_prep does not gather
+  // from the table), so the moment format is all it plans.
+  const int plan = loop_plan(q, flags, LoopCall{}).fold;
   bool prepared = false;
   int32_t* cur = x;      // where x_t of the step lives: the fused launch cannot store in place, so it alternates between x and x_alt
   for (int i = 0; i < N; ++i) {
@@ -1578,24 +1229,12 @@ static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     D3PM_TRY(denoiser_blocks(q, cur, t, film, sh->n_layers, flags, s, nullptr, plan, prepared));
     prepared = false;
     D3PM_TRY(final_logits(*sh, *w, batch, ws, ws.logits, logits_ld(*sh), flags, s));
-    RevealArgs a;
-    a.logits = ws.logits; a.logits_dtype = sh->dtype; a.ldl = logits_ld(*sh); a.x_t = cur;
+    RevealArgs a = reveal_args(*sh, batch, ws.logits, sh->dtype, logits_ld(*sh), cur, cm, cand, score, t, t_next, sched, seed, utt0, flags, nucleus,
+                               reveal->choice_temperature);
     a.x_next2 = trace ? trace + static_cast<size_t>(i) * rows : nullptr;
-    a.frame_mask = cm.frame_mask; a.mask_period = cm.period; a.known = cm.known; a.cand = cand; a.score = score;
-    a.rows = rows; a.canvas = sh->canvas; a.n_classes = sh->n_classes; a.mask_id = sh->mask_id;
-    a.seed = seed; a.row0 = utt0 * static_cast<uint32_t>(sh->canvas); a.greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0;
-    if (nucleus) { a.temperature = nucleus->temperature; a.top_k = nucleus->top_k; a.top_p = nucleus->top_p; }
-    reveal_step_scalars(a, sched, t, t_next, reveal->choice_temperature);
     ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0, static_cast<double>(rows) * (sh->n_classes * es + 16.0));
     D3PM_TRY(reveal_candidates(a, s));
-    NextIterPrep nx;
-    if (t_next > 0 && plan != FOLD_NONE) {
-      nx.dtype = sh->dtype; nx.table = w->resps_emb; nx.x = ws.x; nx.stats = ws.stats; nx.frame_mask = cm.frame_mask; nx.mask_period = cm.period; nx.d = sh->d_model;
-      nx.quads = plan == FOLD_QUADS;
-      nx.blocks = w->blocks; nx.n_layers = sh->n_layers;
-      nx.film_t = at(film, static_cast<size_t>(t_next) * sh->n_layers * 2 * sh->d_model, es);
-      nx.Wf = ws.fc1f; nx.s_out = ws.fc1f_s; nx.b_out = ws.fc1f_b;
-    }
+    const NextIterPrep nx = t_next > 0 && plan != FOLD_NONE ? next_iter_prep(q, film, t_next, plan == FOLD_QUADS) : NextIterPrep{};
     a.x_next = cur == x ? x_alt : x;
     if (nx.table && reveal_commit_prep_supported(a, nx)) {
       D3PM_TRY(reveal_commit_prep(a, nx, s));      // + the embedding rows, their moments and the fc1 fold of t_next

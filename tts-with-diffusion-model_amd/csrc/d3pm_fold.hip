@@ -108,8 +108,6 @@ __global__ __launch_bounds__(256) void qkv_table_input_rows(const T* __restrict_
 
 }  // namespace
 
-bool fold_shape_ok(int dtype, int d) { return (dtype == D3PM_F16 || dtype == D3PM_BF16) && d >= 256 && d % 256 == 0; }
-
 int fold_rows_launch(int dtype, const void* W, const void* bias, const void* gamma, const void* beta, const void* film, long film_ld,
                      int n_rows, int n_t, int K, void* Wf, float* s_out, float* b_out, hipStream_t s) {
   const long rows = static_cast<long>(n_rows) * n_t;

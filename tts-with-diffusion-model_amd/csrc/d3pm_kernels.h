@@ -40,7 +40,7 @@ struct LinearArgs {
   // moments of the rows this launch stores (N = d_model, after residual / mask): stats_out [M][N / 32][2] partial (sum, sum of squares)
   float* stats_out = nullptr;
   // stats_in / stats_out in the quad format [M / 16][d / 128][16][2] (d3pm_mfma_tile.h EpiFold) instead of 32-column parts: d_model = 512,
-  // big-tile GEMM only (LIN_QUADS_REFUSED, d3pm_plan.h: mfma_linear fails with D3PM_E_SHAPE on any other family); one host decision per folded sequence (d3pm_api.hip)
+  // big-tile GEMM only (LIN_QUADS_REFUSED, d3pm_plan.h: mfma_linear fails with D3PM_E_SHAPE on any other family); one host decision per folded sequence (fold_plan, d3pm_sequence.h)
   bool moment_quads = false;
   // optional live row count in device memory (row deduplication, d3pm_dedup.hip): only the tiles that hold a row < *m_live run; M stays
   // the capacity the plan was made for.  Big-tile family, gemm_mfma_128_glds and gemm_mfma_panel64 (mfma_linear refuses it elsewhere).
@@ -85,7 +85,7 @@ struct AttnArgs {
   const void* Q2 = nullptr; const void* K2 = nullptr; const void* V2 = nullptr; void* O2 = nullptr; int S2 = 0;
   // the same mask for the second problem (device int32[B], 1 .. S2); key_len then belongs to the first problem alone
   const int32_t* key_len2 = nullptr;
-  // set by the denoiser plan (d3pm_api.hip, d3pm_keys): a masked self-attention takes the automatic choice of the unmasked one,
+  // set by the denoiser's launch sequence (d3pm_sequence.h with_frame_keys, d3pm_keys): a masked self-attention takes the automatic choice of the unmasked one,
   // so switching the mask on does not switch the instruction shape.  Unset, a masked call with attn_query_groups = 0 keeps the
   // 16 x 16 x 32 kernel it has always had (the stock NAR stage, d3pm_op_attention_keylen).
   bool masked_keeps_schedule = false;
@@ -221,7 +221,7 @@ int posterior_sample_guided(const SampleArgs& a, hipStream_t s);
 // ---- row deduplication (d3pm_dedup.hip): one compact row per distinct (id | padded) class of an utterance -------------------------
 // The denoiser adds no positional term, so two frames of one utterance with the same id get the same logits bit for bit; every
 // projection and every attention query runs on the compact rows, only the keys and the sampler stay per canvas position.
-struct DedupIndex {      // all device memory, [n = batch * canvas] unless noted; carved from the workspace (d3pm_api.hip)
+struct DedupIndex {      // all device memory, [n = batch * canvas] unless noted; carved from the workspace (d3pm_sequence.cpp)
   int32_t* cnt = nullptr;         // [batch] distinct classes of an utterance
   int32_t* seg_start = nullptr;   // [batch] first compact row of an utterance: the exclusive prefix sum of seg_len
   int32_t* seg_len = nullptr;     // [batch] cnt rounded up to DedupArgs::seg_align (1: cnt itself, no zero row inside a segment)
@@ -321,7 +321,6 @@ int fast_layernorm(int dtype, const LayerNormArgs& a, hipStream_t s);
 PosteriorConsts make_posterior_consts(const d3pm_schedule* sched, int t);
 
 // LayerNorm folded into the projections (d3pm_fold.hip): weight preparation and the non-GEMM producers of row moments
-bool fold_shape_ok(int dtype, int d);
 int fold_rows_launch(int dtype, const void* W, const void* bias, const void* gamma, const void* beta, const void* film, long film_ld,
                      int n_rows, int n_t, int K, void* Wf, float* s_out, float* b_out, hipStream_t s);
 int fold_fc1_step_launch(int dtype, const d3pm_block_weights* blocks, int n_layers, const void* film_t, int d, void* Wf, float* s_out,

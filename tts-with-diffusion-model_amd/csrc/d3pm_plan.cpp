@@ -187,7 +187,7 @@ LinearPlan plan_linear(int dtype, const LinearArgs& a, bool force_generic) {
   const bool autosel = variant == 0 || (variant >= 6 && variant <= 8);
   const int epi = epi_of(a);
   // an iteration of the deduplicated loop with few live rows: the latency family whatever the capacity (moments as parts: the loop
-  // chooses the format per iteration, d3pm_api.hip)
+  // chooses the format per iteration, LoopPlan::m_est in d3pm_sequence.h)
   if (variant == 0 && live_latency(a.m_est) && !a.moment_quads && panel64_ok(dtype, a)) return panel64_plan(a, panel64_geometry(a), epi, false);
   if (autosel)
     if (const int id = big_tile(dtype, a, big_want(variant))) return big_plan(a, id, epi | (a.moment_quads ? EPI_QUADS : 0));
@@ -225,7 +225,7 @@ CrossOutPlan plan_cross_out(int dtype, const LinearArgs& g, const void* X2, bool
   // one or two utterances: both products through one resident weight panel of the latency GEMM (o_text stays in registers):
   // whole 32 x 64 tiles, K = 512 (both operand panels and the weight panel resident: 128 KiB)
   // (g.moment_quads is not looked at, as it never was: this form writes parts, and fold_plan, which asks in the parts format, answers
-  // FOLD_PARTS whenever it is chosen -- d3pm_api.hip FoldPlanner::dual)
+  // FOLD_PARTS whenever it is chosen -- d3pm_sequence.h FoldPlanner::dual)
   if ((tn.row_panel & 8) && tn.gemm_variant == 0 && panel64_ok(dtype, g) && g.K == 2 * KC && g.M % 32 == 0 && g.N % 64 == 0 &&
       (g.M <= 2048 || live_latency(g.m_est))) {
     c.form = CROSS_OUT_PANEL64_DUAL;
@@ -270,6 +270,17 @@ int plan_live_rows(int batch, int canvas, float cbar_t) {
 #define D3PM_LIVE_LATENCY_ROWS 3840
 #endif
 int live_latency_rows() { return D3PM_LIVE_LATENCY_ROWS; }
+
+// ---- d3pm_tuning.ln_fold (include/d3pm_hip.h): 0 the LayerNorm launches, 1 everything (default), 2 the fold alone, 3 fold + table,
+// 4 fold + table + deduplication without the latency list.  The only place that reads the codes.
+FoldFeatures fold_features(const d3pm_tuning& tn) {
+  FoldFeatures f;
+  f.fold = tn.ln_fold != 0;
+  f.table = tn.ln_fold != 2;
+  f.dedup = tn.ln_fold == 1 || tn.ln_fold == 4;
+  f.latency = tn.ln_fold == 1;
+  return f;
+}
 
 // ---- attention ----
 namespace {

@@ -2,7 +2,8 @@
 // by pure host functions of (dtype, arguments, tuning).  d3pm_plan.cpp holds no kernel and makes no HIP runtime call, so a test
 // on a machine without a GPU can link it and read every choice (tests/test_launch_plan_api.py).  The launchers in
 // d3pm_mfma_*.hip take a plan and only translate it into a template instantiation and a <<<>>>; d3pm_api.hip asks the planner
-// where it used to ask the launchers' *_supported functions.
+// for every launch it enqueues, and d3pm_sequence.{h,cpp} -- host-only by the same rule -- for the launches of a whole block when a
+// call plans its loop.
 #pragma once
 #include "d3pm_kernels.h"
 
@@ -49,6 +50,13 @@ int plan_live_rows(int batch, int canvas, float cbar_t);
 // on gemm_mfma_panel64, moments as parts); LinearArgs::m_est carries the estimate to plan_linear / plan_cross_out.  0 = no estimate.
 int live_latency_rows();
 inline bool live_latency(int m_est) { return m_est > 0 && m_est <= live_latency_rows(); }
+
+// ---- what d3pm_tuning.ln_fold switches on, by name: nothing outside fold_features compares the field with a number ----
+// fold: the LayerNorms folded into the projections.  On top of it, each a condition among others of loop_plan (d3pm_sequence.h):
+// table: block-0 QKV from the per-id table; dedup: one row per distinct token of an utterance; latency: the per-iteration switch of
+// the deduplicated loop to the latency launch list.
+struct FoldFeatures { bool fold, table, dedup, latency; };
+FoldFeatures fold_features(const d3pm_tuning& tn);
 
 // the instantiated epilogues of each family (the switch of its launcher has exactly these cases), 0-terminated after the first entry
 extern const int kEpi128[], kEpiBig[], kEpiPanel64[], kEpiBigDual[], kEpiPanel64Dual[];
