@@ -68,7 +68,9 @@ extern "C" {
  *    d3pm_op_attention_pair_segments take a segment of any length at any row); key-padding masks in the training step
  *    (d3pm_op_attention_bwd_keylen_f32, d3pm_op_attention_dropout_keylen_f32); the NAR stage's own kernels one at a time
  *    (d3pm_op_nar_embed, d3pm_op_adaln, d3pm_op_nar_sample); the latency GEMM family in the iterations of the deduplicated loop
- *    that have few live rows (d3pm_op_linear_live_est; ln_fold value 4 = the deduplicated loop without that switch) */
+ *    that have few live rows (d3pm_op_linear_live_est; ln_fold value 4 = the deduplicated loop without that switch); the per-frame
+ *    log-probability of the revealed id from either loop (d3pm_frame_scores, d3pm_frame_scores_init, d3pm_frame_scores_step,
+ *    d3pm_sample_loop_scored, d3pm_reveal_loop_scored) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -684,6 +686,70 @@ int d3pm_sample_loop_guided(const d3pm_shape *shape, const d3pm_weights *weights
                             const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
                             size_t workspace_bytes, int32_t *trace, const d3pm_nucleus *nucleus, const d3pm_keys *keys,
                             const d3pm_guidance *guidance, void *stream);
+
+/* ---- per-frame log-probability of the revealed id (additions; ABI version unchanged) -----------------------------------------------
+ * How sure the model was of every frame it revealed, from either loop: what ranks seeds of one utterance, finds the span to
+ * regenerate (known = ids, known_mask = logprob >= threshold) or compares two guidance weights.  n_q = 1 only.  Two device grids
+ * [batch][canvas] travel in d3pm_frame_scores:
+ *   step[r]     -1   row r was not a free masked row when the loop was entered: padding (frame mask 0), known, or already an id;
+ *                0   the row is free and still masked (at loop exit only with t_stop > 0);
+ *                t   (>= 1) the row left the mask in the iteration that evaluated the denoiser at timestep t (the reveal loop: the
+ *                    t_i of the step that revealed it).
+ *   logprob[r]  defined for a row with step[r] = t >= 1, 0.0f otherwise.  With j the id the row took in that iteration and l the
+ *               logits of that evaluation:
+ *                   z_k = rn16(float(l_k))        under guidance z_k = rn16(fmaf(w, float(c_k) - float(u_k), float(c_k)))
+ *                   z_mask_id = -inf,  m = max_k z_k,  S = sum_k expf(z_k - m) in fp32,  logprob = z_j - m - logf(S) in fp32
+ *               -- the model's own log-probability of j among the codec ids.  Temperature, top_k and top_p are deliberately NOT
+ *               applied: the number then compares across sampling options, is always finite, and on the D3PM path a class the
+ *               filter cut can still be drawn through the posterior's eps term.
+ * The arithmetic order is that of the reveal step's confidence (K = 1025: 4 x 4 values per lane + the tail; otherwise the general
+ * layout: per-lane partial sums in ascending class, the tail last, then the wave reductions), so under the neutral triple the value
+ * is the conf of d3pm_reveal bit for bit.  Like that score it sits within 1.0e-4 of the definition in exact arithmetic (the same three
+ * roundings and a sum of <= 1280 terms).
+ * On the D3PM path a revealed row is still redrawn every iteration and may, with probability of order eps, change later: logprob
+ * belongs to the id the row took at `step`, not necessarily to the id the loop returns.
+ * State, not history: a step call touches only rows with step 0 whose x_next is no longer the mask id; every other entry of both
+ * grids is left bit for bit as it was.
+ * Refused with nothing launched: NULL scores or either grid NULL (D3PM_E_ARG), n_q > 1 (D3PM_E_SHAPE), D3PM_FLAG_SEED_IN_HBM
+ * (D3PM_E_ARG), row_of together with guidance or with fp32 logits (D3PM_E_ARG). */
+typedef struct d3pm_frame_scores {
+  float *logprob;      /* device fp32 [batch][canvas] */
+  int32_t *step;       /* device int32 [batch][canvas] */
+} d3pm_frame_scores;
+
+/* step = (live && !known && x == mask_id) ? 0 : -1 and logprob = 0 for the canvas x (device int32 [batch][canvas]) a loop is about
+ * to start from.  Exactly one of frame_mask (device uint8 [canvas], shared by the batch) and canvas (per utterance, with the optional
+ * known map) is given, as for the loops. */
+int d3pm_frame_scores_init(const d3pm_shape *shape, int batch, const int32_t *x, const uint8_t *frame_mask,
+                           const d3pm_canvas *canvas, const d3pm_frame_scores *scores, void *stream);
+
+/* The launch behind one sampler launch: logits are those of the evaluation at t (1 <= t <= shape->timesteps), x_next (device int32
+ * [batch][canvas]) the grid the sampler has just written.  logits device, rows of stride ldl >= n_classes elements of logits_dtype:
+ *   plain     (row_of NULL, guidance NULL)  batch * canvas rows;
+ *   guided    (guidance given)              2 * batch * canvas rows, the null twins behind the conditioned rows;
+ *   indexed   (row_of device int32 [batch * canvas])  row r reads logits[row_of[r]], the index clamped into [0, batch * canvas - 1]:
+ *             the buffer holds batch * canvas rows, as the deduplicated loop's does; 16-bit logits, no guidance. */
+int d3pm_frame_scores_step(const d3pm_shape *shape, int batch, const void *logits, int logits_dtype, int ldl,
+                           const int32_t *row_of, const d3pm_guidance *guidance, const int32_t *x_next, int t,
+                           const d3pm_frame_scores *scores, void *stream);
+
+/* d3pm_sample_loop_guided with the two grids: guidance may be NULL here (then d3pm_sample_loop_keys), and fp8_blocks is allowed when
+ * keys and guidance are NULL.  The loop initialises both grids from x, then every iteration issues one more launch behind its sampler
+ * launch (in the deduplicated loop in front of the next index).  x and trace are bit for bit those of the unscored loop; both grids
+ * are those of d3pm_frame_scores_init + one d3pm_frame_scores_step behind each step of the chained step entries. */
+int d3pm_sample_loop_scored(const d3pm_shape *shape, const d3pm_weights *weights, const d3pm_fp8_block_weights *fp8_blocks,
+                            int batch, int32_t *x, const uint8_t *frame_mask, const d3pm_canvas *canvas, int t_start,
+                            int t_stop, const void *film, const void *kv_text, const void *kv_prompt,
+                            const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
+                            size_t workspace_bytes, int32_t *trace, const d3pm_nucleus *nucleus, const d3pm_keys *keys,
+                            const d3pm_guidance *guidance, const d3pm_frame_scores *scores, void *stream);
+
+/* d3pm_reveal_loop_keys with the two grids: the launch goes behind the commit launch of every step and reads the grid it wrote. */
+int d3pm_reveal_loop_scored(const d3pm_shape *shape, const d3pm_weights *weights, int batch, int32_t *x,
+                            const uint8_t *frame_mask, const d3pm_canvas *canvas, const void *film, const void *kv_text,
+                            const void *kv_prompt, const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags,
+                            void *workspace, size_t workspace_bytes, int32_t *trace, const d3pm_nucleus *nucleus,
+                            const d3pm_reveal *reveal, const d3pm_keys *keys, const d3pm_frame_scores *scores, void *stream);
 
 /* Replaces AR.q_sample / q_probs (ar_discrete.py:467-502): forward noising of x0 at step t with
  * Philox stream 1.  x0, x_out device int32 [batch][canvas]. */

@@ -757,6 +757,7 @@ struct CallOptions {
   KeyCounts keys = {};
   const d3pm_guidance* guide = nullptr;
   float* theta_out = nullptr;                       // d3pm_posterior_sample_nucleus
+  const d3pm_frame_scores* scores = nullptr;        // d3pm_sample_loop_scored: the grids of the launch behind every sampler launch
 };
 // one mask [canvas] shared by the batch, or one per utterance (+ the known frames): the entries that take either check that one is given
 static CanvasMask either_mask(const d3pm_shape* sh, int batch, const uint8_t* frame_mask, const d3pm_canvas* canvas) {
@@ -935,13 +936,36 @@ static NextIterPrep next_iter_prep(const DenoiserArgs& q, const void* film, int 
   return nx;
 }
 
+// ---- per-frame log-probability of the revealed id (d3pm_frame_scores, d3pm_logprob.hip) ---------------------------------------------
+static LogprobArgs logprob_args(const d3pm_shape& sh, int rows, const void* logits, int logits_dtype, int ldl, const int32_t* row_of, bool guided,
+                                float guidance, const int32_t* x_next, int t, const d3pm_frame_scores* scores) {
+  LogprobArgs a;
+  a.logits = logits; a.logits_dtype = logits_dtype; a.ldl = ldl; a.row_of = row_of; a.guided = guided; a.guidance = guidance; a.x_next = x_next;
+  a.logprob = scores->logprob; a.step = scores->step; a.rows = rows; a.n_classes = sh.n_classes; a.mask_id = sh.mask_id; a.t = t;
+  return a;
+}
+// the launch behind a sampler launch, counted with the samplers (algorithmic bytes: two words per row + the logits of the rows that
+// leave the mask, on average rows / (T - 1) of them)
+static int run_frame_logprob(const Ctx& cx, const LogprobArgs& a, hipStream_t s) {
+  ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0, static_cast<double>(a.rows) * 8.0);
+  return frame_logprob(a, s);
+}
+// what every entry that takes d3pm_frame_scores refuses before anything is launched
+static int check_scores(const d3pm_shape* sh, const d3pm_frame_scores* scores, const char* who) {
+  D3PM_REQUIRE(sh, D3PM_E_ARG, "null shape");
+  D3PM_REQUIRE(scores && scores->logprob && scores->step, D3PM_E_ARG, "%s: null d3pm_frame_scores or a null grid in it", who);
+  D3PM_REQUIRE(levels(*sh) == 1, D3PM_E_SHAPE, "%s: n_q = %d; frame scores are defined for n_q = 1", who, sh->n_q);
+  return D3PM_OK;
+}
+
 // The sampler launch of an iteration in whichever of its five forms applies -- deduplicated (every canvas row draws from the logits of
 // its compact row; then the index and the compact embedding of the next iteration), with the next iteration's preparation inside the
 // launch (plain or guided), or alone (plain or guided).  `preps`: there is a next iteration on the folded path, at t_next, whose moments
 // travel as quads_next says.  *prepared: the launch (or the index launch behind it) has embedded x_t and folded fc1 for t_next;
 // *qkv_ready: ... and gathered ws.q0 | ws.kv0 for every row of that evaluation.
+// `scores` (d3pm_sample_loop_scored): one more launch behind the sampler's, in front of the index launch that rebuilds row_of.
 static int run_sampler(const Ctx& cx, const DenoiserArgs& q, const SampleArgs& a, const void* film, int t_next, bool preps, bool quads_next,
-                       hipStream_t s, bool* prepared, bool* qkv_ready) {
+                       hipStream_t s, bool* prepared, bool* qkv_ready, const d3pm_frame_scores* scores = nullptr) {
   const d3pm_shape& sh = q.sh;
   const size_t es = dtype_size(sh.dtype);
   const NextIterPrep nx = preps ? next_iter_prep(q, film, t_next, quads_next) : NextIterPrep{};
@@ -962,6 +986,8 @@ static int run_sampler(const Ctx& cx, const DenoiserArgs& q, const SampleArgs& a
       D3PM_TRY(a.guided ? posterior_sample_guided(a, s) : posterior_sample(a, s));
     }
   }
+  if (scores) D3PM_TRY(run_frame_logprob(cx, logprob_args(sh, a.rows, a.logits, a.logits_dtype, a.ldl, q.dd ? q.dd->row_of : nullptr,
+                                                          a.guided, a.guidance, a.x_next, a.pc.t, scores), s));
   if (q.dd && preps) {
     D3PM_TRY(run_dedup_index(q, a.x_next, quads_next, s));
     *prepared = *qkv_ready = true;
@@ -1006,6 +1032,7 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     q.qkv_table = ws.tab_qkv;
   }
   if (plan.dedup) q.dd = &ws.dd;
+  if (o.scores) D3PM_TRY(frame_scores_init(x, cm.frame_mask, cm.period, cm.known, o.scores->logprob, o.scores->step, rows, sh->mask_id, s));
   bool prepared = false, qkv_ready = false;      // by the previous iteration's sampler launch
   for (int t = t_start; t > t_stop; --t) {
     if (cx.prof) cx.prof->sample_now = (t % cx.prof->stride) == 0;
@@ -1016,7 +1043,8 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     a.x_next2 = trace ? trace + static_cast<size_t>(t_start - t) * rows * levels(*sh) : nullptr;
     if (flags & D3PM_FLAG_SEED_IN_HBM) a.seed_hbm = reinterpret_cast<const uint64_t*>(static_cast<uintptr_t>(seed));
     const bool preps = t - 1 > t_stop && plan.fold != FOLD_NONE;
-    D3PM_TRY(run_sampler(cx, q, a, film, t - 1, preps, plan.fold == FOLD_QUADS && !plan.m_est(sched, t - 1), s, &prepared, &qkv_ready));
+    D3PM_TRY(run_sampler(cx, q, a, film, t - 1, preps, plan.fold == FOLD_QUADS && !plan.m_est(sched, t - 1), s, &prepared, &qkv_ready,
+                         o.scores));
   }
   if (cx.prof) cx.prof->sample_now = false;
   return D3PM_OK;
@@ -1134,6 +1162,57 @@ int d3pm_sample_loop_guided(const d3pm_shape* sh, const d3pm_weights* w, const d
                           stream, CallOptions{who, either_mask(sh, batch, frame_mask, canvas), nullptr, nucleus, key_counts(keys), guidance});
 }
 
+// ---- per-frame log-probability of the revealed id (d3pm_frame_scores): the step entries and the D3PM loop ------------------------------
+int d3pm_frame_scores_init(const d3pm_shape* sh, int batch, const int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
+                           const d3pm_frame_scores* scores, void* stream) {
+  const char* who = "d3pm_frame_scores_init";
+  D3PM_TRY(check_scores(sh, scores, who));
+  D3PM_TRY(check_shape(sh, batch));
+  D3PM_REQUIRE((frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
+               "%s: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)", who);
+  D3PM_REQUIRE(x && (!canvas || canvas->frame_mask), D3PM_E_ARG, "%s: null pointer", who);
+  const CanvasMask cm = either_mask(sh, batch, frame_mask, canvas);
+  return frame_scores_init(x, cm.frame_mask, cm.period, cm.known, scores->logprob, scores->step, batch * sh->canvas, sh->mask_id,
+                           static_cast<hipStream_t>(stream));
+}
+
+int d3pm_frame_scores_step(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, int ldl, const int32_t* row_of,
+                           const d3pm_guidance* guidance, const int32_t* x_next, int t, const d3pm_frame_scores* scores, void* stream) {
+  const char* who = "d3pm_frame_scores_step";
+  D3PM_TRY(check_scores(sh, scores, who));
+  D3PM_TRY(check_shape(sh, batch));
+  if (guidance) D3PM_TRY(check_guidance(sh, guidance, who));
+  D3PM_REQUIRE(logits && x_next, D3PM_E_ARG, "%s: null pointer", who);
+  D3PM_REQUIRE(logits_dtype == D3PM_F32 || logits_dtype == D3PM_F16 || logits_dtype == D3PM_BF16, D3PM_E_ARG, "%s: unknown logits dtype %d", who,
+               logits_dtype);
+  D3PM_REQUIRE(ldl >= sh->n_classes, D3PM_E_ARG, "%s: row stride %d below n_classes %d", who, ldl, sh->n_classes);
+  D3PM_REQUIRE(t >= 1 && t <= sh->timesteps, D3PM_E_ARG, "%s: t = %d outside 1 .. %d", who, t, sh->timesteps);
+  D3PM_REQUIRE(!(row_of && guidance), D3PM_E_ARG, "%s: indexed logits take no guidance", who);
+  D3PM_REQUIRE(!(row_of && logits_dtype == D3PM_F32), D3PM_E_ARG, "%s: indexed logits are 16-bit", who);
+  return frame_logprob(logprob_args(*sh, batch * sh->canvas, logits, logits_dtype, ldl, row_of, guidance != nullptr, guidance ? guidance->weight : 0.f,
+                                    x_next, t, scores),
+                       static_cast<hipStream_t>(stream));
+}
+
+int d3pm_sample_loop_scored(const d3pm_shape* sh, const d3pm_weights* w, const d3pm_fp8_block_weights* fp8_blocks, int batch, int32_t* x,
+                            const uint8_t* frame_mask, const d3pm_canvas* canvas, int t_start, int t_stop, const void* film, const void* kv_text,
+                            const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace,
+                            size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus, const d3pm_keys* keys, const d3pm_guidance* guidance,
+                            const d3pm_frame_scores* scores, void* stream) {
+  const char* who = "d3pm_sample_loop_scored";
+  D3PM_TRY(check_scores(sh, scores, who));
+  if (guidance) D3PM_TRY(check_guidance(sh, guidance, who));
+  D3PM_REQUIRE((frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
+               "%s: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)", who);
+  D3PM_REQUIRE(!(flags & D3PM_FLAG_SEED_IN_HBM), D3PM_E_ARG, "%s: D3PM_FLAG_SEED_IN_HBM (graph replay) is not supported with frame scores", who);
+  D3PM_REQUIRE(!(fp8_blocks && (keys || guidance)), D3PM_E_ARG, "%s: the fp8 fast path takes no key mask and no guidance", who);
+  D3PM_REQUIRE(sh->n_classes <= 1280, D3PM_E_SHAPE, "%s: the frame scores support up to 1280 classes", who);
+  CallOptions o{who, either_mask(sh, batch, frame_mask, canvas), fp8_blocks, nucleus, key_counts(keys), guidance};
+  o.scores = scores;
+  return sample_loop_impl(sh, w, batch, x, t_start, t_stop, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          stream, o);
+}
+
 // ---- confidence-ordered reveal (d3pm_reveal) ------------------------------------------------------------------------------------------
 int d3pm_reveal_plan(const d3pm_schedule* sched, int n_steps, int32_t* t_out) {
   D3PM_REQUIRE(sched && t_out, D3PM_E_ARG, "d3pm_reveal_plan: null pointer");
@@ -1193,7 +1272,7 @@ int d3pm_reveal_step(const d3pm_shape* sh, int batch, const void* logits, int lo
 static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
                      const void* film, const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags,
                      void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus, const d3pm_reveal* reveal,
-                     const KeyCounts& keys, void* stream) {
+                     const KeyCounts& keys, void* stream, const d3pm_frame_scores* scores = nullptr) {
   D3PM_REQUIRE(reveal, D3PM_E_ARG, "d3pm_reveal_loop: null d3pm_reveal");
   D3PM_TRY(check_reveal(sh, batch, sched, reveal->choice_temperature, flags, "d3pm_reveal_loop"));
   D3PM_TRY(check_sampling(sh, nucleus, "d3pm_reveal_loop"));
@@ -1220,6 +1299,7 @@ static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   // Asked as for one evaluation: the reveal loop keeps the block-0 QKV projection and every row (reveal_commit_prep does not gather
   // from the table), so the moment format is all it plans.
   const int plan = loop_plan(q, flags, LoopCall{}).fold;
+  if (scores) D3PM_TRY(frame_scores_init(x, cm.frame_mask, cm.period, cm.known, scores->logprob, scores->step, rows, sh->mask_id, s));
   bool prepared = false;
   int32_t* cur = x;      // where x_t of the step lives: the fused launch cannot store in place, so it alternates between x and x_alt
   for (int i = 0; i < N; ++i) {
@@ -1232,19 +1312,23 @@ static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     RevealArgs a = reveal_args(*sh, batch, ws.logits, sh->dtype, logits_ld(*sh), cur, cm, cand, score, t, t_next, sched, seed, utt0, flags, nucleus,
                                reveal->choice_temperature);
     a.x_next2 = trace ? trace + static_cast<size_t>(i) * rows : nullptr;
-    ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0, static_cast<double>(rows) * (sh->n_classes * es + 16.0));
-    D3PM_TRY(reveal_candidates(a, s));
-    const NextIterPrep nx = t_next > 0 && plan != FOLD_NONE ? next_iter_prep(q, film, t_next, plan == FOLD_QUADS) : NextIterPrep{};
-    a.x_next = cur == x ? x_alt : x;
-    if (nx.table && reveal_commit_prep_supported(a, nx)) {
-      D3PM_TRY(reveal_commit_prep(a, nx, s));      // + the embedding rows, their moments and the fc1 fold of t_next
-      prepared = true;
-      cur = a.x_next;
-    } else {
-      a.x_next = x;      // one wave per utterance: in place when cur is x, else back into x
-      D3PM_TRY(reveal_commit(a, s));
-      cur = x;
+    {
+      ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0, static_cast<double>(rows) * (sh->n_classes * es + 16.0));
+      D3PM_TRY(reveal_candidates(a, s));
+      const NextIterPrep nx = t_next > 0 && plan != FOLD_NONE ? next_iter_prep(q, film, t_next, plan == FOLD_QUADS) : NextIterPrep{};
+      a.x_next = cur == x ? x_alt : x;
+      if (nx.table && reveal_commit_prep_supported(a, nx)) {
+        D3PM_TRY(reveal_commit_prep(a, nx, s));      // + the embedding rows, their moments and the fc1 fold of t_next
+        prepared = true;
+        cur = a.x_next;
+      } else {
+        a.x_next = x;      // one wave per utterance: in place when cur is x, else back into x
+        D3PM_TRY(reveal_commit(a, s));
+        cur = x;
+      }
     }
+    // (d3pm_reveal_loop_scored) behind the commit, on the grid it wrote: the rows this step revealed
+    if (scores) D3PM_TRY(run_frame_logprob(cx, logprob_args(*sh, rows, ws.logits, sh->dtype, logits_ld(*sh), nullptr, false, 0.f, a.x_next, t, scores), s));
   }
   if (cx.prof) cx.prof->sample_now = false;
   return D3PM_OK;      // the last step is never fused (no next evaluation): the result is in x
@@ -1263,6 +1347,16 @@ int d3pm_reveal_loop_keys(const d3pm_shape* sh, const d3pm_weights* w, int batch
                           const d3pm_reveal* reveal, const d3pm_keys* keys, void* stream) {
   return reveal_loop_impl(sh, w, batch, x, frame_mask, canvas, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
                           nucleus, reveal, key_counts(keys), stream);
+}
+
+int d3pm_reveal_loop_scored(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
+                            const void* film, const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                            uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus,
+                            const d3pm_reveal* reveal, const d3pm_keys* keys, const d3pm_frame_scores* scores, void* stream) {
+  D3PM_TRY(check_scores(sh, scores, "d3pm_reveal_loop_scored"));
+  D3PM_REQUIRE(sh->n_classes <= 1280, D3PM_E_SHAPE, "d3pm_reveal_loop_scored: the frame scores support up to 1280 classes");
+  return reveal_loop_impl(sh, w, batch, x, frame_mask, canvas, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          nucleus, reveal, key_counts(keys), stream, scores);
 }
 
 int d3pm_q_sample(const d3pm_shape* sh, int batch, const int32_t* x0, int32_t* x_out, const uint8_t* frame_mask, int t,

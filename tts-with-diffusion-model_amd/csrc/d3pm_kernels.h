@@ -276,6 +276,22 @@ int reveal_commit(const RevealArgs& a, hipStream_t s);
 bool reveal_commit_prep_supported(const RevealArgs& a, const NextIterPrep& n);
 int reveal_commit_prep(const RevealArgs& a, const NextIterPrep& n, hipStream_t s);
 
+// ---- per-frame log-probability of the revealed id (d3pm_frame_scores, d3pm_logprob.hip; n_q = 1) -------------------------------------
+// frame_scores_init: step = (live && !known && x == mask_id) ? 0 : -1, logprob = 0 over [rows].  frame_logprob, the launch behind a
+// sampler launch: a row with step 0 whose x_next is no longer the mask id gets logprob = log-softmax over the codec ids of its logits
+// at x_next and step = t; every other row is left as it is.
+struct LogprobArgs {
+  const void* logits = nullptr; int logits_dtype = D3PM_F16; int ldl = 0;
+  const int32_t* row_of = nullptr;               // [rows] or nullptr: row r reads logits[row_of[r]] (clamped into the rows; 16-bit, unguided)
+  bool guided = false; float guidance = 0.f;     // logits holds 2 * rows rows, z = rn16(fmaf(guidance, c - u, c)) (SampleArgs.guided)
+  const int32_t* x_next = nullptr;               // [rows]: the grid the sampler launch has just written
+  float* logprob = nullptr; int32_t* step = nullptr;      // [rows]
+  int rows = 0, n_classes = 0, mask_id = 0, t = 0;
+};
+int frame_scores_init(const int32_t* x, const uint8_t* frame_mask, int mask_period, const uint8_t* known, float* logprob, int32_t* step, int rows,
+                      int mask_id, hipStream_t s);
+int frame_logprob(const LogprobArgs& a, hipStream_t s);
+
 // fp8 fast path on the block-scaled MFMA (d3pm_mx.hip): e4m3 codes [rows][K] + e8m0 block scales [rows][4][K / 128]
 //   Y[M][N] = epilogue(sum_k X8 2^sx . W8 2^sw + bias), epilogue as LinearArgs (plain, GELU, R1, R1 + mask); with Y8 / SY set the
 //   output is written in the MX format itself (codes [M][N] + scales [M][4][N / 128]: the next projection's operand) instead of Y

@@ -37,6 +37,10 @@ The second form takes what those front-ends write (formats.py) and writes what E
                 the utterance does not attend to its own padding: the keys of every attention are its live frames, its phonemes and
                 its prompt frames only (include/d3pm_hip.h: d3pm_keys).  Default off: upstream has the padded rows as keys, and the
                 weights were trained that way
+  --logprobs PATH
+                also save how sure the D3PM stage was of every frame: torch.save({"logprob": float32 [N], "step": int32 [N]}) of the
+                N frames written -- the model's log-probability of the id a frame took when it left the mask, and the timestep of that
+                evaluation (-1: a frame of the --continue-from prefix; include/d3pm_hip.h: d3pm_frame_scores)
 """
 import argparse
 from pathlib import Path
@@ -67,6 +71,7 @@ def main(argv=None):
     ap.add_argument("--choice-temperature", type=float, default=0.0, help="D3PM stage, with --reveal-steps: Gumbel noise on the reveal order (>= 0)")
     ap.add_argument("--mask-padding", action="store_true", help="D3PM stage: key-padding masks, the utterance ignores its own padding")
     ap.add_argument("--guidance", type=float, default=0.0, help="D3PM stage: classifier-free guidance weight w (>= 0, 0 = off): draw from (1 + w) cond - w null")
+    ap.add_argument("--logprobs", type=Path, default=None, help="D3PM stage: save the per-frame log-probability of the revealed ids and their timesteps here")
     ap.add_argument("--native", action="store_true", help="the shape upstream's class really builds (d=32, 16 heads, 8 blocks)")
     args = ap.parse_args(argv)
 
@@ -124,12 +129,17 @@ def main(argv=None):
     n_frames = model.cfg.n_frames if args.frames is None else args.frames
     sampling = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, reveal_steps=args.reveal_steps,
                     choice_temperature=args.choice_temperature, mask_padding=args.mask_padding, guidance=args.guidance)
+    if args.logprobs is not None:      # (the keyword reaches generate_audio only when the flag is given)
+        sampling["return_logprobs"] = True
     if args.frames is None and args.continue_from is None:
         codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed, **sampling)
     else:
         prefix = None if args.continue_from is None else [formats.load_quants(args.continue_from)[:, 0]]
         codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed, n_frames=[n_frames], known=prefix,
                                      **sampling)
+    if args.logprobs is not None:
+        codes, scores = codes
+        torch.save({"logprob": scores.logprob[:n_frames].cpu(), "step": scores.step[:n_frames].cpu()}, args.logprobs)
     resps = codes[:n_frames].unsqueeze(-1)                                         # __main__.py:64 of the reference
     if args.nar_ckpt is not None:
         nar = get_model(args.nar_model)

@@ -232,6 +232,11 @@ def reveal_options(reveal_steps, choice_temperature=0.0, timesteps=None):
     return Reveal(n, C.c_float(ct).value)
 
 
+class FrameScores(C.Structure):
+    """d3pm_frame_scores: the two device grids [batch][canvas] of the per-frame log-probability (include/d3pm_hip.h)."""
+    _fields_ = [("logprob", C.c_void_p), ("step", C.c_void_p)]
+
+
 class ScheduleC(C.Structure):
     _fields_ = [("timesteps", C.c_int32), ("d", C.POINTER(C.c_uint16)), ("c", C.POINTER(C.c_uint16)),
                 ("dbar", C.POINTER(C.c_uint16)), ("cbar", C.POINTER(C.c_uint16))]
@@ -293,6 +298,19 @@ SIGNATURES = {
                                           C.POINTER(Canvas), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.POINTER(Nucleus), C.POINTER(Keys), C.POINTER(Guidance), C.c_void_p]),
+    "d3pm_frame_scores_init": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Canvas), C.POINTER(FrameScores),
+                                         C.c_void_p]),
+    "d3pm_frame_scores_step": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(Guidance), C.c_void_p,
+                                         C.c_int, C.POINTER(FrameScores), C.c_void_p]),
+    "d3pm_sample_loop_scored": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.POINTER(Canvas), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.POINTER(Nucleus), C.POINTER(Keys), C.POINTER(Guidance), C.POINTER(FrameScores),
+                                          C.c_void_p]),
+    "d3pm_reveal_loop_scored": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Canvas),
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32,
+                                          C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(Nucleus), C.POINTER(Reveal), C.POINTER(Keys),
+                                          C.POINTER(FrameScores), C.c_void_p]),
     "d3pm_denoise_step": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                     C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]),
@@ -834,15 +852,76 @@ class Sampler:
                                           _p(post), stream_ptr()), "d3pm_posterior_sample")
         return x_next, post
 
+    def _check_scores(self, scores, B):
+        """scores: a (logprob float32, step int32) pair of preallocated [B, canvas] tensors on the device -> the d3pm_frame_scores
+        struct (keeps its tensors alive)."""
+        if self.n_q != 1:
+            raise ValueError("frame scores are defined for n_q = 1")
+        if not isinstance(scores, (tuple, list)) or len(scores) != 2:
+            raise D3PMError("scores must be a (logprob float32, step int32) pair of [B, canvas] device tensors")
+        logprob, step = scores
+        _require(logprob, "scores.logprob", (B, self.cfg.canvas), (torch.float32,), self.device)
+        _require(step, "scores.step", (B, self.cfg.canvas), (torch.int32,), self.device)
+        fs = FrameScores(logprob.data_ptr(), step.data_ptr())
+        fs._keep = (logprob, step)
+        return fs
+
+    def new_scores(self, B):
+        """A (logprob, step) pair for `scores=`: float32 / int32 [B, canvas] on the sampler's device (contents set by the library)."""
+        return (torch.empty((B, self.cfg.canvas), dtype=torch.float32, device=self.device),
+                torch.empty((B, self.cfg.canvas), dtype=torch.int32, device=self.device))
+
+    def frame_scores_init(self, x, frame_mask, scores, known=None):
+        """d3pm_frame_scores_init on the canvas x a loop is about to start from: step = 0 on the free masked rows, -1 elsewhere, logprob
+        = 0.  frame_mask uint8 [canvas] or [B, canvas]; known uint8 [B, canvas] or None; scores as for sample_loop."""
+        per_utt = known is not None or (isinstance(frame_mask, torch.Tensor) and frame_mask.dim() == 2)
+        B = self._check_grid(x, None if per_utt else frame_mask, "x")
+        cv = self._check_canvas(B, frame_mask, known) if per_utt else None
+        fs = self._check_scores(scores, B)
+        check(lib().d3pm_frame_scores_init(C.byref(self.shape), B, _p(x), None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None,
+                                           C.byref(fs), stream_ptr()), "d3pm_frame_scores_init")
+
+    def frame_scores_step(self, logits, x_next, t, scores, *, row_of=None, guidance=0.0, null_logits=None):
+        """d3pm_frame_scores_step behind one sampler step: the rows of `scores` with step 0 whose x_next is no longer the mask id get the
+        log-probability of that id under `logits` (the evaluation at t) and step = t.  logits [B, canvas, n_classes] (any of the three
+        dtypes); guidance (> 0) with null_logits as for posterior_sample; row_of int32 [B * canvas] with logits [B * canvas,
+        n_classes] (16-bit, a view with a wider row stride allowed): row r reads logits[row_of[r]], clamped into the rows."""
+        cfg = self.cfg
+        gd = guidance_options(guidance)
+        if (gd is None) != (null_logits is None):
+            raise ValueError("guidance and null_logits go together: a weight > 0 needs the null logits, and they need a weight")
+        B = self._check_grid(x_next, None, "x_next")
+        fs = self._check_scores(scores, B)
+        rows = B * cfg.canvas
+        if row_of is not None:
+            if not isinstance(logits, torch.Tensor) or tuple(logits.shape) != (rows, cfg.n_classes) or logits.dtype not in _DTYPES or \
+                    logits.device != self.device or logits.stride(1) != 1 or logits.stride(0) < cfg.n_classes:
+                raise D3PMError(f"logits must be a [{rows}, {cfg.n_classes}] tensor on {self.device} with unit column stride")
+            _require_int32([("row_of", row_of, (rows,))], self.device)
+            ldl = logits.stride(0)
+        else:
+            logits = logits.contiguous() if isinstance(logits, torch.Tensor) else logits
+            _require(logits, "logits", (B, cfg.canvas, cfg.n_classes), tuple(_DTYPES), self.device)
+            ldl = cfg.n_classes
+            if gd is not None:
+                _require(null_logits, "null_logits", tuple(logits.shape), (logits.dtype,), self.device)
+                logits = torch.cat([logits, null_logits.contiguous()], 0)      # [2B, canvas, K]: the null twins behind the conditioned rows
+        check(lib().d3pm_frame_scores_step(C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), int(ldl), _p(row_of),
+                                           None if gd is None else C.byref(gd), _p(x_next), int(t), C.byref(fs), stream_ptr()),
+              "d3pm_frame_scores_step")
+
     def sample_loop(self, x, frame_mask, t_start, t_stop, kv_t, kv_p, seed, utt0=0, flags=0, trace=False, slot=0,
-                    fp8=False, known=None, temperature=1.0, top_k=0, top_p=1.0, keys=None, guidance=0.0):
+                    fp8=False, known=None, temperature=1.0, top_k=0, top_p=1.0, keys=None, guidance=0.0, scores=None):
         """frame_mask uint8 [canvas] (shared by the batch) runs d3pm_sample_loop(_fp8); a per-utterance mask [B, canvas] and / or a
         known-frame map `known` (uint8 [B, canvas]; `x` already carries the given ids) run the *_canvas entries.  temperature /
         top_k other than the neutral (1, 0) run d3pm_sample_loop_sampling, which covers the four of them; top_p other than 1 runs
         d3pm_sample_loop_nucleus, which takes the same arguments.  keys: None or the (frames, text, prompt) key counts of make_keys
         (d3pm_sample_loop_keys, which covers all of the above but fp8).  guidance > 0 (classifier-free guidance,
         d3pm_sample_loop_guided): kv_t / kv_p hold 2B utterances -- the null twins behind the conditioned ones -- and so do the three
-        arrays of `keys`; x, frame_mask, known and the trace stay those of B utterances.  No fp8, no n_q > 1."""
+        arrays of `keys`; x, frame_mask, known and the trace stay those of B utterances.  No fp8, no n_q > 1.
+        scores: None (the branches above, untouched) or a (logprob float32, step int32) pair of preallocated [B, canvas] tensors
+        (new_scores) that d3pm_sample_loop_scored fills with the per-frame log-probability of the revealed ids (n_q = 1; it covers
+        every combination above)."""
         cfg = self.cfg
         smp = nucleus_options(temperature, top_k, top_p, cfg.n_classes)
         gd = guidance_options(guidance)
@@ -853,11 +932,22 @@ class Sampler:
         per_utt = known is not None or (isinstance(frame_mask, torch.Tensor) and frame_mask.dim() == 2)
         B = self._check_grid(x, None if per_utt else frame_mask, "x")
         cv = self._check_canvas(B, frame_mask, known) if per_utt else None
+        fs = None if scores is None else self._check_scores(scores, B)
         eval_B = B if gd is None else 2 * B
         self._check_kv(kv_t, kv_p, eval_B)
         ks = make_keys(keys, eval_B, self.device)
         ws = self.workspace(eval_B, slot)
         tr = torch.empty((t_start - t_stop, B, cfg.canvas) + self._lvl(), dtype=torch.int32, device=self.device) if trace else None
+        if fs is not None:
+            nuc = self._as_nucleus(smp)
+            check(lib().d3pm_sample_loop_scored(C.byref(self.shape), C.byref(self.weights.c_struct),
+                                                C.cast(self.fp8_weights().blocks, C.c_void_p) if fp8 else None, B, _p(x),
+                                                None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None,
+                                                int(t_start), int(t_stop), _p(self.film), _p(kv_t), _p(kv_p),
+                                                C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
+                                                None if nuc is None else C.byref(nuc), None if ks is None else C.byref(ks),
+                                                None if gd is None else C.byref(gd), C.byref(fs), stream_ptr()), "d3pm_sample_loop_scored")
+            return tr
         if gd is not None:
             nuc = self._as_nucleus(smp)
             check(lib().d3pm_sample_loop_guided(C.byref(self.shape), C.byref(self.weights.c_struct), None, B, _p(x),
@@ -948,9 +1038,10 @@ class Sampler:
         return x_next, cand, score
 
     def reveal_loop(self, x, frame_mask, n_steps, kv_t, kv_p, seed, utt0=0, flags=0, trace=False, slot=0, known=None, temperature=1.0,
-                    top_k=0, top_p=1.0, choice_temperature=0.0, keys=None):
+                    top_k=0, top_p=1.0, choice_temperature=0.0, keys=None, scores=None):
         """The reveal schedule in n_steps denoiser evaluations (d3pm_reveal_loop), in place on x; masks and known frames as for
-        sample_loop.  keys: None or the (frames, text, prompt) key counts of make_keys (d3pm_reveal_loop_keys).
+        sample_loop.  keys: None or the (frames, text, prompt) key counts of make_keys (d3pm_reveal_loop_keys).  scores: None or the
+        (logprob, step) pair of sample_loop (d3pm_reveal_loop_scored).
         -> the trace int32 [n_steps, B, canvas] (x after every step) or None."""
         cfg = self.cfg
         smp = self._as_nucleus(nucleus_options(temperature, top_k, top_p, cfg.n_classes))
@@ -964,8 +1055,16 @@ class Sampler:
         cv = self._check_canvas(B, frame_mask, known) if per_utt else None
         self._check_kv(kv_t, kv_p, B)
         ws = self.workspace(B, slot)
+        fs = None if scores is None else self._check_scores(scores, B)
         tr = torch.empty((rv.n_steps, B, cfg.canvas), dtype=torch.int32, device=self.device) if trace else None
         ks = make_keys(keys, B, self.device)
+        if fs is not None:
+            check(lib().d3pm_reveal_loop_scored(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), None if per_utt else _p(frame_mask),
+                                                C.byref(cv) if per_utt else None, _p(self.film), _p(kv_t), _p(kv_p),
+                                                C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
+                                                None if smp is None else C.byref(smp), C.byref(rv), None if ks is None else C.byref(ks),
+                                                C.byref(fs), stream_ptr()), "d3pm_reveal_loop_scored")
+            return tr
         if ks is not None:
             check(lib().d3pm_reveal_loop_keys(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), None if per_utt else _p(frame_mask),
                                               C.byref(cv) if per_utt else None, _p(self.film), _p(kv_t), _p(kv_p),

@@ -18,6 +18,7 @@ Differences from upstream, all opt-in or strictly more general:
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 from numbers import Integral
 from typing import Optional, Sequence, Union
 
@@ -27,6 +28,9 @@ from torch import Tensor, nn
 
 from . import _hip
 from .synth import MASK_ID, N_CLASSES, D3PMConfig
+
+# generate_audio(return_logprobs=True): logprob float32 and step int32, [B, canvas] each (include/d3pm_hip.h: d3pm_frame_scores)
+FrameScores = namedtuple("FrameScores", ("logprob", "step"))
 
 
 class _Mlp(nn.Module):
@@ -373,7 +377,8 @@ class AR(SymmapState, nn.Module):
                        known_mask: Optional[Sequence[Optional[Tensor]]] = None, temperature: float = 1.0, top_k: int = 0,
                        top_p: float = 1.0, reveal_steps: Optional[int] = None, choice_temperature: float = 0.0,
                        mask_padding: bool = False, guidance: float = 0.0,
-                       null_text_list: Optional[Sequence[Tensor]] = None, null_proms_list: Optional[Sequence[Tensor]] = None):
+                       null_text_list: Optional[Sequence[Tensor]] = None, null_proms_list: Optional[Sequence[Tensor]] = None,
+                       return_logprobs: bool = False):
         """Reverse diffusion for len(text_list) utterances.  Positional behaviour as upstream:
         one utterance -> int64 [canvas] (squeezed, untrimmed; rows >= n_frames are sampled from
         final.bias and meaningless); with n_q > 1 (constructor) [canvas, n_q] / [B, canvas, n_q].  `resps_list` is ignored, as
@@ -444,10 +449,29 @@ class AR(SymmapState, nn.Module):
         its frames are its partner's); with graph=True, fp8=True, reveal_steps or an n_q > 1 model it raises ValueError before any
         GPU work, as do a negative, non-finite or bool weight and null lists without guidance or of the wrong length.  Guidance
         is meaningful for weights trained with the conditions dropped some of the time (forward_backward(cond_drop=...)); no
-        statement about audio quality is made for the synthetic or the upstream weights."""
+        statement about audio quality is made for the synthetic or the upstream weights.
+        `return_logprobs=True` (default False: the loops above, untouched) also returns how sure the model was of every frame it
+        revealed (include/d3pm_hip.h: d3pm_frame_scores): the result becomes (ids, scores), or (ids, trace, scores) with return_trace,
+        where scores is the named pair FrameScores(logprob float32, step int32), [B, canvas] each and squeezed like ids for one
+        utterance.  step is -1 for a frame that was padding, known or already an id when the loop started, else the timestep of the
+        evaluation that revealed the frame (0: still masked); logprob is the model's log-probability of the id the frame took in
+        that iteration among the codec ids -- log-softmax of that evaluation's logits (under guidance: of the guided logits) with the
+        mask class removed, and WITHOUT temperature / top_k / top_p, so the number compares across sampling options and is always
+        finite; 0.0 where step < 1.  On the default path a revealed frame is still redrawn every iteration and may, rarely, change
+        later: logprob belongs to the id taken at `step`.  One short launch more per iteration; the ids are bit for bit those of
+        the call without it.  It composes with everything the two loops compose with -- n_frames, known / known_mask, temperature /
+        top_k / top_p, greedy, mask_padding, guidance, fp8, steps, reveal_steps, utt0 / global_batch and streams; a value that is
+        not a bool, graph=True or an n_q > 1 model raise ValueError before any GPU work.  To regenerate the least sure frames call
+        again with known = ids and known_mask = logprob >= threshold."""
         if len(text_list) != len(proms_list) or len(text_list) == 0:
             raise ValueError("text_list and proms_list must be non-empty and of equal length")
         B = len(text_list)
+        if not isinstance(return_logprobs, bool):
+            raise ValueError(f"return_logprobs must be a bool, got {return_logprobs!r}")
+        if return_logprobs:
+            for name, bad in (("graph=True", bool(graph)), ("an n_q > 1 model", self.cfg.n_q > 1)):
+                if bad:
+                    raise ValueError(f"return_logprobs does not combine with {name}")
         guided = _hip.guidance_options(guidance) is not None      # host validation before any GPU work
         if not guided and (null_text_list is not None or null_proms_list is not None):
             raise ValueError("null_text_list / null_proms_list without guidance")
@@ -514,6 +538,10 @@ class AR(SymmapState, nn.Module):
             if not per_utt:
                 x, frame_mask, kmap = self.canvas_init(B, n_frames) + (None,)
             fl = flags | (_hip.FLAG_GREEDY if greedy else 0)
+            scores = smp.new_scores(B) if return_logprobs else None      # (logprob, step), [B, canvas]: a stream chunk gets its slice
+
+            def scored(lo=0, hi=B):      # the keyword reaches the loops only when asked for
+                return {} if scores is None else {"scores": tuple(g[lo:hi] for g in scores)}
             use_graph = bool(graph)
             if fp8 and (use_graph or (n_streams > 1 and not return_trace)):
                 raise ValueError("fp8=True runs on the single-stream eager loop only (no graph replay, no stream chunks)")
@@ -527,10 +555,10 @@ class AR(SymmapState, nn.Module):
                 if rv is not None:
                     trace = smp.reveal_loop(x, frame_mask, rv.n_steps, kv_t, kv_p, seed, utt0, fl, trace=return_trace, known=kmap,
                                             temperature=temperature, top_k=top_k, top_p=top_p, choice_temperature=rv.choice_temperature,
-                                            keys=keys)
+                                            keys=keys, **scored())
                 else:
                     trace = smp.sample_loop(x, frame_mask, t_start, 0, kv_t, kv_p, seed, utt0, fl, trace=return_trace, fp8=fp8, known=kmap,
-                                            temperature=temperature, top_k=top_k, top_p=top_p, keys=keys, guidance=guidance)
+                                            temperature=temperature, top_k=top_k, top_p=top_p, keys=keys, guidance=guidance, **scored())
             else:
                 # utterances are independent: chunks of the batch run the whole loop on their own stream so that
                 # the short kernels of one chunk fill the ramp-up / epilogue bubbles of the others
@@ -548,17 +576,20 @@ class AR(SymmapState, nn.Module):
                         if rv is not None:
                             smp.reveal_loop(x[lo:hi], frame_mask[lo:hi] if per_utt else frame_mask, rv.n_steps, kv_t, kv_p, seed, utt0 + lo, fl,
                                             slot=i, known=None if kmap is None else kmap[lo:hi], temperature=temperature, top_k=top_k,
-                                            top_p=top_p, choice_temperature=rv.choice_temperature, keys=chunk_keys(lo, hi))
+                                            top_p=top_p, choice_temperature=rv.choice_temperature, keys=chunk_keys(lo, hi), **scored(lo, hi))
                         else:
                             smp.sample_loop(x[lo:hi], frame_mask[lo:hi] if per_utt else frame_mask, t_start, 0, kv_t, kv_p, seed, utt0 + lo, fl,
                                             slot=i, known=None if kmap is None else kmap[lo:hi], temperature=temperature, top_k=top_k,
-                                            top_p=top_p, keys=chunk_keys(lo, hi), guidance=guidance)
-                        for t_ in (kv_t, kv_p, cond_text, cond_prompt, x):
+                                            top_p=top_p, keys=chunk_keys(lo, hi), guidance=guidance, **scored(lo, hi))
+                        for t_ in (kv_t, kv_p, cond_text, cond_prompt, x) + (scores or ()):
                             t_.record_stream(st)
                 for i in range(n_streams):
                     cur.wait_stream(self._streams[i])
         out = x.long()
         out = out[0] if B == 1 else out
+        if return_logprobs:
+            fs = FrameScores(*(g[0] if B == 1 else g for g in scores))
+            return (out, trace, fs) if return_trace else (out, fs)
         return (out, trace) if return_trace else out
 
     # ------------------------------------------------------------------ upstream method names
