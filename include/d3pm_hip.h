@@ -70,7 +70,8 @@ extern "C" {
  *    (d3pm_op_nar_embed, d3pm_op_adaln, d3pm_op_nar_sample); the latency GEMM family in the iterations of the deduplicated loop
  *    that have few live rows (d3pm_op_linear_live_est; ln_fold value 4 = the deduplicated loop without that switch); the per-frame
  *    log-probability of the revealed id from either loop (d3pm_frame_scores, d3pm_frame_scores_init, d3pm_frame_scores_step,
- *    d3pm_sample_loop_scored, d3pm_reveal_loop_scored) */
+ *    d3pm_sample_loop_scored, d3pm_reveal_loop_scored); the reveal schedule whose held frames compete again in every step
+ *    (d3pm_revise, d3pm_reveal_step_revise, d3pm_reveal_loop_revise) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -750,6 +751,63 @@ int d3pm_reveal_loop_scored(const d3pm_shape *shape, const d3pm_weights *weights
                             const void *kv_prompt, const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags,
                             void *workspace, size_t workspace_bytes, int32_t *trace, const d3pm_nucleus *nucleus,
                             const d3pm_reveal *reveal, const d3pm_keys *keys, const d3pm_frame_scores *scores, void *stream);
+
+/* ---- reveal with revision: later steps re-mask frames the model has come to doubt (additions; ABI version unchanged) ------------------
+ * By its definition a row revealed by d3pm_reveal "is never drawn again": a frame committed from an almost empty canvas at step 0
+ * stays, whatever the later evaluations say about it.  With d3pm_revise the frames that already hold an id compete again for their
+ * place in every step (the Token-Critic / remasking family of decoders).  No statement about audio quality is made; what follows is
+ * an exact definition.  Everything of d3pm_reveal holds unless changed here: the timesteps t_i, FREE rows, the Philox keys,
+ * D3PM_FLAG_GREEDY, temperature / top_k / top_p on masked rows, canvas <= 1024 and n_q = 1.
+ *   rows       a free row is MASKED (x_t == mask_id) or HELD (it holds an id j != mask_id): a row revealed by an earlier step is
+ *              held, and so is a free row that was already an id when the loop started.
+ * At the step that evaluates at t_i and is followed by t_{i+1}:
+ *   masked row cand and score are those of d3pm_reveal, bit for bit: the same routine, arguments and noise.
+ *   held row   with id j: cand = j.  conf_h is the logprob that d3pm_frame_scores defines for id j on this evaluation's logits:
+ *              z = rn16(logit), mask class removed, NO temperature / top_k / top_p, the arithmetic order stated there -- bit for bit
+ *              what d3pm_frame_scores_step reports for that row and id.  It is always finite, so a sampling filter can never force
+ *              a re-mask.  score = (conf_h + hold_bonus) + lambda_i * gumbel(v): one fp32 add, then the same statement that turns
+ *              a masked row's conf into its score; lambda_i and v (Philox key (seed; 0, global row, t_i, stream 4)) are unchanged.
+ *              choice_temperature = 0, D3PM_FLAG_GREEDY and the last step draw no v.  An id j >= n_classes is outside the
+ *              contract; no memory is read through j.
+ *   quota      after the step utterance b holds  hold = F_b - floor((double) F_b * (double) float(cbar[t_{i+1}]))  ids on its free
+ *              rows; after the last step it holds F_b.  The masked count after step i is therefore floor(F_b * cbar[t_{i+1}]),
+ *              whatever the canvas looked like before; it does not grow from one step to the next, since cbar falls with t.
+ *   selection  the order is the existing one: the uint32 image of the score, descending, then frame index ascending.  The `hold`
+ *              free rows that come first among ALL free rows hold an id after the step: a selected masked row takes cand, a
+ *              selected held row keeps its id, an unselected masked row stays masked, an unselected held row is re-masked (takes
+ *              mask_id).  Known and padded rows are never given a value.  In place (x_next == x_t) only changed rows are stored.
+ *              Given the scores the device reports, the result is exact.
+ *   cand_out / score_out  receive a value for every free row; rows that are not free are left unwritten.
+ *   frame scores  (optional d3pm_frame_scores) the commit launch sets step = 0, logprob = 0.0f on every row it re-masks, including a
+ *              row whose step was -1 because it entered the loop as an id.  The existing launch behind it is unchanged: a re-masked
+ *              row therefore records its next reveal, and at loop exit step / logprob describe the LAST time a row left the mask.
+ *              Rows never re-masked keep what they had, bit for bit.
+ * hold_bonus is the stickiness: 0 lets held and masked rows compete on equal terms; a bonus larger than any |conf| pins every held
+ * row, so that rows are re-masked only where the quota demands it.
+ * Refused with D3PM_E_ARG, nothing launched and no pointer read: a NULL d3pm_revise, a negative or non-finite hold_bonus; and
+ * everything d3pm_reveal refuses.  Kernels of their own: a call without d3pm_revise runs none of this code. */
+typedef struct d3pm_revise {
+  float hold_bonus;     /* finite, >= 0 */
+} d3pm_revise;
+
+/* d3pm_reveal_step under d3pm_revise, the definition above: its arguments, then revise and the optional scores (NULL: no grids; else
+ * both grids, which the commit launch resets on the rows it re-masks -- the launch behind it stays the caller's,
+ * d3pm_frame_scores_step on x_next). */
+int d3pm_reveal_step_revise(const d3pm_shape *shape, int batch, const void *logits, int logits_dtype, const int32_t *x_t,
+                            int32_t *x_next, const uint8_t *frame_mask, const d3pm_canvas *canvas, int t, int t_next,
+                            const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags, const d3pm_nucleus *nucleus,
+                            float choice_temperature, int32_t *cand_out, float *score_out, const d3pm_revise *revise,
+                            const d3pm_frame_scores *scores, void *stream);
+
+/* d3pm_reveal_loop_scored under d3pm_revise, the definition above; keys and scores are optional (NULL).  The loop equals
+ * d3pm_frame_scores_init + the chained d3pm_reveal_step_revise / d3pm_frame_scores_step entries, step by step; the second launch is
+ * the fused one wherever d3pm_reveal_loop's is. */
+int d3pm_reveal_loop_revise(const d3pm_shape *shape, const d3pm_weights *weights, int batch, int32_t *x,
+                            const uint8_t *frame_mask, const d3pm_canvas *canvas, const void *film, const void *kv_text,
+                            const void *kv_prompt, const d3pm_schedule *sched, uint64_t seed, uint32_t utt0, uint32_t flags,
+                            void *workspace, size_t workspace_bytes, int32_t *trace, const d3pm_nucleus *nucleus,
+                            const d3pm_reveal *reveal, const d3pm_keys *keys, const d3pm_revise *revise,
+                            const d3pm_frame_scores *scores, void *stream);
 
 /* Replaces AR.q_sample / q_probs (ar_discrete.py:467-502): forward noising of x0 at step t with
  * Philox stream 1.  x0, x_out device int32 [batch][canvas]. */

@@ -1269,10 +1269,45 @@ int d3pm_reveal_step(const d3pm_shape* sh, int batch, const void* logits, int lo
   return reveal_commit(a, s);
 }
 
+// what the entries that take d3pm_revise refuse before anything else is looked at
+static int check_revise(const d3pm_revise* revise, const char* who) {
+  D3PM_REQUIRE(revise, D3PM_E_ARG, "%s: null d3pm_revise", who);
+  D3PM_REQUIRE(std::isfinite(revise->hold_bonus) && revise->hold_bonus >= 0.f, D3PM_E_ARG, "%s: hold_bonus %g is not a finite number >= 0", who,
+               static_cast<double>(revise->hold_bonus));
+  return D3PM_OK;
+}
+
+// d3pm_reveal_step under d3pm_revise (include/d3pm_hip.h, "reveal with revision"): the two launches of d3pm_revise.hip
+int d3pm_reveal_step_revise(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t, int32_t* x_next,
+                            const uint8_t* frame_mask, const d3pm_canvas* canvas, int t, int t_next, const d3pm_schedule* sched, uint64_t seed,
+                            uint32_t utt0, uint32_t flags, const d3pm_nucleus* nucleus, float choice_temperature, int32_t* cand_out, float* score_out,
+                            const d3pm_revise* revise, const d3pm_frame_scores* scores, void* stream) {
+  const char* who = "d3pm_reveal_step_revise";
+  D3PM_TRY(check_revise(revise, who));
+  D3PM_TRY(check_reveal(sh, batch, sched, choice_temperature, flags, who));
+  D3PM_TRY(check_sampling(sh, nucleus, who));
+  if (scores) D3PM_TRY(check_scores(sh, scores, who));
+  D3PM_REQUIRE((frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
+               "%s: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)", who);
+  D3PM_REQUIRE(logits && x_t && x_next && cand_out && score_out && (!canvas || canvas->frame_mask), D3PM_E_ARG, "%s: null pointer", who);
+  D3PM_REQUIRE(t >= 1 && t < sched->timesteps && t_next >= 0 && t_next < t, D3PM_E_ARG, "%s: t = %d, t_next = %d outside %d > t > t_next >= 0", who, t,
+               t_next, sched->timesteps);
+  ReviseArgs v;
+  v.r = reveal_args(*sh, batch, logits, logits_dtype, sh->n_classes, x_t, either_mask(sh, batch, frame_mask, canvas), cand_out, score_out, t, t_next,
+                    sched, seed, utt0, flags, nucleus, choice_temperature);
+  v.r.x_next = x_next;
+  v.hold_bonus = revise->hold_bonus;
+  if (scores) { v.logprob = scores->logprob; v.step = scores->step; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  D3PM_TRY(revise_candidates(v, s));
+  return revise_commit(v, s);
+}
+
+// revise (d3pm_reveal_loop_revise): the two launches of every step are those of d3pm_revise.hip; null: every launch is d3pm_reveal's
 static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
                      const void* film, const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags,
                      void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus, const d3pm_reveal* reveal,
-                     const KeyCounts& keys, void* stream, const d3pm_frame_scores* scores = nullptr) {
+                     const KeyCounts& keys, void* stream, const d3pm_frame_scores* scores = nullptr, const d3pm_revise* revise = nullptr) {
   D3PM_REQUIRE(reveal, D3PM_E_ARG, "d3pm_reveal_loop: null d3pm_reveal");
   D3PM_TRY(check_reveal(sh, batch, sched, reveal->choice_temperature, flags, "d3pm_reveal_loop"));
   D3PM_TRY(check_sampling(sh, nucleus, "d3pm_reveal_loop"));
@@ -1314,16 +1349,26 @@ static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     a.x_next2 = trace ? trace + static_cast<size_t>(i) * rows : nullptr;
     {
       ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0, static_cast<double>(rows) * (sh->n_classes * es + 16.0));
-      D3PM_TRY(reveal_candidates(a, s));
+      // under d3pm_revise each launch is its twin of d3pm_revise.hip, which also takes the bonus and the grids to reset
+      auto revised = [&](const RevealArgs& r) {
+        ReviseArgs v;
+        v.r = r; v.hold_bonus = revise->hold_bonus;
+        if (scores) { v.logprob = scores->logprob; v.step = scores->step; }
+        return v;
+      };
+      if (revise) D3PM_TRY(revise_candidates(revised(a), s));
+      else D3PM_TRY(reveal_candidates(a, s));
       const NextIterPrep nx = t_next > 0 && plan != FOLD_NONE ? next_iter_prep(q, film, t_next, plan == FOLD_QUADS) : NextIterPrep{};
       a.x_next = cur == x ? x_alt : x;
       if (nx.table && reveal_commit_prep_supported(a, nx)) {
-        D3PM_TRY(reveal_commit_prep(a, nx, s));      // + the embedding rows, their moments and the fc1 fold of t_next
+        if (revise) D3PM_TRY(revise_commit_prep(revised(a), nx, s));
+        else D3PM_TRY(reveal_commit_prep(a, nx, s));      // + the embedding rows, their moments and the fc1 fold of t_next
         prepared = true;
         cur = a.x_next;
       } else {
         a.x_next = x;      // one wave per utterance: in place when cur is x, else back into x
-        D3PM_TRY(reveal_commit(a, s));
+        if (revise) D3PM_TRY(revise_commit(revised(a), s));
+        else D3PM_TRY(reveal_commit(a, s));
         cur = x;
       }
     }
@@ -1357,6 +1402,21 @@ int d3pm_reveal_loop_scored(const d3pm_shape* sh, const d3pm_weights* w, int bat
   D3PM_REQUIRE(sh->n_classes <= 1280, D3PM_E_SHAPE, "d3pm_reveal_loop_scored: the frame scores support up to 1280 classes");
   return reveal_loop_impl(sh, w, batch, x, frame_mask, canvas, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
                           nucleus, reveal, key_counts(keys), stream, scores);
+}
+
+// d3pm_reveal_loop_scored under d3pm_revise (include/d3pm_hip.h, "reveal with revision"); keys and scores optional
+int d3pm_reveal_loop_revise(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
+                            const void* film, const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                            uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus,
+                            const d3pm_reveal* reveal, const d3pm_keys* keys, const d3pm_revise* revise, const d3pm_frame_scores* scores,
+                            void* stream) {
+  D3PM_TRY(check_revise(revise, "d3pm_reveal_loop_revise"));
+  if (scores) {
+    D3PM_TRY(check_scores(sh, scores, "d3pm_reveal_loop_revise"));
+    D3PM_REQUIRE(sh->n_classes <= 1280, D3PM_E_SHAPE, "d3pm_reveal_loop_revise: the frame scores support up to 1280 classes");
+  }
+  return reveal_loop_impl(sh, w, batch, x, frame_mask, canvas, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
+                          nucleus, reveal, key_counts(keys), stream, scores, revise);
 }
 
 int d3pm_q_sample(const d3pm_shape* sh, int batch, const int32_t* x0, int32_t* x_out, const uint8_t* frame_mask, int t,

@@ -276,6 +276,19 @@ int reveal_commit(const RevealArgs& a, hipStream_t s);
 bool reveal_commit_prep_supported(const RevealArgs& a, const NextIterPrep& n);
 int reveal_commit_prep(const RevealArgs& a, const NextIterPrep& n, hipStream_t s);
 
+// The same step under d3pm_revise (d3pm_revise.hip, kernels of their own): revise_candidates writes cand / score of every FREE row
+// (a held row: its own id, and logprob of that id + hold_bonus + the order noise), revise_commit / revise_commit_prep leave
+// F - floor(F keep_frac) free rows with an id, may store mask_id, and reset logprob / step (both or neither; [rows]) on the rows they
+// re-mask.  revise_commit_prep applies wherever reveal_commit_prep_supported(v.r, n) holds.
+struct ReviseArgs {
+  RevealArgs r;
+  float hold_bonus = 0.f;
+  float* logprob = nullptr; int32_t* step = nullptr;
+};
+int revise_candidates(const ReviseArgs& v, hipStream_t s);
+int revise_commit(const ReviseArgs& v, hipStream_t s);
+int revise_commit_prep(const ReviseArgs& v, const NextIterPrep& n, hipStream_t s);
+
 // ---- per-frame log-probability of the revealed id (d3pm_frame_scores, d3pm_logprob.hip; n_q = 1) -------------------------------------
 // frame_scores_init: step = (live && !known && x == mask_id) ? 0 : -1, logprob = 0 over [rows].  frame_logprob, the launch behind a
 // sampler launch: a row with step 0 whose x_next is no longer the mask id gets logprob = log-softmax over the codec ids of its logits

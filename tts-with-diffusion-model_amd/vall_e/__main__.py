@@ -33,6 +33,10 @@ The second form takes what those front-ends write (formats.py) and writes what E
                 run the D3PM stage as a confidence-ordered reveal in N denoiser evaluations (1 .. timesteps - 1; default: the
                 timesteps - 1 evaluations of the D3PM loop): every step reveals the frames the model is most sure of; F (>= 0,
                 default 0) adds annealed Gumbel noise to that order (include/d3pm_hip.h: d3pm_reveal)
+  --revise [BONUS]
+                with --reveal-steps: in every step the frames that already hold an id compete again for their place and may be
+                re-masked; BONUS (>= 0, default 0 when the flag is bare) is added to a held frame's log-probability before it is
+                ranked against the masked frames (include/d3pm_hip.h: d3pm_revise)
   --mask-padding
                 the utterance does not attend to its own padding: the keys of every attention are its live frames, its phonemes and
                 its prompt frames only (include/d3pm_hip.h: d3pm_keys).  Default off: upstream has the padded rows as keys, and the
@@ -69,6 +73,8 @@ def main(argv=None):
     ap.add_argument("--top-p", type=float, default=1.0, help="D3PM stage: draw from the smallest set of classes that carries this share of the mass (1 = off)")
     ap.add_argument("--reveal-steps", type=int, default=None, help="D3PM stage: confidence-ordered reveal in this many denoiser evaluations")
     ap.add_argument("--choice-temperature", type=float, default=0.0, help="D3PM stage, with --reveal-steps: Gumbel noise on the reveal order (>= 0)")
+    ap.add_argument("--revise", type=float, nargs="?", const=0.0, default=None, metavar="BONUS",
+                    help="D3PM stage, with --reveal-steps: held frames compete again in every step; BONUS (>= 0, default 0) favours them")
     ap.add_argument("--mask-padding", action="store_true", help="D3PM stage: key-padding masks, the utterance ignores its own padding")
     ap.add_argument("--guidance", type=float, default=0.0, help="D3PM stage: classifier-free guidance weight w (>= 0, 0 = off): draw from (1 + w) cond - w null")
     ap.add_argument("--logprobs", type=Path, default=None, help="D3PM stage: save the per-frame log-probability of the revealed ids and their timesteps here")
@@ -82,6 +88,8 @@ def main(argv=None):
         _hip.reveal_options(args.reveal_steps, args.choice_temperature)
         if _hip.guidance_options(args.guidance) is not None and args.reveal_steps is not None:
             raise ValueError("--guidance does not combine with --reveal-steps")
+        if _hip.revise_options(args.revise) is not None and args.reveal_steps is None:
+            raise ValueError("--revise needs --reveal-steps")
     except ValueError as e:
         ap.error(str(e))
     if len(args.paths) not in (1, 3):
@@ -131,6 +139,8 @@ def main(argv=None):
                     choice_temperature=args.choice_temperature, mask_padding=args.mask_padding, guidance=args.guidance)
     if args.logprobs is not None:      # (the keyword reaches generate_audio only when the flag is given)
         sampling["return_logprobs"] = True
+    if args.revise is not None:
+        sampling["revise"] = args.revise
     if args.frames is None and args.continue_from is None:
         codes = model.generate_audio(text_list=[phns], proms_list=[proms], seed=args.seed, **sampling)
     else:

@@ -232,6 +232,24 @@ def reveal_options(reveal_steps, choice_temperature=0.0, timesteps=None):
     return Reveal(n, C.c_float(ct).value)
 
 
+class Revise(C.Structure):
+    """d3pm_revise: the reveal schedule whose held frames compete again in every step (include/d3pm_hip.h)."""
+    _fields_ = [("hold_bonus", C.c_float)]
+
+
+def revise_options(revise=None):
+    """Host validation of the revise option (ValueError, before any GPU work) -> None for None (the entries and kernels that know
+    nothing of it), a Revise struct for a real number >= 0: the hold bonus, 0 included."""
+    if revise is None:
+        return None
+    if isinstance(revise, bool) or not isinstance(revise, (int, float)):
+        raise ValueError(f"revise must be None or a number (the hold bonus), got {revise!r}")
+    hb = float(revise)
+    if not (math.isfinite(hb) and hb >= 0.0) or not math.isfinite(C.c_float(hb).value):
+        raise ValueError(f"revise (the hold bonus) must be finite and >= 0, got {revise!r}")
+    return Revise(C.c_float(hb).value)
+
+
 class FrameScores(C.Structure):
     """d3pm_frame_scores: the two device grids [batch][canvas] of the per-frame log-probability (include/d3pm_hip.h)."""
     _fields_ = [("logprob", C.c_void_p), ("step", C.c_void_p)]
@@ -311,6 +329,14 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32,
                                           C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(Nucleus), C.POINTER(Reveal), C.POINTER(Keys),
                                           C.POINTER(FrameScores), C.c_void_p]),
+    "d3pm_reveal_step_revise": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(Canvas), C.c_int, C.c_int, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32,
+                                          C.POINTER(Nucleus), C.c_float, C.c_void_p, C.c_void_p, C.POINTER(Revise), C.POINTER(FrameScores),
+                                          C.c_void_p]),
+    "d3pm_reveal_loop_revise": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Canvas),
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ScheduleC), C.c_uint64, C.c_uint32, C.c_uint32,
+                                          C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(Nucleus), C.POINTER(Reveal), C.POINTER(Keys),
+                                          C.POINTER(Revise), C.POINTER(FrameScores), C.c_void_p]),
     "d3pm_denoise_step": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                     C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]),
@@ -1012,14 +1038,20 @@ class Sampler:
         return smp if smp is None or isinstance(smp, Nucleus) else Nucleus(smp.temperature, smp.top_k, 1.0)
 
     def reveal_step(self, logits, x_t, frame_mask, t, t_next, seed, utt0=0, flags=0, known=None, temperature=1.0, top_k=0, top_p=1.0,
-                    choice_temperature=0.0, x_next=None):
+                    choice_temperature=0.0, x_next=None, revise=None, scores=None):
         """One step of the reveal schedule (d3pm_reveal_step) on the logits of the evaluation at `t`, followed by `t_next` (0 = the
         last step) -> (x_next, cand, score): cand int32 / score float32 [B, canvas] hold a value only where x_t was a masked free
         row (the other entries are 0).  frame_mask uint8 [canvas] or [B, canvas]; known uint8 [B, canvas] or None.  x_next: the grid
-        to store into (x_t itself for an in-place step), default a new one."""
+        to store into (x_t itself for an in-place step), default a new one.
+        revise: None, or the hold bonus (a number >= 0) of d3pm_revise (d3pm_reveal_step_revise): the free rows that hold an id
+        compete again, cand / score then hold a value on every free row, and x_next may receive the mask id.  scores (with revise
+        only): the (logprob, step) pair whose entries the commit resets on the rows it re-masks."""
         cfg = self.cfg
         smp = self._as_nucleus(nucleus_options(temperature, top_k, top_p, cfg.n_classes))
         reveal_options(1, choice_temperature)
+        rs = revise_options(revise)
+        if scores is not None and rs is None:
+            raise ValueError("reveal_step takes scores only with revise")
         per_utt = known is not None or (isinstance(frame_mask, torch.Tensor) and frame_mask.dim() == 2)
         B = self._check_grid(x_t, None if per_utt else frame_mask)
         cv = self._check_canvas(B, frame_mask, known) if per_utt else None
@@ -1031,6 +1063,14 @@ class Sampler:
             _require(x_next, "x_next", tuple(x_t.shape), (torch.int32,), self.device)
         cand = torch.zeros((B, cfg.canvas), dtype=torch.int32, device=self.device)
         score = torch.zeros((B, cfg.canvas), dtype=torch.float32, device=self.device)
+        if rs is not None:
+            fs = None if scores is None else self._check_scores(scores, B)
+            check(lib().d3pm_reveal_step_revise(C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), _p(x_t), _p(x_next),
+                                                None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None, int(t), int(t_next),
+                                                C.byref(self.schedule.c_struct), seed, utt0, flags, None if smp is None else C.byref(smp),
+                                                float(choice_temperature), _p(cand), _p(score), C.byref(rs),
+                                                None if fs is None else C.byref(fs), stream_ptr()), "d3pm_reveal_step_revise")
+            return x_next, cand, score
         check(lib().d3pm_reveal_step(C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), _p(x_t), _p(x_next),
                                      None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None, int(t), int(t_next),
                                      C.byref(self.schedule.c_struct), seed, utt0, flags, None if smp is None else C.byref(smp),
@@ -1038,10 +1078,11 @@ class Sampler:
         return x_next, cand, score
 
     def reveal_loop(self, x, frame_mask, n_steps, kv_t, kv_p, seed, utt0=0, flags=0, trace=False, slot=0, known=None, temperature=1.0,
-                    top_k=0, top_p=1.0, choice_temperature=0.0, keys=None, scores=None):
+                    top_k=0, top_p=1.0, choice_temperature=0.0, keys=None, scores=None, revise=None):
         """The reveal schedule in n_steps denoiser evaluations (d3pm_reveal_loop), in place on x; masks and known frames as for
         sample_loop.  keys: None or the (frames, text, prompt) key counts of make_keys (d3pm_reveal_loop_keys).  scores: None or the
-        (logprob, step) pair of sample_loop (d3pm_reveal_loop_scored).
+        (logprob, step) pair of sample_loop (d3pm_reveal_loop_scored).  revise: None (the branches below, untouched) or the hold
+        bonus (a number >= 0) of d3pm_revise (d3pm_reveal_loop_revise, which covers keys and scores): every step may re-mask frames.
         -> the trace int32 [n_steps, B, canvas] (x after every step) or None."""
         cfg = self.cfg
         smp = self._as_nucleus(nucleus_options(temperature, top_k, top_p, cfg.n_classes))
@@ -1058,6 +1099,14 @@ class Sampler:
         fs = None if scores is None else self._check_scores(scores, B)
         tr = torch.empty((rv.n_steps, B, cfg.canvas), dtype=torch.int32, device=self.device) if trace else None
         ks = make_keys(keys, B, self.device)
+        rs = revise_options(revise)
+        if rs is not None:
+            check(lib().d3pm_reveal_loop_revise(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), None if per_utt else _p(frame_mask),
+                                                C.byref(cv) if per_utt else None, _p(self.film), _p(kv_t), _p(kv_p),
+                                                C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
+                                                None if smp is None else C.byref(smp), C.byref(rv), None if ks is None else C.byref(ks),
+                                                C.byref(rs), None if fs is None else C.byref(fs), stream_ptr()), "d3pm_reveal_loop_revise")
+            return tr
         if fs is not None:
             check(lib().d3pm_reveal_loop_scored(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), None if per_utt else _p(frame_mask),
                                                 C.byref(cv) if per_utt else None, _p(self.film), _p(kv_t), _p(kv_p),

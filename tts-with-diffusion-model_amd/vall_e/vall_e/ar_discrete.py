@@ -378,7 +378,7 @@ class AR(SymmapState, nn.Module):
                        top_p: float = 1.0, reveal_steps: Optional[int] = None, choice_temperature: float = 0.0,
                        mask_padding: bool = False, guidance: float = 0.0,
                        null_text_list: Optional[Sequence[Tensor]] = None, null_proms_list: Optional[Sequence[Tensor]] = None,
-                       return_logprobs: bool = False):
+                       return_logprobs: bool = False, revise: Optional[float] = None):
         """Reverse diffusion for len(text_list) utterances.  Positional behaviour as upstream:
         one utterance -> int64 [canvas] (squeezed, untrimmed; rows >= n_frames are sampled from
         final.bias and meaningless); with n_q > 1 (constructor) [canvas, n_q] / [B, canvas, n_q].  `resps_list` is ignored, as
@@ -462,7 +462,20 @@ class AR(SymmapState, nn.Module):
         the call without it.  It composes with everything the two loops compose with -- n_frames, known / known_mask, temperature /
         top_k / top_p, greedy, mask_padding, guidance, fp8, steps, reveal_steps, utt0 / global_batch and streams; a value that is
         not a bool, graph=True or an n_q > 1 model raise ValueError before any GPU work.  To regenerate the least sure frames call
-        again with known = ids and known_mask = logprob >= threshold."""
+        again with known = ids and known_mask = logprob >= threshold.
+        `revise=bonus` (a finite number >= 0; None = the reveal loop above, untouched) lets later steps of the reveal schedule re-mask
+        frames the model has come to doubt (include/d3pm_hip.h: d3pm_revise).  In every step the free frames that already hold an id
+        compete again for their place: such a frame's score is the model's log-probability of its id on THIS evaluation's logits
+        (as return_logprobs defines it: mask class removed, no temperature / top_k / top_p, always finite) plus `bonus`, plus the
+        same order noise a masked frame gets; masked frames are scored as before, bit for bit.  After the step that is followed by
+        timestep t' an utterance with F free frames holds F - floor(F * cbar[t']) ids on them, the frames that come first in the
+        order among ALL free frames; a held frame that does not is re-masked and may be revealed again later, with another id.
+        bonus = 0 lets held and masked frames compete on equal terms; a bonus larger than any |log-probability| pins every held
+        frame.  With return_logprobs, step / logprob describe the LAST time a frame left the mask.  It needs reveal_steps (ValueError
+        before any GPU work without it, as for a bool, a negative or a non-finite value) and composes with everything reveal_steps
+        composes with: n_frames sequences, known / known_mask, temperature / top_k / top_p, choice_temperature, greedy,
+        mask_padding, utt0 / global_batch, streams, return_trace and return_logprobs.  No statement about audio quality is made
+        for it."""
         if len(text_list) != len(proms_list) or len(text_list) == 0:
             raise ValueError("text_list and proms_list must be non-empty and of equal length")
         B = len(text_list)
@@ -498,6 +511,8 @@ class AR(SymmapState, nn.Module):
             for name, bad in (("steps", steps is not None), ("graph=True", bool(graph)), ("fp8=True", bool(fp8)), ("an n_q > 1 model", self.cfg.n_q > 1)):
                 if bad:
                     raise ValueError(f"reveal_steps does not combine with {name}")
+        if _hip.revise_options(revise) is not None and rv is None:      # host validation before any GPU work
+            raise ValueError("revise needs reveal_steps: it is an option of the reveal schedule")
         per_utt = known is not None or known_mask is not None or not (n_frames is None or isinstance(n_frames, Integral))
         if per_utt:
             if graph:
@@ -540,8 +555,11 @@ class AR(SymmapState, nn.Module):
             fl = flags | (_hip.FLAG_GREEDY if greedy else 0)
             scores = smp.new_scores(B) if return_logprobs else None      # (logprob, step), [B, canvas]: a stream chunk gets its slice
 
-            def scored(lo=0, hi=B):      # the keyword reaches the loops only when asked for
-                return {} if scores is None else {"scores": tuple(g[lo:hi] for g in scores)}
+            def scored(lo=0, hi=B):      # the keywords reach the loops only when asked for
+                kw = {} if scores is None else {"scores": tuple(g[lo:hi] for g in scores)}
+                if revise is not None:
+                    kw["revise"] = revise
+                return kw
             use_graph = bool(graph)
             if fp8 and (use_graph or (n_streams > 1 and not return_trace)):
                 raise ValueError("fp8=True runs on the single-stream eager loop only (no graph replay, no stream chunks)")

@@ -42,7 +42,7 @@ def _shard_kwargs(kw: dict, lo: int, hi: int) -> dict:
 def generate_audio_dp(model, text_list: Sequence[torch.Tensor], proms_list: Sequence[torch.Tensor], *, seed: int,
                       group=None, generate_fn: Optional[Callable] = None, **kw) -> torch.Tensor:
     """Every rank passes the same global lists and gets back the same int64 [B, canvas] grid ([B, canvas, n_q] for a model
-    built with n_q > 1).  Keyword arguments that are per call (steps, greedy, fp8, temperature, top_k, top_p, reveal_steps, choice_temperature, mask_padding, ...) go to every
+    built with n_q > 1).  Keyword arguments that are per call (steps, greedy, fp8, temperature, top_k, top_p, reveal_steps, choice_temperature, revise, mask_padding, ...) go to every
     rank as they are (mask_padding derives its key counts from the shard's own texts, prompts and n_frames); the per-utterance ones (a sequence n_frames, known, known_mask) are cut to the rank's shard."""
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank(group) if world > 1 else 0
