@@ -311,18 +311,25 @@ def test_loop_equals_steps_native_fp16(native):
     _loop_vs_steps(m, cfg, texts, proms, LENS, _known(), 3, 0.5, temperature=0.7, top_k=50, top_p=0.9, choice_temperature=4.5)
 
 
-def test_loop_equals_steps_d512_bf16_fused_commit(built_lib):
-    """The d = 512 bf16 configuration takes the folded LayerNorms, so the loop's second launch is revise_commit_prep_rows (commit + the
-    next evaluation's embedding rows, moments and fc1 fold), in whichever moment format the plan picks."""
+@pytest.mark.parametrize("with_known", [True, False], ids=["known", "none_known"])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+def test_loop_equals_steps_d512_bf16_fused_commit(built_lib, dtype, with_known):
+    """The d = 512 16-bit configurations take the folded LayerNorms, so the loop's second launch is reveal_commit_prep_rows (commit +
+    the next evaluation's embedding rows, moments and fc1 fold), in whichever moment format the plan picks: every instantiation of it
+    under kRevise = true (dtype x known-frame map or none).  N = 3: two fused commits, x -> x_alt and x_alt -> x, then the unfused last."""
     from vall_e.vall_e import AR, synth
     cfg = synth.D3PMConfig.libritts()
     m = AR.from_config(cfg)
     m.load_state_dict(synth.make_state_dict(cfg, 0))
-    m = m.to(torch.bfloat16).to(DEV)
+    m = m.to(dtype).to(DEV)
     texts, proms = synth.make_inputs(cfg, 2, 1)
     g = torch.Generator().manual_seed(4)
-    n = _loop_vs_steps(m, cfg, texts, proms, [750, 333], [torch.randint(0, 1024, (60,), generator=g), None], 4, 0.0, choice_temperature=1.0)
-    assert n > 0, "the fused commit re-masked rows"
+    known = [torch.randint(0, 1024, (60,), generator=g), None] if with_known else [None, None]
+    assert (m.canvas_init_known(2, [750, 333], known)[2] is None) == (not with_known)
+    n = _loop_vs_steps(m, cfg, texts, proms, [750, 333], known, 3, 0.0, choice_temperature=1.0)
+    print(f"[fused commit {dtype} known={with_known}] rows re-masked in 3 steps: {n}")
+    if dtype == torch.bfloat16 and with_known:
+        assert n > 0, "the fused commit re-masked rows"
 
 
 @pytest.mark.parametrize("N", [1, 4, 16])

@@ -298,8 +298,8 @@ def test_reveal_kernels_have_no_scratch_and_the_sampler_kernels_keep_their_regis
     """The kernels of d3pm_reveal.hip compile without scratch and at four waves per SIMD or better; d3pm_sample_row.h gained the
     shared row code, and the kernels of d3pm_sample.hip that include it report the register counts they had.  Cross-compiles, no GPU."""
     res, out = _resources("d3pm_reveal.hip", "reveal")
-    # 3 dtypes x {known, not} x {plain, filtered}; 2 dtypes x {known, not}; one commit kernel
-    assert {k: len(v) for k, v in res.items()} == dict(reveal_candidate_rows=12, reveal_commit_prep_rows=4, reveal_commit_rows=1), out[-4000:]
+    # 3 dtypes x {known, not} x {plain, filtered}; 2 dtypes x {known, not}; one commit kernel -- each with kRevise off and on
+    assert {k: len(v) for k, v in res.items()} == dict(reveal_candidate_rows=24, reveal_commit_prep_rows=8, reveal_commit_rows=2), out[-4000:]
     for name, rows in res.items():
         for vgpr, scratch in rows:
             assert scratch == 0 and vgpr <= 128, (name, vgpr, scratch)

@@ -289,34 +289,42 @@ def _listing(src, flt):
 
 
 def _arm(line):
-    """(dtype, known, filter) of a candidate-kernel line, whichever way the tool printed the name: demangled, mangled, or what c++filt
-    makes of the bf16 / known instantiations."""
-    m = re.search(r"rows<float, (true|false), (\d)>", line)
+    """((dtype, known, filter), revise) of a candidate-kernel line, whichever way the tool printed the name: demangled, mangled, or what
+    c++filt makes of the bf16 / known instantiations.  revise is kRevise, the last template argument."""
+    m = re.search(r"rows<float, (true|false), (\d), (true|false)>", line)
     if m:
-        return "f32", m.group(1) == "true", int(m.group(2))
-    m = re.search(r"rowsI(DF16_|DF16b)Lb([01])ELi(\d)E", line)
+        return ("f32", m.group(1) == "true", int(m.group(2))), m.group(3) == "true"
+    m = re.search(r"rowsI(DF16_|DF16b)Lb([01])ELi(\d)ELb([01])E", line)
     if m:
-        return ("f16" if m.group(1) == "DF16_" else "bf16"), m.group(2) == "1", int(m.group(3))
-    m = re.search(r"rows<bool _Accum, bool, E, (\d)>", line)
+        return (("f16" if m.group(1) == "DF16_" else "bf16"), m.group(2) == "1", int(m.group(3))), m.group(4) == "1"
+    m = re.search(r"rows<bool _Accum, bool, E, (\d), (true|false)>", line)
     assert m, line
-    return "bf16", True, int(m.group(1))
+    return ("bf16", True, int(m.group(1))), m.group(2) == "true"
 
 
 def test_revise_kernels_have_no_scratch_and_the_candidate_kernel_keeps_the_occupancy():
-    """hipcc's resource remarks for every instantiation of d3pm_revise.hip: no scratch anywhere, and the candidate kernel -- which
-    carries the masked row's routine AND the held row's -- runs no fewer waves per SIMD than reveal_candidate_rows of the same dtype
-    and arms in the same build.  Cross-compiles, no GPU."""
-    new, out = _listing("d3pm_revise.hip", "revise")
-    count = lambda rows, name: sum(name in ln for ln in rows)
-    # 3 dtypes x {known, not} x {plain, filtered}; 2 dtypes x {known, not}; one commit kernel
-    assert (count(new, "revise_candidate_rows"), count(new, "revise_commit_prep_rows"), count(new, "revise_commit_rows")) == (12, 4, 1), out[-4000:]
-    assert len(new) == 17
-    for ln in new:
+    """hipcc's resource remarks for every instantiation of d3pm_reveal.hip, split by kRevise: no scratch anywhere, and the revise form
+    of the candidate kernel -- which carries the masked row's routine AND the held row's -- runs no fewer waves per SIMD than the
+    reveal form of the same dtype and arms.  Cross-compiles, no GPU."""
+    rows, out = _listing("d3pm_reveal.hip", "reveal")
+
+    def revise(ln):      # kRevise, the last template argument, demangled or mangled
+        m = re.search(r"(true|false)>|Lb([01])EEEv", ln)
+        assert m, ln
+        return m.group(1) == "true" or m.group(2) == "1"
+
+    count = lambda name, rv: sum(name in ln and revise(ln) == rv for ln in rows)
+    # 3 dtypes x {known, not} x {plain, filtered}; 2 dtypes x {known, not}; one commit kernel -- each as reveal and as revise
+    for rv in (False, True):
+        assert (count("reveal_candidate_rows", rv), count("reveal_commit_prep_rows", rv), count("reveal_commit_rows", rv)) == (12, 4, 1), out[-4000:]
+    assert len(rows) == 34
+    for ln in rows:
         assert re.search(r"scratch\s+0\b", ln), ln
     occ = lambda ln: int(re.search(r"occ (\d+)", ln).group(1))
-    mine = {_arm(ln): occ(ln) for ln in new if "revise_candidate_rows" in ln}
-    old, _ = _listing("d3pm_reveal.hip", "reveal_candidate_rows")
-    theirs = {_arm(ln): occ(ln) for ln in old}
-    assert len(mine) == len(theirs) == 12 and set(mine) == set(theirs)
+    arms = {_arm(ln): occ(ln) for ln in rows if "reveal_candidate_rows" in ln}
+    assert all(_arm(ln)[1] == revise(ln) for ln in rows if "reveal_candidate_rows" in ln)
+    mine = {arm: o for (arm, rv), o in arms.items() if rv}
+    theirs = {arm: o for (arm, rv), o in arms.items() if not rv}
+    assert len(arms) == 24 and len(mine) == len(theirs) == 12 and set(mine) == set(theirs)
     for arm, o in theirs.items():
         assert mine[arm] >= o, (arm, mine[arm], o)

@@ -758,6 +758,8 @@ struct CallOptions {
   const d3pm_guidance* guide = nullptr;
   float* theta_out = nullptr;                       // d3pm_posterior_sample_nucleus
   const d3pm_frame_scores* scores = nullptr;        // d3pm_sample_loop_scored: the grids of the launch behind every sampler launch
+  const d3pm_reveal* reveal = nullptr;              // the reveal loop: n_steps and the choice temperature
+  const d3pm_revise* revise = nullptr;              // d3pm_reveal_loop_revise: the hold bonus
 };
 // one mask [canvas] shared by the batch, or one per utterance (+ the known frames): the entries that take either check that one is given
 static CanvasMask either_mask(const d3pm_shape* sh, int batch, const uint8_t* frame_mask, const d3pm_canvas* canvas) {
@@ -1214,11 +1216,14 @@ int d3pm_sample_loop_scored(const d3pm_shape* sh, const d3pm_weights* w, const d
 }
 
 // ---- confidence-ordered reveal (d3pm_reveal) ------------------------------------------------------------------------------------------
+// the timestep of plan index i of n_steps over a schedule of T timesteps: t_0 = T - 1, strictly decreasing, t_{N-1} >= 1
+static int reveal_plan_t(int T, int n_steps, int i) { return (T - 1) - static_cast<int>((static_cast<long long>(i) * (T - 1)) / n_steps); }
+
 int d3pm_reveal_plan(const d3pm_schedule* sched, int n_steps, int32_t* t_out) {
   D3PM_REQUIRE(sched && t_out, D3PM_E_ARG, "d3pm_reveal_plan: null pointer");
   const int T = sched->timesteps;
   D3PM_REQUIRE(T >= 2 && n_steps >= 1 && n_steps <= T - 1, D3PM_E_ARG, "d3pm_reveal_plan: n_steps %d outside 1 .. %d (timesteps - 1)", n_steps, T - 1);
-  for (int i = 0; i < n_steps; ++i) t_out[i] = (T - 1) - static_cast<int>((static_cast<long long>(i) * (T - 1)) / n_steps);
+  for (int i = 0; i < n_steps; ++i) t_out[i] = reveal_plan_t(T, n_steps, i);
   return D3PM_OK;
 }
 
@@ -1235,10 +1240,13 @@ static int check_reveal(const d3pm_shape* sh, int batch, const d3pm_schedule* sc
 }
 
 // The two launches of the reveal step that evaluates at t and is followed by t_next (0: the last step, which keeps nothing and draws
-// no v): logits rows of stride ldl.  The caller sets x_next (and the loop its trace grid).
+// no v): logits rows of stride ldl.  revise (may be null): the step runs under d3pm_revise, with `scores` (may be null) the grids its
+// commit resets on the rows it re-masks; a call without revise launches only the kRevise = false kernels of d3pm_reveal.hip.  The
+// caller sets x_next (and the loop its trace grid).
 static RevealArgs reveal_args(const d3pm_shape& sh, int batch, const void* logits, int logits_dtype, int ldl, const int32_t* x_t, const CanvasMask& cm,
                               int32_t* cand, float* score, int t, int t_next, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
-                              uint32_t flags, const d3pm_nucleus* nucleus, float choice_temperature) {
+                              uint32_t flags, const d3pm_nucleus* nucleus, float choice_temperature, const d3pm_revise* revise,
+                              const d3pm_frame_scores* scores) {
   RevealArgs a;
   a.logits = logits; a.logits_dtype = logits_dtype; a.ldl = ldl; a.x_t = x_t;
   a.frame_mask = cm.frame_mask; a.mask_period = cm.period; a.known = cm.known; a.cand = cand; a.score = score;
@@ -1248,25 +1256,39 @@ static RevealArgs reveal_args(const d3pm_shape& sh, int batch, const void* logit
   a.t = t;
   a.keep_frac = t_next > 0 ? host_h2f(sched->cbar[t_next]) : 0.f;
   a.lambda = t_next > 0 ? choice_temperature * a.keep_frac : 0.f;
+  if (revise) {
+    a.revise = true; a.hold_bonus = revise->hold_bonus;
+    if (scores) { a.logprob = scores->logprob; a.step = scores->step; }
+  }
   return a;
+}
+
+// d3pm_reveal_step (revise and scores null) and d3pm_reveal_step_revise, which has run check_revise
+static int reveal_step_impl(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t, int32_t* x_next,
+                            const uint8_t* frame_mask, const d3pm_canvas* canvas, int t, int t_next, const d3pm_schedule* sched, uint64_t seed,
+                            uint32_t utt0, uint32_t flags, const d3pm_nucleus* nucleus, float choice_temperature, int32_t* cand_out, float* score_out,
+                            const d3pm_revise* revise, const d3pm_frame_scores* scores, void* stream, const char* who) {
+  D3PM_TRY(check_reveal(sh, batch, sched, choice_temperature, flags, who));
+  D3PM_TRY(check_sampling(sh, nucleus, who));
+  if (scores) D3PM_TRY(check_scores(sh, scores, who));
+  D3PM_REQUIRE((frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
+               "%s: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)", who);
+  D3PM_REQUIRE(logits && x_t && x_next && cand_out && score_out && (!canvas || canvas->frame_mask), D3PM_E_ARG, "%s: null pointer", who);
+  D3PM_REQUIRE(t >= 1 && t < sched->timesteps && t_next >= 0 && t_next < t, D3PM_E_ARG, "%s: t = %d, t_next = %d outside %d > t > t_next >= 0", who, t,
+               t_next, sched->timesteps);
+  RevealArgs a = reveal_args(*sh, batch, logits, logits_dtype, sh->n_classes, x_t, either_mask(sh, batch, frame_mask, canvas), cand_out, score_out, t,
+                             t_next, sched, seed, utt0, flags, nucleus, choice_temperature, revise, scores);
+  a.x_next = x_next;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  D3PM_TRY(reveal_candidates(a, s));
+  return reveal_commit(a, s);
 }
 
 int d3pm_reveal_step(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t, int32_t* x_next,
                      const uint8_t* frame_mask, const d3pm_canvas* canvas, int t, int t_next, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
                      uint32_t flags, const d3pm_nucleus* nucleus, float choice_temperature, int32_t* cand_out, float* score_out, void* stream) {
-  D3PM_TRY(check_reveal(sh, batch, sched, choice_temperature, flags, "d3pm_reveal_step"));
-  D3PM_TRY(check_sampling(sh, nucleus, "d3pm_reveal_step"));
-  D3PM_REQUIRE((frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
-               "d3pm_reveal_step: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)");
-  D3PM_REQUIRE(logits && x_t && x_next && cand_out && score_out && (!canvas || canvas->frame_mask), D3PM_E_ARG, "d3pm_reveal_step: null pointer");
-  D3PM_REQUIRE(t >= 1 && t < sched->timesteps && t_next >= 0 && t_next < t, D3PM_E_ARG, "d3pm_reveal_step: t = %d, t_next = %d outside %d > t > t_next >= 0", t,
-               t_next, sched->timesteps);
-  RevealArgs a = reveal_args(*sh, batch, logits, logits_dtype, sh->n_classes, x_t, either_mask(sh, batch, frame_mask, canvas), cand_out, score_out, t,
-                             t_next, sched, seed, utt0, flags, nucleus, choice_temperature);
-  a.x_next = x_next;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  D3PM_TRY(reveal_candidates(a, s));
-  return reveal_commit(a, s);
+  return reveal_step_impl(sh, batch, logits, logits_dtype, x_t, x_next, frame_mask, canvas, t, t_next, sched, seed, utt0, flags, nucleus,
+                          choice_temperature, cand_out, score_out, nullptr, nullptr, stream, "d3pm_reveal_step");
 }
 
 // what the entries that take d3pm_revise refuse before anything else is looked at
@@ -1277,40 +1299,28 @@ static int check_revise(const d3pm_revise* revise, const char* who) {
   return D3PM_OK;
 }
 
-// d3pm_reveal_step under d3pm_revise (include/d3pm_hip.h, "reveal with revision"): the two launches of d3pm_revise.hip
+// d3pm_reveal_step under d3pm_revise (include/d3pm_hip.h, "reveal with revision")
 int d3pm_reveal_step_revise(const d3pm_shape* sh, int batch, const void* logits, int logits_dtype, const int32_t* x_t, int32_t* x_next,
                             const uint8_t* frame_mask, const d3pm_canvas* canvas, int t, int t_next, const d3pm_schedule* sched, uint64_t seed,
                             uint32_t utt0, uint32_t flags, const d3pm_nucleus* nucleus, float choice_temperature, int32_t* cand_out, float* score_out,
                             const d3pm_revise* revise, const d3pm_frame_scores* scores, void* stream) {
-  const char* who = "d3pm_reveal_step_revise";
-  D3PM_TRY(check_revise(revise, who));
-  D3PM_TRY(check_reveal(sh, batch, sched, choice_temperature, flags, who));
-  D3PM_TRY(check_sampling(sh, nucleus, who));
-  if (scores) D3PM_TRY(check_scores(sh, scores, who));
-  D3PM_REQUIRE((frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
-               "%s: give exactly one of frame_mask (shared by the batch) and canvas (per utterance)", who);
-  D3PM_REQUIRE(logits && x_t && x_next && cand_out && score_out && (!canvas || canvas->frame_mask), D3PM_E_ARG, "%s: null pointer", who);
-  D3PM_REQUIRE(t >= 1 && t < sched->timesteps && t_next >= 0 && t_next < t, D3PM_E_ARG, "%s: t = %d, t_next = %d outside %d > t > t_next >= 0", who, t,
-               t_next, sched->timesteps);
-  ReviseArgs v;
-  v.r = reveal_args(*sh, batch, logits, logits_dtype, sh->n_classes, x_t, either_mask(sh, batch, frame_mask, canvas), cand_out, score_out, t, t_next,
-                    sched, seed, utt0, flags, nucleus, choice_temperature);
-  v.r.x_next = x_next;
-  v.hold_bonus = revise->hold_bonus;
-  if (scores) { v.logprob = scores->logprob; v.step = scores->step; }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  D3PM_TRY(revise_candidates(v, s));
-  return revise_commit(v, s);
+  D3PM_TRY(check_revise(revise, "d3pm_reveal_step_revise"));
+  return reveal_step_impl(sh, batch, logits, logits_dtype, x_t, x_next, frame_mask, canvas, t, t_next, sched, seed, utt0, flags, nucleus,
+                          choice_temperature, cand_out, score_out, revise, scores, stream, "d3pm_reveal_step_revise");
 }
 
-// revise (d3pm_reveal_loop_revise): the two launches of every step are those of d3pm_revise.hip; null: every launch is d3pm_reveal's
+// o.reveal: the plan; o.revise (null but for d3pm_reveal_loop_revise): every step runs under d3pm_revise; o.scores: the launch behind every
+// commit; o.who: the entry.  o.mask is not used: the loop takes frame_mask / canvas as the entry received them, behind its own checks.
 static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
-                     const void* film, const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags,
-                     void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus, const d3pm_reveal* reveal,
-                     const KeyCounts& keys, void* stream, const d3pm_frame_scores* scores = nullptr, const d3pm_revise* revise = nullptr) {
+                            const void* film, const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
+                            uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, void* stream, const CallOptions& o) {
+  const d3pm_reveal* reveal = o.reveal;
+  const d3pm_frame_scores* scores = o.scores;
+  // (an entry that passes scores has run check_scores on them) the launch behind every commit reads whole rows of logits, d3pm_logprob.hip
+  D3PM_REQUIRE(!scores || sh->n_classes <= 1280, D3PM_E_SHAPE, "%s: the frame scores support up to 1280 classes", o.who);
   D3PM_REQUIRE(reveal, D3PM_E_ARG, "d3pm_reveal_loop: null d3pm_reveal");
   D3PM_TRY(check_reveal(sh, batch, sched, reveal->choice_temperature, flags, "d3pm_reveal_loop"));
-  D3PM_TRY(check_sampling(sh, nucleus, "d3pm_reveal_loop"));
+  D3PM_TRY(check_sampling(sh, o.nucleus, "d3pm_reveal_loop"));
   const int T = sched->timesteps, N = reveal->n_steps;
   D3PM_REQUIRE(N >= 1 && N <= T - 1 && T - 1 <= sh->timesteps, D3PM_E_ARG, "d3pm_reveal_loop: n_steps %d outside 1 .. %d (timesteps - 1)", N, T - 1);
   D3PM_REQUIRE((frame_mask != nullptr) != (canvas != nullptr), D3PM_E_ARG,
@@ -1330,7 +1340,7 @@ static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   hipStream_t s = static_cast<hipStream_t>(stream);
   const CanvasMask cm = either_mask(sh, batch, frame_mask, canvas);
   const Ctx cx(sh->tuning);
-  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, keys};
+  const DenoiserArgs q{*sh, *w, batch, cm.frame_mask, cm.period, kv_text, kv_prompt, ws, o.keys};
   // Asked as for one evaluation: the reveal loop keeps the block-0 QKV projection and every row (reveal_commit_prep does not gather
   // from the table), so the moment format is all it plans.
   const int plan = loop_plan(q, flags, LoopCall{}).fold;
@@ -1338,39 +1348,27 @@ static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   bool prepared = false;
   int32_t* cur = x;      // where x_t of the step lives: the fused launch cannot store in place, so it alternates between x and x_alt
   for (int i = 0; i < N; ++i) {
-    const int t = (T - 1) - static_cast<int>((static_cast<long long>(i) * (T - 1)) / N);
-    const int t_next = i + 1 < N ? (T - 1) - static_cast<int>((static_cast<long long>(i + 1) * (T - 1)) / N) : 0;
+    const int t = reveal_plan_t(T, N, i), t_next = i + 1 < N ? reveal_plan_t(T, N, i + 1) : 0;
     if (cx.prof) cx.prof->sample_now = (t % cx.prof->stride) == 0;
     D3PM_TRY(denoiser_blocks(q, cur, t, film, sh->n_layers, flags, s, nullptr, plan, prepared));
     prepared = false;
     D3PM_TRY(final_logits(*sh, *w, batch, ws, ws.logits, logits_ld(*sh), flags, s));
-    RevealArgs a = reveal_args(*sh, batch, ws.logits, sh->dtype, logits_ld(*sh), cur, cm, cand, score, t, t_next, sched, seed, utt0, flags, nucleus,
-                               reveal->choice_temperature);
+    RevealArgs a = reveal_args(*sh, batch, ws.logits, sh->dtype, logits_ld(*sh), cur, cm, cand, score, t, t_next, sched, seed, utt0, flags, o.nucleus,
+                               reveal->choice_temperature, o.revise, scores);
     a.x_next2 = trace ? trace + static_cast<size_t>(i) * rows : nullptr;
     {
       ProfScope p(cx, D3PM_K_SAMPLE, s, 0.0, static_cast<double>(rows) * (sh->n_classes * es + 16.0));
-      // under d3pm_revise each launch is its twin of d3pm_revise.hip, which also takes the bonus and the grids to reset
-      auto revised = [&](const RevealArgs& r) {
-        ReviseArgs v;
-        v.r = r; v.hold_bonus = revise->hold_bonus;
-        if (scores) { v.logprob = scores->logprob; v.step = scores->step; }
-        return v;
-      };
-      if (revise) D3PM_TRY(revise_candidates(revised(a), s));
-      else D3PM_TRY(reveal_candidates(a, s));
+      D3PM_TRY(reveal_candidates(a, s));
       const NextIterPrep nx = t_next > 0 && plan != FOLD_NONE ? next_iter_prep(q, film, t_next, plan == FOLD_QUADS) : NextIterPrep{};
       a.x_next = cur == x ? x_alt : x;
       if (nx.table && reveal_commit_prep_supported(a, nx)) {
-        if (revise) D3PM_TRY(revise_commit_prep(revised(a), nx, s));
-        else D3PM_TRY(reveal_commit_prep(a, nx, s));      // + the embedding rows, their moments and the fc1 fold of t_next
+        D3PM_TRY(reveal_commit_prep(a, nx, s));      // + the embedding rows, their moments and the fc1 fold of t_next
         prepared = true;
-        cur = a.x_next;
       } else {
         a.x_next = x;      // one wave per utterance: in place when cur is x, else back into x
-        if (revise) D3PM_TRY(revise_commit(revised(a), s));
-        else D3PM_TRY(reveal_commit(a, s));
-        cur = x;
+        D3PM_TRY(reveal_commit(a, s));
       }
+      cur = a.x_next;
     }
     // (d3pm_reveal_loop_scored) behind the commit, on the grid it wrote: the rows this step revealed
     if (scores) D3PM_TRY(run_frame_logprob(cx, logprob_args(*sh, rows, ws.logits, sh->dtype, logits_ld(*sh), nullptr, false, 0.f, a.x_next, t, scores), s));
@@ -1379,11 +1377,12 @@ static int reveal_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   return D3PM_OK;      // the last step is never fused (no next evaluation): the result is in x
 }
 
+// what the reveal loop's entries fill of CallOptions: {who, -, -, nucleus, keys, -, -, scores, reveal, revise}
 int d3pm_reveal_loop(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
                      const void* film, const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0, uint32_t flags,
                      void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus, const d3pm_reveal* reveal, void* stream) {
   return reveal_loop_impl(sh, w, batch, x, frame_mask, canvas, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
-                          nucleus, reveal, KeyCounts{}, stream);
+                          stream, CallOptions{"d3pm_reveal_loop", {}, nullptr, nucleus, KeyCounts{}, nullptr, nullptr, nullptr, reveal, nullptr});
 }
 
 int d3pm_reveal_loop_keys(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
@@ -1391,17 +1390,17 @@ int d3pm_reveal_loop_keys(const d3pm_shape* sh, const d3pm_weights* w, int batch
                           uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus,
                           const d3pm_reveal* reveal, const d3pm_keys* keys, void* stream) {
   return reveal_loop_impl(sh, w, batch, x, frame_mask, canvas, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
-                          nucleus, reveal, key_counts(keys), stream);
+                          stream, CallOptions{"d3pm_reveal_loop_keys", {}, nullptr, nucleus, key_counts(keys), nullptr, nullptr, nullptr, reveal, nullptr});
 }
 
 int d3pm_reveal_loop_scored(const d3pm_shape* sh, const d3pm_weights* w, int batch, int32_t* x, const uint8_t* frame_mask, const d3pm_canvas* canvas,
                             const void* film, const void* kv_text, const void* kv_prompt, const d3pm_schedule* sched, uint64_t seed, uint32_t utt0,
                             uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus,
                             const d3pm_reveal* reveal, const d3pm_keys* keys, const d3pm_frame_scores* scores, void* stream) {
-  D3PM_TRY(check_scores(sh, scores, "d3pm_reveal_loop_scored"));
-  D3PM_REQUIRE(sh->n_classes <= 1280, D3PM_E_SHAPE, "d3pm_reveal_loop_scored: the frame scores support up to 1280 classes");
+  const char* who = "d3pm_reveal_loop_scored";
+  D3PM_TRY(check_scores(sh, scores, who));
   return reveal_loop_impl(sh, w, batch, x, frame_mask, canvas, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
-                          nucleus, reveal, key_counts(keys), stream, scores);
+                          stream, CallOptions{who, {}, nullptr, nucleus, key_counts(keys), nullptr, nullptr, scores, reveal, nullptr});
 }
 
 // d3pm_reveal_loop_scored under d3pm_revise (include/d3pm_hip.h, "reveal with revision"); keys and scores optional
@@ -1410,13 +1409,11 @@ int d3pm_reveal_loop_revise(const d3pm_shape* sh, const d3pm_weights* w, int bat
                             uint32_t flags, void* workspace, size_t workspace_bytes, int32_t* trace, const d3pm_nucleus* nucleus,
                             const d3pm_reveal* reveal, const d3pm_keys* keys, const d3pm_revise* revise, const d3pm_frame_scores* scores,
                             void* stream) {
-  D3PM_TRY(check_revise(revise, "d3pm_reveal_loop_revise"));
-  if (scores) {
-    D3PM_TRY(check_scores(sh, scores, "d3pm_reveal_loop_revise"));
-    D3PM_REQUIRE(sh->n_classes <= 1280, D3PM_E_SHAPE, "d3pm_reveal_loop_revise: the frame scores support up to 1280 classes");
-  }
+  const char* who = "d3pm_reveal_loop_revise";
+  D3PM_TRY(check_revise(revise, who));
+  if (scores) D3PM_TRY(check_scores(sh, scores, who));
   return reveal_loop_impl(sh, w, batch, x, frame_mask, canvas, film, kv_text, kv_prompt, sched, seed, utt0, flags, workspace, workspace_bytes, trace,
-                          nucleus, reveal, key_counts(keys), stream, scores, revise);
+                          stream, CallOptions{who, {}, nullptr, nucleus, key_counts(keys), nullptr, nullptr, scores, reveal, revise});
 }
 
 int d3pm_q_sample(const d3pm_shape* sh, int batch, const int32_t* x0, int32_t* x_out, const uint8_t* frame_mask, int t,

@@ -257,37 +257,29 @@ int posterior_sample_prep_guided(const SampleArgs& a, const NextIterPrep& n, hip
 // One step of the confidence-ordered reveal (d3pm_reveal, d3pm_reveal.hip; n_q = 1): reveal_candidates scores the masked free rows at
 // timestep t into cand / score, then reveal_commit (one wave per utterance) or reveal_commit_prep (one wave per row + NextIterPrep
 // with film_t = the row of the NEXT timestep of the plan; x_next != x_t) picks the step's rows and stores x_next.
+// revise (d3pm_revise; the kRevise = true instantiations of the same kernels, which no call without it launches): reveal_candidates
+// writes cand / score of every FREE row (a held row: its own id, and logprob of that id + hold_bonus + the order noise); the commits
+// leave F - floor(F keep_frac) free rows with an id, may store mask_id, and reset logprob / step on the rows they re-mask.
 struct RevealArgs {
   const void* logits = nullptr; int logits_dtype = D3PM_F16; int ldl = 0;
   const int32_t* x_t = nullptr; int32_t* x_next = nullptr; int32_t* x_next2 = nullptr;
   const uint8_t* frame_mask = nullptr; int mask_period = 0;      // frame_mask[row % mask_period]
   const uint8_t* known = nullptr;                                // [rows] or nullptr
-  int32_t* cand = nullptr; float* score = nullptr;               // [rows]: written for masked free rows only
+  int32_t* cand = nullptr; float* score = nullptr;               // [rows]: written for masked free rows only (revise: for every free row)
   int rows = 0, canvas = 0, n_classes = 0, mask_id = 0;
   uint64_t seed = 0; uint32_t row0 = 0; int greedy = 0;
   int t = 0;                  // timestep of the evaluation: keys the uniforms
   float lambda = 0.f;         // choice_temperature * float(cbar[t_next]); 0 on the last step
   float keep_frac = 0.f;      // float(cbar[t_next]); 0 on the last step
   float temperature = 1.0f; int top_k = 0; float top_p = 1.0f;
+  bool revise = false; float hold_bonus = 0.f;
+  float* logprob = nullptr; int32_t* step = nullptr;             // revise: the grids of d3pm_frame_scores ([rows]), both or neither
   bool filtered() const { return temperature != 1.0f || top_k != 0 || top_p < 1.0f; }
 };
 int reveal_candidates(const RevealArgs& a, hipStream_t s);
 int reveal_commit(const RevealArgs& a, hipStream_t s);
 bool reveal_commit_prep_supported(const RevealArgs& a, const NextIterPrep& n);
 int reveal_commit_prep(const RevealArgs& a, const NextIterPrep& n, hipStream_t s);
-
-// The same step under d3pm_revise (d3pm_revise.hip, kernels of their own): revise_candidates writes cand / score of every FREE row
-// (a held row: its own id, and logprob of that id + hold_bonus + the order noise), revise_commit / revise_commit_prep leave
-// F - floor(F keep_frac) free rows with an id, may store mask_id, and reset logprob / step (both or neither; [rows]) on the rows they
-// re-mask.  revise_commit_prep applies wherever reveal_commit_prep_supported(v.r, n) holds.
-struct ReviseArgs {
-  RevealArgs r;
-  float hold_bonus = 0.f;
-  float* logprob = nullptr; int32_t* step = nullptr;
-};
-int revise_candidates(const ReviseArgs& v, hipStream_t s);
-int revise_commit(const ReviseArgs& v, hipStream_t s);
-int revise_commit_prep(const ReviseArgs& v, const NextIterPrep& n, hipStream_t s);
 
 // ---- per-frame log-probability of the revealed id (d3pm_frame_scores, d3pm_logprob.hip; n_q = 1) -------------------------------------
 // frame_scores_init: step = (live && !known && x == mask_id) ? 0 : -1, logprob = 0 over [rows].  frame_logprob, the launch behind a

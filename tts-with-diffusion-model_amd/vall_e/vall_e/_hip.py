@@ -1063,25 +1063,21 @@ class Sampler:
             _require(x_next, "x_next", tuple(x_t.shape), (torch.int32,), self.device)
         cand = torch.zeros((B, cfg.canvas), dtype=torch.int32, device=self.device)
         score = torch.zeros((B, cfg.canvas), dtype=torch.float32, device=self.device)
+        head = (C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), _p(x_t), _p(x_next), None if per_utt else _p(frame_mask),
+                C.byref(cv) if per_utt else None, int(t), int(t_next), C.byref(self.schedule.c_struct), seed, utt0, flags,
+                None if smp is None else C.byref(smp), float(choice_temperature), _p(cand), _p(score))
         if rs is not None:
             fs = None if scores is None else self._check_scores(scores, B)
-            check(lib().d3pm_reveal_step_revise(C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), _p(x_t), _p(x_next),
-                                                None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None, int(t), int(t_next),
-                                                C.byref(self.schedule.c_struct), seed, utt0, flags, None if smp is None else C.byref(smp),
-                                                float(choice_temperature), _p(cand), _p(score), C.byref(rs),
-                                                None if fs is None else C.byref(fs), stream_ptr()), "d3pm_reveal_step_revise")
-            return x_next, cand, score
-        check(lib().d3pm_reveal_step(C.byref(self.shape), B, _p(logits), dtype_code(logits.dtype), _p(x_t), _p(x_next),
-                                     None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None, int(t), int(t_next),
-                                     C.byref(self.schedule.c_struct), seed, utt0, flags, None if smp is None else C.byref(smp),
-                                     float(choice_temperature), _p(cand), _p(score), stream_ptr()), "d3pm_reveal_step")
+            check(lib().d3pm_reveal_step_revise(*head, C.byref(rs), None if fs is None else C.byref(fs), stream_ptr()), "d3pm_reveal_step_revise")
+        else:
+            check(lib().d3pm_reveal_step(*head, stream_ptr()), "d3pm_reveal_step")
         return x_next, cand, score
 
     def reveal_loop(self, x, frame_mask, n_steps, kv_t, kv_p, seed, utt0=0, flags=0, trace=False, slot=0, known=None, temperature=1.0,
                     top_k=0, top_p=1.0, choice_temperature=0.0, keys=None, scores=None, revise=None):
         """The reveal schedule in n_steps denoiser evaluations (d3pm_reveal_loop), in place on x; masks and known frames as for
         sample_loop.  keys: None or the (frames, text, prompt) key counts of make_keys (d3pm_reveal_loop_keys).  scores: None or the
-        (logprob, step) pair of sample_loop (d3pm_reveal_loop_scored).  revise: None (the branches below, untouched) or the hold
+        (logprob, step) pair of sample_loop (d3pm_reveal_loop_scored).  revise: None or the hold
         bonus (a number >= 0) of d3pm_revise (d3pm_reveal_loop_revise, which covers keys and scores): every step may re-mask frames.
         -> the trace int32 [n_steps, B, canvas] (x after every step) or None."""
         cfg = self.cfg
@@ -1100,31 +1096,18 @@ class Sampler:
         tr = torch.empty((rv.n_steps, B, cfg.canvas), dtype=torch.int32, device=self.device) if trace else None
         ks = make_keys(keys, B, self.device)
         rs = revise_options(revise)
+        head = (C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), None if per_utt else _p(frame_mask), C.byref(cv) if per_utt else None,
+                _p(self.film), _p(kv_t), _p(kv_p), C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
+                None if smp is None else C.byref(smp), C.byref(rv))
+        kp, fp = None if ks is None else C.byref(ks), None if fs is None else C.byref(fs)
         if rs is not None:
-            check(lib().d3pm_reveal_loop_revise(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), None if per_utt else _p(frame_mask),
-                                                C.byref(cv) if per_utt else None, _p(self.film), _p(kv_t), _p(kv_p),
-                                                C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
-                                                None if smp is None else C.byref(smp), C.byref(rv), None if ks is None else C.byref(ks),
-                                                C.byref(rs), None if fs is None else C.byref(fs), stream_ptr()), "d3pm_reveal_loop_revise")
-            return tr
-        if fs is not None:
-            check(lib().d3pm_reveal_loop_scored(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), None if per_utt else _p(frame_mask),
-                                                C.byref(cv) if per_utt else None, _p(self.film), _p(kv_t), _p(kv_p),
-                                                C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
-                                                None if smp is None else C.byref(smp), C.byref(rv), None if ks is None else C.byref(ks),
-                                                C.byref(fs), stream_ptr()), "d3pm_reveal_loop_scored")
-            return tr
-        if ks is not None:
-            check(lib().d3pm_reveal_loop_keys(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), None if per_utt else _p(frame_mask),
-                                              C.byref(cv) if per_utt else None, _p(self.film), _p(kv_t), _p(kv_p),
-                                              C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
-                                              None if smp is None else C.byref(smp), C.byref(rv), C.byref(ks), stream_ptr()),
-                  "d3pm_reveal_loop_keys")
-            return tr
-        check(lib().d3pm_reveal_loop(C.byref(self.shape), C.byref(self.weights.c_struct), B, _p(x), None if per_utt else _p(frame_mask),
-                                     C.byref(cv) if per_utt else None, _p(self.film), _p(kv_t), _p(kv_p),
-                                     C.byref(self.schedule.c_struct), seed, utt0, flags, _p(ws), ws.numel(), _p(tr),
-                                     None if smp is None else C.byref(smp), C.byref(rv), stream_ptr()), "d3pm_reveal_loop")
+            check(lib().d3pm_reveal_loop_revise(*head, kp, C.byref(rs), fp, stream_ptr()), "d3pm_reveal_loop_revise")
+        elif fs is not None:
+            check(lib().d3pm_reveal_loop_scored(*head, kp, fp, stream_ptr()), "d3pm_reveal_loop_scored")
+        elif ks is not None:
+            check(lib().d3pm_reveal_loop_keys(*head, kp, stream_ptr()), "d3pm_reveal_loop_keys")
+        else:
+            check(lib().d3pm_reveal_loop(*head, stream_ptr()), "d3pm_reveal_loop")
         return tr
 
     def ce_loss_rows(self, logits, targets, frame_mask):
