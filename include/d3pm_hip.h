@@ -71,7 +71,8 @@ extern "C" {
  *    that have few live rows (d3pm_op_linear_live_est; ln_fold value 4 = the deduplicated loop without that switch); the per-frame
  *    log-probability of the revealed id from either loop (d3pm_frame_scores, d3pm_frame_scores_init, d3pm_frame_scores_step,
  *    d3pm_sample_loop_scored, d3pm_reveal_loop_scored); the reveal schedule whose held frames compete again in every step
- *    (d3pm_revise, d3pm_reveal_step_revise, d3pm_reveal_loop_revise) */
+ *    (d3pm_revise, d3pm_reveal_step_revise, d3pm_reveal_loop_revise); the self-attention of the few-row iterations of the
+ *    deduplicated loop with an utterance's distinct K | V rows pooled in LDS (d3pm_op_attention_gather_pool) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -981,6 +982,18 @@ int d3pm_op_attention_keylen(int dtype, int family, const void *Q, int ldq, cons
 int d3pm_op_attention_gather(int dtype, const void *Q, int ldq, const void *K, const void *V, int ldkv, int kv_rows,
                              const int32_t *key_row, const int32_t *seg_start, const int32_t *seg_len, void *O, int ldo, int B, int Tq,
                              int S, int H, int hd, float scale, const int32_t *key_len, const d3pm_tuning *tuning, void *stream);
+/* d3pm_op_attention_gather with the K | V rows of an utterance pooled in LDS (tests): what the deduplicated loop launches in the
+ * iterations that expect few distinct rows per utterance.  The workgroups of an utterance with seg_len[b] <= pool_rows copy, per head,
+ * pool row r = row pool_src[seg_start[b] + r] of K / V (pool_src NULL: row seg_start[b] + r), clamped into [0, kv_rows - 1], for
+ * r < seg_len[b], and read key j from pool row seg_key[b * S + j] - seg_start[b], clamped into [0, seg_len[b] - 1] (seg_key: device
+ * int32 [B][S]); those of an utterance with more rows walk key_row as d3pm_op_attention_gather does, in the same launch.  The caller
+ * promises that both ways name rows with the same bytes: the result is then d3pm_op_attention_gather's, bit for bit.  The grid holds
+ * qblocks_grid (1 .. Tq / 128) 128-query blocks per (utterance, head) and a workgroup strides over the blocks of its segment.  The
+ * tiles (48 KiB), the index (4 S bytes) and the pool (256 bytes per row) must fit 160 KiB of LDS; D3PM_E_SHAPE otherwise. */
+int d3pm_op_attention_gather_pool(int dtype, const void *Q, int ldq, const void *K, const void *V, int ldkv, int kv_rows,
+                                  const int32_t *key_row, const int32_t *seg_start, const int32_t *seg_len, void *O, int ldo, int B,
+                                  int Tq, int S, int H, int hd, float scale, const int32_t *key_len, const int32_t *seg_key,
+                                  const int32_t *pool_src, int pool_rows, int qblocks_grid, const d3pm_tuning *tuning, void *stream);
 /* The text and prompt cross-attentions of a DiT block (ar_discrete.py:138,142) as the block launches them: two independent
  * problems with the same B / Tq / H / hd -- queries Q1 / Q2 [B][Tq][ldq], keys and values K / V [B][S][ldkv] with S1 / S2 keys,
  * outputs O1 / O2 [B][Tq][ldo] -- in ONE launch (tuning->attn_cross_resident / attn_pair_sequential pick the schedule). */

@@ -96,10 +96,11 @@ static int run_attention(const Ctx& cx, int dtype, AttnArgs a, uint32_t flags, h
               dtype_size(dtype) * ((a.Q2 ? 4.0 : 2.0) * a.B * a.Tq * a.H * a.hd + 2.0 * a.B * (a.S + a.S2) * a.H * a.hd));
   const AttnPlan plan = plan_attention(dtype, a, forced_generic(flags));
   // query segments exist in two kernels only: any other choice would read Q at b * Tq and ignore them
-  D3PM_REQUIRE(!a.seg_len || plan.kernel == ATTN_32P || plan.kernel == ATTN_32_CROSS, D3PM_E_SHAPE,
+  const bool self32p = plan.kernel == ATTN_32P || plan.kernel == ATTN_32P_POOL;
+  D3PM_REQUIRE(!a.seg_len || self32p || plan.kernel == ATTN_32_CROSS, D3PM_E_SHAPE,
                "query segments: the planner names attention kernel %d, which does not take them", plan.kernel);
   // ... and a key index in one: attn32p_hd64 with segments
-  D3PM_REQUIRE(!a.key_row || (plan.kernel == ATTN_32P && a.seg_len && !a.Q2), D3PM_E_SHAPE,
+  D3PM_REQUIRE(!a.key_row || (self32p && a.seg_len && !a.Q2), D3PM_E_SHAPE,
                "gathered keys: the planner names attention kernel %d, or the call has no query segments", plan.kernel);
   if (plan.mfma()) return mfma_attention(dtype, a, plan, s);
   if (a.Q2) {   // the generic kernel takes one problem per launch
@@ -1039,6 +1040,7 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
   for (int t = t_start; t > t_stop; --t) {
     if (cx.prof) cx.prof->sample_now = (t % cx.prof->stride) == 0;
     q.m_est = plan.m_est(sched, t);
+    q.seg_est = plan.seg_est(sched, t);
     D3PM_TRY(denoiser_blocks(q, x, t, film, sh->n_layers, flags, s, o.f8, q.m_est ? FOLD_PARTS : plan.fold, prepared, qkv_ready));
     D3PM_TRY(final_logits(*sh, *w, eval_batch, ws, ws.logits, logits_ld(*sh), flags, s, q.dd ? q.dd->m_live : nullptr));
     SampleArgs a = sample_args(*sh, batch, ws.logits, sh->dtype, logits_ld(*sh), x, x, cm.known, t, sched, seed, utt0, flags, o.nucleus, guide);
@@ -1647,6 +1649,28 @@ int d3pm_op_attention_gather(int dtype, const void* Q, int ldq, const void* K, c
   const AttnPlan plan = plan_attention(dtype, a);
   D3PM_REQUIRE(plan.kernel == ATTN_32P, D3PM_E_SHAPE,
                "d3pm_op_attention_gather: needs a 16-bit dtype, head width 64, Tq a multiple of 128, S of 64 and 16-byte aligned rows");
+  return mfma_attention(dtype, a, plan, static_cast<hipStream_t>(stream));
+}
+
+// the pooled attn32p_hd64 with the pool and the grid the caller names; an utterance beyond the pool takes the gathered walk in the same launch
+int d3pm_op_attention_gather_pool(int dtype, const void* Q, int ldq, const void* K, const void* V, int ldkv, int kv_rows, const int32_t* key_row,
+                                  const int32_t* seg_start, const int32_t* seg_len, void* O, int ldo, int B, int Tq, int S, int H, int hd, float scale,
+                                  const int32_t* key_len, const int32_t* seg_key, const int32_t* pool_src, int pool_rows, int qblocks_grid,
+                                  const d3pm_tuning* tuning, void* stream) {
+  D3PM_REQUIRE(Q && K && V && O && key_row && seg_start && seg_len && seg_key && kv_rows > 0 && B > 0 && Tq > 0 && S > 0 && H > 0 && hd > 0 &&
+                   pool_rows > 0 && qblocks_grid > 0,
+               D3PM_E_ARG, "d3pm_op_attention_gather_pool: bad arguments");
+  d3pm_tuning tn = tune_of(tuning);
+  tn.attn_query_groups = 32;
+  AttnArgs a;
+  a.tune = &tn;
+  a.Q = Q; a.ldq = ldq; a.K = K; a.V = V; a.ldkv = ldkv; a.O = O; a.ldo = ldo; a.B = B; a.Tq = Tq; a.S = S; a.H = H;
+  a.hd = hd; a.scale = scale; a.key_len = key_len; a.seg_start = seg_start; a.seg_len = seg_len; a.key_row = key_row; a.kv_rows = kv_rows;
+  a.seg_key = seg_key; a.pool_src = pool_src; a.pool_rows = pool_rows; a.qblocks_grid = qblocks_grid;
+  const AttnPlan plan = plan_attention(dtype, a);
+  D3PM_REQUIRE(plan.kernel == ATTN_32P_POOL, D3PM_E_SHAPE,
+               "d3pm_op_attention_gather_pool: needs what d3pm_op_attention_gather needs, qblocks_grid <= Tq / 128, and the tiles, the index "
+               "(4 S bytes) and the pool (256 bytes per row) within 160 KiB of LDS");
   return mfma_attention(dtype, a, plan, static_cast<hipStream_t>(stream));
 }
 

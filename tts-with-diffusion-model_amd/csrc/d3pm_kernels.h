@@ -97,6 +97,16 @@ struct AttnArgs {
   // of K / V, which are then [kv_rows][ldkv] with no per-utterance base; the kernel clamps the index into [0, kv_rows - 1];
   // kv_rows * ldkv * the element size < 2^32
   const int32_t* key_row = nullptr; int kv_rows = 0;
+  // optional key pool (with key_row; attn32p_hd64 POOL): seg_est = the rows per utterance the host expects (0 = none; it only chooses
+  // speed).  Within attn_pool_rows() the workgroup of an utterance whose seg_len[b] fits the pool copies the K | V columns of its head
+  // into LDS once -- pool row r = row pool_src[seg_start[b] + r] of K / V (null: row seg_start[b] + r), clamped into [0, kv_rows - 1] --
+  // and key j is pool row seg_key[b * S + j] - seg_start[b], clamped into [0, seg_len[b] - 1]; any other workgroup of the launch walks
+  // key_row as without a pool.  The caller's promise: the row named through key_row and the one named through seg_key / pool_src hold
+  // the same bytes.  pool_rows / qblocks_grid (d3pm_op_attention_gather_pool): the pool's rows and the query blocks per (utterance,
+  // head) in the grid, named by the caller instead of derived from seg_est
+  int seg_est = 0;
+  const int32_t* seg_key = nullptr; const int32_t* pool_src = nullptr;
+  int pool_rows = 0, qblocks_grid = 0;
   const d3pm_tuning* tune = nullptr;
 };
 

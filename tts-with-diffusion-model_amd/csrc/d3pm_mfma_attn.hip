@@ -534,7 +534,7 @@ __global__ __launch_bounds__(512, 2) void attn_cross_hd64(const T* __restrict__ 
 // automatic choices are described.  What is left here is the plan -> instantiation table.
 int mfma_attention(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_t s) {
   switch (p.kernel) {
-    case ATTN_32P: case ATTN_32: return mfma_attention32(dtype, a, p, s);
+    case ATTN_32P: case ATTN_32: case ATTN_32P_POOL: return mfma_attention32(dtype, a, p, s);
     case ATTN_32_CROSS: return mfma_attention32_cross(dtype, a, p, s);
     case ATTN_SPLIT: return mfma_attention_split(dtype, a, p, s);
     case ATTN_CROSS: case ATTN_TILES: break;

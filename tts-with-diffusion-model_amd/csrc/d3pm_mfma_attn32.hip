@@ -288,15 +288,28 @@ __global__ __launch_bounds__(256, 2) void attn32_hd64(const T* __restrict__ Q, i
 // of dynamic LDS behind the 48 KiB of tiles, three workgroups per CU up to S = 1344.  load_tile and the STG halves of `block` take
 // their two row offsets per thread from there; LDS layout, swizzles, barriers and the walk are those of GATHER = false, and so is
 // every bit of the result on the same key values.  GATHER = false is the code it was.
-template <typename T, bool MASK = false, bool SEG = false, bool GATHER = false>
+// POOL (with GATHER only; AttnArgs::seg_est / seg_key / pool_src, plan_attention): the launch of an iteration that expects few distinct
+// rows per utterance is one workgroup per (utterance, head) alone on its CU, and nothing covers the L2 round trip of the two staged
+// halves of each 32-key block (20 - 22 us per launch at any row count).  A workgroup whose seg_len[b] <= pool_rows copies the K and
+// V columns of head h of its utterance's rows into dynamic LDS behind the index once, 128 rows per flight -- pool row r = row
+// pool_src[seg_start[b] + r] of Kp / Vp (null: row seg_start[b] + r), clamped into [0, kv_rows - 1] -- and stages, for key j, the byte
+// offset of pool row clamp(seg_key[b * S + j] - seg_start[b], 0, seg_len[b] - 1); load_tile and the STG halves then read their
+// 16-byte pieces from the pool (POOLED).  Any other workgroup of the launch walks key_row as GATHER does: block-uniform, decided once.
+// The caller promises that both ways name rows with the same bytes, so the tile image, and with it every bit, is the gathered
+// kernel's.  The grid holds n_qblocks query blocks per (utterance, head) -- the host's estimate -- and a workgroup walks qb,
+// qb + n_qblocks, .. while the segment has them.  48 KiB + 4 S + 256 pool_rows bytes of LDS (83 KiB at 128 rows and 768 keys).
+// POOL = false is the code it was.
+template <typename T, bool MASK = false, bool SEG = false, bool GATHER = false, bool POOL = false>
 __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, int ldq, const T* __restrict__ Kp,
                                                        const T* __restrict__ Vp, int ldkv, T* __restrict__ O, int ldo, int Tq,
                                                        int S, float scale, int H, int n_qblocks, const int32_t* __restrict__ key_len,
                                                        const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_len,
-                                                       const int32_t* __restrict__ key_row, int kv_rows) {
+                                                       const int32_t* __restrict__ key_row, int kv_rows,
+                                                       const int32_t* __restrict__ seg_key, const int32_t* __restrict__ pool_src, int pool_rows) {
   static_assert(!GATHER || SEG, "gathered keys: the segment form only");
+  static_assert(!POOL || GATHER, "the key pool: the gathered form only");
   __shared__ __attribute__((aligned(16))) char smem[3 * 2 * TILE];   // [buffer][K tile | V tile]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;      // (the lane constants of the walk: inside `walk`)
   int bid;
   {
     const int nblocks = gridDim.x, q = nblocks >> 3, r = nblocks & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
@@ -308,24 +321,75 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
     if (qb * 128 >= seg_len[b]) return;      // block-uniform
     qbase = static_cast<size_t>(seg_start[b]);
   }
-  const int q0 = (qb * 4 + wave) * 32;
-  const int qn = lane & 31, hh = lane >> 5;
   const T* Kb = Kp + (GATHER ? 0 : static_cast<size_t>(b) * S * ldkv) + h * HD;
   const T* Vb = Vp + (GATHER ? 0 : static_cast<size_t>(b) * S * ldkv) + h * HD;
-  const uint32_t* kidx = nullptr;      // GATHER: [S] byte offset of the row of key j in Kp / Vp
+  const uint32_t* kidx = nullptr;      // GATHER: [S] byte offset of the row of key j in Kp / Vp (pooled: in the pool)
+  bool pooled = false;                 // POOL: this workgroup's utterance fits the pool (block-uniform, decided here once)
+  const char* pool_k = nullptr;        // POOL: [pool_rows][128 B] K columns of head h of the utterance's distinct rows, then V likewise
+  const char* pool_v = nullptr;
   if constexpr (GATHER) {
     extern __shared__ __attribute__((aligned(16))) char smem_idx[];
     uint32_t* w = reinterpret_cast<uint32_t*>(smem_idx);
-    const int32_t* src = key_row + static_cast<size_t>(b) * S;
-    for (int j = tid; j < S; j += 256) {
-      int r = src[j];
-      r = r < 0 ? 0 : (r >= kv_rows ? kv_rows - 1 : r);
-      w[j] = static_cast<uint32_t>(r) * static_cast<uint32_t>(ldkv) * static_cast<uint32_t>(sizeof(T));
+    if constexpr (POOL) {
+      const int live = seg_len[b], s0 = seg_start[b];
+      char* pk = smem_idx + static_cast<size_t>(S) * 4;
+      char* pv = pk + static_cast<size_t>(pool_rows) * ROWB;
+      pool_k = pk; pool_v = pv;
+      pooled = live <= pool_rows;
+      if (pooled) {
+        const int32_t* sk = seg_key + static_cast<size_t>(b) * S;
+        for (int j = tid; j < S; j += 256) {
+          int r = sk[j] - s0;
+          r = r < 0 ? 0 : (r >= live ? live - 1 : r);
+          w[j] = static_cast<uint32_t>(r) * static_cast<uint32_t>(ROWB);
+        }
+        // the pool: 128 rows (16 KiB of K and of V) per flight -- every load of a flight is issued in front of its first LDS write
+        const int fr = tid >> 3, fc = (tid & 7) * 16;
+        const char* kg = reinterpret_cast<const char*>(Kb) + fc;
+        const char* vg = reinterpret_cast<const char*>(Vb) + fc;
+        for (int r0 = 0; r0 < live; r0 += 128) {      // block-uniform trip count
+          uint4 fk[4], fv[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int r = min(r0 + fr + 32 * i, live - 1);
+            int row = pool_src ? pool_src[s0 + r] : s0 + r;
+            row = row < 0 ? 0 : (row >= kv_rows ? kv_rows - 1 : row);
+            const uint32_t g = static_cast<uint32_t>(row) * static_cast<uint32_t>(ldkv) * static_cast<uint32_t>(sizeof(T));
+            fk[i] = *reinterpret_cast<const uint4*>(kg + g);
+            fv[i] = *reinterpret_cast<const uint4*>(vg + g);
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int r = r0 + fr + 32 * i;
+            if (r < live) {
+              *reinterpret_cast<uint4*>(pk + r * ROWB + fc) = fk[i];
+              *reinterpret_cast<uint4*>(pv + r * ROWB + fc) = fv[i];
+            }
+          }
+        }
+      }
+    }
+    if (!POOL || !pooled) {
+      const int32_t* src = key_row + static_cast<size_t>(b) * S;
+      for (int j = tid; j < S; j += 256) {
+        int r = src[j];
+        r = r < 0 ? 0 : (r >= kv_rows ? kv_rows - 1 : r);
+        w[j] = static_cast<uint32_t>(r) * static_cast<uint32_t>(ldkv) * static_cast<uint32_t>(sizeof(T));
+      }
     }
     kidx = w;
     __syncthreads();
   }
 
+  // the walk of one 128-query block.  POOLED (POOL only): the staged 16-byte pieces come from the pool
+  auto walk = [&](const int qbk, auto POOLED_) __attribute__((always_inline)) {
+  constexpr bool POOLED = decltype(POOLED_)::value;
+  // POOL (a walk inside a loop): the lane constants of the walk are formed again from an opaque thread id, or hipcc keeps all of them
+  // in registers across the walk for the next one's queries (40 bytes of scratch at three workgroups per CU)
+  int tid_w = threadIdx.x;
+  if constexpr (POOL) asm volatile("" : "+v"(tid_w));
+  const int tid = tid_w, lane = tid & 63, wave = tid >> 6, qn = lane & 31, hh = lane >> 5;
+  const int q0 = (qbk * 4 + wave) * 32;
   const float qscale = scale * 1.4426950408889634f;
   uint4 qf[4];
   {
@@ -349,6 +413,14 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
   const uint32_t lo0 = static_cast<uint32_t>(r0s * ldkv + chs * 8) * 2u, lo1 = lo0 + static_cast<uint32_t>(32 * ldkv) * 2u;
   auto load_tile = [=](int tile) -> Staged {
     Staged st;
+    if constexpr (POOLED) {
+      const uint32_t g0 = kidx[tile * BKV + r0s] + chs * 16u, g1 = kidx[tile * BKV + r0s + 32] + chs * 16u;
+      st.k0 = *reinterpret_cast<const uint4*>(pool_k + g0);
+      st.k1 = *reinterpret_cast<const uint4*>(pool_k + g1);
+      st.v0 = *reinterpret_cast<const uint4*>(pool_v + g0);
+      st.v1 = *reinterpret_cast<const uint4*>(pool_v + g1);
+      return st;
+    }
     if constexpr (GATHER) {
       const uint32_t g0 = kidx[tile * BKV + r0s] + chs * 16u, g1 = kidx[tile * BKV + r0s + 32] + chs * 16u;
       const char* kt = reinterpret_cast<const char*>(Kb);
@@ -478,7 +550,11 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
     if constexpr (STG != 0) {      // unconditional in the tile index (a branch on it splits the block and hipcc sinks the vector work
       // behind it): past the end the last tile is staged again, into a buffer that is no longer read
       const int stc = stile < n_tiles ? stile : n_tiles - 1;
-      if constexpr (GATHER) {
+      if constexpr (POOLED) {
+        const char* gt = STG == 1 ? pool_k : pool_v;
+        h0 = *reinterpret_cast<const uint4*>(gt + (kidx[stc * BKV + r0s] + chs * 16u));
+        h1 = *reinterpret_cast<const uint4*>(gt + (kidx[stc * BKV + r0s + 32] + chs * 16u));
+      } else if constexpr (GATHER) {
         const char* gt = reinterpret_cast<const char*>(STG == 1 ? Kb : Vb);
         h0 = *reinterpret_cast<const uint4*>(gt + (kidx[stc * BKV + r0s] + chs * 16u));
         h1 = *reinterpret_cast<const uint4*>(gt + (kidx[stc * BKV + r0s + 32] + chs * 16u));
@@ -606,6 +682,25 @@ __global__ __launch_bounds__(256, 3) void attn32p_hd64(const T* __restrict__ Q, 
     store_rows32<T>(O + (qbase + min(q0 + qn, live_rows - 1)) * ldo + h * HD, acc_o, inv, hh, q0 + qn < live_rows);
   } else {
     store_rows32<T>(O + (qbase + q0 + qn) * ldo + h * HD, acc_o, inv, hh, true);
+  }
+  };      // walk
+  if constexpr (!POOL) {
+    walk(qb, std::false_type{});
+  } else {
+    // the grid holds n_qblocks query blocks per (utterance, head): a workgroup walks qb, qb + n_qblocks, .. of the segment; the pool and
+    // the index are staged once, the barrier keeps the tile buffers of one walk from the next
+    const int live = seg_len[b];
+    if (pooled) {
+      for (int q = qb; q * 128 < live; q += n_qblocks) {
+        if (q != qb) __syncthreads();
+        walk(q, std::true_type{});
+      }
+    } else {
+      for (int q = qb; q * 128 < live; q += n_qblocks) {
+        if (q != qb) __syncthreads();
+        walk(q, std::false_type{});
+      }
+    }
   }
 }
 
@@ -910,11 +1005,38 @@ int mfma_attention32(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_
                                 static_cast<T*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, a.key_len)
 #define D3PM_ATTN32P(KERNEL, T) \
   KERNEL<<<grid, block, 0, s>>>(static_cast<const T*>(a.Q), a.ldq, static_cast<const T*>(a.K), static_cast<const T*>(a.V), a.ldkv, \
-                                static_cast<T*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, a.key_len, a.seg_start, a.seg_len, nullptr, 0)
-  D3PM_REQUIRE((a.seg_len != nullptr) == (a.seg_start != nullptr) && (!a.seg_len || p.kernel == ATTN_32P), D3PM_E_SHAPE,
+                                static_cast<T*>(a.O), a.ldo, a.Tq, a.S, a.scale, a.H, n_qblocks, a.key_len, a.seg_start, a.seg_len, nullptr, 0, \
+                                nullptr, nullptr, 0)
+  const bool pool = p.kernel == ATTN_32P_POOL;
+  D3PM_REQUIRE((a.seg_len != nullptr) == (a.seg_start != nullptr) && (!a.seg_len || p.kernel == ATTN_32P || pool), D3PM_E_SHAPE,
                "query segments: the pipelined 32 x 32 x 16 self-attention only");
-  D3PM_REQUIRE(!a.key_row || (p.kernel == ATTN_32P && a.seg_len), D3PM_E_SHAPE,
+  D3PM_REQUIRE(!a.key_row || ((p.kernel == ATTN_32P || pool) && a.seg_len), D3PM_E_SHAPE,
                "gathered keys: the pipelined 32 x 32 x 16 self-attention with query segments only");
+  D3PM_REQUIRE(!pool || (a.key_row && a.seg_key && p.pool_rows > 0 && p.n_qblocks > 0), D3PM_E_SHAPE,
+               "the key pool: gathered keys, a segment key index and a pool of at least one row");
+  if (pool) {      // the keys of an utterance with few distinct rows from a pool in LDS; instantiations of their own once more
+    const size_t es = dtype == D3PM_F16 ? sizeof(f16) : sizeof(bf16);
+    const size_t lds = static_cast<size_t>(a.S) * 4 + 2 * static_cast<size_t>(p.pool_rows) * ROWB;
+    D3PM_REQUIRE(a.kv_rows > 0 && static_cast<unsigned long long>(a.kv_rows) * static_cast<unsigned long long>(a.ldkv) * es < (1ull << 32) &&
+                     static_cast<size_t>(a.S) * 4 <= kGatherIndexBytes && p.lds == lds && 3 * 2 * TILE + lds <= kAttnPoolLdsBytes,
+                 D3PM_E_SHAPE, "the key pool: kv_rows * ldkv * sizeof(T) must stay under 2^32, S (%d) under %d, index and pool (%d rows) in %d KiB of LDS",
+                 a.S, static_cast<int>(kGatherIndexBytes / 4) + 1, p.pool_rows, static_cast<int>((kAttnPoolLdsBytes - 3 * 2 * TILE) / 1024));
+#define D3PM_ATTN32PL(MASK, T)                                                                                                            \
+  do {                                                                                                                                    \
+    D3PM_LDS_ATTR((&attn32p_hd64<T, MASK, true, true, true>), kAttnPoolLdsBytes - 3 * 2 * TILE);                                          \
+    attn32p_hd64<T, MASK, true, true, true><<<grid, block, p.lds, s>>>(                                                                   \
+        static_cast<const T*>(a.Q), a.ldq, static_cast<const T*>(a.K), static_cast<const T*>(a.V), a.ldkv, static_cast<T*>(a.O), a.ldo, a.Tq, \
+        a.S, a.scale, a.H, n_qblocks, a.key_len, a.seg_start, a.seg_len, a.key_row, a.kv_rows, a.seg_key, a.pool_src, p.pool_rows);       \
+  } while (0)
+    if (p.masked) {
+      if (dtype == D3PM_F16) D3PM_ATTN32PL(true, f16); else D3PM_ATTN32PL(true, bf16);
+    } else {
+      if (dtype == D3PM_F16) D3PM_ATTN32PL(false, f16); else D3PM_ATTN32PL(false, bf16);
+    }
+#undef D3PM_ATTN32PL
+    D3PM_LAUNCH_CHECK();
+    return D3PM_OK;
+  }
   if (a.key_row) {      // keys through a row index: instantiations of their own again
     // the staged index holds 32-bit byte offsets of the rows; 4 S bytes of LDS behind the tiles stay inside a workgroup's 64 KiB
     const size_t es = dtype == D3PM_F16 ? sizeof(f16) : sizeof(bf16);
@@ -925,7 +1047,8 @@ int mfma_attention32(int dtype, const AttnArgs& a, const AttnPlan& p, hipStream_
 #define D3PM_ATTN32G(MASK, T)                                                                                                             \
   attn32p_hd64<T, MASK, true, true><<<grid, block, p.lds, s>>>(static_cast<const T*>(a.Q), a.ldq, static_cast<const T*>(a.K),            \
                                                                static_cast<const T*>(a.V), a.ldkv, static_cast<T*>(a.O), a.ldo, a.Tq, a.S, \
-                                                               a.scale, a.H, n_qblocks, a.key_len, a.seg_start, a.seg_len, a.key_row, a.kv_rows)
+                                                               a.scale, a.H, n_qblocks, a.key_len, a.seg_start, a.seg_len, a.key_row, a.kv_rows, \
+                                                               nullptr, nullptr, 0)
     if (p.masked) {
       if (dtype == D3PM_F16) D3PM_ATTN32G(true, f16); else D3PM_ATTN32G(true, bf16);
     } else {

@@ -271,6 +271,16 @@ int plan_live_rows(int batch, int canvas, float cbar_t) {
 #endif
 int live_latency_rows() { return D3PM_LIVE_LATENCY_ROWS; }
 
+// The rows of the self-attention's K | V pool, and the largest per-utterance estimate that takes it (a compile-time constant for the same
+// reason).  The gathered walk costs 20.6 us per launch (sd 0.25) from 2 to about 120 rows per utterance -- one workgroup alone on
+// its CU waits out the L2 round trip of every 32-key block -- so the bound is not a crossover but the LDS a pool row costs: 256 bytes,
+// 83 KiB in all at 128 rows with the 768-key index, one workgroup per CU, which is what these iterations launch anyway.  Measurements:
+// profiles/round25_few_rows_ab_interleaved.txt.
+#ifndef D3PM_ATTN_POOL_ROWS
+#define D3PM_ATTN_POOL_ROWS 128
+#endif
+int attn_pool_rows() { return D3PM_ATTN_POOL_ROWS; }
+
 // ---- d3pm_tuning.ln_fold (include/d3pm_hip.h): 0 the LayerNorm launches, 1 everything (default), 2 the fold alone, 3 fold + table,
 // 4 fold + table + deduplication without the latency list.  The only place that reads the codes.
 FoldFeatures fold_features(const d3pm_tuning& tn) {
@@ -329,6 +339,19 @@ AttnPlan plan_attention(int dtype, const AttnArgs& a, bool force_generic) {
     p.n_qblocks = a.Tq / 128;
     p.grid = static_cast<unsigned>(p.n_qblocks * a.H * a.B);
     if (a.key_row && !plain_walk32) p.lds = static_cast<size_t>(a.S) * 4;      // the staged key index behind the static tiles
+    // Few distinct rows per utterance (AttnArgs::seg_est): one workgroup per CU, which nothing covers while it waits for the staged
+    // halves of each 32-key block, so the utterance's K | V rows of the head go to LDS once and the walk stages from there.  The grid
+    // covers the estimated query blocks; a longer segment is walked all the same (stride), one beyond the pool through key_row.
+    const bool pool_named = a.pool_rows > 0 && a.qblocks_grid > 0;
+    if (a.key_row && a.seg_len && a.seg_key && p.kernel == ATTN_32P && (pool_named || (a.seg_est > 0 && a.seg_est <= attn_pool_rows()))) {
+      const int rows = pool_named ? a.pool_rows : attn_pool_rows(), qblocks = pool_named ? a.qblocks_grid : (a.seg_est + 127) / 128;
+      const size_t lds = p.lds + 2 * static_cast<size_t>(rows) * ROWB;
+      if (3 * 2 * TILE + lds <= kAttnPoolLdsBytes && qblocks <= p.n_qblocks) {
+        p.kernel = ATTN_32P_POOL;
+        p.pool_rows = rows; p.n_qblocks = qblocks; p.lds = lds;
+        p.grid = static_cast<unsigned>(qblocks * a.H * a.B);
+      }
+    }
     return p;
   }
   // The resident cross pair (<= 64 text keys, <= 256 prompt keys; key lengths do not change the choice: S / S2 are the padded

@@ -20,6 +20,8 @@ constexpr int HD = 64, BKV = 64, ROWB = 128;            // attention: head width
 constexpr int TILE = BKV * ROWB;                        // 8 KiB per K or V tile
 // gathered keys (AttnArgs::key_row, attn32p_hd64): the staged index, 4 bytes per key, shares a workgroup's 64 KiB with 48 KiB of tiles
 constexpr size_t kGatherIndexBytes = 16 * 1024;
+// the key pool (AttnArgs::seg_est, attn32p_hd64 POOL): tiles, staged index and 256 bytes per pool row within a workgroup's 160 KiB
+constexpr size_t kAttnPoolLdsBytes = 160 * 1024;
 
 // epilogue bits = the EPI template argument of every GEMM kernel (d3pm_mfma_tile.h epilogue_store)
 constexpr int EPI_GELU = 1, EPI_R1 = 2, EPI_R2 = 4, EPI_MASK = 8, EPI_RELU = 16, EPI_SILU = 32, EPI_LNF = 64, EPI_STATS = 128;
@@ -85,7 +87,8 @@ enum AttnKernel {
   ATTN_32_CROSS,       // attn32_cross_hd64: the cross pair with K / V resident, 32 x 32 x 16
   ATTN_CROSS,          // attn_cross_hd64: the cross pair with K / V resident, 16 x 16 x 32
   ATTN_SPLIT,          // attn_split_hd64: key tiles split over the four waves
-  ATTN_TILES           // attn_mfma_hd64<qg, pair_seq>: tile by tile
+  ATTN_TILES,          // attn_mfma_hd64<qg, pair_seq>: tile by tile
+  ATTN_32P_POOL        // attn32p_hd64 POOL: the gathered walk of ATTN_32P with the distinct K | V rows of an utterance pooled in LDS
 };
 struct AttnPlan {
   int kernel = ATTN_GENERIC;
@@ -93,13 +96,16 @@ struct AttnPlan {
   int qg = 0;                    // ATTN_TILES: 16-query groups per wave (1 or 2)
   bool pair_seq = false;         // ATTN_TILES: a workgroup runs both problems of a pair one after the other
   int n_qsplit = 0;              // resident cross kernels: workgroups per (utterance, head)
-  int n_qblocks = 0;
+  int n_qblocks = 0;             // ATTN_32P_POOL: the query blocks per (utterance, head) in the grid; a workgroup strides over the rest
+  int pool_rows = 0;             // ATTN_32P_POOL: rows of the K | V pool
   int n_first = 0;               // paired grids: workgroups of the first problem (-1: sequential pair)
   unsigned grid = 0;
   size_t lds = 0;                // dynamic LDS bytes
   bool mfma() const { return kernel != ATTN_GENERIC; }
 };
 AttnPlan plan_attention(int dtype, const AttnArgs& a, bool force_generic = false);
+// the largest AttnArgs::seg_est that takes the pooled self-attention, and the rows of its pool
+int attn_pool_rows();
 
 // the batch the automatic attention choices are made for (a shard of a split batch takes the kernels of the whole batch)
 inline int logical_batch(const d3pm_tuning& tn, int B) { return tn.regime_batch > 0 ? tn.regime_batch : B; }

@@ -146,6 +146,9 @@ struct DenoiserArgs {      // what every block of one evaluation sees
   // with dd, per iteration: the host's estimate of the live rows (plan_live_rows) when the iteration takes the latency launch list --
   // every projection of a block on gemm_mfma_panel64, sized for the estimate, moments as parts -- or 0: the big-tile list, quads
   int m_est = 0;
+  // with dd, per iteration: the rows per utterance the host expects (LoopPlan::seg_est), or 0.  With it the self-attention may pool an
+  // utterance's K | V rows in LDS (AttnArgs::seg_est, plan_attention decides)
+  int seg_est = 0;
 };
 
 // ---- the block sequence with the LayerNorms folded into the projections (ar_discrete.py:126-161; d3pm_mfma_tile.h EPI_LNF / EPI_STATS)
@@ -191,6 +194,8 @@ int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v, bool qkv_
     if (from_table) { sa.K = at(q.qkv_table, d, es); sa.V = at(q.qkv_table, 2 * d, es); sa.key_row = q.dd->key_cls; sa.kv_rows = qkv_table_rows(sh.n_classes); }
     else { sa.key_row = q.dd->row_of; sa.kv_rows = n; }
     sa.ldkv = 3 * d;
+    // the pool names the same rows through the compact row of a position: row_of, and in block 0 the class of that compact row
+    if (q.seg_est) { sa.seg_est = q.seg_est; sa.seg_key = q.dd->row_of; sa.pool_src = from_table ? q.dd->cid : nullptr; }
   }
   D3PM_TRY(v.attention(segments(with_frame_keys(sa, q.keys))));
   D3PM_TRY(v.linear(producer(ws.att, d, b.attn_out_w, b.attn_out_b)));
@@ -248,7 +253,8 @@ struct DedupPlanner {
   }
   int attention(AttnArgs a) {
     a.tune = tune;
-    ok = ok && plan_attention(dt, a).kernel == (a.Q2 ? ATTN_32_CROSS : ATTN_32P);
+    const int k = plan_attention(dt, a).kernel;
+    ok = ok && (a.Q2 ? k == ATTN_32_CROSS : (k == ATTN_32P || k == ATTN_32P_POOL));
     return D3PM_OK;
   }
   int dual(const CrossOutPlan& c, const LinearArgs&, const void*) {
@@ -291,6 +297,12 @@ struct LoopPlan {
     if (!latency || t <= t_stop) return 0;
     const int est = plan_live_rows(batch, canvas, host_h2f(sched->cbar[t]));
     return live_latency(est) ? est : 0;
+  }
+  // DenoiserArgs::seg_est of iteration t: the same estimate per utterance, rounded up.  It follows the `latency` switch (ln_fold = 4
+  // keeps the gathered self-attention in every iteration) but not the bound of the GEMMs: plan_attention has its own.
+  int seg_est(const d3pm_schedule* sched, int t) const {
+    if (!latency || t <= t_stop || batch <= 0) return 0;
+    return (plan_live_rows(batch, canvas, host_h2f(sched->cbar[t])) + batch - 1) / batch;
   }
 };
 LoopPlan loop_plan(const DenoiserArgs& q, uint32_t flags, const LoopCall& call);

@@ -413,6 +413,9 @@ SIGNATURES = {
     "d3pm_op_attention_gather": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                            C.c_void_p, C.POINTER(Tuning), C.c_void_p]),
+    "d3pm_op_attention_gather_pool": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Tuning), C.c_void_p]),
     "d3pm_op_attention_pair": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_float, C.POINTER(Tuning), C.c_void_p]),
@@ -1304,6 +1307,35 @@ def op_attention_gather(q, k, v, key_row, seg_start, seg_len, n_heads, scale, ou
     check(lib().d3pm_op_attention_gather(dtype_code(q.dtype), _p(q), q.stride(0), _p(k), _p(v), k.stride(0), k.shape[0], _p(key_row),
                                          _p(seg_start), _p(seg_len), _p(out), out.stride(0), B, rows // 128 * 128, S, n_heads, d // n_heads,
                                          float(scale), _p(key_len), C.byref(TUNING), stream_ptr()), "d3pm_op_attention_gather")
+    return out
+
+
+def op_attention_gather_pool(q, k, v, key_row, seg_key, seg_start, seg_len, n_heads, scale, out, *, pool_rows, qblocks_grid, pool_src=None,
+                             key_len=None):
+    """op_attention_gather with an utterance's distinct k | v rows pooled in LDS (d3pm_op_attention_gather_pool): seg_key int32 [B, S] names
+    key j of utterance b as row seg_key[b, j] - seg_start[b] of its pool (clamped into the segment), pool row r being row
+    pool_src[seg_start[b] + r] of k / v (int32 [any]; None: row seg_start[b] + r), clamped into them.  An utterance with more than
+    pool_rows rows walks key_row instead.  The caller promises that both name rows with the same bytes.  qblocks_grid: 128-query blocks
+    per (utterance, head) in the grid."""
+    rows, d = q.shape
+    B, S = key_row.shape
+    dev = q.device
+    if k.shape != v.shape or k.shape[1] != d or out.shape != q.shape or out.dtype != q.dtype or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise D3PMError("op_attention_gather_pool: q / out [rows, d] and k / v [kv_rows, d] of one dtype")
+    if k.stride(0) != v.stride(0) or any(t.stride(1) != 1 for t in (q, k, v, out)) or any(t.device != dev for t in (k, v, out, key_row)):
+        raise D3PMError("op_attention_gather_pool: k and v share a row stride; unit column strides; one device")
+    ints = [("key_row", key_row, (B, S)), ("seg_key", seg_key, (B, S)), ("seg_start", seg_start, (B,)), ("seg_len", seg_len, (B,))]
+    if key_len is not None:
+        ints.append(("key_len", key_len, (B,)))
+    if pool_src is not None:
+        ints.append(("pool_src", pool_src, tuple(pool_src.shape[:1])))
+    for name, t, shape in ints:
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise D3PMError(f"{name} must be a contiguous int32 {list(shape)} tensor on {dev}")
+    check(lib().d3pm_op_attention_gather_pool(dtype_code(q.dtype), _p(q), q.stride(0), _p(k), _p(v), k.stride(0), k.shape[0], _p(key_row),
+                                              _p(seg_start), _p(seg_len), _p(out), out.stride(0), B, rows // 128 * 128, S, n_heads, d // n_heads,
+                                              float(scale), _p(key_len), _p(seg_key), _p(pool_src), int(pool_rows), int(qblocks_grid),
+                                              C.byref(TUNING), stream_ptr()), "d3pm_op_attention_gather_pool")
     return out
 
 
