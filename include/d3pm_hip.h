@@ -72,7 +72,8 @@ extern "C" {
  *    log-probability of the revealed id from either loop (d3pm_frame_scores, d3pm_frame_scores_init, d3pm_frame_scores_step,
  *    d3pm_sample_loop_scored, d3pm_reveal_loop_scored); the reveal schedule whose held frames compete again in every step
  *    (d3pm_revise, d3pm_reveal_step_revise, d3pm_reveal_loop_revise); the self-attention of the few-row iterations of the
- *    deduplicated loop with an utterance's distinct K | V rows pooled in LDS (d3pm_op_attention_gather_pool) */
+ *    deduplicated loop with an utterance's distinct K | V rows pooled in LDS (d3pm_op_attention_gather_pool); the NAR stage's
+ *    training step (d3pm_op_adaln_bwd_f32, d3pm_op_nar_embed_bwd_f32, d3pm_op_nar_ce_f32) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -1168,6 +1169,53 @@ int d3pm_op_attention_bwd_keylen_f32(const float *Q, int ldq, const float *K, co
                                      float *dQ, int lddq, float *dK, float *dV, int lddkv, float *stats, int B, int Tq, int S, int H,
                                      int hd, float scale, float beta_kv, const int32_t *key_len, float p, uint64_t seed,
                                      uint32_t utt0, uint32_t site, void *stream);
+
+/* ---- NAR training step: the three ops of the stock NAR model's backward pass that the entries above do not cover ----------
+ * The reference trains the NAR with autograd over the training branch of NAR.forward (vall_e/vall_e/nar.py:53-74: a quantizer
+ * level l_b per utterance, response levels 0 .. l_b in, level l_b + 1 the target) and Base.forward (base.py:403-488).  The host side
+ * (vall_e/vall_e/nar_train.py) runs the forward through d3pm_op_nar_embed / d3pm_op_adaln / d3pm_op_linear /
+ * d3pm_op_attention_keylen on fp32 tensors with a stash and walks it backwards through d3pm_op_matmul_f32, d3pm_op_colsum_f32,
+ * d3pm_op_act_bwd_f32, d3pm_op_mask_rows_f32, d3pm_op_attention_bwd_keylen_f32 and these three.  Device pointers owned by the
+ * caller, fp32, nothing allocates or synchronises; 0 = ok.  Refused with nothing launched: a NULL pointer or a size that is not
+ * positive (D3PM_E_ARG), and what each entry names below.
+ *
+ * d3pm_op_adaln_bwd_f32      the backward pass of d3pm_op_adaln on fp32 rows (AdaLN.forward, base.py:145-158):
+ *                         y = exp(lg) (f h) + beta, h = LayerNorm(x, eps 1e-5) without affine, f = c (1 - k h) with k = 0.1, c = 2, and
+ *                         f a CONSTANT of the backward pass -- upstream writes `(self.k * h).detach()` (:154).  x, dy, dx [M][d] dense,
+ *                         emb_row [2d] = (lg | beta) of one level, row_mask uint8 [M].  For a row with row_mask != 0:
+ *                           dbeta += dy;  dlg += dy exp(lg) f h;  dh = dy exp(lg) f;
+ *                           dx = r (dh - mean(dh) - h mean(dh h)),  r = 1 / sqrt(var + eps)   (added to dx when accumulate != 0);
+ *                         a row with row_mask == 0 contributes nothing, neither x nor dy of it is read, and its dx row is 0 (left as
+ *                         it was when accumulate != 0).  demb_row [2d] = (dlg | dbeta) is accumulated into (the caller zeroes it
+ *                         or hands in the gradient row itself); each element has one writer that adds the rows in a fixed order,
+ *                         so the sums are the same bits from run to run.  Any d > 0.
+ * d3pm_op_nar_embed_bwd_f32  the backward pass of d3pm_op_nar_embed on fp32 tables (base.py:427-435; MultiEmbedding :244-274): the
+ *                         index arrays and sizes of that entry, dx [batch][t_max][d]; each row below its utterance's total adds
+ *                         its dx row to the rows that produced it -- d_text [n_tokens][d], d_prom [n_prom_levels][n_tokens][d] (a code
+ *                         < 0 = level absent, skipped), d_resp [>= n_given][n_tokens][d] (levels 0 .. n_given - 1 only; the others are
+ *                         not touched), d_sep [d] from the two separator rows of every utterance.  Rows at or past the total are not
+ *                         read; the sinusoid table has no gradient.  An id outside [0, n_tokens - 1] is outside the contract: the
+ *                         forward clamps it, here it adds nowhere, and no memory is written through it.  All four gradients are
+ *                         accumulated into; a table row that several tokens share (inside an utterance or across the batch) has
+ *                         one writer that adds their dx rows in grid order, so the result is the same bits from run to run.
+ *                         1 <= n_given <= resp_stride; max(n_prom_levels, n_given) <= 65535, else D3PM_E_SHAPE.
+ * d3pm_op_nar_ce_f32         F.cross_entropy over the response rows (base.py:445-488, resp_loss_only) per grid row: logits
+ *                         [batch][t_max][ldl], ldl >= n_tokens; levels int32 [batch] on the device, 0 <= levels[b] <= resp_stride - 2
+ *                         (the caller's contract; the column read is clamped into the row).  Frame f < t_response of utterance b is
+ *                         grid row t_text + t_prompt + 2 + f (a row outside the grid does not exist) with target
+ *                         resp[b][f][levels[b] + 1] (clamped into [0, n_tokens - 1]):
+ *                           row_loss = logsumexp(logits) - logits[target],  dlogits = (softmax(logits) - onehot(target)) gscale;
+ *                         every other row -- text, separators, prompt, padding -- gets row_loss 0 and an all-zero dlogits row.
+ *                         row_loss [batch][t_max]; dlogits [batch][t_max][ldd], ldd >= n_tokens, or NULL = the loss alone.
+ *                         The step's loss is sum(row_loss) / N and gscale = 1 / N, N the response frames of the call. */
+int d3pm_op_adaln_bwd_f32(const float *x, const float *dy, const float *emb_row, const uint8_t *row_mask, int M, int d, float *dx,
+                          int accumulate, float *demb_row, void *stream);
+int d3pm_op_nar_embed_bwd_f32(const int32_t *lens, const int32_t *text, int tt_max, const int32_t *prom, int tp_max, int n_prom_levels,
+                              const int32_t *resp, int tr_max, int resp_stride, int n_given, const float *dx, float *d_text,
+                              float *d_prom, float *d_resp, float *d_sep, int batch, int t_max, int d, int n_tokens, void *stream);
+int d3pm_op_nar_ce_f32(const float *logits, int ldl, const int32_t *lens, const int32_t *resp, int tr_max, int resp_stride,
+                       const int32_t *levels, int batch, int t_max, int n_tokens, float gscale, float *row_loss, float *dlogits, int ldd,
+                       void *stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

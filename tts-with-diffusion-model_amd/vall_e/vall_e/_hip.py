@@ -470,6 +470,13 @@ SIGNATURES = {
                                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                    C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_uint64,
                                                    C.c_uint32, C.c_uint32, C.c_void_p]),
+    "d3pm_op_adaln_bwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_void_p]),
+    "d3pm_op_nar_embed_bwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_void_p]),
+    "d3pm_op_nar_ce_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                     C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "d3pm_tuning_default": (None, [C.POINTER(Tuning)]),
     "d3pm_prof_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "d3pm_prof_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),

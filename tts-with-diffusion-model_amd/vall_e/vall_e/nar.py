@@ -5,8 +5,9 @@ SURVEY.md §8f row 1).
 Same surface as the reference's /root/reference/vall_e/vall_e/nar.py `class NAR(Base)`: ctor
 `NAR(n_tokens, d_model=512, n_heads=8, n_layers=12, p_dropout=0.1)` (base.py:316-323), state-dict key layout
 (base.py:336-360), `forward(text_list, proms_list, resps_list, sampling_temperature=0.2) -> [LongTensor[t, 8]]`.
-Every level runs in HIP behind `d3pm_nar_level`; PyTorch stores the weights.  The training branch
-(nar.py:53-74) is out of scope.  Sampling uses a Philox Gumbel-max instead of torch's multinomial stream (`seed=`).
+Every level runs in HIP behind `d3pm_nar_level`; PyTorch stores the weights.  Sampling uses a Philox Gumbel-max instead of
+torch's multinomial stream (`seed=`).  The training branch (nar.py:53-74: responses of 8 levels) computes the loss in HIP as well
+(`forward`), and `forward_backward` adds the gradient of every parameter to `.grad` (nar_train.py: fp32 models).
 """
 from __future__ import annotations
 
@@ -93,8 +94,7 @@ class NAR(SymmapState, nn.Module):
         return self.classifier.weight.device
 
     def runner(self, t_max: int) -> _hip.NarRunner:
-        if self.device.type != "cuda":
-            raise RuntimeError("the NAR levels run on MI355X only: move the model to a HIP device; there is no CPU path")
+        self._no_cpu_path()
         sd = dict(self.named_parameters())
         key = (self.dtype, self.device, tuple((k, v.data_ptr(), v._version) for k, v in sd.items()))
         if self._runner is None or self._runner_key != key or self._runner.weights.pe_rows < t_max:
@@ -130,17 +130,49 @@ class NAR(SymmapState, nn.Module):
                 t_max = padded
         return lens, text.contiguous(), prom.contiguous(), resp.contiguous(), t_max, lens_host
 
+    def _no_cpu_path(self):
+        if self.device.type != "cuda":
+            raise RuntimeError("the NAR levels run on MI355X only: move the model to a HIP device; there is no CPU path")
+
+    @torch.no_grad()
+    def forward_backward(self, text_list: Sequence[Tensor], proms_list: Sequence[Tensor], resps_list: Sequence[Tensor], *,
+                         seed: Optional[int] = None, utt0: int = 0, quant_levels=None, dropout=False) -> Tensor:
+        """One training step's loss and gradients (nar.py:53-74, base.py:403-488; nar_train.py): resps_list [t, 8] each.  Utterance b
+        takes the level l_b = quant_levels[b], or the draw of (seed, utt0 + b) (seed=None: one from torch.randint, as generate_audio
+        does); levels 0 .. l_b go in and level l_b + 1 is the target.  nll = the mean cross-entropy over all response frames of the
+        call; its gradient is ADDED to `.grad` (fp32) of every parameter.  dropout: False = eval arithmetic, True = upstream's
+        p = 0.1 at its three sites per block, a number = that probability.  Returns the fp32 scalar loss and sets
+        `self.loss = {"nll": loss}`, where upstream's gather_attribute("loss") reads it.  Data parallel: each rank's loss is the mean
+        over its own frames and train.all_reduce_gradients averages the ranks, as DeepSpeed does upstream.
+        ValueError before any GPU work: lists of unequal length, a response that is not 8 levels wide or is empty, quant_levels of
+        the wrong length or outside 0 .. 6, a dropout outside [0, 1)."""
+        from . import nar_train
+        nar_train.validate(text_list, proms_list, resps_list, quant_levels=quant_levels, dropout=dropout, n_layers=self.cfg.n_layers)
+        self._no_cpu_path()
+        loss, _ = nar_train.NARTrainer(self).step(text_list, proms_list, resps_list, seed=seed, utt0=utt0, quant_levels=quant_levels,
+                                                  dropout=dropout)
+        self.loss = {"nll": loss}
+        return loss
+
     @torch.no_grad()
     def forward(self, text_list: Sequence[Tensor], proms_list: Sequence[Tensor], resps_list: Sequence[Tensor],
                 sampling_temperature: float = 0.2, *, seed: Optional[int] = None, greedy: bool = False, utt0: int = 0,
-                return_logits_level: Optional[int] = None):
-        """resps_list: [t, l] with the levels already known (l = 1 after the D3PM stage) -> [LongTensor[t, 8]]."""
+                return_logits_level: Optional[int] = None, quant_levels=None):
+        """resps_list: [t, l] with the levels already known (l = 1 after the D3PM stage) -> [LongTensor[t, 8]].
+        l = 8 is upstream's training call (nar.py:53-74): the loss of forward_backward(..., seed=, utt0=, quant_levels=) without
+        gradients goes to `self.loss = {"nll": loss}` and [] is returned."""
         levels = {r.shape[-1] for r in resps_list}
         if len(levels) > 1:
             raise ValueError(f"Please give only one level, got {levels}.")
         n_given = next(iter(levels))
         if n_given == self.n_resp_levels + 1:
-            raise NotImplementedError("the training branch of NAR.forward (nar.py:53-74) is outside this build's scope")
+            from . import nar_train
+            nar_train.validate(text_list, proms_list, resps_list, quant_levels=quant_levels)
+            self._no_cpu_path()
+            loss, _ = nar_train.NARTrainer(self).step(text_list, proms_list, resps_list, seed=seed, utt0=utt0, quant_levels=quant_levels,
+                                                      backward=False)
+            self.loss = {"nll": loss}
+            return []
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         lens, text, prom, resp, t_max, lens_host = self._pack(text_list, proms_list, resps_list)

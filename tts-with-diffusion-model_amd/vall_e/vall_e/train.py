@@ -594,7 +594,8 @@ def all_reduce_gradients(model, *, bucket_bytes: int = 64 << 20, average: bool =
     rank but not on this one contributes zeros, so all ranks issue identical collectives; a parameter without a gradient
     on EVERY rank (upstream's dead `cross_attn2` / `token_emb` tensors) is left out and keeps `.grad = None`, exactly as at
     world size 1 -- otherwise weight decay would touch it in data-parallel runs only (one small MAX all-reduce of the
-    has-gradient bitmask decides that)."""
+    has-gradient bitmask decides that).  `model` is any nn.Module: the NAR after `NAR.forward_backward` works the same way (every
+    parameter of it has a gradient on every rank; each rank's loss is the mean over its own frames and the ranks are averaged)."""
     import torch.distributed as dist
     if not dist.is_available() or not dist.is_initialized() or dist.get_world_size() == 1:
         return 0
