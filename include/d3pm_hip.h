@@ -73,7 +73,8 @@ extern "C" {
  *    d3pm_sample_loop_scored, d3pm_reveal_loop_scored); the reveal schedule whose held frames compete again in every step
  *    (d3pm_revise, d3pm_reveal_step_revise, d3pm_reveal_loop_revise); the self-attention of the few-row iterations of the
  *    deduplicated loop with an utterance's distinct K | V rows pooled in LDS (d3pm_op_attention_gather_pool); the NAR stage's
- *    training step (d3pm_op_adaln_bwd_f32, d3pm_op_nar_embed_bwd_f32, d3pm_op_nar_ce_f32) */
+ *    training step (d3pm_op_adaln_bwd_f32, d3pm_op_nar_embed_bwd_f32, d3pm_op_nar_ce_f32); the NAR stage's level draw with known
+ *    frames, top-k / top-p and log-probabilities (d3pm_nar_draw, d3pm_nar_level_draw, d3pm_op_nar_draw) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -872,6 +873,52 @@ int d3pm_nar_level(const d3pm_nar_shape *shape, const d3pm_nar_weights *w, int b
                    int level, float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
                    size_t workspace_bytes, void *logits_out, void *stream);
 
+/* The level draw with options: known frames, top-k / top-p, log-probabilities ----------------------------------------------
+ * What d3pm_sampling / d3pm_nucleus / `known` / d3pm_frame_scores are to the D3PM stage, for the draw of levels 1..7.  Per response
+ * frame, on the row's n_tokens logits l_j of storage type T (no tolerance anywhere):
+ *     v_j    = rn<T>(float(l_j) / temperature)         what the draw without options compares
+ *     theta1 = the top_k-th largest v_j counted with multiplicity                          (top_k 0: -inf)
+ *     v'_j   = v_j >= theta1 ? v_j : -inf              ties at theta1 are all kept, so >= top_k classes survive
+ *     m      = max v'_j,  q_j = (uint32) (expf(v'_j - m) * 1048576.0f),  Q = sum_j q_j     (integers: the same in any order)
+ *     theta  = value of the LARGEST order key c with (double) mass(c) >= (double) top_p * (double) Q,  mass(c) = sum_{key(v'_j) >= c} q_j
+ *                                                                                          (top_p 1: -inf)
+ *     v''_j  = v'_j >= theta ? v'_j : -inf             compared on VALUES: -0 / +0 stand or fall together
+ *     id     = first-index argmax_j v''_j + gumbel(u_j)                                    (D3PM_FLAG_GREEDY: of v''_j)
+ * i.e. d3pm_sampling / d3pm_nucleus above restated for the NAR's v, and a call equals the draw without options fed with the
+ * host-filtered v'' stored in T at temperature 1, id for id.  The order key is that of the value in ITS OWN storage type: 16 bits of
+ * the f16 / bf16 pattern, 32 bits of an fp32 (negative values reverse, the others move above them).  What d3pm_nucleus lists holds
+ * here as well: theta is one of the row's values; the maximum is always kept; top_p <= 1/1280 keeps exactly the classes tied at the
+ * maximum (the ids of top_k = 1); for every set S of classes |sum_S q / Q - sum_S softmax(v')| <= n_tokens / 2^20 + 2^-20.  The noise
+ * does not move: u_j is the Philox word of (j >> 2, (utt0 + b) * 65536 + f, level, stream 2) whatever is cut, and a class that was
+ * cut still draws its own.  A row that is -inf throughout is outside the top-p contract; it still gets an id in 0 .. n_tokens - 1.
+ *   top_p        finite, 0 < top_p <= 1; 1 = off            top_k  0 = off, else 1 .. n_tokens
+ *   known        device uint8 [batch][tr_max] or NULL: a frame with known[b][f] != 0 is not drawn, resp[b][f][level + 1] stays exactly
+ *                as the caller put it; every other frame takes the id it takes without `known`.
+ *   logprob_out  device float [batch][tr_max][n_resp_levels] or NULL: entry [b][f][level] = z_j - max z - logf(sum_k expf(z_k - max z))
+ *                over z = float(l) -- the row's own logits: no temperature, no top-k, no top-p, no further rounding -- at the id j
+ *                that stands in resp[b][f][level + 1] after the call (the drawn id, or a known frame's held id; an id outside
+ *                0 .. n_tokens - 1 reads nothing and gives -inf).  Per-lane partial sums in ascending class, then the wave's sum, as in
+ *                d3pm_frame_scores.  Finite whenever l_j is finite; within 1.0e-4 of the fp64 log-softmax.
+ *   theta_out    device float [batch][tr_max] or NULL: the row's theta (-inf when nothing is cut), NaN on a known frame.  Non-NULL
+ *                takes the kernel's nucleus arm whatever top_p is; the ids are those of the same call without it.
+ * Frames outside an utterance (f >= t_response) or outside the grid write nothing to resp, logprob_out or theta_out.
+ * A NULL d3pm_nar_draw, or {1.0f, 0, NULL, NULL, NULL}, launches what the entry without it launches, bit for bit; anything else
+ * takes the kernel of csrc/d3pm_nar_draw.hip, which needs n_tokens <= 1280 (D3PM_E_SHAPE otherwise).  Refused with D3PM_E_ARG before
+ * anything is launched: a temperature that is not finite and > 0, top_k outside 0 .. n_tokens, top_p not finite or outside (0, 1]. */
+typedef struct d3pm_nar_draw {
+  float top_p;
+  int32_t top_k;
+  const uint8_t *known;
+  float *logprob_out;
+  float *theta_out;
+} d3pm_nar_draw;
+
+/* d3pm_nar_level with draw options. */
+int d3pm_nar_level_draw(const d3pm_nar_shape *shape, const d3pm_nar_weights *w, int batch, int t_max, const int32_t *lens,
+                        const int32_t *text, int tt_max, const int32_t *prom, int tp_max, int32_t *resp, int tr_max,
+                        int level, float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
+                        size_t workspace_bytes, void *logits_out, const d3pm_nar_draw *draw, void *stream);
+
 /* Single-operator entry points (kernel-level parity tests and micro-benchmarks).  `family`:
  * 0 = auto (MFMA when the shape tiles, else generic), 1 = generic FMA kernels, 2 = MFMA (fails with
  * D3PM_E_SHAPE when unsupported).  Same contracts as inside the denoiser:
@@ -1053,6 +1100,11 @@ int d3pm_op_nar_embed(int dtype, const int32_t *lens, const int32_t *text, int t
 int d3pm_op_adaln(int dtype, const void *x, void *y, const void *emb_row, const uint8_t *row_mask, int M, int d, void *stream);
 int d3pm_op_nar_sample(int dtype, const void *logits, int ldl, const int32_t *lens, int32_t *resp, int tr_max, int resp_stride, int t_max,
                        int n_tokens, int level, float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, int batch, void *stream);
+/* d3pm_op_nar_sample with draw options (d3pm_nar_draw above, with n_resp_levels = resp_stride - 1 in logprob_out's layout): the call
+ * d3pm_nar_level_draw makes behind its classifier.  Refusals as for d3pm_op_nar_sample, and those d3pm_nar_draw lists. */
+int d3pm_op_nar_draw(int dtype, const void *logits, int ldl, const int32_t *lens, int32_t *resp, int tr_max, int resp_stride, int t_max,
+                     int n_tokens, int level, float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, int batch,
+                     const d3pm_nar_draw *draw, void *stream);
 int d3pm_op_layernorm(int dtype, const void *X, void *Y, const void *w, const void *b, const void *film,
                       int M, int d, float eps, void *stream);
 /* Row-panel projection (d_model = 512): a Linear whose output is added to the residual stream, together with the LayerNorm(s)

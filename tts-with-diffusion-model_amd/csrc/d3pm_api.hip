@@ -1472,17 +1472,30 @@ size_t d3pm_nar_workspace_bytes(const d3pm_nar_shape* sh, int batch, int t_max) 
   return carve_nar(*sh, batch, t_max, nullptr).total;
 }
 
-int d3pm_nar_level(const d3pm_nar_shape* sh, const d3pm_nar_weights* w, int batch, int t_max, const int32_t* lens,
-                   const int32_t* text, int tt_max, const int32_t* prom, int tp_max, int32_t* resp, int tr_max, int level,
-                   float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace, size_t workspace_bytes,
-                   void* logits_out, void* stream) {
+// d3pm_nar_draw: validated, then `opt` = the kernel's arguments and `neutral` = whether the call is the draw without options
+static int check_nar_draw(const char* who, const d3pm_nar_draw* draw, float temperature, int n_tokens, NarDrawArgs* opt, bool* neutral) {
+  D3PM_REQUIRE(std::isfinite(temperature) && temperature > 0.f, D3PM_E_ARG, "%s: temperature must be finite and > 0", who);
+  *neutral = true;
+  if (!draw) return D3PM_OK;
+  D3PM_REQUIRE(draw->top_k >= 0 && draw->top_k <= n_tokens, D3PM_E_ARG, "%s: top_k %d outside 0 .. %d", who, draw->top_k, n_tokens);
+  D3PM_REQUIRE(std::isfinite(draw->top_p) && draw->top_p > 0.f && draw->top_p <= 1.f, D3PM_E_ARG, "%s: top_p must be within (0, 1]", who);
+  opt->top_p = draw->top_p; opt->top_k = draw->top_k; opt->known = draw->known; opt->logprob_out = draw->logprob_out;
+  opt->theta_out = draw->theta_out;
+  *neutral = draw->top_p == 1.0f && draw->top_k == 0 && !draw->known && !draw->logprob_out && !draw->theta_out;
+  return D3PM_OK;
+}
+
+static int nar_level_run(const char* who, const d3pm_nar_shape* sh, const d3pm_nar_weights* w, int batch, int t_max, const int32_t* lens,
+                         const int32_t* text, int tt_max, const int32_t* prom, int tp_max, int32_t* resp, int tr_max, int level,
+                         float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace, size_t workspace_bytes,
+                         void* logits_out, const NarDrawArgs* draw, void* stream) {
   D3PM_TRY(check_nar(sh, batch, t_max));
   D3PM_REQUIRE(w && w->blocks && w->text_emb && w->proms_emb && w->resps_emb && w->sep && w->classifier_w && w->classifier_b &&
                    w->pe && lens && text && prom && resp && workspace,
-               D3PM_E_ARG, "d3pm_nar_level: null pointer");
+               D3PM_E_ARG, "%s: null pointer", who);
   D3PM_REQUIRE(level >= 0 && level < sh->n_resp_levels && temperature > 0.f && w->pe_rows >= t_max && tt_max > 0 && tp_max > 0 &&
                    tr_max > 0,
-               D3PM_E_ARG, "d3pm_nar_level: bad level / temperature / sizes");
+               D3PM_E_ARG, "%s: bad level / temperature / sizes", who);
   NarWs ws = carve_nar(*sh, batch, t_max, static_cast<char*>(workspace));
   D3PM_REQUIRE(workspace_bytes >= ws.total, D3PM_E_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, ws.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1515,8 +1528,32 @@ int d3pm_nar_level(const d3pm_nar_shape* sh, const d3pm_nar_weights* w, int batc
   D3PM_TRY(run_linear(cx, dt, projection(ws.x, w->classifier_w, w->classifier_b, ws.logits, n, sh->n_tokens, d), flags, s));
   if (logits_out)
     D3PM_CHECK_HIP(hipMemcpyAsync(logits_out, ws.logits, static_cast<size_t>(n) * sh->n_tokens * es, hipMemcpyDeviceToDevice, s));
+  if (draw)
+    return nar_draw(dt, ws.logits, sh->n_tokens, lens, resp, tr_max, stride, t_max, sh->n_tokens, level, temperature, seed, utt0,
+                    (flags & D3PM_FLAG_GREEDY) ? 1 : 0, batch, *draw, s);
   return nar_sample(dt, ws.logits, sh->n_tokens, lens, resp, tr_max, stride, t_max, sh->n_tokens, level, temperature, seed, utt0,
                     (flags & D3PM_FLAG_GREEDY) ? 1 : 0, batch, s);
+}
+
+int d3pm_nar_level(const d3pm_nar_shape* sh, const d3pm_nar_weights* w, int batch, int t_max, const int32_t* lens,
+                   const int32_t* text, int tt_max, const int32_t* prom, int tp_max, int32_t* resp, int tr_max, int level,
+                   float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace, size_t workspace_bytes,
+                   void* logits_out, void* stream) {
+  return nar_level_run("d3pm_nar_level", sh, w, batch, t_max, lens, text, tt_max, prom, tp_max, resp, tr_max, level, temperature, seed,
+                       utt0, flags, workspace, workspace_bytes, logits_out, nullptr, stream);
+}
+
+int d3pm_nar_level_draw(const d3pm_nar_shape* sh, const d3pm_nar_weights* w, int batch, int t_max, const int32_t* lens,
+                        const int32_t* text, int tt_max, const int32_t* prom, int tp_max, int32_t* resp, int tr_max, int level,
+                        float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace, size_t workspace_bytes,
+                        void* logits_out, const d3pm_nar_draw* draw, void* stream) {
+  D3PM_TRY(check_nar(sh, batch, t_max));
+  NarDrawArgs opt;
+  bool neutral = true;
+  D3PM_TRY(check_nar_draw("d3pm_nar_level_draw", draw, temperature, sh->n_tokens, &opt, &neutral));
+  D3PM_REQUIRE(neutral || sh->n_tokens <= 1280, D3PM_E_SHAPE, "d3pm_nar_level_draw: the draw with options supports up to 1280 tokens");
+  return nar_level_run("d3pm_nar_level_draw", sh, w, batch, t_max, lens, text, tt_max, prom, tp_max, resp, tr_max, level, temperature,
+                       seed, utt0, flags, workspace, workspace_bytes, logits_out, neutral ? nullptr : &opt, stream);
 }
 
 // the three kernels of the stage one at a time (tests): host validation, then the call d3pm_nar_level makes
@@ -1555,6 +1592,22 @@ int d3pm_op_nar_sample(int dtype, const void* logits, int ldl, const int32_t* le
                D3PM_E_ARG, "d3pm_op_nar_sample: sizes must be positive, ldl >= n_tokens, 0 <= level < resp_stride - 1, temperature > 0");
   return nar_sample(dtype, logits, ldl, lens, resp, tr_max, resp_stride, t_max, n_tokens, level, temperature, seed, utt0,
                     (flags & D3PM_FLAG_GREEDY) ? 1 : 0, batch, static_cast<hipStream_t>(stream));
+}
+
+int d3pm_op_nar_draw(int dtype, const void* logits, int ldl, const int32_t* lens, int32_t* resp, int tr_max, int resp_stride, int t_max,
+                     int n_tokens, int level, float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, int batch,
+                     const d3pm_nar_draw* draw, void* stream) {
+  D3PM_REQUIRE(storage_dtype(dtype), D3PM_E_ARG, "d3pm_op_nar_draw: bad dtype %d", dtype);
+  D3PM_REQUIRE(logits && lens && resp, D3PM_E_ARG, "d3pm_op_nar_draw: null pointer");
+  D3PM_REQUIRE(batch > 0 && t_max > 0 && tr_max > 0 && n_tokens > 0 && ldl >= n_tokens && level >= 0 && level + 1 < resp_stride,
+               D3PM_E_ARG, "d3pm_op_nar_draw: sizes must be positive, ldl >= n_tokens, 0 <= level < resp_stride - 1");
+  NarDrawArgs opt;
+  bool neutral = true;
+  D3PM_TRY(check_nar_draw("d3pm_op_nar_draw", draw, temperature, n_tokens, &opt, &neutral));
+  const int greedy = (flags & D3PM_FLAG_GREEDY) ? 1 : 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (neutral) return nar_sample(dtype, logits, ldl, lens, resp, tr_max, resp_stride, t_max, n_tokens, level, temperature, seed, utt0, greedy, batch, s);
+  return nar_draw(dtype, logits, ldl, lens, resp, tr_max, resp_stride, t_max, n_tokens, level, temperature, seed, utt0, greedy, batch, opt, s);
 }
 
 int d3pm_op_linear(int dtype, int family, const void* X, int ldx, const void* W, const void* bias, void* Y, int ldy,

@@ -377,5 +377,16 @@ int adaln(int dtype, const void* x, void* y, const void* emb_row, const uint8_t*
 int nar_sample(int dtype, const void* logits, int ldl, const int32_t* lens, int32_t* resp, int tr_max, int resp_stride,
                int t_max, int n_tokens, int level, float temperature, uint64_t seed, uint32_t utt0, int greedy, int batch,
                hipStream_t s);
+// the same draw with options (d3pm_nar_draw.hip; d3pm_nar_draw of include/d3pm_hip.h, validated by the caller): n_tokens <= 1280
+struct NarDrawArgs {
+  float top_p = 1.0f;
+  int top_k = 0;
+  const uint8_t* known = nullptr;      // [B][tr_max], != 0: the frame keeps the id it holds
+  float* logprob_out = nullptr;        // [B][tr_max][resp_stride - 1]
+  float* theta_out = nullptr;          // [B][tr_max]; non-NULL takes the nucleus arm
+};
+int nar_draw(int dtype, const void* logits, int ldl, const int32_t* lens, int32_t* resp, int tr_max, int resp_stride, int t_max,
+             int n_tokens, int level, float temperature, uint64_t seed, uint32_t utt0, int greedy, int batch, const NarDrawArgs& d,
+             hipStream_t s);
 
 }  // namespace d3pm

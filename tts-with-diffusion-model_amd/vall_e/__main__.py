@@ -45,6 +45,17 @@ The second form takes what those front-ends write (formats.py) and writes what E
                 also save how sure the D3PM stage was of every frame: torch.save({"logprob": float32 [N], "step": int32 [N]}) of the
                 N frames written -- the model's log-probability of the id a frame took when it left the mask, and the timestep of that
                 evaluation (-1: a frame of the --continue-from prefix; include/d3pm_hip.h: d3pm_frame_scores)
+  --nar-top-k N, --nar-top-p P
+                the same two cuts for the NAR stage (with --nar-ckpt): every draw of levels 1..7 takes the N largest of its
+                logit / sampling_temperature (0 = off, the default; ties kept) and the smallest set of them that carries the share P
+                of the mass (default 1 = off; include/d3pm_hip.h: d3pm_nar_draw)
+  --nar-logprobs PATH
+                also save how sure the NAR stage was: torch.save(float32 [N, 7]), column c = the model's log-probability of the
+                level c + 1 code of every frame written (of the prefix's own codes under --keep-prefix-levels)
+  --keep-prefix-levels
+                with --continue-from and --nar-ckpt: all 8 levels of that file are known to the NAR stage, so the first rows of OUT
+                are the file's in every level and the recording's sound is kept.  Without it the NAR stage fills levels 1..7 of the
+                prefix again, as it always did
 """
 import argparse
 from pathlib import Path
@@ -78,6 +89,10 @@ def main(argv=None):
     ap.add_argument("--mask-padding", action="store_true", help="D3PM stage: key-padding masks, the utterance ignores its own padding")
     ap.add_argument("--guidance", type=float, default=0.0, help="D3PM stage: classifier-free guidance weight w (>= 0, 0 = off): draw from (1 + w) cond - w null")
     ap.add_argument("--logprobs", type=Path, default=None, help="D3PM stage: save the per-frame log-probability of the revealed ids and their timesteps here")
+    ap.add_argument("--nar-top-k", type=int, default=0, help="NAR stage: draw every level from its N largest logits only (0 = off)")
+    ap.add_argument("--nar-top-p", type=float, default=1.0, help="NAR stage: draw from the smallest set of classes that carries this share of the mass (1 = off)")
+    ap.add_argument("--nar-logprobs", type=Path, default=None, help="NAR stage: save the [frames, 7] log-probabilities of the codes of levels 1..7 here")
+    ap.add_argument("--keep-prefix-levels", action="store_true", help="with --continue-from: the prefix's 8 levels are known to the NAR stage")
     ap.add_argument("--native", action="store_true", help="the shape upstream's class really builds (d=32, 16 heads, 8 blocks)")
     args = ap.parse_args(argv)
 
@@ -90,6 +105,12 @@ def main(argv=None):
             raise ValueError("--guidance does not combine with --reveal-steps")
         if _hip.revise_options(args.revise) is not None and args.reveal_steps is None:
             raise ValueError("--revise needs --reveal-steps")
+        _hip.nar_draw_options(args.nar_top_k, args.nar_top_p, 1024)
+        if args.keep_prefix_levels and args.continue_from is None:
+            raise ValueError("--keep-prefix-levels needs --continue-from")
+        nar_flags = args.nar_top_k != 0 or args.nar_top_p != 1.0 or args.nar_logprobs is not None or args.keep_prefix_levels
+        if nar_flags and args.nar_ckpt is None:
+            raise ValueError("--nar-top-k / --nar-top-p / --nar-logprobs / --keep-prefix-levels need --nar-ckpt")
     except ValueError as e:
         ap.error(str(e))
     if len(args.paths) not in (1, 3):
@@ -155,8 +176,25 @@ def main(argv=None):
         nar = get_model(args.nar_model)
         nar.load_state_dict(torch.load(args.nar_ckpt, map_location="cpu"))
         nar = nar.to(dtype).to(args.device)
+        nar_kw = {}                        # (the keywords reach the NAR model only when their flags are given)
+        if args.nar_top_k != 0:
+            nar_kw["top_k"] = args.nar_top_k
+        if args.nar_top_p != 1.0:
+            nar_kw["top_p"] = args.nar_top_p
+        if args.keep_prefix_levels:
+            full = formats.load_quants(args.continue_from)[:n_frames]                # (t, 8): every level of the prefix
+            known = torch.zeros((n_frames, full.shape[1]), dtype=torch.long)
+            known[: len(full)] = full
+            nar_kw["known"] = [known]
+            nar_kw["known_mask"] = [torch.arange(n_frames) < len(full)]
+        if args.nar_logprobs is not None:
+            nar_kw["return_logprobs"] = True
         resps = nar(text_list=[phns.to(args.device)], proms_list=[proms.to(args.device)], resps_list=[resps],
-                    seed=args.seed)[0]
+                    seed=args.seed, **nar_kw)
+        if args.nar_logprobs is not None:
+            resps, nar_scores = resps
+            torch.save(nar_scores[0].cpu(), args.nar_logprobs)
+        resps = resps[0]
     if upstream_form:
         from . import frontends
         frontends.encodec_decode_to_file(resps, args.out_path, args.device)         # qnt.decode_to_file, __main__.py:72

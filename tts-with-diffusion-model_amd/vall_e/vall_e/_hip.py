@@ -190,6 +190,35 @@ def nucleus_options(temperature=1.0, top_k=0, top_p=1.0, n_classes=None):
     return Nucleus(1.0, 0, p) if smp is None else Nucleus(smp.temperature, smp.top_k, p)
 
 
+class NarDraw(C.Structure):
+    """d3pm_nar_draw: the options of the NAR stage's level draw (include/d3pm_hip.h)."""
+    _fields_ = [("top_p", C.c_float), ("top_k", C.c_int32), ("known", C.c_void_p), ("logprob_out", C.c_void_p), ("theta_out", C.c_void_p)]
+
+
+def nar_draw_options(top_k=0, top_p=1.0, n_tokens=None):
+    """Host validation of the NAR draw's two filter options (ValueError, before any GPU work) -> (top_k, top_p as the float the
+    library receives)."""
+    if isinstance(top_k, bool) or not isinstance(top_k, Integral):
+        raise ValueError(f"top_k must be an int, got {top_k!r}")
+    k = int(top_k)
+    if k < 0 or (n_tokens is not None and k > n_tokens):
+        raise ValueError(f"top_k must be 0 (off) or 1..{n_tokens}, got {k}")
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)):
+        raise ValueError(f"top_p must be a number, got {top_p!r}")
+    p = float(top_p)
+    if not (math.isfinite(p) and 0.0 < p <= 1.0) or not 0.0 < C.c_float(p).value <= 1.0:
+        raise ValueError(f"top_p must be finite, > 0 and <= 1 (1 = off), got {top_p!r}")
+    return k, C.c_float(p).value
+
+
+def nar_draw_struct(top_k=0, top_p=1.0, known=None, logprob_out=None, theta_out=None):
+    """-> None for the neutral options (the entries and the kernel that know nothing of them), else a NarDraw over the tensors'
+    addresses (the caller keeps the tensors alive over the call)."""
+    if top_k == 0 and top_p == 1.0 and known is None and logprob_out is None and theta_out is None:
+        return None
+    return NarDraw(top_p, top_k, _p(known), _p(logprob_out), _p(theta_out))
+
+
 class Guidance(C.Structure):
     """d3pm_guidance: the weight w of classifier-free guidance, z = rn16(fmaf(w, c - u, c)) (include/d3pm_hip.h)."""
     _fields_ = [("weight", C.c_float)]
@@ -401,6 +430,9 @@ SIGNATURES = {
     "d3pm_nar_level": (C.c_int, [C.POINTER(NarShape), C.POINTER(NarWeights), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64,
                                  C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "d3pm_nar_level_draw": (C.c_int, [C.POINTER(NarShape), C.POINTER(NarWeights), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64,
+                                      C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(NarDraw), C.c_void_p]),
     "d3pm_op_linear": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.POINTER(Tuning), C.c_void_p]),
@@ -432,6 +464,8 @@ SIGNATURES = {
     "d3pm_op_adaln": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "d3pm_op_nar_sample": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
+    "d3pm_op_nar_draw": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(NarDraw), C.c_void_p]),
     "d3pm_op_layernorm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_int, C.c_float, C.c_void_p]),
     "d3pm_op_linear_rowpanel": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1501,10 +1535,8 @@ def op_adaln(x, emb_row, row_mask, *, out=None):
     return out
 
 
-def op_nar_sample(logits, lens, resp, level, temperature, seed, *, utt0=0, flags=0):
-    """The NAR stage's level draw on its own (d3pm_op_nar_sample): logits [B, t_max, n_tokens] of a float dtype (a view with a wider
-    row stride allowed, dense in t), lens int32 [B, 3], resp int32 [B, tr_max, resp_stride]: column level + 1 of every response frame
-    inside the grid is written in place; returns resp.  flags: FLAG_GREEDY."""
+def _nar_draw_extents(logits, lens, resp, level):
+    """The tensor checks the two draw entries share -> (B, t_max, n_tokens, ldl, device)."""
     if not isinstance(logits, torch.Tensor) or logits.dim() != 3 or logits.dtype not in _DTYPES or logits.numel() == 0:
         raise D3PMError(f"logits must be a [B, t_max, n_tokens] tensor of one of {tuple(_DTYPES)}")
     B, t_max, n_tokens = logits.shape
@@ -1516,8 +1548,38 @@ def op_nar_sample(logits, lens, resp, level, temperature, seed, *, utt0=0, flags
     _require_int32([("lens", lens, (B, 3)), ("resp", resp, (B, resp.shape[1], resp.shape[2]))], dev)
     if not isinstance(level, int) or not 0 <= level < resp.shape[2] - 1:
         raise D3PMError(f"level {level!r} must be within 0 .. {resp.shape[2] - 2}")
+    return B, t_max, n_tokens, ldl, dev
+
+
+def op_nar_sample(logits, lens, resp, level, temperature, seed, *, utt0=0, flags=0):
+    """The NAR stage's level draw on its own (d3pm_op_nar_sample): logits [B, t_max, n_tokens] of a float dtype (a view with a wider
+    row stride allowed, dense in t), lens int32 [B, 3], resp int32 [B, tr_max, resp_stride]: column level + 1 of every response frame
+    inside the grid is written in place; returns resp.  flags: FLAG_GREEDY."""
+    B, t_max, n_tokens, ldl, dev = _nar_draw_extents(logits, lens, resp, level)
     check(lib().d3pm_op_nar_sample(dtype_code(logits.dtype), _p(logits), ldl, _p(lens), _p(resp), resp.shape[1], resp.shape[2], t_max,
                                    n_tokens, level, float(temperature), seed, utt0, flags, B, stream_ptr()), "d3pm_op_nar_sample")
+    return resp
+
+
+def op_nar_draw(logits, lens, resp, level, temperature, seed, *, utt0=0, flags=0, top_k=0, top_p=1.0, known=None, logprob_out=None,
+                theta_out=None):
+    """op_nar_sample with the draw options (d3pm_op_nar_draw): top_k / top_p as nar_draw_options checks them; known uint8 [B, tr_max]
+    (a frame with a non-zero byte keeps the id resp holds); logprob_out float32 [B, tr_max, resp_stride - 1], column `level` of every
+    response frame inside the grid written; theta_out float32 [B, tr_max].  With every option at its default this is op_nar_sample's
+    launch.  Returns resp."""
+    B, t_max, n_tokens, ldl, dev = _nar_draw_extents(logits, lens, resp, level)
+    top_k, top_p = nar_draw_options(top_k, top_p, n_tokens)
+    tr_max = resp.shape[1]
+    if known is not None:
+        _require(known, "known", (B, tr_max), (torch.uint8,), dev)
+    if logprob_out is not None:
+        _require(logprob_out, "logprob_out", (B, tr_max, resp.shape[2] - 1), (torch.float32,), dev)
+    if theta_out is not None:
+        _require(theta_out, "theta_out", (B, tr_max), (torch.float32,), dev)
+    draw = nar_draw_struct(top_k, top_p, known, logprob_out, theta_out)
+    check(lib().d3pm_op_nar_draw(dtype_code(logits.dtype), _p(logits), ldl, _p(lens), _p(resp), tr_max, resp.shape[2], t_max, n_tokens,
+                                 level, float(temperature), seed, utt0, flags, B, None if draw is None else C.byref(draw), stream_ptr()),
+          "d3pm_op_nar_draw")
     return resp
 
 
@@ -1691,8 +1753,9 @@ class NarRunner:
                                   ptr("classifier.weight"), ptr("classifier.bias"), pe.data_ptr(), pe.shape[0], self.blocks)
         self._ws = None
 
-    def level(self, lens, text, prom, resp, t_max, level, temperature, seed, utt0=0, flags=0, want_logits=False):
-        """One quantizer level for the whole batch; `resp` [B, tr_max, n_resp_levels+1] int32 is updated in place."""
+    def level(self, lens, text, prom, resp, t_max, level, temperature, seed, utt0=0, flags=0, want_logits=False, draw=None):
+        """One quantizer level for the whole batch; `resp` [B, tr_max, n_resp_levels+1] int32 is updated in place.  draw: None = the
+        draw without options (d3pm_nar_level), else a NarDraw (d3pm_nar_level_draw) whose tensors the caller keeps alive."""
         cfg, B = self.cfg, lens.shape[0]
         need = lib().d3pm_nar_workspace_bytes(C.byref(self.shape), B, t_max)
         if need == 0:
@@ -1700,6 +1763,12 @@ class NarRunner:
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         logits = torch.empty((B, t_max, cfg.n_tokens), dtype=self.dtype, device=self.device) if want_logits else None
+        if draw is not None:
+            check(lib().d3pm_nar_level_draw(C.byref(self.shape), C.byref(self.weights), B, t_max, _p(lens), _p(text), text.shape[1],
+                                            _p(prom), prom.shape[1], _p(resp), resp.shape[1], int(level), float(temperature), seed,
+                                            utt0, flags, _p(self._ws), self._ws.numel(), _p(logits), C.byref(draw), stream_ptr()),
+                  "d3pm_nar_level_draw")
+            return logits
         check(lib().d3pm_nar_level(C.byref(self.shape), C.byref(self.weights), B, t_max, _p(lens), _p(text), text.shape[1],
                                    _p(prom), prom.shape[1], _p(resp), resp.shape[1], int(level), float(temperature), seed,
                                    utt0, flags, _p(self._ws), self._ws.numel(), _p(logits), stream_ptr()), "d3pm_nar_level")

@@ -77,13 +77,16 @@ def generate_audio_dp(model, text_list: Sequence[torch.Tensor], proms_list: Sequ
 
 def generate_codes_dp(ar, nar, text_list: Sequence[torch.Tensor], proms_list: Sequence[torch.Tensor], *, seed: int,
                       group=None, ar_fn: Optional[Callable] = None, nar_fn: Optional[Callable] = None,
-                      **kw) -> torch.Tensor:
+                      nar_kw: Optional[dict] = None, **kw) -> torch.Tensor:
     """Both stages of the reference's inference script (/root/reference/vall_e/__main__.py:60-71) sharded the same way:
     every rank runs the D3PM stage and then the NAR stage (levels 1..7) for its contiguous slice of the utterances --
     noise keyed by the global utterance index in both -- and ONE all-gather returns the int64 [B, n_frames, 8] codes
     to every rank.  No collective sits between the stages: a rank's NAR input is its own D3PM output.
     With a sequence `n_frames` (one length per utterance) the NAR stage sees utterance b's own L_b frames and the result is
-    [B, max L, 8], zero beyond L_b."""
+    [B, max L, 8], zero beyond L_b.
+    nar_kw: keyword options of the NAR stage (NAR.forward: sampling_temperature, greedy, top_k, top_p, known, known_mask); the
+    per-utterance lists among them (known, known_mask) are cut to the rank's shard like those of the D3PM stage.  The result is the
+    codes alone, so return_logprobs is not taken here."""
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank(group) if world > 1 else 0
     B = len(text_list)
@@ -94,6 +97,9 @@ def generate_codes_dp(ar, nar, text_list: Sequence[torch.Tensor], proms_list: Se
     if len(lens) != B:
         raise ValueError(f"n_frames has {len(lens)} entries for {B} utterances")
     n_frames = max(lens)
+    nar_kw = dict(nar_kw or {})
+    if nar_kw.get("return_logprobs") or nar_kw.get("return_logits_level") is not None:
+        raise ValueError("generate_codes_dp returns the codes alone: call the NAR model itself for its log-probabilities or logits")
     gen = ar_fn or ar.generate_audio
     fill = nar_fn or nar
     if ar_fn is None:
@@ -103,7 +109,7 @@ def generate_codes_dp(ar, nar, text_list: Sequence[torch.Tensor], proms_list: Se
         texts, proms = list(text_list[lo:hi]), list(proms_list[lo:hi])
         lvl0 = gen(texts, proms, seed=seed, utt0=lo, **_shard_kwargs(kw, lo, hi)).reshape(hi - lo, -1)
         resps = [lvl0[b][: lens[lo + b]].clamp(max=nar.n_tokens - 1).reshape(-1, 1) for b in range(hi - lo)]
-        full = fill(texts, proms, resps, seed=seed, utt0=lo)
+        full = fill(texts, proms, resps, seed=seed, utt0=lo, **_shard_kwargs(nar_kw, lo, hi))
         local = torch.zeros((hi - lo, n_frames, levels), dtype=torch.int32, device=full[0].device)
         for b, f in enumerate(full):
             local[b, : lens[lo + b]] = f.reshape(lens[lo + b], levels).to(torch.int32)

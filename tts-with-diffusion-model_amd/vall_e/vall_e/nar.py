@@ -154,17 +154,55 @@ class NAR(SymmapState, nn.Module):
         self.loss = {"nll": loss}
         return loss
 
+    def _check_known(self, resps_list, known, known_mask):
+        """ValueError for a known / known_mask pair that does not fit the responses; nothing here reads a tensor's contents."""
+        if (known is None) != (known_mask is None):
+            raise ValueError("known and known_mask go together: give both or neither")
+        if known is None:
+            return
+        if len(known) != len(resps_list) or len(known_mask) != len(resps_list):
+            raise ValueError(f"known has {len(known)} and known_mask {len(known_mask)} entries for {len(resps_list)} utterances")
+        for b, (r, k, m) in enumerate(zip(resps_list, known, known_mask)):
+            if not isinstance(k, Tensor) or k.dim() != 2 or tuple(k.shape) != (r.shape[0], self.n_resp_levels + 1) or k.is_floating_point():
+                raise ValueError(f"known[{b}] must be an integer [{r.shape[0]}, {self.n_resp_levels + 1}] tensor of codes, got "
+                                 f"{tuple(k.shape) if isinstance(k, Tensor) else type(k).__name__}")
+            if not isinstance(m, Tensor) or m.dtype != torch.bool or tuple(m.shape) != (r.shape[0],):
+                raise ValueError(f"known_mask[{b}] must be a bool [{r.shape[0]}] tensor")
+
     @torch.no_grad()
     def forward(self, text_list: Sequence[Tensor], proms_list: Sequence[Tensor], resps_list: Sequence[Tensor],
                 sampling_temperature: float = 0.2, *, seed: Optional[int] = None, greedy: bool = False, utt0: int = 0,
-                return_logits_level: Optional[int] = None, quant_levels=None):
+                return_logits_level: Optional[int] = None, quant_levels=None, top_k: int = 0, top_p: float = 1.0, known=None,
+                known_mask=None, return_logprobs: bool = False):
         """resps_list: [t, l] with the levels already known (l = 1 after the D3PM stage) -> [LongTensor[t, 8]].
         l = 8 is upstream's training call (nar.py:53-74): the loss of forward_backward(..., seed=, utt0=, quant_levels=) without
-        gradients goes to `self.loss = {"nll": loss}` and [] is returned."""
+        gradients goes to `self.loss = {"nll": loss}` and [] is returned.
+
+        Options of the level draw (include/d3pm_hip.h: d3pm_nar_draw; with all of them at their defaults the call makes the launches it
+        makes without them):
+          top_k, top_p     every level draws from the top_k largest of its rn(logit / sampling_temperature) (0 = off, ties kept) and
+                           from the smallest set of them that carries the share top_p of the softmax mass (1 = off).
+          known, known_mask  per utterance a [t, 8] tensor of codes and a bool [t]: at a frame whose mask is set, levels l .. 7 of the
+                           result are known's and the later levels are conditioned on them; levels < l of `known` are ignored (those
+                           of resps_list stand).  Both or neither.
+          return_logprobs  -> (codes, [FloatTensor[t, 7]]): column c = the model's log-probability (its own logits: no temperature, no
+                           cut) of the level c + 1 code that stands in the result, drawn or known; 0 in the columns of levels that
+                           were given.
+        ValueError before any GPU work: lists of unequal length, a known / known_mask of the wrong shape or one without the other,
+        top_k / top_p out of range, and any of these options together with the 8-level training call."""
         levels = {r.shape[-1] for r in resps_list}
         if len(levels) > 1:
             raise ValueError(f"Please give only one level, got {levels}.")
         n_given = next(iter(levels))
+        options = top_k != 0 or top_p != 1.0 or known is not None or known_mask is not None or return_logprobs
+        if options:
+            if n_given == self.n_resp_levels + 1:
+                raise ValueError("top_k / top_p / known / known_mask / return_logprobs belong to the inference call: the responses "
+                                 "have all 8 levels, which is the training call")
+            if not (len(text_list) == len(proms_list) == len(resps_list)):
+                raise ValueError(f"{len(text_list)} texts, {len(proms_list)} prompts and {len(resps_list)} responses")
+            top_k, top_p = _hip.nar_draw_options(top_k, top_p, self.n_tokens)
+            self._check_known(resps_list, known, known_mask)
         if n_given == self.n_resp_levels + 1:
             from . import nar_train
             nar_train.validate(text_list, proms_list, resps_list, quant_levels=quant_levels)
@@ -175,15 +213,30 @@ class NAR(SymmapState, nn.Module):
             return []
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        held = None
+        if known is not None:
+            # the known codes go into the levels the stage has yet to fill, at the masked frames alone: _pack carries them into `resp`,
+            # where the draw leaves them and the next level's input assembly reads them
+            dev = self.device
+            resps_list = [torch.cat([r.to(dev), (k.to(dev)[:, n_given:] * m.to(dev)[:, None]).to(r.dtype)], dim=1)
+                          for r, k, m in zip(resps_list, known, known_mask)]
         lens, text, prom, resp, t_max, lens_host = self._pack(text_list, proms_list, resps_list)
         run = self.runner(t_max)
         flags = _hip.FLAG_GREEDY if greedy else 0
         logits = None
         with torch.cuda.device(self.device):
+            if known is not None:
+                from torch.nn.utils.rnn import pad_sequence
+                held = pad_sequence([m.to(device=self.device, dtype=torch.uint8) for m in known_mask], batch_first=True).contiguous()
+            logprob = torch.zeros((resp.shape[0], resp.shape[1], self.n_resp_levels), dtype=torch.float32, device=self.device) if return_logprobs else None
+            draw = _hip.nar_draw_struct(top_k, top_p, held, logprob) if options else None
             for level in range(n_given - 1, self.n_resp_levels):
                 lg = run.level(lens, text, prom, resp, t_max, level, sampling_temperature, seed, utt0, flags,
-                               want_logits=(return_logits_level == level))
+                               want_logits=(return_logits_level == level), draw=draw)
                 if lg is not None:
                     logits = lg
         out = [resp[b, : lens_host[b][2]].long() for b in range(len(text_list))]
+        if return_logprobs:
+            scores = [logprob[b, : lens_host[b][2]] for b in range(len(text_list))]
+            return (out, logits, lens, t_max, scores) if return_logits_level is not None else (out, scores)
         return (out, logits, lens, t_max) if return_logits_level is not None else out
