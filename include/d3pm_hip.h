@@ -113,7 +113,12 @@ enum {
  *                      4 = always the latency schedule (64 x 64 tiles, every DMA piece of K <= 512 in flight at once);
  *                      5 = throughput schedule with one tile per workgroup (the non-persistent form of 2);
  *                      6 / 7 / 8 = as auto, but only the 192 x 256 / 96 x 512 / 192 x 128 (two 4-wave workgroups per CU) big
- *                          tile is considered, for any shape made of whole tiles.
+ *                          tile is considered, for any shape made of whole tiles;
+ *                      9 / 10 = as auto, but a projection onto the residual stream that leaves its row moments as quads (and the
+ *                          dual cross-attention out-projection) takes the 96 x 128 / 128 x 128 tile (four waves of three / four
+ *                          16-row blocks) for any shape made of whole tiles.  In auto mode the deduplicated sampler loop gives
+ *                          these projections the shortest such tile whose tiles of the estimated distinct rows fit two per CU
+ *                          in one round (12 288 / 16 384 rows at d_model = 512), and the 192 x 128 tile beyond.
  *   gemm_persist_slots resident workgroups of the persistent 128 x 128 schedule, a multiple of 8 (default 1024 = 4 per CU).
  *   lat_tile           tile of the latency GEMM: 0 = auto (fewest rounds over the 256 CUs, then most workgroups),
  *                      1 / 2 / 3 = always 64 x 64 / 96 x 64 / 32 x 64.
@@ -994,6 +999,14 @@ int d3pm_op_linear_live_est(int dtype, const void *X, const void *X2, int ldx, c
                             const void *R1, int ldr, const uint8_t *row_mask, int mask_period, int M, int N, int K, int act,
                             const float *fold_s, const float *fold_b, const float *stats_in, float *stats_out, const int32_t *m_live,
                             int m_est, const d3pm_tuning *tuning, void *stream);
+/* The same with the second estimate, the one the loop gives the projections onto the residual stream in the iterations that stay on big
+ * tiles (tests; rows_est = 0 = none, which is d3pm_op_linear_live_est): with 0 < rows_est < M and gemm_variant = 0 the big-tile geometry
+ * of a projection with R1 and quads out (the dual included) is chosen for the tiles of rows_est rows -- 96 x 128 or 128 x 128 instead
+ * of 192 x 128 while those fit two per CU in one round.  Any *m_live in 0 .. M gives the same rows whatever the estimate. */
+int d3pm_op_linear_live_rows(int dtype, const void *X, const void *X2, int ldx, const void *W, const void *bias, void *Y, int ldy,
+                             const void *R1, int ldr, const uint8_t *row_mask, int mask_period, int M, int N, int K, int act,
+                             const float *fold_s, const float *fold_b, const float *stats_in, float *stats_out, const int32_t *m_live,
+                             int m_est, int rows_est, const d3pm_tuning *tuning, void *stream);
 /* The block-0 QKV rows of `n` token ids as the sampler loop makes them under ln_fold = 1 (tests): builds the table [rows][3 d_model]
  * (row id = the folded QKV projection of resps_emb[id] with that row's moments, row n_classes = that of a zero row) in `storage`
  * (device, 256-byte aligned, >= d3pm_op_embed_qkv_bytes(shape, n)), then q_out[r] [n][d_model] | kv_out[r] [n][2 d_model] = the q and

@@ -557,8 +557,17 @@ int d3pm_op_linear_live(int dtype, const void* X, const void* X2, int ldx, const
 int d3pm_op_linear_live_est(int dtype, const void* X, const void* X2, int ldx, const void* W, const void* bias, void* Y, int ldy, const void* R1,
                             int ldr, const uint8_t* row_mask, int mask_period, int M, int N, int K, int act, const float* fold_s, const float* fold_b,
                             const float* stats_in, float* stats_out, const int32_t* m_live, int m_est, const d3pm_tuning* tuning, void* stream) {
-  D3PM_REQUIRE(X && W && Y && m_live && M > 0 && N > 0 && K > 0 && m_est >= 0, D3PM_E_ARG, "d3pm_op_linear_live: bad arguments");
+  return d3pm_op_linear_live_rows(dtype, X, X2, ldx, W, bias, Y, ldy, R1, ldr, row_mask, mask_period, M, N, K, act, fold_s, fold_b, stats_in, stats_out,
+                                  m_live, m_est, 0, tuning, stream);
+}
+
+int d3pm_op_linear_live_rows(int dtype, const void* X, const void* X2, int ldx, const void* W, const void* bias, void* Y, int ldy, const void* R1,
+                             int ldr, const uint8_t* row_mask, int mask_period, int M, int N, int K, int act, const float* fold_s, const float* fold_b,
+                             const float* stats_in, float* stats_out, const int32_t* m_live, int m_est, int rows_est, const d3pm_tuning* tuning,
+                             void* stream) {
+  D3PM_REQUIRE(X && W && Y && m_live && M > 0 && N > 0 && K > 0 && m_est >= 0 && rows_est >= 0, D3PM_E_ARG, "d3pm_op_linear_live: bad arguments");
   LinearArgs g;
+  g.rows_est = rows_est;
   g.tune = tuning;
   g.X = X; g.ldx = ldx; g.W = W; g.bias = bias; g.Y = Y; g.ldy = ldy; g.R1 = R1; g.ldr = ldr; g.M = M; g.N = N; g.K = K; g.act = act;
   g.row_mask = row_mask; g.mask_period = mask_period > 0 ? mask_period : 1;
@@ -576,9 +585,13 @@ int d3pm_op_linear_live_est(int dtype, const void* X, const void* X2, int ldx, c
     return big_dual(dtype, g, X2, c.dual, s);
   }
   LinearPlan plan = plan_linear(dtype, g);
-  if (plan.kernel != LIN_PANEL64) {
-    g.moment_quads = quads;
-    plan = plan_linear(dtype, g);
+  // (a gemm_variant that forces a big-tile geometry is asked again with quads even where the parts format fell to the latency family:
+  // the short tiles exist with quads only)
+  if (plan.kernel != LIN_PANEL64 || tune_of(tuning).gemm_variant >= 6) {
+    LinearArgs gq = g;
+    gq.moment_quads = quads;
+    const LinearPlan pq = plan_linear(dtype, gq);
+    if (plan.kernel != LIN_PANEL64 || pq.big()) { g = gq; plan = pq; }
   }
   D3PM_REQUIRE(plan.big() || plan.kernel == LIN_128_GLDS || plan.kernel == LIN_PANEL64, D3PM_E_SHAPE,
                "d3pm_op_linear_live: %d x %d x %d takes a kernel without a device-side row count", M, N, K);
@@ -1041,6 +1054,7 @@ static int sample_loop_impl(const d3pm_shape* sh, const d3pm_weights* w, int bat
     if (cx.prof) cx.prof->sample_now = (t % cx.prof->stride) == 0;
     q.m_est = plan.m_est(sched, t);
     q.seg_est = plan.seg_est(sched, t);
+    q.rows_est = plan.rows_est(sched, t);
     D3PM_TRY(denoiser_blocks(q, x, t, film, sh->n_layers, flags, s, o.f8, q.m_est ? FOLD_PARTS : plan.fold, prepared, qkv_ready));
     D3PM_TRY(final_logits(*sh, *w, eval_batch, ws, ws.logits, logits_ld(*sh), flags, s, q.dd ? q.dd->m_live : nullptr));
     SampleArgs a = sample_args(*sh, batch, ws.logits, sh->dtype, logits_ld(*sh), x, x, cm.known, t, sched, seed, utt0, flags, o.nucleus, guide);

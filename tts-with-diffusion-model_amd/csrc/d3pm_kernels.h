@@ -49,6 +49,11 @@ struct LinearArgs {
   // gemm_mfma_panel64 for min(M, m_est) rows.  It only chooses speed: the kernel walks every live tile whatever the grid.  Without
   // an estimate a launch plans for the capacity, as it did before the field existed.
   int m_est = 0;
+  // a second host-side estimate of *m_live for the launches that stay on big tiles (d3pm_plan.h plan_distinct_rows; set on the
+  // projections onto the residual stream), 0 = none: where the capacity takes 192 x 128 tiles, big_tile gives a producer with quads
+  // the 96- or 128-row tile while the tiles of rows_est rows fit two per CU in one round.  Speed only, as m_est: the kernel walks every live tile
+  // of whichever geometry, and all of them give the same bits.
+  int rows_est = 0;
 };
 // which LayerNorm-fold combinations the MFMA epilogues instantiate: LNF [+ GELU] without residual / mask; STATS with R1, R1 + R2, R1 + mask
 inline bool fold_args_ok(const LinearArgs& a) {

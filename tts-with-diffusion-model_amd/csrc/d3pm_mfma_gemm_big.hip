@@ -77,14 +77,17 @@ template <typename T> struct RowPanelArgs {
 };
 constexpr int FUSE_DUAL = 1, FUSE_LN = 2, FUSE_LN2 = 4, FUSE_FILM = 8, FUSE_MX = 32;
 
-template <typename T, int EPI, int WM, int WN, int FUSE = 0>
+// MT: 16-row blocks per wave.  6 everywhere but on the short tiles of the deduplicated loop's producers (3 / 4 with 2 x 2 waves: 96 x 128
+// and 128 x 128 tiles, d3pm_plan.cpp big_tile); whatever carries an MT below was a 6, or a 12 = 2 x 6, before them.
+template <typename T, int EPI, int WM, int WN, int FUSE = 0, int MT = 6>
 __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __restrict__ X, int ldx, const T* __restrict__ W,
                                                         const T* __restrict__ bias, T* Y, int ldy, const T* R1,
                                                         const T* R2, int ldr, const uint8_t* __restrict__ row_mask,
                                                         int mask_period, int M, int N, int K, int n_tiles,
                                                         int tiles_total, RowPanelArgs<T> rp, EpiFold ef,
                                                         const int* __restrict__ m_live = nullptr) {
-  constexpr int NW = WM * WN, TM = 96 * WM, TN = 64 * WN;   // 8 waves: one workgroup per CU; 4 waves: two
+  constexpr int NW = WM * WN, WR = 16 * MT, TM = WR * WM, TN = 64 * WN;   // 8 waves: one workgroup per CU; 4 waves: two
+  static_assert(MT == 6 || ((MT == 3 || MT == 4) && WM == 2 && WN == 2 && (FUSE == 0 || FUSE == 1)), "short tiles: 2 x 2 waves, plain or dual");
   // live row count from device memory (LinearArgs::m_live): the tiles that hold a row below it, walked over the XCD ranges of THAT total
   // (never more than the plan's: M is the capacity of every operand)
   if (m_live) tiles_total = min(((*m_live + TM - 1) / TM) * n_tiles, tiles_total);
@@ -93,7 +96,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
   constexpr int NDMA = XPW + WPW;                      // 7 (192 x 256), 10 (96 x 512: waves 4..7 repeat an X piece), 10 (192 x 128)
   static_assert(NW % 2 == 0 && WD % NW == 0 && (XD % NW == 0 || (XD % NW) % 2 == 0), "piece distribution keeps the parity of the wave");
   constexpr int X_BYTES = TM * ROW_BYTES, STAGE = (TM + TN) * ROW_BYTES;
-  static_assert(NDMA <= 12, "one DMA piece per group of four MFMAs");
+  static_assert(NDMA <= 4 * MT, "one DMA piece per group of four MFMAs (MT = 3: seven pieces for six groups, the first group issues two)");
   // EPI_LNF (K = 512: the launcher): the row moments a lane needs for its six row blocks are 24 x 8 bytes per tile -- 48 KB per
   // workgroup tile beside its 320 KB of operands, through the same CU <-> L2 path (EPI_QUADS: 6 x 8 bytes, 12 KB) -- and a round trip
   // the epilogue would start with.  Loaded where the epilogue needs them they cost qkv 36.7 -> 45.1 us and fc1 69.7 -> 84.8 us in the loop; requested at
@@ -107,8 +110,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
   constexpr bool kQuads = (EPI & EPI_QUADS) != 0;
   static_assert(!kQuads || ((EPI & (EPI_LNF | EPI_STATS)) != 0 && WN % 2 == 0), "a quad = the 128 columns of two neighbouring waves");
   constexpr int MPR = kQuads ? 1 : 4;                   // moment loads per row block and lane: one quad, or parts 4 g .. 4 g + 3
-  constexpr int NMOM = 6 * MPR;                         // the moment loads of a tile: what the epilogue's counted wait leaves in flight
-  static_assert(NMOM == (kQuads ? 6 : 24) && NMOM < 64, "vmcnt operand");
+  constexpr int NMOM = MT * MPR;                        // the moment loads of a tile: what the epilogue's counted wait leaves in flight
+  static_assert(NMOM == (kQuads ? MT : 4 * MT) && NMOM < 64, "vmcnt operand");
   constexpr bool kDual = (FUSE & FUSE_DUAL) != 0, kLn = (FUSE & FUSE_LN) != 0, kLn2 = (FUSE & FUSE_LN2) != 0, kFilm = (FUSE & FUSE_FILM) != 0;
   constexpr bool kMx = (FUSE & FUSE_MX) != 0;
   static_assert(!kMx || kLn, "the MX output is the LayerNorm output");
@@ -157,7 +160,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
   // retired deferred-store schedule captured, the instantiations keep the instruction streams they were measured with (all but two
   // unfolded bf16 GELU ones, which the epilogue's lost table arm moved) -- without them scalar code of every prologue moves
   // (profiles/round12_experiment_library_retired_same_code.txt).  Drop them only with a new measurement.
-  const char* const fx_base = smem + wm * 96 * ROW_BYTES;
+  const char* const fx_base = smem + wm * WR * ROW_BYTES;
   const char* const fw_base = smem + X_BYTES + wn * 64 * ROW_BYTES;
 
   const int nk = K / BK;                                             // even (checked by the launcher)
@@ -167,14 +170,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
 #pragma unroll
   for (int p = 0; p < NDMA; ++p) dma(p, sx, sw, lds_base);          // first k-step of the first tile
   typedef float float2v __attribute__((ext_vector_type(2)));
-  [[maybe_unused]] float2v lst[6][MPR];                              // EPI_LNF: the moments of the tile about to start, in flight
+  [[maybe_unused]] float2v lst[MT][MPR];                              // EPI_LNF: the moments of the tile about to start, in flight
   auto moments_request = [&](int mrow0) __attribute__((always_inline)) {
     // entries MPR g .. MPR g + MPR - 1 of row (lane & 15) of each of the six 16-row blocks: [row block][entry][row][2] (stats_index,
     // 16 parts or 4 quads per row; one entry of a row block = one 128-byte line), NMOM loads
     constexpr int P = 4 * MPR;
-    const float* sp = ef.stats_in + stats_index(static_cast<size_t>(mrow0 + wm * 96 + (lane & 15)), (lane >> 4) * MPR, P);
+    const float* sp = ef.stats_in + stats_index(static_cast<size_t>(mrow0 + wm * WR + (lane & 15)), (lane >> 4) * MPR, P);
 #pragma unroll
-    for (int mt = 0; mt < 6; ++mt) {
+    for (int mt = 0; mt < MT; ++mt) {
       asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(lst[mt][0]) : "v"(sp + mt * P * 32) : "memory");
       if constexpr (MPR == 4) {
         asm volatile("global_load_dwordx2 %0, %1, off offset:128" : "=v"(lst[mt][MPR - 3]) : "v"(sp + mt * P * 32) : "memory");
@@ -184,7 +187,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
     }
   };
   if constexpr (kLnfPre) moments_request((tile / n_tiles) * TM);     // the first tile's: covered by the wait below
-  [[maybe_unused]] RowScalars<6> rows;
+  [[maybe_unused]] RowScalars<MT> rows;
   [[maybe_unused]] bool fresh = true;                                // lst holds moments that have not been reduced yet
   // the first step of a tile waits with vmcnt(12): behind an epilogue the DMA pieces are older than its 12 stores; the very
   // first tile has no stores behind its pieces, so they are waited for here
@@ -198,32 +201,32 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
   // columns.  Waves 2 j and 2 j + 1 own the 128 columns of quad j: the even one adds its two parts from 0.f, hands that over through
   // stage 1 (its last reads were the k-step that has just ended; the next DMA into it is issued behind the next tile's first barrier,
   // after the odd wave has consumed the hand-over), the odd one adds its own two parts and stores the quad
-  [[maybe_unused]] auto quads_out = [&](const float (&z)[12], int m0, int n0) __attribute__((always_inline)) {
-    float* xch = reinterpret_cast<float*>(smem + STAGE) + (wm * (WN / 2) + (wn >> 1)) * 6 * 64 + lane;
-    static_assert(WM * (WN / 2) * 6 * 64 * 4 <= STAGE, "hand-over fits in one stage");
+  [[maybe_unused]] auto quads_out = [&](const float (&z)[2 * MT], int m0, int n0) __attribute__((always_inline)) {
+    float* xch = reinterpret_cast<float*>(smem + STAGE) + (wm * (WN / 2) + (wn >> 1)) * MT * 64 + lane;
+    static_assert(WM * (WN / 2) * MT * 64 * 4 <= STAGE, "hand-over fits in one stage");
     asm volatile("s_barrier" ::: "memory");             // every wave has retired its fragment reads of stage 1
     if ((wn & 1) == 0) {
 #pragma unroll
-      for (int mt = 0; mt < 6; ++mt) xch[mt * 64] = (0.f + z[mt * 2]) + z[mt * 2 + 1];
+      for (int mt = 0; mt < MT; ++mt) xch[mt * 64] = (0.f + z[mt * 2]) + z[mt * 2 + 1];
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the hand-over is in LDS
     if ((wn & 1) != 0) {
       const int g = lane >> 4;
 #pragma unroll
-      for (int mt = 0; mt < 6; ++mt) {
+      for (int mt = 0; mt < MT; ++mt) {
         const float qv = (xch[mt * 64] + z[mt * 2]) + z[mt * 2 + 1];
-        if (g < 2) ef.stats_out[stats_index(static_cast<size_t>(m0 + wm * 96 + mt * 16 + (lane & 15)), (n0 + wn * 64) >> 7, N >> 7) + g] = qv;
+        if (g < 2) ef.stats_out[stats_index(static_cast<size_t>(m0 + wm * WR + mt * 16 + (lane & 15)), (n0 + wn * 64) >> 7, N >> 7) + g] = qv;
       }
     }
   };
   for (;;) {
-    floatx4 acc[4][6];
+    floatx4 acc[4][MT];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-      for (int b = 0; b < 6; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
+      for (int b = 0; b < MT; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
     const int m0 = (tile / n_tiles) * TM, n0 = (tile % n_tiles) * TN;
-    [[maybe_unused]] EpiPre<T, 4, 6> pre;
+    [[maybe_unused]] EpiPre<T, 4, MT> pre;
     // what follows this tile (block-uniform); the last tile re-reads its own first k-step: valid memory, never used
     const int t_next = t + t_step;
     const bool more = t_next < t_end;
@@ -247,21 +250,33 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
         // issue order of the 20 fragment reads of a k-step: W0..3 X0 X1 | g0: X2 | g1: X3 | g2: X4 W'0 | g3: X5 W'1 | g4: X6 W'2 |
         // g5: X7 W'3 | g6: X8 | g7: X9 | g8: X10 | g9: X11 (X six row blocks per k-half, W' = the second k-half's W fragments);
         // group g consumes X_g (and W at g = 0, W' at g = 6): the counts below are the reads younger than what it needs
-        const uint32_t ax0 = lds_base + S * STAGE + wm * 96 * ROW_BYTES + fo0, ax1 = ax0 - fo0 + fo1;
+        // MT = 4 (eight groups): W0..3 X0 X1 | g0: X2 W'0 | g1: X3 W'1 | g2: X4 W'2 | g3: X5 W'3 | g4: X6 | g5: X7.
+        // MT = 3 (six groups):   W0..3 X0 X1 | g0: X2 W'0 W'1 | g1: X3 W'2 | g2: X4 W'3 | g3: X5: the same rule -- X two groups ahead
+        // through a ring of three registers, W' spread over the groups of the first k-half -- with its own counts.
+        const uint32_t ax0 = lds_base + S * STAGE + wm * WR * ROW_BYTES + fo0, ax1 = ax0 - fo0 + fo1;
         const uint32_t aw0 = lds_base + S * STAGE + X_BYTES + wn * 64 * ROW_BYTES + fo0, aw1 = aw0 - fo0 + fo1;
         uintx4 fw0[4], fw1[4], fx[3];
         static_for<4>([&](auto NT) { lds_read16(fw0[NT.value], aw0, NT.value * 16 * ROW_BYTES); });
         lds_read16(fx[0], ax0, 0);
         lds_read16(fx[1], ax0, 16 * ROW_BYTES);
-        static_for<12>([&](auto G) {
-          constexpr int g = G.value, ks = g / 6, mt = g % 6;
-          if constexpr (g + 2 < 12) lds_read16(fx[(g + 2) % 3], (g + 2) / 6 ? ax1 : ax0, ((g + 2) % 6) * 16 * ROW_BYTES);
-          if constexpr (ks == 0 && mt >= 2) lds_read16(fw1[mt - 2], aw1, (mt - 2) * 16 * ROW_BYTES);
+        static_for<2 * MT>([&](auto G) {
+          constexpr int g = G.value, ks = g / MT, mt = g % MT;
+          if constexpr (g + 2 < 2 * MT) lds_read16(fx[(g + 2) % 3], (g + 2) / MT ? ax1 : ax0, ((g + 2) % MT) * 16 * ROW_BYTES);
+          if constexpr (MT == 6) {
+            if constexpr (ks == 0 && mt >= 2) lds_read16(fw1[mt - 2], aw1, (mt - 2) * 16 * ROW_BYTES);
+          } else if constexpr (MT == 4) {
+            if constexpr (ks == 0) lds_read16(fw1[mt], aw1, mt * 16 * ROW_BYTES);
+          } else {
+            if constexpr (g == 0) lds_read16(fw1[0], aw1, 0);
+            if constexpr (ks == 0) lds_read16(fw1[mt + 1], aw1, (mt + 1) * 16 * ROW_BYTES);
+          }
           if constexpr (g < NDMA) dma(g, px, pw, nxt);
-          constexpr int kWait[12] = {2, 2, 3, 4, 5, 5, 1, 2, 2, 2, 1, 0};
-          if constexpr (g == 0) lds_wait<kWait[g]>(fw0[0], fw0[1], fw0[2], fw0[3], fx[0]);
-          else if constexpr (g == 6) lds_wait<kWait[g]>(fw1[0], fw1[1], fw1[2], fw1[3], fx[g % 3]);
-          else lds_wait<kWait[g]>(fx[g % 3]);
+          if constexpr (2 * MT + g < NDMA) dma(2 * MT + g, px, pw, nxt);
+          constexpr int kWait6[12] = {2, 2, 3, 4, 5, 5, 1, 2, 2, 2, 1, 0}, kWait4[12] = {3, 4, 5, 5, 1, 2, 1, 0}, kWait3[12] = {4, 5, 6, 1, 1, 0};
+          constexpr int kWait = MT == 6 ? kWait6[g] : MT == 4 ? kWait4[g] : kWait3[g];
+          if constexpr (g == 0) lds_wait<kWait>(fw0[0], fw0[1], fw0[2], fw0[3], fx[0]);
+          else if constexpr (g == MT) lds_wait<kWait>(fw1[0], fw1[1], fw1[2], fw1[3], fx[g % 3]);
+          else lds_wait<kWait>(fx[g % 3]);
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) acc[nt][mt] = mma<T>(__builtin_bit_cast(uint4, ks ? fw1[nt] : fw0[nt]), __builtin_bit_cast(uint4, fx[g % 3]), acc[nt][mt]);
           if constexpr (WAITN < 0 && g < 0) { if (pending) *reinterpret_cast<uintx4*>(pend_y + ldy) = pend[g]; }      // pin: never instantiated
@@ -272,7 +287,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
 
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
-    uintx4 h1p[kDual ? 12 : 1];
+    uintx4 h1p[kDual ? 2 * MT : 1];
     // the nk k-steps of one product: operand rows `ax`, weights `sw`; (nx, nw) = the first k-step of whatever follows
     auto run_k = [&](const T* ax, const T* nx, const T* nw, auto FIRSTW) __attribute__((always_inline)) {
       step(I0{}, FIRSTW, ax + BK, sw + BK);
@@ -281,7 +296,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
         // those stores, have landed (the "+v" operands keep every use behind that wait)
         if (fresh)
 #pragma unroll
-        for (int mt = 0; mt < 6; ++mt) {
+        for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
           for (int i = 0; i < MPR; ++i) asm volatile("" : "+v"(lst[mt][i]));
           float a = 0.f, q = 0.f;                        // fold_row_moments' order: a quad is these four adds done by the producer
@@ -306,31 +321,31 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
 #pragma unroll 1
       for (int ph = 0; ph < 2; ++ph) {
         const bool mid = ph == 0;
-        run_k(ax, mid ? sx2 : sx_next, mid ? sw : sw_next, std::integral_constant<int, 12>{});
+        run_k(ax, mid ? sx2 : sx_next, mid ? sw : sw_next, std::integral_constant<int, 2 * MT>{});
         if (mid) {
-          epilogue_store<T, 0, 4, 6, true, true>(acc, bias, Y, ldy, nullptr, nullptr, ldr, nullptr, 1, M, N, m0 + wm * 96, n0 + wn * 64, lane, h1p);
+          epilogue_store<T, 0, 4, MT, true, true>(acc, bias, Y, ldy, nullptr, nullptr, ldr, nullptr, 1, M, N, m0 + wm * WR, n0 + wn * 64, lane, h1p);
 #pragma unroll
           for (int a = 0; a < 4; ++a)
 #pragma unroll
-            for (int b = 0; b < 6; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
+            for (int b = 0; b < MT; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // nothing but the bias loads follows these DMA pieces: wait for all
           ax = sx2;
         }
       }
     } else {
-      run_k(sx, sx_next, sw_next, std::integral_constant<int, 12>{});
+      run_k(sx, sx_next, sw_next, std::integral_constant<int, 2 * MT>{});
     }
     if constexpr (FUSE != 0) {
-      uintx4 xp[12];
+      uintx4 xp[2 * MT];
       if constexpr (kDual) {
         // x' = rn(rn(R1 + h) + rn(X2 W^T + b)): the R1 + R2 epilogue of the two-launch form with R2 = h taken from registers
-        epilogue_store<T, 0, 4, 6, true, true>(acc, bias, Y, ldy, nullptr, nullptr, ldr, nullptr, 1, M, N, m0 + wm * 96, n0 + wn * 64, lane, xp);
-        const T* r1row = R1 + static_cast<size_t>(m0 + wm * 96 + (lane & 15)) * ldr + n0 + wn * 64 + epilogue_nq(lane);
-        Pack8<T> r1p[12];
+        epilogue_store<T, 0, 4, MT, true, true>(acc, bias, Y, ldy, nullptr, nullptr, ldr, nullptr, 1, M, N, m0 + wm * WR, n0 + wn * 64, lane, xp);
+        const T* r1row = R1 + static_cast<size_t>(m0 + wm * WR + (lane & 15)) * ldr + n0 + wn * 64 + epilogue_nq(lane);
+        Pack8<T> r1p[2 * MT];
 #pragma unroll
-        for (int j = 0; j < 12; ++j) r1p[j] = *reinterpret_cast<const Pack8<T>*>(r1row + static_cast<size_t>((j / 2) * 16) * ldr + (j % 2) * 32);
+        for (int j = 0; j < 2 * MT; ++j) r1p[j] = *reinterpret_cast<const Pack8<T>*>(r1row + static_cast<size_t>((j / 2) * 16) * ldr + (j % 2) * 32);
 #pragma unroll
-        for (int j = 0; j < 12; ++j) {
+        for (int j = 0; j < 2 * MT; ++j) {
           const Pack8<T> hh = __builtin_bit_cast(Pack8<T>, h1p[j]), yy = __builtin_bit_cast(Pack8<T>, xp[j]);
           Pack8<T> o;
 #pragma unroll
@@ -339,31 +354,32 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
           xp[j] = __builtin_bit_cast(uintx4, o);
         }
       } else {
-        epilogue_store<T, EPI, 4, 6, true, true>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0, n0 + wn * 64, lane, xp);
+        epilogue_store<T, EPI, 4, MT, true, true>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0, n0 + wn * 64, lane, xp);
       }
       // ---- the finished rows: store x', then LayerNorm them in place (layernorm_vec's arithmetic, bit for bit)
       const int g = lane >> 4, nq = epilogue_nq(lane);
-      T* yrow = Y + static_cast<size_t>(m0 + wm * 96 + (lane & 15)) * ldy + n0 + wn * 64 + nq;
+      T* yrow = Y + static_cast<size_t>(m0 + wm * WR + (lane & 15)) * ldy + n0 + wn * 64 + nq;
 #pragma unroll
-      for (int j = 0; j < 12; ++j) {
+      for (int j = 0; j < 2 * MT; ++j) {
         T* yp = yrow + static_cast<size_t>((j / 2) * 16) * ldy + (j % 2) * 32;
         if constexpr (FUSE == FUSE_DUAL) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(yp), "v"(xp[j]) : "memory");   // as the plain epilogue (kNts)
         else *reinterpret_cast<uintx4*>(yp) = xp[j];
       }
       if constexpr ((EPI & EPI_STATS) != 0) {        // the row moments of the new rows for the folded LayerNorm that reads them next
-        [[maybe_unused]] float z[12];
+        [[maybe_unused]] float z[2 * MT];
 #pragma unroll
-        for (int j = 0; j < 12; ++j) {
+        for (int j = 0; j < 2 * MT; ++j) {
           const Pack8<T> p = __builtin_bit_cast(Pack8<T>, xp[j]);
           float v[8];
 #pragma unroll
           for (int i = 0; i < 8; ++i) v[i] = static_cast<float>(p.v[i]);
           if constexpr (kQuads) z[j] = part_stats_reduce(v);
-          else part_stats_store(v, ef.stats_out, static_cast<size_t>(m0 + wm * 96 + (j / 2) * 16 + (lane & 15)), N, n0 + wn * 64 + (j % 2) * 32, g, true);
+          else part_stats_store(v, ef.stats_out, static_cast<size_t>(m0 + wm * WR + (j / 2) * 16 + (lane & 15)), N, n0 + wn * 64 + (j % 2) * 32, g, true);
         }
         if constexpr (kQuads) quads_out(z, m0, n0);
       }
       if constexpr (kLn) {
+        static_assert(!kLn || MT == 6, "row-panel LayerNorm: 96 x 512 tiles");
         float* red = reinterpret_cast<float*>(smem + 2 * STAGE);              // [2][96 rows][8 waves] partial sums
         auto unpack = [&](int j, float (&v)[8]) __attribute__((always_inline)) {
           const Pack8<T> p = __builtin_bit_cast(Pack8<T>, xp[j]);
@@ -518,14 +534,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_mfma_big(const T* __rest
 #pragma unroll
           for (int r = 0; r < 4; ++r) { pre.bv[nt][r] = bq[nt][r]; pre.sv[nt][r] = sq[nt][r]; }
         }
-        epilogue_store<T, EPI, 4, 6, true, false, true, true>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 96,
+        epilogue_store<T, EPI, 4, MT, true, false, true, true>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * WR,
                                                               n0 + wn * 64, lane, nullptr, &pre, &ef, &rows);
       } else {
         // output rows leave as `sc1` stores (kNts): they are not read again by this launch, and left in the XCD's L2 they displace the
         // operand panels the other tiles of the launch still stream (in the loop: 103.8 k -> 106.2 k tokens/s with the stand-alone
         // LayerNorms, 104.5 k -> 110.5 k with them folded; `nt`, which keeps the line in L2, was tried and lost)
-        [[maybe_unused]] float z[12];
-        epilogue_store<T, EPI, 4, 6, true, false, true>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * 96,
+        [[maybe_unused]] float z[2 * MT];
+        epilogue_store<T, EPI, 4, MT, true, false, true>(acc, bias, Y, ldy, R1, R2, ldr, row_mask, mask_period, M, N, m0 + wm * WR,
                                                           n0 + wn * 64, lane, nullptr, &pre, &ef, nullptr, z);
         if constexpr (kQuads && (EPI & EPI_STATS) != 0) quads_out(z, m0, n0);
       }
@@ -543,12 +559,13 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 
 
 }  // namespace
 
-// Which shapes take which geometry (1 = 96 x 512, 1 x 8 waves; 2 = 192 x 256, 2 x 4; 3 = 192 x 128, 2 x 2, two workgroups per CU),
-// with which grid and LDS: d3pm_plan.cpp (big_tile, big_plan).  The launchers below instantiate what a plan names.
-template <typename U, int E, int WM, int WN>
+// Which shapes take which geometry (1 = 96 x 512, 1 x 8 waves; 2 = 192 x 256, 2 x 4; 3 = 192 x 128, 2 x 2, two workgroups per CU;
+// 4 = 96 x 128 and 5 = 128 x 128, 2 x 2 waves of three / four row blocks), with which grid and LDS: d3pm_plan.cpp (big_tile, big_plan).
+// The launchers below instantiate what a plan names.
+template <typename U, int E, int WM, int WN, int MT = 6>
 static int big_launch(const LinearArgs& a, const LinearPlan& p, hipStream_t s) {
-  D3PM_LDS_ATTR((&gemm_mfma_big<U, E, WM, WN>), 160 * 1024);
-  gemm_mfma_big<U, E, WM, WN><<<dim3(p.grid), dim3(WM * WN * 64), p.lds, s>>>(
+  D3PM_LDS_ATTR((&gemm_mfma_big<U, E, WM, WN, 0, MT>), 160 * 1024);
+  gemm_mfma_big<U, E, WM, WN, 0, MT><<<dim3(p.grid), dim3(WM * WN * 64), p.lds, s>>>(
       static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
       static_cast<const U*>(a.R1), static_cast<const U*>(a.R2), a.ldr, a.row_mask, a.mask_period, a.M, a.N, a.K, p.n_tiles,
       p.tiles_total, RowPanelArgs<U>{}, epi_fold_of(a), a.m_live);
@@ -560,18 +577,24 @@ template <typename U, int E>
 static int big_launch_geometry(const LinearArgs& a, const LinearPlan& p, hipStream_t s) {
   if (p.geom == 1) return big_launch<U, E, 1, 8>(a, p, s);
   if (p.geom == 2) return big_launch<U, E, 2, 4>(a, p, s);
+  // the short tiles: the producers of the deduplicated loop and nothing else (d3pm_plan.cpp short_tile_epilogue)
+  if constexpr (E == (EPI_R1 | EPI_STATS | EPI_QUADS) || E == (EPI_R1 | EPI_MASK | EPI_STATS | EPI_QUADS)) {
+    if (p.geom == 4) return big_launch<U, E, 2, 2, 3>(a, p, s);
+    if (p.geom == 5) return big_launch<U, E, 2, 2, 4>(a, p, s);
+  }
+  if (p.geom != 3) return D3PM_E_SHAPE;
   return big_launch<U, E, 2, 2>(a, p, s);
 }
 
 // Both cross-attention out-projections (ar_discrete.py:138,142: the SAME weights) in one launch of the ordinary big-tile geometry:
 // a second product through the tile, the first result kept packed in 48 registers, x' = rn(rn(R1 + rn(X W^T + b)) + rn(X2 W^T + b))
 // -- the bits of the two launches it replaces -- and, with stats_out, the row moments of x' for the folded norm3 of fc1.
-template <typename U, int E, int WM, int WN>
+template <typename U, int E, int WM, int WN, int MT = 6>
 static int big_dual_launch(const LinearArgs& a, const void* X2, const LinearPlan& p, hipStream_t s) {
-  D3PM_LDS_ATTR((&gemm_mfma_big<U, E, WM, WN, FUSE_DUAL>), 160 * 1024);
+  D3PM_LDS_ATTR((&gemm_mfma_big<U, E, WM, WN, FUSE_DUAL, MT>), 160 * 1024);
   RowPanelArgs<U> rp{};
   rp.X2 = static_cast<const U*>(X2);
-  gemm_mfma_big<U, E, WM, WN, FUSE_DUAL><<<dim3(p.grid), dim3(WM * WN * 64), p.lds, s>>>(
+  gemm_mfma_big<U, E, WM, WN, FUSE_DUAL, MT><<<dim3(p.grid), dim3(WM * WN * 64), p.lds, s>>>(
       static_cast<const U*>(a.X), a.ldx, static_cast<const U*>(a.W), static_cast<const U*>(a.bias), static_cast<U*>(a.Y), a.ldy,
       static_cast<const U*>(a.R1), nullptr, a.ldr, nullptr, 1, a.M, a.N, a.K, p.n_tiles, p.tiles_total, rp, epi_fold_of(a), a.m_live);
   D3PM_LAUNCH_CHECK();
@@ -581,8 +604,11 @@ static int big_dual_launch(const LinearArgs& a, const void* X2, const LinearPlan
 int big_dual(int dtype, const LinearArgs& a, const void* X2, const LinearPlan& p, hipStream_t s) {
   auto go = [&](auto* tag) -> int {
     using U = std::remove_pointer_t<decltype(tag)>;
-    switch (p.epi) {      // kEpiBigDual (d3pm_plan.cpp); geometry 2 or 3
+    if (p.geom < 2 || p.geom > 5 || (p.geom > 3 && p.epi != (EPI_R2 | EPI_STATS | EPI_QUADS))) return D3PM_E_SHAPE;
+    switch (p.epi) {      // kEpiBigDual (d3pm_plan.cpp); geometry 2 or 3, with quads also the short tiles 4 and 5
       case EPI_R2 | EPI_STATS | EPI_QUADS:
+        if (p.geom == 4) return big_dual_launch<U, EPI_R2 | EPI_STATS | EPI_QUADS, 2, 2, 3>(a, X2, p, s);
+        if (p.geom == 5) return big_dual_launch<U, EPI_R2 | EPI_STATS | EPI_QUADS, 2, 2, 4>(a, X2, p, s);
         return p.geom == 2 ? big_dual_launch<U, EPI_R2 | EPI_STATS | EPI_QUADS, 2, 4>(a, X2, p, s)
                            : big_dual_launch<U, EPI_R2 | EPI_STATS | EPI_QUADS, 2, 2>(a, X2, p, s);
       case EPI_R2 | EPI_STATS:

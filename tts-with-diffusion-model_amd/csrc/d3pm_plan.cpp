@@ -43,29 +43,28 @@ bool k128_ok(int dtype, const LinearArgs& a) {
 }
 
 // ---- big tiles (d3pm_mfma_gemm_big.hip) ----
-// Tile geometries: id 1 = 96 x 512 (1 x 8 waves), 2 = 192 x 256 (2 x 4 waves), 3 = 192 x 128 (2 x 2 waves, two workgroups per CU)
+// Tile geometries: id 1 = 96 x 512 (1 x 8 waves), 2 = 192 x 256 (2 x 4 waves), 3 = 192 x 128 (2 x 2 waves, two workgroups per CU);
+// the short tiles of the deduplicated loop's producers: 4 = 96 x 128, 5 = 128 x 128 (2 x 2 waves of three / four 16-row blocks)
 void big_geometry(int id, int& tm, int& tn, int& waves) {
-  tm = id == 1 ? 96 : 192;
+  tm = id == 1 || id == 4 ? 96 : id == 5 ? 128 : 192;
   tn = id == 1 ? 512 : id == 2 ? 256 : 128;
-  waves = id == 3 ? 4 : 8;
+  waves = id >= 3 ? 4 : 8;
 }
 
-// 0 = not applicable, else the geometry id.  `want` (tuning knob): 0 auto, 1 / 2 / 3 forced.
-int big_tile(int dtype, const LinearArgs& a, int want) {
-  if (!is16(dtype)) return 0;
-  if (a.K < 4 * BK || a.K % (2 * BK) != 0 || a.M < 96 || a.N < 128) return 0;
-  if (!operands_ok(a)) return 0;
-  if (!fold_args_ok(a) || (a.fold_s && a.K != 512)) return 0;      // the big tile prefetches the 16 moment parts of a 512-wide row
-  if (!epi_ok(kEpiBig, a)) return 0;
-  if (a.ldx >= (1 << 24) || a.K >= (1 << 24)) return 0;       // 32-bit per-lane DMA offsets
-  auto fits = [&](int id, bool forced) {
+// The short tiles are instantiated for what the loop launches on them and nothing else: the projections onto the residual stream with
+// quads -- R1 [+ mask] + moments, and the dual out-projection, whose first launch argument looks the same (plan_cross_out)
+bool short_tile_epilogue(const LinearArgs& a) {
+  return a.stats_out && a.moment_quads && a.R1 && !a.R2 && a.act == ACT_NONE && !a.fold_s;
+}
+
+// today's automatic choice among the geometries 1 .. 3 for the capacity a.M (0: none)
+int big_tile_capacity(const LinearArgs& a) {
+  auto fits = [&](int id) {
     int tm, tn, waves;
     big_geometry(id, tm, tn, waves);
     if (a.M % tm != 0 || a.N % tn != 0) return false;
-    if (forced) return true;                                        // tuning knob / kernel tests: any shape of whole tiles
     return fills_rounds(static_cast<long long>(a.M / tm) * (a.N / tn), kCUs * (8 / waves));   // >= 85 % of the slot-rounds do work
   };
-  if (want >= 1 && want <= 3) return fits(want, true) ? want : 0;
   // Under the GELU epilogue 192 x 128 tiles win clearly: its VALU work only overlaps with MFMAs when a second workgroup shares the
   // CU (two 4-wave workgroups per CU).  For the other K = 512 projections the microbenchmark cannot tell 192 x 128 from 192 x 256
   // (qkv 43.3 vs 44.5 us, merged q 30.5 vs 31.4: profiles/round3_v_ab_gemm_geometries.txt) but the sampler's loop can, where the
@@ -74,9 +73,9 @@ int big_tile(int dtype, const LinearArgs& a, int want) {
   // gemm_variant=8, profiles/round3_v_ab_tune_geom.txt)
   // -- and fc2 (K = 2048) likewise: with 192 x 128 for the K = 512 projections only the class is at 1294 us, with fc2 too at 1249
   // (profiles/round3_w_ab_tune_geom.txt).  So: two 4-wave workgroups per CU wherever that geometry fills its rounds.
-  if (fits(3, false)) return 3;
-  if (fits(2, false)) return 2;
-  if (fits(1, false)) return 1;
+  if (fits(3)) return 3;
+  if (fits(2)) return 2;
+  if (fits(1)) return 1;
   // Mid-size batches (the VCTK config: 32 x 384 rows; 8 .. 16 utterances of the libritts shape) leave the chip partly idle with
   // every big tile, yet 192 x 128 tiles of four waves still beat the 128 x 128 kernels there once at least half (long K) or all
   // of the CUs get one: measured at M = 12288 / 6144 (tests/ab_gemm_shapes.py, profiles/round3_f_ab_gemm_shapes.txt): qkv 24.1 vs
@@ -86,6 +85,42 @@ int big_tile(int dtype, const LinearArgs& a, int want) {
     if (tiles >= (a.K >= 1024 ? kCUs / 2 : kCUs)) return 3;
   }
   return 0;
+}
+
+// 0 = not applicable, else the geometry id.  `want` (tuning knob): 0 auto, 1 .. 5 forced (4 / 5 where they are instantiated, else auto).
+int big_tile(int dtype, const LinearArgs& a, int want) {
+  if (!is16(dtype)) return 0;
+  if (a.K < 4 * BK || a.K % (2 * BK) != 0 || a.M < 96 || a.N < 128) return 0;
+  if (!operands_ok(a)) return 0;
+  if (!fold_args_ok(a) || (a.fold_s && a.K != 512)) return 0;      // the big tile prefetches the 16 moment parts of a 512-wide row
+  if (!epi_ok(kEpiBig, a)) return 0;
+  if (a.ldx >= (1 << 24) || a.K >= (1 << 24)) return 0;       // 32-bit per-lane DMA offsets
+  auto whole = [&](int id) {                                   // tuning knob / kernel tests: any shape of whole tiles
+    int tm, tn, waves;
+    big_geometry(id, tm, tn, waves);
+    return a.M % tm == 0 && a.N % tn == 0;
+  };
+  if (want >= 1 && want <= 3) return whole(want) ? want : 0;
+  if ((want == 4 || want == 5) && short_tile_epilogue(a) && whole(want)) return want;
+  const int id = big_tile_capacity(a);
+  // A producer of the deduplicated loop with an estimate of its live rows below the capacity (LinearArgs::rows_est): the kernel walks
+  // the live tiles alone, so what counts is how THEY lie on the chip.  A shorter tile spreads the same rows over more workgroups, each
+  // of which stages (96 | 128) + 128 operand rows per k-step instead of 320 through its CU's L2 -> LDS path.  Measured along the
+  // 32 x 750-frame loop with each tile forced in every iteration (profiles/round26_live_tiles_ab_interleaved.txt), fc2 / dual / self
+  // out-projection in us per launch: at t = 73 (3 180 live rows) 192 x 128 takes 32.7 / 21.0 / 15.3, 128 x 128 27.3 / 17.1 / 12.1,
+  // 96 x 128 25.0 / 15.4 / 10.8; at t = 35 (about 11 500) 36.4 / 22.8 / 15.9, 34.8 / 22.7 / 14.5 and 34.3 / 19.8 / 13.1; at t = 1
+  // (14 997) 42.7 / 28.7 / 18.2, 39.1 / 24.0 / 15.3 and 55.4 / 31.8 / 19.5.  The 96-row tile wins while its tiles fit the 512 workgroup slots (two
+  // four-wave workgroups per CU) and loses a whole round beyond (12 288 rows at N = 512); the 128-row tile wins from there to its own
+  // last whole round (16 384 rows).  So: the shortest tile whose tiles of the ESTIMATE fit the slots in one round, bounded by
+  // live_short96_rows() / live_short128_rows().  The estimate errs high (plan_distinct_rows), which here costs a few us; erring low
+  // would cost a round.  192 x 256 tiles (one eight-wave workgroup per CU) were measured for the late iterations and lost everywhere.
+  // Correctness never depends on the estimate: every geometry accumulates in the same order.
+  if (id == 3 && want == 0 && a.m_live && a.rows_est > 0 && a.rows_est < a.M && short_tile_epilogue(a)) {
+    const long long n_tiles = a.N / 128, slots = 2 * kCUs;
+    if (a.rows_est <= live_short96_rows() && whole(4) && (a.rows_est + 95) / 96 * n_tiles <= slots) return 4;
+    if (a.rows_est <= live_short128_rows() && whole(5) && (a.rows_est + 127) / 128 * n_tiles <= slots) return 5;
+  }
+  return id;
 }
 
 // a persistent launch of geometry `id` over the whole tiles of M x N: at most one workgroup per slot, a multiple of the 8 XCDs
@@ -142,11 +177,14 @@ LinearPlan panel64_plan(const LinearArgs& a, int geom, int epi, bool dual) {
   return p;
 }
 
-// d3pm_tuning.gemm_variant -> the big-tile geometry it forces (0: the automatic choice).  6 / 7 / 8 = 192 x 256 / 96 x 512 / 192 x 128.
-inline int big_want(int gemm_variant) { return gemm_variant == 6 ? 2 : gemm_variant == 7 ? 1 : gemm_variant == 8 ? 3 : 0; }
+// d3pm_tuning.gemm_variant -> the big-tile geometry it forces (0: the automatic choice).  6 / 7 / 8 = 192 x 256 / 96 x 512 / 192 x 128;
+// 9 / 10 = 96 x 128 / 128 x 128 for the producers they are instantiated for, the automatic choice for everything else.
+inline int big_want(int gemm_variant) {
+  return gemm_variant == 6 ? 2 : gemm_variant == 7 ? 1 : gemm_variant == 8 ? 3 : gemm_variant == 9 ? 4 : gemm_variant == 10 ? 5 : 0;
+}
 // The dual reads 6 and 8 only: 7 (96 x 512) means "auto" to it, because the dual needs geometry >= 2.  Carried over as it was on
 // purpose: whether 7 should rather switch the dual off is a behaviour question of its own.
-inline int big_want_dual(int gemm_variant) { return gemm_variant == 6 ? 2 : gemm_variant == 8 ? 3 : 0; }
+inline int big_want_dual(int gemm_variant) { return gemm_variant == 6 ? 2 : gemm_variant == 8 ? 3 : gemm_variant == 9 ? 4 : gemm_variant == 10 ? 5 : 0; }
 
 }  // namespace
 
@@ -176,7 +214,7 @@ bool epi_listed(const int* table, int epi) {
 // d3pm_tuning.gemm_variant: 0 auto, 2 throughput (128 x 128 persistent over whole tiles), 3 the round-1 latency schedule
 // (128 x 128, two stages), 4 the latency schedule (64 x 64 tiles, whole-K panels), 5 throughput with one 128 x 128 tile per
 // workgroup, 6 / 7 / 8 big tiles (192 x 256 / 96 x 512 / 192 x 128, d3pm_mfma_gemm_big.hip) wherever they apply, else as auto
-// without big tiles.  gemm_persist_slots: resident workgroups of the persistent schedule (4 per CU).
+// without big tiles, 9 / 10 the short tiles (96 x 128 / 128 x 128) for the producers with quads, auto for everything else.  gemm_persist_slots: resident workgroups of the persistent schedule (4 per CU).
 LinearPlan plan_linear(int dtype, const LinearArgs& a, bool force_generic) {
   LinearPlan p;
   if (force_generic || !k128_ok(dtype, a)) return p;
@@ -184,7 +222,7 @@ LinearPlan plan_linear(int dtype, const LinearArgs& a, bool force_generic) {
   const int variant = tn.gemm_variant;
   // below 8 the slot count means the default (deliberate: 0 in a zero-initialised d3pm_tuning); otherwise whole groups of the 8 XCDs
   const int persist_slots = tn.gemm_persist_slots >= 8 ? (tn.gemm_persist_slots & ~7) : 4 * kCUs;
-  const bool autosel = variant == 0 || (variant >= 6 && variant <= 8);
+  const bool autosel = variant == 0 || (variant >= 6 && variant <= 10);
   const int epi = epi_of(a);
   // an iteration of the deduplicated loop with few live rows: the latency family whatever the capacity (moments as parts: the loop
   // chooses the format per iteration, LoopPlan::m_est in d3pm_sequence.h)
@@ -252,6 +290,28 @@ int plan_live_rows(int batch, int canvas, float cbar_t) {
   const long long rows = static_cast<long long>(batch) * per_utt;
   return rows > INT32_MAX ? INT32_MAX : static_cast<int>(rows);
 }
+
+int plan_distinct_rows(int batch, int canvas, int n_classes, float cbar_t) {
+  const double revealed = static_cast<float>(canvas) * (1.0f - cbar_t);      // plan_live_rows' float product, so that ceil never exceeds its
+  const double n = n_classes > 0 ? static_cast<double>(n_classes) : 1.0;
+  const double distinct = revealed > 0.0 ? n * (1.0 - std::exp(-revealed / n)) : 0.0;      // <= revealed
+  long long per_utt = 2 + static_cast<long long>(std::ceil(distinct));
+  if (per_utt > canvas) per_utt = canvas;
+  const long long rows = static_cast<long long>(batch) * per_utt;
+  return rows > INT32_MAX ? INT32_MAX : static_cast<int>(rows);
+}
+
+// The largest estimates that take the 96-row and the 128-row tile (big_tile, where the measurements are).  Compile-time constants
+// like R below so that A/B builds can move them; big_tile also asks that the tiles fit the 512 slots in one round, which at N = 512
+// is the same 12 288 and 16 384 rows.
+#ifndef D3PM_LIVE_SHORT96_ROWS
+#define D3PM_LIVE_SHORT96_ROWS 12288
+#endif
+#ifndef D3PM_LIVE_SHORT128_ROWS
+#define D3PM_LIVE_SHORT128_ROWS 16384
+#endif
+int live_short96_rows() { return D3PM_LIVE_SHORT96_ROWS; }
+int live_short128_rows() { return D3PM_LIVE_SHORT128_ROWS; }
 
 // R, the largest estimate that takes the latency launch list: measured, not derived (profiles/round19_live_regime_ab_interleaved.txt).
 // Interleaved arms of the 32 x 750-frame bf16 loop over library builds that differ in this constant alone (tools/build_variant.py), ms

@@ -33,7 +33,7 @@ constexpr int EPI_QUADS = 256;
 enum LinearKernel { LIN_GENERIC = 0, LIN_QUADS_REFUSED, LIN_BIG, LIN_PANEL64, LIN_128_PF, LIN_128_PERSIST, LIN_128_GLDS };
 struct LinearPlan {
   int kernel = LIN_GENERIC;
-  int geom = 0;                  // LIN_BIG: 1 = 96 x 512, 2 = 192 x 256, 3 = 192 x 128;  LIN_PANEL64: 0 = 64 x 64, 1 = 96 x 64, 2 = 32 x 64
+  int geom = 0;                  // LIN_BIG: 1 = 96 x 512, 2 = 192 x 256, 3 = 192 x 128, 4 = 96 x 128, 5 = 128 x 128;  LIN_PANEL64: 0 = 64 x 64, 1 = 96 x 64, 2 = 32 x 64
   int tm = 0, tn = 0;            // rows x columns of a tile
   int epi = 0;                   // EPI_* bits: an entry of the family's table below
   unsigned grid = 0;
@@ -52,6 +52,15 @@ int plan_live_rows(int batch, int canvas, float cbar_t);
 // on gemm_mfma_panel64, moments as parts); LinearArgs::m_est carries the estimate to plan_linear / plan_cross_out.  0 = no estimate.
 int live_latency_rows();
 inline bool live_latency(int m_est) { return m_est > 0 && m_est <= live_latency_rows(); }
+// The second estimate, for the iterations that stay on big tiles (LinearArgs::rows_est): the DISTINCT classes among the revealed frames.
+// batch * min(canvas, 2 + ceil(n_classes * (1 - exp(-r / n_classes)))) with r = canvas * (1 - cbar_t): r uniform draws from n_classes
+// ids hit that many different ones in expectation, and a uniform draw maximises the count, so a trained model lies below it.  Never
+// above plan_live_rows of the same arguments (n (1 - exp(-r / n)) <= r).  Erring high is the cheap side: a tile sized for more rows.
+int plan_distinct_rows(int batch, int canvas, int n_classes, float cbar_t);
+// the rule of big_tile for a producer with quads and 0 < rows_est < M whose capacity takes 192 x 128 tiles: 96 x 128 tiles up to
+// live_short96_rows() estimated rows, 128 x 128 up to live_short128_rows(), each while its tiles fit the 2 * kCUs slots in one round
+int live_short96_rows();
+int live_short128_rows();
 
 // ---- what d3pm_tuning.ln_fold switches on, by name: nothing outside fold_features compares the field with a number ----
 // fold: the LayerNorms folded into the projections.  On top of it, each a condition among others of loop_plan (d3pm_sequence.h):
@@ -75,7 +84,7 @@ inline bool fills_rounds(long long tiles, long long slots) {
 enum { CROSS_OUT_TWO_LAUNCHES = 0, CROSS_OUT_PANEL64_DUAL, CROSS_OUT_BIG_DUAL };
 struct CrossOutPlan {
   int form = CROSS_OUT_TWO_LAUNCHES;
-  LinearPlan dual;               // the one launch of the two dual forms: LIN_PANEL64 (32 x 64) or LIN_BIG (geometry 2 or 3)
+  LinearPlan dual;               // the one launch of the two dual forms: LIN_PANEL64 (32 x 64) or LIN_BIG (geometry 2 .. 5)
 };
 CrossOutPlan plan_cross_out(int dtype, const LinearArgs& g, const void* X2, bool force_generic, bool big_dual_allowed);
 

@@ -116,6 +116,10 @@ LoopPlan loop_plan(const DenoiserArgs& q0, uint32_t flags, const LoopCall& call)
   // projection of a block plans onto gemm_mfma_panel64 for it (the final projection keeps its kernel).  The estimate chooses speed
   // only: every kernel reads the live count from the device.  Known frames are the caller's and cannot be counted here: such a loop
   // keeps the big-tile list.
+  // The iterations that stay on big tiles get an estimate of their own (LoopPlan::rows_est), by the same reasoning and under the same
+  // condition on known frames; it moves the tile geometry of the projections onto the residual stream and nothing else.
+  p.live_tiles = p.dedup && !call.known;
+  p.n_classes = sh.n_classes;
   if (p.dedup && on.latency && !call.known) {
     q.dd = &ws.dd;
     q.m_est = live_latency_rows();

@@ -149,6 +149,9 @@ struct DenoiserArgs {      // what every block of one evaluation sees
   // with dd, per iteration: the rows per utterance the host expects (LoopPlan::seg_est), or 0.  With it the self-attention may pool an
   // utterance's K | V rows in LDS (AttnArgs::seg_est, plan_attention decides)
   int seg_est = 0;
+  // with dd, per iteration that stays on the big-tile list: the distinct rows the host expects (LoopPlan::rows_est), or 0.  The
+  // projections onto the residual stream carry it to big_tile (LinearArgs::rows_est), which sizes their tiles to it
+  int rows_est = 0;
 };
 
 // ---- the block sequence with the LayerNorms folded into the projections (ar_discrete.py:126-161; d3pm_mfma_tile.h EPI_LNF / EPI_STATS)
@@ -180,7 +183,7 @@ int folded_block(const DenoiserArgs& q, int l, bool quads, Visitor& v, bool qkv_
   // a projection onto the residual stream: x += X . W^T + bias (+ R2), then the moments of the new rows
   auto producer = [&](const void* X, int K, const void* W, const void* bias, const void* R2 = nullptr) {
     LinearArgs g = with_moments_out(with_residual(projection(X, W, bias, ws.x, n, d, K), ws.x, R2), ws.stats, quads);
-    g.m_live = m_live; g.m_est = q.m_est;
+    g.m_live = m_live; g.m_est = q.m_est; g.rows_est = q.rows_est;
     return g;
   };
   // ---- self-attention ----
@@ -303,6 +306,14 @@ struct LoopPlan {
   int seg_est(const d3pm_schedule* sched, int t) const {
     if (!latency || t <= t_stop || batch <= 0) return 0;
     return (plan_live_rows(batch, canvas, host_h2f(sched->cbar[t])) + batch - 1) / batch;
+  }
+  // DenoiserArgs::rows_est of iteration t: plan_distinct_rows, for every iteration of the deduplicated loop that does not take the
+  // latency list (with ln_fold = 4 that is all of them), or 0.  Known frames are the caller's and cannot be counted: no estimate then.
+  bool live_tiles = false;
+  int n_classes = 0;
+  int rows_est(const d3pm_schedule* sched, int t) const {
+    if (!live_tiles || t <= t_stop || m_est(sched, t)) return 0;
+    return plan_distinct_rows(batch, canvas, n_classes, host_h2f(sched->cbar[t]));
   }
 };
 LoopPlan loop_plan(const DenoiserArgs& q, uint32_t flags, const LoopCall& call);

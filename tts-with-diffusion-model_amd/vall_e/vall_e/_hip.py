@@ -313,6 +313,9 @@ SIGNATURES = {
     "d3pm_op_linear_live_est": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int, C.POINTER(Tuning), C.c_void_p]),
+    "d3pm_op_linear_live_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int, C.c_int, C.POINTER(Tuning), C.c_void_p]),
     "d3pm_op_embed_qkv_bytes": (C.c_size_t, [C.POINTER(Shape), C.c_int]),
     "d3pm_op_embed_qkv": (C.c_int, [C.POINTER(Shape), C.POINTER(Weights), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1637,15 +1640,18 @@ def op_dedup_index(tokens, frame_mask, n_classes, table=None, seg_align=128):
 
 
 def op_linear_live(x, w, bias, y, m_live, x2=None, r1=None, row_mask=None, act=0, fold_s=None, fold_b=None, stats_in=None, stats_out=None,
-                   m_est=None):
+                   m_est=None, rows_est=None):
     """y [M, N] (written in place: only the tiles that hold a row < m_live[0]) = the projection of d3pm_op_linear_live; M = x.shape[0]
-    is the capacity.  m_est: the host's estimate of m_live (d3pm_op_linear_live_est; 0 = none).  The schedule is the module's TUNING."""
+    is the capacity.  m_est: the host's estimate of m_live (d3pm_op_linear_live_est; 0 = none).  rows_est: the estimate that sizes big
+    tiles (d3pm_op_linear_live_rows; 0 = none).  The schedule is the module's TUNING."""
     M, K = x.shape
     N = w.shape[0]
     args = (dtype_code(x.dtype), _p(x), _p(x2), x.stride(0), _p(w), _p(bias), _p(y), y.stride(0), _p(r1),
             r1.stride(0) if r1 is not None else 0, _p(row_mask), row_mask.numel() if row_mask is not None else 1, M, N, K, act,
             _p(fold_s), _p(fold_b), _p(stats_in), _p(stats_out), _p(m_live))
-    if m_est is None:
+    if rows_est is not None:
+        check(lib().d3pm_op_linear_live_rows(*args, int(m_est or 0), int(rows_est), C.byref(TUNING), stream_ptr()), "d3pm_op_linear_live_rows")
+    elif m_est is None:
         check(lib().d3pm_op_linear_live(*args, C.byref(TUNING), stream_ptr()), "d3pm_op_linear_live")
     else:
         check(lib().d3pm_op_linear_live_est(*args, int(m_est), C.byref(TUNING), stream_ptr()), "d3pm_op_linear_live_est")
@@ -1830,7 +1836,7 @@ def set_workspace_alias(v: bool):
 
 # (ln_fold = 3, the every-row arm of the row deduplication, and 4, its big-tiles-in-every-iteration arm, are A/B values: set_tuning_field /
 # bench.py --tune take them, tuning() does not)
-_TUNING_VALUES = {"gemm_variant": (0, 2, 3, 4, 5, 6, 7, 8), "attn_query_groups": (0, 1, 2, 4, 32, 33), "lat_tile": (0, 1, 2, 3),
+_TUNING_VALUES = {"gemm_variant": (0, 2, 3, 4, 5, 6, 7, 8, 9, 10), "attn_query_groups": (0, 1, 2, 4, 32, 33), "lat_tile": (0, 1, 2, 3),
                   "attn_pair_sequential": (0, 1, 2), "attn_cross_resident": (0, 1, 2, 3, 4, 5), "workspace_alias": (0, 1), "ln_fold": (0, 1, 2)}
 
 
