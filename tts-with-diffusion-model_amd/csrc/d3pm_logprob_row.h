@@ -5,7 +5,8 @@
 //     m = max z,  S = sum_k expf(z_k - m)  (per-lane partial sums in ascending class, the tail last, then wave_sum),
 //     logprob = z_j - m - logf(S)
 // for the id j the caller names (wave-uniform, not the mask id).  No temperature, no top-k, no top-p: for the greedy candidate of
-// d3pm_reveal under the neutral triple this is that row's conf, bit for bit.
+// d3pm_reveal under the neutral triple this is that row's conf, bit for bit.  The NAR draw (d3pm_nar_draw.hip) calls logprob_from_z
+// on a row's own float(logit) with mask_id = -1 (no class is the mask) and no tail.
 #pragma once
 #include <cmath>
 

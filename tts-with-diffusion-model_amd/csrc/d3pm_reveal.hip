@@ -69,19 +69,14 @@ __global__ __launch_bounds__(256) void reveal_candidate_rows(
   }
 }
 
-// fp32 bits -> key whose unsigned order is the order of the values (negative values reverse, the others move above them)
-__device__ __forceinline__ uint32_t f32_order_key(float v) {
-  const uint32_t u = __builtin_bit_cast(uint32_t, v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 struct RevealSel { uint32_t sel, free; };      // per lane, bit i <=> frame lane + 64 i: takes its candidate by this step / is a free row
 
 // The selection of one utterance by one wave.  x / fm / kn / score point at the utterance's `canvas` (<= 1024) entries; kn may be
 // null.  keep_frac = float(cbar[t_next]) (0 on the last step); F free rows, quota = floor((double) F * (double) keep_frac).
 //   !kRevise: the `masked` masked free rows compete, and masked - min(quota, masked) of them are revealed;
 //   kRevise:  all F free rows compete, masked and held alike (x is not read), and F - quota of them hold an id after the step.
-// The selected rows are the ones that come first in the order (score key descending, frame index ascending).  The threshold key is
+// The selected rows are the ones that come first in the order (score key descending -- the fp32 key of d3pm_order_key.h --, frame
+// index ascending).  The threshold key is
 // the largest c with #{key >= c} >= the number to select, built bit by bit from the top as filter_row builds theta: every count is a
 // popcount of a wave-wide compare mask on the scalar unit, wave-uniform by construction.  Ties at the threshold go out in ascending
 // slot, and within a slot by the lane prefix count of the ballot.
@@ -97,7 +92,7 @@ __device__ __forceinline__ RevealSel reveal_select(const int32_t* __restrict__ x
     const bool free_row = f < canvas && fm[f] != 0 && !(kn && kn[f] != 0);
     bool competes = free_row;
     if constexpr (!kRevise) competes = free_row && x[f] == mask_id;
-    key[i] = competes ? f32_order_key(score[f]) : 0u;
+    key[i] = competes ? order_key<float>(score[f]) : 0u;
     r.free |= free_row ? 1u << i : 0u;
     n_free += __popcll(__ballot(free_row));
     if constexpr (!kRevise) n_masked += __popcll(__ballot(competes));

@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "d3pm_kernels.h"
+#include "d3pm_order_key.h"
 
 namespace d3pm {
 namespace {
@@ -17,7 +18,7 @@ constexpr float kEps = 1.0e-6f;        // self.eps (ar_discrete.py:276), added i
 //     z'  = rn16(z / temperature)                         (fp32 division, one rounding)
 //     z'' = z' >= theta ? z' : -inf,  theta = the top_k-th largest z' counted with multiplicity (top_k = 0: no cut)
 // and everything behind the load runs on z'' as it is.  theta is found without LDS and without a sort: every fp16 value maps to a
-// 16-bit key whose unsigned order is the order of the values, and the key of theta is the largest c with
+// 16-bit key whose unsigned order is the order of the values (d3pm_order_key.h), and the key of theta is the largest c with
 // #{key >= c} >= top_k, built bit by bit from the top.  One round counts each of the lane's values with one vector compare
 // whose wave-wide mask is popcounted on the scalar unit, so the count is wave-uniform by construction: no shuffle, no barrier,
 // no divergence.  The final cut compares VALUES (z' >= theta), so that -0 and +0 (two keys, one value) are kept or cut together.
@@ -26,37 +27,30 @@ struct RowFilter {
   int top_k = 0;
 };
 
-// fp16-exact float -> key: negative values reverse (all bits flipped), the others move above them (sign bit set)
-__device__ __forceinline__ uint32_t f16_order_key(float v) {
-  const uint32_t u = __builtin_bit_cast(uint16_t, static_cast<f16>(v));
-  return (u & 0x8000u) ? (~u & 0xFFFFu) : (u | 0x8000u);
-}
-__device__ __forceinline__ float f16_order_value(uint32_t key) {
-  const uint16_t u = static_cast<uint16_t>((key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu));
-  return static_cast<float>(__builtin_bit_cast(f16, u));
-}
-
 // z[R][4]: the lane's classes (valid(i, w) says which slots hold a class of the row; the others hold -inf and stay -inf);
 // zt: one more class in the lanes where has_tail is set (sample_row_1025's class 1024), -inf elsewhere.
-template <int R, typename V>
+// TKey: the storage type whose rounding the temperature division takes and whose bit pattern is the key (d3pm_order_key.h): as
+// many rounds per search as the key has bits.  The D3PM kernels key every value as fp16; the NAR draw (d3pm_nar_draw.hip) keys a
+// row in the model's own dtype.
+template <typename TKey = f16, int R, typename V>
 __device__ __forceinline__ void filter_row(float (&z)[R][4], float& zt, bool has_tail, V valid, const RowFilter& f) {
   if (f.temperature != 1.0f) {      // kernel-uniform
 #pragma unroll
     for (int i = 0; i < R; ++i)
 #pragma unroll
-      for (int w = 0; w < 4; ++w) z[i][w] = rn16(z[i][w] / f.temperature);      // -inf stays -inf
-    zt = rn16(zt / f.temperature);
+      for (int w = 0; w < 4; ++w) z[i][w] = rn<TKey>(z[i][w] / f.temperature);      // -inf stays -inf
+    zt = rn<TKey>(zt / f.temperature);
   }
   if (f.top_k > 0) {                // kernel-uniform
     uint32_t key[R][4];             // 0 for a slot without a class: below every candidate (>= 1), never counted
 #pragma unroll
     for (int i = 0; i < R; ++i)
 #pragma unroll
-      for (int w = 0; w < 4; ++w) key[i][w] = valid(i, w) ? f16_order_key(z[i][w]) : 0u;
-    const uint32_t kt = has_tail ? f16_order_key(zt) : 0u;
+      for (int w = 0; w < 4; ++w) key[i][w] = valid(i, w) ? order_key<TKey>(z[i][w]) : 0u;
+    const uint32_t kt = has_tail ? order_key<TKey>(zt) : 0u;
     uint32_t c = 0u;
 #pragma unroll
-    for (uint32_t bit = 0x8000u; bit; bit >>= 1) {
+    for (uint32_t bit = kKeyTop<TKey>; bit; bit >>= 1) {
       const uint32_t cand = c | bit;
       int n = __popcll(__ballot(kt >= cand));
 #pragma unroll
@@ -65,7 +59,7 @@ __device__ __forceinline__ void filter_row(float (&z)[R][4], float& zt, bool has
         for (int w = 0; w < 4; ++w) n += __popcll(__ballot(key[i][w] >= cand));
       c = n >= f.top_k ? cand : c;
     }
-    const float theta = f16_order_value(c);
+    const float theta = order_value<TKey>(c);
 #pragma unroll
     for (int i = 0; i < R; ++i)
 #pragma unroll
@@ -108,7 +102,7 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 }
 
 // z, zt, has_tail, valid: as for filter_row (which has run).  Returns theta in every lane.
-template <int R, typename V>
+template <typename TKey = f16, int R, typename V>
 __device__ __forceinline__ float nucleus_row(float (&z)[R][4], float& zt, bool has_tail, V valid, float top_p) {
   if (!(top_p < 1.0f)) return -INFINITY;      // kernel-uniform
   float mx = zt;
@@ -123,17 +117,17 @@ __device__ __forceinline__ float nucleus_row(float (&z)[R][4], float& zt, bool h
   for (int i = 0; i < R; ++i)
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
-      key[i][w] = valid(i, w) ? f16_order_key(z[i][w]) : 0u;
+      key[i][w] = valid(i, w) ? order_key<TKey>(z[i][w]) : 0u;
       q[i][w] = static_cast<uint32_t>(expf(z[i][w] - mx) * 1048576.0f);
       part += q[i][w];
     }
-  const uint32_t kt = has_tail ? f16_order_key(zt) : 0u;
+  const uint32_t kt = has_tail ? order_key<TKey>(zt) : 0u;
   const uint32_t qt = static_cast<uint32_t>(expf(zt - mx) * 1048576.0f);
   const uint32_t Q = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(wave_sum_u32(part + qt))));
   const uint32_t target = static_cast<uint32_t>(ceil(static_cast<double>(top_p) * static_cast<double>(Q)));
   uint32_t c = 0u;
 #pragma unroll
-  for (uint32_t bit = 0x8000u; bit; bit >>= 1) {
+  for (uint32_t bit = kKeyTop<TKey>; bit; bit >>= 1) {
     const uint32_t cand = c | bit;
     uint32_t m = kt >= cand ? qt : 0u;
 #pragma unroll
@@ -143,7 +137,7 @@ __device__ __forceinline__ float nucleus_row(float (&z)[R][4], float& zt, bool h
     m = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(wave_sum_u32(m))));      // every lane holds the sum
     c = m >= target ? cand : c;
   }
-  const float theta = f16_order_value(c);
+  const float theta = order_value<TKey>(c);
 #pragma unroll
   for (int i = 0; i < R; ++i)
 #pragma unroll
