@@ -74,7 +74,8 @@ extern "C" {
  *    (d3pm_revise, d3pm_reveal_step_revise, d3pm_reveal_loop_revise); the self-attention of the few-row iterations of the
  *    deduplicated loop with an utterance's distinct K | V rows pooled in LDS (d3pm_op_attention_gather_pool); the NAR stage's
  *    training step (d3pm_op_adaln_bwd_f32, d3pm_op_nar_embed_bwd_f32, d3pm_op_nar_ce_f32); the NAR stage's level draw with known
- *    frames, top-k / top-p and log-probabilities (d3pm_nar_draw, d3pm_nar_level_draw, d3pm_op_nar_draw) */
+ *    frames, top-k / top-p and log-probabilities (d3pm_nar_draw, d3pm_nar_level_draw, d3pm_op_nar_draw); classifier-free guidance
+ *    in that draw (d3pm_nar_level_guided, d3pm_op_nar_draw_guided) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -924,6 +925,39 @@ int d3pm_nar_level_draw(const d3pm_nar_shape *shape, const d3pm_nar_weights *w, 
                         int level, float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
                         size_t workspace_bytes, void *logits_out, const d3pm_nar_draw *draw, void *stream);
 
+/* Classifier-free guidance in the level draw (additions; ABI version unchanged) ------------------------------------------------------
+ * The d3pm_guidance struct above, for levels 1..7: every level draws from the extrapolated logits of its frame, as the D3PM stage does for
+ * level 0.  Exact definition:
+ *   null twin    the twin of utterance b is the same utterance with no phonemes and no prompt frames: input assembly
+ *                [sep | sep | response], i.e. t_text = t_prompt = 0 and the same response levels.  No new weights, no new embedding
+ *                rule: a twin is an ordinary utterance of the grid, and a caller may put any "negative" text or prompt there instead.
+ *   evaluation   a guided level is ONE evaluation of 2 * batch utterances, utterance batch + b the twin of b: exactly what
+ *                d3pm_nar_level launches for those 2 * batch utterances, up to and including the classifier.
+ *   guided row   for frame f of pair b, with c_j = row t_text_b + t_prompt_b + 2 + f of utterance b and u_j = row t_text_n +
+ *                t_prompt_n + 2 + f of utterance batch + b (the twin's own lengths), both of the logits' storage type T:
+ *                    z_j = rn<T>( fmaf(w, float(c_j) - float(u_j), float(c_j)) )
+ *                -- the subtraction in fp32, an explicit fma, ONE rounding to T (none for fp32).  Everything behind it is the draw of
+ *                d3pm_nar_draw with z in place of l: v_j = rn<T>(z_j / temperature), top-k, top-p and the order key in T, Gumbel-max
+ *                with the Philox words of (j >> 2, (utt0 + b) * 65536 + f, level, stream 2) -- b the LOGICAL index, so the noise is
+ *                that of the unguided call --, D3PM_FLAG_GREEDY, theta_out, and logprob_out = the log-softmax of z (the guided
+ *                logits, as d3pm_frame_scores has it under guidance).  Where c == u, z = c for any w; w = 0 is legal and gives z = c.
+ *   frames       a frame is skipped (nothing read, nothing written) if f >= t_response of b or if either of its two rows lies
+ *                outside the grid.  The drawn id goes to resp[b][f][level + 1] AND to resp[batch + b][f][level + 1]: two halves that
+ *                start equal stay equal through all seven levels.  A known frame writes nothing: the caller put its codes into
+ *                both halves.
+ * `batch` counts LOGICAL utterances; lens / text / prom / resp hold 2 * batch utterances; the workspace is
+ * d3pm_nar_workspace_bytes of (shape, 2 * batch, t_max); logits_out (optional) is [2 * batch][t_max][n_tokens]; draw may be NULL and
+ * its known / logprob_out / theta_out are [batch]...  Under guidance every draw is the kernel of csrc/d3pm_nar_draw.hip, with no cut
+ * where no option is set.  Refused, nothing launched: D3PM_E_ARG for a NULL d3pm_guidance, a negative or non-finite weight and
+ * anything d3pm_nar_draw refuses; D3PM_E_SHAPE for n_tokens > 1280; D3PM_E_WORKSPACE for a workspace that is too small.  A call
+ * without guidance runs none of this: the plain kernels take no further argument.  No statement about audio quality is made:
+ * guidance is meaningful for weights trained with the conditions dropped some of the time (vall_e/vall_e/nar.py: cond_drop). */
+int d3pm_nar_level_guided(const d3pm_nar_shape *shape, const d3pm_nar_weights *w, int batch, int t_max, const int32_t *lens,
+                          const int32_t *text, int tt_max, const int32_t *prom, int tp_max, int32_t *resp, int tr_max,
+                          int level, float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, void *workspace,
+                          size_t workspace_bytes, void *logits_out, const d3pm_nar_draw *draw, const d3pm_guidance *guidance,
+                          void *stream);
+
 /* Single-operator entry points (kernel-level parity tests and micro-benchmarks).  `family`:
  * 0 = auto (MFMA when the shape tiles, else generic), 1 = generic FMA kernels, 2 = MFMA (fails with
  * D3PM_E_SHAPE when unsupported).  Same contracts as inside the denoiser:
@@ -1118,6 +1152,12 @@ int d3pm_op_nar_sample(int dtype, const void *logits, int ldl, const int32_t *le
 int d3pm_op_nar_draw(int dtype, const void *logits, int ldl, const int32_t *lens, int32_t *resp, int tr_max, int resp_stride, int t_max,
                      int n_tokens, int level, float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, int batch,
                      const d3pm_nar_draw *draw, void *stream);
+/* d3pm_op_nar_draw under guidance: the one draw launch of d3pm_nar_level_guided on given logits [2 * batch][t_max][ldl], lens
+ * [2 * batch][3] and resp [2 * batch][tr_max][resp_stride]; `batch` counts logical utterances, draw may be NULL.  Refusals as for
+ * d3pm_op_nar_draw and as d3pm_nar_level_guided lists them. */
+int d3pm_op_nar_draw_guided(int dtype, const void *logits, int ldl, const int32_t *lens, int32_t *resp, int tr_max, int resp_stride,
+                            int t_max, int n_tokens, int level, float temperature, uint64_t seed, uint32_t utt0, uint32_t flags,
+                            int batch, const d3pm_nar_draw *draw, const d3pm_guidance *guidance, void *stream);
 int d3pm_op_layernorm(int dtype, const void *X, void *Y, const void *w, const void *b, const void *film,
                       int M, int d, float eps, void *stream);
 /* Row-panel projection (d_model = 512): a Linear whose output is added to the residual stream, together with the LayerNorm(s)

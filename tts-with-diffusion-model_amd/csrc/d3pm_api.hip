@@ -1502,7 +1502,8 @@ static int check_nar_draw(const char* who, const d3pm_nar_draw* draw, float temp
 static int nar_level_run(const char* who, const d3pm_nar_shape* sh, const d3pm_nar_weights* w, int batch, int t_max, const int32_t* lens,
                          const int32_t* text, int tt_max, const int32_t* prom, int tp_max, int32_t* resp, int tr_max, int level,
                          float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace, size_t workspace_bytes,
-                         void* logits_out, const NarDrawArgs* draw, void* stream) {
+                         void* logits_out, const NarDrawArgs* draw, void* stream, const float* guidance = nullptr) {
+  // guidance: `batch` counts the 2 * logical utterances of the evaluation and the draw pairs utterance b with batch / 2 + b
   D3PM_TRY(check_nar(sh, batch, t_max));
   D3PM_REQUIRE(w && w->blocks && w->text_emb && w->proms_emb && w->resps_emb && w->sep && w->classifier_w && w->classifier_b &&
                    w->pe && lens && text && prom && resp && workspace,
@@ -1544,7 +1545,7 @@ static int nar_level_run(const char* who, const d3pm_nar_shape* sh, const d3pm_n
     D3PM_CHECK_HIP(hipMemcpyAsync(logits_out, ws.logits, static_cast<size_t>(n) * sh->n_tokens * es, hipMemcpyDeviceToDevice, s));
   if (draw)
     return nar_draw(dt, ws.logits, sh->n_tokens, lens, resp, tr_max, stride, t_max, sh->n_tokens, level, temperature, seed, utt0,
-                    (flags & D3PM_FLAG_GREEDY) ? 1 : 0, batch, *draw, s);
+                    (flags & D3PM_FLAG_GREEDY) ? 1 : 0, guidance ? batch / 2 : batch, *draw, s, guidance);
   return nar_sample(dt, ws.logits, sh->n_tokens, lens, resp, tr_max, stride, t_max, sh->n_tokens, level, temperature, seed, utt0,
                     (flags & D3PM_FLAG_GREEDY) ? 1 : 0, batch, s);
 }
@@ -1568,6 +1569,31 @@ int d3pm_nar_level_draw(const d3pm_nar_shape* sh, const d3pm_nar_weights* w, int
   D3PM_REQUIRE(neutral || sh->n_tokens <= 1280, D3PM_E_SHAPE, "d3pm_nar_level_draw: the draw with options supports up to 1280 tokens");
   return nar_level_run("d3pm_nar_level_draw", sh, w, batch, t_max, lens, text, tt_max, prom, tp_max, resp, tr_max, level, temperature,
                        seed, utt0, flags, workspace, workspace_bytes, logits_out, neutral ? nullptr : &opt, stream);
+}
+
+// d3pm_guidance for the NAR stage: any n_q (the levels are drawn one at a time), the draw kernel's token limit always
+static int check_nar_guidance(const char* who, const d3pm_guidance* g, int batch, int n_tokens) {
+  D3PM_REQUIRE(g, D3PM_E_ARG, "%s: null d3pm_guidance", who);
+  D3PM_REQUIRE(std::isfinite(g->weight) && g->weight >= 0.f, D3PM_E_ARG, "%s: guidance weight %g is not a finite number >= 0", who,
+               static_cast<double>(g->weight));
+  D3PM_REQUIRE(batch > 0 && batch <= (1 << 30), D3PM_E_ARG, "%s: batch %d (logical utterances) out of range", who, batch);
+  D3PM_REQUIRE(n_tokens <= 1280, D3PM_E_SHAPE, "%s: the guided draw supports up to 1280 tokens", who);
+  return D3PM_OK;
+}
+
+int d3pm_nar_level_guided(const d3pm_nar_shape* sh, const d3pm_nar_weights* w, int batch, int t_max, const int32_t* lens,
+                          const int32_t* text, int tt_max, const int32_t* prom, int tp_max, int32_t* resp, int tr_max, int level,
+                          float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, void* workspace, size_t workspace_bytes,
+                          void* logits_out, const d3pm_nar_draw* draw, const d3pm_guidance* guidance, void* stream) {
+  const char* who = "d3pm_nar_level_guided";
+  D3PM_TRY(check_nar(sh, batch, t_max));
+  NarDrawArgs opt;
+  bool neutral = true;
+  D3PM_TRY(check_nar_draw(who, draw, temperature, sh->n_tokens, &opt, &neutral));
+  D3PM_TRY(check_nar_guidance(who, guidance, batch, sh->n_tokens));
+  // every guided draw is the kernel of d3pm_nar_draw.hip, with the neutral options where none is set
+  return nar_level_run(who, sh, w, 2 * batch, t_max, lens, text, tt_max, prom, tp_max, resp, tr_max, level, temperature, seed, utt0, flags,
+                       workspace, workspace_bytes, logits_out, &opt, stream, &guidance->weight);
 }
 
 // the three kernels of the stage one at a time (tests): host validation, then the call d3pm_nar_level makes
@@ -1622,6 +1648,22 @@ int d3pm_op_nar_draw(int dtype, const void* logits, int ldl, const int32_t* lens
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (neutral) return nar_sample(dtype, logits, ldl, lens, resp, tr_max, resp_stride, t_max, n_tokens, level, temperature, seed, utt0, greedy, batch, s);
   return nar_draw(dtype, logits, ldl, lens, resp, tr_max, resp_stride, t_max, n_tokens, level, temperature, seed, utt0, greedy, batch, opt, s);
+}
+
+int d3pm_op_nar_draw_guided(int dtype, const void* logits, int ldl, const int32_t* lens, int32_t* resp, int tr_max, int resp_stride,
+                            int t_max, int n_tokens, int level, float temperature, uint64_t seed, uint32_t utt0, uint32_t flags, int batch,
+                            const d3pm_nar_draw* draw, const d3pm_guidance* guidance, void* stream) {
+  const char* who = "d3pm_op_nar_draw_guided";
+  D3PM_REQUIRE(storage_dtype(dtype), D3PM_E_ARG, "%s: bad dtype %d", who, dtype);
+  D3PM_REQUIRE(logits && lens && resp, D3PM_E_ARG, "%s: null pointer", who);
+  D3PM_REQUIRE(batch > 0 && t_max > 0 && tr_max > 0 && n_tokens > 0 && ldl >= n_tokens && level >= 0 && level + 1 < resp_stride,
+               D3PM_E_ARG, "%s: sizes must be positive, ldl >= n_tokens, 0 <= level < resp_stride - 1", who);
+  NarDrawArgs opt;
+  bool neutral = true;
+  D3PM_TRY(check_nar_draw(who, draw, temperature, n_tokens, &opt, &neutral));
+  D3PM_TRY(check_nar_guidance(who, guidance, batch, n_tokens));
+  return nar_draw(dtype, logits, ldl, lens, resp, tr_max, resp_stride, t_max, n_tokens, level, temperature, seed, utt0,
+                  (flags & D3PM_FLAG_GREEDY) ? 1 : 0, batch, opt, static_cast<hipStream_t>(stream), &guidance->weight);
 }
 
 int d3pm_op_linear(int dtype, int family, const void* X, int ldx, const void* W, const void* bias, void* Y, int ldy,

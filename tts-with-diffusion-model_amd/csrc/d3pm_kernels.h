@@ -390,8 +390,10 @@ struct NarDrawArgs {
   float* logprob_out = nullptr;        // [B][tr_max][resp_stride - 1]
   float* theta_out = nullptr;          // [B][tr_max]; non-NULL takes the nucleus arm
 };
+// guidance non-NULL = the guided arm with that weight: logits / lens / resp hold 2 * batch utterances (batch + b the null twin of b), the
+// frame's row is rn<T>(fmaf(w, c - u, c)) and the id goes to both halves of resp; d's arrays stay [batch]...
 int nar_draw(int dtype, const void* logits, int ldl, const int32_t* lens, int32_t* resp, int tr_max, int resp_stride, int t_max,
              int n_tokens, int level, float temperature, uint64_t seed, uint32_t utt0, int greedy, int batch, const NarDrawArgs& d,
-             hipStream_t s);
+             hipStream_t s, const float* guidance = nullptr);
 
 }  // namespace d3pm

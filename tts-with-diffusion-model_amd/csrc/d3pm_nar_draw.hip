@@ -6,6 +6,9 @@
 // The cuts are filter_row / nucleus_row (d3pm_sample_row.h) with the key of a value in ITS OWN storage type -- 16 bits of the f16 /
 // bf16 pattern (16 rounds), 32 bits of an fp32 (32 rounds) -- where the D3PM kernels key every value as fp16; the log-probability is
 // logprob_from_z (d3pm_logprob_row.h).  A launch without options never comes here: d3pm_api.hip sends it to nar_sample_rows.
+// Under classifier-free guidance (d3pm_nar_level_guided, d3pm_op_nar_draw_guided) the same kernel takes its guided arm: the grid holds
+// 2 * batch utterances, utterance batch + b the null twin of b, and a frame's row is z = rn<T>(fmaf(w, float(c) - float(u), float(c)))
+// of its two rows, formed where a plain row is loaded -- for the draw and once more for the log-probability.
 // No LDS, no atomics, no barrier anywhere in this file.
 #include <cmath>
 
@@ -18,19 +21,33 @@ namespace {
 
 constexpr int kR = kMaxGroupsPerLane;
 
+__device__ __forceinline__ float guide_weight(float w) { return w; }
+
 // kFilter: 0 = no cut (known frames and / or the log-probability alone), kFilterArm = top-k, kNucleusArm = top-k and top-p
-template <typename T, int kFilter>
+// W: empty = the plain draw, whose kernels take no further argument; one float = the guided arm and its weight w (lens / logits /
+// resp then hold 2 * batch utterances and `batch` counts the logical ones)
+template <typename T, int kFilter, typename... W>
 __global__ __launch_bounds__(256) void nar_draw_rows(const T* __restrict__ logits, int ldl, const int32_t* __restrict__ lens,
                                                      int32_t* __restrict__ resp, int tr_max, int resp_stride, int t_max, int n_tokens,
                                                      int level, float temperature, uint64_t seed, uint32_t utt0, int greedy, int batch,
                                                      int top_k, float top_p, const uint8_t* __restrict__ known,
-                                                     float* __restrict__ logprob_out, float* __restrict__ theta_out) {
+                                                     float* __restrict__ logprob_out, float* __restrict__ theta_out, W... weight) {
+  static_assert(sizeof...(W) <= 1, "at most the guidance weight");
+  constexpr bool kGuided = sizeof...(W) == 1;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int idx = blockIdx.x * (blockDim.x >> 6) + wave;
   if (idx >= batch * tr_max) return;
   const int b = idx / tr_max, f = idx % tr_max;
   const int tt = lens[b * 3], tp = lens[b * 3 + 1], tr = lens[b * 3 + 2];
   if (f >= tr || tt + tp + 2 + f >= t_max) return;   // outside the utterance or the grid: nothing is read, nothing is written
+  const T* ur = nullptr;      // the twin's row of the same frame
+  float gw = 0.0f;
+  if constexpr (kGuided) {
+    const int un = lens[(batch + b) * 3] + lens[(batch + b) * 3 + 1] + 2 + f;
+    if (un >= t_max) return;
+    ur = logits + (static_cast<size_t>(batch + b) * t_max + un) * ldl;
+    gw = guide_weight(weight...);
+  }
   int32_t* out = resp + (static_cast<size_t>(b) * tr_max + f) * resp_stride + level + 1;
   const bool held = known != nullptr && __builtin_amdgcn_readfirstlane(static_cast<int>(known[idx])) != 0;      // wave-uniform
   if (held) {
@@ -47,7 +64,9 @@ __global__ __launch_bounds__(256) void nar_draw_rows(const T* __restrict__ logit
 #pragma unroll
       for (int w = 0; w < 4; ++w) {
         const int j = (lane + i * kWave) * 4 + w;
-        const float l = ldf(lr + (j < n_tokens ? j : n_tokens - 1));
+        const int at = j < n_tokens ? j : n_tokens - 1;
+        float l = ldf(lr + at);
+        if constexpr (kGuided) l = rn<T>(__builtin_fmaf(gw, l - ldf(ur + at), l));      // the subtraction in fp32, one rounding to T
         z[i][w] = j < n_tokens ? l : -INFINITY;
       }
   };
@@ -91,7 +110,10 @@ __global__ __launch_bounds__(256) void nar_draw_rows(const T* __restrict__ logit
     }
     wave_argmax(best_v, best_j);
     id = best_j;
-    if (lane == 0) *out = id;
+    if (lane == 0) {
+      *out = id;
+      if constexpr (kGuided) out[static_cast<size_t>(batch) * tr_max * resp_stride] = id;      // the twin's half takes the same id
+    }
   }
   if (logprob_out) {      // of the row's own logits: no mask class, no tail (an id outside the row selects no register: -inf)
     float z[kR][4];
@@ -105,14 +127,19 @@ __global__ __launch_bounds__(256) void nar_draw_rows(const T* __restrict__ logit
 
 int nar_draw(int dtype, const void* logits, int ldl, const int32_t* lens, int32_t* resp, int tr_max, int resp_stride, int t_max,
              int n_tokens, int level, float temperature, uint64_t seed, uint32_t utt0, int greedy, int batch, const NarDrawArgs& d,
-             hipStream_t s) {
+             hipStream_t s, const float* guidance) {
   D3PM_REQUIRE(n_tokens >= 1 && n_tokens <= kWave * kMaxGroupsPerLane * 4, D3PM_E_SHAPE, "the NAR draw with options supports up to %d tokens",
                kWave * kMaxGroupsPerLane * 4);
   const dim3 grid((batch * tr_max + 3) / 4), block(256);
   const int arm = (d.theta_out || d.top_p < 1.0f) ? kNucleusArm : (d.top_k > 0 ? kFilterArm : 0);
-#define D3PM_DRAW_ARM(T, kArm)                                                                                                          \
-  nar_draw_rows<T, kArm><<<grid, block, 0, s>>>(static_cast<const T*>(logits), ldl, lens, resp, tr_max, resp_stride, t_max, n_tokens, level, \
-                                                temperature, seed, utt0, greedy, batch, d.top_k, d.top_p, d.known, d.logprob_out, d.theta_out)
+#define D3PM_DRAW_ARGS(T) \
+  static_cast<const T*>(logits), ldl, lens, resp, tr_max, resp_stride, t_max, n_tokens, level, temperature, seed, utt0, greedy, batch, d.top_k, \
+      d.top_p, d.known, d.logprob_out, d.theta_out
+#define D3PM_DRAW_ARM(T, kArm)                                                                          \
+  do {                                                                                                  \
+    if (guidance) nar_draw_rows<T, kArm, float><<<grid, block, 0, s>>>(D3PM_DRAW_ARGS(T), *guidance);   \
+    else nar_draw_rows<T, kArm><<<grid, block, 0, s>>>(D3PM_DRAW_ARGS(T));                              \
+  } while (0)
 #define D3PM_DRAW(T)                                        \
   do {                                                      \
     if (arm == kNucleusArm) D3PM_DRAW_ARM(T, kNucleusArm);  \
@@ -127,6 +154,7 @@ int nar_draw(int dtype, const void* logits, int ldl, const int32_t* lens, int32_
   }
 #undef D3PM_DRAW
 #undef D3PM_DRAW_ARM
+#undef D3PM_DRAW_ARGS
   D3PM_LAUNCH_CHECK();
   return D3PM_OK;
 }

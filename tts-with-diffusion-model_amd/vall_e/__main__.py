@@ -49,6 +49,11 @@ The second form takes what those front-ends write (formats.py) and writes what E
                 the same two cuts for the NAR stage (with --nar-ckpt): every draw of levels 1..7 takes the N largest of its
                 logit / sampling_temperature (0 = off, the default; ties kept) and the smallest set of them that carries the share P
                 of the mass (default 1 = off; include/d3pm_hip.h: d3pm_nar_draw)
+  --nar-guidance W
+                classifier-free guidance in the NAR stage (with --nar-ckpt): every draw of levels 1..7 takes rn(fmaf(W, c - u, c)) of
+                the frame's logits under the text and the speaker (c) and under the empty text and prompt (u), one evaluation of
+                both per level (W >= 0, 0 = off, the default; include/d3pm_hip.h: d3pm_nar_level_guided).  --guidance stays the D3PM
+                stage's weight; neither implies the other
   --nar-logprobs PATH
                 also save how sure the NAR stage was: torch.save(float32 [N, 7]), column c = the model's log-probability of the
                 level c + 1 code of every frame written (of the prefix's own codes under --keep-prefix-levels)
@@ -91,6 +96,7 @@ def main(argv=None):
     ap.add_argument("--logprobs", type=Path, default=None, help="D3PM stage: save the per-frame log-probability of the revealed ids and their timesteps here")
     ap.add_argument("--nar-top-k", type=int, default=0, help="NAR stage: draw every level from its N largest logits only (0 = off)")
     ap.add_argument("--nar-top-p", type=float, default=1.0, help="NAR stage: draw from the smallest set of classes that carries this share of the mass (1 = off)")
+    ap.add_argument("--nar-guidance", type=float, default=0.0, help="NAR stage: classifier-free guidance weight w (>= 0, 0 = off) in the draw of levels 1..7")
     ap.add_argument("--nar-logprobs", type=Path, default=None, help="NAR stage: save the [frames, 7] log-probabilities of the codes of levels 1..7 here")
     ap.add_argument("--keep-prefix-levels", action="store_true", help="with --continue-from: the prefix's 8 levels are known to the NAR stage")
     ap.add_argument("--native", action="store_true", help="the shape upstream's class really builds (d=32, 16 heads, 8 blocks)")
@@ -108,9 +114,10 @@ def main(argv=None):
         _hip.nar_draw_options(args.nar_top_k, args.nar_top_p, 1024)
         if args.keep_prefix_levels and args.continue_from is None:
             raise ValueError("--keep-prefix-levels needs --continue-from")
-        nar_flags = args.nar_top_k != 0 or args.nar_top_p != 1.0 or args.nar_logprobs is not None or args.keep_prefix_levels
+        nar_guided = _hip.guidance_options(args.nar_guidance) is not None
+        nar_flags = args.nar_top_k != 0 or args.nar_top_p != 1.0 or args.nar_logprobs is not None or args.keep_prefix_levels or nar_guided
         if nar_flags and args.nar_ckpt is None:
-            raise ValueError("--nar-top-k / --nar-top-p / --nar-logprobs / --keep-prefix-levels need --nar-ckpt")
+            raise ValueError("--nar-top-k / --nar-top-p / --nar-guidance / --nar-logprobs / --keep-prefix-levels need --nar-ckpt")
     except ValueError as e:
         ap.error(str(e))
     if len(args.paths) not in (1, 3):
@@ -187,6 +194,8 @@ def main(argv=None):
             known[: len(full)] = full
             nar_kw["known"] = [known]
             nar_kw["known_mask"] = [torch.arange(n_frames) < len(full)]
+        if nar_guided:
+            nar_kw["guidance"] = args.nar_guidance
         if args.nar_logprobs is not None:
             nar_kw["return_logprobs"] = True
         resps = nar(text_list=[phns.to(args.device)], proms_list=[proms.to(args.device)], resps_list=[resps],

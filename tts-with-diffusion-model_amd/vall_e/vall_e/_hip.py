@@ -436,6 +436,10 @@ SIGNATURES = {
     "d3pm_nar_level_draw": (C.c_int, [C.POINTER(NarShape), C.POINTER(NarWeights), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64,
                                       C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(NarDraw), C.c_void_p]),
+    "d3pm_nar_level_guided": (C.c_int, [C.POINTER(NarShape), C.POINTER(NarWeights), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64,
+                                        C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(NarDraw),
+                                        C.POINTER(Guidance), C.c_void_p]),
     "d3pm_op_linear": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.POINTER(Tuning), C.c_void_p]),
@@ -469,6 +473,9 @@ SIGNATURES = {
                                      C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "d3pm_op_nar_draw": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(NarDraw), C.c_void_p]),
+    "d3pm_op_nar_draw_guided": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(NarDraw), C.POINTER(Guidance),
+                                          C.c_void_p]),
     "d3pm_op_layernorm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_int, C.c_float, C.c_void_p]),
     "d3pm_op_linear_rowpanel": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1586,6 +1593,33 @@ def op_nar_draw(logits, lens, resp, level, temperature, seed, *, utt0=0, flags=0
     return resp
 
 
+def op_nar_draw_guided(logits, lens, resp, level, temperature, seed, guidance, *, utt0=0, flags=0, top_k=0, top_p=1.0, known=None,
+                       logprob_out=None, theta_out=None):
+    """op_nar_draw under classifier-free guidance (d3pm_op_nar_draw_guided): logits [2 B, t_max, n_tokens], lens [2 B, 3] and resp
+    [2 B, tr_max, resp_stride] hold the B utterances and behind them their null twins; the draw runs on rn<T>(fmaf(guidance, c - u, c))
+    and writes the id into both halves of resp.  known / logprob_out / theta_out are [B, ...].  guidance: a finite weight >= 0 (0 is
+    legal here and draws from the conditioned half).  Returns resp."""
+    B2, t_max, n_tokens, ldl, dev = _nar_draw_extents(logits, lens, resp, level)
+    if B2 % 2:
+        raise D3PMError(f"guided logits hold 2 * batch utterances, got {B2}")
+    B = B2 // 2
+    guidance_options(guidance)
+    gd = Guidance(float(guidance))
+    top_k, top_p = nar_draw_options(top_k, top_p, n_tokens)
+    tr_max = resp.shape[1]
+    if known is not None:
+        _require(known, "known", (B, tr_max), (torch.uint8,), dev)
+    if logprob_out is not None:
+        _require(logprob_out, "logprob_out", (B, tr_max, resp.shape[2] - 1), (torch.float32,), dev)
+    if theta_out is not None:
+        _require(theta_out, "theta_out", (B, tr_max), (torch.float32,), dev)
+    draw = nar_draw_struct(top_k, top_p, known, logprob_out, theta_out)
+    check(lib().d3pm_op_nar_draw_guided(dtype_code(logits.dtype), _p(logits), ldl, _p(lens), _p(resp), tr_max, resp.shape[2], t_max, n_tokens,
+                                        level, float(temperature), seed, utt0, flags, B, None if draw is None else C.byref(draw),
+                                        C.byref(gd), stream_ptr()), "d3pm_op_nar_draw_guided")
+    return resp
+
+
 def stats_buffer(M: int, parts: int, device) -> torch.Tensor:
     """Storage of the row moments in the library's layout [ceil(M / 16), parts, 16, 2] (include/d3pm_hip.h: d3pm_op_row_stats)."""
     return torch.zeros(((M + 15) // 16, parts, 16, 2), dtype=torch.float32, device=device)
@@ -1759,9 +1793,12 @@ class NarRunner:
                                   ptr("classifier.weight"), ptr("classifier.bias"), pe.data_ptr(), pe.shape[0], self.blocks)
         self._ws = None
 
-    def level(self, lens, text, prom, resp, t_max, level, temperature, seed, utt0=0, flags=0, want_logits=False, draw=None):
+    def level(self, lens, text, prom, resp, t_max, level, temperature, seed, utt0=0, flags=0, want_logits=False, draw=None,
+              guidance=None):
         """One quantizer level for the whole batch; `resp` [B, tr_max, n_resp_levels+1] int32 is updated in place.  draw: None = the
-        draw without options (d3pm_nar_level), else a NarDraw (d3pm_nar_level_draw) whose tensors the caller keeps alive."""
+        draw without options (d3pm_nar_level), else a NarDraw (d3pm_nar_level_draw) whose tensors the caller keeps alive.
+        guidance: a Guidance struct = d3pm_nar_level_guided: the arrays hold the B // 2 utterances and behind them their null twins, the
+        draw's arrays are [B // 2, ...] and the logits returned are those of all B."""
         cfg, B = self.cfg, lens.shape[0]
         need = lib().d3pm_nar_workspace_bytes(C.byref(self.shape), B, t_max)
         if need == 0:
@@ -1769,6 +1806,15 @@ class NarRunner:
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         logits = torch.empty((B, t_max, cfg.n_tokens), dtype=self.dtype, device=self.device) if want_logits else None
+        if guidance is not None:
+            if B % 2:
+                raise D3PMError(f"a guided level holds 2 * batch utterances, got {B}")
+            check(lib().d3pm_nar_level_guided(C.byref(self.shape), C.byref(self.weights), B // 2, t_max, _p(lens), _p(text), text.shape[1],
+                                              _p(prom), prom.shape[1], _p(resp), resp.shape[1], int(level), float(temperature), seed,
+                                              utt0, flags, _p(self._ws), self._ws.numel(), _p(logits),
+                                              None if draw is None else C.byref(draw), C.byref(guidance), stream_ptr()),
+                  "d3pm_nar_level_guided")
+            return logits
         if draw is not None:
             check(lib().d3pm_nar_level_draw(C.byref(self.shape), C.byref(self.weights), B, t_max, _p(lens), _p(text), text.shape[1],
                                             _p(prom), prom.shape[1], _p(resp), resp.shape[1], int(level), float(temperature), seed,

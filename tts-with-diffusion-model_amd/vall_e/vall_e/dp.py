@@ -84,8 +84,9 @@ def generate_codes_dp(ar, nar, text_list: Sequence[torch.Tensor], proms_list: Se
     to every rank.  No collective sits between the stages: a rank's NAR input is its own D3PM output.
     With a sequence `n_frames` (one length per utterance) the NAR stage sees utterance b's own L_b frames and the result is
     [B, max L, 8], zero beyond L_b.
-    nar_kw: keyword options of the NAR stage (NAR.forward: sampling_temperature, greedy, top_k, top_p, known, known_mask); the
-    per-utterance lists among them (known, known_mask) are cut to the rank's shard like those of the D3PM stage.  The result is the
+    nar_kw: keyword options of the NAR stage (NAR.forward: sampling_temperature, greedy, top_k, top_p, known, known_mask, guidance,
+    null_text_list, null_proms_list); the per-utterance lists among them (known, known_mask, the null lists) are cut to the rank's
+    shard like those of the D3PM stage.  The result is the
     codes alone, so return_logprobs is not taken here."""
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank(group) if world > 1 else 0

@@ -66,6 +66,37 @@ class _BlockParams(nn.Module):
         self.ffn = _Prenorm(nn.Sequential(nn.Linear(d, 4 * d), nn.GELU(), nn.Dropout(0.0), nn.Linear(4 * d, d)), d, n_levels)
 
 
+def guidance_twins(text_list, proms_list, resps_list, null_text_list=None, null_proms_list=None):
+    """The 2 B lists of a guided call (include/d3pm_hip.h: d3pm_nar_level_guided): behind the B utterances their null twins -- the empty
+    text `text[:0]` and the empty prompt `prom[:0]` unless the caller gives others, which are used as they are -- each with the
+    response of its utterance (the same tensor).  Host only: nothing here reads a tensor's contents.  ValueError for lists of
+    the wrong length."""
+    B = len(resps_list)
+    if not (len(text_list) == len(proms_list) == B):
+        raise ValueError(f"{len(text_list)} texts, {len(proms_list)} prompts and {B} responses")
+    for name, given in (("null_text_list", null_text_list), ("null_proms_list", null_proms_list)):
+        if given is not None and len(given) != B:
+            raise ValueError(f"{name} has {len(given)} entries for {B} utterances")
+    null_text = [t[:0] for t in text_list] if null_text_list is None else list(null_text_list)
+    null_proms = [p[:0] for p in proms_list] if null_proms_list is None else list(null_proms_list)
+    return list(text_list) + null_text, list(proms_list) + null_proms, list(resps_list) + list(resps_list)
+
+
+def cond_drop_lists(text_list, proms_list, seed, utt0, cond_drop, device):
+    """The texts and prompts of a training step under cond_drop = p or (p_text, p_prompt) (train.cond_drop_probs): utterance b loses
+    its text and / or its prompt (replaced by the empty one) by train.cond_drop_decision(seed, utt0 + b, ...), a function of (seed,
+    utt) alone -- Philox stream 5, the D3PM stage's rule.  -> (texts, prompts, [(dropped text?, dropped prompt?)])."""
+    from . import train
+    p_text, p_prompt = train.cond_drop_probs(cond_drop)
+    texts, proms, dropped = [], [], []
+    for b, (t, p) in enumerate(zip(text_list, proms_list)):
+        dt, dp_ = train.cond_drop_decision(seed, utt0 + b, p_text, p_prompt, device)
+        texts.append(t[:0] if dt else t)
+        proms.append(p[:0] if dp_ else p)
+        dropped.append((dt, dp_))
+    return texts, proms, dropped
+
+
 class NAR(SymmapState, nn.Module):
     n_resp_levels = 7
     n_prom_levels = 8
@@ -118,6 +149,12 @@ class NAR(SymmapState, nn.Module):
         # absent prompt levels are -1 (they contribute nothing), padded prompt rows are 0 like upstream's zero padding
         prom = pad_sequence([F.pad(i32(p), (0, self.n_prom_levels - p.shape[-1]), value=-1) for p in proms_list], batch_first=True)
         resp = pad_sequence([F.pad(i32(r), (0, self.n_resp_levels + 1 - r.shape[-1])) for r in resps_list], batch_first=True)
+        # a batch without a single phoneme or without a single prompt frame (dropped conditions, null twins alone) keeps one padding
+        # column / row: the index arrays the kernels take are never empty, and nothing reads past an utterance's own length
+        if text.shape[1] == 0:
+            text = text.new_zeros((text.shape[0], 1))
+        if prom.shape[1] == 0:
+            prom = prom.new_zeros((prom.shape[0], 1, self.n_prom_levels))
         lens = torch.tensor(lens_host, dtype=torch.int32).to(dev, non_blocking=True)
         t_max = max(a + b_ + c for a, b_, c in lens_host) + 2
         if self.pad_rows_to_tiles:
@@ -136,19 +173,28 @@ class NAR(SymmapState, nn.Module):
 
     @torch.no_grad()
     def forward_backward(self, text_list: Sequence[Tensor], proms_list: Sequence[Tensor], resps_list: Sequence[Tensor], *,
-                         seed: Optional[int] = None, utt0: int = 0, quant_levels=None, dropout=False) -> Tensor:
+                         seed: Optional[int] = None, utt0: int = 0, quant_levels=None, dropout=False, cond_drop=0.0) -> Tensor:
         """One training step's loss and gradients (nar.py:53-74, base.py:403-488; nar_train.py): resps_list [t, 8] each.  Utterance b
         takes the level l_b = quant_levels[b], or the draw of (seed, utt0 + b) (seed=None: one from torch.randint, as generate_audio
         does); levels 0 .. l_b go in and level l_b + 1 is the target.  nll = the mean cross-entropy over all response frames of the
         call; its gradient is ADDED to `.grad` (fp32) of every parameter.  dropout: False = eval arithmetic, True = upstream's
         p = 0.1 at its three sites per block, a number = that probability.  Returns the fp32 scalar loss and sets
-        `self.loss = {"nll": loss}`, where upstream's gather_attribute("loss") reads it.  Data parallel: each rank's loss is the mean
+        `self.loss = {"nll": loss}`, where upstream's gather_attribute("loss") reads it.
+        cond_drop: p or (p_text, p_prompt) -- per utterance the text and / or the prompt is replaced by the empty one (the null twin of
+        forward(guidance=...)) before packing, decided by train.cond_drop_decision(seed, utt0 + b, ...): Philox stream 5, the D3PM
+        stage's rule, a function of (seed, utt) alone; 0 / False (default) is the step without it, bit for bit.  Data parallel: each rank's loss is the mean
         over its own frames and train.all_reduce_gradients averages the ranks, as DeepSpeed does upstream.
         ValueError before any GPU work: lists of unequal length, a response that is not 8 levels wide or is empty, quant_levels of
-        the wrong length or outside 0 .. 6, a dropout outside [0, 1)."""
-        from . import nar_train
+        the wrong length or outside 0 .. 6, a dropout outside [0, 1), a cond_drop that is no probability or pair of them."""
+        from . import nar_train, train
         nar_train.validate(text_list, proms_list, resps_list, quant_levels=quant_levels, dropout=dropout, n_layers=self.cfg.n_layers)
+        p_text, p_prompt = train.cond_drop_probs(cond_drop)
         self._no_cpu_path()
+        if p_text > 0.0 or p_prompt > 0.0:
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            with torch.cuda.device(self.device):
+                text_list, proms_list, _ = cond_drop_lists(text_list, proms_list, seed, utt0, (p_text, p_prompt), self.device)
         loss, _ = nar_train.NARTrainer(self).step(text_list, proms_list, resps_list, seed=seed, utt0=utt0, quant_levels=quant_levels,
                                                   dropout=dropout)
         self.loss = {"nll": loss}
@@ -173,7 +219,7 @@ class NAR(SymmapState, nn.Module):
     def forward(self, text_list: Sequence[Tensor], proms_list: Sequence[Tensor], resps_list: Sequence[Tensor],
                 sampling_temperature: float = 0.2, *, seed: Optional[int] = None, greedy: bool = False, utt0: int = 0,
                 return_logits_level: Optional[int] = None, quant_levels=None, top_k: int = 0, top_p: float = 1.0, known=None,
-                known_mask=None, return_logprobs: bool = False):
+                known_mask=None, return_logprobs: bool = False, guidance: float = 0.0, null_text_list=None, null_proms_list=None):
         """resps_list: [t, l] with the levels already known (l = 1 after the D3PM stage) -> [LongTensor[t, 8]].
         l = 8 is upstream's training call (nar.py:53-74): the loss of forward_backward(..., seed=, utt0=, quant_levels=) without
         gradients goes to `self.loss = {"nll": loss}` and [] is returned.
@@ -188,13 +234,29 @@ class NAR(SymmapState, nn.Module):
           return_logprobs  -> (codes, [FloatTensor[t, 7]]): column c = the model's log-probability (its own logits: no temperature, no
                            cut) of the level c + 1 code that stands in the result, drawn or known; 0 in the columns of levels that
                            were given.
+          guidance         w > 0: classifier-free guidance in every level's draw (include/d3pm_hip.h: d3pm_nar_level_guided).  Each
+                           level is one evaluation of 2 B utterances -- behind the B of the call their null twins, `text[:0]` and
+                           `prom[:0]` with the same response, or null_text_list / null_proms_list as they are -- and frame f draws from
+                           rn(fmaf(w, c - u, c)) of its two rows; top_k / top_p, known, return_logprobs (the log-softmax of the guided
+                           logits), greedy and utt0 act on that row, and the noise is that of the call without guidance.  The
+                           results are those of the B utterances; return_logits_level returns the grid of all 2 B.  0 (default) is
+                           the call without it, launch for launch.  Meaningful for weights trained with the conditions dropped some of
+                           the time (forward_backward(cond_drop=...)); no statement about audio quality is made.
         ValueError before any GPU work: lists of unequal length, a known / known_mask of the wrong shape or one without the other,
-        top_k / top_p out of range, and any of these options together with the 8-level training call."""
+        top_k / top_p out of range, a guidance that is not finite and >= 0, null lists without guidance or of the wrong length, and
+        any of these options together with the 8-level training call."""
         levels = {r.shape[-1] for r in resps_list}
         if len(levels) > 1:
             raise ValueError(f"Please give only one level, got {levels}.")
         n_given = next(iter(levels))
         options = top_k != 0 or top_p != 1.0 or known is not None or known_mask is not None or return_logprobs
+        guide = _hip.guidance_options(guidance)
+        if guide is None and (null_text_list is not None or null_proms_list is not None):
+            raise ValueError("null_text_list / null_proms_list belong to guidance: give a weight > 0 with them")
+        if guide is not None and n_given == self.n_resp_levels + 1:
+            raise ValueError("guidance belongs to the inference call: the responses have all 8 levels, which is the training call")
+        if guide is not None:
+            guidance_twins(text_list, proms_list, resps_list, null_text_list, null_proms_list)      # the lists' lengths
         if options:
             if n_given == self.n_resp_levels + 1:
                 raise ValueError("top_k / top_p / known / known_mask / return_logprobs belong to the inference call: the responses "
@@ -220,6 +282,10 @@ class NAR(SymmapState, nn.Module):
             dev = self.device
             resps_list = [torch.cat([r.to(dev), (k.to(dev)[:, n_given:] * m.to(dev)[:, None]).to(r.dtype)], dim=1)
                           for r, k, m in zip(resps_list, known, known_mask)]
+        B = len(resps_list)
+        if guide is not None:
+            # (after the known codes went into the responses: both halves carry them)
+            text_list, proms_list, resps_list = guidance_twins(text_list, proms_list, resps_list, null_text_list, null_proms_list)
         lens, text, prom, resp, t_max, lens_host = self._pack(text_list, proms_list, resps_list)
         run = self.runner(t_max)
         flags = _hip.FLAG_GREEDY if greedy else 0
@@ -228,15 +294,15 @@ class NAR(SymmapState, nn.Module):
             if known is not None:
                 from torch.nn.utils.rnn import pad_sequence
                 held = pad_sequence([m.to(device=self.device, dtype=torch.uint8) for m in known_mask], batch_first=True).contiguous()
-            logprob = torch.zeros((resp.shape[0], resp.shape[1], self.n_resp_levels), dtype=torch.float32, device=self.device) if return_logprobs else None
+            logprob = torch.zeros((B, resp.shape[1], self.n_resp_levels), dtype=torch.float32, device=self.device) if return_logprobs else None
             draw = _hip.nar_draw_struct(top_k, top_p, held, logprob) if options else None
             for level in range(n_given - 1, self.n_resp_levels):
                 lg = run.level(lens, text, prom, resp, t_max, level, sampling_temperature, seed, utt0, flags,
-                               want_logits=(return_logits_level == level), draw=draw)
+                               want_logits=(return_logits_level == level), draw=draw, guidance=guide)
                 if lg is not None:
                     logits = lg
-        out = [resp[b, : lens_host[b][2]].long() for b in range(len(text_list))]
+        out = [resp[b, : lens_host[b][2]].long() for b in range(B)]
         if return_logprobs:
-            scores = [logprob[b, : lens_host[b][2]] for b in range(len(text_list))]
+            scores = [logprob[b, : lens_host[b][2]] for b in range(B)]
             return (out, logits, lens, t_max, scores) if return_logits_level is not None else (out, scores)
         return (out, logits, lens, t_max) if return_logits_level is not None else out
