@@ -987,7 +987,11 @@ int d3pm_op_linear_mx(int out_dtype, const void *X8, int ldx, const void *SX, co
 /* The folded-LayerNorm pieces as single ops (MFMA family, 16-bit; d3pm_fold_block above):
  *   row_stats     per row and 32-column part the pair (sum x, sum x^2), fp32 -- what a producing projection leaves behind -- in the
  *                 layout [ceil(M / 16)][d / 32][16][2] (the 16 rows of a row block side by side: one part of one row block is one
- *                 128-byte line): the pair of (row, part) starts at float (((row / 16) * (d / 32) + part) * 16 + row % 16) * 2;
+ *                 128-byte line): the pair of (row, part) starts at float (((row / 16) * (d / 32) + part) * 16 + row % 16) * 2.
+ *                 The buffer therefore holds slots for the rows M .. 16 ceil(M / 16) - 1 as well; no row owns them and no producer --
+ *                 row_stats, linear_stats, linear_live, the sampler's launches -- writes them (every store of a pair is predicated on
+ *                 row < M), and no consumer reads them (rows beyond M read the pair of row M - 1 and are not stored).  They keep
+ *                 what the caller left there (tests/test_gpu_gemm_edges.py);
  *   linear_stats  d3pm_op_linear with a residual (R1 [+ R2] [+ row mask]) that also writes the moments of the rows it stores (N = d);
  *   linear_fold   Y = act(rstd_r (X_r . Wf^T - mean_r fold_s) + fold_b) with the moments of X's rows from `stats_in` (layout of row_stats, K columns)
  *                 (X = the raw rows, Wf / fold_s / fold_b as d3pm_fold_build makes them); act 0 / 1 (GELU). */

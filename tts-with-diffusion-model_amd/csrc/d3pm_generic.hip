@@ -160,7 +160,12 @@ __global__ __launch_bounds__(256) void linear_tiled(const T* __restrict__ X, int
         if (R2) r = rn<T>(r + ldf(R2 + static_cast<size_t>(m) * ldr + n));
         v = rn<T>(r + v);
       }
-      stf(Y + static_cast<size_t>(m) * ldy + n, v * mk);
+      // y = v * mask in IEEE arithmetic: a masked negative value is -0, as in eager PyTorch and in the MFMA epilogues.  The empty asm keeps
+      // hipcc from fusing the product into the f16 conversion as v_fma_mixlo_f16(mk, v, +0), whose +0 addend turns -0 into +0
+      // (seen in the .s of hipcc 7.2; found by tests/test_gpu_gemm_edges.py, where the f16 generic family alone stored +0)
+      float y = v * mk;
+      asm volatile("" : "+v"(y));
+      stf(Y + static_cast<size_t>(m) * ldy + n, y);
     }
   }
 }

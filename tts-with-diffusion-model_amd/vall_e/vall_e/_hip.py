@@ -1630,21 +1630,23 @@ def stats_rows(st: torch.Tensor, M: int) -> torch.Tensor:
     return st.permute(0, 2, 1, 3).reshape(-1, st.shape[1], 2)[:M]
 
 
-def op_row_stats(x):
-    """[M, d] 16-bit rows -> the fp32 partial (sum, sum of squares) per 32-column part, in the library's layout (stats_buffer)."""
+def op_row_stats(x, *, stats=None):
+    """[M, d] 16-bit rows -> the fp32 partial (sum, sum of squares) per 32-column part, in the library's layout (stats_buffer).
+    stats: a preallocated moment buffer (tests)."""
     M, d = x.shape
-    st = stats_buffer(M, d // 32, x.device)
+    st = stats_buffer(M, d // 32, x.device) if stats is None else stats
     check(lib().d3pm_op_row_stats(dtype_code(x.dtype), _p(x), x.stride(0), M, d, _p(st), stream_ptr()), "d3pm_op_row_stats")
     return st
 
 
-def op_linear_stats(x, w, bias, r1, *, r2=None, row_mask=None, mask_period=1):
-    """(y, stats): y = residual epilogue of d3pm_op_linear, stats = the moments of the rows of y (layout of stats_buffer)."""
+def op_linear_stats(x, w, bias, r1, *, r2=None, row_mask=None, mask_period=1, out=None, stats=None):
+    """(y, stats): y = residual epilogue of d3pm_op_linear, stats = the moments of the rows of y (layout of stats_buffer).
+    out: a preallocated y [M, N] (any row stride; it may be r1); stats: a preallocated moment buffer (tests)."""
     M, K = x.shape
     N = w.shape[0]
-    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    st = stats_buffer(M, N // 32, x.device)
-    check(lib().d3pm_op_linear_stats(dtype_code(x.dtype), _p(x), x.stride(0), _p(w), _p(bias), _p(y), N, _p(r1), _p(r2), r1.stride(0),
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device) if out is None else out
+    st = stats_buffer(M, N // 32, x.device) if stats is None else stats
+    check(lib().d3pm_op_linear_stats(dtype_code(x.dtype), _p(x), x.stride(0), _p(w), _p(bias), _p(y), y.stride(0), _p(r1), _p(r2), r1.stride(0),
                                      _p(row_mask), mask_period, M, N, K, _p(st), C.byref(TUNING), stream_ptr()), "d3pm_op_linear_stats")
     return y, st
 
@@ -1703,12 +1705,13 @@ def op_fold_weights(w, bias, gamma, beta, film=None):
     return wf, fs, fb
 
 
-def op_linear_fold(x, wf, fold_s, fold_b, stats, *, act=0, eps=1e-6):
-    """act(LN-folded projection) of the raw rows x [M, K] with their moments `stats` (d3pm_op_linear_fold)."""
+def op_linear_fold(x, wf, fold_s, fold_b, stats, *, act=0, eps=1e-6, out=None):
+    """act(LN-folded projection) of the raw rows x [M, K] with their moments `stats` (d3pm_op_linear_fold).
+    out: a preallocated y [M, N] with any row stride (tests)."""
     M, K = x.shape
     N = wf.shape[0]
-    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    check(lib().d3pm_op_linear_fold(dtype_code(x.dtype), _p(x), x.stride(0), _p(wf), _p(fold_s), _p(fold_b), _p(stats), eps, _p(y), N,
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device) if out is None else out
+    check(lib().d3pm_op_linear_fold(dtype_code(x.dtype), _p(x), x.stride(0), _p(wf), _p(fold_s), _p(fold_b), _p(stats), eps, _p(y), y.stride(0),
                                     M, N, K, act, C.byref(TUNING), stream_ptr()), "d3pm_op_linear_fold")
     return y
 
