@@ -75,7 +75,8 @@ extern "C" {
  *    deduplicated loop with an utterance's distinct K | V rows pooled in LDS (d3pm_op_attention_gather_pool); the NAR stage's
  *    training step (d3pm_op_adaln_bwd_f32, d3pm_op_nar_embed_bwd_f32, d3pm_op_nar_ce_f32); the NAR stage's level draw with known
  *    frames, top-k / top-p and log-probabilities (d3pm_nar_draw, d3pm_nar_level_draw, d3pm_op_nar_draw); classifier-free guidance
- *    in that draw (d3pm_nar_level_guided, d3pm_op_nar_draw_guided) */
+ *    in that draw (d3pm_nar_level_guided, d3pm_op_nar_draw_guided); the two-output LayerNorm -> MX launch as a single op
+ *    (d3pm_op_layernorm_mx_pair) */
 #define D3PM_ABI_VERSION 6
 
 enum { D3PM_F32 = 0, D3PM_F16 = 1, D3PM_BF16 = 2 };
@@ -981,6 +982,10 @@ int d3pm_op_linear(int dtype, int family, const void *X, int ldx, const void *W,
 int d3pm_op_quantize_mx(int dtype, const void *X, int ldx, void *X8, void *SX, int M, int K, void *stream);
 int d3pm_op_layernorm_mx(int dtype, const void *X, void *Y8, void *SX, const void *w, const void *b, const void *film, int M,
                          int d, float eps, void *stream);
+/* layernorm_mx with a second LayerNorm (w2, b2) of the same rows and the same moments -> Y8_2, SX_2, as the sampler's norm2 | norm22
+ * launch; FiLM applies to the first output alone.  Every pointer but `film` is required. */
+int d3pm_op_layernorm_mx_pair(int dtype, const void *X, void *Y8, void *SX, const void *w, const void *b, const void *film,
+                              const void *w2, const void *b2, void *Y8_2, void *SX_2, int M, int d, float eps, void *stream);
 int d3pm_op_linear_mx(int out_dtype, const void *X8, int ldx, const void *SX, const void *W8, const void *SW, const void *bias,
                       void *Y, int ldy, const void *R1, int ldr, const uint8_t *row_mask, int mask_period, void *Y8, void *SY,
                       int M, int N, int K, int act, const d3pm_tuning *tuning, void *stream);

@@ -9,6 +9,7 @@ for st in $STAGES; do
     kernels) timeout -k 10 600 python -m pytest tests/test_gpu_kernels.py -m gpu -q -p no:cacheprovider -x > $OUT/pytest_kernels.log 2>&1; rc=$?; tail -15 $OUT/pytest_kernels.log;;
     fold)    timeout -k 10 900 python -m pytest tests/test_gpu_fold.py tests/test_gpu_batch_sweep.py -m gpu -q -p no:cacheprovider > $OUT/pytest_fold.log 2>&1; rc=$?; tail -40 $OUT/pytest_fold.log;;
     gemm)    timeout -k 10 300 python -m pytest tests/test_gpu_gemm_edges.py -m gpu -q -p no:cacheprovider > $OUT/pytest_gemm.log 2>&1; rc=$?; tail -40 $OUT/pytest_gemm.log;;
+    mx)      timeout -k 10 300 python -m pytest tests/test_gpu_mx_exact.py -m gpu -q -p no:cacheprovider > $OUT/pytest_mx.log 2>&1; rc=$?; tail -40 $OUT/pytest_mx.log;;
     all)     timeout -k 10 1150 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/pytest_all.log 2>&1; rc=$?; tail -40 $OUT/pytest_all.log;;
     benchq)  timeout -k 10 600 python bench.py --full --steps 3 --warmup 1 --cpu-steps 0 --no-nar --no-nq8 --no-fp8 --no-vctk 2> $OUT/benchq.err | tee $OUT/benchq.json; rc=${PIPESTATUS[0]}; tail -5 $OUT/benchq.err;;
     profab)  cd /tmp && export TMPDIR=/tmp; rc=0

@@ -1697,6 +1697,13 @@ int d3pm_op_layernorm_mx(int dtype, const void* X, void* Y8, void* SX, const voi
                       eps, static_cast<hipStream_t>(stream));
 }
 
+int d3pm_op_layernorm_mx_pair(int dtype, const void* X, void* Y8, void* SX, const void* w, const void* b, const void* film, const void* w2,
+                              const void* b2, void* Y8_2, void* SX_2, int M, int d, float eps, void* stream) {
+  D3PM_REQUIRE(X && Y8 && SX && w && b && w2 && b2 && Y8_2 && SX_2 && M > 0, D3PM_E_ARG, "d3pm_op_layernorm_mx_pair: bad arguments");
+  return layernorm_mx(dtype, X, static_cast<uint8_t*>(Y8), static_cast<uint8_t*>(SX), w, b, film, w2, b2, static_cast<uint8_t*>(Y8_2),
+                      static_cast<uint8_t*>(SX_2), M, d, eps, static_cast<hipStream_t>(stream));
+}
+
 int d3pm_op_linear_mx(int out_dtype, const void* X8, int ldx, const void* SX, const void* W8, const void* SW, const void* bias, void* Y,
                       int ldy, const void* R1, int ldr, const uint8_t* row_mask, int mask_period, void* Y8, void* SY, int M, int N, int K,
                       int act, const d3pm_tuning* tuning, void* stream) {

@@ -423,6 +423,7 @@ SIGNATURES = {
     "d3pm_op_quantize_mx": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "d3pm_op_layernorm_mx": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "d3pm_op_layernorm_mx_pair": (C.c_int, [C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "d3pm_op_linear_mx": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.POINTER(Tuning), C.c_void_p]),
@@ -1282,38 +1283,64 @@ def dequantize_mx(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
     return (codes.view(torch.float8_e4m3fn).float().reshape(N, K // 128, 4, 32) * sc[..., None]).reshape(N, K)
 
 
-def op_quantize_mx(x):
+def _mx_pair(M, K, device, out):
+    """(codes [M, K], scales [M, 4, K // 128]): `out` where the caller brings the pair (contiguous uint8 of those shapes), else new."""
+    if out is None:
+        return (torch.empty((M, K), dtype=torch.uint8, device=device), torch.empty((M, 4, K // 128), dtype=torch.uint8, device=device))
+    c, s = out
+    assert c.dtype == s.dtype == torch.uint8 and c.shape == (M, K) and s.shape == (M, 4, K // 128) and c.is_contiguous() and s.is_contiguous()
+    return c, s
+
+
+def op_quantize_mx(x, *, out=None):
+    """x [M, K] (row stride x.stride(0)) -> (codes, scales); out = (codes, scales) to write into."""
     M, K = x.shape
-    x8 = torch.empty((M, K), dtype=torch.uint8, device=x.device)
-    sx = torch.empty((M, 4, K // 128), dtype=torch.uint8, device=x.device)
+    x8, sx = _mx_pair(M, K, x.device, out)
     check(lib().d3pm_op_quantize_mx(dtype_code(x.dtype), _p(x), x.stride(0), _p(x8), _p(sx), M, K, stream_ptr()), "d3pm_op_quantize_mx")
     return x8, sx
 
 
-def op_layernorm_mx(x, w, b, film=None, eps=1e-6):
+def op_layernorm_mx(x, w, b, film=None, eps=1e-6, *, out=None):
     M, d = x.shape
-    y8 = torch.empty((M, d), dtype=torch.uint8, device=x.device)
-    sx = torch.empty((M, 4, d // 128), dtype=torch.uint8, device=x.device)
+    y8, sx = _mx_pair(M, d, x.device, out)
     check(lib().d3pm_op_layernorm_mx(dtype_code(x.dtype), _p(x), _p(y8), _p(sx), _p(w), _p(b), _p(film), M, d, eps,
                                      stream_ptr()), "d3pm_op_layernorm_mx")
     return y8, sx
 
 
-def op_linear_mx(x8, sx, w8, sw, bias, out_dtype, *, act=0, r1=None, row_mask=None, mask_period=1, mx_out=False):
-    """16-bit result [M, N], or with mx_out=True the result as (codes [M, N], scales [M, 4, N // 128])."""
+def op_layernorm_mx_pair(x, w, b, w2, b2, film=None, eps=1e-6, *, out=None, out2=None):
+    """Two LayerNorms of the same rows in one launch (the sampler's norm2 | norm22): ((codes, scales), (codes_2, scales_2));
+    FiLM applies to the first."""
+    M, d = x.shape
+    y8, sx = _mx_pair(M, d, x.device, out)
+    y8_2, sx_2 = _mx_pair(M, d, x.device, out2)
+    check(lib().d3pm_op_layernorm_mx_pair(dtype_code(x.dtype), _p(x), _p(y8), _p(sx), _p(w), _p(b), _p(film), _p(w2), _p(b2), _p(y8_2),
+                                          _p(sx_2), M, d, eps, stream_ptr()), "d3pm_op_layernorm_mx_pair")
+    return (y8, sx), (y8_2, sx_2)
+
+
+def op_linear_mx(x8, sx, w8, sw, bias, out_dtype, *, act=0, r1=None, row_mask=None, mask_period=1, mx_out=False, out=None, ldy=None,
+                 out8=None, out_scales=None):
+    """16-bit result [M, N], or with mx_out=True the result as (codes [M, N], scales [M, 4, N // 128]).  out / ldy: the 16-bit
+    result goes to `out` with row stride ldy; out8 / out_scales: the MX result goes there (either one implies mx_out; the library
+    refuses one without the other)."""
     M, K = x8.shape
     N = w8.shape[0]
+    mx_out = mx_out or out8 is not None or out_scales is not None
     if mx_out:
-        y8 = torch.empty((M, N), dtype=torch.uint8, device=x8.device)
-        sy = torch.empty((M, 4, N // 128), dtype=torch.uint8, device=x8.device)
-        y = None
+        given = out8 is not None or out_scales is not None
+        y8 = out8 if given else torch.empty((M, N), dtype=torch.uint8, device=x8.device)
+        sy = out_scales if given else torch.empty((M, 4, N // 128), dtype=torch.uint8, device=x8.device)
+        y = out
+        ldy = N if ldy is None else ldy
     else:
         y8 = sy = None
-        y = torch.empty((M, N), dtype=out_dtype, device=x8.device)
-    check(lib().d3pm_op_linear_mx(dtype_code(out_dtype), _p(x8), x8.stride(0), _p(sx), _p(w8), _p(sw), _p(bias), _p(y), N, _p(r1),
+        ldy = N if ldy is None else ldy
+        y = torch.empty((M, ldy), dtype=out_dtype, device=x8.device) if out is None else out
+    check(lib().d3pm_op_linear_mx(dtype_code(out_dtype), _p(x8), x8.stride(0), _p(sx), _p(w8), _p(sw), _p(bias), _p(y), ldy, _p(r1),
                                   0 if r1 is None else r1.stride(0), _p(row_mask), mask_period, _p(y8), _p(sy), M, N, K, act,
                                   C.byref(TUNING), stream_ptr()), "d3pm_op_linear_mx")
-    return (y8, sy) if mx_out else y
+    return (y8, sy) if mx_out else y[:, :N]
 
 
 def op_attention(q, k, v, n_heads, scale, *, family=0, key_len=None):
